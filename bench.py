@@ -28,6 +28,10 @@ launch time, so `frac` <= 1 is HBM utilisation.  In the lazy matrix-memory mode 
 SURVEY 8d's materialised read+write figure; the 8d-equivalent rate is reported apart as `effective_8d_GBps`.
 `traffic` = HBM bytes per launch from a separate rocprofv3 --pmc pass (profiles/, `traffic_source`), never measured
 in this process.  `cpu_baseline`: the CPU oracle timed on the host cores on a bounded sample (rank 0, N = 1 only).
+
+`--dump-outputs DIR`: right after the timed region, rank 0 writes what the last timed step handed its caller -- the actions
+[global batch, act_dim] and their token ids -- to DIR/actions.npy and DIR/tokens.npy.  Every input is seeded, so two builds
+run with the same arguments can be compared file for file.
 """
 import argparse
 import json
@@ -437,7 +441,37 @@ def parse_args(argv=None):
     ap.add_argument("--engine-factory", default="",
                     help="test hook: 'file.py:attr' or 'module:attr' of a stand-in engine factory(spec, batch, device); the "
                          "run then stays on the CPU over gloo (tests/test_dist_rollout.py).  Never used on the product path")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(actions, tokens; see dump_outputs), so that two builds can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy, floating point as float32, integers as float64 (token ids stay
+    exact).  All arrays share their first (env slot) axis.  Above DUMP_LIMIT_BYTES in all, every array keeps the same fixed
+    sample of rows (seed 0, ascending) and out_dir/rows.npy holds their indices; the files never exceed the limit."""
+    import numpy as np
+    host = {k: v.detach().cpu() for k, v in arrays.items() if v is not None}
+    host = {k: v.to(torch.float32 if v.is_floating_point() else torch.float64) for k, v in host.items()}
+    n = next(iter(host.values())).shape[0]
+    row_bytes = sum(v[0].numel() * v.element_size() for v in host.values())
+    rows = None
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (row_bytes + 8)          # (+ 8: the row's index in rows.npy)
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        host = {k: v[rows] for k, v in host.items()}
+        host["rows"] = rows.to(torch.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v.numpy())
+    log(f"[bench] wrote {', '.join(sorted(host))} to {out_dir}")
 
 
 def _resolve_factory(ref):
@@ -627,6 +661,7 @@ def main(argv=None, engine_factory=None, device=None):
         emb = torch.empty(B, spec.d_model, device=dev)
 
     clock = [0]  # global timestep: the episode schedule (resets, returns-to-go) runs on without repeating step 0
+    last_tokens = [None]  # the token ids the latest step wrote beside its actions (--dump-outputs)
 
     def next_t():
         t = clock[0] if clock[0] < steps_total else 1 + (clock[0] - 1) % (steps_total - 1)
@@ -637,11 +672,12 @@ def main(argv=None, engine_factory=None, device=None):
         t = next_t()
         if img_ring is not None and TWO_CALL_IMAGES:
             eng.embed_images(img_ring[t % n_ring], emb)
-            a, _ = eng.step(emb, rtgs[t], reward_tok, masks[t], discrete=True, obs_is_embedding=True)
+            a, tok = eng.step(emb, rtgs[t], reward_tok, masks[t], discrete=True, obs_is_embedding=True)
         elif img_ring is not None:
-            a, _ = eng.step_images(img_ring[t % n_ring], rtgs[t], reward_tok, masks[t], discrete=True)
+            a, tok = eng.step_images(img_ring[t % n_ring], rtgs[t], reward_tok, masks[t], discrete=True)
         else:
-            a, _ = eng.step(obs_ring[t % n_ring], rtgs[t], reward_tok, masks[t])
+            a, tok = eng.step(obs_ring[t % n_ring], rtgs[t], reward_tok, masks[t])
+        last_tokens[0] = tok
         if dist_on:
             a = ldist.all_gather_actions(a, args.global_batch if args.global_batch > 0 else None)
         return a
@@ -677,6 +713,13 @@ def main(argv=None, engine_factory=None, device=None):
         kern_ms, kern_n, fold_ms, fold_n = eng.profile_end_split()
     else:
         kern_ms, kern_n, fold_ms, fold_n = 0.0, 0, 0.0, 0
+    if args.dump_outputs:
+        # now, before any later step overwrites the engine's output buffers; the tokens are gathered like the actions
+        tokens = last_tokens[0]
+        if dist_on and tokens is not None:
+            tokens = ldist.all_gather_actions(tokens, args.global_batch if args.global_batch > 0 else None)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"actions": last, "tokens": tokens})
     value = global_batch * K / wall
     ranks_seen = ldist.count_ranks(dev)
 

@@ -1,6 +1,8 @@
 """Stand-in for lram_amd.engine.Engine inside bench.main on CPU (test infrastructure; bench.py --engine-factory)."""
 import os
 
+import torch
+
 
 class StubEngine:
     """Stands in for lram_amd.engine.Engine inside bench.main on CPU: actions are a fixed function of the inputs, so
@@ -20,7 +22,7 @@ class StubEngine:
     def step(self, obs, rtg, reward, reset_mask=None, **kw):
         self.steps += 1
         a = obs[:, :self.spec.act_dim] * 0.5 + rtg.view(-1, 1) + reset_mask.float().view(-1, 1)
-        return a, None
+        return a, (a * 64).round().to(torch.int32)
 
 
 def factory(spec, batch, device):

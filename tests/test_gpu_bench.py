@@ -45,6 +45,31 @@ def test_bench_line_contract_and_physical_roofline(hip_lib, capsys):
     capsys.readouterr()
 
 
+def test_bench_dump_outputs_repeat_exactly(hip_lib, tmp_path, capsys):
+    """--dump-outputs on the engine: the last timed step's actions and token ids, the same bits from run to run (seeded
+    inputs, deterministic kernels), the actions being the de-tokenised tokens of that step."""
+    import numpy as np
+    import torch
+    import bench
+    from lram_amd import preset
+    from oracle.dt_ref import minmax_inv_tokenize
+    argv = ["--config", "xlstm_16m", "--batch", "512", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
+            "--no-stream-ceilings", "--host-io-steps", "0", "--no-kernel-timing"]
+    runs = []
+    for i in range(2):
+        bench.main(argv + ["--dump-outputs", str(tmp_path / str(i))])
+        runs.append({n: np.load(str(tmp_path / str(i) / (n + ".npy"))) for n in ("actions", "tokens")})
+    spec = preset("xlstm_16m")
+    a, tok = runs[0]["actions"], runs[0]["tokens"]
+    assert a.dtype == np.float32 and a.shape == (512, spec.act_dim) and tok.dtype == np.float64 and tok.shape == a.shape
+    assert np.array_equal(tok, np.round(tok)) and tok.min() >= 0 and tok.max() < spec.n_vocab
+    want = minmax_inv_tokenize(torch.from_numpy(tok).long(), spec.action_channels, spec.n_discrete).numpy()
+    assert np.abs(a - want).max() <= 1e-6
+    for n in runs[0]:
+        assert np.array_equal(runs[0][n], runs[1][n]), n
+    capsys.readouterr()
+
+
 def test_bench_config_legs_contract(hip_lib, capsys):
     """`configs` on the default bench line: BASELINE.json's configurations 2-5 at their per-GPU sizes, each timed on a fresh
     engine with its own roofline / matrix-core block (bench.config_legs).  Here: the contract of every leg, fractions physical,
