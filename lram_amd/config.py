@@ -369,6 +369,21 @@ def preset(name: str) -> ModelSpec:
         "mamba_48m": dict(backbone="mamba", kind="MDDMamba", d_model=768, n_blocks=12),
         # C4/C5: xLSTM[7:1] 206M = xlstm_huge.yaml + slstm_at=[1,3,5] (reference README.md:234)
         "xlstm_206m": dict(backbone="xlstm", kind="MDDXLSTM", d_model=1280, n_blocks=20, slstm_at=[1, 3, 5]),
+        # the other published sizes (reference README.md:186-240)
+        # xLSTM[7:1] 48M = xlstm_mediumplus.yaml + slstm_at=[1,3] (reference README.md:204)
+        "xlstm_48m": dict(backbone="xlstm", kind="MDDXLSTM", d_model=768, n_blocks=12, slstm_at=[1, 3]),
+        # xLSTM[1:0] 48M = xlstm_mediumplus.yaml (reference README.md:201)
+        "xlstm_48m_mlstm": dict(backbone="xlstm", kind="MDDXLSTM", d_model=768, n_blocks=12, slstm_at=[]),
+        # xLSTM[7:1] 110M = xlstm_large.yaml + slstm_at=[1,3] (reference README.md:219)
+        "xlstm_110m": dict(backbone="xlstm", kind="MDDXLSTM", d_model=1024, n_blocks=16, slstm_at=[1, 3]),
+        # xLSTM[1:0] 110M = xlstm_large.yaml (reference README.md:216)
+        "xlstm_110m_mlstm": dict(backbone="xlstm", kind="MDDXLSTM", d_model=1024, n_blocks=16, slstm_at=[]),
+        # Mamba 16M = mamba_medium.yaml (reference README.md:195)
+        "mamba_16m": dict(backbone="mamba", kind="MDDMamba", d_model=512, n_blocks=8),
+        # Mamba 110M = mamba_large.yaml (reference README.md:225)
+        "mamba_110m": dict(backbone="mamba", kind="MDDMamba", d_model=1024, n_blocks=16),
+        # Mamba 206M = mamba_huge.yaml (reference README.md:240)
+        "mamba_206m": dict(backbone="mamba", kind="MDDMamba", d_model=1280, n_blocks=20),
         # small shapes for tests
         "xlstm_tiny": dict(backbone="xlstm", kind="MDDXLSTM", d_model=128, n_blocks=3, slstm_at=[1], state_dim=20,
                            act_dim=4),

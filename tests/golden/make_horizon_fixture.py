@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/horizon_{xlstm16m,mamba48m}[_fp64].npz: the step path at the reference's real episode length.
+"""Generate tests/golden/horizon_<case>[_<scheme>][_fp64].npz: the step path at the reference's real episode length.
 
-    python tests/golden/make_horizon_fixture.py [--fp64] [--model xlstm|mamba|xlstm206m] [--scheme exercise|reference|trained_like]
+    python tests/golden/make_horizon_fixture.py [--fp64] [--model xlstm|mamba|xlstm206m|xlstm110m|mamba206m]
+                                                [--scheme exercise|reference|trained_like]
                                                                                     (about 5 + 10 minutes on 8 cores)
 
 The reference loop runs an episode to `done` (src/callbacks/evaluation.py:130-177: DMControl episodes are 1000 steps,
@@ -14,13 +15,17 @@ OraclePolicy.step -- for
          evaluation.py:165 does), 1000 env-steps without a reset, a reset of envs 0..3 at the 1001st, 60 more;
   mamba  Mamba 48M, 8 envs, Meta-World-shaped inputs (39 native dims), 200 env-steps, reset of envs 0..3, 20 more;
   xlstm206m  xLSTM[7:1] 206M (20 blocks, head dim 640), 4 envs, 200 env-steps, reset of envs 0..1, 20 more,
+  xlstm110m  xLSTM[7:1] 110M (16 blocks, head dim 512), 4 envs, as xlstm206m (fixtures for exercise and trained_like),
+  mamba206m  Mamba 206M (20 layers, dt_rank 80), 8 envs, as mamba (fixtures for exercise and trained_like),
 
 far too slow to repeat inside the GPU test run, so the outputs are committed as fixtures: inputs are regenerated from
 the seed by `horizon_inputs`, weights by init_state_dict(seed) (checksum stored and asserted); expected values =
 actions / logits / hidden at the listed steps, the recurrent state at the end of the long episode and at the end of
 the run (n, m, conv in full; the matrix memory C through its products with a fixed probe vector), and the range the
-stabiliser m covered.  `--fp64` evaluates the same trajectory in float64 (tests/helpers.py::Fp64Oracle): the reference
-point of the conditioning-aware comparison.  tests/test_gpu_horizon.py drives lram_step over the same inputs."""
+stabiliser m covered.  The cases marked `compact` store hidden states, logits and state tensors through `fold` (64 products
+per env with a fixed probe matrix) and the top two logits per action dim, which keeps their files small.  `--fp64`
+evaluates the same trajectory in float64 (tests/helpers.py::Fp64Oracle): the reference point of the conditioning-aware
+comparison.  tests/test_gpu_horizon.py drives lram_step over the same inputs."""
 import os
 import sys
 import time
@@ -43,6 +48,14 @@ CASES = {
     # 16M case touches) over a Meta-World-length episode; 4 envs (the oracle takes ~1 s per step at this size)
     "xlstm206m": dict(preset="xlstm_206m", native=39, episode=200, tail=20, rtg0=6.50346, drtg=0.02, envs=4,
                       marks=(1, 10, 50, 100, 150, 200, 201, 220), blocks=(0, 19), slstm=3, file="horizon_xlstm206m"),
+    # xLSTM[7:1] 110M (head dim 512: the read pass's 64-column instance; sLSTM head dim 256), Meta-World-length episode, 4 envs
+    "xlstm110m": dict(preset="xlstm_110m", native=39, episode=200, tail=20, rtg0=6.50346, drtg=0.02, envs=4,
+                      marks=(1, 10, 50, 100, 150, 200, 201, 220), blocks=(0, 15), slstm=1, file="horizon_xlstm110m",
+                      compact=True),
+    # Mamba 206M (dt_rank 80: the generic state-update kernel; x_proj N = 112 on the tile GEMM path)
+    "mamba206m": dict(preset="mamba_206m", native=39, episode=200, tail=20, rtg0=6.50346, drtg=0.02,
+                      marks=(1, 10, 50, 100, 150, 200, 201, 220), blocks=(0, 19), slstm=None, file="horizon_mamba206m",
+                      compact=True),
 }
 
 
@@ -83,6 +96,30 @@ def probe(dh):
     return torch.linspace(-1.0, 1.0, dh).cos()
 
 
+FOLD_COLS = 64
+
+
+def probe_matrix(n, k=FOLD_COLS):
+    """[n, k] float64, closed form (no RNG): columns of pseudo-random phase, every entry O(1 / sqrt(n))."""
+    i = torch.arange(1, n + 1, dtype=torch.float64).unsqueeze(1)
+    j = torch.arange(1, k + 1, dtype=torch.float64).unsqueeze(0)
+    return torch.cos(0.7 * i * j + 0.3 * j) / n ** 0.5
+
+
+def fold(x):
+    """Compact cases: a tensor [a, ...] as its products with probe_matrix over everything behind the first axis -> [a, 64]
+    float32 (the first axis is the env axis, or the sLSTM state's plane axis).  The GPU test folds the engine's tensor the same
+    way; a wrong entry anywhere moves every one of the 64 products."""
+    x = torch.as_tensor(x).detach().cpu().double()
+    x = x.reshape(x.shape[0], -1)
+    return (x @ probe_matrix(x.shape[1])).float().numpy()
+
+
+def put(out, c, key, x):
+    """Store x under key: in full, or folded for the compact cases (whose full tensors would make fixtures of megabytes)."""
+    out[key] = fold(x) if c.get("compact") else torch.as_tensor(x).numpy().copy()
+
+
 def weight_checksum(sd):
     return float(sum(v.double().abs().sum() for v in sd.values()))
 
@@ -92,17 +129,18 @@ def store_state(out, tag, ora, c, fp64):
         if c["preset"].startswith("xlstm"):
             cm, n, m = ora.state[f"block_{i}"]["mlstm_state"]
             r = probe(cm.shape[-1]).to(cm.dtype)
-            out[f"{tag}_b{i}_n"], out[f"{tag}_b{i}_m"] = n.numpy().copy(), m.numpy().copy()
-            out[f"{tag}_b{i}_conv"] = ora.state[f"block_{i}"]["conv_state"][0].numpy().copy()
-            out[f"{tag}_b{i}_Cr"] = (cm @ r).numpy()
-            out[f"{tag}_b{i}_rC"] = (r @ cm).numpy()
+            put(out, c, f"{tag}_b{i}_n", n)
+            out[f"{tag}_b{i}_m"] = m.numpy().copy()
+            put(out, c, f"{tag}_b{i}_conv", ora.state[f"block_{i}"]["conv_state"][0])
+            put(out, c, f"{tag}_b{i}_Cr", cm @ r)
+            put(out, c, f"{tag}_b{i}_rC", r @ cm)
             out[f"{tag}_b{i}_Cabsmax"] = cm.abs().amax(dim=(-1, -2)).numpy()
         else:
             conv, ssm = ora.state[i]
-            out[f"{tag}_l{i}_conv"] = conv.numpy().copy()
-            out[f"{tag}_l{i}_ssm"] = ssm[list(SSM_ENVS)].numpy().copy()   # (0.8 MB per layer and tag for all eight)
+            put(out, c, f"{tag}_l{i}_conv", conv)
+            put(out, c, f"{tag}_l{i}_ssm", ssm[list(SSM_ENVS)])   # (0.8 MB per layer and tag for all eight, in full)
     if c["slstm"] is not None:
-        out[f"{tag}_b{c['slstm']}_slstm"] = ora.state[f"block_{c['slstm']}"]["slstm_state"].numpy().copy()
+        put(out, c, f"{tag}_b{c['slstm']}_slstm", ora.state[f"block_{c['slstm']}"]["slstm_state"])
 
 
 def main(case, fp64=False, scheme="exercise"):
@@ -129,8 +167,10 @@ def main(case, fp64=False, scheme="exercise"):
         act, dbg = step(obs[t], rtg[t], zero, mask[t] if mask[t].any() else None, return_debug=True)
         if t + 1 in c["marks"]:
             out[f"actions_{t + 1}"] = act.numpy()
-            out[f"logits_{t + 1}"] = dbg["logits"].numpy()
-            out[f"hidden_{t + 1}"] = dbg["hidden"].numpy()
+            put(out, c, f"logits_{t + 1}", dbg["logits"])
+            put(out, c, f"hidden_{t + 1}", dbg["hidden"])
+            if c.get("compact"):   # the two largest logits per action dim: all the tie rule needs
+                out[f"top2_{t + 1}"] = dbg["logits"].reshape(act.shape[0], act.shape[1], -1).topk(2, dim=-1).values.float().numpy()
         if c["preset"].startswith("xlstm"):
             for i in c["blocks"]:
                 m = ora.state[f"block_{i}"]["mlstm_state"][2]

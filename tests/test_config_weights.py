@@ -185,6 +185,28 @@ def test_every_reference_preset_resolves_and_engine_limits_are_stated():
         assert engine_limits(spec_from_agent_params(presets[name])) == []
 
 
+def test_published_model_presets_are_the_reference_configurations():
+    """The presets of the published sizes (reference README.md:186-240) are the reference's huggingface presets with slstm_at set
+    as the README's command lines set it ([7:1]: `+agent_params.huggingface.xlstm_config.slstm_at='[1,3]'`; [1:0]: none), and
+    the engine runs every one of them."""
+    from lram_amd.config import engine_limits, spec_from_agent_params
+    presets = _ref_vectors()["reference_presets"]
+    published = {"xlstm_48m": ("xlstm_mediumplus", [1, 3]), "xlstm_48m_mlstm": ("xlstm_mediumplus", []),
+                 "xlstm_110m": ("xlstm_large", [1, 3]), "xlstm_110m_mlstm": ("xlstm_large", []),
+                 "mamba_16m": ("mamba_medium", None), "mamba_110m": ("mamba_large", None), "mamba_206m": ("mamba_huge", None)}
+    for name, (yaml_name, slstm_at) in published.items():
+        want = spec_from_agent_params(presets[yaml_name])
+        if slstm_at is not None:
+            want = dataclasses.replace(want, slstm_at=slstm_at)
+        assert preset(name) == want, name
+        assert engine_limits(preset(name)) == [], name
+    geo = {n: preset(n) for n in published}
+    assert (geo["xlstm_48m"].head_dim, geo["xlstm_48m"].d_model // geo["xlstm_48m"].n_heads, geo["xlstm_48m"].n_blocks) == (384, 192, 12)
+    assert (geo["xlstm_110m"].head_dim, geo["xlstm_110m"].d_model // geo["xlstm_110m"].n_heads, geo["xlstm_110m"].n_blocks) == (512, 256, 16)
+    assert [(geo[m].d_inner, geo[m].dt_rank, geo[m].n_blocks) for m in ("mamba_16m", "mamba_110m", "mamba_206m")] == \
+        [(1024, 32, 8), (2048, 64, 16), (2560, 80, 20)]
+
+
 def test_sb3_zip_roundtrip_and_prefix_strip(tmp_path):
     import zipfile
     spec = preset("mamba_tiny")
