@@ -203,7 +203,16 @@ __global__ __launch_bounds__(256) void embed_chunk_kernel(float* x, const float*
   *reinterpret_cast<float4*>(row + 2 * D) = make_float4(r * wr.x + br.x, r * wr.y + br.y, r * wr.z + br.z, r * wr.w + br.w);
 }
 
-// One wave per (env, action dim): first index of the maximum (torch.argmax tie rule), then
+// torch.argmax order of (value, index) candidates: NaN is the maximum, the first index wins among equal values (NaNs
+// included), +-Inf compare as ordinary values.  Starting from (-inf, INT_MAX) every element of a non-empty row is taken
+// or loses to one that was, so the winner is always a real index.
+__device__ __forceinline__ bool argmax_beats(float v, int i, float best, int bi) {
+  const bool v_nan = v != v, best_nan = best != best;
+  if (v_nan) return !best_nan || i < bi;
+  return !best_nan && (v > best || (v == best && i < bi));
+}
+
+// One wave per (env, action dim): first index of the maximum (torch.argmax rule, argmax_beats), then
 // inv_tokenize: max(tok - shift, 0) * ((max - min) / channels) + min.
 __global__ __launch_bounds__(256) void action_argmax_kernel(const float* logits, float* actions, int32_t* tokens,
                                                             int B, int act_dim, int n_vocab, int n_discrete,
@@ -222,7 +231,7 @@ __global__ __launch_bounds__(256) void action_argmax_kernel(const float* logits,
   int bi = 0x7fffffff;
   for (int i = lane; i < n; i += 64) {
     const float v = lg[i];
-    if (v > best || (v == best && i < bi)) {
+    if (argmax_beats(v, i, best, bi)) {
       best = v;
       bi = i;
     }
@@ -231,7 +240,7 @@ __global__ __launch_bounds__(256) void action_argmax_kernel(const float* logits,
   for (int off = 32; off > 0; off >>= 1) {
     const float ov = __shfl_xor(best, off, 64);
     const int oi = __shfl_xor(bi, off, 64);
-    if (ov > best || (ov == best && oi < bi)) {
+    if (argmax_beats(ov, oi, best, bi)) {
       best = ov;
       bi = oi;
     }

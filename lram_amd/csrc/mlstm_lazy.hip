@@ -484,8 +484,10 @@ __global__ __launch_bounds__(256) void mlstm_lazy_cell_kernel(MlstmLazyArgs a) {
   const int64_t base = ((int64_t)b * NH + h) * W;
   if (tid < W) s_coef[tid] = tid < n ? coef_raw : 0.f;
   if (KPL < 0) {  // scores and bookkeeping come from mlstm_lazy_score_kernel
+    // (the score kernel writes each row's first n + T entries only: the rest is an earlier step's, possibly another episode's
+    // NaN, which the zero v rows beyond the window would turn into NaN * 0)
     const float* pwi = a.pw + (((int64_t)b * NH + h) * T) * WT;
-    for (int idx = tid; idx < T * WT; idx += 256) pw[idx] = pwi[idx];
+    for (int idx = tid; idx < T * WT; idx += 256) pw[idx] = idx % WT < n + T ? pwi[idx] : 0.f;
   } else {
     for (int idx = tid; idx < T * WT; idx += 256) pw[idx] = 0.f;
   }

@@ -66,7 +66,7 @@ def embed_tokens(spec, sd, obs, rtg, reward, state_mean=None, state_std=None):
     """obs: (B, state_dim) float32 already zero-padded to max_state_dim (decision_xlstm.py:16-19), or
     uint8 (B,3,64,64); rtg, reward: (B,).  Returns embed_ln(stack(s, rtg, r)) of shape (B, 3, D)."""
     if obs.dim() == 4:
-        s = impala_cnn(sd, "embed_image.", obs.float() / 255.0)
+        s = impala_cnn(sd, "embed_image.", obs.to(sd["embed_return.weight"].dtype) / 255.0)
     else:
         if state_mean is not None:
             obs = (obs - state_mean) / state_std  # decision_transformer_sb3.py:650-651

@@ -58,8 +58,11 @@ def zero_state(spec, B):
 
 
 def reset_state_rows(state, mask):
-    keep = (~mask).to(torch.float32).view(-1, 1, 1)
-    return {i: (c * keep, s * keep) for i, (c, s) in state.items()}
+    """Zero the conv / ssm state of every env whose mask entry is True: a select, not a multiply by 0, so a NaN / Inf
+    row of a diverged env is reset too."""
+    sel = mask.view(-1, 1, 1)
+    return {i: (torch.where(sel, torch.zeros_like(c), c), torch.where(sel, torch.zeros_like(s), s))
+            for i, (c, s) in state.items()}
 
 
 def encoder_forward_cached(spec, sd, inputs_embeds, state=None, prefix="encoder."):

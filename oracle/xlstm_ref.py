@@ -352,16 +352,19 @@ def zero_state(spec, B):
 
 def reset_state_rows(state, mask):
     """Zero the recurrent state of every env whose mask entry is True (what the rollout loop does by
-    setting `model.past_key_values = None` for its single env, src/callbacks/evaluation.py:238-251)."""
-    keep = (~mask).to(torch.float32)
+    setting `model.past_key_values = None` for its single env, src/callbacks/evaluation.py:238-251).
+    A select, not a multiply by 0: a NaN / Inf row (a diverged env, or the stabiliser m = -inf) is reset too."""
+    def zero(t, view):
+        return torch.where(mask.view(view), torch.zeros_like(t), t)
+
     out = {}
     for name, blk in state.items():
         nb = {}
         if "mlstm_state" in blk:
             c, n, m = blk["mlstm_state"]
-            nb["mlstm_state"] = (c * keep.view(-1, 1, 1, 1), n * keep.view(-1, 1, 1, 1), m * keep.view(-1, 1, 1, 1))
+            nb["mlstm_state"] = (zero(c, (-1, 1, 1, 1)), zero(n, (-1, 1, 1, 1)), zero(m, (-1, 1, 1, 1)))
         if "slstm_state" in blk:
-            nb["slstm_state"] = blk["slstm_state"] * keep.view(1, -1, 1)
-        nb["conv_state"] = (blk["conv_state"][0] * keep.view(-1, 1, 1),)
+            nb["slstm_state"] = zero(blk["slstm_state"], (1, -1, 1))
+        nb["conv_state"] = (zero(blk["conv_state"][0], (-1, 1, 1)),)
         out[name] = nb
     return out
