@@ -121,3 +121,50 @@ def assert_close_or_as_close_as_fp32_oracle(got, ref32, ref64, tol=2e-4, factor=
                             f"{float(err_engine.max() / scale):.2e}, fp32 oracle vs fp64 {float(err_oracle.max() / scale):.2e} "
                             f"(cap {cap:.0e})")
     return float((err_engine / (err_oracle + 1e-30))[~strict].max()) if bool((~strict).any()) else 0.0
+
+
+# Per-element bar on C / n of an mLSTM block after a trajectory: |err| / (|ref| + 1e-3 max|ref|); measured worst 8.9e-4 (16M, B = 12)
+ELEM_STATE_TOL = 5e-3
+
+
+def sampled_state(eng, spec, sample):
+    """export(block, which) of the engine's state at the env slots `sample` (the sLSTM state is [4, B, D]: slots on axis 1)."""
+    idx = torch.as_tensor(sample, device=eng.device)
+
+    def export(i, w):
+        t = eng.export_state_tensor(i, w)
+        return t[:, idx] if (spec.backbone == "xlstm" and i in spec.slstm_at and w == 0) else t[idx]
+    return export
+
+
+def state_vs_oracle(export, ora_state, spec, what, tol=2e-4, rows=None):
+    """Every state tensor of the sampled envs (export(block, which), see sampled_state) against the oracle's state
+    (OraclePolicy.state over the same envs): rel_err < tol, and C / n of every mLSTM block per element within ELEM_STATE_TOL.
+    `rows`: the env slot of each sampled env, named in the message with the env that is furthest off."""
+    def check(ok, got, want, name, env_axis=0):
+        if ok:
+            return
+        msg = f"{what}: {name}"
+        if rows is not None:
+            d = (_as_double(got) - _as_double(want)).abs().transpose(0, env_axis)
+            msg += f" (furthest off: row {rows[int(d.reshape(d.shape[0], -1).amax(1).argmax())]})"
+        raise AssertionError(msg)
+
+    for i in range(spec.n_blocks):
+        if spec.backbone == "mamba":
+            for w, j, name in ((3, 0, "conv"), (0, 1, "ssm")):
+                got, want = export(i, w), ora_state[i][j]
+                check(rel_err(got, want) < tol, got, want, f"layer {i} {name}")
+        elif i in spec.slstm_at:
+            got, want = export(i, 0), ora_state[f"block_{i}"]["slstm_state"]
+            check(rel_err(got, want) < tol, got, want, f"block {i} sLSTM", env_axis=1)
+        else:
+            ref = ora_state[f"block_{i}"]["mlstm_state"]
+            for w in range(3):
+                got = export(i, w)
+                check(rel_err(got, ref[w]) < tol, got, ref[w], f"block {i} state {w}")
+                if w < 2:
+                    check(elem_rel_err(got, ref[w]) < ELEM_STATE_TOL, got, ref[w], f"block {i} state {w} per element")
+        if spec.backbone == "xlstm":
+            got, want = export(i, 3), ora_state[f"block_{i}"]["conv_state"][0]
+            check(rel_err(got, want) < tol, got, want, f"block {i} conv")

@@ -28,9 +28,9 @@ import torch
 
 from lram_amd import init_state_dict, preset
 from oracle.dt_ref import OraclePolicy
-from tests.helpers import (Fp64Oracle, assert_actions_match, assert_close_or_as_close_as_fp32_oracle, elem_rel_err,
-                           make_inputs, rel_err, relaxed_rows_fraction, relaxed_rows_reset)
-from tests.test_gpu_parity import ELEM_STATE_TOL
+from tests.helpers import (ELEM_STATE_TOL, Fp64Oracle, assert_actions_match, assert_close_or_as_close_as_fp32_oracle,
+                           elem_rel_err, make_inputs, rel_err, relaxed_rows_fraction, relaxed_rows_reset, sampled_state,
+                           state_vs_oracle)
 
 pytestmark = pytest.mark.gpu
 
@@ -261,24 +261,6 @@ def _seq_tensors(seq, L):
     return [torch.stack([x[k] for x in seq[:L]], 1).contiguous().cuda() for k in range(3)]
 
 
-def _state_vs_oracle(eng, ora, spec, sample, what, tol=2e-4):
-    idx = torch.as_tensor(sample, device="cuda")
-    for i in range(spec.n_blocks):
-        if spec.backbone == "mamba":
-            assert rel_err(eng.export_state_tensor(i, 3)[idx], ora.state[i][0]) < tol, f"{what}: layer {i} conv"
-            assert rel_err(eng.export_state_tensor(i, 0)[idx], ora.state[i][1]) < tol, f"{what}: layer {i} ssm"
-        elif i in spec.slstm_at:
-            assert rel_err(eng.export_state_tensor(i, 0)[:, idx], ora.state[f"block_{i}"]["slstm_state"]) < tol, f"{what}: block {i} sLSTM"
-        else:
-            want = ora.state[f"block_{i}"]["mlstm_state"]
-            for w in range(3):
-                got = eng.export_state_tensor(i, w)[idx]
-                assert rel_err(got, want[w]) < tol, f"{what}: block {i} state {w}"
-                if w < 2:
-                    assert elem_rel_err(got, want[w]) < ELEM_STATE_TOL, f"{what}: block {i} state {w} per element"
-            assert rel_err(eng.export_state_tensor(i, 3)[idx], ora.state[f"block_{i}"]["conv_state"][0]) < tol, f"{what}: block {i} conv"
-
-
 def _all_states_equal(a, b, spec, what):
     for blk in range(spec.n_blocks):
         kinds = (0, 3) if (spec.backbone == "mamba" or blk in spec.slstm_at) else (0, 1, 2, 3)
@@ -332,10 +314,10 @@ def test_xlstm_stored_context_then_lazy_decode(hip_lib, monkeypatch, name, schem
         a_ref, dbg = ora.step(obs[sample], rtg[sample], rew[sample], mask[sample], return_debug=True)
         if t + 1 == L_4K1:
             ties += assert_actions_match(a_t[sample], a_ref, dbg["logits"], spec, what=f"{name} prefill L={L_4K1}")
-            _state_vs_oracle(engines["0"], ora, spec, SAMPLE, f"{name} prefill L={L_4K1}")
+            state_vs_oracle(sampled_state(engines["0"], spec, SAMPLE), ora.state, spec, f"{name} prefill L={L_4K1}")
         elif t + 1 == L_UNEVEN:
             ties += assert_actions_match(a_l[sample], a_ref, dbg["logits"], spec, what=f"{name} prefill L={L_UNEVEN}")
-            _state_vs_oracle(lanes, ora, spec, SAMPLE, f"{name} prefill L={L_UNEVEN}")
+            state_vs_oracle(sampled_state(lanes, spec, SAMPLE), ora.state, spec, f"{name} prefill L={L_UNEVEN}")
         elif t + 1 > L_UNEVEN:   # lazy decoding from the state the prefill left
             a, _ = lanes.step(obs.cuda(), rtg.cuda(), rew.cuda(), None)
             torch.cuda.synchronize()
@@ -343,7 +325,7 @@ def test_xlstm_stored_context_then_lazy_decode(hip_lib, monkeypatch, name, schem
             _, hidden, _ = lanes.taps()
             assert rel_err(hidden[sample.cuda()], dbg["hidden"]) < 2e-4, f"{name} decode step {t}: hidden"
             ties += assert_actions_match(a[sample.cuda()], a_ref, dbg["logits"], spec, what=f"{name} decode step {t}")
-    _state_vs_oracle(lanes, ora, spec, SAMPLE, f"{name} after {DECODE} lazy steps")
+    state_vs_oracle(sampled_state(lanes, spec, SAMPLE), ora.state, spec, f"{name} after {DECODE} lazy steps")
     assert ties == 0, ties
     for e in engines.values():
         e.close()
@@ -379,6 +361,6 @@ def test_mamba_stored_context_through_the_chunk_lanes(hip_lib, monkeypatch, name
     for obs, rtg, rew, mask in seq:
         a_ref, dbg = ora.step(obs[sample], rtg[sample], rew[sample], mask[sample], return_debug=True)
     assert assert_actions_match(a_l[sample.cuda()], a_ref, dbg["logits"], spec, what=f"{name} prefill") == 0
-    _state_vs_oracle(lanes, ora, spec, SAMPLE, f"{name} prefill")
+    state_vs_oracle(sampled_state(lanes, spec, SAMPLE), ora.state, spec, f"{name} prefill")
     for e in (lanes, serial, stepper):
         e.close()
