@@ -18,8 +18,15 @@ configuration: xLSTM[7:1] 16M, batch 4096 env slots per GPU (weak scaling).
 
 `value`: inputs (observations, returns-to-go, reset masks for every step) are resident in HBM before the timed region
 starts; K steps are enqueued back to back between barrier + synchronize on both sides; max over ranks.
-`host_io` (extra object, rank 0's GPU): SURVEY.md 8d's host-inclusive variant of the same step, measured in the same
-run -- observations / returns-to-go / masks in pinned host memory, H2D copies, lram_step, D2H of the actions, host
+
+A plain run does only what `value` needs: set up, prime and warm up, time the K steps, write `--dump-outputs`, print the
+line.  The line also carries what the timed region measures anyway (the sampled state-pass events behind `roofline`, the
+GEMM dispatch counters).  `--full` adds every measurement that takes time of its own, after the timed region: `host_io`,
+`roofline.standalone`, the STREAM-like ceilings, `configs` (BASELINE configurations 2-5), `cpu_baseline` and, where the
+steps all-gather (N > 1 or LRAM_DIST_SINGLE_RANK=1), `collective`.  `--no-cpu-baseline`, `--no-configs`,
+`--no-stream-ceilings` and `--host-io-steps 0` leave single ones out of a --full run.
+`host_io` (--full; extra object, rank 0's GPU): SURVEY.md 8d's host-inclusive variant of the same step, measured in the
+same run -- observations / returns-to-go / masks in pinned host memory, H2D copies, lram_step, D2H of the actions, host
 synchronisation EVERY step (so launch ramp and PCIe are inside the time).  It is reported beside `value`, never as it.
 
 `roofline` (dominant kernel = the mLSTM state pass, HIP-event timed on the stream it is launched on, inside the timed
@@ -27,7 +34,7 @@ region): `achieved` = the bytes that kernel's algorithm has to move per launch (
 launch time, so `frac` <= 1 is HBM utilisation.  In the lazy matrix-memory mode the algorithm moves fewer bytes than
 SURVEY 8d's materialised read+write figure; the 8d-equivalent rate is reported apart as `effective_8d_GBps`.
 `traffic` = HBM bytes per launch from a separate rocprofv3 --pmc pass (profiles/, `traffic_source`), never measured
-in this process.  `cpu_baseline`: the CPU oracle timed on the host cores on a bounded sample (rank 0, N = 1 only).
+in this process.  `cpu_baseline` (--full): the CPU oracle timed on the host cores on a bounded sample (rank 0, N = 1 only).
 
 `--dump-outputs DIR`: right after the timed region, rank 0 writes what the last timed step handed its caller -- the actions
 [global batch, act_dim] and their token ids -- to DIR/actions.npy and DIR/tokens.npy.  Every input is seeded, so two builds
@@ -428,16 +435,20 @@ def parse_args(argv=None):
                     help="Mamba: the reference agent's trajectory (one forward per action dim, layer-0-only resets; "
                          "lram_set_compat_mode) instead of one state advance per env-step")
     ap.add_argument("--env-act-dim", type=int, default=0, help="action dims the env uses (compat forwards per step)")
-    ap.add_argument("--host-io-steps", type=int, default=48, help="steps of the host-inclusive leg (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also take every measurement that needs time of its own: the host-inclusive "
+                         "leg, the state pass with the chip to itself, the STREAM-like ceilings, the `configs` legs, the CPU "
+                         "baseline and the collective report.  Without it the run times the headline and nothing else")
+    ap.add_argument("--host-io-steps", type=int, default=48, help="--full: steps of the host-inclusive leg (0 = skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (and the `configs` legs)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the `configs` legs (BASELINE configs 2-5 at their per-GPU sizes; they run on default-workload N = 1 runs "
-                         "that also take the CPU baseline, i.e. the driver's command line)")
+                    help="--full: skip the `configs` legs (BASELINE configs 2-5 at their per-GPU sizes; they run on default-workload "
+                         "N = 1 runs that also take the CPU baseline)")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--timing-every", type=int, default=4,
                     help="live HIP-event timing of the dominant kernel on every n-th step of the timed region (1 = every step)")
     ap.add_argument("--kernel-timing", action="store_true", help="keep the live state-pass timing below 256 env slots")
-    ap.add_argument("--no-stream-ceilings", action="store_true")
+    ap.add_argument("--no-stream-ceilings", action="store_true", help="--full: skip the STREAM-like ceilings")
     ap.add_argument("--engine-factory", default="",
                     help="test hook: 'file.py:attr' or 'module:attr' of a stand-in engine factory(spec, batch, device); the "
                          "run then stays on the CPU over gloo (tests/test_dist_rollout.py).  Never used on the product path")
@@ -746,7 +757,7 @@ def main(argv=None, engine_factory=None, device=None):
         from lram_amd.engine import load_library
         out["build_id"] = load_library().lram_build_id().decode()
         out["build_id_matches_sources"] = out["build_id"] == _build.source_hash()
-    if dist_on:   # (every rank takes part; rank 0 logs it and carries it on the line)
+    if dist_on and args.full:   # (every rank takes part; rank 0 logs it and carries it on the line)
         out["collective"] = ldist.collective_report(torch.zeros(B, last.shape[-1], dtype=last.dtype, device=last.device),
                                                     args.global_batch if args.global_batch > 0 else None)
         if rank == 0:
@@ -763,7 +774,7 @@ def main(argv=None, engine_factory=None, device=None):
         return out
 
     # ---- host-inclusive leg: pinned host -> H2D -> step -> D2H -> host sync, every step ------
-    if args.host_io_steps > 0 and img_ring is None:
+    if args.full and args.host_io_steps > 0 and img_ring is None:
         n_h = args.host_io_steps
         h_obs = obs_ring.cpu().pin_memory()
         t_base = clock[0]
@@ -851,7 +862,7 @@ def main(argv=None, engine_factory=None, device=None):
                             "read once, window rows, q / v / h, 1/13 of a fold's read + write of C_base) against the measured "
                             "time of one read pass plus its share of the fold launches; `effective_8d_GBps` prices SURVEY 8d's "
                             "materialised read + write of C against the same time and is not a bandwidth")
-    if timing and spec.backbone == "xlstm" and args.micro != 1:
+    if args.full and timing and spec.backbone == "xlstm" and args.micro != 1:
         # the same kernel with the chip to itself (no overlapping slice): 8 extra, untimed-for-`value` steps
         eng.set_micro_batches(1)
         one_step()
@@ -921,7 +932,7 @@ def main(argv=None, engine_factory=None, device=None):
         out["mfma"] = m
 
     # STREAM-like ceilings on this box, for context (not the roofline peak)
-    if not args.no_stream_ceilings:
+    if args.full and not args.no_stream_ceilings:
         from lram_amd.engine import stream_copy, stream_read, stream_rmw
         n_copy = 256 * 1024 * 1024
         src = torch.empty(n_copy, device=dev)
@@ -963,13 +974,14 @@ def main(argv=None, engine_factory=None, device=None):
     default_workload = (args.config == "xlstm_16m" and args.obs == "state" and args.batch == 4096 and args.global_batch == 0
                         and not args.mamba_compat and not args.graph)
     # (measurement scripts pass --no-cpu-baseline: profiler / counter / A-B runs of the headline must not drag five other engines along)
-    if rank == 0 and world == 1 and not dist_on and default_workload and not args.no_configs and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not dist_on and default_workload and not args.no_configs \
+            and not args.no_cpu_baseline:
         # BASELINE.json's other configurations, each on a fresh engine after the headline's is gone
         eng.close()
         eng = None
         torch.cuda.empty_cache()
         out["configs"] = config_legs(dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if eng is not None:
             eng.close()
         torch.cuda.empty_cache()

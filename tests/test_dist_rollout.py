@@ -131,7 +131,7 @@ def test_bench_starts_its_own_ranks_from_a_plain_process(tmp_path):
     env["OMP_NUM_THREADS"] = "1"
     factory = os.path.join(root, "tests", "stub_engine.py") + ":factory"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--config",
-           "xlstm_tiny", "--batch", "6", "--engine-factory", factory]
+           "xlstm_tiny", "--batch", "6", "--full", "--engine-factory", factory]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -166,12 +166,19 @@ def test_bench_single_rank_collectives_mode_on_gloo():
     env = dict(os.environ, LRAM_DIST_SINGLE_RANK="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(port), OMP_NUM_THREADS="1")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "xlstm_tiny",
-           "--batch", "6", "--engine-factory", os.path.join(root, "tests", "stub_engine.py") + ":factory"]
+           "--batch", "6", "--full", "--engine-factory", os.path.join(root, "tests", "stub_engine.py") + ":factory"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["ranks_seen"] == 1
     assert line["collective"]["backend"] == "gloo" and line["collective"]["world_size"] == 1
+    assert torch.tensor(line["last_actions"]).shape == (6, 4)
+    # a plain run (no --full) still all-gathers every step through the process group, but takes no collective report
+    plain = [a for a in cmd if a != "--full"]
+    res = subprocess.run(plain, env=env, capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr[-2000:]
+    line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["ranks_seen"] == 1 and "collective" not in line
     assert torch.tensor(line["last_actions"]).shape == (6, 4)
     # without the switch a single rank creates no process group and reports no collective
     env.pop("LRAM_DIST_SINGLE_RANK")

@@ -1,13 +1,24 @@
 """GPU: bench.py's own line -- the contract keys, the physical roofline (fractions <= 1), the host-inclusive leg -- on a
-reduced batch so that it runs in seconds."""
+reduced batch so that it runs in seconds; and the plain run (no --full): the headline alone, within its time budget."""
+import json
+import os
+import subprocess
+import sys
+import time
+
 import pytest
 
 pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADLINE_KEYS = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")
+# what only --full measures, each after the timed region with time of its own
+FULL_ONLY_KEYS = ("host_io", "value_host_inclusive", "hbm_copy_measured_GBps", "hbm_rmw_measured_GBps", "hbm_read_measured_GBps",
+                  "hbm_read_4GiB_launch_GBps", "configs", "cpu_baseline", "collective")
 
 
 def test_bench_line_contract_and_physical_roofline(hip_lib, capsys):
     import bench
-    out = bench.main(["--config", "xlstm_16m", "--batch", "512", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
+    out = bench.main(["--config", "xlstm_16m", "--batch", "512", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline",
                       "--no-stream-ceilings", "--host-io-steps", "3", "--timing-every", "2"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline"):
@@ -43,6 +54,71 @@ def test_bench_line_contract_and_physical_roofline(hip_lib, capsys):
     assert out["build_id"] == build.source_hash() and out["build_id_matches_sources"] is True
     assert "cpu_baseline" not in out and "_copy_ceiling_pending" not in out
     capsys.readouterr()
+
+
+def test_plain_run_times_the_headline_and_nothing_else(hip_lib, monkeypatch, capsys):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full, on the default workload (the one that also runs the config legs
+    and the CPU baseline under --full): one engine, the lazy priming + W warm-up + K timed steps and no other step, the
+    state-pass events of the timed region on the line, nothing measured after it."""
+    import torch
+    import bench
+    from lram_amd import engine as _engine
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LRAM_DIST_SINGLE_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    built, calls = [], []
+
+    class Counting(_engine.Engine):
+        def __init__(self, *a, **kw):
+            super().__init__(*a, **kw)
+            built.append(self)
+
+        def step(self, *a, **kw):
+            calls.append("step")
+            return super().step(*a, **kw)
+
+        def set_micro_batches(self, n):
+            calls.append(f"micro {n}")
+            return super().set_micro_batches(n)
+
+    monkeypatch.setattr("lram_amd.engine.Engine", Counting)
+    W, K = 2, 8
+    try:
+        out = bench.main(["--gpus", "1", "--steps", str(K), "--warmup", str(W)])
+    finally:
+        for e in built:
+            e.close()
+        torch.cuda.empty_cache()
+    assert len(built) == 1
+    assert calls == ["micro 0"] + ["step"] * (16 + W + K), calls
+    for key in HEADLINE_KEYS:
+        assert key in out, key
+    assert out["metric"] == "env-steps/sec (action-inference)" and out["unit"] == "env-steps/s" and out["dtype"] == "f32"
+    assert out["higher_is_better"] is True and out["steps"] == K and out["warmup"] == W and out["config"]["batch_per_gpu"] == 4096
+    assert abs(out["value"] - 4096 * K / (out["ms_per_step"] * K * 1e-3)) < 1e-6 * out["value"]
+    for key in FULL_ONLY_KEYS:
+        assert key not in out, key
+    r = out["roofline"]   # the sampled events of the timed region (every 4th step), unchanged; no standalone sub-leg
+    assert r["launches_per_step"] == 14 and r["steps_timed"] == 2 and 0.0 < r["frac"] <= 1.0 and "standalone" not in r
+    capsys.readouterr()
+
+
+def test_plain_run_spends_at_most_30_s_outside_its_steps(hip_lib):
+    """`bench.py --gpus 1 --steps K --warmup W` in a new process, start to exit, less (K + W) x ms_per_step: interpreter and
+    torch start, library check, weights, engine set-up, the lazy priming steps and teardown all count."""
+    K, W = 20, 5
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LRAM_DIST_SINGLE_RANK")}
+    t0 = time.perf_counter()
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W)],
+                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    wall = time.perf_counter() - t0
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, proc.stdout[-2000:]
+    out = json.loads(lines[0])
+    for key in FULL_ONLY_KEYS:
+        assert key not in out, key
+    outside = wall - (K + W) * out["ms_per_step"] * 1e-3
+    assert outside <= 30.0, f"{outside:.1f} s outside the steps ({wall:.1f} s wall)"
 
 
 def test_bench_dump_outputs_repeat_exactly(hip_lib, tmp_path, capsys):

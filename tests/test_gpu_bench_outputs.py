@@ -1,8 +1,9 @@
 """GPU: what bench.py times, held to the oracle call for call.
 
-bench.main and bench.config_legs run exactly as the driver runs them, with every engine they build under the recorder of
-tests/bench_replay.py; each engine's record is then replayed through the CPU oracle on a sample of rows (rows 0 and B - 1,
-both ends of every env slice, rows the bench's reset schedule restarts inside the run, a row that never restarts):
+bench.main and bench.config_legs run exactly as `bench.py --full` runs them (a plain run makes the same steps up to the end
+of its timed region), with every engine they build under the recorder of tests/bench_replay.py; each engine's record is then
+replayed through the CPU oracle on a sample of rows (rows 0 and B - 1, both ends of every env slice, rows the bench's reset
+schedule restarts inside the run, a row that never restarts):
 
   headline    16M x 4096 with the lazy priming steps, the sampled state-pass events, the standalone sub-leg (one env slice in
               the middle of the run) and the host-inclusive leg; the --dump-outputs arrays are the recorder's last timed step,
@@ -26,7 +27,8 @@ from tests.helpers import assert_actions_match, rel_err
 
 pytestmark = pytest.mark.gpu
 
-COMMON = ["--gpus", "1", "--no-cpu-baseline", "--no-stream-ceilings", "--no-configs"]
+# --full: the host-inclusive leg and the standalone sub-leg run after the timed steps and are replayed with them
+COMMON = ["--gpus", "1", "--full", "--no-cpu-baseline", "--no-stream-ceilings", "--no-configs"]
 
 
 def _report(line):

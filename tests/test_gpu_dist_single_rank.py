@@ -26,7 +26,7 @@ def test_bench_n_gt_1_path_runs_on_rccl_with_one_rank(hip_lib):
                MASTER_PORT=str(port))
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "512", "--steps", "6", "--warmup", "2",
-           "--no-cpu-baseline", "--no-stream-ceilings", "--host-io-steps", "3"]
+           "--full", "--no-cpu-baseline", "--no-stream-ceilings", "--host-io-steps", "3"]
     proc = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert proc.returncode == 0, proc.stderr[-2000:]
     line = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")][-1]
