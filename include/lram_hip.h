@@ -108,7 +108,8 @@ int64_t lram_state_bytes_per_env(const lram_engine* e);
 int32_t lram_reset(lram_engine* e, const uint8_t* dev_env_mask, void* stream);
 
 /* One env-step for all `batch` slots: embed (state, rtg, reward) -> embed_ln -> tokens_per_step
- * recurrent token steps through the block stack -> post norm -> action head -> argmax -> inv_tokenize.
+ * recurrent token steps through the block stack -> post norm -> action head -> argmax -> inv_tokenize
+ * (with lram_set_sampling armed: -> token drawn from the logits -> inv_tokenize).
  * Replaces policy.forward(..., use_inference_cache=True, past_key_values=...) as called from
  * get_action_pred (src/algos/discrete_decision_transformer_sb3.py:60-68) for every env at once.
  *   dev_obs        device float[batch, state_dim]  (zero-padded obs, decision_xlstm.py:16-19), or, when
@@ -120,7 +121,10 @@ int32_t lram_reset(lram_engine* e, const uint8_t* dev_env_mask, void* stream);
  *   discrete       0: continuous head (argmax over n_vocab per action dim, de-tokenised to fp32)
  *                  1: discrete head (argmax over the first n_discrete logits of action dim 0)
  *   dev_actions    device float[batch, act_dim]    out; discrete: column 0 holds the action index
- *   dev_tokens     device int32[batch, act_dim] or NULL   out; raw argmax token ids */
+ *   dev_tokens     device int32[batch, act_dim] or NULL   out; raw token ids
+ * Sampling off (the default, a_sample_kwargs = None in the reference): the token is the argmax of its row.  Sampling on
+ * (lram_set_sampling): the token is drawn from its row; dev_actions holds what the argmax path would write for that
+ * token id (continuous: inv_tokenize(token); discrete: the id), and the call counts as one draw. */
 int32_t lram_step(lram_engine* e, const float* dev_obs, int32_t obs_is_embedding, const float* dev_rtg,
                   const float* dev_reward, const uint8_t* dev_reset_mask, int32_t discrete,
                   float* dev_actions, int32_t* dev_tokens, void* stream);
@@ -224,6 +228,39 @@ int32_t lram_set_micro_batches(lram_engine* e, int32_t n);
 int32_t lram_set_compat_mode(lram_engine* e, int32_t mamba_repeat, int32_t stale_state);
 int32_t lram_get_compat_mode(const lram_engine* e, int32_t* mamba_repeat, int32_t* stale_state);
 
+/* Sampling mode of the action head, off by default: the counterpart of the agents' `a_sample_kwargs`
+ * (src/algos/discrete_decision_transformer_sb3.py:8-11,63-64; src/algos/decision_mamba.py:118-120), which hand the head's
+ * logits to sample_from_logits(logits, temperature, top_k, top_p) (src/algos/models/model_utils.py:7-32).  With enable != 0
+ * lram_step, lram_step_images and lram_prefill draw each (env, action dim) token from its row of logits -- n_vocab values, or
+ * the first n_discrete of action dim 0 for the discrete head -- instead of taking the argmax.  Row by row, as the reference:
+ *   1. top_p > 0: q = torch.quantile(row, top_p) in float64 (linear interpolation between the order statistics at
+ *      floor / ceil(top_p * (n - 1))); unless q equals the row's maximum, every logit <= q is dropped.  This is a quantile of
+ *      the logit VALUES, not nucleus sampling.
+ *   2. top_k > 0: only the k largest of what is left stay (ties at the k-th place: the lowest index first).
+ *   3. probabilities = softmax(temperature * logits) over what is left: `temperature` MULTIPLIES the logits, as in the
+ *      reference (a larger value sharpens the distribution).
+ *   4. the token is the first one, in vocabulary order, whose cumulative probability exceeds one uniform u in [0, 1).
+ * The reference draws with torch's generator; here u is word x0 of Philox4x32-10 (Salmon et al., SC'11), u = x0 * 2^-32, with
+ *      key     = (seed & 0xffffffff, seed >> 32)
+ *      counter = ((slot_base + s) & 0xffffffff, j, d & 0xffffffff, d >> 32)
+ * for env slot s (index within this engine), action dim j and draw d.  d counts the action-producing calls (lram_step,
+ * lram_step_images, lram_prefill with dev_actions) since sampling was last armed: one per call, also when the Mamba
+ * reference-trajectory mode runs several forwards in it (they share d and differ in j).  Resets do not touch d.  It lives in
+ * device memory and is advanced on the device behind the head launches of the call, so replayed hipGraph steps draw afresh.
+ * slot_base is the global index of this engine's first env slot: engines holding ranges of one slot numbering (lram_amd.dist
+ * shard bounds) draw what one engine over all slots would.
+ * Rows the rule has no answer for -- a NaN in the row, a maximum of +inf or -inf, or nothing left after step 1 (a NaN
+ * quantile) -- take the argmax rule of the default path (the reference raises); -inf logits have probability 0.
+ * Errors: temperature not finite or <= 0, top_p outside [0, 1], top_k < 0 or > n_vocab, n_vocab > 512; a discrete-head call
+ * with top_k > n_discrete fails at that call.  enable = 0 restores the argmax launches; the other arguments are then ignored.
+ * Arming zeroes d.  Synchronises the device and drops a captured graph: not a hot-path call. */
+int32_t lram_set_sampling(lram_engine* e, int32_t enable, double temperature, int32_t top_k, double top_p, uint64_t seed,
+                          uint64_t slot_base);
+/* Reads the settings back (the last armed ones when disabled) and, into *draws, d (0 when disabled; synchronises the device).
+ * Any pointer may be NULL. */
+int32_t lram_get_sampling(lram_engine* e, int32_t* enable, double* temperature, int32_t* top_k, double* top_p, uint64_t* seed,
+                          uint64_t* slot_base, uint64_t* draws);
+
 /* Per-kernel timing of the recurrent step, measured with HIP events on the stream the kernels are
  * launched on.  lram_profile_begin arms it; every later lram_step records one (start, stop) event pair
  * around the mLSTM cell-update launches (xLSTM) or the selective-state-update launches (Mamba).
@@ -293,6 +330,15 @@ int32_t lram_gemm_f16x2(const float* dev_a, int64_t lda, const float* dev_w, int
 int32_t lram_gemm_f16x2_presplit(const float* dev_a, int64_t lda, const float* dev_w, int64_t ldw, float* dev_c,
                                  int64_t ldc, const float* dev_bias, int32_t accumulate, int32_t m, int32_t n,
                                  int32_t k, void* stream);
+/* The device code of the sampling head on caller data (test / evidence entry): row r = dev_logits + r * ld holds n <= 512
+ * logits (ld = 0: every row is row 0), dev_uniform[r] (device double) its uniform in [0, 1); dev_tokens[r] (device int32)
+ * receives the token of steps 1-4 of lram_set_sampling. */
+int32_t lram_sample_tokens(const float* dev_logits, int64_t rows, int32_t n, int64_t ld, double temperature, int32_t top_k,
+                           double top_p, const double* dev_uniform, int32_t* dev_tokens, void* stream);
+/* The uniforms an armed step would use at draw `draw`: dev_out (device double[n_slots, act_dim]) [s, j] for env slots
+ * slot_base .. slot_base + n_slots - 1 (test / evidence entry). */
+int32_t lram_sample_uniforms(uint64_t seed, uint64_t slot_base, int64_t n_slots, int32_t act_dim, uint64_t draw,
+                             double* dev_out, void* stream);
 /* Image observations: uint8 frames [batch, channels, height, width] -> state-token embeddings [batch, d_model]
  * through the IMPALA CNN (3 x [conv3x3 -> maxpool(3,2,1) -> 2 residual blocks], 16/32/32 channels, ReLU, flatten,
  * Linear, ReLU).  Replaces `self.embed_image(state.float() / 255)` (online_decision_transformer_model.py:523-526;

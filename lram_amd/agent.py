@@ -30,6 +30,30 @@ from .config import ModelSpec
 from .engine import Engine
 
 
+SAMPLE_DEFAULTS = {"temperature": 1.0, "top_k": 0, "top_p": 0.5}   # sample_from_logits' own (model_utils.py:7)
+
+
+def resolve_sample_kwargs(kwargs: Optional[dict], n_head: int) -> Optional[dict]:
+    """`a_sample_kwargs` -> the settings the engine is armed with: None stays None (argmax); a dict -- `{}` included --
+    is completed with the reference's defaults.  Unknown keys raise KeyError, values the head refuses ValueError
+    (`n_head`: logits per row of the head in use)."""
+    if kwargs is None:
+        return None
+    unknown = set(kwargs) - set(SAMPLE_DEFAULTS)
+    if unknown:
+        raise KeyError(f"unknown key(s) in a_sample_kwargs: {sorted(unknown)} (sample_from_logits takes "
+                       f"{sorted(SAMPLE_DEFAULTS)})")
+    out = {**SAMPLE_DEFAULTS, **kwargs}
+    t, k, p = float(out["temperature"]), out["top_k"], float(out["top_p"])
+    if not (t > 0.0 and t < float("inf")):
+        raise ValueError(f"a_sample_kwargs.temperature must be finite and > 0 (it multiplies the logits), got {t}")
+    if int(k) != k or not 0 <= int(k) <= n_head:
+        raise ValueError(f"a_sample_kwargs.top_k must be an integer in 0 .. {n_head} (the head's logits per row), got {k}")
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"a_sample_kwargs.top_p must be in [0, 1], got {p}")
+    return {"temperature": t, "top_k": int(k), "top_p": p}
+
+
 class _InferenceParams:
     """Stand-in for the reference's InferenceParams (src/algos/decision_mamba.py:9-25): reset() clears the
     cache -- every layer by default; with the agent's `compat_stale_state` only layer 0, as the reference does
@@ -50,8 +74,18 @@ class RecurrentAgent:
                  state_std: Optional[torch.Tensor] = None, target_return: float = 0.0, reward_scale: float = 1.0,
                  graph: bool = False, reprime_context: bool = False, persist_context: bool = False,
                  compat_mamba_repeat: bool = False,
-                 compat_stale_state: bool = False):
+                 compat_stale_state: bool = False,
+                 a_sample_kwargs: Optional[dict] = None, sample_seed: int = 0, sample_slot_base: int = 0):
         self.spec = spec
+        # a_sample_kwargs (src/algos/discrete_decision_transformer_sb3.py:8-11): None = argmax actions, today's behaviour;
+        # a dict = actions drawn on the device (Engine.set_sampling), with sample_from_logits' keyword names and defaults
+        # (src/algos/models/model_utils.py:7).  `deterministic` is accepted and ignored by predict / get_action_pred, as in
+        # the reference, where a_sample_kwargs alone decides.
+        # Not given here: what the configuration set (agent_params.a_sample_kwargs -> ModelSpec.a_sample_kwargs; no preset does).
+        if a_sample_kwargs is None:
+            a_sample_kwargs = spec.a_sample_kwargs
+        self.a_sample_kwargs = resolve_sample_kwargs(a_sample_kwargs, spec.n_discrete if discrete else spec.n_vocab)
+        self.sample_seed, self.sample_slot_base = int(sample_seed), int(sample_slot_base)
         # host copy of the weights: lets the agent cross a process boundary (make_pickleable / reinit_cuda_kernels)
         self._state_dict = {k: v.detach().to("cpu") for k, v in state_dict.items()}
         self._graph = bool(graph)
@@ -95,11 +129,19 @@ class RecurrentAgent:
         self._compat_repeat_now = 1
         if self.compat_stale_state:
             self.engine.set_compat_mode(1, True)
+        self._arm_sampling()
+
+    def _arm_sampling(self):
+        if self.a_sample_kwargs is not None:
+            self.engine.set_sampling(seed=self.sample_seed, slot_base=self.sample_slot_base, **self.a_sample_kwargs)
 
     @property
     def trajectory_mode(self) -> dict:
         """Which trajectory semantics the rollout uses (logged by rollout / bench)."""
-        return {"compat_mamba_repeat": self.compat_mamba_repeat, "compat_stale_state": self.compat_stale_state}
+        mode = {"compat_mamba_repeat": self.compat_mamba_repeat, "compat_stale_state": self.compat_stale_state}
+        if getattr(self, "a_sample_kwargs", None) is not None:   # (argmax actions: the record stays as it always was)
+            mode["a_sample_kwargs"] = dict(self.a_sample_kwargs, seed=self.sample_seed, slot_base=self.sample_slot_base)
+        return mode
 
     # ---- cache handle: `model.past_key_values = None` resets, reading exports the reference layout ----
     @property
@@ -122,13 +164,15 @@ class RecurrentAgent:
             self.engine = None
 
     def reinit_cuda_kernels(self, replace_cell: bool = False):
-        """Worker-side counterpart of make_pickleable: build a fresh engine (recurrent state starts empty)."""
+        """Worker-side counterpart of make_pickleable: build a fresh engine (recurrent state starts empty; sampling is
+        armed again with the same settings and its draw count restarts at 0)."""
         if self.engine is None:
             self.engine = Engine(self.spec, self._state_dict, self.n_envs, self.device)
             if self._graph:
                 self.engine.set_graph_mode(True)
             if self.compat_stale_state or self._compat_repeat_now != 1:
                 self.engine.set_compat_mode(self._compat_repeat_now, self.compat_stale_state)
+            self._arm_sampling()
 
     def __getstate__(self):
         d = dict(self.__dict__)

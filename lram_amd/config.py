@@ -69,6 +69,9 @@ class ModelSpec:
     max_length: int = 50
     use_inference_cache: bool = True
     reset_inf_cache_freq: Optional[int] = None
+    # agent_params.a_sample_kwargs (src/algos/discrete_decision_transformer_sb3.py:8-11): None = argmax actions; a dict
+    # (keys temperature / top_k / top_p, the reference's defaults for missing ones) = actions drawn by the sampling head
+    a_sample_kwargs: Optional[Dict[str, Any]] = None
 
     def __post_init__(self):
         if self.backbone not in ("xlstm", "mamba"):
@@ -286,6 +289,7 @@ def spec_from_agent_params(ap: Dict[str, Any]) -> ModelSpec:
         max_length=int(hf.get("max_length", 50)),
         use_inference_cache=bool(ap.get("use_inference_cache", True)),
         reset_inf_cache_freq=ap.get("reset_inf_cache_freq"),
+        a_sample_kwargs=None if ap.get("a_sample_kwargs") is None else dict(ap["a_sample_kwargs"]),
     )
     if kind in XLSTM_KINDS:
         _strict(hf, _XLSTM_HF_KEYS, "agent_params.huggingface")

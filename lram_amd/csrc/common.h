@@ -233,6 +233,26 @@ void launch_embed_chunk(float* x, const float* emb, int64_t emb_stride, const fl
 void launch_action_argmax(const float* logits, float* actions, int32_t* tokens, int B, int act_dim, int n_vocab,
                           int n_discrete, int action_channels, float tok_min, float tok_max, int discrete,
                           int col_begin, hipStream_t stream, int col_end = -1);
+// The sampling mode of the same head (sample_kernels.hip): the token is drawn from the row instead of being its argmax.
+constexpr int kSampleMaxRow = 512;  // logits per row the sampling kernels hold in registers (8 per lane)
+struct SampleArgs {
+  double temperature = 1.0;  // MULTIPLIES the logits, as the reference's sample_from_logits does
+  double top_p = 0.0;        // quantile of the logit values below which logits are dropped; 0 = off
+  int top_k = 0;             // 0 = off
+  uint64_t seed = 0;         // Philox key
+  uint64_t slot0 = 0;        // global index of logits row 0's env slot (counter word 0)
+  const uint64_t* draw = nullptr;  // device: action-producing calls since sampling was armed (counter words 2, 3)
+};
+void launch_action_sample(const float* logits, float* actions, int32_t* tokens, int B, int act_dim, int n_vocab,
+                          int n_discrete, int action_channels, float tok_min, float tok_max, int discrete, int col_begin,
+                          int col_end, const SampleArgs& sp, hipStream_t stream);
+void launch_sample_advance(uint64_t* draw, hipStream_t stream);  // ++*draw, one thread
+// rows of n logits at logits + r * ld (ld = 0: every row is row 0), one caller uniform per row -> tokens[rows]
+void launch_sample_tokens(const float* logits, int64_t rows, int n, int64_t ld, double temperature, int top_k, double top_p,
+                          const double* uniform, int32_t* tokens, hipStream_t stream);
+// out[s * act_dim + j] = the uniform of env slot slot_base + s, action dim j, draw `draw`
+void launch_sample_uniforms(uint64_t seed, uint64_t slot_base, int64_t n_slots, int act_dim, uint64_t draw, double* out,
+                            hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // xLSTM

@@ -11,6 +11,15 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// torch.argmax order of (value, index) candidates: NaN is the maximum, the first index wins among equal values (NaNs
+// included), +-Inf compare as ordinary values.  Starting from (-inf, INT_MAX) every element of a non-empty row is taken
+// or loses to one that was, so the winner is always a real index.  (Action head: misc_kernels.hip, sample_kernels.hip.)
+__device__ __forceinline__ bool argmax_beats(float v, int i, float best, int bi) {
+  const bool v_nan = v != v, best_nan = best != best;
+  if (v_nan) return !best_nan || i < bi;
+  return !best_nan && (v > best || (v == best && i < bi));
+}
+
 // torch.nn.functional.logsigmoid: min(x, 0) - log1p(exp(-|x|))
 __device__ __forceinline__ float log_sigmoid(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
 

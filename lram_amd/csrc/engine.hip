@@ -222,6 +222,11 @@ struct lram_engine {
   int compat_pass = 0, compat_passes = 1;
   bool compat_share = true;   // LRAM_COMPAT_SHARE=0: every repeated forward recomputes the front end and layer 0's in_proj
   bool compat_stale = false;  // a reset re-initialises layer 0 only; layers >= 1 keep the previous episode's state
+  // action head, sampling mode (lram_set_sampling): the settings travel as kernel arguments; the draw counter is device memory,
+  // read by every head launch of an env-step and advanced once behind them (a replayed graph has frozen arguments)
+  bool sampling = false;
+  SampleArgs sample;             // .slot0 holds slot_base; a slice adds its first env slot
+  uint64_t* sample_draw = nullptr;
   static constexpr int cell_unroll = 16;  // C rows in flight per thread of the materialised cell kernel
   std::vector<hipStream_t> micro_streams;
   hipStream_t hbm_stream = nullptr;
@@ -253,6 +258,7 @@ struct lram_engine {
     for (auto& kv : weights) kv.second.release();
     drop_splits();
     release_state();
+    if (sample_draw) (void)hipFree(sample_draw);
   }
   void drop_splits() {
     for (auto& kv : split) (void)hipFree(kv.second.p);
@@ -1843,12 +1849,27 @@ void timesteps_launches(lram_engine* e, const float* obs, int emb, const float* 
       gh.c = e->LOGITS.p + b0 * nlog + (size_t)col0 * c.n_vocab, gh.ldc = nlog, gh.bias = e->b_head + (size_t)col0 * c.n_vocab;
       gh.m = x.nb, gh.n = (col_end - col0) * c.n_vocab, gh.k = D;
       gemm(e, gh, x.s);
+      if (e->sampling) {
+        SampleArgs sp = e->sample;
+        sp.slot0 += b0, sp.draw = e->sample_draw;
+        launch_action_sample(e->LOGITS.p + b0 * nlog, actions + b0 * c.act_dim, tokens ? tokens + b0 * c.act_dim : nullptr,
+                             x.nb, c.act_dim, c.n_vocab, c.n_discrete, c.action_channels, c.tok_min, c.tok_max, discrete,
+                             col_begin, col_end, sp, x.s);
+        continue;
+      }
       launch_action_argmax(e->LOGITS.p + b0 * nlog, actions + b0 * c.act_dim,
                            tokens ? tokens + b0 * c.act_dim : nullptr, x.nb, c.act_dim, c.n_vocab, c.n_discrete,
                            c.action_channels, c.tok_min, c.tok_max, discrete, col_begin, x.s, col_end);
     }
   }
   if (multi && (fork_join & 2)) join_slices(e, sl, hbm, s);
+}
+
+// Sampling mode: one draw per action-producing call.  Launched on the caller's stream behind the join of the env slices
+// (and behind the last of the repeated forwards), so that every row of the call has read the same count; the next call's
+// slices fork from this stream and see the new one.  In a captured step it is one more node on the graph's single chain.
+void sample_draw_advance(lram_engine* e, hipStream_t s) {
+  if (e->sampling) launch_sample_advance(e->sample_draw, s);
 }
 
 // Do the repeated forwards of the Mamba reference-trajectory mode share the token front end and layer 0's in_proj?
@@ -1888,6 +1909,7 @@ void step_launches(lram_engine* e, const float* obs, int emb, const float* rtg, 
                        share ? passes : 0, fj);
   }
   e->compat_pass = 0, e->compat_passes = 1;
+  sample_draw_advance(e, s);
 }
 
 struct StateView {
@@ -2136,6 +2158,7 @@ int32_t lram_prefill(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_em
     prof_tick(e);
     timesteps_launches(e, dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps, dev_reset_mask, discrete,
                        dev_actions, dev_tokens, static_cast<hipStream_t>(stream));
+    if (dev_actions != nullptr) sample_draw_advance(e, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -2318,6 +2341,74 @@ int32_t lram_set_compat_mode(lram_engine* e, int32_t mamba_repeat, int32_t stale
     if (e->compat_repeat != mamba_repeat || e->compat_stale != (stale_state != 0)) e->drop_graph();
     e->compat_repeat = mamba_repeat;
     e->compat_stale = stale_state != 0;
+  });
+}
+
+int32_t lram_set_sampling(lram_engine* e, int32_t enable, double temperature, int32_t top_k, double top_p, uint64_t seed,
+                          uint64_t slot_base) {
+  return guarded([&] {
+    LRAM_REQUIRE(e != nullptr, "lram_set_sampling: null engine");
+    if (enable) {
+      LRAM_REQUIRE(temperature > 0.0 && temperature < (double)INFINITY,
+                   "lram_set_sampling: temperature must be finite and > 0 (it multiplies the logits)");
+      LRAM_REQUIRE(top_p >= 0.0 && top_p <= 1.0, "lram_set_sampling: top_p must be in [0, 1]");
+      LRAM_REQUIRE(top_k >= 0, "lram_set_sampling: top_k must be >= 0");
+      LRAM_REQUIRE(top_k <= e->cfg.n_vocab, "lram_set_sampling: top_k exceeds the head's n_vocab logits");
+      LRAM_REQUIRE(e->cfg.n_vocab <= kSampleMaxRow, "lram_set_sampling: the sampling kernel holds rows of up to 512 logits");
+    }
+    LRAM_HIP_CHECK(hipSetDevice(e->device));
+    LRAM_HIP_CHECK(hipDeviceSynchronize());  // steps in flight (non-blocking streams included) keep the mode they were launched in
+    e->drop_graph();                         // the head kernel and its arguments are part of a captured step
+    if (enable) {
+      if (!e->sample_draw) LRAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->sample_draw), sizeof(uint64_t)));
+      LRAM_HIP_CHECK(hipMemset(e->sample_draw, 0, sizeof(uint64_t)));
+      LRAM_HIP_CHECK(hipDeviceSynchronize());
+      e->sample.temperature = temperature, e->sample.top_k = top_k, e->sample.top_p = top_p;
+      e->sample.seed = seed, e->sample.slot0 = slot_base;
+    }
+    e->sampling = enable != 0;
+  });
+}
+
+int32_t lram_get_sampling(lram_engine* e, int32_t* enable, double* temperature, int32_t* top_k, double* top_p, uint64_t* seed,
+                          uint64_t* slot_base, uint64_t* draws) {
+  return guarded([&] {
+    LRAM_REQUIRE(e != nullptr, "lram_get_sampling: null engine");
+    if (enable) *enable = e->sampling ? 1 : 0;
+    if (temperature) *temperature = e->sample.temperature;
+    if (top_k) *top_k = e->sample.top_k;
+    if (top_p) *top_p = e->sample.top_p;
+    if (seed) *seed = e->sample.seed;
+    if (slot_base) *slot_base = e->sample.slot0;
+    if (draws) {
+      *draws = 0;
+      if (e->sampling) {
+        LRAM_HIP_CHECK(hipSetDevice(e->device));
+        LRAM_HIP_CHECK(hipDeviceSynchronize());
+        LRAM_HIP_CHECK(hipMemcpy(draws, e->sample_draw, sizeof(uint64_t), hipMemcpyDeviceToHost));
+      }
+    }
+  });
+}
+
+int32_t lram_sample_tokens(const float* dev_logits, int64_t rows, int32_t n, int64_t ld, double temperature, int32_t top_k,
+                           double top_p, const double* dev_uniform, int32_t* dev_tokens, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(dev_logits && dev_uniform && dev_tokens, "lram_sample_tokens: null device pointer");
+    LRAM_REQUIRE(temperature > 0.0 && temperature < (double)INFINITY, "lram_sample_tokens: temperature must be finite and > 0");
+    LRAM_REQUIRE(top_p >= 0.0 && top_p <= 1.0, "lram_sample_tokens: top_p must be in [0, 1]");
+    LRAM_REQUIRE(top_k >= 0 && top_k <= n, "lram_sample_tokens: top_k must be in 0 .. n");
+    LRAM_REQUIRE(ld == 0 || ld >= n, "lram_sample_tokens: ld must be 0 (one shared row) or >= n");
+    launch_sample_tokens(dev_logits, rows, n, ld, temperature, top_k, top_p, dev_uniform, dev_tokens,
+                         static_cast<hipStream_t>(stream));
+  });
+}
+
+int32_t lram_sample_uniforms(uint64_t seed, uint64_t slot_base, int64_t n_slots, int32_t act_dim, uint64_t draw,
+                             double* dev_out, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(dev_out != nullptr, "lram_sample_uniforms: null device pointer");
+    launch_sample_uniforms(seed, slot_base, n_slots, act_dim, draw, dev_out, static_cast<hipStream_t>(stream));
   });
 }
 

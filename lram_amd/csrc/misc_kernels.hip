@@ -203,16 +203,7 @@ __global__ __launch_bounds__(256) void embed_chunk_kernel(float* x, const float*
   *reinterpret_cast<float4*>(row + 2 * D) = make_float4(r * wr.x + br.x, r * wr.y + br.y, r * wr.z + br.z, r * wr.w + br.w);
 }
 
-// torch.argmax order of (value, index) candidates: NaN is the maximum, the first index wins among equal values (NaNs
-// included), +-Inf compare as ordinary values.  Starting from (-inf, INT_MAX) every element of a non-empty row is taken
-// or loses to one that was, so the winner is always a real index.
-__device__ __forceinline__ bool argmax_beats(float v, int i, float best, int bi) {
-  const bool v_nan = v != v, best_nan = best != best;
-  if (v_nan) return !best_nan || i < bi;
-  return !best_nan && (v > best || (v == best && i < bi));
-}
-
-// One wave per (env, action dim): first index of the maximum (torch.argmax rule, argmax_beats), then
+// One wave per (env, action dim): first index of the maximum (torch.argmax rule, device_math.h::argmax_beats), then
 // inv_tokenize: max(tok - shift, 0) * ((max - min) / channels) + min.
 __global__ __launch_bounds__(256) void action_argmax_kernel(const float* logits, float* actions, int32_t* tokens,
                                                             int B, int act_dim, int n_vocab, int n_discrete,

@@ -61,6 +61,16 @@ _SYMBOLS = {
     "lram_set_micro_batches": (ctypes.c_int32, [_VP, ctypes.c_int32]),
     "lram_set_compat_mode": (ctypes.c_int32, [_VP, ctypes.c_int32, ctypes.c_int32]),
     "lram_get_compat_mode": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "lram_set_sampling": (ctypes.c_int32, [_VP, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_double,
+                                           ctypes.c_uint64, ctypes.c_uint64]),
+    "lram_get_sampling": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                           ctypes.POINTER(ctypes.c_uint64)]),
+    "lram_sample_tokens": (ctypes.c_int32, [_VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_double,
+                                            ctypes.c_int32, ctypes.c_double, _VP, _VP, _VP]),
+    "lram_sample_uniforms": (ctypes.c_int32, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32,
+                                              ctypes.c_uint64, _VP, _VP]),
     "lram_profile_begin": (ctypes.c_int32, [_VP]),
     "lram_profile_begin_sampled": (ctypes.c_int32, [_VP, ctypes.c_int32]),
     "lram_profile_end": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
@@ -434,6 +444,33 @@ class Engine:
         self.lib.lram_get_compat_mode(self._h, ctypes.byref(r), ctypes.byref(st))
         return {"mamba_repeat": int(r.value), "stale_state": bool(st.value)}
 
+    def set_sampling(self, temperature: Optional[float] = 1.0, top_k: int = 0, top_p: float = 0.0, seed: int = 0,
+                     slot_base: int = 0):
+        """Arm the sampling mode of the action head (lram_set_sampling): step / step_images / prefill then draw every
+        (env, action dim) token from its logits row -- quantile filter `top_p` (a quantile of the logit values, as the
+        reference's sample_from_logits, not nucleus sampling), the `top_k` largest, softmax(temperature * logits): the
+        temperature MULTIPLIES -- with Philox uniforms keyed by `seed` and counted per (slot_base + slot, action dim, draw).
+        Arming zeroes the draw count.  set_sampling(None) restores the argmax head."""
+        if temperature is None:
+            _check(self.lib, self.lib.lram_set_sampling(self._h, 0, 1.0, 0, 0.0, 0, 0))
+            return
+        _check(self.lib, self.lib.lram_set_sampling(self._h, 1, float(temperature), int(top_k), float(top_p),
+                                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(slot_base) & 0xFFFFFFFFFFFFFFFF))
+
+    @property
+    def sampling(self) -> Optional[dict]:
+        """None while the head takes the argmax; else the armed settings and `draws`, the action-producing calls since
+        arming (reads a device counter: synchronises)."""
+        on, k = ctypes.c_int32(0), ctypes.c_int32(0)
+        t, p = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        seed, base, draws = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(self.lib, self.lib.lram_get_sampling(self._h, ctypes.byref(on), ctypes.byref(t), ctypes.byref(k), ctypes.byref(p),
+                                                    ctypes.byref(seed), ctypes.byref(base), ctypes.byref(draws)))
+        if not on.value:
+            return None
+        return {"temperature": t.value, "top_k": int(k.value), "top_p": p.value, "seed": int(seed.value),
+                "slot_base": int(base.value), "draws": int(draws.value)}
+
     def profile_begin_sampled(self, every_n_steps: int):
         """Time every n-th step only (lram_profile_begin_sampled): 1/n of the event bookkeeping on the state-pass queue."""
         _check(self.lib, self.lib.lram_profile_begin_sampled(self._h, int(every_n_steps)))
@@ -489,6 +526,38 @@ def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = No
         out = torch.empty(M, N, dtype=torch.float32, device=a.device)
     _check(lib, fn(_ptr(a), a.stride(0), _ptr(w), w.stride(0), _ptr(out), out.stride(0), _ptr(bias),
                                   int(accumulate), M, N, K, _stream_ptr(a.device)))
+    return out
+
+
+def sample_tokens(logits: torch.Tensor, uniform: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 0.0,
+                  rows: Optional[int] = None) -> torch.Tensor:
+    """The sampling head's device code on caller data (lram_sample_tokens): logits float32 [R, n] (row stride free) or, with
+    `rows` given, one row [n] shared by all `rows` draws; uniform float64 [R] in [0, 1) -> tokens int32 [R]."""
+    lib = load_library()
+    if rows is None:
+        R, n = logits.shape
+        ld = logits.stride(0)
+        if logits.stride(1) != 1:
+            raise ValueError("logits rows must be contiguous")
+    else:
+        R, n, ld = int(rows), logits.shape[-1], 0
+        logits = logits.reshape(-1).contiguous()
+    _chk_dev(uniform, torch.float64, (R,), logits.device, "uniform")
+    if logits.dtype != torch.float32:
+        raise ValueError("logits must be float32")
+    out = torch.empty(R, dtype=torch.int32, device=logits.device)
+    _check(lib, lib.lram_sample_tokens(_ptr(logits), R, int(n), int(ld), float(temperature), int(top_k), float(top_p),
+                                       _ptr(uniform), _ptr(out), _stream_ptr(logits.device)))
+    return out
+
+
+def sample_uniforms(seed: int, slot_base: int, n_slots: int, act_dim: int, draw: int, device=None) -> torch.Tensor:
+    """The uniforms an armed step uses at draw `draw` (lram_sample_uniforms): float64 [n_slots, act_dim]."""
+    lib = load_library()
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    out = torch.empty(int(n_slots), int(act_dim), dtype=torch.float64, device=device)
+    _check(lib, lib.lram_sample_uniforms(int(seed) & 0xFFFFFFFFFFFFFFFF, int(slot_base) & 0xFFFFFFFFFFFFFFFF, int(n_slots),
+                                         int(act_dim), int(draw) & 0xFFFFFFFFFFFFFFFF, _ptr(out), _stream_ptr(device)))
     return out
 
 
