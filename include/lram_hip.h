@@ -32,6 +32,11 @@ extern "C" {
 
 #define LRAM_MAX_BLOCKS 64
 
+/* Mixed-domain batches (lram_set_slot_table below) */
+#define LRAM_HEAD_PER_SLOT 2 /* value of `discrete`: take the head mode of each slot from the slot table */
+#define LRAM_SLOT_DISCRETE 1 /* flags[b] bit 0: discrete head (first n_discrete logits of action dim 0, action = index) */
+#define LRAM_SLOT_IMAGE    2 /* flags[b] bit 1: the slot's observation is a uint8 frame */
+
 /* Model description.  Mirrors the fields the reference reads from `agent_params.huggingface`
  * (configs/agent_params/huggingface/xlstm_*.yaml, mamba_*.yaml -> xLSTMConfig / MambaConfig,
  * src/algos/models/decision_xlstm.py:104-116, src/algos/models/decision_mamba.py:15-49) and from
@@ -120,6 +125,8 @@ int32_t lram_reset(lram_engine* e, const uint8_t* dev_env_mask, void* stream);
  *   dev_reset_mask device uint8[batch] or NULL     slots to reset before this step
  *   discrete       0: continuous head (argmax over n_vocab per action dim, de-tokenised to fp32)
  *                  1: discrete head (argmax over the first n_discrete logits of action dim 0)
+ *                  LRAM_HEAD_PER_SLOT: the head mode and the action dims in use of every slot come from the slot table
+ *                  (lram_set_slot_table); the observation kind stays the call's own
  *   dev_actions    device float[batch, act_dim]    out; discrete: column 0 holds the action index
  *   dev_tokens     device int32[batch, act_dim] or NULL   out; raw token ids
  * Sampling off (the default, a_sample_kwargs = None in the reference): the token is the argmax of its row.  Sampling on
@@ -356,6 +363,49 @@ int32_t lram_step_images(lram_engine* e, const uint8_t* dev_images, int32_t chan
                          const float* dev_rtg, const float* dev_reward, const uint8_t* dev_reset_mask, int32_t discrete,
                          float* dev_actions_out, int32_t* dev_tokens_out, void* stream);
 
+/* Slot table: per env slot the head mode, the number of action dims in use and the observation kind -- what the reference's
+ * evaluation loop hands every call for ONE env (`env_act_dim`, `is_discrete`: src/callbacks/evaluation.py:90-138; the head
+ * treats the two kinds differently, multi_domain_discrete_dt_model.py:83-108), here for every slot of one batch, so that envs
+ * of several domains (Atari / Procgen frames with 18 discrete actions beside Meta-World / DMControl vectors with 1-8 tokenised
+ * action dims) step together.  Host arrays of `batch` entries; NULL, NULL clears the table.  flags[b]: LRAM_SLOT_* bits;
+ * act_dim[b] in 1 .. cfg.act_dim, a discrete slot has act_dim 1.
+ *   - Not a hot-path call: synchronises the device, drops a captured graph, keeps a host copy (it gives every env slice its
+ *     range of frames) and a device copy (read by the head launches).  lram_state_alloc clears the table.  lram_config and
+ *     LRAM_ABI_VERSION are unchanged.  A refused table leaves the one in effect as it was.
+ *   - Errors: an unknown flag bit; act_dim out of range; a discrete slot with act_dim != 1 or with cfg.n_discrete == 0.  Image
+ *     slots without `embed_image.*` weights fail at the first lram_step_slots call that needs them.
+ *   - Head output for slot b (discrete = LRAM_HEAD_PER_SLOT or lram_step_slots), the same in argmax and sampling mode:
+ *       continuous slot: columns j < act_dim[b] hold what discrete = 0 writes;
+ *       discrete slot:   column 0 holds what discrete = 1 writes;
+ *       every other column: actions = 0.0f, tokens = -1, written on every call.
+ *   - Sampling: the Philox counter stays (slot_base + s, j, d), so a slot of a mixed batch draws what the same slot of a
+ *     homogeneous batch draws.  Armed with top_k > n_discrete while the table holds a discrete slot: the call fails (as a
+ *     discrete = 1 call does).
+ *   - discrete = LRAM_HEAD_PER_SLOT is accepted by lram_step, lram_step_images and lram_prefill (head of the last timestep) and
+ *     fails without a table.  In graph mode it is one more value of the captured step's key.
+ *   - Together with the Mamba repeated-forward mode (lram_set_compat_mode, mamba_repeat > 1) it is refused: the reference
+ *     advances the state env_act_dim times there (src/algos/decision_mamba.py:107-122), which differs per slot and is not a
+ *     batchable trajectory.
+ * lram_get_slot_table copies the table in effect back (any pointer may be NULL) and fails when none is set. */
+int32_t lram_set_slot_table(lram_engine* e, const uint8_t* host_flags, const uint8_t* host_act_dim);
+int32_t lram_get_slot_table(lram_engine* e, uint8_t* host_flags, uint8_t* host_act_dim, int32_t* n_image_slots);
+
+/* One env-step of a mixed batch: per slot the observation is a vector or a frame and the head is continuous or discrete, as the
+ * slot table says -- the batched form of the reference's forward, which embeds `states` through embed_state or embed_image
+ * depending on the env (online_decision_transformer_model.py:463-530) and reads the head as the env's kind asks
+ * (multi_domain_discrete_dt_model.py:83-108).
+ *   dev_obs    device float[batch, state_dim]: rows of image slots are never used (any bit pattern); NULL when every slot is
+ *              an image slot
+ *   dev_images device uint8[n_image_slots, C, H, W]: frame k belongs to the k-th image slot in ascending slot order (NULL if
+ *              the table holds none)
+ * Other arguments as lram_step; the head mode is per slot.  Per env slice and on the slice's stream: the state Linear over the
+ * slice's rows, the IMPALA CNN over the slice's frames (a contiguous range), and a scatter of the CNN rows into the image
+ * slots' state tokens; a slice without image slots launches no CNN.  Runs launch-per-kernel also in graph mode (a captured
+ * step would pin the frame buffer, as in lram_step_images).  Fails without a table. */
+int32_t lram_step_slots(lram_engine* e, const float* dev_obs, const uint8_t* dev_images, int32_t channels, int32_t height,
+                        int32_t width, const float* dev_rtg, const float* dev_reward, const uint8_t* dev_reset_mask,
+                        float* dev_actions, int32_t* dev_tokens, void* stream);
+
 /* Observation front end on the device: native obs [batch, n_native] -> model input [batch, state_dim].
  * dev_inv_index == NULL: zero-pad (DecisionXLSTM.pad_inputs, src/algos/decision_xlstm.py:16-19); otherwise
  * int32[state_dim] giving, per output dim, the native column it is filled from or -1 (DMControl full-space
@@ -363,6 +413,14 @@ int32_t lram_step_images(lram_engine* e, const uint8_t* dev_images, int32_t chan
  * normalisation (x - mean) / std over the padded vector (src/algos/decision_transformer_sb3.py:650-651). */
 int32_t lram_pad_obs(const float* dev_native, int32_t n_native, const int32_t* dev_inv_index, const float* dev_mean,
                      const float* dev_std, float* dev_out, int32_t batch, int32_t state_dim, void* stream);
+
+/* lram_pad_obs with one index / mean / std row per slot: tables [n_rows, state_dim] (dev_inv_index NULL: zero-pad for every
+ * slot), dev_slot_row int32[batch] in 0 .. n_rows - 1 (a slot with any other value gets zeros).  One batch of envs whose
+ * domains map their observations differently (a Meta-World zero-pad beside the DMControl full-space mapping,
+ * src/envs/dmcontrol_utils.py:35-59).  With n_rows = 1 and dev_slot_row all zero it equals lram_pad_obs bit for bit. */
+int32_t lram_pad_obs_slots(const float* dev_native, int32_t n_native, const int32_t* dev_slot_row, const int32_t* dev_inv_index,
+                           const float* dev_mean, const float* dev_std, int32_t n_rows, float* dev_out, int32_t batch,
+                           int32_t state_dim, void* stream);
 
 /* Diagnostic: runs the mLSTM front-end kernel beside a bf16x3 GEMM on a second stream `iters` times and counts
  * output elements that differ from a solo run (must be 0; see lram_amd/csrc/selftest.hip for the gfx950

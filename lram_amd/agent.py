@@ -75,8 +75,22 @@ class RecurrentAgent:
                  graph: bool = False, reprime_context: bool = False, persist_context: bool = False,
                  compat_mamba_repeat: bool = False,
                  compat_stale_state: bool = False,
-                 a_sample_kwargs: Optional[dict] = None, sample_seed: int = 0, sample_slot_base: int = 0):
+                 a_sample_kwargs: Optional[dict] = None, sample_seed: int = 0, sample_slot_base: int = 0,
+                 slot_table=None):
         self.spec = spec
+        # slot_table (lram_amd.domains.SlotTable): the batch holds envs of several domains -- head mode, action dims and
+        # observation kind per env slot (the reference passes `env_act_dim` / `is_discrete` per call for its one env,
+        # src/callbacks/evaluation.py:90-138).  predict_batch then takes (vector_obs, images) and every slot gets its own head.
+        self.slot_table = slot_table
+        if slot_table is not None:
+            if slot_table.n_slots != n_envs:
+                raise ValueError(f"slot_table lays out {slot_table.n_slots} env slots, the agent has n_envs = {n_envs}")
+            if int(slot_table.act_dim.max()) > spec.act_dim:
+                raise ValueError(f"slot_table: a domain uses {int(slot_table.act_dim.max())} action dims, the model has {spec.act_dim}")
+            if compat_mamba_repeat:
+                raise ValueError("compat_mamba_repeat advances the state once per action dim of the env; that differs per "
+                                 "slot of a mixed batch and cannot be combined with slot_table")
+            discrete = False
         # a_sample_kwargs (src/algos/discrete_decision_transformer_sb3.py:8-11): None = argmax actions, today's behaviour;
         # a dict = actions drawn on the device (Engine.set_sampling), with sample_from_logits' keyword names and defaults
         # (src/algos/models/model_utils.py:7).  `deterministic` is accepted and ignored by predict / get_action_pred, as in
@@ -84,7 +98,8 @@ class RecurrentAgent:
         # Not given here: what the configuration set (agent_params.a_sample_kwargs -> ModelSpec.a_sample_kwargs; no preset does).
         if a_sample_kwargs is None:
             a_sample_kwargs = spec.a_sample_kwargs
-        self.a_sample_kwargs = resolve_sample_kwargs(a_sample_kwargs, spec.n_discrete if discrete else spec.n_vocab)
+        any_discrete = discrete if slot_table is None else bool(slot_table.discrete.any())
+        self.a_sample_kwargs = resolve_sample_kwargs(a_sample_kwargs, spec.n_discrete if any_discrete else spec.n_vocab)
         self.sample_seed, self.sample_slot_base = int(sample_seed), int(sample_slot_base)
         # host copy of the weights: lets the agent cross a process boundary (make_pickleable / reinit_cuda_kernels)
         self._state_dict = {k: v.detach().to("cpu") for k, v in state_dict.items()}
@@ -130,6 +145,18 @@ class RecurrentAgent:
         if self.compat_stale_state:
             self.engine.set_compat_mode(1, True)
         self._arm_sampling()
+        self._apply_slot_table()
+
+    def _apply_slot_table(self):
+        if getattr(self, "slot_table", None) is not None:
+            self.engine.set_slot_table(*self.slot_table.engine_arrays())
+
+    @property
+    def slot_is_discrete(self) -> torch.Tensor:
+        """bool [n_envs]: which env slots read the discrete head (every slot, or none, without a slot table)."""
+        if getattr(self, "slot_table", None) is not None:
+            return self.slot_table.discrete.clone()
+        return torch.full((self.n_envs,), self.is_discrete, dtype=torch.bool)
 
     def _arm_sampling(self):
         if self.a_sample_kwargs is not None:
@@ -173,6 +200,7 @@ class RecurrentAgent:
             if self.compat_stale_state or self._compat_repeat_now != 1:
                 self.engine.set_compat_mode(self._compat_repeat_now, self.compat_stale_state)
             self._arm_sampling()
+            self._apply_slot_table()
 
     def __getstate__(self):
         d = dict(self.__dict__)
@@ -187,9 +215,17 @@ class RecurrentAgent:
         self.inference_params = _InferenceParams(self)
 
     def compute_target_return_val(self, env=None, task_id=0):
+        """Target return in model units (already divided by the reward scale).  With a slot table: of the domain `task_id`
+        names -- a domain name or its position in the table (decision_transformer_sb3.py:542-559 looks it up per task)."""
+        if getattr(self, "slot_table", None) is not None and task_id is not None:
+            dom = self.slot_table.find(task_id)
+            return float(dom.target_return) / float(dom.reward_scale)
         return self.target_return
 
     def get_reward_scale_for_env(self, envid=None):
+        """With a slot table: the reward scale of the domain `envid` names (decision_transformer_sb3.py:373-382)."""
+        if getattr(self, "slot_table", None) is not None and envid is not None:
+            return float(self.slot_table.find(envid).reward_scale)
         return self.reward_scale
 
     # ---- native batched entry ---------------------------------------------------------------------
@@ -217,7 +253,13 @@ class RecurrentAgent:
                       env_act_dim: Optional[int] = None) -> torch.Tensor:
         """observation [B, obs_dim] (or uint8 [B,3,64,64]), returns_to_go [B] -> actions [B, env_act_dim]
         (float32; for discrete agents int64 [B, 1]).  The returned tensor is a view of an engine-owned
-        buffer that the next call overwrites."""
+        buffer that the next call overwrites.
+        With a slot table `observation` is the pair (vector_obs [B, obs_dim] or None, images uint8 [n_image, C, H, W] or None):
+        rows of vector_obs that belong to image slots are never read, frame k belongs to the k-th image slot.  Returns float32
+        [B, act_dim]: a continuous slot's action in the columns below its act_dim, a discrete slot's index in column 0 (exact in
+        fp32), 0.0 elsewhere; `env_act_dim` is ignored."""
+        if getattr(self, "slot_table", None) is not None:
+            return self._predict_batch_slots(observation, returns_to_go, rewards, reset_mask)
         images = observation.dim() == 4
         if images:   # frames go to the engine as they are: lram_step_images runs the CNN inside the step (per env slice)
             if not self.has_image_encoder:
@@ -242,6 +284,33 @@ class RecurrentAgent:
         if self.is_discrete:
             return actions[:, :1].to(torch.int64)
         return actions if env_act_dim is None else actions[:, :env_act_dim]
+
+    def _predict_batch_slots(self, observation, returns_to_go, rewards, reset_mask):
+        if not isinstance(observation, (tuple, list)) or len(observation) != 2:
+            raise ValueError("with a slot table predict_batch takes observation = (vector_obs, images)")
+        vec, images = observation
+        n_img = self.slot_table.n_image
+        if n_img > 0:
+            if not self.has_image_encoder:
+                raise RuntimeError("the slot table holds image slots but the state dict has no embed_image.* weights")
+            if images is None or images.dim() != 4 or images.shape[0] != n_img:
+                raise ValueError(f"images: expected uint8 [{n_img}, C, H, W] (one frame per image slot, in slot order)")
+            images = images.to(self.device).to(torch.uint8).contiguous()
+        else:
+            images = None
+        if vec is None:
+            if n_img != self.n_envs:
+                raise ValueError("vector_obs: None is allowed only when every slot is an image slot")
+        else:
+            if vec.dim() != 2 or vec.shape[0] != self.n_envs:
+                raise ValueError(f"vector_obs: expected [{self.n_envs}, obs_dim]")
+            vec, _ = self._prepare_obs(vec)
+        rtg = returns_to_go.to(self.device, torch.float32).reshape(-1).contiguous()
+        rew = self._zero_reward if rewards is None else rewards.to(self.device, torch.float32).reshape(-1).contiguous()
+        if reset_mask is not None:
+            reset_mask = reset_mask.to(self.device, torch.uint8).contiguous()
+        actions, _ = self.engine.step_slots(vec, images, rtg, rew, reset_mask)
+        return actions
 
     # ---- reference single-env surface -------------------------------------------------------------
     @torch.no_grad()

@@ -226,13 +226,17 @@ void launch_embed_scalars(float* x, const float* rtg, const float* rew, int64_t 
                           hipStream_t stream);
 // copy caller-provided state embeddings [B,D] into token slot 0 of x [B,T,D]
 void launch_scatter_token0(float* x, const float* emb, int64_t emb_stride, int B, int T, int D, hipStream_t stream);
+// compact row k of emb [n, D] -> token row 0 of env slot slot[k] (slot numbers of the whole batch x [B, T, D])
+void launch_scatter_token0_indexed(float* x, const float* emb, const int32_t* slot, int n, int B, int T, int D,
+                                   hipStream_t stream);
 void launch_embed_chunk(float* x, const float* emb, int64_t emb_stride, const float* rtg, const float* rew, int64_t in_stride,
                         const float* w_rtg, const float* b_rtg, const float* w_rew, const float* b_rew, int B, int steps, int T,
                         int D, hipStream_t stream);
 // argmax over logits [B, act_dim*n_vocab] (+ de-tokenise)
 void launch_action_argmax(const float* logits, float* actions, int32_t* tokens, int B, int act_dim, int n_vocab,
                           int n_discrete, int action_channels, float tok_min, float tok_max, int discrete,
-                          int col_begin, hipStream_t stream, int col_end = -1);
+                          int col_begin, hipStream_t stream, int col_end = -1, const uint8_t* slot_flags = nullptr,
+                          const uint8_t* slot_act = nullptr);   // slot table [B] + [B]: head mode / dims in use per env slot
 // The sampling mode of the same head (sample_kernels.hip): the token is drawn from the row instead of being its argmax.
 constexpr int kSampleMaxRow = 512;  // logits per row the sampling kernels hold in registers (8 per lane)
 struct SampleArgs {
@@ -245,7 +249,8 @@ struct SampleArgs {
 };
 void launch_action_sample(const float* logits, float* actions, int32_t* tokens, int B, int act_dim, int n_vocab,
                           int n_discrete, int action_channels, float tok_min, float tok_max, int discrete, int col_begin,
-                          int col_end, const SampleArgs& sp, hipStream_t stream);
+                          int col_end, const SampleArgs& sp, hipStream_t stream, const uint8_t* slot_flags = nullptr,
+                          const uint8_t* slot_act = nullptr);
 void launch_sample_advance(uint64_t* draw, hipStream_t stream);  // ++*draw, one thread
 // rows of n logits at logits + r * ld (ld = 0: every row is row 0), one caller uniform per row -> tokens[rows]
 void launch_sample_tokens(const float* logits, int64_t rows, int n, int64_t ld, double temperature, int top_k, double top_p,
@@ -511,6 +516,9 @@ void launch_relu(float* x, int64_t n, hipStream_t stream);
 // misc
 void launch_pad_obs(const float* native, int n_native, const int32_t* inv_index, const float* mean, const float* stdv,
                     float* out, int B, int state_dim, hipStream_t stream);
+void launch_pad_obs_slots(const float* native, int n_native, const int32_t* slot_row, const int32_t* inv_index,
+                          const float* mean, const float* stdv, int n_rows, float* out, int B, int state_dim,
+                          hipStream_t stream);
 void launch_stream_copy(float* dst, const float* src, size_t numel, hipStream_t stream);
 void launch_stream_read(const float* buf, size_t numel, float* sink, hipStream_t stream);  // read only; sink: 1024 floats
 void launch_stream_rmw(float* buf, size_t numel, hipStream_t stream);  // in place, the cell kernel's access pattern

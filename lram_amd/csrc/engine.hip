@@ -154,6 +154,17 @@ struct lram_engine {
   // (206M, 512 slots, same box: two calls 31.03k env-steps/s; one call with 2 / 5 / 8 / 11 / 14 folds ahead 31.36k / 31.68k / 31.81k /
   // 31.65k / 31.31k; the second slice's CNN held back until the first slice's is done: 31.4k -- not kept)
   static constexpr int fold_bubbles_images = 8;
+  // Slot table (lram_set_slot_table): head mode, action dims in use and observation kind per env slot.  Host copy + device
+  // copy; the ascending list of image slots (frame k belongs to slot_img_list[k]) and its prefix counts give every env slice
+  // its contiguous range of frames.  step_slots: the env-step under way is a lram_step_slots call (mixed front end).
+  bool slot_table = false;
+  std::vector<uint8_t> slot_flags, slot_act;   // host [B] each
+  std::vector<int32_t> slot_img_prefix;        // host [B + 1]: image slots below slot b
+  uint8_t* slot_dev = nullptr;                 // device [2][B]: flags, act_dim
+  int32_t* slot_img_list = nullptr;            // device [n_image_slots]
+  int slot_n_image = 0;
+  bool slot_has_discrete = false;
+  bool step_slots = false;
   size_t img_cap = 0;  // batch * input pixels the image buffers were sized for
   // lazy matrix memory: C_base read once per step, rewritten once per `lazy_period` steps (see mlstm_lazy.hip)
   int lazy_mode = 2;        // 0 materialised, 1 lazy, 2 auto (LRAM_STATE / lram_set_state_mode)
@@ -259,6 +270,14 @@ struct lram_engine {
     drop_splits();
     release_state();
     if (sample_draw) (void)hipFree(sample_draw);
+    drop_slot_table();
+  }
+  void drop_slot_table() {
+    if (slot_dev) (void)hipFree(slot_dev);
+    if (slot_img_list) (void)hipFree(slot_img_list);
+    slot_dev = nullptr, slot_img_list = nullptr;
+    slot_flags.clear(), slot_act.clear(), slot_img_prefix.clear();
+    slot_n_image = 0, slot_has_discrete = false, slot_table = false;
   }
   void drop_splits() {
     for (auto& kv : split) (void)hipFree(kv.second.p);
@@ -783,6 +802,7 @@ void state_alloc(lram_engine* e, int B) {
   LRAM_HIP_CHECK(hipSetDevice(e->device));
   e->drop_graph();
   e->release_state();
+  e->drop_slot_table();   // the table describes the slots of one allocation
   const lram_config& c = e->cfg;
   const size_t D = c.d_model;
   e->st.resize(c.n_blocks);
@@ -1802,13 +1822,29 @@ void timesteps_launches(lram_engine* e, const float* obs, int emb, const float* 
         launch_row_norm(X, D, X, D, e->eln_g, e->eln_b, x.nb * Tc, D, 1e-5f, 0, x.s);
         continue;
       }
-      if (e->step_images != nullptr)   // lram_step_images: this slice's frames -> its rows of `obs` (= IMG_EMB), on its own stream
+      // lram_step_slots: the slice's frames are the contiguous range [k0, k0 + nk) of the call's frames (frames come in slot
+      // order); they go through the CNN into compact rows of IMG_EMB, every slice in its own region of the CNN work buffers
+      const int k0 = e->step_slots ? e->slot_img_prefix[b0] : 0;
+      const int nk = e->step_slots ? e->slot_img_prefix[b0 + x.nb] - k0 : 0;
+      if (e->step_slots) {
+        if (nk > 0)
+          embed_images(e, e->step_images + (size_t)k0 * e->step_img_c * e->step_img_h * e->step_img_w, e->step_img_c,
+                       e->step_img_h, e->step_img_w, e->IMG_EMB.p + (size_t)k0 * D, x.s, k0, nk);
+      } else if (e->step_images != nullptr)   // lram_step_images: this slice's frames -> its rows of `obs` (= IMG_EMB), on its own stream
         embed_images(e, e->step_images + b0 * e->step_img_c * e->step_img_h * e->step_img_w, e->step_img_c, e->step_img_h,
                      e->step_img_w, e->IMG_EMB.p + b0 * D, x.s, (int)b0, x.nb);
       for (int j = 0; j < Lc; ++j) {
         const float* o = obs + (b0 * L + l + j) * obs_w;
         float* Xj = X + (size_t)(T * j) * D;  // token slots 3j .. 3j+2 of every env row group
-        if (emb) {
+        if (e->step_slots) {   // (L == 1) state Linear over the slice's rows, then the image slots' token 0 from the CNN rows
+          if (nk < x.nb) {
+            GemmArgs ge;
+            ge.a = o, ge.lda = c.state_dim, ge.w = e->w_state, ge.ldw = c.state_dim, ge.c = Xj;
+            ge.ldc = (int64_t)Tc * D, ge.bias = e->b_state, ge.m = x.nb, ge.n = D, ge.k = c.state_dim;
+            gemm(e, ge, x.s);
+          }
+          launch_scatter_token0_indexed(e->X.p, e->IMG_EMB.p + (size_t)k0 * D, e->slot_img_list + k0, nk, e->B, Tc, D, x.s);
+        } else if (emb) {
           launch_scatter_token0(Xj, o, (int64_t)L * D, x.nb, Tc, D, x.s);
         } else {
           GemmArgs ge;
@@ -1842,8 +1878,16 @@ void timesteps_launches(lram_engine* e, const float* obs, int emb, const float* 
     // the head evaluates that column block of action_net alone
     const int col_end = (shared_passes > 1 && col_begin + 1 < shared_passes) ? col_begin + 1 : c.act_dim;
     const int col0 = shared_passes > 1 ? col_begin : 0;
+    const bool per_slot = discrete == LRAM_HEAD_PER_SLOT;
+    if (per_slot) {
+      LRAM_REQUIRE(e->slot_table, "LRAM_HEAD_PER_SLOT: no slot table is set (lram_set_slot_table)");
+      LRAM_REQUIRE(!(e->sampling && e->slot_has_discrete && e->sample.top_k > c.n_discrete),
+                   "action sampling: top_k exceeds n_discrete and the slot table holds a discrete slot");
+    }
     for (const Slice& x : sl) {
       const size_t r0 = (size_t)x.b0 * Tc, b0 = x.b0;
+      const uint8_t* sf = per_slot ? e->slot_dev + b0 : nullptr;
+      const uint8_t* sa = per_slot ? e->slot_dev + e->B + b0 : nullptr;
       GemmArgs gh;
       gh.a = e->HID.p + (r0 + pred) * D, gh.lda = (int64_t)Tc * D, gh.w = e->w_head + (size_t)col0 * c.n_vocab * D, gh.ldw = D;
       gh.c = e->LOGITS.p + b0 * nlog + (size_t)col0 * c.n_vocab, gh.ldc = nlog, gh.bias = e->b_head + (size_t)col0 * c.n_vocab;
@@ -1854,12 +1898,12 @@ void timesteps_launches(lram_engine* e, const float* obs, int emb, const float* 
         sp.slot0 += b0, sp.draw = e->sample_draw;
         launch_action_sample(e->LOGITS.p + b0 * nlog, actions + b0 * c.act_dim, tokens ? tokens + b0 * c.act_dim : nullptr,
                              x.nb, c.act_dim, c.n_vocab, c.n_discrete, c.action_channels, c.tok_min, c.tok_max, discrete,
-                             col_begin, col_end, sp, x.s);
+                             col_begin, col_end, sp, x.s, sf, sa);
         continue;
       }
       launch_action_argmax(e->LOGITS.p + b0 * nlog, actions + b0 * c.act_dim,
                            tokens ? tokens + b0 * c.act_dim : nullptr, x.nb, c.act_dim, c.n_vocab, c.n_discrete,
-                           c.action_channels, c.tok_min, c.tok_max, discrete, col_begin, x.s, col_end);
+                           c.action_channels, c.tok_min, c.tok_max, discrete, col_begin, x.s, col_end, sf, sa);
     }
   }
   if (multi && (fork_join & 2)) join_slices(e, sl, hbm, s);
@@ -1870,6 +1914,18 @@ void timesteps_launches(lram_engine* e, const float* obs, int emb, const float* 
 // slices fork from this stream and see the new one.  In a captured step it is one more node on the graph's single chain.
 void sample_draw_advance(lram_engine* e, hipStream_t s) {
   if (e->sampling) launch_sample_advance(e->sample_draw, s);
+}
+
+// discrete = LRAM_HEAD_PER_SLOT: what the call needs, checked before anything is launched (the recurrent state is untouched
+// by a refused call).
+void check_head_mode(const lram_engine* e, int discrete, const char* who) {
+  if (discrete != LRAM_HEAD_PER_SLOT) return;
+  const std::string w(who);
+  LRAM_REQUIRE(e->slot_table, w + ": LRAM_HEAD_PER_SLOT needs a slot table (lram_set_slot_table)");
+  LRAM_REQUIRE(e->compat_repeat <= 1, w + ": LRAM_HEAD_PER_SLOT cannot be combined with the Mamba repeated-forward mode "
+                                          "(mamba_repeat > 1 advances the state once per action dim of the env, which differs per slot)");
+  LRAM_REQUIRE(!(e->sampling && e->slot_has_discrete && e->sample.top_k > e->cfg.n_discrete),
+               w + ": sampling top_k exceeds n_discrete and the slot table holds a discrete slot");
 }
 
 // Do the repeated forwards of the Mamba reference-trajectory mode share the token front end and layer 0's in_proj?
@@ -2083,6 +2139,7 @@ int32_t lram_step(lram_engine* e, const float* dev_obs, int32_t obs_is_embedding
     LRAM_REQUIRE(e && e->B > 0, "lram_step: state not allocated (call lram_state_alloc)");
     LRAM_REQUIRE(dev_obs && dev_rtg && dev_reward && dev_actions, "lram_step: null device pointer");
     LRAM_REQUIRE(e->cfg.tokens_per_step == 3, "lram_step: the (state, rtg, reward) front end needs tokens_per_step == 3");
+    check_head_mode(e, discrete, "lram_step");
     LRAM_HIP_CHECK(hipSetDevice(e->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     compat_prepare(e, discrete);  // (workspace of the shared repeated forwards: outside any capture)
@@ -2127,6 +2184,7 @@ int32_t lram_step_images(lram_engine* e, const uint8_t* dev_images, int32_t chan
                  "lram_step_images: bad argument");
     LRAM_REQUIRE(e->cfg.tokens_per_step == 3, "lram_step_images: the (state, rtg, reward) front end needs tokens_per_step == 3");
     LRAM_REQUIRE(e->img_lin_w != nullptr, "lram_step_images: no embed_image.* weights were uploaded");
+    check_head_mode(e, discrete, "lram_step_images");
     LRAM_HIP_CHECK(hipSetDevice(e->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     image_buffers(e, height, width);
@@ -2146,6 +2204,100 @@ int32_t lram_step_images(lram_engine* e, const uint8_t* dev_images, int32_t chan
   });
 }
 
+int32_t lram_set_slot_table(lram_engine* e, const uint8_t* host_flags, const uint8_t* host_act_dim) {
+  return guarded([&] {
+    LRAM_REQUIRE(e && e->B > 0, "lram_set_slot_table: state not allocated (call lram_state_alloc)");
+    LRAM_REQUIRE((host_flags == nullptr) == (host_act_dim == nullptr), "lram_set_slot_table: flags and act_dim go together");
+    const int B = e->B;
+    const lram_config& c = e->cfg;
+    int n_img = 0;
+    bool has_discrete = false;
+    if (host_flags != nullptr) {  // validate before anything changes: a refused table leaves the one in effect as it is
+      for (int b = 0; b < B; ++b) {
+        const int f = host_flags[b], a = host_act_dim[b];
+        const std::string at = " (slot " + std::to_string(b) + ")";
+        LRAM_REQUIRE((f & ~(LRAM_SLOT_DISCRETE | LRAM_SLOT_IMAGE)) == 0, "lram_set_slot_table: unknown flag bit" + at);
+        LRAM_REQUIRE(a >= 1 && a <= c.act_dim, "lram_set_slot_table: act_dim must be in 1 .. cfg.act_dim" + at);
+        if (f & LRAM_SLOT_DISCRETE) {
+          LRAM_REQUIRE(a == 1, "lram_set_slot_table: a discrete slot has act_dim 1" + at);
+          LRAM_REQUIRE(c.n_discrete > 0, "lram_set_slot_table: a discrete slot needs n_discrete > 0" + at);
+          has_discrete = true;
+        }
+        n_img += (f & LRAM_SLOT_IMAGE) ? 1 : 0;
+      }
+    }
+    LRAM_HIP_CHECK(hipSetDevice(e->device));
+    LRAM_HIP_CHECK(hipDeviceSynchronize());  // steps in flight read the table they were launched with
+    e->drop_graph();                         // the head launch and its table pointers are part of a captured step
+    if (host_flags == nullptr) {
+      e->drop_slot_table();
+      return;
+    }
+    if (!e->slot_dev) LRAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->slot_dev), 2 * (size_t)B));
+    if (!e->slot_img_list) LRAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->slot_img_list), sizeof(int32_t) * (size_t)B));
+    e->slot_flags.assign(host_flags, host_flags + B);
+    e->slot_act.assign(host_act_dim, host_act_dim + B);
+    e->slot_img_prefix.assign(B + 1, 0);
+    std::vector<int32_t> list;
+    list.reserve(n_img);
+    for (int b = 0; b < B; ++b) {
+      const bool img = (host_flags[b] & LRAM_SLOT_IMAGE) != 0;
+      if (img) list.push_back(b);
+      e->slot_img_prefix[b + 1] = e->slot_img_prefix[b] + (img ? 1 : 0);
+    }
+    LRAM_HIP_CHECK(hipMemcpy(e->slot_dev, host_flags, B, hipMemcpyHostToDevice));
+    LRAM_HIP_CHECK(hipMemcpy(e->slot_dev + B, host_act_dim, B, hipMemcpyHostToDevice));
+    if (n_img > 0) LRAM_HIP_CHECK(hipMemcpy(e->slot_img_list, list.data(), sizeof(int32_t) * n_img, hipMemcpyHostToDevice));
+    LRAM_HIP_CHECK(hipDeviceSynchronize());
+    e->slot_n_image = n_img, e->slot_has_discrete = has_discrete, e->slot_table = true;
+  });
+}
+
+int32_t lram_get_slot_table(lram_engine* e, uint8_t* host_flags, uint8_t* host_act_dim, int32_t* n_image_slots) {
+  return guarded([&] {
+    LRAM_REQUIRE(e && e->B > 0, "lram_get_slot_table: state not allocated (call lram_state_alloc)");
+    LRAM_REQUIRE(e->slot_table, "lram_get_slot_table: no slot table is set");
+    if (host_flags) std::memcpy(host_flags, e->slot_flags.data(), e->B);
+    if (host_act_dim) std::memcpy(host_act_dim, e->slot_act.data(), e->B);
+    if (n_image_slots) *n_image_slots = e->slot_n_image;
+  });
+}
+
+int32_t lram_step_slots(lram_engine* e, const float* dev_obs, const uint8_t* dev_images, int32_t channels, int32_t height,
+                        int32_t width, const float* dev_rtg, const float* dev_reward, const uint8_t* dev_reset_mask,
+                        float* dev_actions, int32_t* dev_tokens, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(e && e->B > 0, "lram_step_slots: state not allocated (call lram_state_alloc)");
+    LRAM_REQUIRE(e->slot_table, "lram_step_slots: no slot table is set (lram_set_slot_table)");
+    const int n_img = e->slot_n_image;
+    LRAM_REQUIRE(dev_rtg && dev_reward && dev_actions, "lram_step_slots: null device pointer");
+    LRAM_REQUIRE(dev_obs != nullptr || n_img == e->B, "lram_step_slots: dev_obs is NULL and the table holds vector slots");
+    LRAM_REQUIRE(e->cfg.tokens_per_step == 3, "lram_step_slots: the (state, rtg, reward) front end needs tokens_per_step == 3");
+    check_head_mode(e, LRAM_HEAD_PER_SLOT, "lram_step_slots");
+    LRAM_HIP_CHECK(hipSetDevice(e->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n_img > 0) {
+      LRAM_REQUIRE(e->img_lin_w != nullptr, "lram_step_slots: the table holds image slots and no embed_image.* weights were uploaded");
+      LRAM_REQUIRE(dev_images && channels > 0 && height > 0 && width > 0, "lram_step_slots: the table holds image slots: frames needed");
+      LRAM_REQUIRE(e->cfg.d_model % 4 == 0, "lram_step_slots: image slots need d_model to be a multiple of 4");
+      image_buffers(e, height, width);
+      if (e->IMG_EMB.n < (size_t)e->B * e->cfg.d_model) {
+        LRAM_HIP_CHECK(hipDeviceSynchronize());
+        e->IMG_EMB.alloc((size_t)e->B * e->cfg.d_model);
+      }
+    }
+    prof_tick(e);
+    struct Scope {   // (the frames and the mixed front end belong to this call only)
+      lram_engine* e;
+      ~Scope() { e->step_images = nullptr, e->step_slots = false; }
+    } scope{e};
+    e->step_slots = true;
+    e->step_images = n_img > 0 ? dev_images : nullptr, e->step_img_c = channels, e->step_img_h = height, e->step_img_w = width;
+    // (launch-per-kernel path also in graph mode: a captured step would pin one frame buffer, as in lram_step_images)
+    step_launches(e, dev_obs, 0, dev_rtg, dev_reward, dev_reset_mask, LRAM_HEAD_PER_SLOT, dev_actions, dev_tokens, s);
+  });
+}
+
 int32_t lram_prefill(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
                      const float* dev_reward_seq, int32_t timesteps, const uint8_t* dev_reset_mask, int32_t discrete,
                      float* dev_actions, int32_t* dev_tokens, void* stream) {
@@ -2154,6 +2306,7 @@ int32_t lram_prefill(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_em
     LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_prefill: null device pointer");
     LRAM_REQUIRE(timesteps >= 1, "lram_prefill: timesteps must be >= 1");
     LRAM_REQUIRE(e->cfg.tokens_per_step == 3, "lram_prefill: the (state, rtg, reward) front end needs tokens_per_step == 3");
+    if (dev_actions != nullptr) check_head_mode(e, discrete, "lram_prefill");
     LRAM_HIP_CHECK(hipSetDevice(e->device));
     prof_tick(e);
     timesteps_launches(e, dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps, dev_reset_mask, discrete,
@@ -2656,6 +2809,19 @@ int32_t lram_pad_obs(const float* dev_native, int32_t n_native, const int32_t* d
     LRAM_REQUIRE((dev_mean == nullptr) == (dev_std == nullptr), "lram_pad_obs: mean and std go together");
     launch_pad_obs(dev_native, n_native, dev_inv_index, dev_mean, dev_std, dev_out, batch, state_dim,
                    static_cast<hipStream_t>(stream));
+  });
+}
+
+int32_t lram_pad_obs_slots(const float* dev_native, int32_t n_native, const int32_t* dev_slot_row, const int32_t* dev_inv_index,
+                           const float* dev_mean, const float* dev_std, int32_t n_rows, float* dev_out, int32_t batch,
+                           int32_t state_dim, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(dev_native && dev_out && dev_slot_row && batch > 0 && state_dim > 0 && n_native > 0 && n_rows > 0,
+                 "lram_pad_obs_slots: bad argument");
+    LRAM_REQUIRE(dev_inv_index != nullptr || n_native <= state_dim, "lram_pad_obs_slots: observation wider than state_dim");
+    LRAM_REQUIRE((dev_mean == nullptr) == (dev_std == nullptr), "lram_pad_obs_slots: mean and std go together");
+    launch_pad_obs_slots(dev_native, n_native, dev_slot_row, dev_inv_index, dev_mean, dev_std, n_rows, dev_out, batch,
+                         state_dim, static_cast<hipStream_t>(stream));
   });
 }
 

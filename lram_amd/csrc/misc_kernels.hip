@@ -182,6 +182,20 @@ __global__ __launch_bounds__(256) void scatter_token0_kernel(float* x, const flo
   x[(int64_t)b * T * D + d] = emb[(int64_t)b * emb_stride + d];
 }
 
+// Mixed batches (lram_step_slots): compact embedding row k -> token row 0 of env slot slot[k] (global slot numbers, x is the
+// whole batch's token buffer).  float4 rows; the lanes of a row share one index load.
+__global__ __launch_bounds__(256) void scatter_token0_indexed_kernel(float* x, const float* emb, const int32_t* slot, int n,
+                                                                     int B, int T, int D) {
+  const int d4 = D >> 2;
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (int64_t)n * d4) return;
+  const int k = (int)(gid / d4);
+  const int d = (int)(gid - (int64_t)k * d4) << 2;
+  const int b = slot[k];
+  if (b < 0 || b >= B) return;  // (the list is built by lram_set_slot_table from a validated table)
+  *reinterpret_cast<float4*>(x + (int64_t)b * T * D + d) = *reinterpret_cast<const float4*>(emb + (int64_t)k * D + d);
+}
+
 // The (state, rtg, reward) token rows of `steps` consecutive timesteps of every env in one launch (stored contexts): token 0 from the
 // state embeddings emb[b][j][:] (a GEMM over all timesteps, or the caller's own embeddings), tokens 1 / 2 as embed_scalars_kernel.
 __global__ __launch_bounds__(256) void embed_chunk_kernel(float* x, const float* emb, int64_t emb_stride, const float* rtg,
@@ -208,14 +222,25 @@ __global__ __launch_bounds__(256) void embed_chunk_kernel(float* x, const float*
 __global__ __launch_bounds__(256) void action_argmax_kernel(const float* logits, float* actions, int32_t* tokens,
                                                             int B, int act_dim, int n_vocab, int n_discrete,
                                                             int action_channels, float tok_min, float tok_max,
-                                                            int discrete, int col_begin, int col_end) {
+                                                            int discrete, int col_begin, int col_end,
+                                                            const uint8_t* slot_flags, const uint8_t* slot_act) {
   const int lane = threadIdx.x & 63;
   const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int ndim = discrete ? 1 : act_dim;
+  const int ndim = (discrete && slot_flags == nullptr) ? 1 : act_dim;
   if (item >= B * ndim) return;
   const int b = item / ndim, j = item - b * ndim;
   if (j < col_begin || j >= col_end) return;  // repeated-forward mode: pass p writes action dim p, the last pass
                                               // every dim from its own on (engine.hip::step_launches)
+  if (slot_flags != nullptr) {  // slot table (LRAM_HEAD_PER_SLOT): the wave's row decides, so the branch is wave-uniform
+    discrete = slot_flags[b] & 1;
+    if (j >= (int)slot_act[b]) {  // a column the slot does not use: the fill values, on every call
+      if (lane == 0) {
+        if (tokens != nullptr) tokens[(int64_t)b * act_dim + j] = -1;
+        actions[(int64_t)b * act_dim + j] = 0.f;
+      }
+      return;
+    }
+  }
   const float* lg = logits + (int64_t)b * act_dim * n_vocab + (int64_t)j * n_vocab;
   const int n = discrete ? n_discrete : n_vocab;
   float best = -INFINITY;
@@ -269,6 +294,32 @@ __global__ __launch_bounds__(256) void pad_obs_kernel(const float* native, int n
     if (src >= 0) v = native[(int64_t)b * n_native + src];
   }
   if (mean != nullptr) v = (v - mean[d]) / stdv[d];
+  out[gid] = v;
+}
+
+// pad_obs_kernel with the index / mean / std row of each env slot taken from slot_row[b] (tables [n_rows, state_dim]): one
+// batch of envs from several domains, each with its own scatter table (a Meta-World zero-pad beside a DMControl mapping).
+__global__ __launch_bounds__(256) void pad_obs_slots_kernel(const float* native, int n_native, const int32_t* slot_row,
+                                                            const int32_t* index, const float* mean, const float* stdv,
+                                                            int n_rows, float* out, int B, int state_dim) {
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (int64_t)B * state_dim) return;
+  const int b = (int)(gid / state_dim);
+  const int d = (int)(gid - (int64_t)b * state_dim);
+  const int r = slot_row[b];
+  float v = 0.f;
+  if (r < 0 || r >= n_rows) {  // no such row: the slot's output is zero (never an out-of-bounds read)
+    out[gid] = v;
+    return;
+  }
+  const int64_t t = (int64_t)r * state_dim + d;
+  if (index == nullptr) {
+    if (d < n_native) v = native[(int64_t)b * n_native + d];
+  } else {
+    const int src = index[t];  // inverse table: source column of output dim d, or -1
+    if (src >= 0 && src < n_native) v = native[(int64_t)b * n_native + src];
+  }
+  if (mean != nullptr) v = (v - mean[t]) / stdv[t];
   out[gid] = v;
 }
 
@@ -382,6 +433,16 @@ void launch_scatter_token0(float* x, const float* emb, int64_t emb_stride, int B
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
+void launch_scatter_token0_indexed(float* x, const float* emb, const int32_t* slot, int n, int B, int T, int D,
+                                   hipStream_t stream) {
+  LRAM_REQUIRE(D % 4 == 0, "indexed token scatter: d_model must be a multiple of 4");
+  if (n <= 0) return;
+  const int64_t items = (int64_t)n * (D >> 2);
+  hipLaunchKernelGGL(scatter_token0_indexed_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, x, emb, slot,
+                     n, B, T, D);
+  LRAM_HIP_CHECK(hipGetLastError());
+}
+
 void launch_embed_chunk(float* x, const float* emb, int64_t emb_stride, const float* rtg, const float* rew, int64_t in_stride,
                         const float* w_rtg, const float* b_rtg, const float* w_rew, const float* b_rew, int B, int steps, int T,
                         int D, hipStream_t stream) {
@@ -394,11 +455,15 @@ void launch_embed_chunk(float* x, const float* emb, int64_t emb_stride, const fl
 
 void launch_action_argmax(const float* logits, float* actions, int32_t* tokens, int B, int act_dim, int n_vocab,
                           int n_discrete, int action_channels, float tok_min, float tok_max, int discrete,
-                          int col_begin, hipStream_t stream, int col_end) {
-  const int items = B * (discrete ? 1 : act_dim);
+                          int col_begin, hipStream_t stream, int col_end, const uint8_t* slot_flags,
+                          const uint8_t* slot_act) {
+  LRAM_REQUIRE((slot_flags == nullptr) == (slot_act == nullptr), "action head: the slot table's two arrays go together");
+  // with a slot table: one wave per (env, action dim) over all act_dim columns, the head mode is read per env slot
+  const int items = B * ((discrete && slot_flags == nullptr) ? 1 : act_dim);
   if (col_end < 0) col_end = act_dim;
   hipLaunchKernelGGL(action_argmax_kernel, dim3((items + 3) / 4), dim3(256), 0, stream, logits, actions, tokens, B,
-                     act_dim, n_vocab, n_discrete, action_channels, tok_min, tok_max, discrete, col_begin, col_end);
+                     act_dim, n_vocab, n_discrete, action_channels, tok_min, tok_max, discrete, col_begin, col_end,
+                     slot_flags, slot_act);
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
@@ -431,6 +496,15 @@ void launch_pad_obs(const float* native, int n_native, const int32_t* inv_index,
   const int64_t n = (int64_t)B * state_dim;
   hipLaunchKernelGGL(pad_obs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, native, n_native,
                      inv_index, mean, stdv, out, B, state_dim);
+  LRAM_HIP_CHECK(hipGetLastError());
+}
+
+void launch_pad_obs_slots(const float* native, int n_native, const int32_t* slot_row, const int32_t* inv_index,
+                          const float* mean, const float* stdv, int n_rows, float* out, int B, int state_dim,
+                          hipStream_t stream) {
+  const int64_t n = (int64_t)B * state_dim;
+  hipLaunchKernelGGL(pad_obs_slots_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, native, n_native,
+                     slot_row, inv_index, mean, stdv, n_rows, out, B, state_dim);
   LRAM_HIP_CHECK(hipGetLastError());
 }
 

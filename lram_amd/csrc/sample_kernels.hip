@@ -218,15 +218,26 @@ template <int PER>
 __global__ __launch_bounds__(256) void action_sample_kernel(const float* logits, float* actions, int32_t* tokens, int B,
                                                             int act_dim, int n_vocab, int n_discrete, int action_channels,
                                                             float tok_min, float tok_max, int discrete, int col_begin,
-                                                            int col_end, SampleArgs sp) {
+                                                            int col_end, SampleArgs sp, const uint8_t* slot_flags,
+                                                            const uint8_t* slot_act) {
   __shared__ float stage[4][64 * PER];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int item = blockIdx.x * 4 + wv;
-  const int ndim = discrete ? 1 : act_dim;
+  const int ndim = (discrete && slot_flags == nullptr) ? 1 : act_dim;
   const int b = item / ndim, j = item - b * ndim;
-  const bool active = item < B * ndim && j >= col_begin && j < col_end;
+  bool active = item < B * ndim && j >= col_begin && j < col_end;
+  bool fill = false;
+  if (active && slot_flags != nullptr) {  // slot table: head mode and dims in use of the wave's env slot (wave-uniform)
+    discrete = slot_flags[b] & 1;
+    fill = j >= (int)slot_act[b];
+    active = !fill;
+  }
   const int n = discrete ? n_discrete : n_vocab;
   stage_row<PER>(stage[wv], logits + (int64_t)b * act_dim * n_vocab + (int64_t)j * n_vocab, n, lane, active);
+  if (fill && lane == 0) {  // a column the slot does not use: the fill values, on every call
+    if (tokens != nullptr) tokens[(int64_t)b * act_dim + j] = -1;
+    actions[(int64_t)b * act_dim + j] = 0.f;
+  }
   if (!active) return;
   const double u = philox_uniform(sp.seed, sp.slot0 + (uint64_t)b, (uint32_t)j, *sp.draw);
   const int tok = sample_row<PER>(stage[wv], n, sp.temperature, sp.top_k, sp.top_p, u, lane);
@@ -276,17 +287,22 @@ __global__ __launch_bounds__(256) void sample_uniforms_kernel(uint64_t seed, uin
 
 void launch_action_sample(const float* logits, float* actions, int32_t* tokens, int B, int act_dim, int n_vocab,
                           int n_discrete, int action_channels, float tok_min, float tok_max, int discrete, int col_begin,
-                          int col_end, const SampleArgs& sp, hipStream_t stream) {
-  const int n = discrete ? n_discrete : n_vocab;
+                          int col_end, const SampleArgs& sp, hipStream_t stream, const uint8_t* slot_flags,
+                          const uint8_t* slot_act) {
+  LRAM_REQUIRE((slot_flags == nullptr) == (slot_act == nullptr), "action sampling: the slot table's two arrays go together");
+  const bool per_slot = slot_flags != nullptr;
+  // with a slot table the rows of one launch differ in length: PER comes from the largest, n_vocab (the engine has checked
+  // top_k against n_discrete where the table holds a discrete slot)
+  const int n = (discrete && !per_slot) ? n_discrete : n_vocab;
   LRAM_REQUIRE(n >= 1 && n <= kSampleMaxRow, "action sampling: a row holds 1 .. 512 logits");
   LRAM_REQUIRE(sp.top_k <= n, "action sampling: top_k exceeds the number of logits of the head in use");
   LRAM_REQUIRE(sp.draw != nullptr, "action sampling: no draw counter");
-  const int items = B * (discrete ? 1 : act_dim);
+  const int items = B * ((discrete && !per_slot) ? 1 : act_dim);
   const dim3 grid((items + 3) / 4), block(256);
   if (col_end < 0) col_end = act_dim;
 #define LRAM_SAMPLE_LAUNCH(PER)                                                                                      \
   hipLaunchKernelGGL(action_sample_kernel<PER>, grid, block, 0, stream, logits, actions, tokens, B, act_dim, n_vocab, \
-                     n_discrete, action_channels, tok_min, tok_max, discrete, col_begin, col_end, sp)
+                     n_discrete, action_channels, tok_min, tok_max, discrete, col_begin, col_end, sp, slot_flags, slot_act)
   if (n <= 64)
     LRAM_SAMPLE_LAUNCH(1);
   else if (n <= 320)

@@ -17,6 +17,9 @@ from .weights import engine_layout
 
 LRAM_ABI_VERSION = 1
 LRAM_MAX_BLOCKS = 64
+LRAM_HEAD_PER_SLOT = 2    # value of `discrete`: head mode per slot, from the slot table
+LRAM_SLOT_DISCRETE = 1    # slot table flag bits
+LRAM_SLOT_IMAGE = 2
 _LIB_NAME = "liblram_hip.so"
 
 
@@ -99,6 +102,12 @@ _SYMBOLS = {
     "lram_stream_rmw": (ctypes.c_int32, [_VP, ctypes.c_size_t, _VP]),
     "lram_stream_read": (ctypes.c_int32, [_VP, ctypes.c_size_t, _VP, _VP]),
     "lram_gemm_counts": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]),
+    "lram_set_slot_table": (ctypes.c_int32, [_VP, _VP, _VP]),
+    "lram_get_slot_table": (ctypes.c_int32, [_VP, _VP, _VP, ctypes.POINTER(ctypes.c_int32)]),
+    "lram_step_slots": (ctypes.c_int32, [_VP, _VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP,
+                                         _VP]),
+    "lram_pad_obs_slots": (ctypes.c_int32, [_VP, ctypes.c_int32, _VP, _VP, _VP, _VP, ctypes.c_int32, _VP, ctypes.c_int32,
+                                            ctypes.c_int32, _VP]),
     "lram_pad_obs": (ctypes.c_int32, [_VP, ctypes.c_int32, _VP, _VP, _VP, _VP, ctypes.c_int32, ctypes.c_int32, _VP]),
     "lram_selftest_concurrent": (ctypes.c_int32, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]),
     "lram_stream_copy": (ctypes.c_int32, [_VP, _VP, ctypes.c_size_t, _VP]),
@@ -177,6 +186,15 @@ def _stream_ptr(device) -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _head_mode(discrete) -> int:
+    """The `discrete` argument of the C ABI: False / True, or "per_slot" (LRAM_HEAD_PER_SLOT: from the slot table)."""
+    if isinstance(discrete, str):
+        if discrete != "per_slot":
+            raise ValueError(f'discrete must be False, True or "per_slot", got {discrete!r}')
+        return LRAM_HEAD_PER_SLOT
+    return int(bool(discrete))
+
+
 def _chk_dev(t: torch.Tensor, dtype, shape, device, name):
     if t.device != device or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
         raise ValueError(f"{name}: expected contiguous {dtype} tensor of shape {tuple(shape)} on {device}, got "
@@ -244,11 +262,12 @@ class Engine:
 
     # -- the hot path ----------------------------------------------------------------------------
     def step(self, obs: torch.Tensor, rtg: torch.Tensor, reward: torch.Tensor,
-             reset_mask: Optional[torch.Tensor] = None, discrete: bool = False, obs_is_embedding: bool = False,
+             reset_mask: Optional[torch.Tensor] = None, discrete=False, obs_is_embedding: bool = False,
              out_actions: Optional[torch.Tensor] = None, out_tokens: Optional[torch.Tensor] = None):
         """One env-step for all slots.  Inputs are device tensors (already resident in HBM).
         Returns (actions float32 [B, act_dim], tokens int32 [B, act_dim]); valid once the current
-        stream has executed.  discrete=True: column 0 holds the action index."""
+        stream has executed.  discrete=True: column 0 holds the action index; discrete="per_slot": the head mode of
+        every slot comes from the slot table (set_slot_table)."""
         B, spec = self.batch, self.spec
         _chk_dev(obs, torch.float32, (B, spec.d_model if obs_is_embedding else spec.state_dim), self.device, "obs")
         _chk_dev(rtg, torch.float32, (B,), self.device, "rtg")
@@ -260,12 +279,91 @@ class Engine:
         _chk_dev(actions, torch.float32, (B, spec.act_dim), self.device, "out_actions")
         _chk_dev(tokens, torch.int32, (B, spec.act_dim), self.device, "out_tokens")
         _check(self.lib, self.lib.lram_step(self._h, _ptr(obs), int(obs_is_embedding), _ptr(rtg), _ptr(reward),
-                                            _ptr(reset_mask), int(discrete), _ptr(actions), _ptr(tokens),
+                                            _ptr(reset_mask), _head_mode(discrete), _ptr(actions), _ptr(tokens),
                                             _stream_ptr(self.device)))
         return actions, tokens
 
+    # -- mixed-domain batches --------------------------------------------------------------------
+    def set_slot_table(self, discrete=None, act_dim=None, image=None):
+        """Per env slot: head mode (bool), action dims in use (int, 1 .. spec.act_dim; 1 for a discrete slot) and observation
+        kind (bool: uint8 frame) -- arrays of length `batch` (lram_set_slot_table).  set_slot_table(None) clears the table.
+        Synchronises and drops a captured graph: not a hot-path call."""
+        if discrete is None and act_dim is None and image is None:
+            _check(self.lib, self.lib.lram_set_slot_table(self._h, None, None))
+            return
+        B = self.batch
+        d = torch.as_tensor(discrete).reshape(-1).to("cpu")
+        a = torch.as_tensor(act_dim).reshape(-1).to("cpu")
+        i = torch.zeros(B, dtype=torch.bool) if image is None else torch.as_tensor(image).reshape(-1).to("cpu")
+        for name, t in (("discrete", d), ("act_dim", a), ("image", i)):
+            if t.numel() != B:
+                raise ValueError(f"{name}: expected {B} entries (one per env slot), got {t.numel()}")
+            if t.dtype.is_floating_point or t.dtype.is_complex:
+                raise ValueError(f"{name}: expected a bool / integer array, got {t.dtype}")
+        if bool(((a < 0) | (a > 255)).any()):
+            raise ValueError("act_dim: entries must be in 1 .. spec.act_dim")
+        flags = (d.bool().to(torch.uint8) * LRAM_SLOT_DISCRETE + i.bool().to(torch.uint8) * LRAM_SLOT_IMAGE).contiguous()
+        acts = a.to(torch.uint8).contiguous()
+        _check(self.lib, self.lib.lram_set_slot_table(self._h, ctypes.c_void_p(flags.data_ptr()),
+                                                      ctypes.c_void_p(acts.data_ptr())))
+
+    def slot_table(self) -> Optional[dict]:
+        """The table in effect (lram_get_slot_table): {"discrete": bool [B], "act_dim": int64 [B], "image": bool [B],
+        "n_image": int} as CPU tensors, or None when no table is set."""
+        try:
+            n = self.n_image_slots
+        except LramError:
+            return None
+        flags = torch.empty(self.batch, dtype=torch.uint8)
+        acts = torch.empty(self.batch, dtype=torch.uint8)
+        _check(self.lib, self.lib.lram_get_slot_table(self._h, ctypes.c_void_p(flags.data_ptr()),
+                                                      ctypes.c_void_p(acts.data_ptr()), None))
+        return {"discrete": (flags & LRAM_SLOT_DISCRETE) != 0, "act_dim": acts.to(torch.int64),
+                "image": (flags & LRAM_SLOT_IMAGE) != 0, "n_image": n}
+
+    @property
+    def n_image_slots(self) -> int:
+        n = ctypes.c_int32(0)
+        _check(self.lib, self.lib.lram_get_slot_table(self._h, None, None, ctypes.byref(n)))
+        return int(n.value)
+
+    def step_slots(self, obs: Optional[torch.Tensor], images: Optional[torch.Tensor], rtg: torch.Tensor,
+                   reward: torch.Tensor, reset_mask: Optional[torch.Tensor] = None,
+                   out_actions: Optional[torch.Tensor] = None, out_tokens: Optional[torch.Tensor] = None):
+        """One env-step of a mixed batch (lram_step_slots): obs float32 [B, state_dim] (rows of image slots are never read),
+        images uint8 [n_image, C, H, W] -- frame k belongs to the k-th image slot in ascending slot order; None when the table
+        holds no image slot.  Head mode per slot: a continuous slot fills columns < its act_dim, a discrete slot column 0 (the
+        action index); every other column holds 0.0 / token -1.  Returns (actions, tokens) as step()."""
+        B, spec = self.batch, self.spec
+        n_img = self.n_image_slots   # raises when no table is set
+        if obs is None:
+            if n_img != B:
+                raise ValueError("obs: None is allowed only when every slot is an image slot")
+        else:
+            _chk_dev(obs, torch.float32, (B, spec.state_dim), self.device, "obs")
+        c = h = w = 0
+        if n_img > 0:
+            if images is None or images.dim() != 4:
+                raise ValueError("images must be [n_image, C, H, W]")
+            _chk_dev(images, torch.uint8, (n_img, *images.shape[1:]), self.device, "images")
+            c, h, w = (int(x) for x in images.shape[1:])
+        elif images is not None and images.shape[0] != 0:
+            raise ValueError(f"images: the slot table holds no image slot, got {images.shape[0]} frames")
+        _chk_dev(rtg, torch.float32, (B,), self.device, "rtg")
+        _chk_dev(reward, torch.float32, (B,), self.device, "reward")
+        if reset_mask is not None:
+            _chk_dev(reset_mask, torch.uint8, (B,), self.device, "reset_mask")
+        actions = self._actions if out_actions is None else out_actions
+        tokens = self._tokens if out_tokens is None else out_tokens
+        _chk_dev(actions, torch.float32, (B, spec.act_dim), self.device, "out_actions")
+        _chk_dev(tokens, torch.int32, (B, spec.act_dim), self.device, "out_tokens")
+        _check(self.lib, self.lib.lram_step_slots(self._h, _ptr(obs), _ptr(images) if n_img > 0 else None, c, h, w, _ptr(rtg),
+                                                  _ptr(reward), _ptr(reset_mask), _ptr(actions), _ptr(tokens),
+                                                  _stream_ptr(self.device)))
+        return actions, tokens
+
     def prefill(self, obs_seq: torch.Tensor, rtg_seq: torch.Tensor, reward_seq: torch.Tensor,
-                reset_mask: Optional[torch.Tensor] = None, discrete: bool = False, obs_is_embedding: bool = False,
+                reset_mask: Optional[torch.Tensor] = None, discrete=False, obs_is_embedding: bool = False,
                 want_action: bool = True):
         """L stored timesteps in one call ([B, L, state_dim], [B, L], [B, L]); == L sequential step() calls.
         Returns (actions, tokens) of the last timestep (None when want_action is False)."""
@@ -280,7 +378,7 @@ class Engine:
         act = self._actions if want_action else None
         tok = self._tokens if want_action else None
         _check(self.lib, self.lib.lram_prefill(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq),
-                                               _ptr(reward_seq), int(L), _ptr(reset_mask), int(discrete), _ptr(act),
+                                               _ptr(reward_seq), int(L), _ptr(reset_mask), _head_mode(discrete), _ptr(act),
                                                _ptr(tok), _stream_ptr(self.device)))
         return (act, tok) if want_action else (None, None)
 
@@ -300,7 +398,7 @@ class Engine:
         return out
 
     def step_images(self, images: torch.Tensor, rtg: torch.Tensor, reward: torch.Tensor,
-                    reset_mask: Optional[torch.Tensor] = None, discrete: bool = False,
+                    reset_mask: Optional[torch.Tensor] = None, discrete=False,
                     out_actions: Optional[torch.Tensor] = None, out_tokens: Optional[torch.Tensor] = None):
         """One env-step from uint8 frames [B, C, H, W]: embed_images + step(obs_is_embedding=True) as one call (the reference's
         forward embeds image states inside `compute_inputs`, online_decision_transformer_model.py:463-530).  Same results as the two
@@ -319,7 +417,7 @@ class Engine:
         _chk_dev(tokens, torch.int32, (B, spec.act_dim), self.device, "out_tokens")
         _check(self.lib, self.lib.lram_step_images(self._h, _ptr(images), int(images.shape[1]), int(images.shape[2]),
                                                    int(images.shape[3]), _ptr(rtg), _ptr(reward), _ptr(reset_mask),
-                                                   int(discrete), _ptr(actions), _ptr(tokens), _stream_ptr(self.device)))
+                                                   _head_mode(discrete), _ptr(actions), _ptr(tokens), _stream_ptr(self.device)))
         return actions, tokens
 
     def encoder_step(self, inputs_embeds: torch.Tensor, reset_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -571,6 +669,31 @@ def pad_obs(native: torch.Tensor, state_dim: int, inv_index: Optional[torch.Tens
         out = torch.empty(B, state_dim, dtype=torch.float32, device=native.device)
     _check(lib, lib.lram_pad_obs(_ptr(native), n, _ptr(inv_index), _ptr(mean), _ptr(std), _ptr(out), B, state_dim,
                                  _stream_ptr(native.device)))
+    return out
+
+
+def pad_obs_slots(native: torch.Tensor, state_dim: int, slot_row: torch.Tensor, inv_index: Optional[torch.Tensor] = None,
+                  mean: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pad_obs with one index / mean / std row per slot (lram_pad_obs_slots): slot_row int32 [B] picks the row of the
+    [n_rows, state_dim] tables (inv_index int32, mean / std float32) that slot b uses; inv_index None zero-pads."""
+    lib = load_library()
+    B, n = native.shape
+    dev = native.device
+    tables = [t for t in (inv_index, mean, std) if t is not None]
+    n_rows = int(tables[0].reshape(-1, state_dim).shape[0]) if tables else 1
+    _chk_dev(native, torch.float32, (B, n), dev, "native")
+    _chk_dev(slot_row, torch.int32, (B,), dev, "slot_row")
+    if inv_index is not None:
+        _chk_dev(inv_index, torch.int32, (n_rows, state_dim), dev, "inv_index")
+    for name, t in (("mean", mean), ("std", std)):
+        if t is not None:
+            _chk_dev(t, torch.float32, (n_rows, state_dim), dev, name)
+    if out is None:
+        out = torch.empty(B, state_dim, dtype=torch.float32, device=dev)
+    _chk_dev(out, torch.float32, (B, state_dim), dev, "out")
+    _check(lib, lib.lram_pad_obs_slots(_ptr(native), n, _ptr(slot_row), _ptr(inv_index), _ptr(mean), _ptr(std), n_rows,
+                                       _ptr(out), B, state_dim, _stream_ptr(dev)))
     return out
 
 

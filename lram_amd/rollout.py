@@ -74,18 +74,33 @@ class SyntheticVecEnv:
 class BatchedRollout:
     """agent: object with predict_batch(obs, rtg, rewards, reset_mask, env_act_dim) (lram_amd.agent.RecurrentAgent)."""
 
-    def __init__(self, agent, env: SyntheticVecEnv, target_return: float, reward_scale: float,
+    def __init__(self, agent, env: SyntheticVecEnv, target_return, reward_scale,
                  env_act_dim: Optional[int] = None, persist_context: bool = False):
+        """target_return / reward_scale: floats, or [n_envs] tensors for a batch of envs from several domains
+        (lram_amd.domains.SlotTable.target_return / .reward_scale): slot b then follows rtg - r / reward_scale[b]."""
         self.agent, self.env = agent, env
         # evaluation.py:213-236: with persist_context the (cached) context survives episode ends -- only the
         # target return and the timestep restart; without it the env's cache is reset (:238-251)
         self.persist_context = bool(persist_context)
-        self.reward_scale = float(reward_scale)
-        self.rtg0 = float(target_return) / float(reward_scale)
-        self.env_act_dim = env_act_dim
         dev = env.device
+        per_slot = torch.is_tensor(target_return) or torch.is_tensor(reward_scale)
+        if per_slot:
+            def as_slots(v, name):
+                t = torch.as_tensor(v).to(device=dev, dtype=torch.float64)   # (float64 tensors keep what a Python float holds)
+                t = t.expand(env.n_envs) if t.dim() == 0 else t
+                if tuple(t.shape) != (env.n_envs,):
+                    raise ValueError(f"{name}: expected a float or a [{env.n_envs}] tensor, got shape {tuple(t.shape)}")
+                return t.contiguous()
+            scale64 = as_slots(reward_scale, "reward_scale")
+            # slot by slot what the float form computes: float(target) / float(scale) in double, then fp32
+            self.rtg0 = (as_slots(target_return, "target_return") / scale64).float()
+            self.reward_scale = scale64.float()
+        else:
+            self.reward_scale = float(reward_scale)
+            self.rtg0 = float(target_return) / float(reward_scale)
+        self.env_act_dim = env_act_dim
         self.obs = env.reset()
-        self.rtg = torch.full((env.n_envs,), self.rtg0, device=dev)
+        self.rtg = self.rtg0.clone() if per_slot else torch.full((env.n_envs,), self.rtg0, device=dev)
         self.reset_mask = torch.ones(env.n_envs, dtype=torch.uint8, device=dev)  # every env starts an episode
         self.timestep = torch.zeros(env.n_envs, dtype=torch.long, device=dev)
         self.ep_return = torch.zeros(env.n_envs, device=dev)
@@ -102,7 +117,8 @@ class BatchedRollout:
             self.finished_returns.append(self.ep_return[done].clone())
             self.finished_lengths.append(self.timestep[done].clone())
         # evaluation.py:163-169 (not done) / :238-246 (done: fresh target return, timestep 0)
-        self.rtg = torch.where(done, torch.full_like(self.rtg, self.rtg0), self.rtg - reward / self.reward_scale)
+        rtg0 = self.rtg0 if torch.is_tensor(self.rtg0) else torch.full_like(self.rtg, self.rtg0)
+        self.rtg = torch.where(done, rtg0, self.rtg - reward / self.reward_scale)
         self.timestep = torch.where(done, torch.zeros_like(self.timestep), self.timestep)
         self.ep_return = torch.where(done, torch.zeros_like(self.ep_return), self.ep_return)
         self.reset_mask = torch.zeros_like(self.reset_mask) if self.persist_context else done.to(torch.uint8)
