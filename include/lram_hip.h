@@ -214,6 +214,47 @@ int32_t lram_get_state_mode(const lram_engine* e);
  * a 1000-step episode: evaluation.py:130-177 never clears the cache inside an episode); fails in materialised mode. */
 int32_t lram_lazy_peek(lram_engine* e, int32_t block, int32_t which, float* dev_dst, void* stream);
 
+/* State of INDIVIDUAL env slots: fork, snapshot / restore, re-pack -- without touching any other slot of the batch.
+ * (lram_state_export / lram_state_import move one whole-batch tensor and fold every pending window of every env first; these
+ * calls fold nothing.)  The reference's counterpart is indexing the batch axis of `past_key_values`
+ * (decision_xlstm.py:138-169) / of InferenceParams.key_value_memory_dict (decision_mamba.py:9-25) for one env.
+ *
+ * Record: the portable per-env format, lram_slot_state_numel() floats = lram_state_bytes_per_env / 4:
+ *   - blocks in order;
+ *   - within a block the state tensors that exist, in `which` order 0, 1, 2, 3 (see lram_state_numel above);
+ *   - each tensor is the env's slice in the reference layout:
+ *       mLSTM block: C [NH, DH, DH], n [NH, DH], m [NH], conv [K, inner]
+ *       sLSTM block: slstm_state [4, D] (y, c, n, m), conv [K, D]
+ *       Mamba layer: ssm_state [d_inner, d_state], conv_state [d_inner, d_conv]
+ *   so a record is exactly the concatenation of env b's slices of what lram_state_export returns.  It does not depend on the
+ *   batch size, the state mode or the micro-batch slicing of the engine that wrote it.
+ *
+ * lram_state_copy_slots: slot host_dst[i] becomes an exact copy of slot host_src[i], as of the last completed step.  Sources may
+ *   repeat (fan-out); destinations must be unique, in range and must not be sources (permute by save then load).
+ * lram_state_save_slots: dev_records (device float[n, slot_state_numel]) receives the records of the listed slots (in range,
+ *   at most `batch` of them; repeats allowed).  Never writes engine state, never changes the fold schedule: in lazy mode the
+ *   record's C is g * C_base + sum_j c_j khat_j v_j^T computed on the fly (fp32 FMAs; a slot whose C_base is logically zero
+ *   contributes only its window), within the state bar of the folded tensor, not bit-identical to it.
+ * lram_state_load_slots: writes the records into the listed slots (unique, in range).  In lazy mode each loaded slot's window is
+ *   marked empty (count 0, g = 1).  Where the sLSTM step runs its f16x2 form the hidden planes of the listed records must pass
+ *   lram_state_import's rule (|y| < 16, no NaN; one small launch + host synchronisation, before anything is written).
+ * Index lists are HOST int32 arrays (validation costs no synchronisation); n = 0 is a no-op.  A refused call (message in
+ * lram_last_error) leaves the state as it was.
+ *   - Unlisted slots, and the sources of a copy or save, are untouched in both state modes: their state and every later output
+ *     are bit-identical to a run without the call.  In lazy mode a copy moves the representation as it is (C_base, window rows,
+ *     the live side of coefficients / scale / count word) and folds nothing.
+ *   - A copied slot's later trajectory, given its source's inputs: bit-identical in materialised mode; in lazy mode bit-identical
+ *     where dst = src modulo the fold period inside one env slice, otherwise equal up to the fp32 rounding of a different
+ *     fold schedule (the parity bars of the step).
+ *   - Ordering against steps on `stream`: as lram_reset (the launches go to `stream`).  State pointers do not change: a captured
+ *     graph stays valid.  With the Mamba stale_state mode every layer is copied all the same.
+ *   - NOT moved: slot-table entries (lram_set_slot_table) and the sampling stream -- the Philox counter is keyed by the slot
+ *     INDEX, so N slots holding copies of one context draw N independent continuations (best-of-N, branching evaluation). */
+int64_t lram_slot_state_numel(const lram_engine* e);
+int32_t lram_state_copy_slots(lram_engine* e, const int32_t* host_src, const int32_t* host_dst, int32_t n, void* stream);
+int32_t lram_state_save_slots(lram_engine* e, const int32_t* host_slots, int32_t n, float* dev_records, void* stream);
+int32_t lram_state_load_slots(lram_engine* e, const int32_t* host_slots, int32_t n, const float* dev_records, void* stream);
+
 /* Micro-batch pipeline (xLSTM): the env slots are processed as `n` slices on engine-owned HIP streams; the
  * HBM-bound matrix-memory kernels of all slices run back to back on one stream while the other slices'
  * fp32-MFMA projections overlap them.  n = 1 disables it, 0 = automatic (2 slices where one mLSTM block's matrix memory over the batch reaches 512 MiB -- 16M from 512 env slots,

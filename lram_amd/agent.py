@@ -182,6 +182,29 @@ class RecurrentAgent:
         else:
             self.engine.import_past_key_values(value)
 
+    # ---- per-slot cache handle: fork / snapshot / restore single env slots (n_envs > 1) ----
+    def _need_batch(self, what: str):
+        if self.n_envs <= 1:
+            raise RuntimeError(f"{what}() moves state between env slots of a batched agent; this agent has n_envs = 1 "
+                               f"(use past_key_values for its one env)")
+
+    def fork_slots(self, src, dst):
+        """Slot dst[i] continues from slot src[i]'s context (Engine.copy_slots): the recurrent state is copied, nothing else of
+        the batch is touched.  With a_sample_kwargs the forked slots draw independent continuations (the sampling stream belongs
+        to the slot index); slot-table entries are not moved, so fork within one domain."""
+        self._need_batch("fork_slots")
+        self.engine.copy_slots(src, dst)
+
+    def save_slots(self, slots) -> torch.Tensor:
+        """float32 [n, engine.slot_state_numel] records of the listed slots (Engine.save_slots): a per-env checkpoint."""
+        self._need_batch("save_slots")
+        return self.engine.save_slots(slots)
+
+    def load_slots(self, slots, records: torch.Tensor):
+        """Restore records (save_slots of this or another agent of the same model) into the listed slots."""
+        self._need_batch("load_slots")
+        self.engine.load_slots(slots, records)
+
     # ---- multiprocess evaluation (src/callbacks/custom_eval_callback.py:22-33, decision_xlstm.py:243-267) ----
     def make_pickleable(self, replace_cell: bool = False):
         """The native engine handle cannot be serialised: release it (spec and host weights stay), as the reference

@@ -383,6 +383,61 @@ bool mlstm_lazy_supported(int DH, int T);
 void launch_mlstm_lazy_clear(int32_t* count, float* g, const uint8_t* mask, int B, int NH, hipStream_t stream);
 void launch_lazy_counts_as_float(const int32_t* count, float* out, int B, hipStream_t stream);
 
+// ---------------------------------------------------------------------------------------------
+// State of individual env slots (slot_state.hip): copy slot -> slot, save slots -> records, load records -> slots, every block
+// and tensor in ONE launch each, driven by a device-resident segment table (built by the engine in state_alloc / lazy_alloc).
+// A segment is one contiguous per-env piece of state: env b's piece is `numel` floats at base + b * stride.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSlotChunk = 4096;  // floats per workgroup: 256 lanes x 4 pieces of 16 bytes
+enum SlotSegKind : int32_t {
+  kSlotSegState = 0,   // part of the record
+  kSlotSegC = 1,       // mLSTM matrix memory: part of the record; in lazy mode the stored tensor is C_base (save computes C)
+  kSlotSegSlstmY = 2,  // sLSTM hidden plane: part of the record; range-checked by a load where the f16x2 step form runs
+  kSlotSegWindow = 3,  // lazy: window rows wk / wv (copy only)
+  kSlotSegCoef = 4,    // lazy: coefficients of one ping-pong parity (copy only)
+  kSlotSegG = 5,       // lazy: scale g of one parity (copy; a load writes 1)
+  kSlotSegCount = 6,   // lazy: count word of one parity (copy; a load writes 0)
+};
+struct SlotSeg {
+  float* base;
+  int64_t stride;    // floats between consecutive env slots
+  int64_t rec_off;   // offset of the piece inside an env's record (floats); -1: not in the record
+  int32_t numel;     // floats per env slot
+  int32_t kind;      // SlotSegKind
+  int32_t parity;    // -1: always live; 0 / 1: the lazy bookkeeping's ping-pong side (live when equal to the call's parity)
+  int32_t vec;       // bit 0: slot side moves as 16-byte pieces; bit 1: record side too (else the scalar path)
+};
+struct SlotChunk {   // workgroup x of a launch: floats [off, off + kSlotChunk) of segment seg
+  int32_t seg, off;
+};
+struct SlotStateArgs {
+  const SlotSeg* segs = nullptr;
+  const SlotChunk* chunks = nullptr;   // the record's segments first (n_rec_chunks), then the lazy representation's
+  int n_segs = 0, n_chunks = 0;
+  const int32_t* src = nullptr;        // device [n]: copy: source slots; save / load: the listed slots
+  const int32_t* dst = nullptr;        // device [n]: copy: destination slots
+  int n = 0;
+  float* records = nullptr;            // save: out, load: in   [n, rec_numel]
+  int64_t rec_numel = 0;
+  int lazy = 0, parity = 0;            // lazy representation in effect; its live ping-pong side
+  int rec_vec = 1;                     // 0: the record buffer is not 16-byte aligned: scalar path for the record side
+};
+void launch_slot_copy(const SlotStateArgs& a, hipStream_t stream);
+void launch_slot_save(const SlotStateArgs& a, hipStream_t stream);
+void launch_slot_load(const SlotStateArgs& a, hipStream_t stream);
+// flag |= any listed record's sLSTM hidden plane (kSlotSegSlstmY segments) holds a value outside (-limit, limit), NaN included
+void launch_slot_y_range(const SlotStateArgs& a, float limit, int* flag, hipStream_t stream);
+// lazy save of one mLSTM block: record C = g C_base + sum_j coef_j khat_j v_j^T (plain fp32 FMAs), for the listed slots
+struct SlotLazySaveArgs {
+  const float *C = nullptr, *wk = nullptr, *wv = nullptr, *coef = nullptr, *g = nullptr;  // coef / g / count: the live side
+  const int32_t* count = nullptr;
+  const int32_t* slots = nullptr;
+  int n = 0, NH = 0, DH = 0;
+  float* records = nullptr;
+  int64_t rec_numel = 0, rec_off = 0;
+  int rec_vec = 1;   // 0: the tile's rows in the record are not 16-byte aligned: scalar stores
+};
+void launch_slot_lazy_save(const SlotLazySaveArgs& a, hipStream_t stream);
 
 // mode 0 (mLSTM): out[r, hd] = (GN(h)[r,hd] * gamma + skip*xa) * silu(z)      z = u[r, inner + hd]
 // mode 1 (sLSTM): x[r, hd] += GN(h)[r,hd] * gamma

@@ -189,6 +189,24 @@ struct lram_engine {
   bool lazy_compact = false;    // this step's fold launches may use the compact grid (no window can overflow)
   bool lazy_dirty = false;      // a lazy step ran since the last materialise: windows may hold pending tokens
   DevBuf LZ_COUNT;          // [2][B] int32 pending tokens per env
+  // State of individual env slots (slot_state.hip; lram_state_copy_slots / save / load): one segment per contiguous per-env
+  // piece of state, cut into chunks of kSlotChunk floats -- the record's segments first, then the lazy representation's.
+  // Built by slot_segments_build (state_alloc, lazy_alloc); the state pointers never change in between.
+  std::vector<SlotSeg> slot_segs;        // host copy
+  SlotSeg* slot_segs_dev = nullptr;
+  SlotChunk* slot_chunks_dev = nullptr;
+  int slot_n_chunks = 0, slot_n_rec_chunks = 0;
+  int32_t* slot_idx_dev = nullptr;       // device [2][B]: the index lists of the call under way (stream-ordered)
+  std::vector<int64_t> slot_c_off;       // record offset of block i's matrix memory (-1: not an mLSTM block)
+  bool slot_y_checked = false;           // some sLSTM block runs the f16x2 step form: a load range-checks its hidden planes
+  void drop_slot_segments() {
+    if (slot_segs_dev) (void)hipFree(slot_segs_dev);
+    if (slot_chunks_dev) (void)hipFree(slot_chunks_dev);
+    if (slot_idx_dev) (void)hipFree(slot_idx_dev);
+    slot_segs_dev = nullptr, slot_chunks_dev = nullptr, slot_idx_dev = nullptr;
+    slot_segs.clear(), slot_c_off.clear();
+    slot_n_chunks = slot_n_rec_chunks = 0;
+  }
   // state + workspace
   int B = 0;
   std::vector<BlockState> st;
@@ -316,6 +334,7 @@ struct lram_engine {
     }
     LZ_COUNT.release();
     lazy_ready = false;
+    drop_slot_segments();
     st.clear();
     for (DevBuf* b : {&X, &XN, &TOK, &HID, &U, &Q, &K, &V, &XA, &H, &G, &SCAL, &RY, &LOGITS, &RES, &DTP, &SK, &GATES,
                       &AMAT, &VEC, &SEQ_EMB, &IMG_EMB, &IMG_P, &IMG_X0, &IMG_X1, &IMG_T, &XN2, &ASCALE, &AMX_XN, &AMX_XA, &AMX_H, &X0, &U0})
@@ -704,6 +723,82 @@ bool lazy_geometry_ok(const lram_engine* e) {
   return e->cfg.backbone == LRAM_BACKBONE_XLSTM && mlstm_lazy_supported(e->cfg.inner / e->cfg.n_heads, e->cfg.tokens_per_step);
 }
 
+// Segment and chunk tables of the per-slot state calls (common.h: SlotSeg).  Record layout = blocks in order, within a block
+// the tensors that exist in `which` order 0..3, each the env's slice in the reference layout (include/lram_hip.h).
+void slot_segments_build(lram_engine* e) {
+  e->drop_slot_segments();
+  if (e->B <= 0) return;
+  const lram_config& c = e->cfg;
+  const int64_t B = e->B;
+  std::vector<SlotSeg>& segs = e->slot_segs;
+  int64_t rec = 0;
+  const int64_t rec_numel = lram_state_bytes_per_env(e) / 4;
+  auto add = [&](float* base, int64_t stride, int64_t numel, int kind, int parity, bool in_record) {
+    if (base == nullptr || numel <= 0) return;
+    SlotSeg sg{};
+    sg.base = base, sg.stride = stride, sg.numel = (int32_t)numel, sg.kind = kind, sg.parity = parity;
+    sg.rec_off = in_record ? rec : -1;
+    const bool slot_ok = numel % 4 == 0 && stride % 4 == 0 && (reinterpret_cast<uintptr_t>(base) & 15) == 0;
+    const bool rec_ok = in_record && rec % 4 == 0 && rec_numel % 4 == 0;
+    sg.vec = (slot_ok ? 1 : 0) | (slot_ok && rec_ok ? 2 : 0);
+    if (in_record) rec += numel;
+    segs.push_back(sg);
+  };
+  e->slot_c_off.assign(c.n_blocks, -1);
+  e->slot_y_checked = false;
+  for (int i = 0; i < c.n_blocks; ++i) {
+    BlockState& s = e->st[i];
+    if (c.backbone == LRAM_BACKBONE_MAMBA) {
+      add(s.s0.p, (int64_t)c.d_inner * c.d_state, (int64_t)c.d_inner * c.d_state, kSlotSegState, -1, true);
+      add(s.conv.p, (int64_t)c.d_inner * c.d_conv, (int64_t)c.d_inner * c.d_conv, kSlotSegState, -1, true);
+    } else if (c.block_is_slstm[i]) {
+      const int64_t D = c.d_model;
+      const bool checked = e->slstm_rinv.size() > (size_t)i && e->slstm_rinv[i].p != nullptr;
+      e->slot_y_checked = e->slot_y_checked || checked;
+      for (int p = 0; p < 4; ++p)   // [4, B, D]: y, c, n, m planes
+        add(s.s0.p + p * B * D, D, D, p == 0 && checked ? kSlotSegSlstmY : kSlotSegState, -1, true);
+      add(s.conv.p, (int64_t)c.conv_k * D, (int64_t)c.conv_k * D, kSlotSegState, -1, true);
+    } else {
+      const int64_t NH = c.n_heads, DH = e->dh();
+      e->slot_c_off[i] = rec;
+      add(s.s0.p, NH * DH * DH, NH * DH * DH, kSlotSegC, -1, true);
+      add(s.n.p, c.inner, c.inner, kSlotSegState, -1, true);
+      add(s.m.p, NH, NH, kSlotSegState, -1, true);
+      add(s.conv.p, (int64_t)c.conv_k * c.inner, (int64_t)c.conv_k * c.inner, kSlotSegState, -1, true);
+    }
+  }
+  LRAM_REQUIRE(rec == rec_numel, "slot state: the segment table does not add up to the record size");
+  const size_t n_rec_segs = segs.size();
+  if (e->lazy_ready) {  // the lazy representation (copy only): window rows, and both ping-pong sides of the bookkeeping
+    const int64_t NH = c.n_heads, DH = e->dh(), W = kLazyWindow;
+    for (int i = 0; i < c.n_blocks; ++i) {
+      if (c.block_is_slstm[i]) continue;
+      BlockState& s = e->st[i];
+      add(s.wk.p, NH * W * DH, NH * W * DH, kSlotSegWindow, -1, false);
+      add(s.wv.p, NH * W * DH, NH * W * DH, kSlotSegWindow, -1, false);
+      for (int p = 0; p < 2; ++p) {
+        add(s.coef.p + p * B * NH * W, NH * W, NH * W, kSlotSegCoef, p, false);
+        add(s.gsc.p + p * B * NH, NH, NH, kSlotSegG, p, false);
+      }
+      // (s.pw, the window scores, is scratch of one step -- written by the score kernel and read by the read pass of the SAME
+      // step, first n + T entries of a row only -- and is not state: nothing to move)
+    }
+    for (int p = 0; p < 2; ++p) add(e->LZ_COUNT.p + p * B, 1, 1, kSlotSegCount, p, false);   // one count word per env, all blocks
+  }
+  std::vector<SlotChunk> chunks;
+  for (size_t k = 0; k < segs.size(); ++k) {
+    if (k == n_rec_segs) e->slot_n_rec_chunks = (int)chunks.size();
+    for (int32_t off = 0; off < segs[k].numel; off += kSlotChunk) chunks.push_back(SlotChunk{(int32_t)k, off});
+  }
+  if (segs.size() == n_rec_segs) e->slot_n_rec_chunks = (int)chunks.size();
+  e->slot_n_chunks = (int)chunks.size();
+  LRAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->slot_segs_dev), segs.size() * sizeof(SlotSeg)));
+  LRAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->slot_chunks_dev), chunks.size() * sizeof(SlotChunk)));
+  LRAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->slot_idx_dev), 2 * (size_t)B * sizeof(int32_t)));
+  LRAM_HIP_CHECK(hipMemcpy(e->slot_segs_dev, segs.data(), segs.size() * sizeof(SlotSeg), hipMemcpyHostToDevice));
+  LRAM_HIP_CHECK(hipMemcpy(e->slot_chunks_dev, chunks.data(), chunks.size() * sizeof(SlotChunk), hipMemcpyHostToDevice));
+}
+
 void lazy_alloc(lram_engine* e) {
   if (e->lazy_ready || e->B <= 0 || !lazy_geometry_ok(e)) return;
   const lram_config& c = e->cfg;
@@ -733,6 +828,7 @@ void lazy_alloc(lram_engine* e) {
   LRAM_HIP_CHECK(hipDeviceSynchronize());
   e->lazy_step = 0;
   e->lazy_ready = true;
+  slot_segments_build(e);
 }
 
 // auto: lazy where the state pass dominates -- one mLSTM block's matrix memory of at least 128 MiB over the batch
@@ -830,6 +926,7 @@ void state_alloc(lram_engine* e, int B) {
   alloc_workspace(e, kMaxTokens);
   e->lazy = lazy_choice(e);
   if (e->lazy) lazy_alloc(e);
+  if (e->slot_segs_dev == nullptr) slot_segments_build(e);
   LRAM_HIP_CHECK(hipDeviceSynchronize());
 }
 
@@ -1985,6 +2082,41 @@ StateView state_view(const lram_engine* e, int block, int which) {
   }
 }
 
+// ---- state of individual env slots: host-side helpers of lram_state_copy_slots / save / load --------------------------
+// Host-side rules of the index lists; `what` prefixes the message.  dst == nullptr: one list (save / load).
+void slot_lists_check(const char* what, const int32_t* src, const int32_t* dst, int n, int B, bool unique_src) {
+  const std::string w(what);
+  std::vector<uint8_t> seen(B, 0);   // bit 0: a source, bit 1: a destination
+  for (int i = 0; i < n; ++i) {
+    LRAM_REQUIRE(src[i] >= 0 && src[i] < B, w + ": slot index out of range");
+    LRAM_REQUIRE(!unique_src || !(seen[src[i]] & 1), w + ": a slot is listed twice");
+    seen[src[i]] |= 1;
+  }
+  if (dst == nullptr) return;
+  for (int i = 0; i < n; ++i) {
+    LRAM_REQUIRE(dst[i] >= 0 && dst[i] < B, w + ": destination slot index out of range");
+    LRAM_REQUIRE(!(seen[dst[i]] & 2), w + ": a destination slot is listed twice");
+    LRAM_REQUIRE(!(seen[dst[i]] & 1), w + ": a slot is both source and destination (permute by save then load)");
+    seen[dst[i]] |= 2;
+  }
+}
+
+SlotStateArgs slot_args(lram_engine* e, const int32_t* host_a, const int32_t* host_b, int n, hipStream_t s) {
+  // (pageable host memory: the copy has read the caller's arrays when it returns; the device side is ordered on `s`)
+  LRAM_HIP_CHECK(hipMemcpyAsync(e->slot_idx_dev, host_a, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (host_b)
+    LRAM_HIP_CHECK(hipMemcpyAsync(e->slot_idx_dev + e->B, host_b, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  SlotStateArgs a;
+  a.segs = e->slot_segs_dev, a.chunks = e->slot_chunks_dev, a.n_segs = (int)e->slot_segs.size();
+  a.src = e->slot_idx_dev, a.dst = host_b ? e->slot_idx_dev + e->B : nullptr, a.n = n;
+  a.rec_numel = lram_state_bytes_per_env(e) / 4;
+  // the lazy representation is what the state IS whenever its buffers exist and the mode is in effect (also while a graph or a
+  // prefill runs the materialised kernels: the windows are then empty, which the same code handles)
+  a.lazy = (e->lazy && e->lazy_ready) ? 1 : 0;
+  a.parity = (int)(e->lazy_step & 1);   // what the next step reads = what the last one wrote
+  return a;
+}
+
 template <typename Fn>
 int32_t guarded(Fn&& fn) {
   try {
@@ -2473,6 +2605,106 @@ int32_t lram_lazy_peek(lram_engine* e, int32_t block, int32_t which, float* dev_
     } else {
       launch_lazy_counts_as_float(reinterpret_cast<const int32_t*>(e->LZ_COUNT.p) + side * B, dev_dst, (int)B, s);
     }
+  });
+}
+
+// ---- state of individual env slots (slot_state.hip) ------------------------------------------------------------------
+int64_t lram_slot_state_numel(const lram_engine* e) {
+  if (!e) {
+    g_last_error = "lram: lram_slot_state_numel: null engine";
+    return 0;
+  }
+  return lram_state_bytes_per_env(e) / 4;
+}
+
+int32_t lram_state_copy_slots(lram_engine* e, const int32_t* host_src, const int32_t* host_dst, int32_t n, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(e && e->B > 0, "lram_state_copy_slots: state not allocated (call lram_state_alloc)");
+    LRAM_REQUIRE(n >= 0 && (n == 0 || (host_src && host_dst)), "lram_state_copy_slots: bad argument");
+    slot_lists_check("lram_state_copy_slots", host_src, host_dst, n, e->B, false);
+    if (n == 0) return;
+    LRAM_HIP_CHECK(hipSetDevice(e->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SlotStateArgs a = slot_args(e, host_src, host_dst, n, s);
+    a.n_chunks = a.lazy ? e->slot_n_chunks : e->slot_n_rec_chunks;
+    launch_slot_copy(a, s);
+    if (a.lazy && (int)e->lazy_bound.size() == e->lazy_period) {
+      // The copy carries its source's pending window into another fold class ((phase + b) % period): that class's host-side
+      // bound must cover it, or the compact fold grid would skip an env whose window is about to overflow (the kernel's own
+      // n_in + T > W guard only runs on the full grid).
+      const int P = e->lazy_period;
+      std::vector<int> before = e->lazy_bound;
+      for (int i = 0; i < n; ++i)
+        e->lazy_bound[host_dst[i] % P] = std::max(e->lazy_bound[host_dst[i] % P], before[host_src[i] % P]);
+    }
+  });
+}
+
+int32_t lram_state_save_slots(lram_engine* e, const int32_t* host_slots, int32_t n, float* dev_records, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(e && e->B > 0, "lram_state_save_slots: state not allocated (call lram_state_alloc)");
+    LRAM_REQUIRE(n >= 0 && n <= e->B && (n == 0 || (host_slots && dev_records)), "lram_state_save_slots: bad argument (at most `batch` slots per call)");
+    slot_lists_check("lram_state_save_slots", host_slots, nullptr, n, e->B, false);
+    if (n == 0) return;
+    LRAM_HIP_CHECK(hipSetDevice(e->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SlotStateArgs a = slot_args(e, host_slots, nullptr, n, s);
+    a.n_chunks = e->slot_n_rec_chunks;
+    a.records = dev_records;
+    a.rec_vec = (reinterpret_cast<uintptr_t>(dev_records) & 15) == 0 ? 1 : 0;
+    launch_slot_save(a, s);
+    if (a.lazy) {   // C = g C_base + window, computed into the record: no fold, no write to engine state
+      const size_t B = e->B, NH = e->cfg.n_heads;
+      for (int i = 0; i < e->cfg.n_blocks; ++i) {
+        if (e->slot_c_off[i] < 0) continue;
+        BlockState& st = e->st[i];
+        SlotLazySaveArgs la;
+        la.C = st.s0.p, la.wk = st.wk.p, la.wv = st.wv.p;
+        la.coef = st.coef.p + (size_t)a.parity * B * NH * kLazyWindow;
+        la.g = st.gsc.p + (size_t)a.parity * B * NH;
+        la.count = reinterpret_cast<const int32_t*>(e->LZ_COUNT.p) + (size_t)a.parity * B;
+        la.slots = a.src, la.n = n, la.NH = (int)NH, la.DH = e->dh();
+        la.records = dev_records, la.rec_numel = a.rec_numel, la.rec_off = e->slot_c_off[i];
+        la.rec_vec = (a.rec_vec && la.rec_off % 4 == 0 && a.rec_numel % 4 == 0) ? 1 : 0;
+        launch_slot_lazy_save(la, s);
+      }
+    }
+  });
+}
+
+int32_t lram_state_load_slots(lram_engine* e, const int32_t* host_slots, int32_t n, const float* dev_records, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(e && e->B > 0, "lram_state_load_slots: state not allocated (call lram_state_alloc)");
+    LRAM_REQUIRE(n >= 0 && (n == 0 || (host_slots && dev_records)), "lram_state_load_slots: bad argument");
+    slot_lists_check("lram_state_load_slots", host_slots, nullptr, n, e->B, true);
+    if (n == 0) return;
+    LRAM_HIP_CHECK(hipSetDevice(e->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SlotStateArgs a = slot_args(e, host_slots, nullptr, n, s);
+    a.n_chunks = e->slot_n_rec_chunks;
+    a.records = const_cast<float*>(dev_records);
+    a.rec_vec = (reinterpret_cast<uintptr_t>(dev_records) & 15) == 0 ? 1 : 0;
+    if (e->slot_y_checked) {
+      // lram_state_import's range rule for the sLSTM hidden planes, on the listed records only and BEFORE anything is written
+      // (a rare call: one small launch and a host synchronisation are affordable)
+      int* dflag = nullptr;
+      int hflag = 0;
+      LRAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dflag), sizeof(int)));
+      try {
+        LRAM_HIP_CHECK(hipMemsetAsync(dflag, 0, sizeof(int), s));
+        launch_slot_y_range(a, 15.9f, dflag, s);
+        LRAM_HIP_CHECK(hipMemcpyAsync(&hflag, dflag, sizeof(int), hipMemcpyDeviceToHost, s));
+        LRAM_HIP_CHECK(hipStreamSynchronize(s));
+      } catch (...) {
+        (void)hipFree(dflag);
+        throw;
+      }
+      (void)hipFree(dflag);
+      LRAM_REQUIRE(hflag == 0,
+                   "lram_state_load_slots: an sLSTM hidden plane holds |h| >= 16 (or NaN): outside what the recurrence produces "
+                   "(|h| < 1) and outside the binary16 planes of the f16x2 step kernel (see lram_state_import)");
+    }
+    launch_slot_load(a, s);   // lazy mode: also empties the loaded slots' windows on the live side
   });
 }
 

@@ -99,6 +99,10 @@ _SYMBOLS = {
     "lram_set_state_mode": (ctypes.c_int32, [_VP, ctypes.c_int32, ctypes.c_int32]),
     "lram_get_state_mode": (ctypes.c_int32, [_VP]),
     "lram_lazy_peek": (ctypes.c_int32, [_VP, ctypes.c_int32, ctypes.c_int32, _VP, _VP]),
+    "lram_slot_state_numel": (ctypes.c_int64, [_VP]),
+    "lram_state_copy_slots": (ctypes.c_int32, [_VP, _VP, _VP, ctypes.c_int32, _VP]),
+    "lram_state_save_slots": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP]),
+    "lram_state_load_slots": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP]),
     "lram_stream_rmw": (ctypes.c_int32, [_VP, ctypes.c_size_t, _VP]),
     "lram_stream_read": (ctypes.c_int32, [_VP, ctypes.c_size_t, _VP, _VP]),
     "lram_gemm_counts": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]),
@@ -199,6 +203,50 @@ def _chk_dev(t: torch.Tensor, dtype, shape, device, name):
     if t.device != device or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
         raise ValueError(f"{name}: expected contiguous {dtype} tensor of shape {tuple(shape)} on {device}, got "
                          f"{t.dtype} {tuple(t.shape)} on {t.device} (contiguous={t.is_contiguous()})")
+
+
+def _slot_list(x, name: str):
+    """A list of env slot indices as plain ints (accepts lists, numpy arrays and integer tensors)."""
+    if isinstance(x, torch.Tensor):
+        if x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == torch.bool:
+            raise ValueError(f"{name}: expected integer slot indices, got {x.dtype}")
+        x = x.reshape(-1).tolist()
+    out = []
+    for v in x:
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{name}: expected integer slot indices, got {v!r}")
+        out.append(int(v))
+    return out
+
+
+def check_slot_lists(src, dst, batch: int):
+    """The rules of lram_state_copy_slots, checked on the host (no GPU needed): every index in 0 .. batch - 1, `dst` entries
+    unique, no slot both source and destination; `src` may repeat (fan-out).  dst=None checks one list the way
+    lram_state_load_slots does (in range, unique).  Returns the lists as ints; raises ValueError.  Empty lists are a no-op."""
+    src = _slot_list(src, "src")
+    for v in src:
+        if not 0 <= v < batch:
+            raise ValueError(f"src: slot index {v} out of range (batch {batch})")
+    if dst is None:
+        if len(set(src)) != len(src):
+            raise ValueError("slots: a slot is listed twice")
+        return src, None
+    dst = _slot_list(dst, "dst")
+    if len(src) != len(dst):
+        raise ValueError(f"src and dst must have the same length, got {len(src)} and {len(dst)}")
+    for v in dst:
+        if not 0 <= v < batch:
+            raise ValueError(f"dst: slot index {v} out of range (batch {batch})")
+    if len(set(dst)) != len(dst):
+        raise ValueError("dst: a destination slot is listed twice")
+    both = set(src) & set(dst)
+    if both:
+        raise ValueError(f"slots {sorted(both)} are both source and destination (permute by save_slots then load_slots)")
+    return src, dst
+
+
+def _i32_array(values):
+    return (ctypes.c_int32 * max(1, len(values)))(*values)
 
 
 class Engine:
@@ -500,6 +548,42 @@ class Engine:
                 for w, t in enumerate(blk["mlstm_state"]):
                     self.import_state_tensor(i, w, t)
             self.import_state_tensor(i, 3, blk["conv_state"][0])
+
+    # -- state of individual env slots: fork / snapshot / restore ---------------------------------
+    @property
+    def slot_state_numel(self) -> int:
+        """Floats in one env slot's state record (lram_slot_state_numel) = state_bytes_per_env() / 4."""
+        return int(self.lib.lram_slot_state_numel(self._h))
+
+    def copy_slots(self, src, dst):
+        """Slot dst[i] becomes an exact copy of slot src[i] (lram_state_copy_slots): no other slot is touched, nothing is
+        folded.  `src` may repeat (fork one context into many slots); slot-table entries and the sampling stream stay with the
+        slot index, so forked slots draw independent continuations."""
+        src, dst = _slot_list(src, "src"), _slot_list(dst, "dst")
+        if len(src) != len(dst):
+            raise ValueError(f"src and dst must have the same length, got {len(src)} and {len(dst)}")
+        _check(self.lib, self.lib.lram_state_copy_slots(self._h, _i32_array(src), _i32_array(dst), len(src),
+                                                        _stream_ptr(self.device)))
+
+    def save_slots(self, slots, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Records of the listed slots, float32 [n, slot_state_numel] on the device (lram_state_save_slots): the portable
+        per-env format (blocks in order, tensors in `which` order, reference layout).  Read-only for the engine."""
+        slots = _slot_list(slots, "slots")
+        n, numel = len(slots), self.slot_state_numel
+        if out is None:
+            out = torch.empty(n, numel, dtype=torch.float32, device=self.device)
+        _chk_dev(out, torch.float32, (n, numel), self.device, "out")
+        _check(self.lib, self.lib.lram_state_save_slots(self._h, _i32_array(slots), n, _ptr(out), _stream_ptr(self.device)))
+        return out
+
+    def load_slots(self, slots, records: torch.Tensor):
+        """Write records [n, slot_state_numel] (as save_slots returns, from this or another engine of the same model) into the
+        listed slots (lram_state_load_slots)."""
+        slots = _slot_list(slots, "slots")
+        records = records.to(device=self.device, dtype=torch.float32).contiguous()
+        _chk_dev(records, torch.float32, (len(slots), self.slot_state_numel), self.device, "records")
+        _check(self.lib, self.lib.lram_state_load_slots(self._h, _i32_array(slots), len(slots), _ptr(records),
+                                                        _stream_ptr(self.device)))
 
     # -- launch-latency removal / measurement ----------------------------------------------------
     def set_graph_mode(self, enable: bool):

@@ -70,6 +70,13 @@ class SyntheticVecEnv:
             self.last_info = {"is_success": done & (self.episodes % self.success_every == 0)}
         return self._sample(), reward, done
 
+    def copy_slots(self, src, dst):
+        """Env dst[i] continues from where env src[i] stands: its position in the episode and its episode count."""
+        src_t = torch.as_tensor(list(src), dtype=torch.long, device=self.device)
+        dst_t = torch.as_tensor(list(dst), dtype=torch.long, device=self.device)
+        self.t[dst_t] = self.t[src_t]
+        self.episodes[dst_t] = self.episodes[src_t]
+
 
 class BatchedRollout:
     """agent: object with predict_batch(obs, rtg, rewards, reset_mask, env_act_dim) (lram_amd.agent.RecurrentAgent)."""
@@ -125,6 +132,25 @@ class BatchedRollout:
         self.obs = obs
         self.last_reward, self.last_done = reward, done
         return actions
+
+    def fork_slots(self, src, dst):
+        """Env slot dst[i] becomes a copy of slot src[i] between two steps: the agent's recurrent state (agent.fork_slots), this
+        driver's per-slot bookkeeping (observation, return-to-go, timestep, episode return; dst does not start an episode) and,
+        where the env offers copy_slots(src, dst), the env's own per-slot state.  Same list rules as Engine.copy_slots."""
+        from .engine import check_slot_lists
+        src, dst = check_slot_lists(src, dst, self.env.n_envs)
+        if not src:
+            return
+        self.agent.fork_slots(src, dst)
+        if hasattr(self.env, "copy_slots"):
+            self.env.copy_slots(src, dst)
+        dev = self.obs.device
+        src_t = torch.as_tensor(src, dtype=torch.long, device=dev)
+        dst_t = torch.as_tensor(dst, dtype=torch.long, device=dev)
+        for name in ("obs", "rtg", "timestep", "ep_return"):
+            t = getattr(self, name)
+            t[dst_t] = t[src_t]
+        self.reset_mask[dst_t] = 0
 
     def run(self, n_steps: int, sync=None) -> Dict[str, float]:
         if sync is not None:
