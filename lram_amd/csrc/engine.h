@@ -1,0 +1,443 @@
+// Internal header of the engine's host files (engine*.hip): the engine object, the context of one call (Pass) and the host
+// functions that cross a file.  Not part of the C ABI (include/lram_hip.h) and not of the kernel launch interface (common.h).
+//
+//   engine.hip          lifecycle: create / destroy, weights, finalize, workspace + state allocation, the mode setters
+//   engine_gemm.hip     the GEMM dispatcher and the standalone lram_gemm_* entries            (calls kernels only)
+//   engine_streams.hip  events, env slices, fork / join, the profiler                          (calls nothing)
+//   engine_xlstm.hip    the xLSTM stack and the lazy matrix memory's host side                 (calls gemm, streams)
+//   engine_mamba.hip    the Mamba stack                                                        (calls gemm, streams)
+//   engine_step.hip     image / token front end, action head, the step and prefill entries     (calls the stacks, gemm, streams)
+//   engine_state.hip    reset, export / import, the slot table and the per-slot state calls
+#pragma once
+#include <algorithm>
+#include <array>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/lram_hip.h"
+#include "common.h"
+
+namespace lram::host {
+
+struct DevBuf {
+  float* p = nullptr;
+  size_t n = 0;
+  void alloc(size_t numel) {
+    release();
+    if (numel == 0) return;
+    LRAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), numel * sizeof(float)));
+    n = numel;
+  }
+  void zero(hipStream_t s = nullptr) {
+    if (p) LRAM_HIP_CHECK(hipMemsetAsync(p, 0, n * sizeof(float), s));
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = 0;
+  }
+};
+
+struct BlockWeights {  // resolved device pointers (nullptr when absent / optional)
+  // common
+  const float *norm_g = nullptr, *norm_b = nullptr;
+  // mLSTM
+  const float *proj_up = nullptr, *conv_w = nullptr, *conv_b = nullptr, *wq = nullptr, *wk = nullptr, *wv = nullptr,
+              *wi = nullptr, *bi = nullptr, *wf = nullptr, *bf = nullptr, *on_g = nullptr, *on_b = nullptr,
+              *skip = nullptr, *proj_down = nullptr;
+  // sLSTM
+  const float *gate_w[4] = {nullptr, nullptr, nullptr, nullptr};  // i, f, z, o slots of the cell
+  const float *rt = nullptr, *rbias = nullptr, *gn_g = nullptr, *gn_b = nullptr, *ffn_norm_g = nullptr,
+              *ffn_norm_b = nullptr, *ffn_up = nullptr, *ffn_down = nullptr;
+  // Mamba
+  const float *in_proj = nullptr, *in_proj_b = nullptr, *x_proj = nullptr, *dt_proj = nullptr, *dt_bias = nullptr,
+              *A_log = nullptr, *Dp = nullptr, *out_proj = nullptr, *out_proj_b = nullptr;
+};
+
+struct BlockState {
+  DevBuf s0;    // mLSTM C | sLSTM state [4,B,D] | Mamba ssm
+  DevBuf n;     // mLSTM n
+  DevBuf m;     // mLSTM m
+  DevBuf conv;  // conv state
+  // lazy matrix memory (mlstm_lazy.hip): window rows and ping-pong bookkeeping, allocated in lazy mode only
+  DevBuf wk, wv;    // [B, NH, W, DH] each
+  DevBuf coef;      // [2][B, NH, W]
+  DevBuf gsc;       // [2][B, NH]
+  DevBuf pw;        // [B, NH, 4, kLazyWT] window scores (head dims with several column slices per head only)
+};
+
+struct GraphKey {
+  const void *obs, *rtg, *rew, *mask, *act, *tok;
+  int emb, discrete, B;
+  hipStream_t stream;
+  bool operator==(const GraphKey& o) const {
+    return obs == o.obs && rtg == o.rtg && rew == o.rew && mask == o.mask && act == o.act && tok == o.tok &&
+           emb == o.emb && discrete == o.discrete && B == o.B && stream == o.stream;
+  }
+};
+
+}  // namespace lram::host
+
+// (a private header of the engine*.hip host files only: they all speak in these names)
+using namespace lram;
+using namespace lram::host;
+
+constexpr int kTokenTapMaxBatch = 1024;  // larger batches skip the per-step copy of the embed_ln tokens (lram_get_taps)
+
+struct lram_engine {
+  lram_config cfg{};
+  int device = 0;
+  std::map<std::string, DevBuf> weights;
+  bool finalized = false;
+  std::vector<BlockWeights> bw;
+  // bf16x3 GEMM: fp32 weight pointer -> its three bf16 planes (built in finalize)
+  struct Split {
+    uint16_t* p;
+    size_t n;
+  };
+  std::map<const float*, Split> split;
+  bool use_bf16x3 = true;  // LRAM_GEMM=f32 selects the exact fp32-MFMA kernel everywhere
+  // f16x2 projection kernel (gemm_f16x2.hip): un-batched weights also get two row-scaled f16 planes + inverse scales;
+  // LRAM_GEMM=bf16x3 keeps the three-plane bf16 kernel for them too
+  bool use_f16x2 = true;
+  int f16x2_min_rows = 256;   // LRAM_F16_MIN_ROWS
+  struct Split16 {
+    uint16_t* planes;  // [2][rows][k] f16
+    float* inv;        // [rows] exact inverse of each weight row's power-of-two scale
+    size_t rows, k;
+  };
+  std::map<const float*, Split16> split16;
+  bool gemm_presplit = true;   // LRAM_GEMM_PRESPLIT=0: the norms ahead of proj_up / in_proj write fp32 + row maxima (round 3) instead of
+                               // the f16x2 GEMM's operand planes (gemm_f16x2p.hip)
+  double gemm_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // launches / fp32-equivalent FLOPs per dispatcher family (lram_gemm_counts)
+  std::vector<DevBuf> slstm_rt2;  // sLSTM: recurrent weights re-packed per block for slstm_seq.hip: fp32 [head][k][channel][gate], or
+                                  // (f16x2 projections, the default) two f16 planes in the same bytes + slstm_rinv, the inverse row scales
+  std::vector<DevBuf> slstm_rinv;
+  int lazy_cap2_envs = 896;       // LRAM_LAZY_CAP2_ENVS: largest slice whose read pass runs two workgroups per CU (0 = never)
+  std::map<const float*, DevBuf> narrow;   // narrow-output weights (Mamba x_proj) packed for gemm_narrow.hip (built in finalize)
+  bool gemm_narrow_on = true;     // LRAM_GEMM_NARROW=0: x_proj through the tile GEMMs (split-K + reduce) as before round 6
+  int gemm_narrow_min_rows = 256;
+  bool upz_beside = true;         // LRAM_UPZ_8P=0: proj_up's z half (issued beside the slice's own state pass) never through the 8-phase kernel
+  bool slstm_gates_one = true;    // LRAM_SLSTM_GATES_ONE=0: the four sLSTM gate projections of larger slices as four bf16x3 launches
+  bool gemm_narrow_f16 = true;    // LRAM_GEMM_NARROW=2: its exact-fp32 form even where the projections run as f16x2
+  bool gn_amax_handover = true;   // LRAM_GN_AMAX=0: proj_down's operand row maxima from their own launch, not from the group norm
+  bool gn_planes = true;          // LRAM_GN_AMAX=1: the group norm writes fp32 + partial row maxima (round 5) instead of proj_down's operand planes
+  bool slstm_seq_f32 = false;     // LRAM_SLSTM_SEQ=2: its exact-fp32 form even where the projections run as f16x2
+  bool slstm_seq = true;          // LRAM_SLSTM_SEQ=0: per-token recurrent GEMM + pointwise launches for slices beyond the token kernel's
+  std::vector<DevBuf> gate_coef;  // mLSTM: folded i / f gate coefficients per block (mlstm_front.hip), geometries it covers
+  bool front_multi = true;     // LRAM_FRONT_MULTI=0: keep the one-workgroup-per-env front end for large launches too
+  int front_min_envs = 256;    // LRAM_FRONT_MIN_ENVS: slices of at least this many env slots take the multi-env front end
+  std::vector<DevBuf> dt_wt;   // Mamba: dt_proj.weight transposed to [dt_rank, d_inner] per block (state-update kernel's operand)
+  DevBuf ASCALE;  // per-row maxima of a GEMM's A operand computed by launch_row_amax, one region per stream slot (like
+  size_t ascale_rows = 0;  // the split-K slabs)
+  // row maxima handed over by the kernels that produce the projections' operands, indexed like the rows of X:
+  // XN (norm -> proj_up / ffn_up / in_proj), XA (Mamba conv -> x_proj), H (Mamba selective state update -> out_proj)
+  DevBuf AMX_XN, AMX_XA, AMX_H;
+  // front end / head
+  const float *w_state = nullptr, *b_state = nullptr, *w_rtg = nullptr, *b_rtg = nullptr, *w_rew = nullptr,
+              *b_rew = nullptr, *eln_g = nullptr, *eln_b = nullptr, *w_head = nullptr, *b_head = nullptr,
+              *post_g = nullptr, *post_b = nullptr;
+  // IMPALA-CNN image front end (optional: present when the embed_image.* weights were uploaded)
+  struct ImgConv {
+    const float *w = nullptr, *b = nullptr;
+    int cin = 0, cout = 0;
+  };
+  ImgConv img_conv[3][5];  // [stage][stage conv, res0.conv_0, res0.conv_1, res1.conv_0, res1.conv_1]
+  const float *img_lin_w = nullptr, *img_lin_b = nullptr;
+  int img_channels = 0, img_flat = 0;  // input channels, flattened feature count of the linear layer
+  DevBuf IMG_P, IMG_X0, IMG_X1, IMG_T;
+  DevBuf IMG_EMB;                      // [B, D] state-token embeddings of lram_step_images
+  // lram_step_images (Pass::images, the frames of the env-step under way): every env slice runs the IMPALA-CNN on
+  // its own frames on its own stream, and the state-pass stream takes fold_bubbles_images folds ahead of the first read pass --
+  // the VALU-bound CNN and the HBM-bound folds share the start of the step
+  // (206M, 512 slots, same box: two calls 31.03k env-steps/s; one call with 2 / 5 / 8 / 11 / 14 folds ahead 31.36k / 31.68k / 31.81k /
+  // 31.65k / 31.31k; the second slice's CNN held back until the first slice's is done: 31.4k -- not kept)
+  static constexpr int fold_bubbles_images = 8;
+  // Slot table (lram_set_slot_table): head mode, action dims in use and observation kind per env slot.  Host copy + device
+  // copy; the ascending list of image slots (frame k belongs to slot_img_list[k]) and its prefix counts give every env slice
+  // its contiguous range of frames.
+  bool slot_table = false;
+  std::vector<uint8_t> slot_flags, slot_act;   // host [B] each
+  std::vector<int32_t> slot_img_prefix;        // host [B + 1]: image slots below slot b
+  uint8_t* slot_dev = nullptr;                 // device [2][B]: flags, act_dim
+  int32_t* slot_img_list = nullptr;            // device [n_image_slots]
+  int slot_n_image = 0;
+  bool slot_has_discrete = false;
+  size_t img_cap = 0;  // batch * input pixels the image buffers were sized for
+  // lazy matrix memory: C_base read once per step, rewritten once per `lazy_period` steps (see mlstm_lazy.hip)
+  int lazy_mode = 2;        // 0 materialised, 1 lazy, 2 auto (LRAM_STATE / lram_set_state_mode)
+  bool lazy = false;        // effective choice for the current batch (decided in state_alloc / set_state_mode)
+  bool lazy_ready = false;  // buffers allocated for the current batch
+  int lazy_period = 13;
+  int gn_fuse = 2;          // LRAM_GN_FUSE: output group norm + skip in the read pass's epilogue, gate in proj_down's
+                            // operand staging.  0 off, 1 on, 2 auto = on from 2048 env slots (round 3, same box, two
+                            // rounds: 391.1k / 393.5k off vs 395.8k / 397.5k on at 4096 slots; 1024 slots: -0.4 %)
+  bool mamba_dt_fuse = true;  // LRAM_MAMBA_DT_FUSE: dt_proj inside the selective-state-update kernel (d_state 16, dt_rank <= 64)
+  int slstm_fused_rows = 512;  // LRAM_SLSTM_FUSED_ROWS: slices of slstm_fused_min .. this many envs (at sLSTM head dim <= 128; fewer above:
+                               // x 128 / head dim) take the one-launch sLSTM token kernel (0 = never)
+  int gemm_skinny_rows = 384;  // LRAM_GEMM_SKINNY_ROWS: GEMMs with 9 .. this many operand rows (half of it for weights above 600k elements) ...
+  static constexpr int slstm_gates_rows = 768;  // sLSTM gate projections (head dim <= 128) of up to this many rows on the few-row kernel as well
+  int gemm_skinny_min = 5;     // LRAM_GEMM_SKINNY_MIN: fewest operand rows (below: the GEMV path; 16M at 1 env 0.372 vs 0.410 ms, at 2 envs 0.443 vs 0.418)
+  static constexpr int gemm_skinny_k = 1024;  // ... and K up to this take the few-row kernel
+  static constexpr int fold_bubbles = 2;  // folds before the first read pass; the rest behind the sLSTM blocks, all on the state-pass
+                                          // stream (measured on one box: k = 0 -- own stream, one block ahead -- 364k, 1 367k, 2 368k,
+                                          // 3 367k, 4 366k env-steps/s)
+  int64_t lazy_step = 0;    // steps taken in lazy mode: fold phase and ping-pong parity
+  std::vector<int> lazy_bound;  // host-side upper bound of pending tokens per fold class (b % period)
+  bool lazy_dirty = false;      // a lazy step ran since the last materialise: windows may hold pending tokens
+  DevBuf LZ_COUNT;          // [2][B] int32 pending tokens per env
+  // State of individual env slots (slot_state.hip; lram_state_copy_slots / save / load): one segment per contiguous per-env
+  // piece of state, cut into chunks of kSlotChunk floats -- the record's segments first, then the lazy representation's.
+  // Built by slot_segments_build (state_alloc, lazy_alloc); the state pointers never change in between.
+  std::vector<SlotSeg> slot_segs;        // host copy
+  SlotSeg* slot_segs_dev = nullptr;
+  SlotChunk* slot_chunks_dev = nullptr;
+  int slot_n_chunks = 0, slot_n_rec_chunks = 0;
+  int32_t* slot_idx_dev = nullptr;       // device [2][B]: the index lists of the call under way (stream-ordered)
+  std::vector<int64_t> slot_c_off;       // record offset of block i's matrix memory (-1: not an mLSTM block)
+  bool slot_y_checked = false;           // some sLSTM block runs the f16x2 step form: a load range-checks its hidden planes
+  void drop_slot_segments() {
+    if (slot_segs_dev) (void)hipFree(slot_segs_dev);
+    if (slot_chunks_dev) (void)hipFree(slot_chunks_dev);
+    if (slot_idx_dev) (void)hipFree(slot_idx_dev);
+    slot_segs_dev = nullptr, slot_chunks_dev = nullptr, slot_idx_dev = nullptr;
+    slot_segs.clear(), slot_c_off.clear();
+    slot_n_chunks = slot_n_rec_chunks = 0;
+  }
+  // state + workspace
+  int B = 0;
+  std::vector<BlockState> st;
+  DevBuf X, XN, TOK, HID, U, Q, K, V, XA, H, G, SCAL, RY, LOGITS, RES, DTP;
+  DevBuf XN2;   // the norm output as f16x2 operand planes [2][B*T, D] f16 (pre-split projections): its own buffer -- a slice inside an
+                // sLSTM block uses XN as fp32 while another slice's mLSTM block holds planes
+  DevBuf GATES, AMAT, VEC;           // chunkwise mLSTM prefill work buffers (allocated with the first long chunk)
+  DevBuf SEQ_EMB;                    // state embeddings of a stored context [B, L, D] (lram_prefill)
+  int tok_cap = 0;                   // tokens per env the activation workspace holds (kMaxTokens until a prefill grows it)
+  bool chunk_prefill = true;         // LRAM_PREFILL_CHUNK=0: keep the token-sequential kernels for prefill
+  bool chunk_exact_fp32 = false;     // LRAM_PREFILL_CHUNK=2: chunkwise cell on the fp32-input matrix cores (the round 1-5 form)
+  // Chunk lanes of lram_prefill: consecutive chunks of a stored context alternate between two activation workspaces and two
+  // streams; block i of chunk c + 1 waits for block i of chunk c only (its recurrent state), so two chunks are in flight one
+  // block apart -- the matrix-core-bound projections of one beside the HBM-bound state passes of the other, and the
+  // token-sequential sLSTM launches of either hidden behind both (one env slice only; LRAM_PREFILL_CHUNK=3: off).
+  bool chunk_lanes = true;
+  static constexpr int kMaxLanes = 3;
+  static constexpr int n_lanes = 3;  // chunks in flight (206M, 64 envs x 512 timesteps, same box: 1 lane 385 ms, 2 lanes 326, 3 lanes 305, 4 lanes 303)
+  DevBuf twin[kMaxLanes - 1][21];    // further copies of the per-token activation workspace (see workspace_set())
+  std::vector<hipEvent_t> lane_ev[kMaxLanes];             // "block i of the lane's current chunk is done"
+  DevBuf SK;                         // split-K partial slabs: one slot per stream that may run a GEMM
+  static constexpr size_t kSplitKSlotElems = 6u << 20;  // 6 Mi floats (24 MiB) >= S*M*N for any GEMM the chooser splits
+  static constexpr int kSplitKSlots = 9;                 // caller's stream + up to 8 micro-batch streams
+  size_t ucols = 0, icols = 0;  // allocated row pitch of U and of Q/K/V/XA/H/G (slice offsets use these)
+  // graph replay
+  bool graph_mode = false;
+  bool graph_valid = false;
+  GraphKey graph_key{};
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t graph_exec = nullptr;
+  hipStream_t capture_stream = nullptr;  // capture needs a non-default stream; replay runs on the caller's
+  // micro-batch pipeline: env slices on their own streams, cell kernels serialised on hbm_stream
+  int n_micro = 0;  // 0 = auto
+  // reference-trajectory modes of the Mamba agent (lram_set_compat_mode)
+  int compat_repeat = 1;      // forwards per env-step: action dim i is read from forward min(i, repeat - 1)
+  // Repeated forwards share what does not depend on the recurrent state: the (s, rtg, r) token embeddings, and with them
+  // layer 0's add + RMSNorm and in_proj (identical inputs in every pass).  Pass 0 keeps them in X0 / U0; later passes skip
+  // the front end and layer 0's first stage (Pass::compat_pass / compat_passes: the pass under way).
+  DevBuf X0, U0;
+  bool compat_share = true;   // LRAM_COMPAT_SHARE=0: every repeated forward recomputes the front end and layer 0's in_proj
+  bool compat_stale = false;  // a reset re-initialises layer 0 only; layers >= 1 keep the previous episode's state
+  // action head, sampling mode (lram_set_sampling): the settings travel as kernel arguments; the draw counter is device memory,
+  // read by every head launch of an env-step and advanced once behind them (a replayed graph has frozen arguments)
+  bool sampling = false;
+  SampleArgs sample;             // .slot0 holds slot_base; a slice adds its first env slot
+  uint64_t* sample_draw = nullptr;
+  static constexpr int cell_unroll = 16;  // C rows in flight per thread of the materialised cell kernel
+  std::vector<hipStream_t> micro_streams;
+  hipStream_t hbm_stream = nullptr;
+  std::vector<hipEvent_t> sync_events, edge_events;   // engine-internal edges (device-scope fence) / fork + join with the caller's stream
+  size_t sync_used = 0, edge_used = 0;
+  bool event_device_scope = true;   // LRAM_EVENT_SCOPE=system: default (system-scope) events for the internal edges too
+  // profiling of the dominant recurrent kernel
+  bool prof_on = false;
+  int prof_every = 1;       // lram_profile_begin_sampled: every n-th lram_step is timed (its launches carry the event pairs)
+  int64_t prof_calls = 0;   // lram_step calls since profiling was armed
+  bool prof_live = true;    // the call under way is one of the timed ones (set by prof_tick at every entry that launches the stack, and
+                            // by the lram_profile_* entries outside any call: the one per-call value that stays in the engine)
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
+  std::vector<uint8_t> prof_aux;  // 1: the pair times a fold launch (adds to the total, is not a state-pass launch)
+  size_t prof_used = 0;
+
+  ~lram_engine() {
+    drop_graph();
+    if (capture_stream) (void)hipStreamDestroy(capture_stream);
+    if (hbm_stream) (void)hipStreamDestroy(hbm_stream);
+    for (hipStream_t ms : micro_streams) (void)hipStreamDestroy(ms);
+    for (hipEvent_t ev : sync_events) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : edge_events) (void)hipEventDestroy(ev);
+    for (auto& v : lane_ev)
+      for (hipEvent_t ev : v) (void)hipEventDestroy(ev);
+    for (auto& e : prof_events) {
+      (void)hipEventDestroy(e.first);
+      (void)hipEventDestroy(e.second);
+    }
+    for (auto& kv : weights) kv.second.release();
+    drop_splits();
+    release_state();
+    if (sample_draw) (void)hipFree(sample_draw);
+    drop_slot_table();
+  }
+  void drop_slot_table() {
+    if (slot_dev) (void)hipFree(slot_dev);
+    if (slot_img_list) (void)hipFree(slot_img_list);
+    slot_dev = nullptr, slot_img_list = nullptr;
+    slot_flags.clear(), slot_act.clear(), slot_img_prefix.clear();
+    slot_n_image = 0, slot_has_discrete = false, slot_table = false;
+  }
+  void drop_splits() {
+    for (auto& kv : split) (void)hipFree(kv.second.p);
+    split.clear();
+    for (auto& kv : split16) (void)hipFree(kv.second.planes), (void)hipFree(kv.second.inv);
+    split16.clear();
+    for (DevBuf& b : dt_wt) b.release();
+    dt_wt.clear();
+    for (auto& kv : narrow) kv.second.release();
+    narrow.clear();
+    for (DevBuf& b : gate_coef) b.release();
+    gate_coef.clear();
+    for (DevBuf& b : slstm_rt2) b.release();
+    slstm_rt2.clear();
+    for (DevBuf& b : slstm_rinv) b.release();
+    slstm_rinv.clear();
+  }
+  void drop_graph() {
+    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+    if (graph) (void)hipGraphDestroy(graph);
+    graph_exec = nullptr;
+    graph = nullptr;
+    graph_valid = false;
+  }
+  void release_state() {
+    for (auto& s : st) {
+      s.s0.release();
+      s.n.release();
+      s.m.release();
+      s.conv.release();
+      s.wk.release();
+      s.wv.release();
+      s.coef.release();
+      s.gsc.release();
+      s.pw.release();
+    }
+    LZ_COUNT.release();
+    lazy_ready = false;
+    drop_slot_segments();
+    st.clear();
+    for (DevBuf* b : {&X, &XN, &TOK, &HID, &U, &Q, &K, &V, &XA, &H, &G, &SCAL, &RY, &LOGITS, &RES, &DTP, &SK, &GATES,
+                      &AMAT, &VEC, &SEQ_EMB, &IMG_EMB, &IMG_P, &IMG_X0, &IMG_X1, &IMG_T, &XN2, &ASCALE, &AMX_XN, &AMX_XA, &AMX_H, &X0, &U0})
+      b->release();
+    for (auto& t : twin)
+      for (DevBuf& b : t) b.release();
+    ascale_rows = 0;
+    img_cap = 0;
+    B = 0;
+    tok_cap = 0;
+  }
+  int dh() const { return cfg.inner / cfg.n_heads; }
+  int sdh() const { return cfg.d_model / cfg.n_heads; }
+};
+
+namespace lram::host {
+
+// A contiguous range of env slots processed on its own stream.  All activation buffers are indexed by
+// row b*T + t, so a slice simply works on rows [b0*T, (b0+nb)*T) of the shared buffers.
+struct Slice {
+  int b0, nb;
+  hipStream_t s;
+};
+
+// What one call hands down to the kernels' launch sequence: built on the stack by the entry (step_launches, timesteps_launches,
+// lram_encoder_step) and passed by const& through run_stack -> run_*_stack -> the block functions.  Nothing of it outlives the call.
+struct Pass {
+  // what the caller handed in
+  const uint8_t* images = nullptr;   // lram_step_images / lram_step_slots: the call's frames
+  int img_c = 0, img_h = 0, img_w = 0;
+  bool slots = false;                // mixed front end (lram_step_slots)
+  // repeated forwards of the Mamba reference-trajectory mode: the forward under way, how many there are, and whether they
+  // share the token front end and layer 0's in_proj (compat_shares())
+  int compat_pass = 0, compat_passes = 1;
+  bool compat_shared = false;
+  // chunk lanes of lram_prefill: "block i of the chunk before this one is done" / "block i of this chunk is done"
+  const std::vector<hipEvent_t>* lane_wait = nullptr;
+  const std::vector<hipEvent_t>* lane_rec = nullptr;
+  int n_slices = 1;                  // env slices of the stack pass under way (set by run_stack)
+};
+
+extern thread_local std::string g_last_error;   // lram_last_error (defined in engine.hip)
+
+// engine.hip
+void alloc_workspace(lram_engine* e, int tokens);
+void swap_workspace(lram_engine* e, int lane);
+bool twin_ready(lram_engine* e);
+int prefill_chunk_steps(lram_engine* e, int L);
+// engine_gemm.hip
+bool takes_skinny(const lram_engine* e, const GemmArgs& g);
+bool takes_skinny_with_norm(const lram_engine* e, const GemmArgs& g);
+bool f16x2_rows(const lram_engine* e, int rows, int n, int k);
+bool f16x2_weight(const lram_engine* e, const float* w, int ldw, GemmArgs* g);
+bool presplit_for(const lram_engine* e, const float* w, int rows, int n, int k);
+void gemm(lram_engine* e, GemmArgs& g, hipStream_t s);
+void make_split(lram_engine* e, const float* w, size_t n);
+// engine_streams.hip
+hipEvent_t new_event(const lram_engine* e, bool boundary);
+void prof_record(lram_engine* e, hipStream_t s, bool start, bool aux = false);
+void prof_tick(lram_engine* e);
+hipEvent_t ring_event(lram_engine* e, bool boundary = false);
+void stream_after(lram_engine* e, hipStream_t dst, hipStream_t src, bool boundary = false);
+std::vector<Slice> make_slices(lram_engine* e, hipStream_t s, hipStream_t* hbm);
+void fork_slices(lram_engine* e, const std::vector<Slice>& sl, hipStream_t hbm, hipStream_t s);
+void join_slices(lram_engine* e, const std::vector<Slice>& sl, hipStream_t hbm, hipStream_t s);
+// engine_xlstm.hip, engine_mamba.hip
+void lazy_materialize(lram_engine* e, hipStream_t s);
+void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* reset, const std::vector<Slice>& sl, hipStream_t hbm);
+void run_mamba_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* reset, const std::vector<Slice>& sl);
+
+// One mLSTM block's matrix memory over the batch, in bytes: what the lazy / side-stream-fold / two-slice thresholds compare.
+inline double mlstm_block_bytes(const lram_engine* e) {
+  const double dh = (double)e->cfg.inner / e->cfg.n_heads;
+  return (double)e->B * e->cfg.n_heads * dh * dh * 4.0;
+}
+
+inline bool lazy_active(const lram_engine* e, int T) {
+  return e->lazy && e->lazy_ready && !e->graph_mode && T >= 1 && T <= 4;
+}
+
+inline int stream_slot(const lram_engine* e, hipStream_t s) {  // split-K slab / row-maximum region of the stream a GEMM runs on
+  for (size_t i = 0; i < e->micro_streams.size() && i + 1 < (size_t)lram_engine::kSplitKSlots; ++i)
+    if (e->micro_streams[i] == s) return (int)i + 1;
+  return 0;
+}
+
+inline void count_gemm(lram_engine* e, int family, const GemmArgs& g) {
+  e->gemm_counts[family] += 1.0;
+  e->gemm_counts[4 + family] += 2.0 * g.m * g.n * g.k * g.nb1 * g.nb2;
+}
+
+template <typename Fn>
+int32_t guarded(Fn&& fn) {
+  try {
+    fn();
+    g_last_error.clear();
+    return 0;
+  } catch (const std::exception& ex) {
+    g_last_error = ex.what();
+    return 1;
+  } catch (...) {
+    g_last_error = "lram: unknown error";
+    return 1;
+  }
+}
+
+}  // namespace lram::host

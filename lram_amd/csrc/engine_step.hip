@@ -1,0 +1,522 @@
+// One call from its inputs to its actions: the image and token front ends, the block stack, the action head; env-steps, repeated
+// forwards, stored contexts in chunks (lram_step, lram_step_images, lram_step_slots, lram_prefill, lram_encoder_step).
+// Calls the stacks, gemm and the streams.
+#include "engine.h"
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------
+// block stack on X [B*T, D] (in place residual stream) -> HID [B*T, D]
+// ---------------------------------------------------------------------------------------------
+void run_stack(lram_engine* e, Pass pass, int T, const uint8_t* reset, const std::vector<Slice>& sl, hipStream_t hbm) {
+  pass.n_slices = (int)sl.size();
+  if (e->cfg.backbone == LRAM_BACKBONE_MAMBA)
+    run_mamba_stack(e, pass, T, reset, sl);
+  else
+    run_xlstm_stack(e, pass, T, reset, sl, hbm);
+}
+
+// uint8 frames [B, C, H, W] -> state-token embeddings [B, d_model] (reference: embed_image(x / 255),
+// online_decision_transformer_model.py:523-526 + image_encoders.py:58-66)
+// Image work buffers for B frames of H x W (synchronises when it has to grow them: never called between a fork and a join)
+void image_buffers(lram_engine* e, int H, int W) {
+  const size_t B = e->B, px = B * H * W;
+  if (px <= e->img_cap) return;
+  LRAM_HIP_CHECK(hipDeviceSynchronize());
+  const size_t hp = (H - 1) / 2 + 1, wp = (W - 1) / 2 + 1;
+  e->IMG_P.alloc(B * 16 * H * W);       // stage-1 conv output before its pool (the largest tensor)
+  e->IMG_X0.alloc(B * 32 * hp * wp);    // pooled maps never exceed 32 channels at half resolution
+  e->IMG_X1.alloc(B * 32 * hp * wp);
+  e->IMG_T.alloc(B * 32 * hp * wp);
+  e->img_cap = px;
+}
+// ... and the rows the frames of an env-step are embedded into (lram_step_images, lram_step_slots)
+void step_image_buffers(lram_engine* e, int H, int W) {
+  image_buffers(e, H, W);
+  if (e->IMG_EMB.n < (size_t)e->B * e->cfg.d_model) {
+    LRAM_HIP_CHECK(hipDeviceSynchronize());
+    e->IMG_EMB.alloc((size_t)e->B * e->cfg.d_model);
+  }
+}
+
+// envs b0 .. b0 + nb - 1 (`images` / `out` point at env b0's frame / row; every env slice keeps to its own fixed region of the
+// work buffers, so slices at different stages of the CNN never touch each other's maps)
+void embed_images(lram_engine* e, const uint8_t* images, int C, int H, int W, float* out, hipStream_t s, int b0 = 0, int nb = -1) {
+  LRAM_REQUIRE(e->img_lin_w != nullptr, "lram_embed_images: no embed_image.* weights were uploaded");
+  LRAM_REQUIRE(C == e->img_channels, "lram_embed_images: channel count does not match embed_image.cnn.0.conv.weight");
+  const int B = nb < 0 ? e->B : nb, D = e->cfg.d_model;
+  int h = H, w = W;
+  for (int k = 0; k < 3; ++k) h = (h - 1) / 2 + 1, w = (w - 1) / 2 + 1;
+  LRAM_REQUIRE(32 * h * w == e->img_flat, "lram_embed_images: image size does not match embed_image.linear.0.weight");
+  LRAM_REQUIRE((size_t)e->B * H * W <= e->img_cap, "image work buffers not allocated");
+  const size_t hp0 = (H - 1) / 2 + 1, wp0 = (W - 1) / 2 + 1;
+  float* const P = e->IMG_P.p + (size_t)b0 * 16 * H * W;
+  float* const X0 = e->IMG_X0.p + (size_t)b0 * 32 * hp0 * wp0;
+  float* const X1 = e->IMG_X1.p + (size_t)b0 * 32 * hp0 * wp0;
+  float* const Tb = e->IMG_T.p + (size_t)b0 * 32 * hp0 * wp0;
+  const void* in = images;
+  int in_u8 = 1;
+  h = H, w = W;
+  for (int sidx = 0; sidx < 3; ++sidx) {
+    const lram_engine::ImgConv* cv = e->img_conv[sidx];
+    auto conv = [&](const lram_engine::ImgConv& c, const void* src, int u8, int relu_in, const float* res, float* dst,
+                    int relu_out) {
+      Conv3x3Args a;
+      a.in = src, a.w = c.w, a.bias = c.b, a.residual = res, a.out = dst;
+      a.B = B, a.CIN = c.cin, a.COUT = c.cout, a.H = h, a.W = w, a.in_relu = relu_in, a.out_relu = relu_out, a.in_u8 = u8;
+      launch_conv3x3(a, s);
+    };
+    conv(cv[0], in, in_u8, 0, nullptr, P, 0);
+    launch_maxpool3s2(P, X0, (int64_t)B * cv[0].cout, h, w, s);
+    h = (h - 1) / 2 + 1, w = (w - 1) / 2 + 1;
+    conv(cv[1], X0, 0, 1, nullptr, Tb, 0);
+    conv(cv[2], Tb, 0, 1, X0, X1, 0);
+    conv(cv[3], X1, 0, 1, nullptr, Tb, 0);
+    conv(cv[4], Tb, 0, 1, X1, X0, sidx == 2 ? 1 : 0);  // act_flatten's ReLU on the last map
+    in = X0;
+    in_u8 = 0;
+  }
+  // stage s > 0 reads X0 and writes P, then pools back into X0: no aliasing within a launch
+  GemmArgs g;
+  g.a = X0, g.lda = e->img_flat, g.w = e->img_lin_w, g.ldw = e->img_flat, g.c = out, g.ldc = D;
+  g.bias = e->img_lin_b, g.m = B, g.n = D, g.k = e->img_flat;
+  gemm(e, g, s);
+  launch_relu(out, (int64_t)B * D, s);
+}
+
+// The (state, rtg, reward) inputs of a call: [B, L, .] / [B, L] row-major (L = 1: one env-step).
+struct Inputs {
+  const float* obs;
+  int emb;   // obs holds state-token embeddings [., d_model] instead of observations [., state_dim]
+  const float *rtg, *rew;
+  int L;
+};
+
+// Token front end of one env slice for the chunk of Lc timesteps that starts at timestep l: embeds the chunk's tokens into the
+// slice's rows of X and applies embed_ln.  seq_emb: the state embeddings of a stored context, made ahead of the chunks.
+void embed_tokens(lram_engine* e, const Pass& pass, const Inputs& in, const float* seq_emb, const Slice& x, int l, int Lc) {
+  const lram_config& c = e->cfg;
+  const int D = c.d_model, T = c.tokens_per_step, Tc = T * Lc, L = in.L, emb = in.emb;
+  const int64_t obs_w = emb ? D : c.state_dim;
+  const float *obs = in.obs, *rtg = in.rtg, *rew = in.rew;
+  const size_t r0 = (size_t)x.b0 * Tc, b0 = x.b0;
+  float* X = e->X.p + r0 * D;
+  if (seq_emb != nullptr) {  // stored context: the chunk's token rows in one launch
+    launch_embed_chunk(X, seq_emb + (b0 * L + l) * D, (int64_t)L * D, rtg + b0 * L + l, rew + b0 * L + l, L, e->w_rtg, e->b_rtg,
+                       e->w_rew, e->b_rew, x.nb, Lc, Tc, D, x.s);
+    launch_row_norm(X, D, X, D, e->eln_g, e->eln_b, x.nb * Tc, D, 1e-5f, 0, x.s);
+    return;
+  }
+  // lram_step_slots: the slice's frames are the contiguous range [k0, k0 + nk) of the call's frames (frames come in slot
+  // order); they go through the CNN into compact rows of IMG_EMB, every slice in its own region of the CNN work buffers
+  const int k0 = pass.slots ? e->slot_img_prefix[b0] : 0;
+  const int nk = pass.slots ? e->slot_img_prefix[b0 + x.nb] - k0 : 0;
+  const size_t frame = (size_t)pass.img_c * pass.img_h * pass.img_w;
+  if (pass.slots) {
+    if (nk > 0)
+      embed_images(e, pass.images + (size_t)k0 * frame, pass.img_c, pass.img_h, pass.img_w, e->IMG_EMB.p + (size_t)k0 * D, x.s, k0, nk);
+  } else if (pass.images != nullptr)   // lram_step_images: this slice's frames -> its rows of `obs` (= IMG_EMB), on its own stream
+    embed_images(e, pass.images + b0 * frame, pass.img_c, pass.img_h, pass.img_w, e->IMG_EMB.p + b0 * D, x.s, (int)b0, x.nb);
+  for (int j = 0; j < Lc; ++j) {
+    const float* o = obs + (b0 * L + l + j) * obs_w;
+    float* Xj = X + (size_t)(T * j) * D;  // token slots 3j .. 3j+2 of every env row group
+    if (pass.slots) {   // (L == 1) state Linear over the slice's rows, then the image slots' token 0 from the CNN rows
+      if (nk < x.nb) {
+        GemmArgs ge;
+        ge.a = o, ge.lda = c.state_dim, ge.w = e->w_state, ge.ldw = c.state_dim, ge.c = Xj;
+        ge.ldc = (int64_t)Tc * D, ge.bias = e->b_state, ge.m = x.nb, ge.n = D, ge.k = c.state_dim;
+        gemm(e, ge, x.s);
+      }
+      launch_scatter_token0_indexed(e->X.p, e->IMG_EMB.p + (size_t)k0 * D, e->slot_img_list + k0, nk, e->B, Tc, D, x.s);
+    } else if (emb) {
+      launch_scatter_token0(Xj, o, (int64_t)L * D, x.nb, Tc, D, x.s);
+    } else {
+      GemmArgs ge;
+      ge.a = o, ge.lda = (int64_t)L * c.state_dim, ge.w = e->w_state, ge.ldw = c.state_dim, ge.c = Xj;
+      ge.ldc = (int64_t)Tc * D, ge.bias = e->b_state, ge.m = x.nb, ge.n = D, ge.k = c.state_dim;
+      gemm(e, ge, x.s);
+    }
+    // (a single timestep per call: the scalar tokens are built by the embed_ln launch below)
+    if (Lc > 1 || T != 3)
+      launch_embed_scalars(Xj, rtg + b0 * L + l + j, rew + b0 * L + l + j, L, e->w_rtg, e->b_rtg, e->w_rew, e->b_rew,
+                           x.nb, Tc, D, x.s);
+  }
+  // embed_ln in place; single env-steps of small batches also keep a copy for lram_get_taps (written by the same launch)
+  ScalarTokens stok;
+  const bool stok_on = Lc == 1 && T == 3;
+  if (stok_on) {
+    stok.rtg = rtg + b0 * L + l, stok.rew = rew + b0 * L + l, stok.in_stride = L, stok.T = T;
+    stok.w_rtg = e->w_rtg, stok.b_rtg = e->b_rtg, stok.w_rew = e->w_rew, stok.b_rew = e->b_rew;
+  }
+  launch_row_norm(X, D, X, D, e->eln_g, e->eln_b, x.nb * Tc, D, 1e-5f, 0, x.s,
+                  (L == 1 && e->B <= kTokenTapMaxBatch) ? e->TOK.p + r0 * D : nullptr, nullptr, stok_on ? &stok : nullptr);
+}
+
+// Action head on the last timestep of the last chunk (Tc tokens per env, last_steps timesteps): logits per env slice, then
+// argmax or a sampled draw.  What discrete = LRAM_HEAD_PER_SLOT needs was checked by the entry (check_head_mode).
+void action_head(lram_engine* e, const Pass& pass, const std::vector<Slice>& sl, int Tc, int last_steps, int discrete,
+                 float* actions, int32_t* tokens) {
+  const lram_config& c = e->cfg;
+  const int D = c.d_model, T = c.tokens_per_step;
+  const int64_t nlog = (int64_t)c.act_dim * c.n_vocab;
+  const int pred = T * (last_steps - 1) + c.pred_token;  // rtg token of the last timestep in the last chunk
+  // shared repeated forwards: pass p only has to produce action dim p (the last pass every dim from its own on), so
+  // the head evaluates that column block of action_net alone
+  const int col_begin = pass.compat_pass;
+  const int col_end = (pass.compat_shared && col_begin + 1 < pass.compat_passes) ? col_begin + 1 : c.act_dim;
+  const int col0 = pass.compat_shared ? col_begin : 0;
+  const bool per_slot = discrete == LRAM_HEAD_PER_SLOT;
+  for (const Slice& x : sl) {
+    const size_t r0 = (size_t)x.b0 * Tc, b0 = x.b0;
+    const uint8_t* sf = per_slot ? e->slot_dev + b0 : nullptr;
+    const uint8_t* sa = per_slot ? e->slot_dev + e->B + b0 : nullptr;
+    GemmArgs gh;
+    gh.a = e->HID.p + (r0 + pred) * D, gh.lda = (int64_t)Tc * D, gh.w = e->w_head + (size_t)col0 * c.n_vocab * D, gh.ldw = D;
+    gh.c = e->LOGITS.p + b0 * nlog + (size_t)col0 * c.n_vocab, gh.ldc = nlog, gh.bias = e->b_head + (size_t)col0 * c.n_vocab;
+    gh.m = x.nb, gh.n = (col_end - col0) * c.n_vocab, gh.k = D;
+    gemm(e, gh, x.s);
+    if (e->sampling) {
+      SampleArgs sp = e->sample;
+      sp.slot0 += b0, sp.draw = e->sample_draw;
+      launch_action_sample(e->LOGITS.p + b0 * nlog, actions + b0 * c.act_dim, tokens ? tokens + b0 * c.act_dim : nullptr,
+                           x.nb, c.act_dim, c.n_vocab, c.n_discrete, c.action_channels, c.tok_min, c.tok_max, discrete,
+                           col_begin, col_end, sp, x.s, sf, sa);
+      continue;
+    }
+    launch_action_argmax(e->LOGITS.p + b0 * nlog, actions + b0 * c.act_dim,
+                         tokens ? tokens + b0 * c.act_dim : nullptr, x.nb, c.act_dim, c.n_vocab, c.n_discrete,
+                         c.action_channels, c.tok_min, c.tok_max, discrete, col_begin, x.s, col_end, sf, sa);
+  }
+}
+
+// L consecutive timesteps for every env slot (L = 1: one env-step).  The reset mask applies before the first timestep; the
+// action head runs on the last timestep only (and only if an output buffer is given).  One fork / join of the slice streams
+// brackets the whole call -- of repeated forwards (call.compat_passes > 1): one fork ahead of the first, one join behind the last.
+void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, const uint8_t* reset, int discrete, float* actions,
+                        int32_t* tokens, hipStream_t s) {
+  const lram_config& c = e->cfg;
+  const int D = c.d_model, T = c.tokens_per_step, L = in.L;
+  e->sync_used = 0, e->edge_used = 0;
+  // Stored context is consumed in chunks: every block then reads and writes its recurrent state once per chunk
+  // instead of once per timestep.  Up to 4 timesteps (12 tokens) per chunk through the token-sequential kernels,
+  // up to 21 (63 tokens) through the chunkwise matrix-core kernels (mlstm_chunk.hip).
+  const int kChunk = L > 1 ? prefill_chunk_steps(e, L) : 1;
+  if (L > 1 || !lazy_active(e, T)) lazy_materialize(e, s);  // stored contexts go through the materialised kernels
+  // Stored contexts: the state embeddings of ALL timesteps as one GEMM ahead of the chunks (rows b * L + l, as the input lies),
+  // instead of one few-row GEMM per timestep (206M, 64 envs x 512 timesteps: 1024 launches of 12-26 us -> 1 + one per chunk)
+  const float* seq_emb = nullptr;
+  if (L > 1 && T == 3 && D % 4 == 0 && !call.compat_shared) {
+    if (in.emb) {
+      seq_emb = in.obs;
+    } else if ((size_t)e->B * L * D <= ((size_t)1 << 29)) {   // <= 2 GiB
+      if (e->SEQ_EMB.n < (size_t)e->B * L * D) {
+        LRAM_HIP_CHECK(hipDeviceSynchronize());
+        e->SEQ_EMB.alloc((size_t)e->B * L * D);
+      }
+      GemmArgs ge;
+      ge.a = in.obs, ge.lda = c.state_dim, ge.w = e->w_state, ge.ldw = c.state_dim, ge.c = e->SEQ_EMB.p, ge.ldc = D;
+      ge.bias = e->b_state, ge.m = e->B * L, ge.n = D, ge.k = c.state_dim;
+      gemm(e, ge, s);
+      seq_emb = e->SEQ_EMB.p;
+    }
+  }
+  // chunk lanes (see lram_engine::chunk_lanes): the last chunk -- the one the action head reads -- is on lane 0 = the primary
+  // workspace and the caller's stream.  Where they apply they replace the automatic env slices of large batches as well: whole-batch
+  // launches, three chunks in flight (16M, 1024 envs x 252 timesteps: 224.4 -> 215.5 ms; 206M, 512 envs x 63: 295.3 -> 274.0 ms).
+  const int n_chunks = (L + kChunk - 1) / kChunk;
+  // (Mamba's stored contexts and the xLSTM geometries without a chunkwise form go through the token-sequential kernels in chunks
+  // of 4 timesteps: the lanes apply to them as they are)
+  const bool lanes = e->n_micro <= 1 && n_chunks >= 2 && e->chunk_lanes && !e->graph_mode && !call.compat_shared && twin_ready(e);
+  hipStream_t hbm = s;
+  const std::vector<Slice> sl = lanes ? std::vector<Slice>{Slice{0, e->B, s}} : make_slices(e, s, &hbm);
+  const bool multi = sl.size() > 1;
+  if (multi && call.compat_pass == 0) fork_slices(e, sl, hbm, s);
+  const int NL = lanes ? e->n_lanes : 1;
+  hipStream_t lane_s[lram_engine::kMaxLanes] = {s, s, s};
+  if (lanes) {
+    while ((int)e->micro_streams.size() < NL - 1) {
+      hipStream_t ns;
+      LRAM_HIP_CHECK(hipStreamCreateWithFlags(&ns, hipStreamNonBlocking));
+      e->micro_streams.push_back(ns);
+    }
+    for (int k = 1; k < NL; ++k) lane_s[k] = e->micro_streams[k - 1];
+    for (auto& v : e->lane_ev)
+      while ((int)v.size() < c.n_blocks) v.push_back(new_event(e, false));
+    for (int k = 1; k < NL; ++k) stream_after(e, lane_s[k], s, true);
+  }
+  int Tc = T, last_steps = 1;
+  for (int l = 0, ci = 0; l < L; l += kChunk, ++ci) {
+    const int Lc = std::min(kChunk, L - l);
+    Tc = T * Lc;
+    last_steps = Lc;
+    const int lane = (n_chunks - 1 - ci) % NL;
+    const std::vector<Slice> lane_sl = {Slice{0, e->B, lane_s[lane]}};
+    const std::vector<Slice>& use = lanes ? lane_sl : sl;
+    // (scope guard: an exception out of a launch below must not leave the engine on a lane's workspace)
+    struct LaneScope {
+      lram_engine* e;
+      int lane;
+      ~LaneScope() {
+        if (lane) swap_workspace(e, lane);
+      }
+    } lane_scope{e, lane};
+    if (lane) swap_workspace(e, lane);
+    // (shared repeated forwards: the tokens of this env-step were embedded by pass 0 -- X0 / U0)
+    if (!(call.compat_shared && call.compat_pass > 0))
+      for (const Slice& x : use) embed_tokens(e, call, in, seq_emb, x, l, Lc);
+    Pass pass = call;
+    if (lanes) pass.lane_wait = ci > 0 ? &e->lane_ev[(lane + 1) % NL] : nullptr, pass.lane_rec = &e->lane_ev[lane];
+    run_stack(e, pass, Tc, l == 0 ? reset : nullptr, use, lanes ? lane_s[lane] : hbm);
+  }
+  for (int k = 1; k < NL; ++k) stream_after(e, s, lane_s[k], true);
+  if (actions != nullptr) action_head(e, call, sl, Tc, last_steps, discrete, actions, tokens);
+  if (multi && call.compat_pass == call.compat_passes - 1) join_slices(e, sl, hbm, s);
+}
+
+// Sampling mode: one draw per action-producing call.  Launched on the caller's stream behind the join of the env slices
+// (and behind the last of the repeated forwards), so that every row of the call has read the same count; the next call's
+// slices fork from this stream and see the new one.  In a captured step it is one more node on the graph's single chain.
+void sample_draw_advance(lram_engine* e, hipStream_t s) {
+  if (e->sampling) launch_sample_advance(e->sample_draw, s);
+}
+
+// discrete = LRAM_HEAD_PER_SLOT: what the call needs, checked before anything is launched (the recurrent state is untouched
+// by a refused call).
+void check_head_mode(const lram_engine* e, int discrete, const char* who) {
+  if (discrete != LRAM_HEAD_PER_SLOT) return;
+  const std::string w(who);
+  LRAM_REQUIRE(e->slot_table, w + ": LRAM_HEAD_PER_SLOT needs a slot table (lram_set_slot_table)");
+  LRAM_REQUIRE(e->compat_repeat <= 1, w + ": LRAM_HEAD_PER_SLOT cannot be combined with the Mamba repeated-forward mode "
+                                          "(mamba_repeat > 1 advances the state once per action dim of the env, which differs per slot)");
+  LRAM_REQUIRE(!(e->sampling && e->slot_has_discrete && e->sample.top_k > e->cfg.n_discrete),
+               w + ": sampling top_k exceeds n_discrete and the slot table holds a discrete slot");
+}
+
+// Do the repeated forwards of the Mamba reference-trajectory mode share the token front end and layer 0's in_proj?
+bool compat_shares(const lram_engine* e, int discrete) {
+  const int passes = discrete ? 1 : std::max(1, std::min(e->compat_repeat, e->cfg.act_dim));
+  return passes > 1 && e->cfg.backbone == LRAM_BACKBONE_MAMBA && e->compat_share && e->cfg.n_blocks >= 2;
+}
+// ... then pass 0 keeps them in X0 / U0.  Called by lram_step BEFORE any stream capture begins: hipMalloc on a thread with
+// an active capture fails with hipErrorStreamCaptureUnsupported and invalidates the capture (graph mode + repeated forwards).
+void compat_prepare(lram_engine* e, int discrete) {
+  if (e->B <= 0 || !compat_shares(e, discrete)) return;
+  const size_t bt = (size_t)e->B * e->cfg.tokens_per_step;
+  if (e->X0.n < bt * e->cfg.d_model) e->X0.alloc(bt * e->cfg.d_model);
+  if (e->U0.n < bt * 2 * e->cfg.d_inner) e->U0.alloc(bt * 2 * e->cfg.d_inner);
+}
+
+void step_launches(lram_engine* e, Pass pass, const Inputs& in, const uint8_t* reset, int discrete, float* actions,
+                   int32_t* tokens, hipStream_t s) {
+  // compat_repeat (reference DiscreteDecisionMamba.get_action_pred, src/algos/decision_mamba.py:107-122): the same
+  // (state, rtg, reward) tokens go through the stack once per action dim with the cache on, and action dim i is the
+  // prediction of forward i.  Forward p writes action columns >= p, so column i keeps forward min(i, repeat - 1).
+  pass.compat_passes = discrete ? 1 : std::max(1, std::min(e->compat_repeat, e->cfg.act_dim));
+  pass.compat_shared = compat_shares(e, discrete);
+  if (pass.compat_shared) {  // (allocated by compat_prepare ahead of this call: never inside a stream capture)
+    const size_t bt = (size_t)e->B * e->cfg.tokens_per_step;
+    LRAM_REQUIRE(e->X0.n >= bt * e->cfg.d_model && e->U0.n >= bt * 2 * e->cfg.d_inner,
+                 "shared repeated forwards: workspace not prepared");
+  }
+  // every forward runs on the same slice streams: a slice's forward p + 1 follows its forward p in stream order (state, X0 / U0,
+  // logits are per slice), so the slices are forked once and joined once instead of draining the two-slice pipeline per forward
+  // (Mamba-48M at 2048 slots, 4 forwards per env-step, same box: 140.35k -> 141.0k env-steps/s)
+  for (pass.compat_pass = 0; pass.compat_pass < pass.compat_passes; ++pass.compat_pass)
+    timesteps_launches(e, pass, in, pass.compat_pass == 0 ? reset : nullptr, discrete, actions, tokens, s);
+  sample_draw_advance(e, s);
+}
+
+// What the entries that run (state, rtg, reward) env-steps share: the state is allocated, the front end fits the geometry, the
+// device is current, and the call counts for a sampled profile.
+void step_entry(lram_engine* e, const char* who) {
+  const std::string w(who);
+  LRAM_REQUIRE(e && e->B > 0, w + ": state not allocated (call lram_state_alloc)");
+  LRAM_REQUIRE(e->cfg.tokens_per_step == 3, w + ": the (state, rtg, reward) front end needs tokens_per_step == 3");
+  LRAM_HIP_CHECK(hipSetDevice(e->device));
+  prof_tick(e);
+}
+
+}  // namespace
+
+// ---- C ABI -----------------------------------------------------------------------------------------------------------
+extern "C" {
+
+int32_t lram_step(lram_engine* e, const float* dev_obs, int32_t obs_is_embedding, const float* dev_rtg,
+                  const float* dev_reward, const uint8_t* dev_reset_mask, int32_t discrete, float* dev_actions,
+                  int32_t* dev_tokens, void* stream) {
+  return guarded([&] {
+    step_entry(e, "lram_step");
+    LRAM_REQUIRE(dev_obs && dev_rtg && dev_reward && dev_actions, "lram_step: null device pointer");
+    check_head_mode(e, discrete, "lram_step");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    compat_prepare(e, discrete);  // (workspace of the shared repeated forwards: outside any capture)
+    const Inputs in{dev_obs, obs_is_embedding, dev_rtg, dev_reward, 1};
+    if (e->graph_mode && !(e->prof_on && e->prof_live)) {  // (a sampled run's un-timed steps keep the graph path)
+      GraphKey key{};
+      key.obs = dev_obs, key.rtg = dev_rtg, key.rew = dev_reward, key.mask = dev_reset_mask, key.act = dev_actions;
+      key.tok = dev_tokens, key.emb = obs_is_embedding, key.discrete = discrete, key.B = e->B, key.stream = s;
+      if (!(e->graph_valid && key == e->graph_key)) {
+        e->drop_graph();
+        if (!e->capture_stream) LRAM_HIP_CHECK(hipStreamCreateWithFlags(&e->capture_stream, hipStreamNonBlocking));
+        hipStream_t cs = e->capture_stream;
+        LRAM_HIP_CHECK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+        try {
+          step_launches(e, Pass{}, in, dev_reset_mask, discrete, dev_actions, dev_tokens, cs);
+        } catch (...) {
+          hipGraph_t g = nullptr;
+          (void)hipStreamEndCapture(cs, &g);
+          if (g) (void)hipGraphDestroy(g);
+          throw;
+        }
+        LRAM_HIP_CHECK(hipStreamEndCapture(cs, &e->graph));
+        LRAM_HIP_CHECK(hipGraphInstantiate(&e->graph_exec, e->graph, nullptr, nullptr, 0));
+        e->graph_key = key;
+        e->graph_valid = true;
+      }
+      LRAM_HIP_CHECK(hipGraphLaunch(e->graph_exec, s));
+    } else {
+      step_launches(e, Pass{}, in, dev_reset_mask, discrete, dev_actions, dev_tokens, s);
+    }
+  });
+}
+
+int32_t lram_step_images(lram_engine* e, const uint8_t* dev_images, int32_t channels, int32_t height, int32_t width,
+                         const float* dev_rtg, const float* dev_reward, const uint8_t* dev_reset_mask, int32_t discrete,
+                         float* dev_actions, int32_t* dev_tokens, void* stream) {
+  return guarded([&] {
+    step_entry(e, "lram_step_images");
+    LRAM_REQUIRE(dev_images && dev_rtg && dev_reward && dev_actions && channels > 0 && height > 0 && width > 0,
+                 "lram_step_images: bad argument");
+    LRAM_REQUIRE(e->img_lin_w != nullptr, "lram_step_images: no embed_image.* weights were uploaded");
+    check_head_mode(e, discrete, "lram_step_images");
+    step_image_buffers(e, height, width);
+    compat_prepare(e, discrete);
+    Pass pass;   // (the frames belong to this call only)
+    pass.images = dev_images, pass.img_c = channels, pass.img_h = height, pass.img_w = width;
+    // (launch-per-kernel path also in graph mode: a captured step would pin one frame buffer)
+    step_launches(e, pass, Inputs{e->IMG_EMB.p, 1, dev_rtg, dev_reward, 1}, dev_reset_mask, discrete, dev_actions, dev_tokens,
+                  static_cast<hipStream_t>(stream));
+  });
+}
+
+int32_t lram_step_slots(lram_engine* e, const float* dev_obs, const uint8_t* dev_images, int32_t channels, int32_t height,
+                        int32_t width, const float* dev_rtg, const float* dev_reward, const uint8_t* dev_reset_mask,
+                        float* dev_actions, int32_t* dev_tokens, void* stream) {
+  return guarded([&] {
+    step_entry(e, "lram_step_slots");
+    LRAM_REQUIRE(e->slot_table, "lram_step_slots: no slot table is set (lram_set_slot_table)");
+    const int n_img = e->slot_n_image;
+    LRAM_REQUIRE(dev_rtg && dev_reward && dev_actions, "lram_step_slots: null device pointer");
+    LRAM_REQUIRE(dev_obs != nullptr || n_img == e->B, "lram_step_slots: dev_obs is NULL and the table holds vector slots");
+    check_head_mode(e, LRAM_HEAD_PER_SLOT, "lram_step_slots");
+    if (n_img > 0) {
+      LRAM_REQUIRE(e->img_lin_w != nullptr, "lram_step_slots: the table holds image slots and no embed_image.* weights were uploaded");
+      LRAM_REQUIRE(dev_images && channels > 0 && height > 0 && width > 0, "lram_step_slots: the table holds image slots: frames needed");
+      LRAM_REQUIRE(e->cfg.d_model % 4 == 0, "lram_step_slots: image slots need d_model to be a multiple of 4");
+      step_image_buffers(e, height, width);
+    }
+    Pass pass;   // (the frames and the mixed front end belong to this call only)
+    pass.slots = true;
+    pass.images = n_img > 0 ? dev_images : nullptr, pass.img_c = channels, pass.img_h = height, pass.img_w = width;
+    // (launch-per-kernel path also in graph mode: a captured step would pin one frame buffer, as in lram_step_images)
+    step_launches(e, pass, Inputs{dev_obs, 0, dev_rtg, dev_reward, 1}, dev_reset_mask, LRAM_HEAD_PER_SLOT, dev_actions, dev_tokens,
+                  static_cast<hipStream_t>(stream));
+  });
+}
+
+int32_t lram_prefill(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
+                     const float* dev_reward_seq, int32_t timesteps, const uint8_t* dev_reset_mask, int32_t discrete,
+                     float* dev_actions, int32_t* dev_tokens, void* stream) {
+  return guarded([&] {
+    step_entry(e, "lram_prefill");
+    LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_prefill: null device pointer");
+    LRAM_REQUIRE(timesteps >= 1, "lram_prefill: timesteps must be >= 1");
+    if (dev_actions != nullptr) check_head_mode(e, discrete, "lram_prefill");
+    timesteps_launches(e, Pass{}, Inputs{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps}, dev_reset_mask,
+                       discrete, dev_actions, dev_tokens, static_cast<hipStream_t>(stream));
+    if (dev_actions != nullptr) sample_draw_advance(e, static_cast<hipStream_t>(stream));
+  });
+}
+
+int32_t lram_encoder_step(lram_engine* e, const float* dev_inputs_embeds, int32_t tokens,
+                          const uint8_t* dev_reset_mask, float* dev_hidden_out, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(e && e->B > 0, "lram_encoder_step: state not allocated");
+    LRAM_REQUIRE(dev_inputs_embeds && dev_hidden_out, "lram_encoder_step: null device pointer");
+    const bool chunk_ok = e->cfg.backbone == LRAM_BACKBONE_XLSTM && e->chunk_prefill && !e->graph_mode &&
+                          mlstm_chunk_supported(e->cfg.inner, e->cfg.n_heads, e->cfg.conv_k);
+    LRAM_REQUIRE((tokens >= 1 && tokens <= 4) || tokens == 6 || tokens == 9 || tokens == 12 ||
+                     (chunk_ok && tokens > kMaxTokens && tokens <= kChunkMaxTokens),
+                 "lram_encoder_step: tokens must be 1..4, 6, 9 or 12 (13..64 too on xLSTM geometries with a head dim "
+                 "that is a multiple of 128)");
+    LRAM_HIP_CHECK(hipSetDevice(e->device));
+    if (tokens > e->tok_cap) {
+      LRAM_HIP_CHECK(hipDeviceSynchronize());
+      alloc_workspace(e, kChunkMaxTokens);
+      LRAM_HIP_CHECK(hipDeviceSynchronize());
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    prof_tick(e);
+    const size_t bytes = sizeof(float) * (size_t)e->B * tokens * e->cfg.d_model;
+    if (!lazy_active(e, tokens)) lazy_materialize(e, s);
+    LRAM_HIP_CHECK(hipMemcpyAsync(e->X.p, dev_inputs_embeds, bytes, hipMemcpyDeviceToDevice, s));
+    e->sync_used = 0, e->edge_used = 0;
+    hipStream_t hbm;
+    const std::vector<Slice> sl = make_slices(e, s, &hbm);
+    if (sl.size() > 1) fork_slices(e, sl, hbm, s);
+    run_stack(e, Pass{}, tokens, dev_reset_mask, sl, hbm);
+    if (sl.size() > 1) join_slices(e, sl, hbm, s);
+    LRAM_HIP_CHECK(hipMemcpyAsync(dev_hidden_out, e->HID.p, bytes, hipMemcpyDeviceToDevice, s));
+  });
+}
+
+int32_t lram_get_taps(lram_engine* e, float* dev_tokens_embed, float* dev_hidden, float* dev_logits, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(e && e->B > 0, "lram_get_taps: state not allocated");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t btd = sizeof(float) * (size_t)e->B * e->cfg.tokens_per_step * e->cfg.d_model;
+    if (dev_tokens_embed) {
+      LRAM_REQUIRE(e->B <= kTokenTapMaxBatch,
+                   "lram_get_taps: the embed_ln token tap is kept for batches of up to 1024 env slots only (it costs a "
+                   "copy of the token buffer per step); pass NULL for it");
+      LRAM_HIP_CHECK(hipMemcpyAsync(dev_tokens_embed, e->TOK.p, btd, hipMemcpyDeviceToDevice, s));
+    }
+    if (dev_hidden) LRAM_HIP_CHECK(hipMemcpyAsync(dev_hidden, e->HID.p, btd, hipMemcpyDeviceToDevice, s));
+    if (dev_logits)
+      LRAM_HIP_CHECK(hipMemcpyAsync(dev_logits, e->LOGITS.p, sizeof(float) * e->LOGITS.n, hipMemcpyDeviceToDevice, s));
+  });
+}
+
+int32_t lram_sample_tokens(const float* dev_logits, int64_t rows, int32_t n, int64_t ld, double temperature, int32_t top_k,
+                           double top_p, const double* dev_uniform, int32_t* dev_tokens, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(dev_logits && dev_uniform && dev_tokens, "lram_sample_tokens: null device pointer");
+    LRAM_REQUIRE(temperature > 0.0 && temperature < (double)INFINITY, "lram_sample_tokens: temperature must be finite and > 0");
+    LRAM_REQUIRE(top_p >= 0.0 && top_p <= 1.0, "lram_sample_tokens: top_p must be in [0, 1]");
+    LRAM_REQUIRE(top_k >= 0 && top_k <= n, "lram_sample_tokens: top_k must be in 0 .. n");
+    LRAM_REQUIRE(ld == 0 || ld >= n, "lram_sample_tokens: ld must be 0 (one shared row) or >= n");
+    launch_sample_tokens(dev_logits, rows, n, ld, temperature, top_k, top_p, dev_uniform, dev_tokens,
+                         static_cast<hipStream_t>(stream));
+  });
+}
+
+int32_t lram_sample_uniforms(uint64_t seed, uint64_t slot_base, int64_t n_slots, int32_t act_dim, uint64_t draw,
+                             double* dev_out, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(dev_out != nullptr, "lram_sample_uniforms: null device pointer");
+    launch_sample_uniforms(seed, slot_base, n_slots, act_dim, draw, dev_out, static_cast<hipStream_t>(stream));
+  });
+}
+
+int32_t lram_embed_images(lram_engine* e, const uint8_t* dev_images, int32_t channels, int32_t height, int32_t width,
+                          float* dev_embeddings, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(e && e->B > 0, "lram_embed_images: state not allocated (call lram_state_alloc)");
+    LRAM_REQUIRE(dev_images && dev_embeddings && channels > 0 && height > 0 && width > 0, "lram_embed_images: bad argument");
+    LRAM_HIP_CHECK(hipSetDevice(e->device));
+    image_buffers(e, height, width);
+    embed_images(e, dev_images, channels, height, width, dev_embeddings, static_cast<hipStream_t>(stream));
+  });
+}
+
+}  // extern "C"

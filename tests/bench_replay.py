@@ -31,7 +31,7 @@ class ReplayError(AssertionError):
 
 
 def slice_bounds(spec, batch, micro, graph):
-    """[(first, end)] of the env slices one engine call runs, by the rule of make_slices (lram_amd/csrc/engine.hip): n = the
+    """[(first, end)] of the env slices one engine call runs, by the rule of make_slices (lram_amd/csrc/engine_streams.hip): n = the
     lram_set_micro_batches value, 0 = auto = two slices where one mLSTM block's matrix memory over the batch (B x n_heads x
     head_dim^2 x 4 bytes) is at least 512 MiB (xLSTM) or from 1024 env slots (Mamba), else one; graph mode always one; n is
     clamped to [1, min(B, 8)]; slices of B / n rows each, the first B % n of them one row more."""

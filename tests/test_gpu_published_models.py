@@ -185,7 +185,7 @@ def _assert_bit_identical(a, b, what):
 
 
 # (model, regime name, slots, state mode, env slices, f16x2 projections).  The thresholds these slot counts sit beside
-# (csrc/engine.hip): lazy from 128 MiB of one block's matrix memory over the batch, side-stream folds from 256 MiB, two env
+# (csrc/engine.hip, engine_xlstm.hip, engine_streams.hip, engine_gemm.hip): lazy from 128 MiB of one block's matrix memory over the batch, side-stream folds from 256 MiB, two env
 # slices from 512 MiB (xLSTM) / 1024 slots (Mamba); f16x2 below 256 operand rows from 96 rows for weights of >= 1.1 M elements
 # and from 48 rows for >= 2.5 M (48M: proj_up 3072 x 768 at 32 envs; 110M: proj_up 4096 x 1024 at 16 envs).
 REGIMES = {
