@@ -392,7 +392,9 @@ int32_t lram_sample_uniforms(uint64_t seed, uint64_t slot_base, int64_t n_slots,
  * Linear, ReLU).  Replaces `self.embed_image(state.float() / 255)` (online_decision_transformer_model.py:523-526;
  * module src/algos/models/image_encoders.py:10-131, built at multi_domain_discrete_dt_model.py:43-46).  Needs the
  * `embed_image.*` tensors (reference names) uploaded before lram_finalize; the result is passed to lram_step /
- * lram_prefill with obs_is_embedding = 1. */
+ * lram_prefill with obs_is_embedding = 1.  Any height, width >= 1 are accepted, square or not, provided the size after the
+ * three poolings (each extent (n - 1) / 2 + 1) matches embed_image.linear.0.weight, and the size may change between calls
+ * (so may it in lram_step_images and lram_step_slots); any other size is an error that names it. */
 int32_t lram_embed_images(lram_engine* e, const uint8_t* dev_images, int32_t channels, int32_t height, int32_t width,
                           float* dev_embeddings, void* stream);
 /* One env-step from image observations: lram_embed_images + lram_step(obs_is_embedding = 1) as ONE call -- what the reference's

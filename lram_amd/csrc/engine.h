@@ -167,7 +167,6 @@ struct lram_engine {
   int32_t* slot_img_list = nullptr;            // device [n_image_slots]
   int slot_n_image = 0;
   bool slot_has_discrete = false;
-  size_t img_cap = 0;  // batch * input pixels the image buffers were sized for
   // lazy matrix memory: C_base read once per step, rewritten once per `lazy_period` steps (see mlstm_lazy.hip)
   int lazy_mode = 2;        // 0 materialised, 1 lazy, 2 auto (LRAM_STATE / lram_set_state_mode)
   bool lazy = false;        // effective choice for the current batch (decided in state_alloc / set_state_mode)
@@ -341,7 +340,6 @@ struct lram_engine {
     for (auto& t : twin)
       for (DevBuf& b : t) b.release();
     ascale_rows = 0;
-    img_cap = 0;
     B = 0;
     tok_cap = 0;
   }

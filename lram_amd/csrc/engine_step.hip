@@ -18,21 +18,43 @@ void run_stack(lram_engine* e, Pass pass, int T, const uint8_t* reset, const std
 
 // uint8 frames [B, C, H, W] -> state-token embeddings [B, d_model] (reference: embed_image(x / 255),
 // online_decision_transformer_model.py:523-526 + image_encoders.py:58-66)
-// Image work buffers for B frames of H x W (synchronises when it has to grow them: never called between a fork and a join)
-void image_buffers(lram_engine* e, int H, int W) {
-  const size_t B = e->B, px = B * H * W;
-  if (px <= e->img_cap) return;
-  LRAM_HIP_CHECK(hipDeviceSynchronize());
+// Floats one H x W frame takes in the image work buffers.  IMG_P holds the stage conv's output before its pool: 16 channels at
+// H x W in stage 1, 32 channels at the pooled size in stages 2 and 3 (the larger of the two when H or W is 1 and the other
+// is odd).  IMG_X0 / IMG_X1 / IMG_T hold pooled maps: at most 32 channels of (H-1)/2+1 x (W-1)/2+1.
+struct ImageFrameFloats {
+  size_t p, x;
+};
+ImageFrameFloats image_frame_floats(int H, int W) {
   const size_t hp = (H - 1) / 2 + 1, wp = (W - 1) / 2 + 1;
-  e->IMG_P.alloc(B * 16 * H * W);       // stage-1 conv output before its pool (the largest tensor)
-  e->IMG_X0.alloc(B * 32 * hp * wp);    // pooled maps never exceed 32 channels at half resolution
-  e->IMG_X1.alloc(B * 32 * hp * wp);
-  e->IMG_T.alloc(B * 32 * hp * wp);
-  e->img_cap = px;
+  const size_t x = 32 * hp * wp;
+  return {std::max((size_t)16 * H * W, x), x};
+}
+
+// Checks the frame size against the uploaded weights, then makes the image work buffers hold B frames of H x W: every buffer
+// by what it holds at this size, each grown on its own need (two sizes that feed the same linear layer can differ in which
+// of them has the larger pooled map).  Synchronises when it has to grow one: never called between a fork and a join.
+void image_buffers(lram_engine* e, int C, int H, int W, const char* who) {
+  const std::string wh(who);
+  LRAM_REQUIRE(e->img_lin_w != nullptr, wh + ": no embed_image.* weights were uploaded");
+  LRAM_REQUIRE(C == e->img_channels, wh + ": channel count " + std::to_string(C) +
+                                         " does not match embed_image.cnn.0.conv.weight (" + std::to_string(e->img_channels) + ")");
+  int h = H, w = W;
+  for (int k = 0; k < 3; ++k) h = (h - 1) / 2 + 1, w = (w - 1) / 2 + 1;
+  LRAM_REQUIRE((int64_t)32 * h * w == e->img_flat, wh + ": image size " + std::to_string(H) + " x " + std::to_string(W) +
+                                              " (pooled " + std::to_string(h) + " x " + std::to_string(w) + ", " +
+                                              std::to_string((int64_t)32 * h * w) + " features) does not match embed_image.linear.0.weight (" +
+                                              std::to_string(e->img_flat) + " features)");
+  const ImageFrameFloats f = image_frame_floats(H, W);
+  const size_t B = e->B, np = B * f.p, nx = B * f.x;
+  if (np <= e->IMG_P.n && nx <= e->IMG_X0.n && nx <= e->IMG_X1.n && nx <= e->IMG_T.n) return;
+  LRAM_HIP_CHECK(hipDeviceSynchronize());
+  if (np > e->IMG_P.n) e->IMG_P.alloc(np);
+  for (DevBuf* b : {&e->IMG_X0, &e->IMG_X1, &e->IMG_T})
+    if (nx > b->n) b->alloc(nx);
 }
 // ... and the rows the frames of an env-step are embedded into (lram_step_images, lram_step_slots)
-void step_image_buffers(lram_engine* e, int H, int W) {
-  image_buffers(e, H, W);
+void step_image_buffers(lram_engine* e, int C, int H, int W, const char* who) {
+  image_buffers(e, C, H, W, who);
   if (e->IMG_EMB.n < (size_t)e->B * e->cfg.d_model) {
     LRAM_HIP_CHECK(hipDeviceSynchronize());
     e->IMG_EMB.alloc((size_t)e->B * e->cfg.d_model);
@@ -42,21 +64,19 @@ void step_image_buffers(lram_engine* e, int H, int W) {
 // envs b0 .. b0 + nb - 1 (`images` / `out` point at env b0's frame / row; every env slice keeps to its own fixed region of the
 // work buffers, so slices at different stages of the CNN never touch each other's maps)
 void embed_images(lram_engine* e, const uint8_t* images, int C, int H, int W, float* out, hipStream_t s, int b0 = 0, int nb = -1) {
-  LRAM_REQUIRE(e->img_lin_w != nullptr, "lram_embed_images: no embed_image.* weights were uploaded");
-  LRAM_REQUIRE(C == e->img_channels, "lram_embed_images: channel count does not match embed_image.cnn.0.conv.weight");
   const int B = nb < 0 ? e->B : nb, D = e->cfg.d_model;
-  int h = H, w = W;
-  for (int k = 0; k < 3; ++k) h = (h - 1) / 2 + 1, w = (w - 1) / 2 + 1;
-  LRAM_REQUIRE(32 * h * w == e->img_flat, "lram_embed_images: image size does not match embed_image.linear.0.weight");
-  LRAM_REQUIRE((size_t)e->B * H * W <= e->img_cap, "image work buffers not allocated");
-  const size_t hp0 = (H - 1) / 2 + 1, wp0 = (W - 1) / 2 + 1;
-  float* const P = e->IMG_P.p + (size_t)b0 * 16 * H * W;
-  float* const X0 = e->IMG_X0.p + (size_t)b0 * 32 * hp0 * wp0;
-  float* const X1 = e->IMG_X1.p + (size_t)b0 * 32 * hp0 * wp0;
-  float* const Tb = e->IMG_T.p + (size_t)b0 * 32 * hp0 * wp0;
+  // (image_buffers has checked C, H, W against the weights; the env slices of one call share its buffers)
+  const ImageFrameFloats f = image_frame_floats(H, W);
+  LRAM_REQUIRE((size_t)e->B * f.p <= e->IMG_P.n && (size_t)e->B * f.x <= e->IMG_X0.n &&
+                   (size_t)e->B * f.x <= e->IMG_X1.n && (size_t)e->B * f.x <= e->IMG_T.n,
+               "image work buffers not allocated");
+  float* const P = e->IMG_P.p + (size_t)b0 * f.p;
+  float* const X0 = e->IMG_X0.p + (size_t)b0 * f.x;
+  float* const X1 = e->IMG_X1.p + (size_t)b0 * f.x;
+  float* const Tb = e->IMG_T.p + (size_t)b0 * f.x;
   const void* in = images;
   int in_u8 = 1;
-  h = H, w = W;
+  int h = H, w = W;
   for (int sidx = 0; sidx < 3; ++sidx) {
     const lram_engine::ImgConv* cv = e->img_conv[sidx];
     auto conv = [&](const lram_engine::ImgConv& c, const void* src, int u8, int relu_in, const float* res, float* dst,
@@ -389,7 +409,7 @@ int32_t lram_step_images(lram_engine* e, const uint8_t* dev_images, int32_t chan
                  "lram_step_images: bad argument");
     LRAM_REQUIRE(e->img_lin_w != nullptr, "lram_step_images: no embed_image.* weights were uploaded");
     check_head_mode(e, discrete, "lram_step_images");
-    step_image_buffers(e, height, width);
+    step_image_buffers(e, channels, height, width, "lram_step_images");
     compat_prepare(e, discrete);
     Pass pass;   // (the frames belong to this call only)
     pass.images = dev_images, pass.img_c = channels, pass.img_h = height, pass.img_w = width;
@@ -413,7 +433,7 @@ int32_t lram_step_slots(lram_engine* e, const float* dev_obs, const uint8_t* dev
       LRAM_REQUIRE(e->img_lin_w != nullptr, "lram_step_slots: the table holds image slots and no embed_image.* weights were uploaded");
       LRAM_REQUIRE(dev_images && channels > 0 && height > 0 && width > 0, "lram_step_slots: the table holds image slots: frames needed");
       LRAM_REQUIRE(e->cfg.d_model % 4 == 0, "lram_step_slots: image slots need d_model to be a multiple of 4");
-      step_image_buffers(e, height, width);
+      step_image_buffers(e, channels, height, width, "lram_step_slots");
     }
     Pass pass;   // (the frames and the mixed front end belong to this call only)
     pass.slots = true;
@@ -514,7 +534,7 @@ int32_t lram_embed_images(lram_engine* e, const uint8_t* dev_images, int32_t cha
     LRAM_REQUIRE(e && e->B > 0, "lram_embed_images: state not allocated (call lram_state_alloc)");
     LRAM_REQUIRE(dev_images && dev_embeddings && channels > 0 && height > 0 && width > 0, "lram_embed_images: bad argument");
     LRAM_HIP_CHECK(hipSetDevice(e->device));
-    image_buffers(e, height, width);
+    image_buffers(e, channels, height, width, "lram_embed_images");
     embed_images(e, dev_images, channels, height, width, dev_embeddings, static_cast<hipStream_t>(stream));
   });
 }

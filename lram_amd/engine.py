@@ -295,8 +295,10 @@ class Engine:
         _check(self.lib, self.lib.lram_state_alloc(self._h, int(batch)))
         self.batch = int(batch)
         B, A = self.batch, self.spec.act_dim
-        self._actions = torch.empty(B, A, dtype=torch.float32, device=self.device)
-        self._tokens = torch.empty(B, A, dtype=torch.int32, device=self.device)
+        # zeroed: a discrete head writes column 0 only, and the columns it leaves alone must not depend on what the allocator
+        # hands out (two runs on the same inputs return the same tensors)
+        self._actions = torch.zeros(B, A, dtype=torch.float32, device=self.device)
+        self._tokens = torch.zeros(B, A, dtype=torch.int32, device=self.device)
 
     def state_bytes_per_env(self) -> int:
         return int(self.lib.lram_state_bytes_per_env(self._h))

@@ -42,7 +42,7 @@ def reference_layout(spec: ModelSpec, with_image_encoder: bool = False) -> Dict[
     }
     if with_image_encoder:
         cin = spec.image_shape[0]
-        hw = spec.image_shape[1]
+        h, w = spec.image_shape[1], spec.image_shape[2]
         for b, cout in enumerate(IMPALA_CHANNELS):
             p = f"embed_image.cnn.{b}."
             lay[p + "conv.weight"] = (cout, cin, 3, 3)
@@ -52,8 +52,8 @@ def reference_layout(spec: ModelSpec, with_image_encoder: bool = False) -> Dict[
                     lay[f"{p}residual_{r}.conv_{cv}.weight"] = (cout, cout, 3, 3)
                     lay[f"{p}residual_{r}.conv_{cv}.bias"] = (cout,)
             cin = cout
-            hw = (hw + 2 - 3) // 2 + 1  # MaxPool2d(3, 2, padding=1)
-        lay["embed_image.linear.0.weight"] = (D, cin * hw * hw)
+            h, w = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1  # MaxPool2d(3, 2, padding=1), each extent on its own
+        lay["embed_image.linear.0.weight"] = (D, cin * h * w)
         lay["embed_image.linear.0.bias"] = (D,)
     if spec.backbone == "xlstm":
         inner, NH = spec.inner, spec.n_heads

@@ -43,7 +43,9 @@ def minmax_inv_tokenize(tok, vocab_size=256, shift=18, min_val=-1.0, max_val=1.0
 # ImpalaCNN (reference: src/algos/models/image_encoders.py:10-131, model_size 1, out_relu True)
 # ----------------------------------------------------------------------------------------------
 def impala_cnn(sd, p, x):
-    """x: float (B,3,64,64) already divided by 255 (online_decision_transformer_model.py:523-525)."""
+    """x: float (B,C,H,W) already divided by 255 (online_decision_transformer_model.py:523-525); any C, H, W >= 1 whose
+    three poolings (each extent (n - 1) // 2 + 1) give the column count of `linear.0.weight` / 32.  Runs in the dtype of
+    `sd` and `x` (float64 for the engine's shape tests)."""
     def conv(key, t):
         return F.conv2d(t, sd[key + ".weight"], sd[key + ".bias"], stride=1, padding=1)
 
@@ -64,7 +66,7 @@ def impala_cnn(sd, p, x):
 # ----------------------------------------------------------------------------------------------
 def embed_tokens(spec, sd, obs, rtg, reward, state_mean=None, state_std=None):
     """obs: (B, state_dim) float32 already zero-padded to max_state_dim (decision_xlstm.py:16-19), or
-    uint8 (B,3,64,64); rtg, reward: (B,).  Returns embed_ln(stack(s, rtg, r)) of shape (B, 3, D)."""
+    uint8 (B,C,H,W) frames; rtg, reward: (B,).  Returns embed_ln(stack(s, rtg, r)) of shape (B, 3, D)."""
     if obs.dim() == 4:
         s = impala_cnn(sd, "embed_image.", obs.to(sd["embed_return.weight"].dtype) / 255.0)
     else:

@@ -20,6 +20,19 @@ def make_inputs(spec, B, steps, seed=1234, reset_prob=0.15, image=False):
     return seq
 
 
+# Frame sizes (C, H, W) of the image front end's shape tests (tests/test_gpu_image_shapes.py, tests/test_oracle_selfchecks.py):
+# (3, 64, 64) is the size every other test uses -- all four maps whole numbers of conv tiles; the others are not.
+IMAGE_SHAPE_SWEEP = [(3, 84, 84), (1, 84, 84), (4, 40, 24), (3, 33, 65), (3, 17, 33), (3, 21, 21), (1, 8, 8), (3, 1, 9),
+                     (3, 64, 64)]
+
+
+def pooled_hw(h, w, times=3):
+    """(h, w) after `times` MaxPool2d(3, stride 2, padding 1): each extent (n - 1) // 2 + 1."""
+    for _ in range(times):
+        h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    return h, w
+
+
 def assert_actions_match(a_gpu, a_ref, logits_ref, spec, discrete=False, gap_tol=2e-4, what=""):
     """Discrete actions bit-exact, continuous within 1e-4 (= identical bins, bin width 2/256).  A mismatch
     is tolerated only where the oracle's own top-2 logit gap is below `gap_tol` (a numerical tie; a NaN gap is none); the

@@ -236,8 +236,9 @@ def _frames_of(img_obs, kinds):
     return img_obs[torch.tensor(_image_rows(kinds), dtype=torch.long)].contiguous()
 
 
-def _check_against_oracle(spec, oracles, groups, kinds, vec_t, img_t, a, hid, what):
-    """One step: the engine's actions / hidden tap (host tensors, all slots) against one oracle per group."""
+def _check_against_oracle(spec, oracles, groups, kinds, vec_t, img_t, a, hid, what, dbg_out=None):
+    """One step: the engine's actions / hidden tap (host tensors, all slots) against one oracle per group.  dbg_out: a dict
+    that receives every group's oracle debug tensors, for callers that check more taps."""
     _, rtg, rew, mask = vec_t
     ties, worst = 0, 0.0
     for (im, di), idx in groups.items():
@@ -245,6 +246,8 @@ def _check_against_oracle(spec, oracles, groups, kinds, vec_t, img_t, a, hid, wh
         obs = (img_t if im else vec_t)[0][ix]
         a_ref, dbg = oracles[(im, di)].step(obs, rtg[ix], rew[ix], mask[ix], discrete=bool(di), return_debug=True)
         got = a[ix]
+        if dbg_out is not None:
+            dbg_out[(im, di)] = dbg
         if di:
             ties += assert_actions_match(got[:, :1], a_ref, dbg["logits"], spec, discrete=True, what=f"{what} group {(im, di)}")
         else:

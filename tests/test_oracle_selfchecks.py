@@ -7,7 +7,7 @@ import torch
 from lram_amd import init_state_dict, preset
 from lram_amd.config import ModelSpec
 from oracle import dt_ref, mamba_ref, xlstm_ref
-from tests.helpers import make_inputs, rel_err
+from tests.helpers import IMAGE_SHAPE_SWEEP, make_inputs, pooled_hw, rel_err
 
 
 def test_mlstm_step_equals_parallel_form():
@@ -161,6 +161,62 @@ def test_impala_cnn_shapes_and_image_path():
     enc = ImageEncoder.from_state_dict(sd, spec.image_shape, spec.d_model)
     ref = dt_ref.impala_cnn(sd, "embed_image.", img.float() / 255.0)
     assert rel_err(enc(img), ref) < 1e-6
+
+
+def _image_spec(shape):
+    return ModelSpec(backbone="xlstm", d_model=128, n_blocks=2, slstm_at=[1], image_shape=shape)
+
+
+@pytest.mark.parametrize("shape", IMAGE_SHAPE_SWEEP + [(3, 21, 27), (3, 62, 56)], ids=lambda s: "x".join(map(str, s)))
+def test_image_layout_pools_height_and_width_separately(shape):
+    """reference_layout / init_state_dict / check_state_dict: the linear layer has 32 * h * w columns with the pooled h, w of the
+    frame (H and W pooled each on its own, three times), and the first conv takes the frame's channel count."""
+    from lram_amd.weights import check_state_dict, reference_layout
+    spec = _image_spec(shape)
+    h, w = pooled_hw(shape[1], shape[2])
+    lay = reference_layout(spec, with_image_encoder=True)
+    assert lay["embed_image.linear.0.weight"] == (128, 32 * h * w)
+    assert lay["embed_image.cnn.0.conv.weight"] == (16, shape[0], 3, 3)
+    sd = init_state_dict(spec, seed=6, with_image_encoder=True)
+    assert tuple(sd["embed_image.linear.0.weight"].shape) == (128, 32 * h * w)
+    check_state_dict(spec, sd, with_image_encoder=True)
+
+
+def test_check_state_dict_tells_frame_sizes_apart_by_their_pooled_size():
+    """A state dict built for (3, 17, 33) passes the check of its own spec; one built for another pooled size fails it.
+    The transposed frame (3, 33, 17) pools to 5 x 3 where (3, 17, 33) pools to 3 x 5: the same 480 columns, so the SHAPES of
+    the two state dicts are equal and no shape check can tell them apart (the flatten order differs, the count does not) --
+    stated here so that nobody expects otherwise."""
+    from lram_amd.weights import check_state_dict, reference_layout
+    spec = _image_spec((3, 17, 33))
+    check_state_dict(spec, init_state_dict(spec, seed=6, with_image_encoder=True), with_image_encoder=True)
+    for other, cols in (((3, 33, 65), 32 * 5 * 9), ((3, 33, 33), 32 * 5 * 5), ((3, 17, 17), 32 * 3 * 3)):
+        sd = init_state_dict(_image_spec(other), seed=6, with_image_encoder=True)
+        assert sd["embed_image.linear.0.weight"].shape[1] == cols
+        with pytest.raises(KeyError, match="embed_image.linear.0.weight"):
+            check_state_dict(spec, sd, with_image_encoder=True)
+    with pytest.raises(KeyError, match="embed_image.cnn.0.conv.weight"):   # ... and another channel count
+        check_state_dict(spec, init_state_dict(_image_spec((1, 17, 33)), seed=6, with_image_encoder=True), with_image_encoder=True)
+    assert pooled_hw(33, 17) == (5, 3) and pooled_hw(17, 33) == (3, 5)
+    assert reference_layout(_image_spec((3, 33, 17)), True) == reference_layout(spec, True)
+
+
+@pytest.mark.parametrize("shape", IMAGE_SHAPE_SWEEP, ids=lambda s: "x".join(map(str, s)))
+def test_impala_cnn_equals_the_torch_module_at_every_swept_frame_size(shape):
+    """The oracle's functional restatement (float32) and tests/torch_image_encoder.ImageEncoder are independent restatements of
+    the reference's module: equal to 1e-6 of max |ref| on every frame size of the engine's shape sweep, and float32 stays within
+    1e-6 of the float64 evaluation that the GPU tests compare against (measured 2.9e-7 .. 5.0e-7)."""
+    from tests.torch_image_encoder import ImageEncoder
+    spec = _image_spec(shape)
+    sd = init_state_dict(spec, seed=6, with_image_encoder=True)
+    img = torch.randint(0, 256, (5, *shape), dtype=torch.uint8, generator=torch.Generator().manual_seed(11))
+    ref = dt_ref.impala_cnn(sd, "embed_image.", img.float() / 255.0)
+    h, w = pooled_hw(shape[1], shape[2])
+    assert ref.shape == (5, 128) and sd["embed_image.linear.0.weight"].shape == (128, 32 * h * w)
+    assert float(ref.abs().max()) > 0.0
+    assert rel_err(ImageEncoder.from_state_dict(sd, shape, spec.d_model)(img), ref) < 1e-6
+    ref64 = dt_ref.impala_cnn({k: v.double() for k, v in sd.items()}, "embed_image.", img.double() / 255.0)
+    assert ref64.dtype == torch.float64 and rel_err(ref, ref64) < 1e-6
 
 
 def test_mlstm_cell_matches_transformers_xlstm_native_step():

@@ -3,7 +3,7 @@ an independent cross-check of the engine's own kernels (`lram_embed_images`, csr
 image backend `RecurrentAgent` has.  Used by tests/ and scripts/bench_image_encoder.py.
 
 
-Front end of the hot path for image domains (Atari / Procgen / Mimicgen-vision): uint8 [B,3,64,64] ->
+Front end of the hot path for image domains (Atari / Procgen / Mimicgen-vision): uint8 [B,C,H,W] (any H, W >= 1, square or not) ->
 x/255 -> 3 x (conv3x3 -> maxpool(3,2,1) -> 2 residual blocks) with 16/32/32 channels -> ReLU -> flatten ->
 Linear -> ReLU.  Behaviour and state-dict key names follow the reference's `embed_image` module
 (src/algos/models/image_encoders.py:10-131, built at multi_domain_discrete_dt_model.py:43-46; the /255 is
@@ -43,14 +43,14 @@ class _Stage(nn.Module):
 class ImageEncoder(nn.Module):
     def __init__(self, image_shape=(3, 64, 64), features_dim: int = 512, channels=(16, 32, 32)):
         super().__init__()
-        cin, hw = image_shape[0], image_shape[1]
+        cin, h, w = image_shape
         stages = []
         for cout in channels:
             stages.append(_Stage(cin, cout))
             cin = cout
-            hw = (hw + 2 - 3) // 2 + 1
+            h, w = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
         self.cnn = nn.ModuleList(stages)
-        self.linear = nn.Sequential(nn.Linear(cin * hw * hw, features_dim), nn.ReLU())
+        self.linear = nn.Sequential(nn.Linear(cin * h * w, features_dim), nn.ReLU())
 
     @torch.no_grad()
     def forward(self, obs_uint8: torch.Tensor) -> torch.Tensor:
