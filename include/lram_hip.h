@@ -158,6 +158,53 @@ int32_t lram_prefill(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_em
                      const float* dev_reward_seq, int32_t timesteps, const uint8_t* dev_reset_mask,
                      int32_t discrete, float* dev_actions, int32_t* dev_tokens, void* stream);
 
+/* Score a stored trajectory: lram_prefill with the action head evaluated at EVERY timestep -- the recurrent counterpart of the
+ * reference's no-cache forward, which returns action logits at every position, and of the loss it takes from them
+ * (src/algos/universal_decision_transformer_sb3.py:398-434: tokenize_actions of the float targets, cross-entropy over
+ * act_dim x n_vocab, attention_mask / action_mask).  Per (env, timestep, action dim) it can return the greedy token, its
+ * de-tokenised action, the log-probability of a recorded action and the raw logits, without a host round trip per timestep.
+ *   inputs, dev_reset_mask, discrete   as lram_prefill (LRAM_HEAD_PER_SLOT included); timesteps >= 1
+ *   dev_target_actions   device float[batch, timesteps, act_dim] or NULL: recorded actions, tokenised on the device as
+ *                        MinMaxTokenizer.tokenize does (src/tokenizers_custom/minmax_tokenizer.py:14-29):
+ *                        trunc((x - tok_min) / bin_width) clamped to 0 .. action_channels - 1, plus n_discrete (fp32 subtract,
+ *                        IEEE fp32 division); discrete rows take (int)x
+ *   dev_target_tokens    device int32[batch, timesteps, act_dim] or NULL: recorded tokens.  At most one of the two.
+ *   dev_valid            device uint8[batch, timesteps] or NULL: 0 masks the OUTPUTS of that (env, timestep) -- the reference's
+ *                        attention_mask; every timestep still advances the state
+ *   over                 0: logp normalises over all n_vocab logits of the row (the reference's cross-entropy);
+ *                        1: over the selectable range -- n_discrete on discrete rows, n_vocab otherwise (what the sampling
+ *                        head draws from)
+ *   temperature          multiplies the logits, as sample_from_logits does (src/algos/models/model_utils.py:7-32); 1 = the plain
+ *                        log-softmax; finite and > 0
+ *   dev_actions, dev_tokens, dev_logp   device float / int32 / float [batch, timesteps, act_dim], each nullable
+ *   dev_logits           device float[batch, timesteps, act_dim * n_vocab] or NULL
+ * logp = temperature * x[target] - logsumexp(temperature * x) with maximum, sum and log in fp64, rounded once to fp32.  A target
+ * outside the normalisation range or a non-finite float target gives -inf, a NaN in the range NaN, a -inf logit at the target -inf.
+ * Masked timesteps, columns j >= act_dim[slot] of a per-slot call and columns j >= 1 of a discrete = 1 call hold logp 0.0f,
+ * token -1, action 0.0f; their logits are not written.
+ * At least one output must be given; dev_logp needs a target.  The recurrent state afterwards is what lram_prefill over the
+ * same inputs leaves, bit for bit.  Row [b, timesteps - 1] goes through the very head launches lram_prefill makes for its action
+ * (and lram_get_taps / lram_score_last then see that row's logits): with sampling off it equals lram_prefill's action bit for
+ * bit.  Rows of earlier timesteps take the exact-fp32 matrix-core kernel over the chunk's rows, in blocks of at most 4096 rows
+ * through an engine-owned scratch (one region per chunk in flight; LRAM_SCORE_ROWS at lram_create lowers the bound, results do
+ * not depend on it).  The call is deterministic: with lram_set_sampling armed it still reports the greedy token, draws nothing
+ * and leaves the draw counter alone.  Never captured: in graph mode it runs launch by launch, as long prefills do.
+ * Refused (message in lram_last_error, nothing launched, state untouched): mamba_repeat > 1 (lram_set_compat_mode), both
+ * targets given, no output given, dev_logp without a target. */
+int32_t lram_score(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
+                   const float* dev_reward_seq, int32_t timesteps, const uint8_t* dev_reset_mask, int32_t discrete,
+                   const float* dev_target_actions, const int32_t* dev_target_tokens, const uint8_t* dev_valid, int32_t over,
+                   double temperature, float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits, void* stream);
+
+/* Log-probabilities of caller-given tokens (device int32[batch, act_dim]: what lram_step* / lram_prefill just returned in
+ * dev_tokens) under the logits of the last action-producing call, which are still in the engine's logits buffer: dev_logp
+ * (device float[batch, act_dim]) as lram_score defines it, one kernel launch, no draw.  The reference's counterpart is
+ * log_softmax(temperature * logits) of the row sample_from_logits drew from (model_utils.py:7-32), gathered at the drawn token;
+ * top-k / top-p filtering is NOT applied.  Head mode and slot table are those of that call.  Refused if no action-producing
+ * call has happened since lram_state_alloc. */
+int32_t lram_score_last(lram_engine* e, const int32_t* dev_tokens, int32_t over, double temperature, float* dev_logp,
+                        void* stream);
+
 /* Encoder-only operator: inputs_embeds[batch, tokens, d_model] -> last_hidden_state of the same shape
  * (after post_blocks_norm / norm_f), state advanced by `tokens` (1..4, 6, 9 or 12; any count in 13..64 as well on
  * xLSTM geometries the chunkwise kernels cover, see lram_prefill).  This is the exact plug point of
@@ -387,6 +434,13 @@ int32_t lram_sample_tokens(const float* dev_logits, int64_t rows, int32_t n, int
  * slot_base .. slot_base + n_slots - 1 (test / evidence entry). */
 int32_t lram_sample_uniforms(uint64_t seed, uint64_t slot_base, int64_t n_slots, int32_t act_dim, uint64_t draw,
                              double* dev_out, void* stream);
+/* The device code of the scoring head on caller logits (test / evidence entry, as lram_sample_tokens is for the sampling head):
+ * dev_logits device float[rows, act_dim * n_vocab]; targets, dev_valid (uint8[rows]) and outputs ([rows, act_dim]) as in
+ * lram_score; discrete 0 or 1. */
+int32_t lram_score_tokens(const float* dev_logits, int64_t rows, int32_t act_dim, int32_t n_vocab, int32_t n_discrete,
+                          int32_t action_channels, float tok_min, float tok_max, int32_t discrete, const float* dev_target_actions,
+                          const int32_t* dev_target_tokens, const uint8_t* dev_valid, int32_t over, double temperature,
+                          float* dev_actions, int32_t* dev_tokens, float* dev_logp, void* stream);
 /* Image observations: uint8 frames [batch, channels, height, width] -> state-token embeddings [batch, d_model]
  * through the IMPALA CNN (3 x [conv3x3 -> maxpool(3,2,1) -> 2 residual blocks], 16/32/32 channels, ReLU, flatten,
  * Linear, ReLU).  Replaces `self.embed_image(state.float() / 255)` (online_decision_transformer_model.py:523-526;

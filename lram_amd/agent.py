@@ -308,6 +308,56 @@ class RecurrentAgent:
             return actions[:, :1].to(torch.int64)
         return actions if env_act_dim is None else actions[:, :env_act_dim]
 
+    # ---- grading: stored trajectories and the actions just taken --------------------------------------
+    @torch.no_grad()
+    def score_trajectories(self, observations: torch.Tensor, returns_to_go: torch.Tensor,
+                           rewards: Optional[torch.Tensor] = None, actions: Optional[torch.Tensor] = None,
+                           lengths: Optional[torch.Tensor] = None, reset: bool = True, over: str = "vocab",
+                           temperature: float = 1.0, want=("actions", "tokens", "logp"), logits: bool = False):
+        """Grade stored trajectories (Engine.score): observations [B, L, obs_dim] -- padded and normalised with state_mean /
+        state_std as predict_batch does -- returns_to_go [B, L] in model units, rewards [B, L] (None: the reference loop's
+        zero reward token), recorded `actions` [B, L, n] (float; n <= act_dim, padded with zeros; a discrete agent's action
+        index in column 0) and `lengths` [B] (timesteps that count per env, from the start; None = all L).  `valid` is built
+        from the lengths; timesteps beyond an env's length still advance its state.  reset=True starts every env from an empty
+        context.  Returns the ScoreResult (per-timestep greedy actions / tokens and the log-probability of the recorded
+        actions); rollout.score_loss turns it into the reference's loss.  With a slot table every slot is scored with its
+        own head; image observations are not taken here (embed them and call Engine.score with obs_is_embedding)."""
+        B = self.n_envs
+        if observations.dim() != 3 or observations.shape[0] != B:
+            raise ValueError(f"observations: expected [{B}, L, obs_dim], got {tuple(observations.shape)}")
+        L = observations.shape[1]
+        obs, _ = self._prepare_obs(observations.reshape(B * L, -1))
+        obs = obs.view(B, L, -1).contiguous()
+        rtg = returns_to_go.to(self.device, torch.float32).reshape(B, L).contiguous()
+        rew = torch.zeros(B, L, dtype=torch.float32, device=self.device) if rewards is None else \
+            rewards.to(self.device, torch.float32).reshape(B, L).contiguous()
+        target = None
+        if actions is not None:
+            a = actions.to(self.device, torch.float32).reshape(B, L, -1)
+            if a.shape[-1] > self.spec.act_dim:
+                raise ValueError(f"actions: {a.shape[-1]} action dims exceed max_act_dim {self.spec.act_dim}")
+            target = torch.zeros(B, L, self.spec.act_dim, dtype=torch.float32, device=self.device)
+            target[..., : a.shape[-1]] = a
+        valid = None
+        if lengths is not None:
+            n = torch.as_tensor(lengths).to(self.device).reshape(B, 1)
+            valid = (torch.arange(L, device=self.device).reshape(1, L) < n).to(torch.uint8).contiguous()
+        mask = torch.ones(B, dtype=torch.uint8, device=self.device) if reset else None
+        want = tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "logp" or target is not None)
+        discrete = "per_slot" if getattr(self, "slot_table", None) is not None else self.is_discrete
+        return self.engine.score(obs, rtg, rew, actions=target, valid=valid, reset_mask=mask, discrete=discrete, over=over,
+                                 temperature=temperature, want=want, logits=logits)
+
+    @torch.no_grad()
+    def action_log_prob(self, over: str = "selectable") -> torch.Tensor:
+        """float32 [n_envs, act_dim]: the log-probability of the tokens the last predict_batch / predict returned, under that
+        call's logits (Engine.last_logp) -- importance weights, or the score that ranks the forks of fork_slots.  With
+        a_sample_kwargs the armed temperature multiplies the logits; top_k and top_p are NOT applied (the probability under the
+        filtered distribution is out of scope): with filtering armed this is the log-probability under the unfiltered softmax.
+        Columns a slot does not use hold 0."""
+        t = 1.0 if self.a_sample_kwargs is None else float(self.a_sample_kwargs["temperature"])
+        return self.engine.last_logp(self.engine._tokens, over=over, temperature=t)
+
     def _predict_batch_slots(self, observation, returns_to_go, rewards, reset_mask):
         if not isinstance(observation, (tuple, list)) or len(observation) != 2:
             raise ValueError("with a slot table predict_batch takes observation = (vector_obs, images)")

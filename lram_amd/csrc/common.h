@@ -258,6 +258,31 @@ void launch_sample_tokens(const float* logits, int64_t rows, int n, int64_t ld, 
 // out[s * act_dim + j] = the uniform of env slot slot_base + s, action dim j, draw `draw`
 void launch_sample_uniforms(uint64_t seed, uint64_t slot_base, int64_t n_slots, int act_dim, uint64_t draw, double* out,
                             hipStream_t stream);
+// The scoring mode of the same head (score_kernels.hip): greedy token / action and the log-probability of a given target per
+// (row, action dim).  A launch covers the flat rows g = row0 .. row0 + rows - 1 of a [envs, inner] grid (g = env * inner + step):
+// row g's logits are at logits + (g - row0) * ld, its outputs, targets and `valid` byte at row
+// (g / inner) * outer + off + g % inner of the caller's tensors, its slot-table entry at g / inner.
+struct ScoreArgs {
+  const float* logits = nullptr;
+  int64_t ld = 0;
+  int64_t row0 = 0, rows = 0;
+  int64_t inner = 1, outer = 1, off = 0;
+  int act_dim = 0, n_vocab = 0, n_discrete = 0, action_channels = 0;
+  float tok_min = -1.f, tok_max = 1.f;
+  int discrete = 0;          // 0 / 1; with a slot table the slot's flag decides
+  int over = 0;              // logp normalises over 0: all n_vocab logits, 1: the selectable range
+  double temperature = 1.0;  // MULTIPLIES the logits
+  const float* target_actions = nullptr;   // [., act_dim] float actions, tokenised on the device -- or
+  const int32_t* target_tokens = nullptr;  // [., act_dim] tokens (at most one of the two)
+  const uint8_t* valid = nullptr;          // [.] nullable: rows with 0 get the fill values
+  const uint8_t* slot_flags = nullptr;     // slot table [envs] + [envs], nullable
+  const uint8_t* slot_act = nullptr;
+  float* actions = nullptr;                // outputs, each nullable: [., act_dim]
+  int32_t* tokens = nullptr;
+  float* logp = nullptr;
+  float* logits_out = nullptr;             // [., act_dim * n_vocab]: the rows as they were read
+};
+void launch_action_score(const ScoreArgs& a, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // xLSTM

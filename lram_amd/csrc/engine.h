@@ -6,7 +6,7 @@
 //   engine_streams.hip  events, env slices, fork / join, the profiler                          (calls nothing)
 //   engine_xlstm.hip    the xLSTM stack and the lazy matrix memory's host side                 (calls gemm, streams)
 //   engine_mamba.hip    the Mamba stack                                                        (calls gemm, streams)
-//   engine_step.hip     image / token front end, action head, the step and prefill entries     (calls the stacks, gemm, streams)
+//   engine_step.hip     image / token front end, action head, the step, prefill and score entries (calls the stacks, gemm, streams)
 //   engine_state.hip    reset, export / import, the slot table and the per-slot state calls
 #pragma once
 #include <algorithm>
@@ -215,6 +215,13 @@ struct lram_engine {
                 // sLSTM block uses XN as fp32 while another slice's mLSTM block holds planes
   DevBuf GATES, AMAT, VEC;           // chunkwise mLSTM prefill work buffers (allocated with the first long chunk)
   DevBuf SEQ_EMB;                    // state embeddings of a stored context [B, L, D] (lram_prefill)
+  // lram_score: the head's logits for a block of (env, timestep) rows of one chunk, one region per chunk lane / env slice in
+  // flight.  A region holds at most score_rows rows of act_dim * n_vocab floats (default 4096 rows: 34 MiB at 8 x 274 logits;
+  // LRAM_SCORE_ROWS at lram_create, at least 16); a chunk with more rows goes through it block by block.
+  DevBuf SCORE_LG;
+  int score_rows = 4096;
+  static constexpr int kScoreMinRows = 16;   // blocks keep clear of the GEMV path (rows <= 8): one kernel, one rounding per row
+  int last_head = -1;                // `discrete` of the last action-producing call (its logits are in LOGITS); -1: none yet
   int tok_cap = 0;                   // tokens per env the activation workspace holds (kMaxTokens until a prefill grows it)
   bool chunk_prefill = true;         // LRAM_PREFILL_CHUNK=0: keep the token-sequential kernels for prefill
   bool chunk_exact_fp32 = false;     // LRAM_PREFILL_CHUNK=2: chunkwise cell on the fp32-input matrix cores (the round 1-5 form)
@@ -335,11 +342,12 @@ struct lram_engine {
     drop_slot_segments();
     st.clear();
     for (DevBuf* b : {&X, &XN, &TOK, &HID, &U, &Q, &K, &V, &XA, &H, &G, &SCAL, &RY, &LOGITS, &RES, &DTP, &SK, &GATES,
-                      &AMAT, &VEC, &SEQ_EMB, &IMG_EMB, &IMG_P, &IMG_X0, &IMG_X1, &IMG_T, &XN2, &ASCALE, &AMX_XN, &AMX_XA, &AMX_H, &X0, &U0})
+                      &AMAT, &VEC, &SEQ_EMB, &IMG_EMB, &IMG_P, &IMG_X0, &IMG_X1, &IMG_T, &XN2, &ASCALE, &AMX_XN, &AMX_XA, &AMX_H, &X0, &U0, &SCORE_LG})
       b->release();
     for (auto& t : twin)
       for (DevBuf& b : t) b.release();
     ascale_rows = 0;
+    last_head = -1;
     B = 0;
     tok_cap = 0;
   }
@@ -371,6 +379,20 @@ struct Pass {
   const std::vector<hipEvent_t>* lane_wait = nullptr;
   const std::vector<hipEvent_t>* lane_rec = nullptr;
   int n_slices = 1;                  // env slices of the stack pass under way (set by run_stack)
+};
+
+// Per-timestep sink of a stored context (lram_score): where the head's outputs of EVERY timestep go.  Tensors are [B, L, act_dim]
+// (logits [B, L, act_dim * n_vocab], valid [B, L]); every output is nullable.
+struct ScoreSink {
+  float* actions = nullptr;
+  int32_t* tokens = nullptr;
+  float* logp = nullptr;
+  float* logits = nullptr;
+  const float* target_actions = nullptr;
+  const int32_t* target_tokens = nullptr;
+  const uint8_t* valid = nullptr;
+  int over = 0;
+  double temperature = 1.0;
 };
 
 extern thread_local std::string g_last_error;   // lram_last_error (defined in engine.hip)

@@ -1,5 +1,6 @@
 // One call from its inputs to its actions: the image and token front ends, the block stack, the action head; env-steps, repeated
-// forwards, stored contexts in chunks (lram_step, lram_step_images, lram_step_slots, lram_prefill, lram_encoder_step).
+// forwards, stored contexts in chunks (lram_step, lram_step_images, lram_step_slots, lram_prefill, lram_encoder_step), and the
+// head at every timestep of a stored context (lram_score, lram_score_last, lram_score_tokens).
 // Calls the stacks, gemm and the streams.
 #include "engine.h"
 
@@ -172,10 +173,53 @@ void embed_tokens(lram_engine* e, const Pass& pass, const Inputs& in, const floa
                   (L == 1 && e->B <= kTokenTapMaxBatch) ? e->TOK.p + r0 * D : nullptr, nullptr, stok_on ? &stok : nullptr);
 }
 
+// What every score launch of a call shares: the head's geometry, the sink's tensors, the slot table of a per-slot call.
+ScoreArgs score_args(const lram_engine* e, const ScoreSink& k, int discrete) {
+  const lram_config& c = e->cfg;
+  ScoreArgs a;
+  a.act_dim = c.act_dim, a.n_vocab = c.n_vocab, a.n_discrete = c.n_discrete, a.action_channels = c.action_channels;
+  a.tok_min = c.tok_min, a.tok_max = c.tok_max;
+  a.discrete = discrete == LRAM_HEAD_PER_SLOT ? 0 : discrete;
+  a.over = k.over, a.temperature = k.temperature;
+  a.target_actions = k.target_actions, a.target_tokens = k.target_tokens, a.valid = k.valid;
+  if (discrete == LRAM_HEAD_PER_SLOT) a.slot_flags = e->slot_dev, a.slot_act = e->slot_dev + e->B;
+  a.actions = k.actions, a.tokens = k.tokens, a.logp = k.logp, a.logits_out = k.logits;
+  return a;
+}
+
+// The head at EVERY timestep of the chunk of Lc timesteps from l0 on that the slice has just run through the stack: the chunk's
+// action-token rows of HID (row (b, l) at ((b * Lc + l) * T + pred) * D: one stride) against action_net, in blocks of at most
+// `cap` rows into the region's scratch, each block scored into rows [b, l0 + l] of the sink.  The exact fp32 matrix-core kernel
+// without split-K: a row's logits are one k-ordered fma chain whatever the block it falls into, so the outputs do not depend
+// on the scratch bound.  (A last block of <= 8 rows would take the GEMV kernel, another summation order: it starts
+// kScoreMinRows before the end instead and recomputes the rows it overlaps.)
+void score_chunk(lram_engine* e, const ScoreSink& k, const Slice& x, float* scratch, int64_t cap, int l0, int Lc, int L,
+                 int discrete) {
+  const lram_config& c = e->cfg;
+  const int D = c.d_model, T = c.tokens_per_step;
+  const int64_t nlog = (int64_t)c.act_dim * c.n_vocab, R = (int64_t)x.nb * Lc;
+  for (int64_t r = 0; r < R;) {
+    int64_t beg = r, nr = std::min(cap, R - r);
+    r += nr;
+    if (nr < lram_engine::kScoreMinRows && beg > 0) beg = R - lram_engine::kScoreMinRows, nr = lram_engine::kScoreMinRows;
+    GemmArgs gh;
+    gh.a = e->HID.p + (((size_t)x.b0 * Lc + beg) * T + c.pred_token) * D, gh.lda = (int64_t)T * D;
+    gh.w = e->w_head, gh.ldw = D, gh.c = scratch, gh.ldc = nlog, gh.bias = e->b_head;
+    gh.m = (int)nr, gh.n = (int)nlog, gh.k = D;
+    launch_gemm_f32(gh, x.s);
+    count_gemm(e, 2, gh);
+    ScoreArgs a = score_args(e, k, discrete);
+    a.logits = scratch, a.ld = nlog, a.row0 = (int64_t)x.b0 * Lc + beg, a.rows = nr;
+    a.inner = Lc, a.outer = L, a.off = l0;
+    launch_action_score(a, x.s);
+  }
+}
+
 // Action head on the last timestep of the last chunk (Tc tokens per env, last_steps timesteps): logits per env slice, then
 // argmax or a sampled draw.  What discrete = LRAM_HEAD_PER_SLOT needs was checked by the entry (check_head_mode).
+// With a sink (lram_score over L timesteps) the same logits are scored into row [b, L - 1] of the sink's tensors instead: no draw.
 void action_head(lram_engine* e, const Pass& pass, const std::vector<Slice>& sl, int Tc, int last_steps, int discrete,
-                 float* actions, int32_t* tokens) {
+                 float* actions, int32_t* tokens, const ScoreSink* sink = nullptr, int L = 1) {
   const lram_config& c = e->cfg;
   const int D = c.d_model, T = c.tokens_per_step;
   const int64_t nlog = (int64_t)c.act_dim * c.n_vocab;
@@ -186,6 +230,7 @@ void action_head(lram_engine* e, const Pass& pass, const std::vector<Slice>& sl,
   const int col_end = (pass.compat_shared && col_begin + 1 < pass.compat_passes) ? col_begin + 1 : c.act_dim;
   const int col0 = pass.compat_shared ? col_begin : 0;
   const bool per_slot = discrete == LRAM_HEAD_PER_SLOT;
+  e->last_head = discrete;
   for (const Slice& x : sl) {
     const size_t r0 = (size_t)x.b0 * Tc, b0 = x.b0;
     const uint8_t* sf = per_slot ? e->slot_dev + b0 : nullptr;
@@ -195,6 +240,13 @@ void action_head(lram_engine* e, const Pass& pass, const std::vector<Slice>& sl,
     gh.c = e->LOGITS.p + b0 * nlog + (size_t)col0 * c.n_vocab, gh.ldc = nlog, gh.bias = e->b_head + (size_t)col0 * c.n_vocab;
     gh.m = x.nb, gh.n = (col_end - col0) * c.n_vocab, gh.k = D;
     gemm(e, gh, x.s);
+    if (sink != nullptr) {
+      ScoreArgs a = score_args(e, *sink, discrete);
+      a.logits = e->LOGITS.p + b0 * nlog, a.ld = nlog, a.row0 = (int64_t)b0, a.rows = x.nb;
+      a.inner = 1, a.outer = L, a.off = L - 1;
+      launch_action_score(a, x.s);
+      continue;
+    }
     if (e->sampling) {
       SampleArgs sp = e->sample;
       sp.slot0 += b0, sp.draw = e->sample_draw;
@@ -212,8 +264,11 @@ void action_head(lram_engine* e, const Pass& pass, const std::vector<Slice>& sl,
 // L consecutive timesteps for every env slot (L = 1: one env-step).  The reset mask applies before the first timestep; the
 // action head runs on the last timestep only (and only if an output buffer is given).  One fork / join of the slice streams
 // brackets the whole call -- of repeated forwards (call.compat_passes > 1): one fork ahead of the first, one join behind the last.
+// With a sink (lram_score; `actions` is then null) the head runs at every timestep: after the stack pass of every chunk, on
+// that chunk's stream and workspace (score_chunk), and once more on the last timestep through the very launches a call without
+// a sink makes for it (action_head) -- row [b, L - 1] of the sink is what lram_prefill computes, and LOGITS is left as it leaves it.
 void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, const uint8_t* reset, int discrete, float* actions,
-                        int32_t* tokens, hipStream_t s) {
+                        int32_t* tokens, hipStream_t s, const ScoreSink* sink = nullptr) {
   const lram_config& c = e->cfg;
   const int D = c.d_model, T = c.tokens_per_step, L = in.L;
   e->sync_used = 0, e->edge_used = 0;
@@ -250,8 +305,18 @@ void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, cons
   hipStream_t hbm = s;
   const std::vector<Slice> sl = lanes ? std::vector<Slice>{Slice{0, e->B, s}} : make_slices(e, s, &hbm);
   const bool multi = sl.size() > 1;
-  if (multi && call.compat_pass == 0) fork_slices(e, sl, hbm, s);
   const int NL = lanes ? e->n_lanes : 1;
+  // scratch of the per-timestep head: one region per lane / slice (a one-timestep call has its only timestep scored by action_head)
+  const int64_t score_cap = std::max<int64_t>(lram_engine::kScoreMinRows, std::min<int64_t>(e->score_rows, (int64_t)e->B * kChunk));
+  const size_t score_region = (size_t)score_cap * c.act_dim * c.n_vocab;
+  if (sink != nullptr && L > 1) {
+    const size_t want = score_region * (lanes ? (size_t)NL : sl.size());
+    if (e->SCORE_LG.n < want) {
+      LRAM_HIP_CHECK(hipDeviceSynchronize());
+      e->SCORE_LG.alloc(want);
+    }
+  }
+  if (multi && call.compat_pass == 0) fork_slices(e, sl, hbm, s);
   hipStream_t lane_s[lram_engine::kMaxLanes] = {s, s, s};
   if (lanes) {
     while ((int)e->micro_streams.size() < NL - 1) {
@@ -287,9 +352,15 @@ void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, cons
     Pass pass = call;
     if (lanes) pass.lane_wait = ci > 0 ? &e->lane_ev[(lane + 1) % NL] : nullptr, pass.lane_rec = &e->lane_ev[lane];
     run_stack(e, pass, Tc, l == 0 ? reset : nullptr, use, lanes ? lane_s[lane] : hbm);
+    if (sink != nullptr && L > 1)
+      for (size_t i = 0; i < use.size(); ++i)
+        score_chunk(e, *sink, use[i], e->SCORE_LG.p + (lanes ? (size_t)lane : i) * score_region, score_cap, l, Lc, L, discrete);
   }
   for (int k = 1; k < NL; ++k) stream_after(e, s, lane_s[k], true);
-  if (actions != nullptr) action_head(e, call, sl, Tc, last_steps, discrete, actions, tokens);
+  if (sink != nullptr)
+    action_head(e, call, sl, Tc, last_steps, discrete, nullptr, nullptr, sink, L);
+  else if (actions != nullptr)
+    action_head(e, call, sl, Tc, last_steps, discrete, actions, tokens);
   if (multi && call.compat_pass == call.compat_passes - 1) join_slices(e, sl, hbm, s);
 }
 
@@ -455,6 +526,72 @@ int32_t lram_prefill(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_em
     timesteps_launches(e, Pass{}, Inputs{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps}, dev_reset_mask,
                        discrete, dev_actions, dev_tokens, static_cast<hipStream_t>(stream));
     if (dev_actions != nullptr) sample_draw_advance(e, static_cast<hipStream_t>(stream));
+  });
+}
+
+int32_t lram_score(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
+                   const float* dev_reward_seq, int32_t timesteps, const uint8_t* dev_reset_mask, int32_t discrete,
+                   const float* dev_target_actions, const int32_t* dev_target_tokens, const uint8_t* dev_valid, int32_t over,
+                   double temperature, float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits, void* stream) {
+  return guarded([&] {
+    step_entry(e, "lram_score");
+    LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_score: null device pointer");
+    LRAM_REQUIRE(timesteps >= 1, "lram_score: timesteps must be >= 1");
+    // refusals: before anything is launched, the recurrent state untouched
+    LRAM_REQUIRE(e->compat_repeat <= 1, "lram_score: the Mamba repeated-forward mode is on (lram_set_compat_mode, mamba_repeat > 1): "
+                                        "its trajectories advance the state once per action dim and are not scored");
+    LRAM_REQUIRE(!(dev_target_actions && dev_target_tokens),
+                 "lram_score: both dev_target_actions and dev_target_tokens are given (at most one)");
+    LRAM_REQUIRE(dev_actions || dev_tokens || dev_logp || dev_logits, "lram_score: no output is given");
+    LRAM_REQUIRE(!dev_logp || dev_target_actions || dev_target_tokens,
+                 "lram_score: dev_logp needs a target (dev_target_actions or dev_target_tokens)");
+    LRAM_REQUIRE(over == 0 || over == 1, "lram_score: over must be 0 (the whole vocabulary) or 1 (the selectable range)");
+    LRAM_REQUIRE(temperature > 0.0 && temperature < (double)INFINITY, "lram_score: temperature must be finite and > 0");
+    LRAM_REQUIRE(discrete == 0 || discrete == 1 || discrete == LRAM_HEAD_PER_SLOT, "lram_score: discrete must be 0, 1 or LRAM_HEAD_PER_SLOT");
+    LRAM_REQUIRE(discrete != LRAM_HEAD_PER_SLOT || e->slot_table, "lram_score: LRAM_HEAD_PER_SLOT needs a slot table (lram_set_slot_table)");
+    LRAM_REQUIRE(discrete != 1 || e->cfg.n_discrete >= 1, "lram_score: a discrete head needs n_discrete >= 1");
+    ScoreSink sink;
+    sink.actions = dev_actions, sink.tokens = dev_tokens, sink.logp = dev_logp, sink.logits = dev_logits;
+    sink.target_actions = dev_target_actions, sink.target_tokens = dev_target_tokens, sink.valid = dev_valid;
+    sink.over = over, sink.temperature = temperature;
+    // (never captured, never a draw: the sampling mode and its counter are left alone)
+    timesteps_launches(e, Pass{}, Inputs{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps}, dev_reset_mask,
+                       discrete, nullptr, nullptr, static_cast<hipStream_t>(stream), &sink);
+  });
+}
+
+int32_t lram_score_last(lram_engine* e, const int32_t* dev_tokens, int32_t over, double temperature, float* dev_logp,
+                        void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(e && e->B > 0, "lram_score_last: state not allocated (call lram_state_alloc)");
+    LRAM_HIP_CHECK(hipSetDevice(e->device));
+    prof_tick(e);
+    LRAM_REQUIRE(dev_tokens && dev_logp, "lram_score_last: null device pointer");
+    LRAM_REQUIRE(e->last_head >= 0, "lram_score_last: no action-producing call since lram_state_alloc: there are no logits to score");
+    LRAM_REQUIRE(e->last_head != LRAM_HEAD_PER_SLOT || e->slot_table,
+                 "lram_score_last: the last call was per-slot and the slot table has been cleared since");
+    ScoreSink sink;
+    sink.logp = dev_logp, sink.target_tokens = dev_tokens, sink.over = over, sink.temperature = temperature;
+    ScoreArgs a = score_args(e, sink, e->last_head);
+    a.logits = e->LOGITS.p, a.ld = (int64_t)e->cfg.act_dim * e->cfg.n_vocab, a.rows = e->B;
+    launch_action_score(a, static_cast<hipStream_t>(stream));
+  });
+}
+
+int32_t lram_score_tokens(const float* dev_logits, int64_t rows, int32_t act_dim, int32_t n_vocab, int32_t n_discrete,
+                          int32_t action_channels, float tok_min, float tok_max, int32_t discrete, const float* dev_target_actions,
+                          const int32_t* dev_target_tokens, const uint8_t* dev_valid, int32_t over, double temperature,
+                          float* dev_actions, int32_t* dev_tokens, float* dev_logp, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(dev_logits != nullptr, "lram_score_tokens: null device pointer");
+    LRAM_REQUIRE(discrete == 0 || discrete == 1, "lram_score_tokens: discrete must be 0 or 1");
+    ScoreArgs a;
+    a.logits = dev_logits, a.ld = (int64_t)act_dim * n_vocab, a.rows = rows;
+    a.act_dim = act_dim, a.n_vocab = n_vocab, a.n_discrete = n_discrete, a.action_channels = action_channels;
+    a.tok_min = tok_min, a.tok_max = tok_max, a.discrete = discrete, a.over = over, a.temperature = temperature;
+    a.target_actions = dev_target_actions, a.target_tokens = dev_target_tokens, a.valid = dev_valid;
+    a.actions = dev_actions, a.tokens = dev_tokens, a.logp = dev_logp;
+    launch_action_score(a, static_cast<hipStream_t>(stream));
   });
 }
 

@@ -1,0 +1,200 @@
+// Action head, scoring mode: per (row, action dim) the greedy token, the de-tokenised greedy action and the log-probability
+// of a GIVEN target token under the row's logits -- what grading a stored trajectory needs at every timestep.
+//
+// Reference computation replaced: the cross-entropy of the recorded actions under the no-cache forward's action logits
+// (src/algos/universal_decision_transformer_sb3.py:398-434: tokenize_actions of the float targets, CE over act_dim x n_vocab),
+// with the targets tokenised as MinMaxTokenizer.tokenize does (src/tokenizers_custom/minmax_tokenizer.py:14-29) and
+// `temperature` multiplying the logits as sample_from_logits does (src/algos/models/model_utils.py:7-32).
+//
+// One wave per (row, action dim), four per workgroup: the grid of action_argmax_kernel (misc_kernels.hip) and
+// action_sample_kernel (sample_kernels.hip).  The row is read from global memory ONCE, coalesced, into the wave's LDS strip
+// (and from there, if asked, copied to the caller's logits tensor); everything else walks the strip:
+//   greedy token   first index of the maximum over the selectable range (argmax_beats: the argmax kernel's rule), then its
+//                  inv_tokenize arithmetic: a row gives the same token and action on both kernels
+//   target token   an int32 token, or a float action tokenised here: trunc((x - min) / bin_width) clamped to
+//                  0 .. action_channels - 1, plus n_discrete -- fp32 subtract, IEEE fp32 division; discrete rows: (int)x
+//   logp           t * x[target] - logsumexp(t * x) over the normalisation range; maximum, sum and log in fp64, one fp32
+//                  rounding at the store.  over = 0: all n_vocab logits (the reference's CE); over = 1: the selectable range
+//                  (n_discrete on discrete rows, n_vocab otherwise: what the sampling head draws from)
+// A target outside the normalisation range or a non-finite float target: -inf.  A NaN in the range: NaN.  A -inf logit at the
+// target: -inf.  Rows with valid[row] == 0, columns j >= act_dim[slot] of a slot table and columns j >= 1 of a discrete call
+// write logp 0, token -1, action 0 and nothing else (wave-uniform branch).  Rows wider than 512 logits are not staged: they
+// are walked in global memory (the second walk is served by the cache).
+#include "common.h"
+#include "device_math.h"
+
+namespace lram {
+namespace {
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// t * x - zmax with the product rounded to fp64 BEFORE the subtraction.  Fused into one fma the product would keep its
+// exact low bits, the row's maximum would not cancel against zmax = t * max x, and a one-logit row would score -7e-17, not 0.
+__device__ __forceinline__ double scaled_minus(double t, float x, double zmax) {
+#pragma clang fp contract(off)
+  const double z = t * (double)x;
+  return z - zmax;
+}
+
+// PER floats per lane in the wave's LDS strip; PER = 0: no strip, the row stays in global memory.
+template <int PER>
+__global__ __launch_bounds__(256) void action_score_kernel(ScoreArgs a) {
+  __shared__ float stage[4][64 * (PER > 0 ? PER : 1)];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t item = (int64_t)blockIdx.x * 4 + wv;
+  const bool in_grid = item < a.rows * a.act_dim;
+  const int64_t r = in_grid ? item / a.act_dim : 0;
+  const int j = in_grid ? (int)(item - r * a.act_dim) : 0;
+  const int64_t g = a.row0 + r, env = g / a.inner;
+  const int64_t orow = env * a.outer + a.off + (g - env * a.inner);   // the row of the outputs, targets and `valid`
+  const int64_t o = orow * a.act_dim + j;
+  int discrete = a.discrete;
+  bool fill = false;
+  if (in_grid) {  // (every condition below is the same for the whole wave)
+    if (a.valid != nullptr && a.valid[orow] == 0) {
+      fill = true;
+    } else if (a.slot_flags != nullptr) {
+      discrete = a.slot_flags[env] & 1;
+      fill = j >= (int)a.slot_act[env];
+    } else {
+      fill = discrete && j >= 1;
+    }
+  }
+  const bool active = in_grid && !fill;
+  const int nsel = discrete ? a.n_discrete : a.n_vocab;      // the greedy token's range
+  const int nnorm = a.over ? nsel : a.n_vocab;               // the softmax's range (>= nsel)
+  const int nread = (a.logits_out != nullptr || !a.over) ? a.n_vocab : nsel;
+  const float* src = a.logits + r * a.ld + (int64_t)j * a.n_vocab;
+  const float* row = src;
+  if constexpr (PER > 0) {
+    if (active) {
+#pragma unroll
+      for (int q = 0; q < PER; ++q) {
+        const int i = lane + 64 * q;
+        if (i < nread) {
+          const float x = src[i];
+          stage[wv][i] = x;
+          if (a.logits_out != nullptr) a.logits_out[o * a.n_vocab + i] = x;
+        }
+      }
+    }
+    __syncthreads();
+    row = stage[wv];
+  } else {
+    if (active && a.logits_out != nullptr)
+      for (int i = lane; i < nread; i += 64) a.logits_out[o * a.n_vocab + i] = src[i];
+  }
+  if (fill && lane == 0) {
+    if (a.logp != nullptr) a.logp[o] = 0.f;
+    if (a.tokens != nullptr) a.tokens[o] = -1;
+    if (a.actions != nullptr) a.actions[o] = 0.f;
+  }
+  if (!active) return;
+
+  float best = -INFINITY, vmax = -INFINITY;
+  int bi = 0x7fffffff;
+  bool nan_here = false;
+  for (int i = lane; i < nnorm; i += 64) {
+    const float x = row[i];
+    nan_here |= x != x;
+    vmax = fmaxf(vmax, x);
+    if (i < nsel && argmax_beats(x, i, best, bi)) best = x, bi = i;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(best, off, 64);
+    const int oi = __shfl_xor(bi, off, 64);
+    if (argmax_beats(ov, oi, best, bi)) best = ov, bi = oi;
+    vmax = fmaxf(vmax, __shfl_xor(vmax, off, 64));
+  }
+  const bool has_nan = __any(nan_here);
+  if (lane == 0) {
+    if (a.tokens != nullptr) a.tokens[o] = bi;
+    if (a.actions != nullptr) {
+      float out;
+      if (discrete) {
+        out = (float)bi;
+      } else {  // inv_tokenize, as action_argmax_kernel
+        int t = bi - a.n_discrete;
+        t = t < 0 ? 0 : t;
+        const float bin_width = (a.tok_max - a.tok_min) / (float)a.action_channels;
+        out = (float)t * bin_width + a.tok_min;
+      }
+      a.actions[o] = out;
+    }
+  }
+  if (a.logp == nullptr) return;
+
+  // the target token (the same value on every lane)
+  int tgt = -1;
+  if (a.target_tokens != nullptr) {
+    tgt = a.target_tokens[o];
+  } else {
+    const float x = a.target_actions[o];
+    if (x - x == 0.f) {  // finite
+      if (discrete) {
+        tgt = (int)x;
+      } else {  // MinMaxTokenizer.tokenize
+        const float bin_width = (a.tok_max - a.tok_min) / (float)a.action_channels;
+        const float q = __fdiv_rn(__fsub_rn(x, a.tok_min), bin_width);
+        const float top = (float)(a.action_channels - 1);
+        const int t = q <= 0.f ? 0 : (q >= top ? a.action_channels - 1 : (int)q);
+        tgt = t + a.n_discrete;
+      }
+    }
+  }
+  // (t > 0 and rounding is monotone: the maximum of t * x is t * max x)
+  const double zmax = a.temperature * (double)vmax;
+  double sum = 0.0;
+  for (int i = lane; i < nnorm; i += 64) sum += exp(scaled_minus(a.temperature, row[i], zmax));
+  sum = wave_sum_f64(sum);
+  if (lane == 0) {
+    float lp;
+    if (tgt < 0 || tgt >= nnorm)
+      lp = -INFINITY;
+    else if (has_nan)
+      lp = __builtin_nanf("");
+    else
+      lp = (float)(scaled_minus(a.temperature, row[tgt], zmax) - log(sum));
+    a.logp[o] = lp;
+  }
+}
+
+}  // namespace
+
+void launch_action_score(const ScoreArgs& a, hipStream_t stream) {
+  LRAM_REQUIRE(a.logits != nullptr && a.rows >= 1 && a.inner >= 1, "action score: bad rows");
+  LRAM_REQUIRE(a.act_dim >= 1 && a.n_vocab >= 1 && a.n_discrete >= 0 && a.n_discrete <= a.n_vocab && a.action_channels >= 1,
+               "action score: bad head dimensions");
+  LRAM_REQUIRE(!(a.discrete == 1 && a.slot_flags == nullptr && a.n_discrete < 1), "action score: a discrete head needs n_discrete >= 1");
+  LRAM_REQUIRE(a.ld >= (int64_t)a.act_dim * a.n_vocab, "action score: ld must be >= act_dim * n_vocab");
+  LRAM_REQUIRE((a.slot_flags == nullptr) == (a.slot_act == nullptr), "action score: the slot table's two arrays go together");
+  LRAM_REQUIRE(a.over == 0 || a.over == 1, "action score: over must be 0 (the whole vocabulary) or 1 (the selectable range)");
+  LRAM_REQUIRE(a.temperature > 0.0 && a.temperature < (double)INFINITY, "action score: temperature must be finite and > 0");
+  LRAM_REQUIRE(a.target_actions == nullptr || a.target_tokens == nullptr,
+               "action score: both target_actions and target_tokens are given (at most one)");
+  LRAM_REQUIRE(a.logp == nullptr || a.target_actions != nullptr || a.target_tokens != nullptr,
+               "action score: logp needs a target (target_actions or target_tokens)");
+  LRAM_REQUIRE(a.actions != nullptr || a.tokens != nullptr || a.logp != nullptr || a.logits_out != nullptr,
+               "action score: no output is given");
+  const int64_t items = a.rows * a.act_dim;
+  LRAM_REQUIRE(items <= ((int64_t)1 << 32), "action score: rows * act_dim must be <= 2^32");
+  const dim3 grid((unsigned)((items + 3) / 4)), block(256);
+#define LRAM_SCORE_LAUNCH(PER) hipLaunchKernelGGL(action_score_kernel<PER>, grid, block, 0, stream, a)
+  if (a.n_vocab <= 64)
+    LRAM_SCORE_LAUNCH(1);
+  else if (a.n_vocab <= 320)
+    LRAM_SCORE_LAUNCH(5);
+  else if (a.n_vocab <= kSampleMaxRow)
+    LRAM_SCORE_LAUNCH(8);
+  else
+    LRAM_SCORE_LAUNCH(0);
+#undef LRAM_SCORE_LAUNCH
+  LRAM_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace lram

@@ -55,6 +55,12 @@ _SYMBOLS = {
     "lram_step": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP, _VP, ctypes.c_int32, _VP, _VP, _VP]),
     "lram_prefill": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP, ctypes.c_int32, _VP, ctypes.c_int32, _VP, _VP,
                                       _VP]),
+    "lram_score": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP, ctypes.c_int32, _VP, ctypes.c_int32, _VP, _VP, _VP,
+                                    ctypes.c_int32, ctypes.c_double, _VP, _VP, _VP, _VP, _VP]),
+    "lram_score_last": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, ctypes.c_double, _VP, _VP]),
+    "lram_score_tokens": (ctypes.c_int32, [_VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.c_float, ctypes.c_float, ctypes.c_int32, _VP, _VP, _VP, ctypes.c_int32,
+                                           ctypes.c_double, _VP, _VP, _VP, _VP]),
     "lram_encoder_step": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP, _VP]),
     "lram_get_taps": (ctypes.c_int32, [_VP, _VP, _VP, _VP, _VP]),
     "lram_state_numel": (ctypes.c_int64, [_VP, ctypes.c_int32, ctypes.c_int32]),
@@ -197,6 +203,28 @@ def _head_mode(discrete) -> int:
             raise ValueError(f'discrete must be False, True or "per_slot", got {discrete!r}')
         return LRAM_HEAD_PER_SLOT
     return int(bool(discrete))
+
+
+def _over_mode(over) -> int:
+    """The `over` argument of the scoring entries: "vocab" (all n_vocab logits, the reference's cross-entropy) or
+    "selectable" (the range the head in use picks from)."""
+    if over not in ("vocab", "selectable"):
+        raise ValueError(f'over must be "vocab" or "selectable", got {over!r}')
+    return int(over == "selectable")
+
+
+class ScoreResult:
+    """What Engine.score returns: `actions` float32, `tokens` int32, `logp` float32 [B, L, act_dim] and `logits` float32
+    [B, L, act_dim, n_vocab]; a field that was not asked for is None.  Masked timesteps and unused columns hold action 0,
+    token -1, logp 0 (and zero logits)."""
+    __slots__ = ("actions", "tokens", "logp", "logits")
+
+    def __init__(self, actions=None, tokens=None, logp=None, logits=None):
+        self.actions, self.tokens, self.logp, self.logits = actions, tokens, logp, logits
+
+    def __repr__(self):
+        f = ", ".join(f"{k}={None if getattr(self, k) is None else tuple(getattr(self, k).shape)}" for k in self.__slots__)
+        return f"ScoreResult({f})"
 
 
 def _chk_dev(t: torch.Tensor, dtype, shape, device, name):
@@ -431,6 +459,64 @@ class Engine:
                                                _ptr(reward_seq), int(L), _ptr(reset_mask), _head_mode(discrete), _ptr(act),
                                                _ptr(tok), _stream_ptr(self.device)))
         return (act, tok) if want_action else (None, None)
+
+    def score(self, obs_seq: torch.Tensor, rtg_seq: torch.Tensor, reward_seq: torch.Tensor, *,
+              actions: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None,
+              valid: Optional[torch.Tensor] = None, reset_mask: Optional[torch.Tensor] = None, discrete=False,
+              over: str = "vocab", temperature: float = 1.0, want=("actions", "tokens", "logp"), logits: bool = False,
+              obs_is_embedding: bool = False) -> ScoreResult:
+        """Score L stored timesteps in one call (lram_score): prefill() with the action head at EVERY timestep -- the
+        reference's no-cache forward plus the loss it takes from the logits (universal_decision_transformer_sb3.py:398-434).
+        `actions` float32 [B, L, act_dim] (recorded actions, tokenised on the device) or `tokens` int32 [B, L, act_dim] are the
+        targets of `logp`; `valid` uint8 / bool [B, L] masks outputs only (the state advances through every timestep);
+        over="vocab" normalises over all n_vocab logits (the reference's cross-entropy), "selectable" over the range the head
+        picks from; `temperature` multiplies the logits.  `want` names the outputs among "actions", "tokens", "logp";
+        logits=True adds the raw logits.  The state afterwards equals prefill()'s; nothing is drawn in sampling mode."""
+        B, spec = self.batch, self.spec
+        if obs_seq.dim() != 3:
+            raise ValueError("obs_seq must be [B, L, state_dim]")
+        L = obs_seq.shape[1]
+        want = (want,) if isinstance(want, str) else tuple(want)
+        for w in want:
+            if w not in ("actions", "tokens", "logp"):
+                raise ValueError(f'want: unknown output {w!r} (choose among "actions", "tokens", "logp")')
+        _chk_dev(obs_seq, torch.float32, (B, L, spec.d_model if obs_is_embedding else spec.state_dim), self.device,
+                 "obs_seq")
+        _chk_dev(rtg_seq, torch.float32, (B, L), self.device, "rtg_seq")
+        _chk_dev(reward_seq, torch.float32, (B, L), self.device, "reward_seq")
+        if reset_mask is not None:
+            _chk_dev(reset_mask, torch.uint8, (B,), self.device, "reset_mask")
+        if actions is not None:
+            _chk_dev(actions, torch.float32, (B, L, spec.act_dim), self.device, "actions")
+        if tokens is not None:
+            _chk_dev(tokens, torch.int32, (B, L, spec.act_dim), self.device, "tokens")
+        if valid is not None:
+            if valid.dtype == torch.bool:
+                valid = valid.to(torch.uint8)
+            _chk_dev(valid, torch.uint8, (B, L), self.device, "valid")
+        A = spec.act_dim
+        # zeroed: the entries the call leaves alone (the logits of masked timesteps) must not depend on the allocator
+        res = ScoreResult(
+            actions=torch.zeros(B, L, A, dtype=torch.float32, device=self.device) if "actions" in want else None,
+            tokens=torch.zeros(B, L, A, dtype=torch.int32, device=self.device) if "tokens" in want else None,
+            logp=torch.zeros(B, L, A, dtype=torch.float32, device=self.device) if "logp" in want else None,
+            logits=torch.zeros(B, L, A, spec.n_vocab, dtype=torch.float32, device=self.device) if logits else None)
+        _check(self.lib, self.lib.lram_score(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq), _ptr(reward_seq),
+                                             int(L), _ptr(reset_mask), _head_mode(discrete), _ptr(actions), _ptr(tokens),
+                                             _ptr(valid), _over_mode(over), float(temperature), _ptr(res.actions),
+                                             _ptr(res.tokens), _ptr(res.logp), _ptr(res.logits), _stream_ptr(self.device)))
+        return res
+
+    def last_logp(self, tokens: torch.Tensor, over: str = "selectable", temperature: float = 1.0) -> torch.Tensor:
+        """Log-probabilities float32 [B, act_dim] of `tokens` (int32 [B, act_dim]: what step / prefill just returned) under the
+        logits of the last action-producing call (lram_score_last).  over="selectable" with the armed temperature is the
+        distribution an unfiltered sampling head draws from; top-k / top-p are not applied."""
+        B, A = self.batch, self.spec.act_dim
+        _chk_dev(tokens, torch.int32, (B, A), self.device, "tokens")
+        out = torch.zeros(B, A, dtype=torch.float32, device=self.device)
+        _check(self.lib, self.lib.lram_score_last(self._h, _ptr(tokens), _over_mode(over), float(temperature), _ptr(out),
+                                                  _stream_ptr(self.device)))
+        return out
 
     def embed_images(self, images: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """uint8 frames [B, C, H, W] -> state-token embeddings [B, d_model] through the IMPALA CNN kernels
@@ -733,6 +819,38 @@ def sample_tokens(logits: torch.Tensor, uniform: torch.Tensor, temperature: floa
     _check(lib, lib.lram_sample_tokens(_ptr(logits), R, int(n), int(ld), float(temperature), int(top_k), float(top_p),
                                        _ptr(uniform), _ptr(out), _stream_ptr(logits.device)))
     return out
+
+
+def score_tokens(logits: torch.Tensor, spec_or_dims, *, actions: Optional[torch.Tensor] = None,
+                 tokens: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None, discrete: bool = False,
+                 over: str = "vocab", temperature: float = 1.0, want=("actions", "tokens", "logp")) -> ScoreResult:
+    """The scoring head's device code on caller logits (lram_score_tokens): logits float32 [R, act_dim, n_vocab];
+    `spec_or_dims` a ModelSpec or (n_discrete, action_channels); targets / valid / outputs per row as Engine.score."""
+    lib = load_library()
+    if logits.dim() != 3 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("logits must be a contiguous float32 tensor [rows, act_dim, n_vocab]")
+    R, A, V = logits.shape
+    if isinstance(spec_or_dims, ModelSpec):
+        n_discrete, channels = spec_or_dims.n_discrete, spec_or_dims.action_channels
+    else:
+        n_discrete, channels = (int(x) for x in spec_or_dims)
+    dev = logits.device
+    if actions is not None:
+        _chk_dev(actions, torch.float32, (R, A), dev, "actions")
+    if tokens is not None:
+        _chk_dev(tokens, torch.int32, (R, A), dev, "tokens")
+    if valid is not None:
+        if valid.dtype == torch.bool:
+            valid = valid.to(torch.uint8)
+        _chk_dev(valid, torch.uint8, (R,), dev, "valid")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    res = ScoreResult(actions=torch.zeros(R, A, dtype=torch.float32, device=dev) if "actions" in want else None,
+                      tokens=torch.zeros(R, A, dtype=torch.int32, device=dev) if "tokens" in want else None,
+                      logp=torch.zeros(R, A, dtype=torch.float32, device=dev) if "logp" in want else None)
+    _check(lib, lib.lram_score_tokens(_ptr(logits), R, A, V, n_discrete, channels, -1.0, 1.0, int(bool(discrete)),
+                                      _ptr(actions), _ptr(tokens), _ptr(valid), _over_mode(over), float(temperature),
+                                      _ptr(res.actions), _ptr(res.tokens), _ptr(res.logp), _stream_ptr(dev)))
+    return res
 
 
 def sample_uniforms(seed: int, slot_base: int, n_slots: int, act_dim: int, draw: int, device=None) -> torch.Tensor:

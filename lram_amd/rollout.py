@@ -273,3 +273,34 @@ def eval_log_record(prefix: str, env_name: str, idx: int, episode_rewards, episo
         if num_envs == 1:
             rec[f"{prefix}/{score_type}"] = score
     return rec
+
+
+def score_loss(result, valid, act_mask=None, reduction: str = "reference") -> torch.Tensor:
+    """The action loss of scored trajectories: `result` is what Engine.score / RecurrentAgent.score_trajectories returned (or
+    its logp tensor [B, L, act_dim]); the per-entry loss is -logp, the cross-entropy of the recorded token.  `valid` [B, L]
+    (the reference's attention_mask), `act_mask` [B, L, act_dim] or [B, act_dim] (its action_mask: the action dims the env
+    uses; None = all).
+      "reference": universal_decision_transformer_sb3.py:422-434 with an un-reduced loss function -- per valid timestep the
+                   masked mean along the action dims, sum(loss * mask) / (sum(mask) + 1e-8), then the mean over the valid
+                   timesteps (a timestep whose action mask is all zero counts with loss 0);
+      "mean":      the plain mean over the valid, unmasked entries (the reference's reduced loss functions).
+    Pure torch, any device; entries that are masked out never reach the sum (a -inf there does no harm)."""
+    logp = getattr(result, "logp", result)
+    if logp is None:
+        raise ValueError("score_loss: the result holds no logp (score with \"logp\" in want and a target)")
+    if logp.dim() != 3:
+        raise ValueError(f"score_loss: logp must be [B, L, act_dim], got {tuple(logp.shape)}")
+    B, L, A = logp.shape
+    valid = torch.as_tensor(valid, device=logp.device).reshape(B, L) > 0
+    if act_mask is None:
+        mask = torch.ones(B, L, A, dtype=torch.bool, device=logp.device)
+    else:
+        mask = torch.as_tensor(act_mask, device=logp.device) > 0
+        mask = (mask.reshape(B, 1, A) if mask.dim() == 2 else mask.reshape(B, L, A)).expand(B, L, A)
+    loss = torch.where(mask, -logp, torch.zeros_like(logp))[valid]     # [n_valid, A]
+    m = mask[valid].to(logp.dtype)
+    if reduction == "reference":
+        return (loss.sum(dim=1) / (m.sum(dim=-1) + 1e-8)).mean()
+    if reduction == "mean":
+        return loss.sum() / m.sum()
+    raise ValueError(f'score_loss: reduction must be "reference" or "mean", got {reduction!r}')
