@@ -296,7 +296,9 @@ int32_t lram_lazy_peek(lram_engine* e, int32_t block, int32_t which, float* dev_
  *   - Ordering against steps on `stream`: as lram_reset (the launches go to `stream`).  State pointers do not change: a captured
  *     graph stays valid.  With the Mamba stale_state mode every layer is copied all the same.
  *   - NOT moved: slot-table entries (lram_set_slot_table) and the sampling stream -- the Philox counter is keyed by the slot
- *     INDEX, so N slots holding copies of one context draw N independent continuations (best-of-N, branching evaluation). */
+ *     INDEX, so N slots holding copies of one context draw N independent continuations (best-of-N, branching evaluation).
+ *     Per-slot sampling settings (lram_set_sampling_slots) stay with the slot index in the same way: copy / save / load and
+ *     lram_reset neither move nor clear them, so the forks of one context can sit on a ladder of temperatures. */
 int64_t lram_slot_state_numel(const lram_engine* e);
 int32_t lram_state_copy_slots(lram_engine* e, const int32_t* host_src, const int32_t* host_dst, int32_t n, void* stream);
 int32_t lram_state_save_slots(lram_engine* e, const int32_t* host_slots, int32_t n, float* dev_records, void* stream);
@@ -355,6 +357,34 @@ int32_t lram_set_sampling(lram_engine* e, int32_t enable, double temperature, in
  * Any pointer may be NULL. */
 int32_t lram_get_sampling(lram_engine* e, int32_t* enable, double* temperature, int32_t* top_k, double* top_p, uint64_t* seed,
                           uint64_t* slot_base, uint64_t* draws);
+
+/* Per-slot sampling settings: host arrays of length `batch`, entry b for env slot b -- mode (0 = greedy: the argmax rule of the
+ * default path, bit for bit; 1 = sample), temperature, top_k, top_p with the meaning they have in lram_set_sampling.  While a
+ * table is set every row of every action-producing call takes its slot's entry in place of lram_set_sampling's temperature /
+ * top_k / top_p; seed, slot_base and the draw counter d stay those of lram_set_sampling, and d advances once per call as before
+ * (greedy slots read no uniform).  All four pointers NULL clears the table: the launches are then again exactly those of
+ * lram_set_sampling alone (the per-slot table is a separate kernel instantiation).
+ * Needs sampling armed; lram_set_sampling (arming or disarming) and lram_state_alloc clear the table.  Errors, each naming the
+ * slot: mode > 1, temperature not finite or <= 0, top_p outside [0, 1], top_k < 0 or > n_vocab.  The top_k bound of the head
+ * in use is per slot: a call whose head (its `discrete` argument, or the slot table's flag under LRAM_HEAD_PER_SLOT /
+ * lram_step_slots) gives some SAMPLING slot n_discrete < top_k logits is refused before anything is launched, with a text
+ * naming the slot; greedy slots and continuous slots of a mixed table are not bound by n_discrete.
+ * Synchronises the device and drops a captured graph: not a hot-path call. */
+int32_t lram_set_sampling_slots(lram_engine* e, const uint8_t* mode, const double* temperature, const int32_t* top_k,
+                                const double* top_p);
+/* Copies the table in effect back (host arrays of length batch; any pointer may be NULL); *set = 0 and nothing written when
+ * no table is set. */
+int32_t lram_get_sampling_slots(lram_engine* e, uint8_t* mode, double* temperature, int32_t* top_k, double* top_p, int32_t* set);
+
+/* Log-probabilities [batch, act_dim] of dev_tokens [batch, act_dim] under the distribution the sampling head draws from: the
+ * logits of the last action-producing call, the settings armed NOW (the per-slot entries where a table is set, those of
+ * lram_set_sampling otherwise), steps 1-3 of lram_set_sampling applied -- t * (x_tok - max) - log(sum over the support of
+ * exp(t * (x - max))) in fp64, one fp32 rounding at the store.  A token outside the support or outside 0 .. n - 1: -inf; a
+ * support of one entry: exactly 0; a row on the argmax rule (a greedy slot, a NaN, a maximum of +-inf, nothing left): 0 at the
+ * argmax token, -inf elsewhere; columns the slot does not use and token -1: the fill value 0 (as lram_score_last).
+ * Deterministic: draws nothing, d is unchanged.  Errors as lram_score_last when there are no logits yet; sampling not armed
+ * is an error too. */
+int32_t lram_score_last_sampled(lram_engine* e, const int32_t* dev_tokens, float* dev_logp, void* stream);
 
 /* Per-kernel timing of the recurrent step, measured with HIP events on the stream the kernels are
  * launched on.  lram_profile_begin arms it; every later lram_step records one (start, stop) event pair
@@ -430,6 +460,14 @@ int32_t lram_gemm_f16x2_presplit(const float* dev_a, int64_t lda, const float* d
  * receives the token of steps 1-4 of lram_set_sampling. */
 int32_t lram_sample_tokens(const float* dev_logits, int64_t rows, int32_t n, int64_t ld, double temperature, int32_t top_k,
                            double top_p, const double* dev_uniform, int32_t* dev_tokens, void* stream);
+/* The same with per-row settings (test / evidence entry of lram_set_sampling_slots / lram_score_last_sampled): dev_mode uint8,
+ * dev_temperature double, dev_top_k int32, dev_top_p double, each [rows] on the device.  dev_uniform + dev_tokens_out
+ * (both or neither): the drawn token per row.  dev_tokens_in + dev_logp_out (both or neither): the log-probability of the
+ * given token per row under that row's settings (token -1: 0).  At least one pair must be given. */
+int32_t lram_sample_rows(const float* dev_logits, int64_t rows, int32_t n, int64_t ld, const uint8_t* dev_mode,
+                         const double* dev_temperature, const int32_t* dev_top_k, const double* dev_top_p,
+                         const double* dev_uniform, const int32_t* dev_tokens_in, int32_t* dev_tokens_out, float* dev_logp_out,
+                         void* stream);
 /* The uniforms an armed step would use at draw `draw`: dev_out (device double[n_slots, act_dim]) [s, j] for env slots
  * slot_base .. slot_base + n_slots - 1 (test / evidence entry). */
 int32_t lram_sample_uniforms(uint64_t seed, uint64_t slot_base, int64_t n_slots, int32_t act_dim, uint64_t draw,

@@ -98,9 +98,16 @@ class RecurrentAgent:
         # Not given here: what the configuration set (agent_params.a_sample_kwargs -> ModelSpec.a_sample_kwargs; no preset does).
         if a_sample_kwargs is None:
             a_sample_kwargs = spec.a_sample_kwargs
-        any_discrete = discrete if slot_table is None else bool(slot_table.discrete.any())
-        self.a_sample_kwargs = resolve_sample_kwargs(a_sample_kwargs, spec.n_discrete if any_discrete else spec.n_vocab)
+        # With a slot table the agent-level setting is checked against the head of every domain that falls back on it (a
+        # domain with its own Domain.a_sample_kwargs is checked against its own head), so a discrete domain in the table no
+        # longer caps the top_k of the continuous ones.
+        if slot_table is None:
+            self.a_sample_kwargs = resolve_sample_kwargs(a_sample_kwargs, spec.n_discrete if discrete else spec.n_vocab)
+        else:
+            self.a_sample_kwargs = resolve_sample_kwargs(a_sample_kwargs, spec.n_vocab)
+            slot_table.sample_settings(spec.n_discrete, spec.n_vocab, a_sample_kwargs)   # (raises what the head would refuse)
         self.sample_seed, self.sample_slot_base = int(sample_seed), int(sample_slot_base)
+        self._slot_sampling = {}   # set_slot_sampling: slot -> resolved dict | "greedy" (plain data: crosses a pickle)
         # host copy of the weights: lets the agent cross a process boundary (make_pickleable / reinit_cuda_kernels)
         self._state_dict = {k: v.detach().to("cpu") for k, v in state_dict.items()}
         self._graph = bool(graph)
@@ -158,9 +165,87 @@ class RecurrentAgent:
             return self.slot_table.discrete.clone()
         return torch.full((self.n_envs,), self.is_discrete, dtype=torch.bool)
 
+    def _head_width(self, slot: int) -> int:
+        return self.spec.n_discrete if bool(self.slot_is_discrete[slot]) else self.spec.n_vocab
+
+    def slot_sample_settings(self) -> Optional[dict]:
+        """The per-slot table the engine is given (Engine.set_sampling_slots' arguments), or None where the agent-level
+        setting serves every slot: the domains' own settings (SlotTable.sample_settings), then set_slot_sampling's.  A slot
+        with no setting of its own, of its domain or of the agent is greedy."""
+        table = getattr(self, "slot_table", None)
+        own = getattr(self, "_slot_sampling", {})
+        cols = None if table is None else table.sample_settings(self.spec.n_discrete, self.spec.n_vocab, self.a_sample_kwargs)
+        if cols is None:
+            if not own:
+                return None
+            base = self.a_sample_kwargs
+            cols = {"temperature": torch.full((self.n_envs,), 1.0 if base is None else base["temperature"], dtype=torch.float64),
+                    "top_k": torch.full((self.n_envs,), 0 if base is None else base["top_k"], dtype=torch.int32),
+                    "top_p": torch.full((self.n_envs,), 0.0 if base is None else base["top_p"], dtype=torch.float64),
+                    "greedy": torch.full((self.n_envs,), base is None, dtype=torch.bool)}
+        for b, s in own.items():
+            cols["greedy"][b] = s == "greedy"
+            if s != "greedy":
+                cols["temperature"][b], cols["top_k"][b], cols["top_p"][b] = s["temperature"], s["top_k"], s["top_p"]
+        return cols
+
     def _arm_sampling(self):
+        cols = self.slot_sample_settings()
         if self.a_sample_kwargs is not None:
             self.engine.set_sampling(seed=self.sample_seed, slot_base=self.sample_slot_base, **self.a_sample_kwargs)
+        elif cols is not None and not bool(cols["greedy"].all()):
+            # only slots / domains sample: the engine-wide settings are placeholders the table overrides on every slot
+            self.engine.set_sampling(temperature=1.0, top_k=0, top_p=0.0, seed=self.sample_seed, slot_base=self.sample_slot_base)
+        else:
+            return
+        if cols is not None:
+            self.engine.set_sampling_slots(temperature=cols["temperature"], top_k=cols["top_k"], top_p=cols["top_p"],
+                                           greedy=cols["greedy"])
+
+    def set_slot_sampling(self, slots, setting):
+        """Sampling settings of single env slots, with or without a slot table -- a temperature ladder over the forks of one
+        context (fork_slots), greedy evaluation slots beside exploring ones.  `setting`: a dict of sample_from_logits'
+        keywords (completed with its defaults, checked against the slot's own head width), "greedy", or None (back to the
+        slot's domain / the agent's setting); one for all `slots`, or a sequence with one entry per slot.  Seed, slot_base and
+        the draw count are kept while sampling is armed; the first sampled slot of an agent that took the argmax everywhere
+        arms it (draw count 0)."""
+        slots = [int(b) for b in (slots.tolist() if isinstance(slots, torch.Tensor) else slots)]
+        one = setting is None or isinstance(setting, (dict, str))
+        settings = [setting] * len(slots) if one else list(setting)
+        if len(settings) != len(slots):
+            raise ValueError(f"set_slot_sampling: {len(slots)} slots and {len(settings)} settings")
+        new = dict(self._slot_sampling)
+        for b, s in zip(slots, settings):
+            if not 0 <= b < self.n_envs:
+                raise IndexError(f"set_slot_sampling: slot {b} outside 0 .. {self.n_envs - 1}")
+            if s is None:
+                new.pop(b, None)
+            elif isinstance(s, str):
+                if s != "greedy":
+                    raise ValueError(f"set_slot_sampling: expected a dict, \"greedy\" or None, got {s!r}")
+                new[b] = "greedy"
+            else:
+                new[b] = resolve_sample_kwargs(s, self._head_width(b))
+        was_armed = self._sampling_armed()
+        self._slot_sampling = new
+        if self.engine is None:
+            return
+        cols = self.slot_sample_settings()
+        if not was_armed or not self._sampling_armed():
+            if was_armed:
+                self.engine.set_sampling(None)
+            self._arm_sampling()
+        elif cols is None:
+            self.engine.set_sampling_slots(None)
+        else:
+            self.engine.set_sampling_slots(temperature=cols["temperature"], top_k=cols["top_k"], top_p=cols["top_p"],
+                                           greedy=cols["greedy"])
+
+    def _sampling_armed(self) -> bool:
+        if self.a_sample_kwargs is not None:
+            return True
+        cols = self.slot_sample_settings()
+        return cols is not None and not bool(cols["greedy"].all())
 
     @property
     def trajectory_mode(self) -> dict:
@@ -168,6 +253,24 @@ class RecurrentAgent:
         mode = {"compat_mamba_repeat": self.compat_mamba_repeat, "compat_stale_state": self.compat_stale_state}
         if getattr(self, "a_sample_kwargs", None) is not None:   # (argmax actions: the record stays as it always was)
             mode["a_sample_kwargs"] = dict(self.a_sample_kwargs, seed=self.sample_seed, slot_base=self.sample_slot_base)
+        cols = self.slot_sample_settings() if hasattr(self, "_slot_sampling") else None
+        if cols is not None:
+            # per distinct setting, the slot ranges that hold it: a domain is one entry, a ladder one entry per rung
+            groups = {}
+            for b in range(self.n_envs):
+                key = ("greedy",) if bool(cols["greedy"][b]) else (float(cols["temperature"][b]), int(cols["top_k"][b]),
+                                                                   float(cols["top_p"][b]))
+                runs = groups.setdefault(key, [])
+                if runs and runs[-1][1] == b:
+                    runs[-1][1] = b + 1
+                else:
+                    runs.append([b, b + 1])
+            mode["a_sample_slots"] = [
+                {"slots": [tuple(r) for r in runs],
+                 "setting": "greedy" if key == ("greedy",) else {"temperature": key[0], "top_k": key[1], "top_p": key[2]}}
+                for key, runs in groups.items()]
+            if "a_sample_kwargs" not in mode and self._sampling_armed():
+                mode["a_sample_kwargs"] = {"seed": self.sample_seed, "slot_base": self.sample_slot_base}
         return mode
 
     # ---- cache handle: `model.past_key_values = None` resets, reading exports the reference layout ----
@@ -215,7 +318,7 @@ class RecurrentAgent:
 
     def reinit_cuda_kernels(self, replace_cell: bool = False):
         """Worker-side counterpart of make_pickleable: build a fresh engine (recurrent state starts empty; sampling is
-        armed again with the same settings and its draw count restarts at 0)."""
+        armed again with the same settings, the per-slot ones included, and its draw count restarts at 0)."""
         if self.engine is None:
             self.engine = Engine(self.spec, self._state_dict, self.n_envs, self.device)
             if self._graph:
@@ -351,10 +454,15 @@ class RecurrentAgent:
     @torch.no_grad()
     def action_log_prob(self, over: str = "selectable") -> torch.Tensor:
         """float32 [n_envs, act_dim]: the log-probability of the tokens the last predict_batch / predict returned, under that
-        call's logits (Engine.last_logp) -- importance weights, or the score that ranks the forks of fork_slots.  With
-        a_sample_kwargs the armed temperature multiplies the logits; top_k and top_p are NOT applied (the probability under the
-        filtered distribution is out of scope): with filtering armed this is the log-probability under the unfiltered softmax.
+        call's logits (Engine.last_logp) -- the score that ranks the forks of fork_slots, or importance weights.
+        over="sampled": under the distribution each token was DRAWN from -- the slot's own temperature, top_k and top_p
+        applied (per-slot settings included; a greedy slot's token scores 0).  These are the importance weights of a sampling
+        agent: with the reference's default top_p = 0.5 half of every row is outside the support.  Needs sampling armed.
+        over="selectable" / "vocab": under the unfiltered softmax -- the agent-level temperature multiplies the logits, top_k,
+        top_p and per-slot settings are NOT applied.
         Columns a slot does not use hold 0."""
+        if over == "sampled":
+            return self.engine.last_logp(self.engine._tokens, over="sampled")
         t = 1.0 if self.a_sample_kwargs is None else float(self.a_sample_kwargs["temperature"])
         return self.engine.last_logp(self.engine._tokens, over=over, temperature=t)
 

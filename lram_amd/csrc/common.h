@@ -247,14 +247,31 @@ struct SampleArgs {
   uint64_t slot0 = 0;        // global index of logits row 0's env slot (counter word 0)
   const uint64_t* draw = nullptr;  // device: action-producing calls since sampling was armed (counter words 2, 3)
 };
+// Per-slot settings (lram_set_sampling_slots): one entry per env slot, read by the wave in place of SampleArgs' scalars.
+struct SampleSlot {
+  double temperature = 1.0;
+  double top_p = 0.0;
+  int32_t top_k = 0;
+  int32_t mode = 1;  // 0: greedy (the argmax rule), 1: sample
+};
+// slots: nullable device table, entry 0 = the launch's first env slot; null: the launch is what it was before the table
 void launch_action_sample(const float* logits, float* actions, int32_t* tokens, int B, int act_dim, int n_vocab,
                           int n_discrete, int action_channels, float tok_min, float tok_max, int discrete, int col_begin,
                           int col_end, const SampleArgs& sp, hipStream_t stream, const uint8_t* slot_flags = nullptr,
-                          const uint8_t* slot_act = nullptr);
+                          const uint8_t* slot_act = nullptr, const SampleSlot* slots = nullptr);
+// logp[B, act_dim] of tokens[B, act_dim] under the distribution launch_action_sample draws from (filters applied; sp.draw unused)
+void launch_action_logp(const float* logits, const int32_t* tokens, float* logp, int B, int act_dim, int n_vocab,
+                        int n_discrete, int discrete, const SampleArgs& sp, hipStream_t stream,
+                        const uint8_t* slot_flags = nullptr, const uint8_t* slot_act = nullptr,
+                        const SampleSlot* slots = nullptr);
 void launch_sample_advance(uint64_t* draw, hipStream_t stream);  // ++*draw, one thread
 // rows of n logits at logits + r * ld (ld = 0: every row is row 0), one caller uniform per row -> tokens[rows]
 void launch_sample_tokens(const float* logits, int64_t rows, int n, int64_t ld, double temperature, int top_k, double top_p,
                           const double* uniform, int32_t* tokens, hipStream_t stream);
+// the same with per-row settings (device arrays [rows]); uniform + tokens_out: draw, tokens_in + logp_out: score (each pair nullable)
+void launch_sample_rows(const float* logits, int64_t rows, int n, int64_t ld, const uint8_t* mode, const double* temperature,
+                        const int32_t* top_k, const double* top_p, const double* uniform, const int32_t* tokens_in,
+                        int32_t* tokens_out, float* logp_out, hipStream_t stream);
 // out[s * act_dim + j] = the uniform of env slot slot_base + s, action dim j, draw `draw`
 void launch_sample_uniforms(uint64_t seed, uint64_t slot_base, int64_t n_slots, int act_dim, uint64_t draw, double* out,
                             hipStream_t stream);

@@ -260,6 +260,29 @@ struct lram_engine {
   bool sampling = false;
   SampleArgs sample;             // .slot0 holds slot_base; a slice adds its first env slot
   uint64_t* sample_draw = nullptr;
+  // per-slot settings (lram_set_sampling_slots): host copy + device table [B], used in place of sample's temperature / top_k /
+  // top_p while set.  They stay with the slot INDEX, as the Philox stream does.  The maxima below are what the per-call top_k
+  // check reads (refreshed when this table or the slot table changes): the largest top_k of a sampling slot, and of one the
+  // slot table marks discrete, each with the slot that holds it.
+  std::vector<SampleSlot> sample_slots;
+  SampleSlot* sample_slots_dev = nullptr;
+  int sslot_k_max = 0, sslot_k_at = -1, sslot_kd_max = 0, sslot_kd_at = -1;
+  void sample_slot_maxima() {
+    sslot_k_max = sslot_kd_max = 0, sslot_k_at = sslot_kd_at = -1;
+    for (size_t b = 0; b < sample_slots.size(); ++b) {
+      const SampleSlot& t = sample_slots[b];
+      if (t.mode == 0) continue;
+      if (t.top_k > sslot_k_max) sslot_k_max = t.top_k, sslot_k_at = (int)b;
+      if (slot_table && b < slot_flags.size() && (slot_flags[b] & 1) && t.top_k > sslot_kd_max)
+        sslot_kd_max = t.top_k, sslot_kd_at = (int)b;
+    }
+  }
+  void drop_sample_slots() {
+    if (sample_slots_dev) (void)hipFree(sample_slots_dev);
+    sample_slots_dev = nullptr;
+    sample_slots.clear();
+    sample_slot_maxima();
+  }
   static constexpr int cell_unroll = 16;  // C rows in flight per thread of the materialised cell kernel
   std::vector<hipStream_t> micro_streams;
   hipStream_t hbm_stream = nullptr;
@@ -293,6 +316,7 @@ struct lram_engine {
     drop_splits();
     release_state();
     if (sample_draw) (void)hipFree(sample_draw);
+    drop_sample_slots();
     drop_slot_table();
   }
   void drop_slot_table() {
@@ -301,6 +325,7 @@ struct lram_engine {
     slot_dev = nullptr, slot_img_list = nullptr;
     slot_flags.clear(), slot_act.clear(), slot_img_prefix.clear();
     slot_n_image = 0, slot_has_discrete = false, slot_table = false;
+    sample_slot_maxima();
   }
   void drop_splits() {
     for (auto& kv : split) (void)hipFree(kv.second.p);

@@ -550,6 +550,7 @@ void state_alloc(lram_engine* e, int B) {
   e->drop_graph();
   e->release_state();
   e->drop_slot_table();   // the table describes the slots of one allocation
+  e->drop_sample_slots(); // and so do the per-slot sampling settings
   const lram_config& c = e->cfg;
   const size_t D = c.d_model;
   e->st.resize(c.n_blocks);
@@ -739,6 +740,7 @@ int32_t lram_set_sampling(lram_engine* e, int32_t enable, double temperature, in
     LRAM_HIP_CHECK(hipSetDevice(e->device));
     LRAM_HIP_CHECK(hipDeviceSynchronize());  // steps in flight (non-blocking streams included) keep the mode they were launched in
     e->drop_graph();                         // the head kernel and its arguments are part of a captured step
+    e->drop_sample_slots();                  // arming and disarming both start without per-slot settings
     if (enable) {
       if (!e->sample_draw) LRAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->sample_draw), sizeof(uint64_t)));
       LRAM_HIP_CHECK(hipMemset(e->sample_draw, 0, sizeof(uint64_t)));
@@ -767,6 +769,62 @@ int32_t lram_get_sampling(lram_engine* e, int32_t* enable, double* temperature, 
         LRAM_HIP_CHECK(hipDeviceSynchronize());
         LRAM_HIP_CHECK(hipMemcpy(draws, e->sample_draw, sizeof(uint64_t), hipMemcpyDeviceToHost));
       }
+    }
+  });
+}
+
+int32_t lram_set_sampling_slots(lram_engine* e, const uint8_t* mode, const double* temperature, const int32_t* top_k,
+                                const double* top_p) {
+  return guarded([&] {
+    LRAM_REQUIRE(e != nullptr, "lram_set_sampling_slots: null engine");
+    LRAM_REQUIRE(e->B > 0, "lram_set_sampling_slots: state not allocated (call lram_state_alloc)");
+    const bool clear = !mode && !temperature && !top_k && !top_p;
+    LRAM_REQUIRE(clear || (mode && temperature && top_k && top_p),
+                 "lram_set_sampling_slots: the four arrays go together (all NULL clears the table)");
+    LRAM_REQUIRE(clear || e->sampling, "lram_set_sampling_slots: sampling is not armed (call lram_set_sampling first)");
+    const int B = e->B;
+    std::vector<SampleSlot> tab;
+    if (!clear) {  // validate before anything changes: a refused table leaves the one in effect as it is
+      tab.resize(B);
+      for (int b = 0; b < B; ++b) {
+        const std::string at = " (slot " + std::to_string(b) + ")";
+        LRAM_REQUIRE(mode[b] <= 1, "lram_set_sampling_slots: mode must be 0 (greedy) or 1 (sample)" + at);
+        LRAM_REQUIRE(temperature[b] > 0.0 && temperature[b] < (double)INFINITY,
+                     "lram_set_sampling_slots: temperature must be finite and > 0 (it multiplies the logits)" + at);
+        LRAM_REQUIRE(top_p[b] >= 0.0 && top_p[b] <= 1.0, "lram_set_sampling_slots: top_p must be in [0, 1]" + at);
+        LRAM_REQUIRE(top_k[b] >= 0, "lram_set_sampling_slots: top_k must be >= 0" + at);
+        LRAM_REQUIRE(top_k[b] <= e->cfg.n_vocab, "lram_set_sampling_slots: top_k exceeds the head's n_vocab logits" + at);
+        tab[b].temperature = temperature[b], tab[b].top_p = top_p[b], tab[b].top_k = top_k[b], tab[b].mode = mode[b];
+      }
+    }
+    LRAM_HIP_CHECK(hipSetDevice(e->device));
+    LRAM_HIP_CHECK(hipDeviceSynchronize());  // steps in flight read the table they were launched with
+    e->drop_graph();                         // the head kernel and its table pointer are part of a captured step
+    if (clear) {
+      e->drop_sample_slots();
+      return;
+    }
+    if (!e->sample_slots_dev)
+      LRAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->sample_slots_dev), sizeof(SampleSlot) * (size_t)B));
+    LRAM_HIP_CHECK(hipMemcpy(e->sample_slots_dev, tab.data(), sizeof(SampleSlot) * (size_t)B, hipMemcpyHostToDevice));
+    LRAM_HIP_CHECK(hipDeviceSynchronize());
+    e->sample_slots.swap(tab);
+    e->sample_slot_maxima();
+  });
+}
+
+int32_t lram_get_sampling_slots(lram_engine* e, uint8_t* mode, double* temperature, int32_t* top_k, double* top_p, int32_t* set) {
+  return guarded([&] {
+    LRAM_REQUIRE(e != nullptr, "lram_get_sampling_slots: null engine");
+    const bool on = !e->sample_slots.empty();
+    if (set) *set = on ? 1 : 0;
+    if (!on) return;
+    for (size_t b = 0; b < e->sample_slots.size(); ++b) {
+      const SampleSlot& t = e->sample_slots[b];
+      if (mode) mode[b] = (uint8_t)t.mode;
+      if (temperature) temperature[b] = t.temperature;
+      if (top_k) top_k[b] = t.top_k;
+      if (top_p) top_p[b] = t.top_p;
     }
   });
 }

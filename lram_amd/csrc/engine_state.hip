@@ -132,6 +132,7 @@ int32_t lram_set_slot_table(lram_engine* e, const uint8_t* host_flags, const uin
     if (n_img > 0) LRAM_HIP_CHECK(hipMemcpy(e->slot_img_list, list.data(), sizeof(int32_t) * n_img, hipMemcpyHostToDevice));
     LRAM_HIP_CHECK(hipDeviceSynchronize());
     e->slot_n_image = n_img, e->slot_has_discrete = has_discrete, e->slot_table = true;
+    e->sample_slot_maxima();   // which sampling slots are discrete has changed
   });
 }
 

@@ -252,7 +252,7 @@ void action_head(lram_engine* e, const Pass& pass, const std::vector<Slice>& sl,
       sp.slot0 += b0, sp.draw = e->sample_draw;
       launch_action_sample(e->LOGITS.p + b0 * nlog, actions + b0 * c.act_dim, tokens ? tokens + b0 * c.act_dim : nullptr,
                            x.nb, c.act_dim, c.n_vocab, c.n_discrete, c.action_channels, c.tok_min, c.tok_max, discrete,
-                           col_begin, col_end, sp, x.s, sf, sa);
+                           col_begin, col_end, sp, x.s, sf, sa, e->sample_slots_dev ? e->sample_slots_dev + b0 : nullptr);
       continue;
     }
     launch_action_argmax(e->LOGITS.p + b0 * nlog, actions + b0 * c.act_dim,
@@ -371,15 +371,27 @@ void sample_draw_advance(lram_engine* e, hipStream_t s) {
   if (e->sampling) launch_sample_advance(e->sample_draw, s);
 }
 
+// Per-slot sampling settings: every sampling slot's top_k must fit the head the call gives that slot -- n_discrete logits
+// on a discrete head, n_vocab otherwise (checked when the table was set).  Read from the host-side maxima: no per-step cost.
+void check_sample_slots(const lram_engine* e, int discrete, const std::string& w) {
+  if (!e->sampling || e->sample_slots.empty() || discrete == 0) return;
+  const bool per_slot = discrete == LRAM_HEAD_PER_SLOT;
+  const int k = per_slot ? e->sslot_kd_max : e->sslot_k_max, at = per_slot ? e->sslot_kd_at : e->sslot_k_at;
+  LRAM_REQUIRE(k <= e->cfg.n_discrete, w + ": sampling top_k " + std::to_string(k) + " of slot " + std::to_string(at) +
+                                           " exceeds the n_discrete = " + std::to_string(e->cfg.n_discrete) +
+                                           " logits of the discrete head that slot gets");
+}
+
 // discrete = LRAM_HEAD_PER_SLOT: what the call needs, checked before anything is launched (the recurrent state is untouched
 // by a refused call).
 void check_head_mode(const lram_engine* e, int discrete, const char* who) {
+  check_sample_slots(e, discrete, who);
   if (discrete != LRAM_HEAD_PER_SLOT) return;
   const std::string w(who);
   LRAM_REQUIRE(e->slot_table, w + ": LRAM_HEAD_PER_SLOT needs a slot table (lram_set_slot_table)");
   LRAM_REQUIRE(e->compat_repeat <= 1, w + ": LRAM_HEAD_PER_SLOT cannot be combined with the Mamba repeated-forward mode "
                                           "(mamba_repeat > 1 advances the state once per action dim of the env, which differs per slot)");
-  LRAM_REQUIRE(!(e->sampling && e->slot_has_discrete && e->sample.top_k > e->cfg.n_discrete),
+  LRAM_REQUIRE(!(e->sampling && e->sample_slots.empty() && e->slot_has_discrete && e->sample.top_k > e->cfg.n_discrete),
                w + ": sampling top_k exceeds n_discrete and the slot table holds a discrete slot");
 }
 
@@ -575,6 +587,49 @@ int32_t lram_score_last(lram_engine* e, const int32_t* dev_tokens, int32_t over,
     ScoreArgs a = score_args(e, sink, e->last_head);
     a.logits = e->LOGITS.p, a.ld = (int64_t)e->cfg.act_dim * e->cfg.n_vocab, a.rows = e->B;
     launch_action_score(a, static_cast<hipStream_t>(stream));
+  });
+}
+
+int32_t lram_score_last_sampled(lram_engine* e, const int32_t* dev_tokens, float* dev_logp, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(e != nullptr, "lram_score_last_sampled: null engine");
+    LRAM_REQUIRE(e->B > 0, "lram_score_last_sampled: state not allocated (call lram_state_alloc)");
+    LRAM_HIP_CHECK(hipSetDevice(e->device));
+    prof_tick(e);
+    LRAM_REQUIRE(dev_tokens && dev_logp, "lram_score_last_sampled: null device pointer");
+    LRAM_REQUIRE(e->last_head >= 0,
+                 "lram_score_last_sampled: no action-producing call since lram_state_alloc: there are no logits to score");
+    LRAM_REQUIRE(e->sampling, "lram_score_last_sampled: sampling is not armed (lram_set_sampling): there is no drawn distribution");
+    const int head = e->last_head;
+    LRAM_REQUIRE(head != LRAM_HEAD_PER_SLOT || e->slot_table,
+                 "lram_score_last_sampled: the last call was per-slot and the slot table has been cleared since");
+    LRAM_REQUIRE(head != 1 || e->cfg.n_discrete >= 1, "lram_score_last_sampled: a discrete head needs n_discrete >= 1");
+    check_sample_slots(e, head, "lram_score_last_sampled");
+    LRAM_REQUIRE(!(head == LRAM_HEAD_PER_SLOT && e->sample_slots.empty() && e->slot_has_discrete &&
+                   e->sample.top_k > e->cfg.n_discrete),
+                 "lram_score_last_sampled: sampling top_k exceeds n_discrete and the slot table holds a discrete slot");
+    const bool per_slot = head == LRAM_HEAD_PER_SLOT;
+    const lram_config& c = e->cfg;
+    // (deterministic: no uniform is read, the draw counter is neither read nor advanced)
+    launch_action_logp(e->LOGITS.p, dev_tokens, dev_logp, e->B, c.act_dim, c.n_vocab, c.n_discrete, head, e->sample,
+                       static_cast<hipStream_t>(stream), per_slot ? e->slot_dev : nullptr, per_slot ? e->slot_dev + e->B : nullptr,
+                       e->sample_slots_dev);
+  });
+}
+
+int32_t lram_sample_rows(const float* dev_logits, int64_t rows, int32_t n, int64_t ld, const uint8_t* dev_mode,
+                         const double* dev_temperature, const int32_t* dev_top_k, const double* dev_top_p,
+                         const double* dev_uniform, const int32_t* dev_tokens_in, int32_t* dev_tokens_out, float* dev_logp_out,
+                         void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(dev_logits && dev_mode && dev_temperature && dev_top_k && dev_top_p, "lram_sample_rows: null device pointer");
+    LRAM_REQUIRE((dev_uniform == nullptr) == (dev_tokens_out == nullptr), "lram_sample_rows: dev_uniform and dev_tokens_out go together");
+    LRAM_REQUIRE((dev_tokens_in == nullptr) == (dev_logp_out == nullptr), "lram_sample_rows: dev_tokens_in and dev_logp_out go together");
+    LRAM_REQUIRE(dev_tokens_out || dev_logp_out, "lram_sample_rows: neither a draw (dev_uniform, dev_tokens_out) nor a score "
+                                                 "(dev_tokens_in, dev_logp_out) is asked for");
+    LRAM_REQUIRE(ld == 0 || ld >= n, "lram_sample_rows: ld must be 0 (one shared row) or >= n");
+    launch_sample_rows(dev_logits, rows, n, ld, dev_mode, dev_temperature, dev_top_k, dev_top_p, dev_uniform, dev_tokens_in,
+                       dev_tokens_out, dev_logp_out, static_cast<hipStream_t>(stream));
   });
 }
 

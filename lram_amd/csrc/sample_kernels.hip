@@ -14,6 +14,10 @@
 // the reference raises there.  Arithmetic: fp64 from the quantile on (a row is 5 values per lane; the selection is a
 // bitwise binary search on the order-preserving integer image of the floats, 32 rounds of PER compares + ballot per
 // order statistic, linear in n).
+// Per-slot settings (lram_set_sampling_slots): action_sample_slots_kernel reads {temperature, top_p, top_k, mode} of the
+// wave's env slot from a device table instead of the launch's scalars; mode 0 = greedy, the argmax rule at once.
+// logp_row (action_logp_kernel, sample_rows_kernel): the log-probability of a GIVEN token under the same support and
+// weights -- t * (x_tok - max) - log(sum over the support of exp(t * (x - max))), fp64, one fp32 rounding at the store.
 #include "common.h"
 #include "device_math.h"
 
@@ -42,6 +46,15 @@ __device__ __forceinline__ double philox_uniform(uint64_t seed, uint64_t slot, u
   return (double)c0 * 2.3283064365386963e-10;  // 2^-32
 }
 
+// A value that is the same on every lane of the wave, moved to scalar registers (the compiler cannot see that a table
+// entry indexed by the wave's row is wave-uniform).
+__device__ __forceinline__ int uniform_i32(int x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ double uniform_f64(double x) {
+  const uint64_t b = (uint64_t)__double_as_longlong(x);
+  const uint32_t lo = (uint32_t)uniform_i32((int)(uint32_t)b), hi = (uint32_t)uniform_i32((int)(uint32_t)(b >> 32));
+  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
 template <int PER>
 __device__ __forceinline__ int wave_count_lt(const uint32_t (&key)[PER], uint32_t x) {
   int cnt = 0;
@@ -62,14 +75,21 @@ __device__ __forceinline__ uint32_t wave_select(const uint32_t (&key)[PER], int 
 }
 
 // One wave, one row, staged in LDS (`row`, n floats); lane l holds the PER consecutive entries from l * PER on, so that
-// vocabulary order is (lane, j) order.  Returns the token (wave-uniform).
-template <int PER>
-__device__ __forceinline__ int sample_row(const float* row, int n, double temperature, int top_k, double top_p, double u,
-                                          int lane) {
+// vocabulary order is (lane, j) order.  The row code comes in parts that the draw (sample_row) and the log-probability of a
+// given token (logp_row) share: the support (steps 1 and 2), its weights (step 3), the argmax rule.
+//
+// with_row_support: v = the lane's entries, vmax = the row maximum, bit j of keep = entry j of this lane is in the support;
+// body(v, vmax, keep) runs on them and returns true if nothing is left for it.  Returns true (wave-uniform) where the row
+// takes the argmax rule instead: greedy (a per-slot setting), a NaN in the row, a maximum of +-inf, or nothing left.
+// (The body runs INSIDE the branch that computed the support: ballots and shuffles pin the control flow, so a second branch
+// on the same condition would not be merged with the first.)
+template <int PER, class Body>
+__device__ __forceinline__ bool with_row_support(const float* row, int n, int top_k, double top_p, int lane, bool greedy,
+                                                 Body&& body) {
   float v[PER];
+  float vmax = -INFINITY;
   uint32_t key[PER];
   bool nan_here = false;
-  float vmax = -INFINITY;
 #pragma unroll
   for (int j = 0; j < PER; ++j) {
     const int i = lane * PER + j;
@@ -79,123 +99,172 @@ __device__ __forceinline__ int sample_row(const float* row, int n, double temper
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, off, 64));
-  bool plain = __any(nan_here) || vmax == INFINITY || vmax == -INFINITY;
-  int token = 0x7fffffff;
+  bool plain = greedy || __any(nan_here) || vmax == INFINITY || vmax == -INFINITY;
   if (!plain) {
     uint32_t keep = 0;  // bit j: entry j of this lane is in the support
 #pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const bool valid = lane * PER + j < n;
-      key[j] = valid ? order_key(v[j]) : 0xffffffffu;  // padding sorts last
-      keep |= (valid ? 1u : 0u) << j;
+  for (int j = 0; j < PER; ++j) {
+    const bool valid = lane * PER + j < n;
+    key[j] = valid ? order_key(v[j]) : 0xffffffffu;  // padding sorts last
+    keep |= (valid ? 1u : 0u) << j;
+  }
+  if (top_p > 0.0) {
+    const double rank = top_p * (double)(n - 1);
+    const int lo = (int)floor(rank), hi = (int)ceil(rank);
+    const double wgt = rank - (double)lo;
+    const uint32_t klo = wave_select<PER>(key, lo);
+    uint32_t khi = klo;
+    if (hi > lo && wave_count_lt<PER>(key, klo + 1u) <= hi) {  // order statistic `hi` is the next larger value
+      uint32_t mn = 0xffffffffu;
+#pragma unroll
+      for (int j = 0; j < PER; ++j) mn = key[j] > klo ? min(mn, key[j]) : mn;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, off, 64));
+      khi = mn;
     }
-    if (top_p > 0.0) {
-      const double rank = top_p * (double)(n - 1);
-      const int lo = (int)floor(rank), hi = (int)ceil(rank);
-      const double wgt = rank - (double)lo;
-      const uint32_t klo = wave_select<PER>(key, lo);
-      uint32_t khi = klo;
-      if (hi > lo && wave_count_lt<PER>(key, klo + 1u) <= hi) {  // order statistic `hi` is the next larger value
-        uint32_t mn = 0xffffffffu;
+    const double a = (double)key_value(klo), b = (double)key_value(khi);
+    const double q = wgt < 0.5 ? a + wgt * (b - a) : b - (b - a) * (1.0 - wgt);  // at::lerp
+    if (q != (double)vmax) {
 #pragma unroll
-        for (int j = 0; j < PER; ++j) mn = key[j] > klo ? min(mn, key[j]) : mn;
+      for (int j = 0; j < PER; ++j)
+        if (!((double)v[j] > q)) keep &= ~(1u << j);
+    }
+  }
+  if (top_k > 0) {
+    int kept = 0;
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, off, 64));
-        khi = mn;
+    for (int j = 0; j < PER; ++j) kept += __popcll(__ballot((keep >> j) & 1u));
+    if (kept > top_k) {
+#pragma unroll
+      for (int j = 0; j < PER; ++j) key[j] = ((keep >> j) & 1u) ? key[j] : 0u;  // dropped entries and padding sort first
+      const uint32_t kth = wave_select<PER>(key, 64 * PER - top_k);           // the k-th largest: a kept key, as kept > k
+      const int above = 64 * PER - wave_count_lt<PER>(key, kth + 1u);           // (kth < 0xffffffff: no NaN in the row)
+      const int room = top_k - above;                                           // ties at the k-th place that stay
+      int ties = 0;
+#pragma unroll
+      for (int j = 0; j < PER; ++j) ties += key[j] == kth ? 1 : 0;
+      int before = ties;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(before, off, 64);
+        if (lane >= off) before += t;
       }
-      const double a = (double)key_value(klo), b = (double)key_value(khi);
-      const double q = wgt < 0.5 ? a + wgt * (b - a) : b - (b - a) * (1.0 - wgt);  // at::lerp
-      if (q != (double)vmax) {
-#pragma unroll
-        for (int j = 0; j < PER; ++j)
-          if (!((double)v[j] > q)) keep &= ~(1u << j);
-      }
-    }
-    if (top_k > 0) {
-      int kept = 0;
-#pragma unroll
-      for (int j = 0; j < PER; ++j) kept += __popcll(__ballot((keep >> j) & 1u));
-      if (kept > top_k) {
-#pragma unroll
-        for (int j = 0; j < PER; ++j) key[j] = ((keep >> j) & 1u) ? key[j] : 0u;  // dropped entries and padding sort first
-        const uint32_t kth = wave_select<PER>(key, 64 * PER - top_k);           // the k-th largest: a kept key, as kept > k
-        const int above = 64 * PER - wave_count_lt<PER>(key, kth + 1u);           // (kth < 0xffffffff: no NaN in the row)
-        const int room = top_k - above;                                           // ties at the k-th place that stay
-        int ties = 0;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) ties += key[j] == kth ? 1 : 0;
-        int before = ties;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const int t = __shfl_up(before, off, 64);
-          if (lane >= off) before += t;
-        }
-        before -= ties;  // ties on lower lanes = at lower indices
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-          if (key[j] == kth) {
-            if (before >= room) keep &= ~(1u << j);
-            ++before;
-          } else if (key[j] < kth) {
-            keep &= ~(1u << j);
-          }
-        }
-      }
-    }
-    double w[PER], loc = 0.0;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      w[j] = ((keep >> j) & 1u) ? exp(temperature * ((double)v[j] - (double)vmax)) : 0.0;
-      loc += w[j];
-    }
-    double inc = loc;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const double t = __shfl_up(inc, off, 64);
-      if (lane >= off) inc += t;
-    }
-    const double total = __shfl(inc, 63, 64);
-    if (total > 0.0 && total < (double)INFINITY) {
-      const double target = u * total;
-      double run = __shfl_up(inc, 1, 64);
-      if (lane == 0) run = 0.0;
-      int first = 0x7fffffff, last = -1;
+      before -= ties;  // ties on lower lanes = at lower indices
 #pragma unroll
       for (int j = 0; j < PER; ++j) {
-        run += w[j];
-        if (w[j] > 0.0) {
-          last = lane * PER + j;
-          if (first == 0x7fffffff && run > target) first = last;
+        if (key[j] == kth) {
+          if (before >= room) keep &= ~(1u << j);
+          ++before;
+        } else if (key[j] < kth) {
+          keep &= ~(1u << j);
         }
       }
+    }
+  }
+    if (body(v, vmax, keep)) plain = true;
+  }
+  return plain;
+}
+
+// w[j] = exp(temperature * (v[j] - vmax)) on the support, 0 elsewhere.  Returns the lane's sum.
+template <int PER>
+__device__ __forceinline__ double row_weights(const float (&v)[PER], float vmax, uint32_t keep, double temperature,
+                                              double (&w)[PER]) {
+  double loc = 0.0;
 #pragma unroll
-      for (int off = 32; off > 0; off >>= 1) first = min(first, __shfl_xor(first, off, 64));
-      if (first == 0x7fffffff) {  // rounding at the top end of the CDF: the last token of the support
+  for (int j = 0; j < PER; ++j) {
+    w[j] = ((keep >> j) & 1u) ? exp(temperature * ((double)v[j] - (double)vmax)) : 0.0;
+    loc += w[j];
+  }
+  return loc;
+}
+// The inclusive scan of the lanes' sums, in lane (= vocabulary) order; lane 63 holds the row's total.  Outside (0, inf)
+// nothing is left (a quantile that is NaN) and the row takes the argmax rule.
+__device__ __forceinline__ double wave_scan_f64(double inc, int lane) {
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) last = max(last, __shfl_xor(last, off, 64));
-        first = last;
+  for (int off = 1; off < 64; off <<= 1) {
+    const double t = __shfl_up(inc, off, 64);
+    if (lane >= off) inc += t;
+  }
+  return inc;
+}
+
+// The default path's rule (argmax_beats), as action_argmax_kernel applies it to the same row.
+__device__ __forceinline__ int row_argmax(const float* row, int n, int lane) {
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int i = lane; i < n; i += 64) {
+    const float x = row[i];
+    if (argmax_beats(x, i, best, bi)) best = x, bi = i;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(best, off, 64);
+    const int oi = __shfl_xor(bi, off, 64);
+    if (argmax_beats(ov, oi, best, bi)) best = ov, bi = oi;
+  }
+  return bi;
+}
+
+// The draw.  Returns the token (wave-uniform); greedy (a per-slot setting, wave-uniform): the argmax rule at once.
+template <int PER>
+__device__ __forceinline__ int sample_row(const float* row, int n, double temperature, int top_k, double top_p, double u,
+                                          int lane, bool greedy = false) {
+  int token = 0x7fffffff;
+  const bool plain = with_row_support<PER>(row, n, top_k, top_p, lane, greedy, [&](const float (&v)[PER], float vmax, uint32_t keep) {
+    double w[PER];
+    const double inc = wave_scan_f64(row_weights<PER>(v, vmax, keep, temperature, w), lane);
+    const double total = __shfl(inc, 63, 64);
+    if (!(total > 0.0 && total < (double)INFINITY)) return true;  // nothing left (a quantile that is NaN): the argmax rule
+    const double target = u * total;
+    double run = __shfl_up(inc, 1, 64);
+    if (lane == 0) run = 0.0;
+    int first = 0x7fffffff, last = -1;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      run += w[j];
+      if (w[j] > 0.0) {
+        last = lane * PER + j;
+        if (first == 0x7fffffff && run > target) first = last;
       }
-      token = first;
-    } else {
-      plain = true;  // nothing left (a quantile that is NaN): the argmax rule
-    }
-  }
-  if (plain) {
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = lane; i < n; i += 64) {
-      const float x = row[i];
-      if (argmax_beats(x, i, best, bi)) best = x, bi = i;
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(best, off, 64);
-      const int oi = __shfl_xor(bi, off, 64);
-      if (argmax_beats(ov, oi, best, bi)) best = ov, bi = oi;
+    for (int off = 32; off > 0; off >>= 1) first = min(first, __shfl_xor(first, off, 64));
+    if (first == 0x7fffffff) {  // rounding at the top end of the CDF: the last token of the support
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) last = max(last, __shfl_xor(last, off, 64));
+      first = last;
     }
-    token = bi;
-  }
+    token = first;
+    return false;
+  });
+  if (plain) token = row_argmax(row, n, lane);
   return token;
+}
+
+// log of the probability with which sample_row returns `tok` (wave-uniform) from this row under these settings:
+// t * (x_tok - max) - log(sum over the support of exp(t * (x - max))), fp64 throughout; the caller rounds once to fp32.
+// Outside 0 .. n - 1 or outside the support: -inf.  A row on the argmax rule: 0 at the argmax token, -inf elsewhere.
+template <int PER>
+__device__ __forceinline__ double logp_row(const float* row, int n, double temperature, int top_k, double top_p, int tok,
+                                           int lane, bool greedy) {
+  double lp = -(double)INFINITY;
+  const bool plain = with_row_support<PER>(row, n, top_k, top_p, lane, greedy, [&](const float (&v)[PER], float vmax, uint32_t keep) {
+    double w[PER], z = -(double)INFINITY;
+    const double loc = row_weights<PER>(v, vmax, keep, temperature, w);
+#pragma unroll
+    for (int j = 0; j < PER; ++j)   // (ahead of the scan: the weights are not kept across it; w = 0: never drawn)
+      if (lane * PER + j == tok && w[j] > 0.0) z = temperature * ((double)v[j] - (double)vmax);
+    const double total = __shfl(wave_scan_f64(loc, lane), 63, 64);   // the draw's own total, bit for bit
+    if (!(total > 0.0 && total < (double)INFINITY)) return true;
+    if (tok >= 0 && tok < n) {
+      z = __shfl(z, tok / PER, 64);  // from the lane that holds the token
+      lp = z - log(total);           // (the support holds the maximum: total >= 1; a support of one entry gives 0 - log(1))
+    }
+    return false;
+  });
+  if (plain) lp = tok == row_argmax(row, n, lane) ? 0.0 : -(double)INFINITY;
+  return lp;
 }
 
 // A wave's row: global -> its LDS strip, coalesced.  Every wave of the workgroup reaches the barrier behind it.
@@ -214,13 +283,14 @@ __device__ __forceinline__ void stage_row(float* strip, const float* src, int n,
 // The sampling counterpart of action_argmax_kernel (misc_kernels.hip), same grid: one wave per (env, action dim), four
 // per workgroup.  sp.draw is read, never written, here: sample_advance_kernel bumps it once per env-step behind every head
 // launch of that step.
-template <int PER>
-__global__ __launch_bounds__(256) void action_sample_kernel(const float* logits, float* actions, int32_t* tokens, int B,
-                                                            int act_dim, int n_vocab, int n_discrete, int action_channels,
-                                                            float tok_min, float tok_max, int discrete, int col_begin,
-                                                            int col_end, SampleArgs sp, const uint8_t* slot_flags,
-                                                            const uint8_t* slot_act) {
-  __shared__ float stage[4][64 * PER];
+// SLOTS: the settings come from the per-slot table (lram_set_sampling_slots; `slots` starts at the launch's first env slot)
+// instead of sp's scalars -- a compile-time split, so that the launch without a table is the code it was before the table.
+template <int PER, bool SLOTS>
+__device__ __forceinline__ void action_sample_body(float (&stage)[4][64 * PER], const float* logits, float* actions,
+                                                   int32_t* tokens, int B, int act_dim, int n_vocab, int n_discrete,
+                                                   int action_channels, float tok_min, float tok_max, int discrete,
+                                                   int col_begin, int col_end, const SampleArgs& sp, const uint8_t* slot_flags,
+                                                   const uint8_t* slot_act, const SampleSlot* slots) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int item = blockIdx.x * 4 + wv;
   const int ndim = (discrete && slot_flags == nullptr) ? 1 : act_dim;
@@ -240,7 +310,13 @@ __global__ __launch_bounds__(256) void action_sample_kernel(const float* logits,
   }
   if (!active) return;
   const double u = philox_uniform(sp.seed, sp.slot0 + (uint64_t)b, (uint32_t)j, *sp.draw);
-  const int tok = sample_row<PER>(stage[wv], n, sp.temperature, sp.top_k, sp.top_p, u, lane);
+  int tok;
+  if constexpr (SLOTS) {  // the env slot's own settings (wave-uniform, like slot_flags[b])
+    const SampleSlot st = slots[b];
+    tok = sample_row<PER>(stage[wv], n, st.temperature, st.top_k, st.top_p, u, lane, st.mode == 0);
+  } else {
+    tok = sample_row<PER>(stage[wv], n, sp.temperature, sp.top_k, sp.top_p, u, lane);
+  }
   if (lane == 0) {
     if (tokens != nullptr) tokens[(int64_t)b * act_dim + j] = tok;
     float out;
@@ -254,6 +330,71 @@ __global__ __launch_bounds__(256) void action_sample_kernel(const float* logits,
     }
     actions[(int64_t)b * act_dim + j] = out;
   }
+}
+
+template <int PER>
+__global__ __launch_bounds__(256) void action_sample_kernel(const float* logits, float* actions, int32_t* tokens, int B,
+                                                            int act_dim, int n_vocab, int n_discrete, int action_channels,
+                                                            float tok_min, float tok_max, int discrete, int col_begin,
+                                                            int col_end, SampleArgs sp, const uint8_t* slot_flags,
+                                                            const uint8_t* slot_act) {
+  __shared__ float stage[4][64 * PER];
+  action_sample_body<PER, false>(stage, logits, actions, tokens, B, act_dim, n_vocab, n_discrete, action_channels, tok_min,
+                                 tok_max, discrete, col_begin, col_end, sp, slot_flags, slot_act, nullptr);
+}
+
+template <int PER>
+__global__ __launch_bounds__(256) void action_sample_slots_kernel(const float* logits, float* actions, int32_t* tokens, int B,
+                                                                  int act_dim, int n_vocab, int n_discrete,
+                                                                  int action_channels, float tok_min, float tok_max,
+                                                                  int discrete, int col_begin, int col_end, SampleArgs sp,
+                                                                  const uint8_t* slot_flags, const uint8_t* slot_act,
+                                                                  const SampleSlot* slots) {
+  __shared__ float stage[4][64 * PER];
+  action_sample_body<PER, true>(stage, logits, actions, tokens, B, act_dim, n_vocab, n_discrete, action_channels, tok_min,
+                                tok_max, discrete, col_begin, col_end, sp, slot_flags, slot_act, slots);
+}
+
+// log-probabilities of given tokens under the distribution the head above draws from: same grid (always act_dim columns per
+// env, as action_score_kernel), same rows, same settings -- sp's scalars, or the per-slot table where `slots` is given.
+// Columns the slot does not use (j >= act_dim[slot]; j >= 1 on a discrete head) and token -1 get the fill value 0.
+template <int PER>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void action_logp_kernel(const float* logits, const int32_t* tokens, float* logp, int B,
+                                                          int act_dim, int n_vocab, int n_discrete, int discrete,
+                                                          SampleArgs sp, const uint8_t* slot_flags, const uint8_t* slot_act,
+                                                          const SampleSlot* slots) {
+  __shared__ float stage[4][64 * PER];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int item = blockIdx.x * 4 + wv;
+  const int b = item / act_dim, j = item - b * act_dim;
+  const bool in_grid = item < B * act_dim;
+  bool fill = false;
+  int tok = -1;
+  if (in_grid) {  // (every condition below is the same for the whole wave)
+    if (slot_flags != nullptr) {
+      discrete = slot_flags[b] & 1;
+      fill = j >= (int)slot_act[b];
+    } else {
+      fill = discrete && j >= 1;
+    }
+    tok = tokens[(int64_t)b * act_dim + j];
+    fill = fill || tok == -1;
+  }
+  const bool active = in_grid && !fill;
+  const int n = discrete ? n_discrete : n_vocab;
+  stage_row<PER>(stage[wv], logits + (int64_t)b * act_dim * n_vocab + (int64_t)j * n_vocab, n, lane, active);
+  if (fill && lane == 0) logp[(int64_t)b * act_dim + j] = 0.f;
+  if (!active) return;
+  double temperature = sp.temperature, top_p = sp.top_p;
+  int top_k = sp.top_k;
+  bool greedy = false;
+  if (slots != nullptr) {
+    const SampleSlot st = slots[b];
+    temperature = st.temperature, top_p = st.top_p, top_k = st.top_k, greedy = st.mode == 0;
+  }
+  const double lp = logp_row<PER>(stage[wv], n, uniform_f64(temperature), uniform_i32(top_k), uniform_f64(top_p),
+                                 uniform_i32(tok), lane, uniform_i32(greedy) != 0);
+  if (lane == 0) logp[(int64_t)b * act_dim + j] = (float)lp;
 }
 
 __global__ void sample_advance_kernel(uint64_t* draw) {
@@ -275,6 +416,33 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* logits,
   if (lane == 0) tokens[r] = tok;
 }
 
+// Test / evidence entry with per-row settings (device arrays of length rows): draws (uniform -> tokens_out) and / or
+// log-probabilities of given tokens (tokens_in -> logp_out; token -1: the fill value 0) through the row code of the head.
+template <int PER>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void sample_rows_kernel(const float* logits, int64_t rows, int n, int64_t ld,
+                                                          const uint8_t* mode, const double* temperature, const int32_t* top_k,
+                                                          const double* top_p, const double* uniform, const int32_t* tokens_in,
+                                                          int32_t* tokens_out, float* logp_out) {
+  __shared__ float stage[4][64 * PER];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t r = (int64_t)blockIdx.x * 4 + wv;
+  const bool active = r < rows;
+  stage_row<PER>(stage[wv], logits + (active ? r : 0) * ld, n, lane, active);
+  if (!active) return;
+  const double t = temperature[r], p = top_p[r];
+  const int k = top_k[r];
+  const bool greedy = mode[r] == 0;
+  if (tokens_out != nullptr) {
+    const int tok = sample_row<PER>(stage[wv], n, t, k, p, uniform[r], lane, greedy);
+    if (lane == 0) tokens_out[r] = tok;
+  }
+  if (logp_out != nullptr) {
+    const int tok = tokens_in[r];
+    const double lp = tok == -1 ? 0.0 : logp_row<PER>(stage[wv], n, t, k, p, tok, lane, greedy);
+    if (lane == 0) logp_out[r] = (float)lp;
+  }
+}
+
 __global__ __launch_bounds__(256) void sample_uniforms_kernel(uint64_t seed, uint64_t slot_base, int64_t n_slots,
                                                               int act_dim, uint64_t draw, double* out) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -288,21 +456,30 @@ __global__ __launch_bounds__(256) void sample_uniforms_kernel(uint64_t seed, uin
 void launch_action_sample(const float* logits, float* actions, int32_t* tokens, int B, int act_dim, int n_vocab,
                           int n_discrete, int action_channels, float tok_min, float tok_max, int discrete, int col_begin,
                           int col_end, const SampleArgs& sp, hipStream_t stream, const uint8_t* slot_flags,
-                          const uint8_t* slot_act) {
+                          const uint8_t* slot_act, const SampleSlot* slots) {
   LRAM_REQUIRE((slot_flags == nullptr) == (slot_act == nullptr), "action sampling: the slot table's two arrays go together");
   const bool per_slot = slot_flags != nullptr;
   // with a slot table the rows of one launch differ in length: PER comes from the largest, n_vocab (the engine has checked
   // top_k against n_discrete where the table holds a discrete slot)
   const int n = (discrete && !per_slot) ? n_discrete : n_vocab;
   LRAM_REQUIRE(n >= 1 && n <= kSampleMaxRow, "action sampling: a row holds 1 .. 512 logits");
-  LRAM_REQUIRE(sp.top_k <= n, "action sampling: top_k exceeds the number of logits of the head in use");
+  // (per-slot settings: the engine has checked every sampling slot's top_k against the head that slot gets)
+  LRAM_REQUIRE(slots != nullptr || sp.top_k <= n, "action sampling: top_k exceeds the number of logits of the head in use");
   LRAM_REQUIRE(sp.draw != nullptr, "action sampling: no draw counter");
   const int items = B * ((discrete && !per_slot) ? 1 : act_dim);
   const dim3 grid((items + 3) / 4), block(256);
   if (col_end < 0) col_end = act_dim;
-#define LRAM_SAMPLE_LAUNCH(PER)                                                                                      \
-  hipLaunchKernelGGL(action_sample_kernel<PER>, grid, block, 0, stream, logits, actions, tokens, B, act_dim, n_vocab, \
-                     n_discrete, action_channels, tok_min, tok_max, discrete, col_begin, col_end, sp, slot_flags, slot_act)
+#define LRAM_SAMPLE_LAUNCH(PER)                                                                                             \
+  do {                                                                                                                      \
+    if (slots == nullptr)                                                                                                   \
+      hipLaunchKernelGGL(action_sample_kernel<PER>, grid, block, 0, stream, logits, actions, tokens, B, act_dim, n_vocab,   \
+                         n_discrete, action_channels, tok_min, tok_max, discrete, col_begin, col_end, sp, slot_flags,       \
+                         slot_act);                                                                                         \
+    else                                                                                                                    \
+      hipLaunchKernelGGL(action_sample_slots_kernel<PER>, grid, block, 0, stream, logits, actions, tokens, B, act_dim,      \
+                         n_vocab, n_discrete, action_channels, tok_min, tok_max, discrete, col_begin, col_end, sp,          \
+                         slot_flags, slot_act, slots);                                                                      \
+  } while (0)
   if (n <= 64)
     LRAM_SAMPLE_LAUNCH(1);
   else if (n <= 320)
@@ -310,6 +487,29 @@ void launch_action_sample(const float* logits, float* actions, int32_t* tokens, 
   else
     LRAM_SAMPLE_LAUNCH(8);
 #undef LRAM_SAMPLE_LAUNCH
+  LRAM_HIP_CHECK(hipGetLastError());
+}
+
+void launch_action_logp(const float* logits, const int32_t* tokens, float* logp, int B, int act_dim, int n_vocab,
+                        int n_discrete, int discrete, const SampleArgs& sp, hipStream_t stream, const uint8_t* slot_flags,
+                        const uint8_t* slot_act, const SampleSlot* slots) {
+  LRAM_REQUIRE((slot_flags == nullptr) == (slot_act == nullptr), "action logp: the slot table's two arrays go together");
+  LRAM_REQUIRE(logits && tokens && logp && B >= 1 && act_dim >= 1, "action logp: bad arguments");
+  const bool per_slot = slot_flags != nullptr;
+  const int n = (discrete && !per_slot) ? n_discrete : n_vocab;
+  LRAM_REQUIRE(n >= 1 && n <= kSampleMaxRow && n_discrete <= n_vocab, "action logp: a row holds 1 .. 512 logits");
+  LRAM_REQUIRE(slots != nullptr || sp.top_k <= n, "action logp: top_k exceeds the number of logits of the head in use");
+  const dim3 grid((B * act_dim + 3) / 4), block(256);
+#define LRAM_LOGP_LAUNCH(PER)                                                                                           \
+  hipLaunchKernelGGL(action_logp_kernel<PER>, grid, block, 0, stream, logits, tokens, logp, B, act_dim, n_vocab, n_discrete, \
+                     discrete, sp, slot_flags, slot_act, slots)
+  if (n <= 64)
+    LRAM_LOGP_LAUNCH(1);
+  else if (n <= 320)
+    LRAM_LOGP_LAUNCH(5);
+  else
+    LRAM_LOGP_LAUNCH(8);
+#undef LRAM_LOGP_LAUNCH
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
@@ -326,6 +526,25 @@ void launch_sample_tokens(const float* logits, int64_t rows, int n, int64_t ld, 
 #define LRAM_SAMPLE_LAUNCH(PER)                                                                                \
   hipLaunchKernelGGL(sample_tokens_kernel<PER>, grid, block, 0, stream, logits, rows, n, ld, temperature, top_k, \
                      top_p, uniform, tokens)
+  if (n <= 64)
+    LRAM_SAMPLE_LAUNCH(1);
+  else if (n <= 320)
+    LRAM_SAMPLE_LAUNCH(5);
+  else
+    LRAM_SAMPLE_LAUNCH(8);
+#undef LRAM_SAMPLE_LAUNCH
+  LRAM_HIP_CHECK(hipGetLastError());
+}
+
+void launch_sample_rows(const float* logits, int64_t rows, int n, int64_t ld, const uint8_t* mode, const double* temperature,
+                        const int32_t* top_k, const double* top_p, const double* uniform, const int32_t* tokens_in,
+                        int32_t* tokens_out, float* logp_out, hipStream_t stream) {
+  LRAM_REQUIRE(n >= 1 && n <= kSampleMaxRow, "sample rows: a row holds 1 .. 512 logits");
+  LRAM_REQUIRE(rows >= 1 && rows <= ((int64_t)1 << 32), "sample rows: rows must be in 1 .. 2^32");
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+#define LRAM_SAMPLE_LAUNCH(PER)                                                                                         \
+  hipLaunchKernelGGL(sample_rows_kernel<PER>, grid, block, 0, stream, logits, rows, n, ld, mode, temperature, top_k, top_p, \
+                     uniform, tokens_in, tokens_out, logp_out)
   if (n <= 64)
     LRAM_SAMPLE_LAUNCH(1);
   else if (n <= 320)

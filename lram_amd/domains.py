@@ -24,8 +24,15 @@ class Domain:
     reward_scale: float = 1.0
     target_return: float = 0.0     # in env units; the rtg token starts at target_return / reward_scale
     inv_index: Optional[Sequence[int]] = None   # full-space scatter table of vector observations (obs.inverse_index), or None = zero-pad
+    # how this domain's slots pick their tokens: None = the agent's own a_sample_kwargs (argmax where it has none); a dict =
+    # sample_from_logits' keywords for this domain, completed with its defaults and checked against THIS domain's head width;
+    # "greedy" = argmax for this domain whatever the agent samples elsewhere
+    a_sample_kwargs: object = None
 
     def __post_init__(self):
+        s = self.a_sample_kwargs
+        if not (s is None or isinstance(s, dict) or s == "greedy"):
+            raise ValueError(f"domain {self.name!r}: a_sample_kwargs must be None, a dict or \"greedy\", got {s!r}")
         if int(self.act_dim) != self.act_dim or self.act_dim < 1:
             raise ValueError(f"domain {self.name!r}: act_dim must be an integer >= 1, got {self.act_dim}")
         if self.discrete and self.act_dim != 1:
@@ -85,6 +92,30 @@ class SlotTable:
     def engine_arrays(self):
         """(discrete bool [B], act_dim int64 [B], image bool [B]): the arguments of Engine.set_slot_table."""
         return self.discrete, self.act_dim, self.image
+
+    def sample_settings(self, n_discrete: int, n_vocab: int, agent_kwargs: Optional[dict] = None) -> Optional[dict]:
+        """Per-slot sampling settings {"temperature": float64 [B], "top_k": int32 [B], "top_p": float64 [B], "greedy": bool [B]}
+        (the arguments of Engine.set_sampling_slots), or None when no domain states its own and the agent's setting serves
+        every slot.  A domain's dict is completed and checked by resolve_sample_kwargs against that domain's head width
+        (n_discrete logits for a discrete domain, n_vocab otherwise); so is `agent_kwargs` for every domain that falls back
+        on it.  Domains with neither are greedy."""
+        from .agent import resolve_sample_kwargs
+        per_domain = []
+        for d in self.domains:
+            n_head = n_discrete if d.discrete else n_vocab
+            s = d.a_sample_kwargs
+            if s is None:
+                s = agent_kwargs
+            per_domain.append(None if s is None or s == "greedy" else resolve_sample_kwargs(s, n_head))
+        if all(d.a_sample_kwargs is None for d in self.domains):
+            return None
+        rep = torch.tensor(self.counts)
+
+        def per_slot(key, fill, dtype):
+            return torch.repeat_interleave(torch.tensor([fill if s is None else s[key] for s in per_domain], dtype=dtype), rep)
+        return {"temperature": per_slot("temperature", 1.0, torch.float64), "top_k": per_slot("top_k", 0, torch.int32),
+                "top_p": per_slot("top_p", 0.0, torch.float64),
+                "greedy": torch.repeat_interleave(torch.tensor([s is None for s in per_domain], dtype=torch.bool), rep)}
 
     @property
     def n_image(self) -> int:

@@ -80,6 +80,11 @@ _SYMBOLS = {
                                             ctypes.c_int32, ctypes.c_double, _VP, _VP, _VP]),
     "lram_sample_uniforms": (ctypes.c_int32, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32,
                                               ctypes.c_uint64, _VP, _VP]),
+    "lram_set_sampling_slots": (ctypes.c_int32, [_VP, _VP, _VP, _VP, _VP]),
+    "lram_get_sampling_slots": (ctypes.c_int32, [_VP, _VP, _VP, _VP, _VP, ctypes.POINTER(ctypes.c_int32)]),
+    "lram_score_last_sampled": (ctypes.c_int32, [_VP, _VP, _VP, _VP]),
+    "lram_sample_rows": (ctypes.c_int32, [_VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, _VP, _VP, _VP, _VP, _VP, _VP,
+                                          _VP, _VP, _VP]),
     "lram_profile_begin": (ctypes.c_int32, [_VP]),
     "lram_profile_begin_sampled": (ctypes.c_int32, [_VP, ctypes.c_int32]),
     "lram_profile_end": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
@@ -510,10 +515,19 @@ class Engine:
     def last_logp(self, tokens: torch.Tensor, over: str = "selectable", temperature: float = 1.0) -> torch.Tensor:
         """Log-probabilities float32 [B, act_dim] of `tokens` (int32 [B, act_dim]: what step / prefill just returned) under the
         logits of the last action-producing call (lram_score_last).  over="selectable" with the armed temperature is the
-        distribution an unfiltered sampling head draws from; top-k / top-p are not applied."""
+        distribution an unfiltered sampling head draws from; top-k / top-p are not applied.
+        over="sampled" (lram_score_last_sampled): under the distribution the armed head draws from -- the per-slot settings
+        where set_sampling_slots set a table, those of set_sampling otherwise, top-k / top-p applied (a token outside the
+        support scores -inf, a greedy slot's argmax token 0).  `temperature` must then be left at its default: the armed one
+        is used."""
         B, A = self.batch, self.spec.act_dim
         _chk_dev(tokens, torch.int32, (B, A), self.device, "tokens")
         out = torch.zeros(B, A, dtype=torch.float32, device=self.device)
+        if over == "sampled":
+            if float(temperature) != 1.0:
+                raise ValueError('last_logp(over="sampled") scores under the armed settings: leave `temperature` at its default')
+            _check(self.lib, self.lib.lram_score_last_sampled(self._h, _ptr(tokens), _ptr(out), _stream_ptr(self.device)))
+            return out
         _check(self.lib, self.lib.lram_score_last(self._h, _ptr(tokens), _over_mode(over), float(temperature), _ptr(out),
                                                   _stream_ptr(self.device)))
         return out
@@ -741,6 +755,36 @@ class Engine:
         return {"temperature": t.value, "top_k": int(k.value), "top_p": p.value, "seed": int(seed.value),
                 "slot_base": int(base.value), "draws": int(draws.value)}
 
+    def set_sampling_slots(self, temperature=1.0, top_k=0, top_p=0.0, greedy=False):
+        """Per-slot settings of the armed sampling head (lram_set_sampling_slots): each argument a scalar (every slot) or an
+        array of length `batch`; `greedy` slots take the argmax of their row.  Seed, slot_base and the draw count stay those
+        of set_sampling, which must be armed.  set_sampling_slots(None) clears the table (the settings of set_sampling apply
+        again); set_sampling itself clears it too.  Synchronises and drops a captured graph: not a hot-path call."""
+        if temperature is None:
+            _check(self.lib, self.lib.lram_set_sampling_slots(self._h, None, None, None, None))
+            return
+        cols = slot_setting_arrays(self.batch, temperature, top_k, top_p, greedy)
+        mode = (~cols["greedy"]).to(torch.uint8).contiguous()
+        t, k, p = cols["temperature"].contiguous(), cols["top_k"].contiguous(), cols["top_p"].contiguous()
+        _check(self.lib, self.lib.lram_set_sampling_slots(self._h, ctypes.c_void_p(mode.data_ptr()), ctypes.c_void_p(t.data_ptr()),
+                                                          ctypes.c_void_p(k.data_ptr()), ctypes.c_void_p(p.data_ptr())))
+
+    @property
+    def sampling_slots(self) -> Optional[dict]:
+        """The per-slot table in effect (lram_get_sampling_slots): {"temperature": float64 [B], "top_k": int32 [B],
+        "top_p": float64 [B], "greedy": bool [B]} as CPU tensors, or None when none is set."""
+        B = self.batch
+        mode = torch.zeros(B, dtype=torch.uint8)
+        t, p = torch.zeros(B, dtype=torch.float64), torch.zeros(B, dtype=torch.float64)
+        k = torch.zeros(B, dtype=torch.int32)
+        on = ctypes.c_int32(0)
+        _check(self.lib, self.lib.lram_get_sampling_slots(self._h, ctypes.c_void_p(mode.data_ptr()), ctypes.c_void_p(t.data_ptr()),
+                                                          ctypes.c_void_p(k.data_ptr()), ctypes.c_void_p(p.data_ptr()),
+                                                          ctypes.byref(on)))
+        if not on.value:
+            return None
+        return {"temperature": t, "top_k": k, "top_p": p, "greedy": mode == 0}
+
     def profile_begin_sampled(self, every_n_steps: int):
         """Time every n-th step only (lram_profile_begin_sampled): 1/n of the event bookkeeping on the state-pass queue."""
         _check(self.lib, self.lib.lram_profile_begin_sampled(self._h, int(every_n_steps)))
@@ -819,6 +863,57 @@ def sample_tokens(logits: torch.Tensor, uniform: torch.Tensor, temperature: floa
     _check(lib, lib.lram_sample_tokens(_ptr(logits), R, int(n), int(ld), float(temperature), int(top_k), float(top_p),
                                        _ptr(uniform), _ptr(out), _stream_ptr(logits.device)))
     return out
+
+
+def slot_setting_arrays(n: int, temperature=1.0, top_k=0, top_p=0.0, greedy=False) -> dict:
+    """Scalars or arrays of length n -> {"temperature": float64 [n], "top_k": int32 [n], "top_p": float64 [n], "greedy": bool [n]}
+    on the CPU (the host arrays of lram_set_sampling_slots / the rows of lram_sample_rows)."""
+    out = {}
+    for name, v, dt in (("temperature", temperature, torch.float64), ("top_k", top_k, torch.int32),
+                        ("top_p", top_p, torch.float64), ("greedy", greedy, torch.bool)):
+        t = torch.as_tensor(v).to("cpu").reshape(-1)
+        if name == "top_k" and (t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool):
+            raise ValueError(f"top_k: expected integers, got {t.dtype}")
+        if t.numel() == 1:
+            t = t.expand(n)
+        if t.numel() != n:
+            raise ValueError(f"{name}: expected a scalar or {n} entries (one per slot / row), got {t.numel()}")
+        out[name] = t.to(dt).contiguous()
+    return out
+
+
+def sample_rows(logits: torch.Tensor, *, temperature=1.0, top_k=0, top_p=0.0, greedy=False,
+                uniform: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None):
+    """The sampling head's row code with per-row settings on caller data (lram_sample_rows): logits float32 [R, n]; the
+    settings scalars or arrays of length R.  uniform float64 [R] -> the drawn tokens int32 [R]; tokens int32 [R] -> their
+    log-probabilities float32 [R] under the row's filtered distribution.  Returns (drawn, logp), None where not asked for."""
+    lib = load_library()
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise ValueError("logits must be float32 [rows, n] with contiguous rows")
+    if uniform is None and tokens is None:
+        raise ValueError("sample_rows: give `uniform` (draw), `tokens` (score) or both")
+    R, n = logits.shape
+    dev = logits.device
+    cols = slot_setting_arrays(R, temperature, top_k, top_p, greedy)
+    t, k, p = cols["temperature"], cols["top_k"], cols["top_p"]
+    if not bool((torch.isfinite(t) & (t > 0)).all()):
+        raise ValueError("temperature must be finite and > 0")
+    if not bool(((p >= 0) & (p <= 1)).all()):
+        raise ValueError("top_p must be in [0, 1]")
+    if not bool(((k >= 0) & (k <= n)).all()):
+        raise ValueError("top_k must be in 0 .. n")
+    mode = (~cols["greedy"]).to(torch.uint8).to(dev)
+    t, k, p = t.to(dev), k.to(dev), p.to(dev)
+    drawn = logp = None
+    if uniform is not None:
+        _chk_dev(uniform, torch.float64, (R,), dev, "uniform")
+        drawn = torch.empty(R, dtype=torch.int32, device=dev)
+    if tokens is not None:
+        _chk_dev(tokens, torch.int32, (R,), dev, "tokens")
+        logp = torch.empty(R, dtype=torch.float32, device=dev)
+    _check(lib, lib.lram_sample_rows(_ptr(logits), R, int(n), int(logits.stride(0)), _ptr(mode), _ptr(t), _ptr(k), _ptr(p),
+                                     _ptr(uniform), _ptr(tokens), _ptr(drawn), _ptr(logp), _stream_ptr(dev)))
+    return drawn, logp
 
 
 def score_tokens(logits: torch.Tensor, spec_or_dims, *, actions: Optional[torch.Tensor] = None,
