@@ -423,6 +423,10 @@ void launch_mlstm_lazy_book(const MlstmLazyArgs& a, hipStream_t stream);
 bool mlstm_lazy_supported(int DH, int T);
 // count[b] = 0, g[b, :] = 1 for masked envs (mask == nullptr: all), both parities handled by the caller
 void launch_mlstm_lazy_clear(int32_t* count, float* g, const uint8_t* mask, int B, int NH, hipStream_t stream);
+// The envs b = first, first + period, ... with pending tokens have been folded in every block ahead of their step (the tail
+// fold completed outside it, lazy_finish_prefold): g != nullptr: one block's g[b, :] = 1; g == nullptr: count[b] = 0 (pending
+// tokens and the zero bit).  One launch per block first -- they read the counts -- then the launch that clears them.
+void launch_mlstm_lazy_folded(int32_t* count, float* g, int B, int NH, int first, int period, hipStream_t stream);
 void launch_lazy_counts_as_float(const int32_t* count, float* out, int B, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------

@@ -184,7 +184,25 @@ struct lram_engine {
   static constexpr int gemm_skinny_k = 1024;  // ... and K up to this take the few-row kernel
   static constexpr int fold_bubbles = 2;  // folds before the first read pass; the rest behind the sLSTM blocks, all on the state-pass
                                           // stream (measured on one box: k = 0 -- own stream, one block ahead -- 364k, 1 367k, 2 368k,
-                                          // 3 367k, 4 366k env-steps/s)
+                                          // 3 367k, 4 366k env-steps/s).  Counts the folds this step still has to launch: the blocks
+                                          // the step before folded in its tail (below) are not among them; re-measured with it there.
+  // Tail fold (two env slices): the folds of the first fold_tail_blocks mLSTM blocks that belong to step n + 1 are launched at the
+  // end of step n, behind the last read pass on the state-pass stream -- that stream has nothing else to run while the last
+  // slice's proj_down, norm and head finish -- and step n + 1 skips those launches (run_xlstm_stack).  `prefold` remembers what
+  // was folded early; every entry that is not the matching next step completes the fold first (lazy_finish_prefold).
+  // (Same box, three interleaved runs each, env-steps/s at 4096 slots, fold_bubbles / fold_tail_blocks: without 470.9k; 2 / 1 472.3k,
+  // 3 / 1 475.4k, 1 / 2 475.9k, 2 / 2 476.5k, 3 / 2 477.8k, 1 / 3 476.9k, 2 / 3 477.7k -- the box's own spread was 0.8 %; with the host
+  // synchronising every step, where the tail folds sit inside the caller's latency: without 456.2k, 2 / 1 467.7k, 2 / 2 468.2k,
+  // 2 / 3 463.3k.  A fold alone on the chip takes ~170 us, beside the sLSTM chains 220-320; from the third on the tail folds only
+  // lengthen the step's end.  profiles/fold_tail_ab.txt)
+  bool fold_tail = true;    // LRAM_FOLD_TAIL=0: every fold inside its own step
+  static constexpr int fold_tail_blocks = 2;
+  struct Prefold {
+    bool pending = false;
+    int blocks = 0;         // the first `blocks` mLSTM blocks are folded for the envs due at `step`
+    int64_t step = 0;       // the lazy_step those folds belong to
+    int period = 0, B = 0;
+  } prefold;
   int64_t lazy_step = 0;    // steps taken in lazy mode: fold phase and ping-pong parity
   std::vector<int> lazy_bound;  // host-side upper bound of pending tokens per fold class (b % period)
   bool lazy_dirty = false;      // a lazy step ran since the last materialise: windows may hold pending tokens
@@ -364,6 +382,7 @@ struct lram_engine {
     }
     LZ_COUNT.release();
     lazy_ready = false;
+    prefold = Prefold{};
     drop_slot_segments();
     st.clear();
     for (DevBuf* b : {&X, &XN, &TOK, &HID, &U, &Q, &K, &V, &XA, &H, &G, &SCAL, &RY, &LOGITS, &RES, &DTP, &SK, &GATES,
@@ -446,6 +465,7 @@ void fork_slices(lram_engine* e, const std::vector<Slice>& sl, hipStream_t hbm, 
 void join_slices(lram_engine* e, const std::vector<Slice>& sl, hipStream_t hbm, hipStream_t s);
 // engine_xlstm.hip, engine_mamba.hip
 void lazy_materialize(lram_engine* e, hipStream_t s);
+void lazy_finish_prefold(lram_engine* e, hipStream_t s);
 void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* reset, const std::vector<Slice>& sl, hipStream_t hbm);
 void run_mamba_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* reset, const std::vector<Slice>& sl);
 

@@ -493,6 +493,7 @@ void lazy_alloc(lram_engine* e) {
   }
   LRAM_HIP_CHECK(hipDeviceSynchronize());
   e->lazy_step = 0;
+  e->prefold = lram_engine::Prefold{};
   e->lazy_ready = true;
   slot_segments_build(e);
 }
@@ -521,6 +522,7 @@ const Knob kKnobs[] = {
      }},
     {"LRAM_LAZY_PERIOD", [](lram_engine& e, const char* v) { e.lazy_period = std::max(1, std::min(14, std::atoi(v))); }},
     {"LRAM_LAZY_CAP2_ENVS", [](lram_engine& e, const char* v) { e.lazy_cap2_envs = std::max(0, std::atoi(v)); }},
+    {"LRAM_FOLD_TAIL", [](lram_engine& e, const char* v) { e.fold_tail = std::atoi(v) != 0; }},
     {"LRAM_GN_FUSE", [](lram_engine& e, const char* v) { e.gn_fuse = std::max(0, std::min(2, std::atoi(v))); }},
     {"LRAM_F16_MIN_ROWS", [](lram_engine& e, const char* v) { e.f16x2_min_rows = std::max(9, std::atoi(v)); }},
     {"LRAM_GEMM_PRESPLIT", [](lram_engine& e, const char* v) { e.gemm_presplit = std::atoi(v) != 0; }},
@@ -667,12 +669,15 @@ int64_t lram_state_bytes_per_env(const lram_engine* e) {
 int32_t lram_set_graph_mode(lram_engine* e, int32_t enable) {
   return guarded([&] {
     LRAM_REQUIRE(e != nullptr, "lram_set_graph_mode: null engine");
-    if (enable != 0 && e->lazy_ready) {  // graph replay bakes kernel arguments: it runs on the materialised state
+    if (e->prefold.pending || (enable != 0 && e->lazy_ready)) {  // graph replay bakes kernel arguments: it runs on the materialised state
       LRAM_HIP_CHECK(hipSetDevice(e->device));
       // steps may still be in flight on a non-blocking caller stream, which the null stream does not order against:
       // drain the device before the folds touch the windows and C
       LRAM_HIP_CHECK(hipDeviceSynchronize());
-      lazy_materialize(e, nullptr);
+      if (enable != 0)
+        lazy_materialize(e, nullptr);
+      else
+        lazy_finish_prefold(e, nullptr);
       LRAM_HIP_CHECK(hipDeviceSynchronize());
     }
     e->graph_mode = enable != 0;
@@ -707,6 +712,12 @@ int32_t lram_get_state_mode(const lram_engine* e) { return (e != nullptr && e->l
 int32_t lram_set_micro_batches(lram_engine* e, int32_t n) {
   return guarded([&] {
     LRAM_REQUIRE(e != nullptr && n >= 0 && n <= 8, "lram_set_micro_batches: n must be in 0..8 (0 = auto)");
+    if (e->prefold.pending) {  // the tail fold belongs to the two-slice schedule: complete it (null stream: drain first, as in
+      LRAM_HIP_CHECK(hipSetDevice(e->device));   // lram_set_graph_mode)
+      LRAM_HIP_CHECK(hipDeviceSynchronize());
+      lazy_finish_prefold(e, nullptr);
+      LRAM_HIP_CHECK(hipDeviceSynchronize());
+    }
     e->n_micro = n;
     e->drop_graph();
   });

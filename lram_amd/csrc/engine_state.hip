@@ -67,6 +67,7 @@ int32_t lram_reset(lram_engine* e, const uint8_t* dev_env_mask, void* stream) {
     LRAM_HIP_CHECK(hipSetDevice(e->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int B = e->B;
+    lazy_finish_prefold(e, s);   // (a fold launched ahead of its step is completed in every block before windows are dropped)
     for (int i = 0; i < e->cfg.n_blocks; ++i) {
       if (e->compat_stale && i > 0) break;  // reference Mamba reset: layers >= 1 keep their cached state (Q1)
       BlockState& st = e->st[i];
@@ -206,6 +207,7 @@ int32_t lram_lazy_peek(lram_engine* e, int32_t block, int32_t which, float* dev_
                  "lram_lazy_peek: no such tensor");
     LRAM_HIP_CHECK(hipSetDevice(e->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
+    lazy_finish_prefold(e, s);   // (looks at a consistent representation: a fold launched ahead of its step is completed first)
     const size_t B = e->B, NH = e->cfg.n_heads;
     const int side = (int)(e->lazy_step & 1);  // what the next step reads = what the last one wrote
     if (which == 0) {
@@ -235,6 +237,7 @@ int32_t lram_state_copy_slots(lram_engine* e, const int32_t* host_src, const int
     if (n == 0) return;
     LRAM_HIP_CHECK(hipSetDevice(e->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
+    lazy_finish_prefold(e, s);
     SlotStateArgs a = slot_args(e, host_src, host_dst, n, s);
     a.n_chunks = a.lazy ? e->slot_n_chunks : e->slot_n_rec_chunks;
     launch_slot_copy(a, s);
@@ -258,6 +261,7 @@ int32_t lram_state_save_slots(lram_engine* e, const int32_t* host_slots, int32_t
     if (n == 0) return;
     LRAM_HIP_CHECK(hipSetDevice(e->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
+    lazy_finish_prefold(e, s);
     SlotStateArgs a = slot_args(e, host_slots, nullptr, n, s);
     a.n_chunks = e->slot_n_rec_chunks;
     a.records = dev_records;
@@ -290,6 +294,7 @@ int32_t lram_state_load_slots(lram_engine* e, const int32_t* host_slots, int32_t
     if (n == 0) return;
     LRAM_HIP_CHECK(hipSetDevice(e->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
+    lazy_finish_prefold(e, s);
     SlotStateArgs a = slot_args(e, host_slots, nullptr, n, s);
     a.n_chunks = e->slot_n_rec_chunks;
     a.records = const_cast<float*>(dev_records);

@@ -535,6 +535,7 @@ int32_t lram_prefill(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_em
     LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_prefill: null device pointer");
     LRAM_REQUIRE(timesteps >= 1, "lram_prefill: timesteps must be >= 1");
     if (dev_actions != nullptr) check_head_mode(e, discrete, "lram_prefill");
+    lazy_finish_prefold(e, static_cast<hipStream_t>(stream));   // (only an env-step takes a tail fold over)
     timesteps_launches(e, Pass{}, Inputs{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps}, dev_reset_mask,
                        discrete, dev_actions, dev_tokens, static_cast<hipStream_t>(stream));
     if (dev_actions != nullptr) sample_draw_advance(e, static_cast<hipStream_t>(stream));
@@ -566,6 +567,7 @@ int32_t lram_score(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embe
     sink.actions = dev_actions, sink.tokens = dev_tokens, sink.logp = dev_logp, sink.logits = dev_logits;
     sink.target_actions = dev_target_actions, sink.target_tokens = dev_target_tokens, sink.valid = dev_valid;
     sink.over = over, sink.temperature = temperature;
+    lazy_finish_prefold(e, static_cast<hipStream_t>(stream));   // (only an env-step takes a tail fold over)
     // (never captured, never a draw: the sampling mode and its counter are left alone)
     timesteps_launches(e, Pass{}, Inputs{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps}, dev_reset_mask,
                        discrete, nullptr, nullptr, static_cast<hipStream_t>(stream), &sink);
@@ -670,6 +672,7 @@ int32_t lram_encoder_step(lram_engine* e, const float* dev_inputs_embeds, int32_
     hipStream_t s = static_cast<hipStream_t>(stream);
     prof_tick(e);
     const size_t bytes = sizeof(float) * (size_t)e->B * tokens * e->cfg.d_model;
+    lazy_finish_prefold(e, s);   // (only an env-step takes a tail fold over)
     if (!lazy_active(e, tokens)) lazy_materialize(e, s);
     LRAM_HIP_CHECK(hipMemcpyAsync(e->X.p, dev_inputs_embeds, bytes, hipMemcpyDeviceToDevice, s));
     e->sync_used = 0, e->edge_used = 0;

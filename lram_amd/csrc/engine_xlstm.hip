@@ -5,10 +5,12 @@
 namespace {
 
 // ---- lazy matrix memory plumbing ------------------------------------------------------------------------
-MlstmLazyArgs lazy_args(lram_engine* e, int i, int T, const uint8_t* reset, int b0, int nb) {
+// step_off = 1: the arguments the NEXT step's launches get (the tail fold: its "in" side is the side this step's read passes write)
+MlstmLazyArgs lazy_args(lram_engine* e, int i, int T, const uint8_t* reset, int b0, int nb, int step_off = 0) {
   const lram_config& c = e->cfg;
   const size_t NH = c.n_heads, DH = e->dh(), B = e->B;
-  const int in = (int)(e->lazy_step & 1), out = 1 - in;
+  const int64_t step = e->lazy_step + step_off;
+  const int in = (int)(step & 1), out = 1 - in;
   BlockState& st = e->st[i];
   MlstmLazyArgs a{};
   a.C = st.s0.p + (size_t)b0 * NH * DH * DH;
@@ -24,8 +26,18 @@ MlstmLazyArgs lazy_args(lram_engine* e, int i, int T, const uint8_t* reset, int 
   a.reset = reset ? reset + b0 : nullptr;
   a.B = nb, a.T = T, a.NH = (int)NH, a.DH = (int)DH;
   // the fold phase is taken relative to the env's global index, so slices fold the same envs as the whole batch
-  a.phase = (int)((e->lazy_step + b0) % e->lazy_period), a.period = e->lazy_period, a.force = 0;
+  a.phase = (int)((step + b0) % e->lazy_period), a.period = e->lazy_period, a.force = 0;
   return a;
+}
+
+// Would a step of T tokens taken at lazy_step == `step` use the compact fold grid (no class but the due one can overflow)?
+bool lazy_bound_compact(const lram_engine* e, int64_t step, int T) {
+  const int P = e->lazy_period;
+  if ((int)e->lazy_bound.size() != P) return false;
+  const int c_due = (P - (int)(step % P)) % P;
+  for (int cls = 0; cls < P; ++cls)
+    if (cls != c_due && e->lazy_bound[cls] + T > kLazyWindow) return false;
+  return true;
 }
 
 }  // namespace
@@ -35,6 +47,7 @@ namespace lram::host {
 // Fold every pending window into C_base and empty the bookkeeping: afterwards the state is the materialised
 // reference layout again (export / import, prefill, long encoder calls, leaving lazy mode).
 void lazy_materialize(lram_engine* e, hipStream_t s) {
+  lazy_finish_prefold(e, s);
   if (!e->lazy_ready || !e->lazy_dirty) return;
   const lram_config& c = e->cfg;
   const size_t B = e->B, NH = c.n_heads;
@@ -52,6 +65,36 @@ void lazy_materialize(lram_engine* e, hipStream_t s) {
   }
   e->lazy_bound.assign(e->lazy_period, 0);
   e->lazy_dirty = false;
+}
+
+// Completes a pending tail fold outside the step it was launched for: the due class's fold in the blocks the tail did not cover
+// (compact grid, the phase of the step that would have come next), then the bookkeeping that fold step would have left -- for the
+// envs of that class with pending tokens the shared count 0 with the zero bit cleared and g = 1 in every mLSTM block, on the
+// side the next step reads.  LZ_COUNT is per env and shared by all blocks, so "block 0 is folded, the others are not" cannot be
+// written into it; afterwards the state is what the normal schedule leaves behind that class's fold, and later steps find nothing
+// pending there.  Called first thing by every entry that reads or edits the lazy representation and is not the matching step.
+void lazy_finish_prefold(lram_engine* e, hipStream_t s) {
+  if (!e->prefold.pending) return;
+  const lram_engine::Prefold pf = e->prefold;
+  e->prefold = lram_engine::Prefold{};
+  LRAM_REQUIRE(e->lazy_ready && pf.B == e->B && pf.period == e->lazy_period && pf.step == e->lazy_step,
+               "lazy mLSTM: a tail fold is pending for another state than the engine holds");
+  const lram_config& c = e->cfg;
+  const int B = e->B, NH = c.n_heads, P = e->lazy_period;
+  const int side = (int)(e->lazy_step & 1);             // what the next step reads = what the last one wrote
+  const int first = (P - (int)(e->lazy_step % P)) % P;   // the due class: smallest b with (lazy_step + b) % P == 0
+  int k = 0;
+  for (int i = 0; i < c.n_blocks; ++i) {
+    if (c.block_is_slstm[i] || k++ < pf.blocks) continue;
+    MlstmLazyArgs a = lazy_args(e, i, 1, nullptr, 0, B);
+    a.compact = 1;
+    launch_mlstm_lazy_fold(a, s);
+  }
+  int32_t* count = reinterpret_cast<int32_t*>(e->LZ_COUNT.p) + (size_t)side * B;
+  for (int i = 0; i < c.n_blocks; ++i)
+    if (!c.block_is_slstm[i]) launch_mlstm_lazy_folded(count, e->st[i].gsc.p + (size_t)side * B * NH, B, NH, first, P, s);
+  launch_mlstm_lazy_folded(count, nullptr, B, NH, first, P, s);
+  if ((int)e->lazy_bound.size() == P) e->lazy_bound[first] = 0;
 }
 
 }  // namespace lram::host
@@ -379,6 +422,22 @@ void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* res
   const lram_config& c = e->cfg;
   const int D = c.d_model;
   const bool lazy = lazy_active(e, T);
+  // Tail fold of the step before (lram_engine::prefold): this step is the one it was launched for when nothing came in between (every
+  // other entry completes it), the period and the batch are the same, there are still two slices and this step's folds take the
+  // compact grid.  Then the pre-folded blocks count as folded: their read passes see the due envs as lazy_view_of reports them --
+  // fold, n = 0, g0 = 1 -- which is what they are.  Otherwise the fold is completed here, ahead of everything the slices launch.
+  int n_prefolded = 0;
+  if (e->prefold.pending) {
+    const lram_engine::Prefold& pf = e->prefold;
+    if (lazy && sl.size() > 1 && pass.lane_rec == nullptr && pf.step == e->lazy_step && pf.period == e->lazy_period && pf.B == e->B &&
+        lazy_bound_compact(e, e->lazy_step, T)) {
+      n_prefolded = pf.blocks;
+      e->prefold = lram_engine::Prefold{};
+    } else {
+      lazy_finish_prefold(e, hbm);
+      for (const Slice& x : sl) stream_after(e, x.s, hbm);
+    }
+  }
   bool lazy_compact = false;   // this step's fold launches may use the compact grid (no window can overflow)
   if (lazy) {
     // Upper bound of pending tokens per fold class (env index mod period), tracked on the host: while no class can
@@ -436,11 +495,18 @@ void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* res
       if (!c.block_is_slstm[k]) return k;
     return -1;
   };
+  for (int i = next_mlstm(-1), k = 0; i >= 0 && k < n_prefolded; i = next_mlstm(i), ++k) folded[i] = 1;   // (by the step before)
   if (bubbles) {
     int k = 0;
     const int ahead = pass.images != nullptr ? e->fold_bubbles_images : lram_engine::fold_bubbles;
-    for (int i = next_mlstm(-1); i >= 0 && k < ahead; i = next_mlstm(i), ++k) launch_folds(i);
+    for (int i = next_mlstm(-1); i >= 0 && k < ahead; i = next_mlstm(i))
+      if (!folded[i]) launch_folds(i), ++k;
   }
+  // the last mLSTM block: the tail fold goes behind its read passes
+  int last_mlstm = -1;
+  for (int i = next_mlstm(-1); i >= 0; i = next_mlstm(i)) last_mlstm = i;
+  // ... where the next step can take it over as it stands: the compact grid, judged by the bounds this step leaves
+  const bool tail = bubbles && e->fold_tail && lazy_compact && pass.lane_rec == nullptr && lazy_bound_compact(e, e->lazy_step + 1, T);
   if (side_folds)
     for (int i = next_mlstm(-1); i >= 0; i = next_mlstm(i)) {
       launch_folds(i);
@@ -505,6 +571,23 @@ void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* res
       mlstm_cell(e, i, T, reset, x, hbm);
       mlstm_up_z(e, i, T, x);
       stream_after(e, x.s, hbm);
+    }
+    if (tail && i == last_mlstm) {
+      // Next step's folds of the first fold_tail_blocks blocks, now: their window rows, coefficients, scales and counts are final
+      // (this step's read passes of those blocks are done, in stream order), and the state-pass stream has nothing else to run
+      // until the step ends.  No reset mask: it is next step's, not known yet -- an env that turns out to restart then has been
+      // folded for nothing (its view sets `zero`, C_base is not read).  Enqueued ahead of the slices' join: the call leaves no
+      // work behind on an engine stream.
+      e->prefold.step = e->lazy_step + 1, e->prefold.period = e->lazy_period, e->prefold.B = e->B, e->prefold.blocks = 0;
+      e->prefold.pending = true;
+      for (int k = next_mlstm(-1); k >= 0 && e->prefold.blocks < lram_engine::fold_tail_blocks; k = next_mlstm(k)) {
+        MlstmLazyArgs la = lazy_args(e, k, T, nullptr, 0, e->B, 1);
+        la.compact = 1;
+        prof_record(e, hbm, true, true);
+        launch_mlstm_lazy_fold(la, hbm);
+        prof_record(e, hbm, false, true);
+        ++e->prefold.blocks;
+      }
     }
     for (const Slice& x : sl) mlstm_back(e, pass, i, T, x);
   }

@@ -786,6 +786,20 @@ __global__ __launch_bounds__(256) void mlstm_lazy_clear_kernel(int32_t* count, f
   if (gid == b * NH) count[b] = 0;
 }
 
+// A fold class (b = first, first + period, ...) folded ahead of its step in every block, outside that step: the bookkeeping its
+// fold step would have left for the envs that had pending tokens.  Bounds: k < ceil((B - first) / period) envs, b < B.
+__global__ __launch_bounds__(256) void mlstm_lazy_folded_kernel(int32_t* count, float* g, int B, int NH, int first, int period) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = gid / NH, h = gid - k * NH;
+  const int64_t b = (int64_t)first + (int64_t)k * period;
+  if (b >= B) return;
+  if ((count[b] & 0xFFFF) == 0) return;
+  if (g != nullptr)
+    g[b * NH + h] = 1.f;
+  else if (h == 0)
+    count[b] = 0;
+}
+
 template <int T, int LPR, int UNR, int KPL, int WP = W>
 void launch_cell_tluk(const MlstmLazyArgs& a, hipStream_t s) {
   constexpr int CW = 4 * LPR, RP = 256 / LPR;
@@ -875,6 +889,15 @@ void launch_mlstm_lazy_cell(const MlstmLazyArgs& a, hipStream_t stream) {
 void launch_mlstm_lazy_clear(int32_t* count, float* g, const uint8_t* mask, int B, int NH, hipStream_t stream) {
   hipLaunchKernelGGL(mlstm_lazy_clear_kernel, dim3((unsigned)((B * NH + 255) / 256)), dim3(256), 0, stream, count, g,
                      mask, B, NH);
+  LRAM_HIP_CHECK(hipGetLastError());
+}
+
+void launch_mlstm_lazy_folded(int32_t* count, float* g, int B, int NH, int first, int period, hipStream_t stream) {
+  LRAM_REQUIRE(period >= 1 && first >= 0 && NH >= 1, "lazy mLSTM: bad fold class");
+  if (first >= B) return;
+  const int envs = (B - first + period - 1) / period;
+  hipLaunchKernelGGL(mlstm_lazy_folded_kernel, dim3((unsigned)((envs * NH + 255) / 256)), dim3(256), 0, stream, count, g, B, NH,
+                     first, period);
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
