@@ -407,6 +407,13 @@ int32_t lram_profile_end_split(lram_engine* e, double* main_ms, int64_t* n_main,
  * nn.Linear calls at src/algos/models/decision_mamba.py:78-93 / [3P] xlstm proj_up / proj_down go to the vendor BLAS.) */
 int32_t lram_gemm_counts(lram_engine* e, double* out8, int32_t reset);
 
+/* Measurement aid: which form of the sLSTM recurrence (engine_xlstm.hip::slstm_block) the engine has launched since lram_create
+ * or the last call with `reset` != 0 -- out[0] token-kernel launches (one per token and slice), out[1] step-kernel launches (one
+ * per pass and slice), out[2] launches of the pointwise kernel behind a recurrent GEMM (one per token and slice).  The choice
+ * depends on d_model / num_heads, the slice size and LRAM_SLSTM_FUSED_ROWS / LRAM_SLSTM_SEQ; tests assert the form they mean
+ * to compare really ran.  (Reference: one sLSTMLayer.step per token, src/algos/models/decision_xlstm.py:155-166.) */
+int32_t lram_slstm_counts(lram_engine* e, int64_t* out3, int32_t reset);
+
 /* Standalone kernel entry points used by tests and micro-benchmarks. */
 /* C[M,N] = A[M,K] * W[N,K]^T (+ bias[N]) (+ residual C_in)   fp32, MFMA 32x32x2 f32 (exact k-ordered fma chain) */
 int32_t lram_gemm_f32(const float* dev_a, int64_t lda, const float* dev_w, int64_t ldw, float* dev_c,

@@ -357,6 +357,8 @@ def engine_limits(spec: ModelSpec) -> List[str]:
     else:
         if spec.d_inner % 4 or spec.d_conv != 4:
             why.append("Mamba d_inner must be a multiple of 4 and d_conv 4")
+        if spec.d_state not in (4, 8, 16, 32, 64):
+            why.append(f"Mamba d_state {spec.d_state} must be 4, 8, 16, 32 or 64")
     return why
 
 

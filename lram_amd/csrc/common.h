@@ -597,6 +597,9 @@ struct MambaSsmArgs {
 inline bool mamba_ssm_dt_fusable(int N, int R) { return N == 16 && R >= 1 && R <= 128; }
 void launch_transpose_f32(const float* src, int rows, int cols, float* dst, hipStream_t stream);
 void launch_mamba_ssm(const MambaSsmArgs& a, hipStream_t stream);
+// dtp[rows, d_inner] = xdb[rows, :R] (row pitch ldx) * w[d_inner, R]^T in plain fp32: for dt_rank / row pitches no GEMM kernel takes
+inline bool mamba_dt_proj_needs_plain_kernel(int N, int R) { return (R & 3) != 0 || ((R + 2 * N) & 3) != 0; }
+void launch_mamba_dt_proj(const float* xdb, int ldx, const float* w, int R, float* dtp, int64_t rows, int di, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // IMPALA-CNN image front end (impala_cnn.hip)

@@ -113,6 +113,7 @@ struct lram_engine {
   std::map<const float*, Split16> split16;
   bool gemm_presplit = true;   // LRAM_GEMM_PRESPLIT=0: the norms ahead of proj_up / in_proj write fp32 + row maxima (round 3) instead of
                                // the f16x2 GEMM's operand planes (gemm_f16x2p.hip)
+  int64_t slstm_counts[3] = {0, 0, 0};  // sLSTM recurrence launches per form: token kernel, step kernel, recurrent GEMM + pointwise (lram_slstm_counts)
   double gemm_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // launches / fp32-equivalent FLOPs per dispatcher family (lram_gemm_counts)
   std::vector<DevBuf> slstm_rt2;  // sLSTM: recurrent weights re-packed per block for slstm_seq.hip: fp32 [head][k][channel][gate], or
                                   // (f16x2 projections, the default) two f16 planes in the same bytes + slstm_rinv, the inverse row scales

@@ -62,6 +62,10 @@ void validate_config(const lram_config& c) {
   } else {
     LRAM_REQUIRE(c.d_inner > 0 && c.d_inner % 4 == 0 && c.d_conv == 4 && c.d_state > 0 && c.dt_rank > 0,
                  "bad Mamba dimensions");
+    // limit of the selective-state-update kernels (mamba_kernels.hip: d_state / 4 lanes per channel, a power of two, reduced by
+    // shuffles inside a wave quarter), checked here for the same reason as the xLSTM limits above
+    LRAM_REQUIRE(c.d_state == 4 || c.d_state == 8 || c.d_state == 16 || c.d_state == 32 || c.d_state == 64,
+                 "Mamba d_state must be 4, 8, 16, 32 or 64");
   }
 }
 

@@ -184,6 +184,14 @@ int32_t lram_gemm_counts(lram_engine* e, double* out8, int32_t reset) {
   return 0;
 }
 
+int32_t lram_slstm_counts(lram_engine* e, int64_t* out3, int32_t reset) {
+  if (e == nullptr || out3 == nullptr) return 1;
+  for (int i = 0; i < 3; ++i) out3[i] = e->slstm_counts[i];
+  if (reset)
+    for (int i = 0; i < 3; ++i) e->slstm_counts[i] = 0;
+  return 0;
+}
+
 int32_t lram_gemm_f32(const float* dev_a, int64_t lda, const float* dev_w, int64_t ldw, float* dev_c, int64_t ldc,
                       const float* dev_bias, int32_t accumulate, int32_t m, int32_t n, int32_t k, void* stream) {
   return guarded([&] {

@@ -77,7 +77,10 @@ void mamba_stage(lram_engine* e, const Pass& pass, int i, int stage, int T, cons
     xp.a = XA, xp.lda = di, xp.w = w.x_proj, xp.ldw = di, xp.c = Q, xp.ldc = ldx;
     xp.m = rows, xp.n = ldx, xp.k = di, xp.a_amax = amx_xa, xp.amax_parts = amx ? parts : 1;
     gemm(e, xp, gs);
-    if (!dt_fused) {
+    if (!dt_fused && mamba_dt_proj_needs_plain_kernel(N, R)) {
+      // (K = dt_rank or the row pitch dt_rank + 2 * d_state not a multiple of 4: the GEMM kernels' 16-byte operand loads do not apply)
+      launch_mamba_dt_proj(Q, ldx, w.dt_proj, R, DTP, rows, di, gs);
+    } else if (!dt_fused) {
       GemmArgs dp;
       dp.a = Q, dp.lda = ldx, dp.w = w.dt_proj, dp.ldw = R, dp.c = DTP, dp.ldc = di;
       dp.m = rows, dp.n = di, dp.k = R;

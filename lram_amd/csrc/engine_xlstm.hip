@@ -359,6 +359,7 @@ void slstm_block(lram_engine* e, int i, int T, const uint8_t* reset, const Slice
     ta.hprev = t == 0 ? state : Y + (int64_t)(t - 1) * Hs, ta.hprev_ld = t == 0 ? Hs : (int64_t)T * Hs;
     ta.B = sl.nb, ta.T = T, ta.t = t, ta.H = Hs, ta.NH = NH, ta.state_B = e->B, ta.write_h = (t == T - 1 && t > 0) ? 1 : 0;
     launch_slstm_token(ta, s);
+    ++e->slstm_counts[0];
   }
   if (tok_fused && T == 1)  // the single launch read the state's h plane: it is refreshed from the output rows afterwards
     LRAM_HIP_CHECK(hipMemcpyAsync(state, Y, (size_t)sl.nb * Hs * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -373,6 +374,7 @@ void slstm_block(lram_engine* e, int i, int T, const uint8_t* reset, const Slice
       qa.rt2 = e->slstm_rt2[i].p;
     qa.B = sl.nb, qa.T = T, qa.H = Hs, qa.NH = NH, qa.state_B = e->B;
     launch_slstm_seq(qa, s);
+    ++e->slstm_counts[1];
   }
   for (int t = 0; !tok_fused && !seq && t < T; ++t) {
     GemmArgs ra;
@@ -385,6 +387,7 @@ void slstm_block(lram_engine* e, int i, int T, const uint8_t* reset, const Slice
     pw.gates = gates, pw.ry = RY, pw.bias = w.rbias, pw.state = state, pw.yout = Y;
     pw.B = sl.nb, pw.T = T, pw.t = t, pw.H = Hs, pw.state_B = e->B;
     launch_slstm_pointwise(pw, s);
+    ++e->slstm_counts[2];
   }
   GroupNormArgs gn;
   gn.h = Y, gn.gamma = w.gn_g, gn.beta = w.gn_b, gn.out = X, gn.rows = rows, gn.NH = NH, gn.DH = SDH;

@@ -4,6 +4,7 @@
 // selective_state_update (Triton) as called from [3P] mamba_ssm Mamba.step via
 // src/algos/models/decision_mamba.py:130-147.  State layouts are the reference's:
 // conv_state [B, d_inner, d_conv], ssm_state [B, d_inner, d_state], fp32.
+#include <algorithm>
 #include <cstdlib>
 
 #include "common.h"
@@ -79,6 +80,22 @@ __global__ void transpose_f32_kernel(const float* src, int rows, int cols, float
   dst[(int64_t)c * rows + r] = src[i];
 }
 
+// dt_proj as its own launch where no GEMM kernel serves it: dt_rank (K) or the x_proj row pitch dt_rank + 2 * d_state (lda) is
+// not a multiple of 4, so neither the operand rows nor the weight rows are 16-byte aligned.  One thread per (row, channel),
+// exact fp32 in k order.  The reference's presets all have dt_rank = ceil(d_model / 16) with d_model a multiple of 64.
+__global__ __launch_bounds__(256) void mamba_dt_proj_kernel(const float* __restrict__ xdb, int ldx, const float* __restrict__ w, int R,
+                                                            float* __restrict__ dtp, int64_t rows, int di) {
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= rows * di) return;
+  const int64_t row = gid / di;
+  const int d = (int)(gid - row * di);
+  const float* x = xdb + row * ldx;
+  const float* wr = w + (int64_t)d * R;
+  float acc = 0.f;
+  for (int r = 0; r < R; ++r) acc += x[r] * wr[r];
+  dtp[gid] = acc;
+}
+
 // kSsmEnvs envs per workgroup (4 for an env-step: amortises A = -exp(A_log) and keeps 4 state loads in flight
 // per lane; 1 for the long prefill chunks, whose LDS staging grows with T)
 
@@ -93,7 +110,7 @@ __global__ __launch_bounds__(256) void mamba_ssm_kernel(MambaSsmArgs a) {
   __shared__ float yo[kSsmEnvs][T][64];
   const int di = a.d_inner, N = a.N;
   const int Q = N >> 2;               // float4 per channel
-  const int cpb = 256 / Q;            // channels per block (<= 64)
+  const int cpb = min(64, 256 / Q);   // channels per block: the LDS rows below hold 64 (d_state 4 / 8: lanes beyond 64 * Q idle)
   const int b0 = blockIdx.y * kSsmEnvs;
   const int ne = min(kSsmEnvs, a.B - b0);
   const int tid = threadIdx.x;
@@ -104,8 +121,9 @@ __global__ __launch_bounds__(256) void mamba_ssm_kernel(MambaSsmArgs a) {
   const int qd = tid % Q;
   const int cl = tid / Q;
   const int d0 = dbase + cl;
-  const bool active = d0 < di;
+  const bool active = cl < cpb && d0 < di;
   const int d = active ? d0 : di - 1;
+  const int cs = min(cl, cpb - 1);    // this lane's column of sc / yo (idle lanes read a valid one and write nothing)
   const float4 al = *reinterpret_cast<const float4*>(a.A_log + (int64_t)d * N + 4 * qd);
   const float4 A = make_float4(-expf(al.x), -expf(al.y), -expf(al.z), -expf(al.w));
   const float Dd = a.Dp[d];
@@ -177,8 +195,8 @@ __global__ __launch_bounds__(256) void mamba_ssm_kernel(MambaSsmArgs a) {
     const int b = b0 + e;
 #pragma unroll
     for (int t = 0; t < T; ++t) {
-      const float x = sc[e][t][0][cl];
-      const float dt = sc[e][t][1][cl];
+      const float x = sc[e][t][0][cs];
+      const float dt = sc[e][t][1][cs];
       const float4 Bm = *reinterpret_cast<const float4*>(&bc[e][t][0][4 * qd]);
       const float4 Cm = *reinterpret_cast<const float4*>(&bc[e][t][1][4 * qd]);
       // decay factors via the hardware exp2 (v_exp_f32): |dt * A| is O(1), relative error ~1e-7
@@ -189,7 +207,7 @@ __global__ __launch_bounds__(256) void mamba_ssm_kernel(MambaSsmArgs a) {
       float y = s[e].x * Cm.x + s[e].y * Cm.y + s[e].z * Cm.z + s[e].w * Cm.w;
       // sum over the Q lanes of this channel (Q is a power of two, lanes are adjacent)
       for (int off = 1; off < Q; off <<= 1) y += __shfl_xor(y, off, 64);
-      if (qd == 0) yo[e][t][cl] = (y + Dd * x) * sc[e][t][2][cl];
+      if (qd == 0 && cl < cpb) yo[e][t][cl] = (y + Dd * x) * sc[e][t][2][cl];
     }
     if (active) {
       v4f_t v;
@@ -367,6 +385,13 @@ void launch_transpose_f32(const float* src, int rows, int cols, float* dst, hipS
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
+void launch_mamba_dt_proj(const float* xdb, int ldx, const float* w, int R, float* dtp, int64_t rows, int di, hipStream_t stream) {
+  LRAM_REQUIRE(rows > 0 && di > 0 && R > 0 && ldx >= R, "Mamba dt_proj: empty problem");
+  const int64_t n = rows * di;
+  hipLaunchKernelGGL(mamba_dt_proj_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, xdb, ldx, w, R, dtp, rows, di);
+  LRAM_HIP_CHECK(hipGetLastError());
+}
+
 void launch_mamba_conv(const MambaConvArgs& a, hipStream_t stream) {
   LRAM_REQUIRE(a.K == 4, "Mamba d_conv must be 4");
   const int64_t n = (int64_t)a.B * a.d_inner;
@@ -386,7 +411,7 @@ void launch_mamba_conv(const MambaConvArgs& a, hipStream_t stream) {
 void launch_mamba_ssm(const MambaSsmArgs& a, hipStream_t stream) {
   const int Q = a.N >> 2;
   LRAM_REQUIRE(a.N % 4 == 0 && Q >= 1 && Q <= 16 && (Q & (Q - 1)) == 0, "Mamba d_state must be 4 * 2^k, <= 64");
-  const int cpb = 256 / Q;
+  const int cpb = std::min(64, 256 / Q);   // (mamba_ssm_kernel: at most 64 channels per workgroup)
   const unsigned gx = (unsigned)((a.d_inner + cpb - 1) / cpb);
   LRAM_REQUIRE(a.dt_wt == nullptr || mamba_ssm_dt_fusable(a.N, a.R), "fused dt_proj needs d_state 16 and dt_rank <= 128");
   LRAM_REQUIRE(a.dt_wt != nullptr || a.dtp != nullptr, "selective state update needs dtp or dt_w");

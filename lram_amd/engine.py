@@ -117,6 +117,7 @@ _SYMBOLS = {
     "lram_stream_rmw": (ctypes.c_int32, [_VP, ctypes.c_size_t, _VP]),
     "lram_stream_read": (ctypes.c_int32, [_VP, ctypes.c_size_t, _VP, _VP]),
     "lram_gemm_counts": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]),
+    "lram_slstm_counts": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]),
     "lram_set_slot_table": (ctypes.c_int32, [_VP, _VP, _VP]),
     "lram_get_slot_table": (ctypes.c_int32, [_VP, _VP, _VP, ctypes.POINTER(ctypes.c_int32)]),
     "lram_step_slots": (ctypes.c_int32, [_VP, _VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP,
@@ -805,6 +806,13 @@ class Engine:
         _check(self.lib, self.lib.lram_gemm_counts(self._h, buf, 1 if reset else 0))
         names = ("f16x2", "bf16x3", "f32", "few_row_f32")
         return {n: {"launches": int(buf[i]), "flop": float(buf[4 + i])} for i, n in enumerate(names)}
+
+    def slstm_counts(self, reset: bool = False) -> dict:
+        """Launches of each form of the sLSTM recurrence since the last reset (lram_slstm_counts): "token" (one launch per
+        token), "step" (one launch per pass) and "gemm" (pointwise launches behind a recurrent GEMM, one per token)."""
+        buf = (ctypes.c_int64 * 3)()
+        _check(self.lib, self.lib.lram_slstm_counts(self._h, buf, 1 if reset else 0))
+        return {"token": int(buf[0]), "step": int(buf[1]), "gemm": int(buf[2])}
 
     def profile_end_split(self):
         """(state-pass ms, state-pass launches, fold ms, fold launches) -- lram_profile_end_split."""

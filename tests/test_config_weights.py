@@ -185,6 +185,45 @@ def test_every_reference_preset_resolves_and_engine_limits_are_stated():
         assert engine_limits(spec_from_agent_params(presets[name])) == []
 
 
+def test_geometry_sweep_cases_are_accepted_and_the_oracle_runs_them():
+    """Every geometry of the GPU sweep (tests/geometry_cases.py): `engine_limits` admits it, it has the sizes the sweep's table
+    states, and the CPU oracle -- the checker of that sweep -- steps it (2 env-steps with a restart, finite actions and state)."""
+    from lram_amd.config import engine_limits
+    from oracle import dt_ref
+    from tests.geometry_cases import ALL_CASES, MAMBA_CASES, XLSTM_CASES, case_spec
+    from tests.helpers import make_inputs
+    assert len(ALL_CASES) == 17
+    for cid in ALL_CASES:
+        spec = case_spec(cid)
+        assert engine_limits(spec) == [], (cid, engine_limits(spec))
+        if cid in XLSTM_CASES:
+            assert (spec.head_dim, spec.d_model // spec.n_heads) == XLSTM_CASES[cid][1:], cid
+        else:
+            assert (spec.d_inner, spec.d_state, spec.dt_rank) == MAMBA_CASES[cid][1:], cid
+        sd = init_state_dict(spec, seed=0)
+        ora = dt_ref.OraclePolicy(spec, sd)
+        for obs, rtg, rew, mask in make_inputs(spec, 3, 2, seed=5, reset_prob=0.5):
+            act, dbg = ora.step(obs, rtg, rew, mask, return_debug=True)
+            assert act.shape == (3, spec.act_dim) and bool(torch.isfinite(dbg["hidden"]).all()), cid
+    assert {case_spec(c).n_heads for c in XLSTM_CASES} == {1, 2, 4, 8}
+    assert {case_spec(c).d_state for c in MAMBA_CASES} == {4, 8, 16, 32, 64}
+
+
+def test_engine_limits_refuse_what_the_kernels_refuse():
+    """The selective-state-update kernel spreads a channel's d_state over d_state / 4 lanes of a wave quarter: 4, 8, 16, 32 or 64.
+    Any other value is refused when the engine is created (validate_config in csrc/engine.hip; tests/test_gpu_geometry.py holds
+    the two to each other), not by a launch in the middle of the first step."""
+    from lram_amd.config import engine_limits
+    for d_state in (12, 128, 1, 2, 20, 48):
+        spec = ModelSpec(backbone="mamba", kind="MDDMamba", d_model=64, n_blocks=2, d_state=d_state)
+        assert engine_limits(spec) == [f"Mamba d_state {d_state} must be 4, 8, 16, 32 or 64"], d_state
+    for d_state in (4, 8, 16, 32, 64):
+        assert engine_limits(ModelSpec(backbone="mamba", kind="MDDMamba", d_model=64, n_blocks=2, d_state=d_state)) == []
+    # dt_rank and expand stay free (dt_rank values that are no multiple of 4 take a plain fp32 dt_proj kernel)
+    for kw in (dict(dt_rank=1), dict(dt_rank=7, expand=3, d_model=68), dict(dt_rank=129), dict(expand=1)):
+        assert engine_limits(ModelSpec(backbone="mamba", kind="MDDMamba", n_blocks=2, **{"d_model": 64, **kw})) == []
+
+
 def test_published_model_presets_are_the_reference_configurations():
     """The presets of the published sizes (reference README.md:186-240) are the reference's huggingface presets with slstm_at set
     as the README's command lines set it ([7:1]: `+agent_params.huggingface.xlstm_config.slstm_at='[1,3]'`; [1:0]: none), and
