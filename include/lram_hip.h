@@ -196,6 +196,65 @@ int32_t lram_score(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embe
                    const float* dev_target_actions, const int32_t* dev_target_tokens, const uint8_t* dev_valid, int32_t over,
                    double temperature, float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits, void* stream);
 
+/* Stored contexts of PER-ENV length: lram_prefill / lram_score where env b's context has n_b = host_lengths[b] timesteps -- held-out
+ * trajectories of different lengths, the demonstrations that prime the envs of an in-context evaluation, the last
+ * eval_context_len steps of envs at different points of their episodes (the reference pads such batches and masks them,
+ * src/algos/universal_decision_transformer_sb3.py:398-434: attention_mask).  Afterwards every env holds the state of ITS OWN
+ * context, so a rollout (lram_step) can follow.
+ *   inputs, outputs   laid out exactly as in lram_prefill / lram_score: [batch, timesteps, ...], LEFT-aligned.  Env b's context is
+ *                     rows [b, 0 .. n_b); rows [b, n_b .. timesteps) have no influence on any output or state and may hold
+ *                     anything, NaN included (the rtg / reward / embedding rows are never read; with raw observations the state
+ *                     Linear runs over all rows of dev_obs_seq in one launch and the padded result rows are never read)
+ *   host_lengths      HOST int32[batch], each in 0 .. timesteps, handed over as lram_state_copy_slots hands its lists over
+ *                     (hipMemcpyAsync from pageable memory, ordered on `stream`, no synchronisation)
+ *   n_b == timesteps      the env behaves as in lram_prefill: dev_reset_mask[b] decides whether it continues or restarts
+ *   0 < n_b < timesteps   the context REPLACES the slot's state: the slot is reset before its first timestep whatever
+ *                         dev_reset_mask[b] says
+ *   n_b == 0              the slot is left alone: its state after the call equals its state before it bit for bit (as
+ *                         lram_state_export shows it; pending lazy windows are folded first, as by every stored-context call),
+ *                         its dev_actions / dev_tokens row holds 0.0f / -1, its score rows are masked.  Such slots still run
+ *                         through the kernels on zero tokens: their records are saved into engine-owned scratch
+ *                         (count x lram_state_bytes_per_env, allocated on first need) ahead of the first chunk and loaded back
+ *                         behind the last
+ *   dev_actions / dev_tokens (lram_prefill_ragged)   env b's action at its OWN last timestep n_b - 1
+ *   lram_score_ragged   row [b, l], l < n_b, as lram_score writes it (dev_valid and the targets are read at the left-aligned
+ *                       row); rows l >= n_b hold logp 0.0f, token -1, action 0.0f on every call, their logits are not written
+ * How: the contexts are END-aligned inside the call -- env b starts at call-timestep s_b = timesteps - n_b -- and the chunk plan
+ * (lram_context_plan) puts a chunk boundary at every distinct s_b; the env's reset flag is set on that chunk and the token front
+ * end feeds it zeros before s_b and its own rows from there on.  No recurrent kernel knows about lengths.  Env b's state
+ * afterwards is what lram_prefill of n_b timesteps over its own rows leaves, up to fp32 rounding (the chunk partition differs);
+ * chunks of 1-4 timesteps run the token-sequential kernels, longer ones the chunkwise kernels where lram_prefill would.  The lazy
+ * matrix memory is materialised first and every chunk of the call runs the materialised kernels.  With every n_b == timesteps
+ * the call makes the launches of lram_prefill / lram_score: outputs and state are bit-identical.  Sampling: one draw per
+ * lram_prefill_ragged call with dev_actions; lram_score_ragged draws nothing.  Never captured.
+ * Cost: chunks <= ceil(timesteps / cap) + distinct starts; with as many distinct lengths as timesteps it degenerates to one
+ * timestep per chunk, i.e. towards `timesteps` lram_step calls.
+ * Refused (message in lram_last_error, nothing launched, state untouched): whatever lram_prefill / lram_score refuse; a length
+ * outside 0 .. timesteps; all lengths 0; tokens_per_step != 3; d_model % 4 != 0; raw observations whose [batch, timesteps,
+ * d_model] embeddings exceed 2 GiB; the Mamba modes of lram_set_compat_mode (mamba_repeat > 1; stale_state, where a reset
+ * re-initialises layer 0 only and the padding would leak into layers >= 1); scratch for the n_b == 0 slots that would leave less
+ * than 2 GiB of device memory free.
+ * Out of scope: a SHORTER context that CONTINUES a slot's state (needs length-aware state kernels); running a call on a subset of
+ * slots without computing the other rows (kept slots are saved and restored, not skipped); image frames as stored contexts; the
+ * Mamba reference-trajectory modes.  The dense entries, the lazy step path and the GEMM dispatcher are unchanged. */
+int32_t lram_prefill_ragged(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
+                            const float* dev_reward_seq, int32_t timesteps, const int32_t* host_lengths,
+                            const uint8_t* dev_reset_mask, int32_t discrete, float* dev_actions, int32_t* dev_tokens, void* stream);
+int32_t lram_score_ragged(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
+                          const float* dev_reward_seq, int32_t timesteps, const int32_t* host_lengths,
+                          const uint8_t* dev_reset_mask, int32_t discrete, const float* dev_target_actions,
+                          const int32_t* dev_target_tokens, const uint8_t* dev_valid, int32_t over, double temperature,
+                          float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits, void* stream);
+/* The chunk plan of such a call, a pure host function (no engine, no GPU): the ascending call-timesteps at which its chunks
+ * start.  s_b = timesteps - host_lengths[b]; the plan starts at the smallest s_b over envs with a context (earlier timesteps run
+ * no chunk at all), holds every distinct s_b of those envs, and cuts the stretch between two such boundaries (or the last one
+ * and `timesteps`) into ceil(len / cap) equal chunks of ceil(len / ceil(len / cap)) timesteps (the last one shorter), cap >= 1
+ * being what a dense call of `timesteps` takes per chunk.  Where no env starts inside the call (every context is of full length)
+ * the plan is the dense call's own: chunks of `cap` from 0 on.  out_starts receives the starts, *out_n their number; with
+ * max_chunks too small nothing is written but *out_n and the call fails.  Errors as the ragged entries' length rules. */
+int32_t lram_context_plan(int32_t timesteps, int32_t cap, const int32_t* host_lengths, int32_t batch, int32_t* out_starts,
+                          int32_t max_chunks, int32_t* out_n);
+
 /* Log-probabilities of caller-given tokens (device int32[batch, act_dim]: what lram_step* / lram_prefill just returned in
  * dev_tokens) under the logits of the last action-producing call, which are still in the engine's logits buffer: dev_logp
  * (device float[batch, act_dim]) as lram_score defines it, one kernel launch, no draw.  The reference's counterpart is

@@ -27,7 +27,7 @@ from typing import Dict, Optional
 import torch
 
 from .config import ModelSpec
-from .engine import Engine
+from .engine import Engine, check_context_lengths
 
 
 SAMPLE_DEFAULTS = {"temperature": 1.0, "top_k": 0, "top_p": 0.5}   # sample_from_logits' own (model_utils.py:7)
@@ -420,9 +420,11 @@ class RecurrentAgent:
         """Grade stored trajectories (Engine.score): observations [B, L, obs_dim] -- padded and normalised with state_mean /
         state_std as predict_batch does -- returns_to_go [B, L] in model units, rewards [B, L] (None: the reference loop's
         zero reward token), recorded `actions` [B, L, n] (float; n <= act_dim, padded with zeros; a discrete agent's action
-        index in column 0) and `lengths` [B] (timesteps that count per env, from the start; None = all L).  `valid` is built
-        from the lengths; timesteps beyond an env's length still advance its state.  reset=True starts every env from an empty
-        context.  Returns the ScoreResult (per-timestep greedy actions / tokens and the log-probability of the recorded
+        index in column 0) and `lengths` [B] (timesteps that count per env, from the start; None = all L).  The lengths go
+        to the engine (Engine.score(lengths=...)): rows beyond an env's length are masked and never read, and the state the call
+        leaves is that of each env's own `lengths[b]` timesteps, so predict_batch can continue every env from there (an env of
+        length 0 keeps the state it had).  reset=True starts every env from an empty context; a length in 1 .. L - 1 always does,
+        so reset=False together with such a length raises ValueError.  Returns the ScoreResult (per-timestep greedy actions / tokens and the log-probability of the recorded
         actions); rollout.score_loss turns it into the reference's loss.  With a slot table every slot is scored with its
         own head; image observations are not taken here (embed them and call Engine.score with obs_is_embedding)."""
         B = self.n_envs
@@ -441,15 +443,44 @@ class RecurrentAgent:
                 raise ValueError(f"actions: {a.shape[-1]} action dims exceed max_act_dim {self.spec.act_dim}")
             target = torch.zeros(B, L, self.spec.act_dim, dtype=torch.float32, device=self.device)
             target[..., : a.shape[-1]] = a
-        valid = None
         if lengths is not None:
-            n = torch.as_tensor(lengths).to(self.device).reshape(B, 1)
-            valid = (torch.arange(L, device=self.device).reshape(1, L) < n).to(torch.uint8).contiguous()
+            lengths = check_context_lengths(torch.as_tensor(lengths).reshape(-1), B, L)
+            if not reset and any(0 < n < L for n in lengths):
+                raise ValueError("score_trajectories: a context shorter than L replaces the env's state; reset=False cannot "
+                                 "be combined with a length in 1 .. L - 1")
         mask = torch.ones(B, dtype=torch.uint8, device=self.device) if reset else None
         want = tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "logp" or target is not None)
         discrete = "per_slot" if getattr(self, "slot_table", None) is not None else self.is_discrete
-        return self.engine.score(obs, rtg, rew, actions=target, valid=valid, reset_mask=mask, discrete=discrete, over=over,
-                                 temperature=temperature, want=want, logits=logits)
+        return self.engine.score(obs, rtg, rew, actions=target, reset_mask=mask, discrete=discrete, over=over,
+                                 temperature=temperature, want=want, logits=logits, lengths=lengths)
+
+    @torch.no_grad()
+    def prime_contexts(self, observations: torch.Tensor, returns_to_go: torch.Tensor,
+                       rewards: Optional[torch.Tensor] = None, lengths=None, want_action: bool = False):
+        """Prime every env with its own stored context in one call (Engine.prefill(lengths=...)), after which predict_batch
+        continues: observations [B, L, obs_dim] -- padded and normalised as predict_batch does -- returns_to_go [B, L], rewards
+        [B, L] (None: zeros) and `lengths` [B]: env b's context is its first lengths[b] timesteps (None = all L).  Every env
+        with a context starts from an empty state; an env of length 0 keeps the state it has.  want_action=True returns the
+        action at each env's own last timestep (as predict_batch returns it), else None.  Image observations are not taken
+        here, as in score_trajectories."""
+        B = self.n_envs
+        if observations.dim() != 3 or observations.shape[0] != B:
+            raise ValueError(f"observations: expected [{B}, L, obs_dim], got {tuple(observations.shape)}")
+        L = observations.shape[1]
+        if lengths is not None:
+            lengths = check_context_lengths(torch.as_tensor(lengths).reshape(-1), B, L)
+        obs, _ = self._prepare_obs(observations.reshape(B * L, -1))
+        obs = obs.view(B, L, -1).contiguous()
+        rtg = returns_to_go.to(self.device, torch.float32).reshape(B, L).contiguous()
+        rew = torch.zeros(B, L, dtype=torch.float32, device=self.device) if rewards is None else \
+            rewards.to(self.device, torch.float32).reshape(B, L).contiguous()
+        mask = torch.ones(B, dtype=torch.uint8, device=self.device)
+        discrete = "per_slot" if getattr(self, "slot_table", None) is not None else self.is_discrete
+        actions, _ = self.engine.prefill(obs, rtg, rew, reset_mask=mask, discrete=discrete, want_action=want_action,
+                                         lengths=lengths)
+        if not want_action:
+            return None
+        return actions[:, :1].to(torch.int64) if self.is_discrete else actions
 
     @torch.no_grad()
     def action_log_prob(self, over: str = "selectable") -> torch.Tensor:

@@ -298,8 +298,32 @@ struct ScoreArgs {
   int32_t* tokens = nullptr;
   float* logp = nullptr;
   float* logits_out = nullptr;             // [., act_dim * n_vocab]: the rows as they were read
+  // Stored contexts of per-env length (lram_score_ragged), nullable: device [envs], the call-timestep at which env's context
+  // starts (outer - its length).  Row g then stands for call-timestep t = off + g % inner of its env: from start[env] on its
+  // outputs, targets and `valid` byte are at row env * outer + t - start[env] (the caller's tensors are left-aligned); before
+  // it the row is padding and writes the fill values to row env * outer + (outer - start[env]) + t, so that the launches of a
+  // call over t = 0 .. outer - 1 write every row of the tensors exactly once.
+  const int32_t* start = nullptr;
 };
 void launch_action_score(const ScoreArgs& a, hipStream_t stream);
+
+// Stored contexts of per-env length (context_kernels.hip; lram_prefill_ragged / lram_score_ragged).  start[b] = L - n_b is the
+// call-timestep at which env b's context begins inside a call of L timesteps (n_b = 0: start[b] = L, the slot only sees padding).
+// launch_embed_chunk with a start per env: the token rows of call-timesteps t0 .. t0 + steps - 1; env b's rows of timestep t come
+// from row t - start[b] of its (left-aligned) emb / rtg / rew, rows with t < start[b] are zeros.
+void launch_embed_chunk_ragged(float* x, const float* emb, int64_t emb_stride, const float* rtg, const float* rew, int64_t in_stride,
+                               const int32_t* start, int t0, const float* w_rtg, const float* b_rtg, const float* w_rew,
+                               const float* b_rew, int B, int steps, int T, int D, hipStream_t stream);
+// mask[c][b] = 1 where env b is reset at the start of chunk c: its context starts there and is shorter than the call
+// (start[b] == chunk_start[c], 0 < start[b] < L); a full-length env (start[b] == 0) takes reset[b] (nullable) on chunk 0.
+void launch_context_masks(uint8_t* mask, const int32_t* start, const int32_t* chunk_start, const uint8_t* reset, int n_chunks,
+                          int B, int L, hipStream_t stream);
+// fill values (logp 0, token -1, action 0) into the padded rows [b, L - start[b] + t], t = 0 .. steps - 1, of [B, L, act_dim]
+// tensors (each nullable): the call-timesteps ahead of the first chunk, which no score launch covers
+void launch_score_fill_ragged(float* actions, int32_t* tokens, float* logp, const int32_t* start, int B, int L, int steps,
+                              int act_dim, hipStream_t stream);
+// rows of slots without a context (start[b] == L): actions 0, tokens -1 (each nullable)
+void launch_action_fill_kept(float* actions, int32_t* tokens, const int32_t* start, int B, int L, int act_dim, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // xLSTM

@@ -234,6 +234,11 @@ struct lram_engine {
                 // sLSTM block uses XN as fp32 while another slice's mLSTM block holds planes
   DevBuf GATES, AMAT, VEC;           // chunkwise mLSTM prefill work buffers (allocated with the first long chunk)
   DevBuf SEQ_EMB;                    // state embeddings of a stored context [B, L, D] (lram_prefill)
+  // Stored contexts of per-env length (lram_prefill_ragged / lram_score_ragged): CTX holds, as bytes of one allocation, int32
+  // start[B] (call-timestep at which each env's context begins), int32 chunk_start[L] and the per-chunk reset masks
+  // uint8[n_chunks, B]; KEEP the state records of the slots the call leaves alone (length 0), saved ahead of the first chunk
+  // and loaded back behind the last.  Both grown outside the launches, as SEQ_EMB is.
+  DevBuf CTX, KEEP;
   // lram_score: the head's logits for a block of (env, timestep) rows of one chunk, one region per chunk lane / env slice in
   // flight.  A region holds at most score_rows rows of act_dim * n_vocab floats (default 4096 rows: 34 MiB at 8 x 274 logits;
   // LRAM_SCORE_ROWS at lram_create, at least 16); a chunk with more rows goes through it block by block.
@@ -387,7 +392,7 @@ struct lram_engine {
     drop_slot_segments();
     st.clear();
     for (DevBuf* b : {&X, &XN, &TOK, &HID, &U, &Q, &K, &V, &XA, &H, &G, &SCAL, &RY, &LOGITS, &RES, &DTP, &SK, &GATES,
-                      &AMAT, &VEC, &SEQ_EMB, &IMG_EMB, &IMG_P, &IMG_X0, &IMG_X1, &IMG_T, &XN2, &ASCALE, &AMX_XN, &AMX_XA, &AMX_H, &X0, &U0, &SCORE_LG})
+                      &AMAT, &VEC, &SEQ_EMB, &IMG_EMB, &IMG_P, &IMG_X0, &IMG_X1, &IMG_T, &XN2, &ASCALE, &AMX_XN, &AMX_XA, &AMX_H, &X0, &U0, &SCORE_LG, &CTX, &KEEP})
       b->release();
     for (auto& t : twin)
       for (DevBuf& b : t) b.release();
@@ -464,6 +469,9 @@ void stream_after(lram_engine* e, hipStream_t dst, hipStream_t src, bool boundar
 std::vector<Slice> make_slices(lram_engine* e, hipStream_t s, hipStream_t* hbm);
 void fork_slices(lram_engine* e, const std::vector<Slice>& sl, hipStream_t hbm, hipStream_t s);
 void join_slices(lram_engine* e, const std::vector<Slice>& sl, hipStream_t hbm, hipStream_t s);
+// engine_state.hip
+void save_slot_records(lram_engine* e, const int32_t* host_slots, int n, float* dev_records, hipStream_t s);
+void load_slot_records(lram_engine* e, const int32_t* host_slots, int n, const float* dev_records, hipStream_t s);
 // engine_xlstm.hip, engine_mamba.hip
 void lazy_materialize(lram_engine* e, hipStream_t s);
 void lazy_finish_prefold(lram_engine* e, hipStream_t s);

@@ -58,6 +58,47 @@ SlotStateArgs slot_args(lram_engine* e, const int32_t* host_a, const int32_t* ho
 
 }  // namespace
 
+namespace lram::host {
+
+// Records of the listed slots into dev_records (the body of lram_state_save_slots; lists checked by the caller).
+void save_slot_records(lram_engine* e, const int32_t* host_slots, int n, float* dev_records, hipStream_t s) {
+  lazy_finish_prefold(e, s);
+  SlotStateArgs a = slot_args(e, host_slots, nullptr, n, s);
+  a.n_chunks = e->slot_n_rec_chunks;
+  a.records = dev_records;
+  a.rec_vec = (reinterpret_cast<uintptr_t>(dev_records) & 15) == 0 ? 1 : 0;
+  launch_slot_save(a, s);
+  if (a.lazy) {   // C = g C_base + window, computed into the record: no fold, no write to engine state
+    const size_t B = e->B, NH = e->cfg.n_heads;
+    for (int i = 0; i < e->cfg.n_blocks; ++i) {
+      if (e->slot_c_off[i] < 0) continue;
+      BlockState& st = e->st[i];
+      SlotLazySaveArgs la;
+      la.C = st.s0.p, la.wk = st.wk.p, la.wv = st.wv.p;
+      la.coef = st.coef.p + (size_t)a.parity * B * NH * kLazyWindow;
+      la.g = st.gsc.p + (size_t)a.parity * B * NH;
+      la.count = reinterpret_cast<const int32_t*>(e->LZ_COUNT.p) + (size_t)a.parity * B;
+      la.slots = a.src, la.n = n, la.NH = (int)NH, la.DH = e->dh();
+      la.records = dev_records, la.rec_numel = a.rec_numel, la.rec_off = e->slot_c_off[i];
+      la.rec_vec = (a.rec_vec && la.rec_off % 4 == 0 && a.rec_numel % 4 == 0) ? 1 : 0;
+      launch_slot_lazy_save(la, s);
+    }
+  }
+}
+
+// Records the engine itself saved, back into their slots (lram_prefill_ragged's kept slots): lram_state_load_slots without the
+// range check of the sLSTM hidden planes, which the recurrence that produced them has kept.
+void load_slot_records(lram_engine* e, const int32_t* host_slots, int n, const float* dev_records, hipStream_t s) {
+  lazy_finish_prefold(e, s);
+  SlotStateArgs a = slot_args(e, host_slots, nullptr, n, s);
+  a.n_chunks = e->slot_n_rec_chunks;
+  a.records = const_cast<float*>(dev_records);
+  a.rec_vec = (reinterpret_cast<uintptr_t>(dev_records) & 15) == 0 ? 1 : 0;
+  launch_slot_load(a, s);   // lazy mode: also empties the loaded slots' windows on the live side
+}
+
+}  // namespace lram::host
+
 // ---- C ABI -----------------------------------------------------------------------------------------------------------
 extern "C" {
 
@@ -260,29 +301,7 @@ int32_t lram_state_save_slots(lram_engine* e, const int32_t* host_slots, int32_t
     slot_lists_check("lram_state_save_slots", host_slots, nullptr, n, e->B, false);
     if (n == 0) return;
     LRAM_HIP_CHECK(hipSetDevice(e->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    lazy_finish_prefold(e, s);
-    SlotStateArgs a = slot_args(e, host_slots, nullptr, n, s);
-    a.n_chunks = e->slot_n_rec_chunks;
-    a.records = dev_records;
-    a.rec_vec = (reinterpret_cast<uintptr_t>(dev_records) & 15) == 0 ? 1 : 0;
-    launch_slot_save(a, s);
-    if (a.lazy) {   // C = g C_base + window, computed into the record: no fold, no write to engine state
-      const size_t B = e->B, NH = e->cfg.n_heads;
-      for (int i = 0; i < e->cfg.n_blocks; ++i) {
-        if (e->slot_c_off[i] < 0) continue;
-        BlockState& st = e->st[i];
-        SlotLazySaveArgs la;
-        la.C = st.s0.p, la.wk = st.wk.p, la.wv = st.wv.p;
-        la.coef = st.coef.p + (size_t)a.parity * B * NH * kLazyWindow;
-        la.g = st.gsc.p + (size_t)a.parity * B * NH;
-        la.count = reinterpret_cast<const int32_t*>(e->LZ_COUNT.p) + (size_t)a.parity * B;
-        la.slots = a.src, la.n = n, la.NH = (int)NH, la.DH = e->dh();
-        la.records = dev_records, la.rec_numel = a.rec_numel, la.rec_off = e->slot_c_off[i];
-        la.rec_vec = (a.rec_vec && la.rec_off % 4 == 0 && a.rec_numel % 4 == 0) ? 1 : 0;
-        launch_slot_lazy_save(la, s);
-      }
-    }
+    save_slot_records(e, host_slots, n, dev_records, static_cast<hipStream_t>(stream));
   });
 }
 

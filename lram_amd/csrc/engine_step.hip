@@ -113,15 +113,33 @@ struct Inputs {
   int L;
 };
 
+// Stored contexts of per-env length (lram_prefill_ragged / lram_score_ragged): the contexts are end-aligned inside the call, env b
+// starting at call-timestep L - n_b, and the chunks are cut so that every env starts on a chunk boundary (context_plan below).
+// Device pointers into lram_engine::CTX, filled on the call's stream ahead of the first chunk.
+struct ContextPlan {
+  std::vector<int> starts;        // ascending call-timesteps at which the chunks start; the last chunk ends at L
+  std::vector<char> has_reset;    // per chunk: some env is reset at its start (others pass no mask at all, as a dense call does)
+  const int32_t* dev_start = nullptr;   // [B]
+  const uint8_t* dev_masks = nullptr;   // [n_chunks, B]
+};
+
 // Token front end of one env slice for the chunk of Lc timesteps that starts at timestep l: embeds the chunk's tokens into the
 // slice's rows of X and applies embed_ln.  seq_emb: the state embeddings of a stored context, made ahead of the chunks.
-void embed_tokens(lram_engine* e, const Pass& pass, const Inputs& in, const float* seq_emb, const Slice& x, int l, int Lc) {
+void embed_tokens(lram_engine* e, const Pass& pass, const Inputs& in, const float* seq_emb, const Slice& x, int l, int Lc,
+                  const ContextPlan* plan = nullptr) {
   const lram_config& c = e->cfg;
   const int D = c.d_model, T = c.tokens_per_step, Tc = T * Lc, L = in.L, emb = in.emb;
   const int64_t obs_w = emb ? D : c.state_dim;
   const float *obs = in.obs, *rtg = in.rtg, *rew = in.rew;
   const size_t r0 = (size_t)x.b0 * Tc, b0 = x.b0;
   float* X = e->X.p + r0 * D;
+  if (plan != nullptr) {  // per-env lengths: every env's rows from its own (left-aligned) context, zeros ahead of it
+    LRAM_REQUIRE(seq_emb != nullptr, "ragged context: no state embeddings");
+    launch_embed_chunk_ragged(X, seq_emb + b0 * L * D, (int64_t)L * D, rtg + b0 * L, rew + b0 * L, L, plan->dev_start + b0, l,
+                              e->w_rtg, e->b_rtg, e->w_rew, e->b_rew, x.nb, Lc, Tc, D, x.s);
+    launch_row_norm(X, D, X, D, e->eln_g, e->eln_b, x.nb * Tc, D, 1e-5f, 0, x.s);
+    return;
+  }
   if (seq_emb != nullptr) {  // stored context: the chunk's token rows in one launch
     launch_embed_chunk(X, seq_emb + (b0 * L + l) * D, (int64_t)L * D, rtg + b0 * L + l, rew + b0 * L + l, L, e->w_rtg, e->b_rtg,
                        e->w_rew, e->b_rew, x.nb, Lc, Tc, D, x.s);
@@ -194,7 +212,7 @@ ScoreArgs score_args(const lram_engine* e, const ScoreSink& k, int discrete) {
 // on the scratch bound.  (A last block of <= 8 rows would take the GEMV kernel, another summation order: it starts
 // kScoreMinRows before the end instead and recomputes the rows it overlaps.)
 void score_chunk(lram_engine* e, const ScoreSink& k, const Slice& x, float* scratch, int64_t cap, int l0, int Lc, int L,
-                 int discrete) {
+                 int discrete, const int32_t* ctx_start = nullptr) {
   const lram_config& c = e->cfg;
   const int D = c.d_model, T = c.tokens_per_step;
   const int64_t nlog = (int64_t)c.act_dim * c.n_vocab, R = (int64_t)x.nb * Lc;
@@ -210,7 +228,7 @@ void score_chunk(lram_engine* e, const ScoreSink& k, const Slice& x, float* scra
     count_gemm(e, 2, gh);
     ScoreArgs a = score_args(e, k, discrete);
     a.logits = scratch, a.ld = nlog, a.row0 = (int64_t)x.b0 * Lc + beg, a.rows = nr;
-    a.inner = Lc, a.outer = L, a.off = l0;
+    a.inner = Lc, a.outer = L, a.off = l0, a.start = ctx_start;
     launch_action_score(a, x.s);
   }
 }
@@ -219,7 +237,7 @@ void score_chunk(lram_engine* e, const ScoreSink& k, const Slice& x, float* scra
 // argmax or a sampled draw.  What discrete = LRAM_HEAD_PER_SLOT needs was checked by the entry (check_head_mode).
 // With a sink (lram_score over L timesteps) the same logits are scored into row [b, L - 1] of the sink's tensors instead: no draw.
 void action_head(lram_engine* e, const Pass& pass, const std::vector<Slice>& sl, int Tc, int last_steps, int discrete,
-                 float* actions, int32_t* tokens, const ScoreSink* sink = nullptr, int L = 1) {
+                 float* actions, int32_t* tokens, const ScoreSink* sink = nullptr, int L = 1, const int32_t* ctx_start = nullptr) {
   const lram_config& c = e->cfg;
   const int D = c.d_model, T = c.tokens_per_step;
   const int64_t nlog = (int64_t)c.act_dim * c.n_vocab;
@@ -243,7 +261,7 @@ void action_head(lram_engine* e, const Pass& pass, const std::vector<Slice>& sl,
     if (sink != nullptr) {
       ScoreArgs a = score_args(e, *sink, discrete);
       a.logits = e->LOGITS.p + b0 * nlog, a.ld = nlog, a.row0 = (int64_t)b0, a.rows = x.nb;
-      a.inner = 1, a.outer = L, a.off = L - 1;
+      a.inner = 1, a.outer = L, a.off = L - 1, a.start = ctx_start;
       launch_action_score(a, x.s);
       continue;
     }
@@ -267,8 +285,10 @@ void action_head(lram_engine* e, const Pass& pass, const std::vector<Slice>& sl,
 // With a sink (lram_score; `actions` is then null) the head runs at every timestep: after the stack pass of every chunk, on
 // that chunk's stream and workspace (score_chunk), and once more on the last timestep through the very launches a call without
 // a sink makes for it (action_head) -- row [b, L - 1] of the sink is what lram_prefill computes, and LOGITS is left as it leaves it.
+// With a plan (per-env lengths) the chunks are the plan's instead of the fixed stride, chunk c takes row c of the plan's reset
+// masks instead of `reset` on the first chunk, and the front end and the sink place every env's rows by its own start.
 void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, const uint8_t* reset, int discrete, float* actions,
-                        int32_t* tokens, hipStream_t s, const ScoreSink* sink = nullptr) {
+                        int32_t* tokens, hipStream_t s, const ScoreSink* sink = nullptr, const ContextPlan* plan = nullptr) {
   const lram_config& c = e->cfg;
   const int D = c.d_model, T = c.tokens_per_step, L = in.L;
   e->sync_used = 0, e->edge_used = 0;
@@ -280,7 +300,7 @@ void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, cons
   // Stored contexts: the state embeddings of ALL timesteps as one GEMM ahead of the chunks (rows b * L + l, as the input lies),
   // instead of one few-row GEMM per timestep (206M, 64 envs x 512 timesteps: 1024 launches of 12-26 us -> 1 + one per chunk)
   const float* seq_emb = nullptr;
-  if (L > 1 && T == 3 && D % 4 == 0 && !call.compat_shared) {
+  if ((L > 1 || plan != nullptr) && T == 3 && D % 4 == 0 && !call.compat_shared) {
     if (in.emb) {
       seq_emb = in.obs;
     } else if ((size_t)e->B * L * D <= ((size_t)1 << 29)) {   // <= 2 GiB
@@ -298,7 +318,14 @@ void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, cons
   // chunk lanes (see lram_engine::chunk_lanes): the last chunk -- the one the action head reads -- is on lane 0 = the primary
   // workspace and the caller's stream.  Where they apply they replace the automatic env slices of large batches as well: whole-batch
   // launches, three chunks in flight (16M, 1024 envs x 252 timesteps: 224.4 -> 215.5 ms; 206M, 512 envs x 63: 295.3 -> 274.0 ms).
-  const int n_chunks = (L + kChunk - 1) / kChunk;
+  std::vector<int> chunk_at;   // first timestep of every chunk, and L
+  if (plan != nullptr)
+    chunk_at = plan->starts;
+  else
+    for (int l = 0; l < L; l += kChunk) chunk_at.push_back(l);
+  chunk_at.push_back(L);
+  const int n_chunks = (int)chunk_at.size() - 1;
+  const int32_t* ctx_start = plan ? plan->dev_start : nullptr;
   // (Mamba's stored contexts and the xLSTM geometries without a chunkwise form go through the token-sequential kernels in chunks
   // of 4 timesteps: the lanes apply to them as they are)
   const bool lanes = e->n_micro <= 1 && n_chunks >= 2 && e->chunk_lanes && !e->graph_mode && !call.compat_shared && twin_ready(e);
@@ -330,8 +357,8 @@ void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, cons
     for (int k = 1; k < NL; ++k) stream_after(e, lane_s[k], s, true);
   }
   int Tc = T, last_steps = 1;
-  for (int l = 0, ci = 0; l < L; l += kChunk, ++ci) {
-    const int Lc = std::min(kChunk, L - l);
+  for (int ci = 0; ci < n_chunks; ++ci) {
+    const int l = chunk_at[ci], Lc = chunk_at[ci + 1] - l;
     Tc = T * Lc;
     last_steps = Lc;
     const int lane = (n_chunks - 1 - ci) % NL;
@@ -346,19 +373,30 @@ void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, cons
       }
     } lane_scope{e, lane};
     if (lane) swap_workspace(e, lane);
+    // Per-env lengths on env slices: a slice's rows of the shared workspace are [b0 * Tc, (b0 + nb) * Tc), and the plan's chunks
+    // differ in length anywhere in the call, so the rows a slice takes for this chunk may be ones another slice -- the slices
+    // run a block or more apart -- is still working on for the chunk before.  Every slice leaves that chunk before any enters
+    // this one.  (A dense call's chunks are all of one length but the last.)
+    if (plan != nullptr && multi && ci > 0 && Lc != l - chunk_at[ci - 1]) {
+      for (const Slice& x : sl) stream_after(e, hbm, x.s);
+      for (const Slice& x : sl) stream_after(e, x.s, hbm);
+    }
     // (shared repeated forwards: the tokens of this env-step were embedded by pass 0 -- X0 / U0)
     if (!(call.compat_shared && call.compat_pass > 0))
-      for (const Slice& x : use) embed_tokens(e, call, in, seq_emb, x, l, Lc);
+      for (const Slice& x : use) embed_tokens(e, call, in, seq_emb, x, l, Lc, plan);
     Pass pass = call;
     if (lanes) pass.lane_wait = ci > 0 ? &e->lane_ev[(lane + 1) % NL] : nullptr, pass.lane_rec = &e->lane_ev[lane];
-    run_stack(e, pass, Tc, l == 0 ? reset : nullptr, use, lanes ? lane_s[lane] : hbm);
+    const uint8_t* chunk_reset = l == 0 ? reset : nullptr;
+    if (plan != nullptr) chunk_reset = plan->has_reset[ci] ? plan->dev_masks + (size_t)ci * e->B : nullptr;
+    run_stack(e, pass, Tc, chunk_reset, use, lanes ? lane_s[lane] : hbm);
     if (sink != nullptr && L > 1)
       for (size_t i = 0; i < use.size(); ++i)
-        score_chunk(e, *sink, use[i], e->SCORE_LG.p + (lanes ? (size_t)lane : i) * score_region, score_cap, l, Lc, L, discrete);
+        score_chunk(e, *sink, use[i], e->SCORE_LG.p + (lanes ? (size_t)lane : i) * score_region, score_cap, l, Lc, L, discrete,
+                    ctx_start);
   }
   for (int k = 1; k < NL; ++k) stream_after(e, s, lane_s[k], true);
   if (sink != nullptr)
-    action_head(e, call, sl, Tc, last_steps, discrete, nullptr, nullptr, sink, L);
+    action_head(e, call, sl, Tc, last_steps, discrete, nullptr, nullptr, sink, L, ctx_start);
   else if (actions != nullptr)
     action_head(e, call, sl, Tc, last_steps, discrete, actions, tokens);
   if (multi && call.compat_pass == call.compat_passes - 1) join_slices(e, sl, hbm, s);
@@ -439,6 +477,154 @@ void step_entry(lram_engine* e, const char* who) {
   prof_tick(e);
 }
 
+
+// lram_score's refusals (before anything is launched, the recurrent state untouched) and its sink; `who` names the entry.
+ScoreSink score_sink_checked(const lram_engine* e, const char* who, int discrete, const float* dev_target_actions,
+                             const int32_t* dev_target_tokens, const uint8_t* dev_valid, int over, double temperature,
+                             float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits) {
+  const std::string w(who);
+  LRAM_REQUIRE(e->compat_repeat <= 1, w + ": the Mamba repeated-forward mode is on (lram_set_compat_mode, mamba_repeat > 1): "
+                                      "its trajectories advance the state once per action dim and are not scored");
+  LRAM_REQUIRE(!(dev_target_actions && dev_target_tokens),
+               w + ": both dev_target_actions and dev_target_tokens are given (at most one)");
+  LRAM_REQUIRE(dev_actions || dev_tokens || dev_logp || dev_logits, w + ": no output is given");
+  LRAM_REQUIRE(!dev_logp || dev_target_actions || dev_target_tokens,
+               w + ": dev_logp needs a target (dev_target_actions or dev_target_tokens)");
+  LRAM_REQUIRE(over == 0 || over == 1, w + ": over must be 0 (the whole vocabulary) or 1 (the selectable range)");
+  LRAM_REQUIRE(temperature > 0.0 && temperature < (double)INFINITY, w + ": temperature must be finite and > 0");
+  LRAM_REQUIRE(discrete == 0 || discrete == 1 || discrete == LRAM_HEAD_PER_SLOT, w + ": discrete must be 0, 1 or LRAM_HEAD_PER_SLOT");
+  LRAM_REQUIRE(discrete != LRAM_HEAD_PER_SLOT || e->slot_table, w + ": LRAM_HEAD_PER_SLOT needs a slot table (lram_set_slot_table)");
+  LRAM_REQUIRE(discrete != 1 || e->cfg.n_discrete >= 1, w + ": a discrete head needs n_discrete >= 1");
+  ScoreSink sink;
+  sink.actions = dev_actions, sink.tokens = dev_tokens, sink.logp = dev_logp, sink.logits = dev_logits;
+  sink.target_actions = dev_target_actions, sink.target_tokens = dev_target_tokens, sink.valid = dev_valid;
+  sink.over = over, sink.temperature = temperature;
+  return sink;
+}
+
+// The chunk plan of a call of L timesteps over contexts of per-env length (include/lram_hip.h: lram_context_plan): pure host code.
+// Throws on a length outside 0 .. L or when every length is 0.
+std::vector<int> context_plan(int L, int cap, const int32_t* lengths, int B, const char* who) {
+  const std::string w(who);
+  LRAM_REQUIRE(L >= 1 && cap >= 1 && B >= 1 && lengths != nullptr, w + ": bad argument (timesteps, cap, batch >= 1, lengths given)");
+  std::vector<char> begins(L, 0);   // begins[t]: some env with a context starts at call-timestep t
+  bool any = false;
+  for (int b = 0; b < B; ++b) {
+    LRAM_REQUIRE(lengths[b] >= 0 && lengths[b] <= L, w + ": length " + std::to_string(lengths[b]) + " of env slot " +
+                                                          std::to_string(b) + " is outside 0 .. timesteps = " + std::to_string(L));
+    if (lengths[b] > 0) begins[L - lengths[b]] = 1, any = true;
+  }
+  LRAM_REQUIRE(any, w + ": every length is 0 (no env slot has a context)");
+  std::vector<int> bounds;
+  for (int t = 0; t < L; ++t)
+    if (begins[t]) bounds.push_back(t);
+  std::vector<int> starts;
+  if (bounds.size() == 1 && bounds[0] == 0) {   // no env starts inside the call: the dense call's own chunks
+    for (int t = 0; t < L; t += cap) starts.push_back(t);
+    return starts;
+  }
+  bounds.push_back(L);
+  for (size_t i = 0; i + 1 < bounds.size(); ++i) {
+    const int len = bounds[i + 1] - bounds[i];
+    const int n = (len + cap - 1) / cap, step = (len + n - 1) / n;
+    for (int t = bounds[i]; t < bounds[i + 1]; t += step) starts.push_back(t);
+  }
+  return starts;
+}
+
+// What lram_prefill_ragged and lram_score_ragged share.  check(): everything that refuses the call, before anything is launched or
+// allocated.  run(): the save of the kept slots, the plan's device tables, the chunks (`launch` runs timesteps_launches with the
+// plan), the load of the kept slots.  A call whose lengths all equal `timesteps` never gets here: it is the dense entry's.
+struct RaggedCall {
+  lram_engine* e;
+  std::string w;
+  int L;
+  const int32_t* lengths;
+  std::vector<int32_t> kept;   // slots with length 0
+
+  void check(int obs_is_embedding) {
+    const lram_config& c = e->cfg;
+    LRAM_REQUIRE(lengths != nullptr, w + ": host_lengths is NULL");
+    bool any = false;
+    for (int b = 0; b < e->B; ++b) {
+      LRAM_REQUIRE(lengths[b] >= 0 && lengths[b] <= L, w + ": length " + std::to_string(lengths[b]) + " of env slot " +
+                                                            std::to_string(b) + " is outside 0 .. timesteps = " + std::to_string(L));
+      any = any || lengths[b] > 0;
+      if (lengths[b] == 0) kept.push_back(b);
+    }
+    LRAM_REQUIRE(any, w + ": every length is 0 (no env slot has a context)");
+    LRAM_REQUIRE(c.d_model % 4 == 0, w + ": per-env lengths need d_model to be a multiple of 4 (the chunk front end moves float4)");
+    LRAM_REQUIRE(e->compat_repeat <= 1, w + ": the Mamba repeated-forward mode is on (lram_set_compat_mode, mamba_repeat > 1): its "
+                                            "trajectories advance the state once per action dim and take no per-env lengths");
+    LRAM_REQUIRE(!e->compat_stale, w + ": the Mamba stale_state mode is on (lram_set_compat_mode): a reset re-initialises layer 0 "
+                                       "only, so the padding ahead of a shorter context would leak into the other layers");
+    LRAM_REQUIRE(obs_is_embedding || (size_t)e->B * L * c.d_model <= ((size_t)1 << 29),
+                 w + ": the [batch, timesteps, d_model] state embeddings of the raw observations exceed 2 GiB");
+  }
+  bool dense() const {
+    for (int b = 0; b < e->B; ++b)
+      if (lengths[b] != L) return false;
+    return true;
+  }
+
+  template <typename Launch>
+  void run(const uint8_t* reset, hipStream_t s, Launch&& launch) {
+    const int B = e->B;
+    // scratch for the kept slots' records: refused, with nothing launched, when it would leave less than 2 GiB free
+    const size_t rec = (size_t)(lram_state_bytes_per_env(e) / 4), need = kept.size() * rec;
+    if (e->KEEP.n < need) {
+      LRAM_HIP_CHECK(hipDeviceSynchronize());
+      size_t free_b = 0, total_b = 0;
+      LRAM_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+      LRAM_REQUIRE(need * sizeof(float) + ((size_t)2 << 30) <= free_b + e->KEEP.n * sizeof(float),
+                   w + ": the records of the " + std::to_string(kept.size()) + " slots of length 0 (" +
+                       std::to_string(need * sizeof(float)) + " bytes) would leave less than 2 GiB of device memory free");
+      e->KEEP.alloc(need);
+    }
+    ContextPlan plan;
+    plan.starts = context_plan(L, L > 1 ? prefill_chunk_steps(e, L) : 1, lengths, B, w.c_str());
+    const int n_chunks = (int)plan.starts.size();
+    // CTX: int32 start[B] | int32 chunk_start[L] | uint8 masks[L, B], as floats of one allocation
+    const size_t want = (size_t)B + L + ((size_t)L * B + 3) / 4;
+    if (e->CTX.n < want) {
+      LRAM_HIP_CHECK(hipDeviceSynchronize());
+      e->CTX.alloc(want);
+    }
+    int32_t* dev_start = reinterpret_cast<int32_t*>(e->CTX.p);
+    int32_t* dev_chunk = dev_start + B;
+    uint8_t* dev_masks = reinterpret_cast<uint8_t*>(dev_chunk + L);
+    plan.dev_start = dev_start, plan.dev_masks = dev_masks;
+    std::vector<int32_t> host(B + n_chunks);
+    plan.has_reset.assign(n_chunks, 0);
+    for (int b = 0; b < B; ++b) {
+      const int sb = L - lengths[b];
+      host[b] = sb;
+      if (sb == 0 && reset != nullptr) plan.has_reset[0] = 1;
+      if (sb > 0 && sb < L)
+        plan.has_reset[std::lower_bound(plan.starts.begin(), plan.starts.end(), sb) - plan.starts.begin()] = 1;
+    }
+    for (int ci = 0; ci < n_chunks; ++ci) host[B + ci] = plan.starts[ci];
+    // ---- from here on the call launches ----
+    lazy_materialize(e, s);   // stored contexts fold pending windows first (and complete a tail fold)
+    if (!kept.empty()) save_slot_records(e, kept.data(), (int)kept.size(), e->KEEP.p, s);
+    // (pageable host memory: the copies have read `host` when they return; the device side is ordered on `s`)
+    LRAM_HIP_CHECK(hipMemcpyAsync(dev_start, host.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    LRAM_HIP_CHECK(hipMemcpyAsync(dev_chunk, host.data() + B, (size_t)n_chunks * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    launch_context_masks(dev_masks, dev_start, dev_chunk, reset, n_chunks, B, L, s);
+    {
+      // every chunk on the materialised kernels, also the chunks of one timestep that an env-step would take through the lazy
+      // read pass: a window left pending by a chunk in the middle of the call would be invisible to the chunk behind it
+      struct LazyOff {
+        lram_engine* e;
+        bool was;
+        ~LazyOff() { e->lazy = was; }
+      } lazy_off{e, e->lazy};
+      e->lazy = false;
+      launch(plan);
+    }
+    if (!kept.empty()) load_slot_records(e, kept.data(), (int)kept.size(), e->KEEP.p, s);
+  }
+};
 }  // namespace
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------
@@ -550,27 +736,79 @@ int32_t lram_score(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embe
     step_entry(e, "lram_score");
     LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_score: null device pointer");
     LRAM_REQUIRE(timesteps >= 1, "lram_score: timesteps must be >= 1");
-    // refusals: before anything is launched, the recurrent state untouched
-    LRAM_REQUIRE(e->compat_repeat <= 1, "lram_score: the Mamba repeated-forward mode is on (lram_set_compat_mode, mamba_repeat > 1): "
-                                        "its trajectories advance the state once per action dim and are not scored");
-    LRAM_REQUIRE(!(dev_target_actions && dev_target_tokens),
-                 "lram_score: both dev_target_actions and dev_target_tokens are given (at most one)");
-    LRAM_REQUIRE(dev_actions || dev_tokens || dev_logp || dev_logits, "lram_score: no output is given");
-    LRAM_REQUIRE(!dev_logp || dev_target_actions || dev_target_tokens,
-                 "lram_score: dev_logp needs a target (dev_target_actions or dev_target_tokens)");
-    LRAM_REQUIRE(over == 0 || over == 1, "lram_score: over must be 0 (the whole vocabulary) or 1 (the selectable range)");
-    LRAM_REQUIRE(temperature > 0.0 && temperature < (double)INFINITY, "lram_score: temperature must be finite and > 0");
-    LRAM_REQUIRE(discrete == 0 || discrete == 1 || discrete == LRAM_HEAD_PER_SLOT, "lram_score: discrete must be 0, 1 or LRAM_HEAD_PER_SLOT");
-    LRAM_REQUIRE(discrete != LRAM_HEAD_PER_SLOT || e->slot_table, "lram_score: LRAM_HEAD_PER_SLOT needs a slot table (lram_set_slot_table)");
-    LRAM_REQUIRE(discrete != 1 || e->cfg.n_discrete >= 1, "lram_score: a discrete head needs n_discrete >= 1");
-    ScoreSink sink;
-    sink.actions = dev_actions, sink.tokens = dev_tokens, sink.logp = dev_logp, sink.logits = dev_logits;
-    sink.target_actions = dev_target_actions, sink.target_tokens = dev_target_tokens, sink.valid = dev_valid;
-    sink.over = over, sink.temperature = temperature;
+    const ScoreSink sink = score_sink_checked(e, "lram_score", discrete, dev_target_actions, dev_target_tokens, dev_valid, over,
+                                              temperature, dev_actions, dev_tokens, dev_logp, dev_logits);
     lazy_finish_prefold(e, static_cast<hipStream_t>(stream));   // (only an env-step takes a tail fold over)
     // (never captured, never a draw: the sampling mode and its counter are left alone)
     timesteps_launches(e, Pass{}, Inputs{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps}, dev_reset_mask,
                        discrete, nullptr, nullptr, static_cast<hipStream_t>(stream), &sink);
+  });
+}
+
+int32_t lram_prefill_ragged(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
+                            const float* dev_reward_seq, int32_t timesteps, const int32_t* host_lengths,
+                            const uint8_t* dev_reset_mask, int32_t discrete, float* dev_actions, int32_t* dev_tokens, void* stream) {
+  return guarded([&] {
+    step_entry(e, "lram_prefill_ragged");
+    LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_prefill_ragged: null device pointer");
+    LRAM_REQUIRE(timesteps >= 1, "lram_prefill_ragged: timesteps must be >= 1");
+    RaggedCall rc{e, "lram_prefill_ragged", timesteps, host_lengths, {}};
+    rc.check(obs_is_embedding);
+    if (dev_actions != nullptr) check_head_mode(e, discrete, "lram_prefill_ragged");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Inputs in{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps};
+    if (rc.dense()) {            // every context of full length: lram_prefill's own launches
+      lazy_finish_prefold(e, s);   // (only an env-step takes a tail fold over)
+      timesteps_launches(e, Pass{}, in, dev_reset_mask, discrete, dev_actions, dev_tokens, s);
+    } else {
+      rc.run(dev_reset_mask, s, [&](const ContextPlan& plan) {
+        timesteps_launches(e, Pass{}, in, nullptr, discrete, dev_actions, dev_tokens, s, nullptr, &plan);
+        if (dev_actions != nullptr)   // slots without a context: 0 / -1 in place of the head's answer to the padding
+          launch_action_fill_kept(dev_actions, dev_tokens, plan.dev_start, e->B, timesteps, e->cfg.act_dim, s);
+      });
+    }
+    if (dev_actions != nullptr) sample_draw_advance(e, s);
+  });
+}
+
+int32_t lram_score_ragged(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
+                          const float* dev_reward_seq, int32_t timesteps, const int32_t* host_lengths,
+                          const uint8_t* dev_reset_mask, int32_t discrete, const float* dev_target_actions,
+                          const int32_t* dev_target_tokens, const uint8_t* dev_valid, int32_t over, double temperature,
+                          float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits, void* stream) {
+  return guarded([&] {
+    step_entry(e, "lram_score_ragged");
+    LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_score_ragged: null device pointer");
+    LRAM_REQUIRE(timesteps >= 1, "lram_score_ragged: timesteps must be >= 1");
+    RaggedCall rc{e, "lram_score_ragged", timesteps, host_lengths, {}};
+    rc.check(obs_is_embedding);
+    const ScoreSink sink = score_sink_checked(e, "lram_score_ragged", discrete, dev_target_actions, dev_target_tokens, dev_valid, over,
+                                              temperature, dev_actions, dev_tokens, dev_logp, dev_logits);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Inputs in{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps};
+    if (rc.dense()) {            // every context of full length: lram_score's own launches
+      lazy_finish_prefold(e, s);   // (only an env-step takes a tail fold over)
+      timesteps_launches(e, Pass{}, in, dev_reset_mask, discrete, nullptr, nullptr, s, &sink);
+      return;
+    }
+    rc.run(dev_reset_mask, s, [&](const ContextPlan& plan) {
+      // the call-timesteps ahead of the first chunk are padding for every env: their rows take the fill values here
+      launch_score_fill_ragged(dev_actions, dev_tokens, dev_logp, plan.dev_start, e->B, timesteps, plan.starts[0], e->cfg.act_dim, s);
+      timesteps_launches(e, Pass{}, in, nullptr, discrete, nullptr, nullptr, s, &sink, &plan);
+    });
+  });
+}
+
+int32_t lram_context_plan(int32_t timesteps, int32_t cap, const int32_t* host_lengths, int32_t batch, int32_t* out_starts,
+                          int32_t max_chunks, int32_t* out_n) {
+  return guarded([&] {
+    LRAM_REQUIRE(out_n != nullptr, "lram_context_plan: out_n is NULL");
+    const std::vector<int> starts = context_plan(timesteps, cap, host_lengths, batch, "lram_context_plan");
+    *out_n = (int32_t)starts.size();
+    LRAM_REQUIRE(out_starts != nullptr && (int64_t)starts.size() <= max_chunks,
+                 "lram_context_plan: the plan has " + std::to_string(starts.size()) + " chunks, out_starts holds " +
+                     std::to_string(max_chunks));
+    std::copy(starts.begin(), starts.end(), out_starts);
   });
 }
 

@@ -40,22 +40,51 @@ __device__ __forceinline__ double scaled_minus(double t, float x, double zmax) {
   return z - zmax;
 }
 
+// The wave's item: (row r of the launch, action dim j); its env and the row `orow` of the outputs, targets and `valid`.
+struct ScoreItem {
+  bool in_grid;
+  int64_t r, env, orow;
+  int j;
+  bool pad;   // a padded timestep of a per-env-length call: the fill values, nothing read
+};
+
+__device__ __forceinline__ ScoreItem score_item(const ScoreArgs& a) {
+  ScoreItem it;
+  const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  it.in_grid = item < a.rows * a.act_dim;
+  it.r = it.in_grid ? item / a.act_dim : 0;
+  it.j = it.in_grid ? (int)(item - it.r * a.act_dim) : 0;
+  const int64_t g = a.row0 + it.r;
+  it.env = g / a.inner;
+  it.orow = it.env * a.outer + a.off + (g - it.env * a.inner);
+  it.pad = false;
+  return it;
+}
+
+// The same with the contexts END-aligned inside the call (ScoreArgs::start): row g is call-timestep t of its env; its outputs go
+// to the left-aligned row t - start[env], those of a padded timestep (t < start[env]) as fill values to row n_env + t.  Over the
+// call-timesteps 0 .. outer - 1 of an env this is a bijection onto its rows.
+__device__ __forceinline__ ScoreItem score_item_ragged(const ScoreArgs& a) {
+  ScoreItem it = score_item(a);
+  const int64_t t = it.orow - it.env * a.outer;
+  const int64_t s = it.in_grid ? (int64_t)a.start[it.env] : 0;
+  it.pad = it.in_grid && t < s;
+  it.orow = it.env * a.outer + (it.pad ? (a.outer - s) + t : t - s);
+  return it;
+}
+
 // PER floats per lane in the wave's LDS strip; PER = 0: no strip, the row stays in global memory.
 template <int PER>
-__global__ __launch_bounds__(256) void action_score_kernel(ScoreArgs a) {
-  __shared__ float stage[4][64 * (PER > 0 ? PER : 1)];
+__device__ __forceinline__ void score_row(const ScoreArgs& a, const ScoreItem& it, float (*stage)[64 * (PER > 0 ? PER : 1)]) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t item = (int64_t)blockIdx.x * 4 + wv;
-  const bool in_grid = item < a.rows * a.act_dim;
-  const int64_t r = in_grid ? item / a.act_dim : 0;
-  const int j = in_grid ? (int)(item - r * a.act_dim) : 0;
-  const int64_t g = a.row0 + r, env = g / a.inner;
-  const int64_t orow = env * a.outer + a.off + (g - env * a.inner);   // the row of the outputs, targets and `valid`
+  const bool in_grid = it.in_grid;
+  const int64_t r = it.r, env = it.env, orow = it.orow;
+  const int j = it.j;
   const int64_t o = orow * a.act_dim + j;
   int discrete = a.discrete;
   bool fill = false;
   if (in_grid) {  // (every condition below is the same for the whole wave)
-    if (a.valid != nullptr && a.valid[orow] == 0) {
+    if (it.pad || (a.valid != nullptr && a.valid[orow] == 0)) {
       fill = true;
     } else if (a.slot_flags != nullptr) {
       discrete = a.slot_flags[env] & 1;
@@ -164,6 +193,19 @@ __global__ __launch_bounds__(256) void action_score_kernel(ScoreArgs a) {
   }
 }
 
+template <int PER>
+__global__ __launch_bounds__(256) void action_score_kernel(ScoreArgs a) {
+  __shared__ float stage[4][64 * (PER > 0 ? PER : 1)];
+  score_row<PER>(a, score_item(a), stage);
+}
+
+// Ragged score sink (lram_score_ragged): the row code above, the rows placed by score_item_ragged.
+template <int PER>
+__global__ __launch_bounds__(256) void action_score_ragged_kernel(ScoreArgs a) {
+  __shared__ float stage[4][64 * (PER > 0 ? PER : 1)];
+  score_row<PER>(a, score_item_ragged(a), stage);
+}
+
 }  // namespace
 
 void launch_action_score(const ScoreArgs& a, hipStream_t stream) {
@@ -184,7 +226,13 @@ void launch_action_score(const ScoreArgs& a, hipStream_t stream) {
   const int64_t items = a.rows * a.act_dim;
   LRAM_REQUIRE(items <= ((int64_t)1 << 32), "action score: rows * act_dim must be <= 2^32");
   const dim3 grid((unsigned)((items + 3) / 4)), block(256);
-#define LRAM_SCORE_LAUNCH(PER) hipLaunchKernelGGL(action_score_kernel<PER>, grid, block, 0, stream, a)
+#define LRAM_SCORE_LAUNCH(PER)                                                              \
+  do {                                                                                      \
+    if (a.start != nullptr)                                                                 \
+      hipLaunchKernelGGL(action_score_ragged_kernel<PER>, grid, block, 0, stream, a);       \
+    else                                                                                    \
+      hipLaunchKernelGGL(action_score_kernel<PER>, grid, block, 0, stream, a);              \
+  } while (0)
   if (a.n_vocab <= 64)
     LRAM_SCORE_LAUNCH(1);
   else if (a.n_vocab <= 320)

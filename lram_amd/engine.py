@@ -57,6 +57,12 @@ _SYMBOLS = {
                                       _VP]),
     "lram_score": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP, ctypes.c_int32, _VP, ctypes.c_int32, _VP, _VP, _VP,
                                     ctypes.c_int32, ctypes.c_double, _VP, _VP, _VP, _VP, _VP]),
+    "lram_prefill_ragged": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP, ctypes.c_int32, _VP, _VP, ctypes.c_int32, _VP,
+                                             _VP, _VP]),
+    "lram_score_ragged": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP, ctypes.c_int32, _VP, _VP, ctypes.c_int32, _VP, _VP,
+                                           _VP, ctypes.c_int32, ctypes.c_double, _VP, _VP, _VP, _VP, _VP]),
+    "lram_context_plan": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, _VP, ctypes.c_int32, _VP, ctypes.c_int32,
+                                           ctypes.POINTER(ctypes.c_int32)]),
     "lram_score_last": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, ctypes.c_double, _VP, _VP]),
     "lram_score_tokens": (ctypes.c_int32, [_VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                            ctypes.c_float, ctypes.c_float, ctypes.c_int32, _VP, _VP, _VP, ctypes.c_int32,
@@ -283,6 +289,49 @@ def _i32_array(values):
     return (ctypes.c_int32 * max(1, len(values)))(*values)
 
 
+def check_context_lengths(lengths, batch: int, L: int):
+    """The length rules of lram_prefill_ragged / lram_score_ragged, checked on the host (no GPU needed): `batch` integer
+    entries (a list, a numpy array or an integer tensor, moved to the host), each in 0 .. L, not all 0.  Returns them as ints;
+    raises ValueError."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
+            raise ValueError(f"lengths: expected integer lengths, got {lengths.dtype}")
+        lengths = lengths.reshape(-1).tolist()
+    out = []
+    for v in lengths:
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"lengths: expected integer lengths, got {v!r}")
+        out.append(int(v))
+    if len(out) != batch:
+        raise ValueError(f"lengths: expected {batch} entries (one per env slot), got {len(out)}")
+    for b, v in enumerate(out):
+        if not 0 <= v <= L:
+            raise ValueError(f"lengths: length {v} of env slot {b} is outside 0 .. {L}")
+    if not any(out):
+        raise ValueError("lengths: every length is 0 (no env slot has a context)")
+    return out
+
+
+def context_plan(L: int, lengths, cap: int):
+    """Mirror of lram_context_plan: the ascending call-timesteps at which the chunks of a call of L timesteps over contexts of
+    per-env length start.  The contexts are end-aligned inside the call (env b starts at s_b = L - lengths[b]); the plan begins
+    at the smallest s_b over envs with a context, holds every distinct s_b, and cuts each stretch between two of them into
+    equal chunks of at most `cap` timesteps.  Where no env starts inside the call the plan is the dense call's: chunks of
+    `cap` from 0 on."""
+    lengths = check_context_lengths(lengths, len(lengths), L)
+    if cap < 1:
+        raise ValueError("cap must be >= 1")
+    bounds = sorted({L - n for n in lengths if n > 0})
+    if bounds == [0]:
+        return list(range(0, L, cap))
+    bounds.append(L)
+    starts = []
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
+        n = -(-(hi - lo) // cap)
+        starts.extend(range(lo, hi, -(-(hi - lo) // n)))
+    return starts
+
+
 class Engine:
     """One engine per GPU: weights + per-env recurrent state resident in HBM, one batched env-step per call.
 
@@ -448,9 +497,13 @@ class Engine:
 
     def prefill(self, obs_seq: torch.Tensor, rtg_seq: torch.Tensor, reward_seq: torch.Tensor,
                 reset_mask: Optional[torch.Tensor] = None, discrete=False, obs_is_embedding: bool = False,
-                want_action: bool = True):
+                want_action: bool = True, lengths=None):
         """L stored timesteps in one call ([B, L, state_dim], [B, L], [B, L]); == L sequential step() calls.
-        Returns (actions, tokens) of the last timestep (None when want_action is False)."""
+        Returns (actions, tokens) of the last timestep (None when want_action is False).
+        `lengths` (list / array / integer tensor of B entries, moved to the host; lram_prefill_ragged): env b's context is rows
+        [b, :lengths[b]] (left-aligned; the rows behind it are ignored), its state afterwards is that of its own context and its
+        action the one at its own last timestep.  A length below L replaces the slot's state (the slot is reset first whatever
+        `reset_mask` says); length L behaves as without lengths; length 0 leaves the slot alone (action 0, token -1)."""
         B, spec = self.batch, self.spec
         L = obs_seq.shape[1]
         _chk_dev(obs_seq, torch.float32, (B, L, spec.d_model if obs_is_embedding else spec.state_dim), self.device,
@@ -461,6 +514,12 @@ class Engine:
             _chk_dev(reset_mask, torch.uint8, (B,), self.device, "reset_mask")
         act = self._actions if want_action else None
         tok = self._tokens if want_action else None
+        if lengths is not None:
+            n = _i32_array(check_context_lengths(lengths, B, L))
+            _check(self.lib, self.lib.lram_prefill_ragged(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq),
+                                                          _ptr(reward_seq), int(L), n, _ptr(reset_mask), _head_mode(discrete),
+                                                          _ptr(act), _ptr(tok), _stream_ptr(self.device)))
+            return (act, tok) if want_action else (None, None)
         _check(self.lib, self.lib.lram_prefill(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq),
                                                _ptr(reward_seq), int(L), _ptr(reset_mask), _head_mode(discrete), _ptr(act),
                                                _ptr(tok), _stream_ptr(self.device)))
@@ -470,14 +529,16 @@ class Engine:
               actions: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None,
               valid: Optional[torch.Tensor] = None, reset_mask: Optional[torch.Tensor] = None, discrete=False,
               over: str = "vocab", temperature: float = 1.0, want=("actions", "tokens", "logp"), logits: bool = False,
-              obs_is_embedding: bool = False) -> ScoreResult:
+              obs_is_embedding: bool = False, lengths=None) -> ScoreResult:
         """Score L stored timesteps in one call (lram_score): prefill() with the action head at EVERY timestep -- the
         reference's no-cache forward plus the loss it takes from the logits (universal_decision_transformer_sb3.py:398-434).
         `actions` float32 [B, L, act_dim] (recorded actions, tokenised on the device) or `tokens` int32 [B, L, act_dim] are the
         targets of `logp`; `valid` uint8 / bool [B, L] masks outputs only (the state advances through every timestep);
         over="vocab" normalises over all n_vocab logits (the reference's cross-entropy), "selectable" over the range the head
         picks from; `temperature` multiplies the logits.  `want` names the outputs among "actions", "tokens", "logp";
-        logits=True adds the raw logits.  The state afterwards equals prefill()'s; nothing is drawn in sampling mode."""
+        logits=True adds the raw logits.  The state afterwards equals prefill()'s; nothing is drawn in sampling mode.
+        `lengths` as in prefill() (lram_score_ragged): rows [b, l] with l >= lengths[b] are masked, and the state afterwards is
+        that of every env's own context."""
         B, spec = self.batch, self.spec
         if obs_seq.dim() != 3:
             raise ValueError("obs_seq must be [B, L, state_dim]")
@@ -507,6 +568,14 @@ class Engine:
             tokens=torch.zeros(B, L, A, dtype=torch.int32, device=self.device) if "tokens" in want else None,
             logp=torch.zeros(B, L, A, dtype=torch.float32, device=self.device) if "logp" in want else None,
             logits=torch.zeros(B, L, A, spec.n_vocab, dtype=torch.float32, device=self.device) if logits else None)
+        if lengths is not None:
+            n = _i32_array(check_context_lengths(lengths, B, L))
+            _check(self.lib, self.lib.lram_score_ragged(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq),
+                                                        _ptr(reward_seq), int(L), n, _ptr(reset_mask), _head_mode(discrete),
+                                                        _ptr(actions), _ptr(tokens), _ptr(valid), _over_mode(over),
+                                                        float(temperature), _ptr(res.actions), _ptr(res.tokens), _ptr(res.logp),
+                                                        _ptr(res.logits), _stream_ptr(self.device)))
+            return res
         _check(self.lib, self.lib.lram_score(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq), _ptr(reward_seq),
                                              int(L), _ptr(reset_mask), _head_mode(discrete), _ptr(actions), _ptr(tokens),
                                              _ptr(valid), _over_mode(over), float(temperature), _ptr(res.actions),
