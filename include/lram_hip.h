@@ -70,7 +70,9 @@ typedef struct lram_config {
   int32_t n_discrete;       /* 18, also the tokenizer shift */
   int32_t action_channels;  /* 256 */
   float   tok_min;          /* -1 */
-  float   tok_max;          /* +1 */
+  float   tok_max;          /* +1: the bin width is formed in fp32 from the two fp32 bounds, (tok_max - tok_min) / action_channels;
+                               for bounds that fp32 does not hold exactly it can differ by an ulp from the reference's double division.
+                               De-tokenisation rounds twice, as MinMaxTokenizer.inv_tokenize: fp32(fp32(t * bin_width) + tok_min) */
 } lram_config;
 
 typedef struct lram_engine lram_engine; /* opaque */
@@ -124,7 +126,7 @@ int32_t lram_reset(lram_engine* e, const uint8_t* dev_env_mask, void* stream);
  *   dev_reward     device float[batch]             reward token (0 in the reference loop)
  *   dev_reset_mask device uint8[batch] or NULL     slots to reset before this step
  *   discrete       0: continuous head (argmax over n_vocab per action dim, de-tokenised to fp32)
- *                  1: discrete head (argmax over the first n_discrete logits of action dim 0)
+ *                  1: discrete head (argmax over the first n_discrete logits of action dim 0); refused when n_discrete == 0
  *                  LRAM_HEAD_PER_SLOT: the head mode and the action dims in use of every slot come from the slot table
  *                  (lram_set_slot_table); the observation kind stays the call's own
  *   dev_actions    device float[batch, act_dim]    out; discrete: column 0 holds the action index

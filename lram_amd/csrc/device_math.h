@@ -20,6 +20,16 @@ __device__ __forceinline__ bool argmax_beats(float v, int i, float best, int bi)
   return !best_nan && (v > best || (v == best && i < bi));
 }
 
+// MinMaxTokenizer.inv_tokenize (src/tokenizers_custom/minmax_tokenizer.py:31-47) on a bin index t >= 0: float(t) * bin_width is
+// rounded to fp32 BEFORE min_val is added -- two roundings, as the reference's two tensor operations.  The compiler contracts
+// a * b + c into one FMA by default (and __fmul_rn / __fadd_rn are plain operators to it), which is 1 ulp off on more than half
+// of the tokens wherever the bin width is no power of two; contraction is switched off for this function alone.
+__device__ __forceinline__ float inv_tokenize_bin(int t, float bin_width, float tok_min) {
+#pragma clang fp contract(off)
+  const float scaled = (float)t * bin_width;
+  return scaled + tok_min;
+}
+
 // torch.nn.functional.logsigmoid: min(x, 0) - log1p(exp(-|x|))
 __device__ __forceinline__ float log_sigmoid(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
 

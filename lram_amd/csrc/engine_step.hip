@@ -423,6 +423,8 @@ void check_sample_slots(const lram_engine* e, int discrete, const std::string& w
 // discrete = LRAM_HEAD_PER_SLOT: what the call needs, checked before anything is launched (the recurrent state is untouched
 // by a refused call).
 void check_head_mode(const lram_engine* e, int discrete, const char* who) {
+  // (n_discrete = 0 is a legal geometry -- the reference's dmcontrol head -- but an argmax over no logits is no action)
+  LRAM_REQUIRE(discrete != 1 || e->cfg.n_discrete >= 1, std::string(who) + ": a discrete head needs n_discrete >= 1");
   check_sample_slots(e, discrete, who);
   if (discrete != LRAM_HEAD_PER_SLOT) return;
   const std::string w(who);

@@ -270,7 +270,7 @@ __global__ __launch_bounds__(256) void action_argmax_kernel(const float* logits,
       int t = bi - n_discrete;
       t = t < 0 ? 0 : t;
       const float bin_width = (tok_max - tok_min) / (float)action_channels;
-      out = (float)t * bin_width + tok_min;
+      out = inv_tokenize_bin(t, bin_width, tok_min);  // two roundings, as the reference: no FMA
     }
     actions[(int64_t)b * act_dim + j] = out;
   }

@@ -326,7 +326,7 @@ __device__ __forceinline__ void action_sample_body(float (&stage)[4][64 * PER], 
       int t = tok - n_discrete;
       t = t < 0 ? 0 : t;
       const float bin_width = (tok_max - tok_min) / (float)action_channels;
-      out = (float)t * bin_width + tok_min;
+      out = inv_tokenize_bin(t, bin_width, tok_min);  // two roundings, as the reference: no FMA
     }
     actions[(int64_t)b * act_dim + j] = out;
   }

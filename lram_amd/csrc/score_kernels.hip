@@ -151,7 +151,7 @@ __device__ __forceinline__ void score_row(const ScoreArgs& a, const ScoreItem& i
         int t = bi - a.n_discrete;
         t = t < 0 ? 0 : t;
         const float bin_width = (a.tok_max - a.tok_min) / (float)a.action_channels;
-        out = (float)t * bin_width + a.tok_min;
+        out = inv_tokenize_bin(t, bin_width, a.tok_min);  // two roundings, as the reference: no FMA
       }
       a.actions[o] = out;
     }

@@ -105,7 +105,8 @@ class OraclePolicy:
     """Batched CPU oracle of one env-step of `agent.predict` with `use_inference_cache=True`.
 
     step(obs, rtg, reward, reset_mask) == for every env independently: (reset its cache if masked,)
-    embed (s, rtg, r), run the 3 tokens through the recurrent stack, read the action at the rtg token.
+    embed (s, rtg, r), run the 3 tokens through the recurrent stack, read the action at token `spec.pred_token` (the rtg token, 1, in every
+    configuration of the reference).
     """
 
     def __init__(self, spec, sd, state_mean=None, state_std=None, mamba_repeat=1, stale_state=False):
@@ -152,7 +153,7 @@ class OraclePolicy:
                 hidden, self.state = mamba_ref.encoder_forward_cached(spec, sd, x, self.state)
             else:
                 hidden, self.state = xlstm_ref.encoder_forward_cached(spec, sd, x, self.state)
-            act_p, logits_p = action_head(spec, sd, hidden[:, 1], discrete)
+            act_p, logits_p = action_head(spec, sd, hidden[:, spec.pred_token], discrete)
             if p == 0:
                 act, logits = act_p.clone(), logits_p.clone()
             else:  # action dim i comes from forward i (columns beyond the last forward follow it)

@@ -751,9 +751,42 @@ def xlstm_model_trace():
             "tok_to_pos": {k: (v if isinstance(v, int) else list(v)) for k, v in model.tok_to_pos.items()}, "envs": out_envs}
 
 
+def minmax_tokenizer_vectors():
+    """MinMaxTokenizer (src/tokenizers_custom/minmax_tokenizer.py:14-47), executed for channel counts whose bin width is no
+    power of two as well (64, 100, 255, 256, 495 channels; shifts 0 / 7 / 18; range [-1, 1]): `inv_tokenize` of EVERY token
+    0 .. channels + shift - 1, and `tokenize` of every bin edge k * bin_width - 1 with one fp32 ulp to either side, the ends of
+    the range, values beyond them and 200 random values.  Data only, to tests/golden/minmax_tokenizer_reference.npz; the CPU
+    oracle is held to it bit for bit (tests/test_oracle_golden.py), and the engine's head kernels to the oracle."""
+    import numpy as np
+    from src.tokenizers_custom import make_tokenizer
+    arrays = {"channels": [], "shift": []}
+    g = torch.Generator().manual_seed(495)
+    i = 0
+    for channels in (64, 100, 255, 256, 495):
+        for shift in (0, 7, 18):
+            tok = make_tokenizer("minmax", {"vocab_size": channels, "shift": shift})
+            edges = torch.arange(channels + 1, dtype=torch.float32) * (2.0 / channels) - 1.0
+            up = torch.nextafter(edges, torch.full_like(edges, 2.0))
+            down = torch.nextafter(edges, torch.full_like(edges, -2.0))
+            extra = torch.tensor([-1.0, 1.0, 1.5, 3e9, -1.5, -3e9, 0.0, -0.0, 0.999999, -0.999999])
+            x = torch.cat([edges, up, down, extra, torch.rand(200, generator=g) * 2 - 1]).reshape(1, -1)
+            all_tokens = torch.arange(0, channels + shift).reshape(1, -1)
+            arrays["channels"].append(channels), arrays["shift"].append(shift)
+            arrays[f"x_{i}"] = x.reshape(-1).numpy().copy()
+            arrays[f"tokens_{i}"] = tok.tokenize(x.clone()).reshape(-1).numpy().astype(np.int64)
+            arrays[f"inv_{i}"] = tok.inv_tokenize(all_tokens.clone()).reshape(-1).numpy().astype(np.float32)
+            i += 1
+    arrays["channels"], arrays["shift"] = np.asarray(arrays["channels"]), np.asarray(arrays["shift"])
+    np.savez_compressed(os.path.join(HERE, "minmax_tokenizer_reference.npz"), **arrays)
+    print("wrote", os.path.join(HERE, "minmax_tokenizer_reference.npz"))
+
+
 def main():
     sys.path.insert(0, REF)
     from src.tokenizers_custom import make_tokenizer  # reference code, executed not copied
+    minmax_tokenizer_vectors()
+    if "--tokenizer-only" in sys.argv:   # only minmax_tokenizer_reference.npz: needs torch and the tokenizer package alone
+        return
     out = {"generator": "tests/golden/make_golden_from_reference.py", "reference": "ml-jku/LRAM @ 2024-11-01"}
 
     tok = make_tokenizer("minmax", {"vocab_size": 256, "shift": 18})

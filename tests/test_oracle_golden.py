@@ -35,6 +35,33 @@ def test_minmax_tokenizer_matches_reference(ref_vectors):
     assert t.tolist() == [18, 18, 146, 210, 273, 273]
 
 
+def test_minmax_tokenizer_matches_reference_at_every_channel_count_bit_for_bit():
+    """64 / 100 / 255 / 256 / 495 channels x shifts 0 / 7 / 18 (tests/golden/minmax_tokenizer_reference.npz, recorded from the
+    reference's MinMaxTokenizer): inv_tokenize of every token and tokenize of every bin edge, its fp32 neighbours and 200 random
+    values.  Where the bin width is no power of two, float(t) * bin_width rounds before min_val is added: the oracle has to
+    round twice too, and the engine's head kernels are held to the oracle bit for bit (tests/test_gpu_head_geometry.py)."""
+    g = np.load(os.path.join(GOLD, "minmax_tokenizer_reference.npz"))
+    assert sorted(set(g["channels"].tolist())) == [64, 100, 255, 256, 495] and sorted(set(g["shift"].tolist())) == [0, 7, 18]
+    inexact = 0
+    for i, (channels, shift) in enumerate(zip(g["channels"].tolist(), g["shift"].tolist())):
+        want_inv = torch.from_numpy(g[f"inv_{i}"])
+        assert want_inv.numel() == channels + shift
+        inv = dt_ref.minmax_inv_tokenize(torch.arange(channels + shift), channels, shift)
+        assert inv.dtype == torch.float32 and torch.equal(inv.view(torch.int32), want_inv.view(torch.int32)), (channels, shift)
+        x = torch.from_numpy(g[f"x_{i}"])
+        assert x.numel() == 3 * (channels + 1) + 210
+        tok = dt_ref.minmax_tokenize(x, channels, shift)
+        assert torch.equal(tok, torch.from_numpy(g[f"tokens_{i}"])), (channels, shift)
+        # (what a single rounding of the exact t * (2 / channels) - 1 would give: it differs from the recorded table exactly
+        # where the bin width is no power of two -- the fixture can tell the two forms apart)
+        t = (torch.arange(channels + shift) - shift).clamp(min=0).double()
+        fused = (t * float(torch.tensor(2.0 / channels, dtype=torch.float32)) - 1.0).float()
+        differ = int((fused != want_inv).sum())
+        assert (differ == 0) == (channels & (channels - 1) == 0), (channels, differ)
+        inexact += differ
+    assert inexact > 0
+
+
 def test_rms_norm_matches_reference(ref_vectors):
     for case in ref_vectors["llama_rms_norm"]:
         x, w, y = torch.tensor(case["x"]), torch.tensor(case["weight"]), torch.tensor(case["y"])
