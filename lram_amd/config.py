@@ -337,6 +337,8 @@ def engine_limits(spec: ModelSpec) -> List[str]:
     why: List[str] = []
     if spec.d_model % 4 or spec.d_model > 2048:
         why.append(f"d_model {spec.d_model} must be a multiple of 4 and <= 2048")
+    if not 1 <= spec.n_blocks <= 64:   # LRAM_MAX_BLOCKS (include/lram_hip.h)
+        why.append(f"n_blocks {spec.n_blocks} must be in 1..64")
     if spec.state_dim % 4:
         why.append(f"state_dim {spec.state_dim} must be a multiple of 4")
     if spec.backbone == "xlstm":

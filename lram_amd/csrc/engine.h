@@ -479,7 +479,15 @@ void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* res
 void run_mamba_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* reset, const std::vector<Slice>& sl);
 
 // One mLSTM block's matrix memory over the batch, in bytes: what the lazy / side-stream-fold / two-slice thresholds compare.
+// (0 for a stack without an mLSTM block -- Mamba, or xLSTM with slstm_at = all: no threshold is met, and there is nothing to be lazy about.)
+inline bool has_mlstm_block(const lram_engine* e) {
+  if (e->cfg.backbone != LRAM_BACKBONE_XLSTM) return false;
+  for (int i = 0; i < e->cfg.n_blocks; ++i)
+    if (!e->cfg.block_is_slstm[i]) return true;
+  return false;
+}
 inline double mlstm_block_bytes(const lram_engine* e) {
+  if (!has_mlstm_block(e)) return 0.0;
   const double dh = (double)e->cfg.inner / e->cfg.n_heads;
   return (double)e->B * e->cfg.n_heads * dh * dh * 4.0;
 }

@@ -390,7 +390,7 @@ namespace {
 
 // ---- lazy matrix memory plumbing ------------------------------------------------------------------------
 bool lazy_geometry_ok(const lram_engine* e) {
-  return e->cfg.backbone == LRAM_BACKBONE_XLSTM && mlstm_lazy_supported(e->cfg.inner / e->cfg.n_heads, e->cfg.tokens_per_step);
+  return has_mlstm_block(e) && mlstm_lazy_supported(e->cfg.inner / e->cfg.n_heads, e->cfg.tokens_per_step);
 }
 
 // Segment and chunk tables of the per-slot state calls (common.h: SlotSeg).  Record layout = blocks in order, within a block
@@ -696,7 +696,7 @@ int32_t lram_set_state_mode(lram_engine* e, int32_t mode, int32_t fold_period) {
     LRAM_REQUIRE(fold_period == 0 || (fold_period >= 1 && fold_period * e->cfg.tokens_per_step + 4 <= kLazyWindow),
                  "lram_set_state_mode: fold_period out of range (the window holds 48 tokens)");
     LRAM_REQUIRE(mode != 1 || lazy_geometry_ok(e),
-                 "lram_set_state_mode: lazy matrix memory needs an xLSTM head dim that is a multiple of 128");
+                 "lram_set_state_mode: lazy matrix memory needs an xLSTM head dim that is a multiple of 128 and at least one mLSTM block");
     LRAM_HIP_CHECK(hipSetDevice(e->device));
     if (e->lazy_ready) {  // leave the current mode with a materialised state
       LRAM_HIP_CHECK(hipDeviceSynchronize());  // pending steps on non-blocking streams first (see lram_set_graph_mode)

@@ -219,6 +219,10 @@ def test_engine_limits_refuse_what_the_kernels_refuse():
         assert engine_limits(spec) == [f"Mamba d_state {d_state} must be 4, 8, 16, 32 or 64"], d_state
     for d_state in (4, 8, 16, 32, 64):
         assert engine_limits(ModelSpec(backbone="mamba", kind="MDDMamba", d_model=64, n_blocks=2, d_state=d_state)) == []
+    # the stack depth: 1 .. LRAM_MAX_BLOCKS = 64, both backbones
+    for kw in (dict(backbone="mamba", kind="MDDMamba", d_model=64), dict(backbone="xlstm", d_model=256)):
+        for n, ok in ((0, False), (1, True), (64, True), (65, False)):
+            assert engine_limits(ModelSpec(n_blocks=n, **kw)) == ([] if ok else [f"n_blocks {n} must be in 1..64"]), (kw, n)
     # dt_rank and expand stay free (dt_rank values that are no multiple of 4 take a plain fp32 dt_proj kernel)
     for kw in (dict(dt_rank=1), dict(dt_rank=7, expand=3, d_model=68), dict(dt_rank=129), dict(expand=1)):
         assert engine_limits(ModelSpec(backbone="mamba", kind="MDDMamba", n_blocks=2, **{"d_model": 64, **kw})) == []
