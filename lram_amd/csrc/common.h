@@ -5,6 +5,7 @@
 
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 namespace lram {
 
@@ -156,6 +157,16 @@ __device__ __forceinline__ void gemm_tile_of(const GemmArgs& g, int bid, int til
   tm = bid / tiles_n;
   tn = bid - tm * tiles_n;
 }
+// The GEMM kernels are templated on <HAS_BIAS, HAS_RES>: calls f(has_bias, has_res) with the launch's two as
+// std::integral_constant<bool, ...> (a generic lambda names its instance with decltype(has_bias)::value).
+template <typename F>
+inline void launch_bias_res(const GemmArgs& g, F&& f) {
+  const bool hb = g.bias != nullptr, hr = g.residual != nullptr;
+  if (hb && hr) f(std::true_type{}, std::true_type{});
+  else if (hb) f(std::true_type{}, std::false_type{});
+  else if (hr) f(std::false_type{}, std::true_type{});
+  else f(std::false_type{}, std::false_type{});
+}
 void launch_splitk_reduce(const GemmArgs& g, hipStream_t stream);  // C = sum_s ws[s] (+ bias) (+ residual)
 void launch_gemm_f32(const GemmArgs& g, hipStream_t stream);      // exact fp32 MFMA (k-ordered fma chain)
 bool gemm_small_m(const GemmArgs& g);                             // M <= 8: launch_gemm_f32 takes the GEMV path
@@ -169,6 +180,7 @@ bool gemm_f16x2_supported(const GemmArgs& g);
 void launch_gemm_f16x2(const GemmArgs& g, hipStream_t stream);    // fp32-accurate, 2 x f16 split operands, row-scaled
 bool gemm_f16x2p_supported(const GemmArgs& g);
 void launch_gemm_f16x2p(const GemmArgs& g, hipStream_t stream);   // the same with A pre-split too: DMA staging, MFMA-only loop
+int gemm_f16x2p_tile(const GemmArgs& g, int S);                   // tile height (64 / 128) of a launch of either, S = its K splits
 // narrow-output projection (N <= 96, K a multiple of 64; gemm_narrow.hip): exact fp32 MFMA, 16 rows per workgroup, W packed at upload
 bool gemm_narrow_shape(int n, int k);
 bool gemm_narrow_supported(const GemmArgs& g);

@@ -171,6 +171,13 @@ struct Scratch {
   Scratch& operator=(const Scratch&) = delete;
 };
 
+// The f16x2 entries' weight operand: splits g's contiguous [n, k] weight into `planes` (2 x split_f16x2_plane_elems(n, k), K-tile-
+// major) and inv[n], and points g at them.
+void entry_split_weight(GemmArgs& g, uint16_t* planes, float* inv, hipStream_t s) {
+  launch_split_f16x2(g.w, g.n, g.k, planes, inv, s);
+  g.w2 = planes, g.w2_plane = (int64_t)split_f16x2_plane_elems((size_t)g.n, (size_t)g.k), g.w2_kt = 32 * (int64_t)g.n, g.w_inv = inv;
+}
+
 }  // namespace
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------
@@ -234,10 +241,9 @@ int32_t lram_gemm_narrow_f16x2(const float* dev_a, int64_t lda, const float* dev
     const size_t numel = split_f16x2_plane_elems((size_t)n, (size_t)k);
     Scratch<uint16_t> planes(2 * numel);
     Scratch<float> scales((size_t)n + m);  // [n] inverse weight scales, then [m] row maxima of A
-    launch_split_f16x2(dev_w, n, k, planes.p, scales.p, s);
-    launch_row_amax(dev_a, lda, nullptr, 0, m, k, scales.p + n, s);
     GemmArgs g = entry_args(dev_a, lda, dev_w, ldw, dev_c, ldc, dev_bias, accumulate, m, n, k);
-    g.w2 = planes.p, g.w2_plane = (int64_t)numel, g.w2_kt = 32 * (int64_t)n, g.w_inv = scales.p;
+    entry_split_weight(g, planes.p, scales.p, s);
+    launch_row_amax(dev_a, lda, nullptr, 0, m, k, scales.p + n, s);
     g.a_amax = scales.p + n, g.amax_parts = 1;
     launch_gemm_narrow16(g, s);
     LRAM_HIP_CHECK(hipStreamSynchronize(s));
@@ -269,10 +275,10 @@ int32_t lram_gemm_f16x2(const float* dev_a, int64_t lda, const float* dev_w, int
     const size_t numel = split_f16x2_plane_elems((size_t)n, (size_t)k);  // (K-tile-major planes)
     Scratch<uint16_t> planes(2 * numel);
     Scratch<float> scales((size_t)n + m);  // [n] inverse weight scales, then [m] activation scales
-    launch_split_f16x2(dev_w, n, k, planes.p, scales.p, s);
-    launch_row_amax(dev_a, lda, nullptr, 0, m, k, scales.p + n, s);
     GemmArgs g = entry_args(dev_a, lda, dev_w, ldw, dev_c, ldc, dev_bias, accumulate, m, n, k);
-    g.w2 = planes.p, g.w2_plane = (int64_t)numel, g.w2_kt = 32 * (int64_t)n, g.w_inv = scales.p, g.a_amax = scales.p + n;
+    entry_split_weight(g, planes.p, scales.p, s);
+    launch_row_amax(dev_a, lda, nullptr, 0, m, k, scales.p + n, s);
+    g.a_amax = scales.p + n;
     launch_gemm_f16x2(g, s);
     LRAM_HIP_CHECK(hipStreamSynchronize(s));
   });
@@ -285,14 +291,13 @@ int32_t lram_gemm_f16x2_presplit(const float* dev_a, int64_t lda, const float* d
     LRAM_REQUIRE(ldw == k, "lram_gemm_f16x2_presplit: W must be contiguous [n, k]");
     LRAM_REQUIRE(k % 32 == 0 && k <= 3072, "lram_gemm_f16x2_presplit: k must be a multiple of 32, <= 3072");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t wn = (size_t)n * k, an = (size_t)m * k;
+    const size_t wn = (size_t)n * k, an = (size_t)m * k;   // (k a multiple of 32: the planes have no padding)
     Scratch<uint16_t> wp(2 * wn), ap(2 * an);
     Scratch<float> scales((size_t)n + m);  // [n] inverse weight scales, then [m] inverse activation scales
-    launch_split_f16x2(dev_w, n, k, wp.p, scales.p, s);
-    launch_row_split_f16x2(dev_a, lda, nullptr, 0, m, k, ap.p, 32 * (int64_t)m, (int64_t)an, scales.p + n, s);
     GemmArgs g = entry_args(dev_a, lda, dev_w, ldw, dev_c, ldc, dev_bias, accumulate, m, n, k);
+    entry_split_weight(g, wp.p, scales.p, s);
+    launch_row_split_f16x2(dev_a, lda, nullptr, 0, m, k, ap.p, 32 * (int64_t)m, (int64_t)an, scales.p + n, s);
     g.a = nullptr, g.lda = k;   // A goes in as its two planes
-    g.w2 = wp.p, g.w2_plane = (int64_t)wn, g.w2_kt = 32 * (int64_t)n, g.w_inv = scales.p;
     g.a2 = ap.p, g.a2_plane = (int64_t)an, g.a2_kt = 32 * (int64_t)m, g.a2_inv = scales.p + n;
     launch_gemm_f16x2p(g, s);
     LRAM_HIP_CHECK(hipStreamSynchronize(s));

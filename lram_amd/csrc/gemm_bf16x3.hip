@@ -243,16 +243,9 @@ bool gemm_bf16x3_supported(const GemmArgs& g) {
 
 template <int BM>
 static void launch_bm(const GemmArgs& g, dim3 grid, hipStream_t stream) {
-  const bool hb = g.bias != nullptr, hr = g.residual != nullptr;
-  dim3 block(256);
-  if (hb && hr)
-    hipLaunchKernelGGL((gemm_bf16x3_kernel<true, true, BM>), grid, block, 0, stream, g);
-  else if (hb)
-    hipLaunchKernelGGL((gemm_bf16x3_kernel<true, false, BM>), grid, block, 0, stream, g);
-  else if (hr)
-    hipLaunchKernelGGL((gemm_bf16x3_kernel<false, true, BM>), grid, block, 0, stream, g);
-  else
-    hipLaunchKernelGGL((gemm_bf16x3_kernel<false, false, BM>), grid, block, 0, stream, g);
+  launch_bias_res(g, [&](auto b, auto r) {
+    hipLaunchKernelGGL((gemm_bf16x3_kernel<decltype(b)::value, decltype(r)::value, BM>), grid, dim3(256), 0, stream, g);
+  });
 }
 
 void launch_gemm_bf16x3(const GemmArgs& g_in, hipStream_t stream) {

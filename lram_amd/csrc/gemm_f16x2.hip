@@ -20,18 +20,14 @@
 // W is split once when the weights are finalised (two [N,K] f16 planes + the per-row inverse scale); A is split on
 // the fly while its fp32 tile is staged into LDS; its per-row scale is derived from the row's largest magnitude, which
 // the kernel that produced A hands over (norm kernels: one wave per row; the Mamba conv / state-update kernels: one
-// partial maximum per wave, plain stores, reduced in this kernel's prologue via `amax_parts`) or `launch_row_amax` computes.  Scales are powers of two: un-scaling the accumulator is exact.
+// partial maximum per wave, plain stores, reduced in this kernel's prologue via `amax_parts`) or `launch_row_amax`
+// computes.  Scales are powers of two: un-scaling the accumulator is exact.
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
-#include "device_math.h"
+#include "gemm_f16x2_tile.h"
 
 namespace lram {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 constexpr int BN = 128, BK = 32;
@@ -46,11 +42,11 @@ constexpr int kPitchPadded = 40;   // f16 elements per padded LDS row (80 B: con
 // memory.  Without it the fp32 -> f16 conversion, the LDS writes and the MFMA block of a workgroup are separated by
 // barriers and overlap only with OTHER workgroups' phases: measured, the MFMA time was simply added on top of the rest
 // (16M proj_up: 66 us with, 52 us without the MFMAs, 15.5 us of pure MFMA time).
-template <bool HAS_BIAS, bool HAS_RES, int BM, bool GATE, int PF, bool DB = false>
-__global__ __launch_bounds__(256, (PF == 1 && !DB) ? 3 : 2) void gemm_f16x2_kernel(GemmArgs g) {
+template <bool HAS_BIAS, bool HAS_RES, int BM, bool GATE, bool DB = false>
+__global__ __launch_bounds__(256, DB ? 2 : 3) void gemm_f16x2_kernel(GemmArgs g) {
   constexpr int WM = BM / 2;   // rows per wave
   constexpr int TI = WM / 32;  // MFMA row tiles per wave
-  // DB: un-padded 64-byte rows with the 16-byte chunk index XOR-ed by (row >> 2) & 3 (the 16 lanes of a ds_read_b128
+  // DB: un-padded 64-byte rows with the 16-byte chunk index XOR-ed by f16x2_chunk_swizzle(row) (the 16 lanes of a ds_read_b128
   // pass then cover all 64 banks: rows r, r + 4, r + 8, r + 12 of a pass would otherwise share their banks) -- 32 KB per
   // stage, two stages of two workgroups fit a CU with room to spare; else rows padded to 80 bytes.
   constexpr int PITCH = DB ? 32 : kPitchPadded;
@@ -72,7 +68,6 @@ __global__ __launch_bounds__(256, (PF == 1 && !DB) ? 3 : 2) void gemm_f16x2_kern
   const int wm = wave >> 1, wn = wave & 1;
   const float* A = g.a;
   const _Float16* W2 = reinterpret_cast<const _Float16*>(g.w2);
-  float* C = g.c;
 
   const int tiles_n = (g.n + BN - 1) / BN;
   const int tiles_m = (g.m + BM - 1) / BM;
@@ -98,9 +93,9 @@ __global__ __launch_bounds__(256, (PF == 1 && !DB) ? 3 : 2) void gemm_f16x2_kern
   const int lr = tid >> 3;        // A: row within a 32-row slab
   const int lc = (tid & 7) << 2;  // A: k offset 0,4,..,28
   constexpr int NA = BM / 32;     // float4 per thread and K tile
-  // PF register sets: tile kt + PF is requested while tile kt is computed, so PF tiles of global loads are in flight
-  // per workgroup at any time (PF = 2 keeps the memory pipe fed across the split / LDS-write / barrier stretch)
-  constexpr int NSET = DB ? 2 : PF;
+  // register sets: the next tile is requested while tile kt is computed -- one tile of global loads in flight per workgroup;
+  // DB: two (tile kt + 1 waits in registers for its conversion while tile kt + 2 is in flight)
+  constexpr int NSET = DB ? 2 : 1;
   float4 ra[NSET][NA];
   float4 rz[NSET][GATE ? NA : 1];
   (void)rz;
@@ -176,13 +171,12 @@ __global__ __launch_bounds__(256, (PF == 1 && !DB) ? 3 : 2) void gemm_f16x2_kern
       f16x4 hi, lo;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float v = xs[e] * se;
-        const _Float16 h = (_Float16)v;
-        hi[e] = h;
-        lo[e] = (_Float16)(v - (float)h);
+        _Float16 h, l;   // (a vector element does not bind to a reference)
+        split2(xs[e] * se, h, l);
+        hi[e] = h, lo[e] = l;
       }
       const int arow = lr + 32 * i;
-      _Float16* dst = As + buf * STAGE + arow * PITCH + (DB ? ((((lc >> 3) ^ ((arow >> 2) & 3)) << 3) | (lc & 4)) : lc);
+      _Float16* dst = As + buf * STAGE + arow * PITCH + (DB ? ((((lc >> 3) ^ f16x2_chunk_swizzle(arow)) << 3) | (lc & 4)) : lc);
       *reinterpret_cast<f16x4*>(dst) = hi;
       *reinterpret_cast<f16x4*>(dst + APLANE) = lo;
     }
@@ -194,7 +188,7 @@ __global__ __launch_bounds__(256, (PF == 1 && !DB) ? 3 : 2) void gemm_f16x2_kern
       const unsigned msk = (wok[j] && (!k_tail || k0 + wkc[j] < g.k)) ? 0xffffffffu : 0u;
       uint4 v = rw[set][j];
       v.x &= msk, v.y &= msk, v.z &= msk, v.w &= msk;
-      const int cs = DB ? (((c >> 3) ^ ((r >> 2) & 3)) << 3) : c;
+      const int cs = DB ? (((c >> 3) ^ f16x2_chunk_swizzle(r)) << 3) : c;
       *reinterpret_cast<uint4*>(Bs + buf * STAGE + plane * PLANE + r * PITCH + cs) = v;
     }
   };
@@ -211,56 +205,26 @@ __global__ __launch_bounds__(256, (PF == 1 && !DB) ? 3 : 2) void gemm_f16x2_kern
   // lane (row li, half lh) holds k = 8*lh + j (j = 0..7) of a 16-deep MFMA step for both operands
   const _Float16* a_base = As + (WM * wm + li) * PITCH + (DB ? 0 : 8 * lh);
   const _Float16* b_base = Bs + (64 * wn + li) * PITCH + (DB ? 0 : 8 * lh);
-  const int sw = (li >> 2) & 3;  // DB: chunk swizzle of this lane's rows (row offsets of the tiles are multiples of 32)
+  const int sw = f16x2_chunk_swizzle(li);  // DB: chunk swizzle of this lane's rows (row offsets of the tiles are multiples of 32)
 
   const int nk_all = (g.k + BK - 1) / BK;
   const int kt0 = g.split_k > 1 ? blockIdx.z * g.k_tiles_per_split : 0;
   const int nk = g.split_k > 1 ? min(nk_all, kt0 + g.k_tiles_per_split) : nk_all;
-  auto mfma_tile = [&]() {
-    if (g.mfma_prio) __builtin_amdgcn_s_setprio(1);
+  // fragment reads + products of 16-deep step ks of the tile in LDS stage `buf`
+  auto frag_mfma = [&](int buf, int ks) {
+    const int ko = DB ? f16x2_frag_offset(ks, lh, sw) : 16 * ks;
+    f16x8 af[TI][2], bf[2][2];
 #pragma unroll
-    for (int ks = 0; ks < BK / 16; ++ks) {
-      f16x8 af[TI][2], bf[2][2];
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-          if (t < TI) af[t][p] = *reinterpret_cast<const f16x8*>(a_base + p * APLANE + 32 * t * PITCH + 16 * ks);
-          bf[t][p] = *reinterpret_cast<const f16x8*>(b_base + p * PLANE + 32 * t * PITCH + 16 * ks);
-        }
-#pragma unroll
-      for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          // smallest terms first
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i][1], bf[j][0], acc[i][j], 0, 0, 0);  // lo * hi
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i][0], bf[j][1], acc[i][j], 0, 0, 0);  // hi * lo
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i][0], bf[j][0], acc[i][j], 0, 0, 0);  // hi * hi
-        }
-    }
-    if (g.mfma_prio) __builtin_amdgcn_s_setprio(0);
+      for (int p = 0; p < 2; ++p) {
+        if (t < TI) af[t][p] = *reinterpret_cast<const f16x8*>(a_base + buf * STAGE + p * APLANE + 32 * t * PITCH + ko);
+        bf[t][p] = *reinterpret_cast<const f16x8*>(b_base + buf * STAGE + p * PLANE + 32 * t * PITCH + ko);
+      }
+    f16x2_products<TI>(acc, af, bf);
   };
   if (DB) {
     // step(kt): tile kt sits in stage cur, register set cur ^ 1 holds tile kt + 1, set cur is free.
-    auto frag_mfma = [&](int buf, int ks) {
-      f16x8 af[TI][2], bf[2][2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-          const int ko = ((2 * ks + lh) ^ sw) << 3;
-          if (t < TI) af[t][p] = *reinterpret_cast<const f16x8*>(a_base + buf * STAGE + p * APLANE + 32 * t * PITCH + ko);
-          bf[t][p] = *reinterpret_cast<const f16x8*>(b_base + buf * STAGE + p * PLANE + 32 * t * PITCH + ko);
-        }
-#pragma unroll
-      for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i][1], bf[j][0], acc[i][j], 0, 0, 0);  // lo * hi
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i][0], bf[j][1], acc[i][j], 0, 0, 0);  // hi * lo
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i][0], bf[j][0], acc[i][j], 0, 0, 0);  // hi * hi
-        }
-    };
     auto step = [&](int cur, int kt) {
       load_tile(cur, min(kt + 2, nk - 1) * BK);       // into the free set; lands during the NEXT step
       frag_mfma(cur, 0);
@@ -280,55 +244,41 @@ __global__ __launch_bounds__(256, (PF == 1 && !DB) ? 3 : 2) void gemm_f16x2_kern
     if (kt < nk) step(0, kt);
   } else {
   // The prefetch of a half is unconditional (past the last tile it re-reads the last one; nothing consumes it) and the
-  // loop body always runs all PF halves: hipcc's wait counts are then exact -- a load behind a condition makes it
+  // loop body always runs its whole half: hipcc's wait counts are then exact -- a load behind a condition makes it
   // assume the shorter queue on every path and wait for the NEWEST register set where the oldest is needed.
-  auto half = [&](int u, int kt) {
+  auto half = [&](int kt) {
     // (scheduling fence: hipcc otherwise hoists the NEXT register set's conversion above this half's barriers and
     // with it the wait for that set's loads -- every load would again have to land before the first barrier)
     __builtin_amdgcn_sched_barrier(0);
-    store_tile(u, kt * BK);
+    store_tile(0, kt * BK);
     __syncthreads();
-    load_tile(u, min(kt + PF, nk - 1) * BK);
-    mfma_tile();
+    load_tile(0, min(kt + 1, nk - 1) * BK);
+    if (g.mfma_prio) __builtin_amdgcn_s_setprio(1);
+    frag_mfma(0, 0);
+    frag_mfma(0, 1);
+    if (g.mfma_prio) __builtin_amdgcn_s_setprio(0);
     __syncthreads();
   };
   load_tile(0, kt0 * BK);
-  if (PF > 1) load_tile(PF - 1, min(kt0 + 1, nk - 1) * BK);
-  int kt = kt0;
-  for (; kt + PF <= nk; kt += PF) {
-#pragma unroll
-    for (int u = 0; u < PF; ++u) half(u, kt + u);
-  }
-  if (PF > 1 && kt < nk) half(0, kt);  // odd tile count: one half left
+  for (int kt = kt0; kt < nk; ++kt) half(kt);
   }
 
   // epilogue (C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5));
   // un-scale with the exact inverse powers of two of the row (A) and column (W) scales
   float* S = g.split_k > 1 ? g.splitk_ws + (int64_t)blockIdx.z * g.m * g.n : nullptr;
 #pragma unroll
-  for (int i = 0; i < TI; ++i)
+  for (int i = 0; i < TI; ++i) {
+    const int row0 = m0 + WM * wm + 32 * i + 4 * lh;
+    float ainv[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) ainv[r] = DB ? sinv_r[DB ? i : 0][DB ? r : 0] : sinv[row0 - m0 + (r & 3) + 8 * (r >> 2)];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int col = n0 + 64 * wn + 32 * j + li;
       if (col >= g.n) continue;
-      const float wi = DB ? winv_r[j] : sinv[BM + col - n0];
-      const float bv = HAS_BIAS ? g.bias[col] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + WM * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (row < g.m) {
-          float v = acc[i][j][r] * (wi * (DB ? sinv_r[DB ? i : 0][DB ? r : 0] : sinv[row - m0]));
-          if (S != nullptr) {  // raw partial sums into this split's slab [M][N]; bias / residual are applied by the reduce
-            S[(int64_t)row * g.n + col] = v;
-            continue;
-          }
-          v += bv;
-          if (HAS_RES) v += g.residual[(int64_t)row * g.ldc + col];
-          if (g.act_silu_from >= 0 && col >= g.act_silu_from) v = silu_hw(v);
-          C[(int64_t)row * g.ldc + col] = v;
-        }
-      }
+      LRAM_F16X2_STORE_ACC_TILE(acc[i][j], ainv, DB ? winv_r[j] : sinv[BM + col - n0], row0, col);
     }
+  }
 }
 
 // One wave per row: amax[r] = max_k |a[r][k] (* gate[r][k])|.
@@ -364,11 +314,8 @@ __global__ __launch_bounds__(256) void split_f16x2_kernel(const float* w, int ro
   for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
   const float s = pow2_scale(mx);
   for (int c = lane; c < k; c += 64) {
-    const float v = wr[c] * s;
-    const _Float16 h = (_Float16)v;
     const int64_t at = ((int64_t)(c >> 5) * rows + row) * 32 + (c & 31);
-    planes[at] = h;
-    planes[plane + at] = (_Float16)(v - (float)h);
+    split2(wr[c] * s, planes[at], planes[plane + at]);
   }
   if (lane == 0) inv[row] = 1.f / s;
 }
@@ -392,43 +339,22 @@ void launch_split_f16x2(const float* w, int rows, int k, uint16_t* planes, float
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
-template <int BM, bool GATE, int PF>
-static void launch_bm_pf(const GemmArgs& g, dim3 grid, hipStream_t stream) {
-  const bool hb = g.bias != nullptr, hr = g.residual != nullptr;
-  dim3 block(256);
-  if (hb && hr)
-    hipLaunchKernelGGL((gemm_f16x2_kernel<true, true, BM, GATE, PF>), grid, block, 0, stream, g);
-  else if (hb)
-    hipLaunchKernelGGL((gemm_f16x2_kernel<true, false, BM, GATE, PF>), grid, block, 0, stream, g);
-  else if (hr)
-    hipLaunchKernelGGL((gemm_f16x2_kernel<false, true, BM, GATE, PF>), grid, block, 0, stream, g);
-  else
-    hipLaunchKernelGGL((gemm_f16x2_kernel<false, false, BM, GATE, PF>), grid, block, 0, stream, g);
-}
-
 template <int BM, bool GATE>
 static void launch_bm(const GemmArgs& g, dim3 grid, hipStream_t stream) {
   // Two LDS stages + one barrier per K tile (the kernel's DB note) pay where the launch cannot fill the chip with
   // workgroups anyway -- at most one per CU: 206M proj_down (240 workgroups) 109 -> 86 us -- and lose where three
   // single-stage workgroups per CU can overlap each other's phases (16M proj_up 62 -> 75 us, Mamba in_proj 128 -> 140).
-  // (Two K tiles of global loads in flight per workgroup -- PF = 2 -- pushed the kernel from three workgroups per CU to two: 94 ->
+  // (Two K tiles of global loads in flight per single-stage workgroup pushed the kernel from three workgroups per CU to two: 94 ->
   // 118 us on proj_up; removed.)
   // (also tried for split-K launches -- Mamba's x_proj, 45 -> 35 us standalone: no end-to-end difference, 365.4k vs 365.1k)
   const long wgs = (long)grid.x * grid.y * grid.z;
-  if (wgs <= 256 && !GATE) {
-    const bool hb = g.bias != nullptr, hr = g.residual != nullptr;
-    dim3 block(256);
-    if (hb && hr)
-      hipLaunchKernelGGL((gemm_f16x2_kernel<true, true, BM, false, 2, true>), grid, block, 0, stream, g);
-    else if (hb)
-      hipLaunchKernelGGL((gemm_f16x2_kernel<true, false, BM, false, 2, true>), grid, block, 0, stream, g);
-    else if (hr)
-      hipLaunchKernelGGL((gemm_f16x2_kernel<false, true, BM, false, 2, true>), grid, block, 0, stream, g);
+  launch_bias_res(g, [&](auto b, auto r) {
+    constexpr bool hb = decltype(b)::value, hr = decltype(r)::value;
+    if (wgs <= 256 && !GATE)
+      hipLaunchKernelGGL((gemm_f16x2_kernel<hb, hr, BM, false, true>), grid, dim3(256), 0, stream, g);
     else
-      hipLaunchKernelGGL((gemm_f16x2_kernel<false, false, BM, false, 2, true>), grid, block, 0, stream, g);
-    return;
-  }
-  launch_bm_pf<BM, GATE, 1>(g, grid, stream);
+      hipLaunchKernelGGL((gemm_f16x2_kernel<hb, hr, BM, GATE, false>), grid, dim3(256), 0, stream, g);
+  });
 }
 
 // g.a_amax: per-row largest magnitude of A (of the gated rows when g.gate is set), from launch_row_amax or A's producer.
@@ -444,13 +370,13 @@ void launch_gemm_f16x2(const GemmArgs& g_in, hipStream_t stream) {
     S = gemm_choose_split_k(g);
   const int tiles_n = (g.n + BN - 1) / BN;
   const int tiles128 = ((g.m + 127) / 128) * tiles_n;
-  // 64-row tiles where 128-row tiles leave workgroup slots empty (three workgroups per CU: 768 slots) and the launch is narrow, or
-  // where they would leave CUs without any workgroup and K is short (1536 x 1024 x 512: 31.6 us with 96 tiles of 128 rows, 20.5
-  // with 192 of 64; long-K launches: see launch_gemm_f16x2p)
-  // (LRAM_GEMM_TILE = 64 / 128 forces one: the knob of launch_gemm_f16x2p)
+  // 64-row tiles where the pre-split kernel takes them (gemm_f16x2p_tile: 128-row tiles would leave CUs without any workgroup and K
+  // is short -- 1536 x 1024 x 512: 31.6 us with 96 tiles of 128 rows, 20.5 with 192 of 64 -- or LRAM_GEMM_TILE = 64 / 128 forces one),
+  // and, this kernel's own clause, where 128-row tiles leave workgroup slots empty (three workgroups per CU: 768 slots) and the
+  // launch is narrow
   const int force_bm = gemm_knobs().tile;
-  constexpr int bm64_below = 256, bm64_anyk = 128;
-  const bool small = force_bm == 64 || (force_bm != 128 && g.m > 64 && ((S == 1 && tiles128 < 768 && tiles_n <= 6) || ((long)tiles128 * S < bm64_below && g.k <= 768) || (long)tiles128 * S < bm64_anyk));
+  const bool forced = force_bm == 64 || force_bm == 128;
+  const bool small = gemm_f16x2p_tile(g, S) == 64 || (!forced && g.m > 64 && S == 1 && tiles128 < 768 && tiles_n <= 6);
   const int tiles = small ? ((g.m + 63) / 64) * tiles_n : tiles128;
   dim3 grid(tiles, 1, S);
   gemm_choose_xcd_split(g, small ? 64 : 128, BN, 4);

@@ -35,13 +35,9 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
-#include "device_math.h"
+#include "gemm_f16x2_tile.h"
 
 namespace lram {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 constexpr int BK = 32;
@@ -58,22 +54,14 @@ constexpr int S_A0 = 0, S_B0 = 1, S_B1 = 2, S_A1 = 3;
 #define LRAM_WAIT_VM(n)
 #endif
 
-// ABL (measurement builds only, scripts/gemm8p_ablate.cpp; the library instantiates 0): 1 = DMA descriptors with zero records (the
-// instruction stream and the waits stay, no byte moves), 2 = no DMA instructions, 3 = fragments read once (no ds_read in the
-// loop), 4 = s_memtime stamps of waves 0 and 4 of workgroup 0 into splitk_ws (phase shares), 5 = both ring tiles staged once, no
-// DMA in the loop (random operands WITHOUT memory traffic: separates delivery from the clock effect of 1 / 2, whose operands are
-// zeros); outputs meaningless in 1-5
-template <bool HAS_BIAS, bool HAS_RES, int ABL = 0>
+// (The measurement variants this kernel carried while it was tuned -- zero-record DMA descriptors, no DMA, fragments read once,
+// the ring staged once, per-phase clock stamps and a per-workgroup timeline, with their harness scripts/gemm8p_ablate.cpp;
+// numbers in profiles/r06_gemm_8phase_ablation.txt -- are in the git history: commit 068f892 is the last that has them.)
+template <bool HAS_BIAS, bool HAS_RES>
 __global__ __launch_bounds__(512, 1) void gemm_f16x2_8p_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(1024))) _Float16 lds[2 * TILE];   // the ONLY LDS object of the kernel (128 KB)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  unsigned long long real_entry = 0;
-  if (ABL == 4) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(real_entry)::"memory");
-#endif
-  }
   const int wr = wave >> 2, wc = wave & 3;
   const int li = lane & 31, lh = lane >> 5;
 
@@ -91,12 +79,12 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_8p_kernel(GemmArgs g) {
   // byte offsets, K tile + plane offsets in the scalar operand.
 #if defined(__HIP_DEVICE_COMPILE__)
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(g.a2) + (int64_t)m0 * 32, 0, ABL == 1 ? 0u : 0xffffffffu, 0x00020000);
+      const_cast<uint16_t*>(g.a2) + (int64_t)m0 * 32, 0, 0xffffffffu, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(g.w2) + (int64_t)n0 * 32, 0, ABL == 1 ? 0u : 0xffffffffu, 0x00020000);
+      const_cast<uint16_t*>(g.w2) + (int64_t)n0 * 32, 0, 0xffffffffu, 0x00020000);
 #endif
   const int rho = 16 * wave + (lane >> 2);
-  const int chunk = (lane & 3) ^ ((rho >> 2) & 3);
+  const int chunk = (lane & 3) ^ f16x2_chunk_swizzle(rho);
   unsigned voff_a[2], voff_b[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -109,9 +97,7 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_8p_kernel(GemmArgs g) {
   const unsigned pl_bytes_a = (unsigned)(g.a2_plane * 2), pl_bytes_w = (unsigned)(g.w2_plane * 2);
 
   // stage half-tile `slot` of K tile kt into ring tile `buf` (2 DMA pieces per wave)
-  bool dma_on = true;
   auto stage = [&](int buf, int slot, int kt) {
-    if (ABL == 2 || (ABL == 5 && !dma_on)) return;
 #if defined(__HIP_DEVICE_COMPILE__)
     const bool is_a = slot == S_A0 || slot == S_A1;
     const int h = (slot == S_A1 || slot == S_B1) ? 1 : 0;
@@ -135,9 +121,9 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_8p_kernel(GemmArgs g) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[a][i][b][r] = 0.f;
 
-  // fragment addresses (f16 units inside a half-tile): row * 32 + ((2 ks + lh) ^ sw) * 8; sw from the row inside its 32-row tile
-  const int sw = (li >> 2) & 3;
-  const int ko0 = ((0 + lh) ^ sw) << 3, ko1 = ((2 + lh) ^ sw) << 3;
+  // fragment addresses (f16 units inside a half-tile): row * 32 + the swizzled chunk of step ks, from the row inside its 32-row tile
+  const int sw = f16x2_chunk_swizzle(li);
+  const int ko0 = f16x2_frag_offset(0, lh, sw), ko1 = f16x2_frag_offset(1, lh, sw);
   const int a_row = (wr * 64 + li) * BK;   // + i * 32 * BK
   const int b_row = (wc * 32 + li) * BK;
 
@@ -148,9 +134,7 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_8p_kernel(GemmArgs g) {
   f16x8 af[2][2][2];     // [row tile i][ks][plane]
   f16x8 bf0[2][2], bf1[2][2];   // [ks][plane]
 
-  bool reads_on = true;
   auto read_a = [&](int buf, int slot) {
-    if (ABL == 3 && !reads_on) return;
     const _Float16* base = lds + buf * TILE + slot * HALF + a_row;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -161,7 +145,6 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_8p_kernel(GemmArgs g) {
       }
   };
   auto read_b = [&](int buf, int slot, f16x8 (&bf)[2][2]) {
-    if (ABL == 3 && !reads_on) return;
     const _Float16* base = lds + buf * TILE + slot * HALF + b_row;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
@@ -169,11 +152,12 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_8p_kernel(GemmArgs g) {
       bf[1][p] = *reinterpret_cast<const f16x8*>(base + p * PLN + ko1);
     }
   };
+  // (its own six MFMAs, not f16x2_products: the two accumulators are interleaved on purpose, so that no MFMA depends on the one before)
   auto quadrant = [&](f32x16 (&c0), f32x16 (&c1), const f16x8 (&bf)[2][2]) {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      // smallest terms first (the order of gemm_f16x2p.hip: bit-identical sums)
+      // smallest terms first (the order of f16x2_products per accumulator: bit-identical sums)
       c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][ks][1], bf[ks][0], c0, 0, 0, 0);  // lo * hi
       c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1][ks][1], bf[ks][0], c1, 0, 0, 0);
       c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][ks][0], bf[ks][1], c0, 0, 0, 0);  // hi * lo
@@ -189,11 +173,6 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_8p_kernel(GemmArgs g) {
     stage(0, S_A0, kt0), stage(0, S_B0, kt0), stage(0, S_B1, kt0), stage(0, S_A1, kt0);
     if (kt0 + 1 < nk) {
       stage(1, S_A0, kt0 + 1), stage(1, S_B0, kt0 + 1);
-      if (ABL == 5) {
-        stage(1, S_B1, kt0 + 1), stage(1, S_A1, kt0 + 1);
-        LRAM_WAIT_VM(0);
-        dma_on = false;
-      }
       LRAM_WAIT_VM(4);
     } else {
       LRAM_WAIT_VM(0);
@@ -202,37 +181,8 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_8p_kernel(GemmArgs g) {
   __builtin_amdgcn_s_barrier();
   if (wr == 1) __builtin_amdgcn_s_barrier();   // waves 4-7 run one barrier behind waves 0-3 from here on
 
-  if (ABL == 3) {   // fragments once, from whatever the prologue staged
-    read_a(0, S_A0), read_b(0, S_B0, bf0), read_b(0, S_B1, bf1);
-    reads_on = false;
-  }
-  // stamps (ABL 4): per phase slot p (0..3) sums of [reads + DMA issue (+ VM wait)] [barrier 1] [MFMA issue] [barrier 2]
-  unsigned long long st_sum[4][4] = {}, st_prev = 0;
-  const bool stamping = ABL == 4 && blockIdx.x == 0 && blockIdx.z == 0 && (wave == 0 || wave == 4);
-  auto stamp = [&](int p, int seg) {
-    if (ABL != 4) return;
-#if defined(__HIP_DEVICE_COMPILE__)
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    if (seg >= 0) st_sum[p][seg] += t - st_prev;
-    st_prev = t;
-#endif
-  };
-  unsigned long long real0 = 0, cyc0 = 0;
-  if (ABL == 4) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_memrealtime %0\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(real0), "=s"(cyc0)::"memory");
-#endif
-  }
-  stamp(0, -1);
   // one K tile = four phases on ring tile BUF
-#define LRAM_PHASE_SYNC_1()                 \
-  __builtin_amdgcn_sched_barrier(0);        \
-  __builtin_amdgcn_s_barrier();             \
-  __builtin_amdgcn_sched_barrier(0)
-#define LRAM_PHASE_SYNC_2()                 \
+#define LRAM_PHASE_SYNC()                   \
   __builtin_amdgcn_sched_barrier(0);        \
   __builtin_amdgcn_s_barrier();             \
   __builtin_amdgcn_sched_barrier(0)
@@ -242,33 +192,21 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_8p_kernel(GemmArgs g) {
     read_b(BUF, S_B0, bf0);                                                                   \
     read_a(BUF, S_A0);                                                                        \
     if ((kt) + 1 < nk) stage((BUF) ^ 1, S_B1, (kt) + 1);                                      \
-    stamp(0, 0);                                                                              \
-    LRAM_PHASE_SYNC_1();                                                                      \
-    stamp(0, 1);                                                                              \
+    LRAM_PHASE_SYNC();                                                                        \
     quadrant(acc[0][0][0], acc[0][1][0], bf0);                                                \
-    stamp(0, 2);                                                                              \
-    LRAM_PHASE_SYNC_2();                                                                      \
-    stamp(0, 3);                                                                              \
+    LRAM_PHASE_SYNC();                                                                        \
     /* phase 1: (a0, b1) */                                                                   \
     read_b(BUF, S_B1, bf1);                                                                   \
     if ((kt) + 1 < nk) stage((BUF) ^ 1, S_A1, (kt) + 1);                                      \
-    stamp(1, 0);                                                                              \
-    LRAM_PHASE_SYNC_1();                                                                      \
-    stamp(1, 1);                                                                              \
+    LRAM_PHASE_SYNC();                                                                        \
     quadrant(acc[0][0][1], acc[0][1][1], bf1);                                                \
-    stamp(1, 2);                                                                              \
-    LRAM_PHASE_SYNC_2();                                                                      \
-    stamp(1, 3);                                                                              \
+    LRAM_PHASE_SYNC();                                                                        \
     /* phase 2: (a1, b1) */                                                                   \
     read_a(BUF, S_A1);                                                                        \
     if ((kt) + 2 < nk) stage(BUF, S_A0, (kt) + 2);                                            \
-    stamp(2, 0);                                                                              \
-    LRAM_PHASE_SYNC_1();                                                                      \
-    stamp(2, 1);                                                                              \
+    LRAM_PHASE_SYNC();                                                                        \
     quadrant(acc[1][0][1], acc[1][1][1], bf1);                                                \
-    stamp(2, 2);                                                                              \
-    LRAM_PHASE_SYNC_2();                                                                      \
-    stamp(2, 3);                                                                              \
+    LRAM_PHASE_SYNC();                                                                        \
     /* phase 3: (a1, b0); the next tile's half-tiles are retired here, read from its phase 0 on */ \
     if ((kt) + 2 < nk) {                                                                      \
       stage(BUF, S_B0, (kt) + 2);                                                             \
@@ -276,13 +214,9 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_8p_kernel(GemmArgs g) {
     } else {                                                                                  \
       LRAM_WAIT_VM(0);                                                                        \
     }                                                                                         \
-    stamp(3, 0);                                                                              \
-    LRAM_PHASE_SYNC_1();                                                                      \
-    stamp(3, 1);                                                                              \
+    LRAM_PHASE_SYNC();                                                                        \
     quadrant(acc[1][0][0], acc[1][1][0], bf0);                                                \
-    stamp(3, 2);                                                                              \
-    LRAM_PHASE_SYNC_2();                                                                      \
-    stamp(3, 3);                                                                              \
+    LRAM_PHASE_SYNC();                                                                        \
   }
 
   for (int kt = kt0; kt < nk; kt += 2) {
@@ -290,41 +224,23 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_8p_kernel(GemmArgs g) {
     if (kt + 1 < nk) LRAM_K_TILE(1, kt + 1);
   }
   if (wr == 0) __builtin_amdgcn_s_barrier();   // (every wave has passed the same number of barriers)
-  if (ABL == 4) {
-    unsigned long long real1 = 0, cyc1 = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_memrealtime %0\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(real1), "=s"(cyc1)::"memory");
-#endif
-    if (stamping && lane == 0) {
-      unsigned long long* out = reinterpret_cast<unsigned long long*>(g.splitk_ws) + (wave == 0 ? 0 : 16);
-      for (int p = 0; p < 4; ++p)
-        for (int sg = 0; sg < 4; ++sg) out[4 * p + sg] = st_sum[p][sg];
-      if (wave == 0) out[32] = real1 - real0, out[33] = cyc1 - cyc0;   // K loop: 100 MHz ticks, s_memtime ticks
-    }
-    if (wave == 0 && lane == 0) {   // every workgroup: entry, loop start, loop end (s_memrealtime); the exit stamp follows the epilogue
-      unsigned long long* tl = reinterpret_cast<unsigned long long*>(g.splitk_ws) + 64 + 4 * (int64_t)blockIdx.x;
-      tl[0] = real_entry, tl[1] = real0, tl[2] = real1;
-    }
-  }
 #undef LRAM_K_TILE
-#undef LRAM_PHASE_SYNC_1
-#undef LRAM_PHASE_SYNC_2
+#undef LRAM_PHASE_SYNC
 
   // ---- epilogue.  C/D layout of the 32 x 32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) -- a lane
   // holds ONE column of 16 rows, so storing from the accumulators is 128 single-dword store instructions per lane, two 128-byte
   // row pieces each: measured 21-24 us per workgroup (38 k cycles for 256 KB, ~7 B / clock / CU: store-issue-bound) against a
-  // K loop of 39-92 us, with nothing to overlap it at one workgroup per CU (scripts/gemm8p_ablate.cpp, per-workgroup timeline;
-  // profiles/r06_gemm_8phase_ablation.txt).  The operand ring is free once every wave has left the K loop, so each wave turns
+  // K loop of 39-92 us, with nothing to overlap it at one workgroup per CU (per-workgroup timeline of the retired measurement
+  // build, profiles/r06_gemm_8phase_ablation.txt).  The operand ring is free once every wave has left the K loop, so each wave turns
   // its 64 x 64 accumulator half through 16 KB of it: ds_write_b32 in [row][col] order (a lane half writes 32 consecutive
   // floats: conflict-free), ds_read_b128 of four whole rows per instruction, un-scale (exact powers of two) + bias + residual
   // + activation on float4s, dwordx4 stores of 256 contiguous bytes per row.  Same arithmetic per element as before:
   // acc * (w_inv * a_inv) + bias, + residual, silu.
-  float* C = g.c;
   float* S = g.split_k > 1 ? g.splitk_ws + (int64_t)blockIdx.z * g.m * g.n : nullptr;
   typedef float __attribute__((may_alias)) lds_f32;
   typedef float4 __attribute__((may_alias)) lds_f32x4;
   const int64_t ld_out = S != nullptr ? (int64_t)g.n : g.ldc;
-  float* out = S != nullptr ? S : C;
+  float* out = S != nullptr ? S : g.c;
   const bool vec = (ld_out & 3) == 0 && (g.n & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
                    (reinterpret_cast<uintptr_t>(g.w_inv + n0) & 15) == 0 &&
                    (!HAS_BIAS || (reinterpret_cast<uintptr_t>(g.bias + n0) & 15) == 0) &&
@@ -355,23 +271,8 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_8p_kernel(GemmArgs g) {
       for (int it = 0; it < 16; ++it) {
         const int grow = grow0 + 4 * it;
         const float4 t = *reinterpret_cast<const lds_f32x4*>(stg + (4 * it + rq) * 64 + c4);
-        if (grow < g.m && col_in) {
-          const float ai = g.a2_inv[grow];
-          float4 v;
-          v.x = t.x * (wi4.x * ai) + bv4.x, v.y = t.y * (wi4.y * ai) + bv4.y;
-          v.z = t.z * (wi4.z * ai) + bv4.z, v.w = t.w * (wi4.w * ai) + bv4.w;
-          if (HAS_RES && S == nullptr) {
-            const float4 rr = *reinterpret_cast<const float4*>(g.residual + (int64_t)grow * g.ldc + gcol);
-            v.x += rr.x, v.y += rr.y, v.z += rr.z, v.w += rr.w;
-          }
-          if (act_from >= 0) {
-            if (gcol + 0 >= act_from) v.x = silu_hw(v.x);
-            if (gcol + 1 >= act_from) v.y = silu_hw(v.y);
-            if (gcol + 2 >= act_from) v.z = silu_hw(v.z);
-            if (gcol + 3 >= act_from) v.w = silu_hw(v.w);
-          }
-          *reinterpret_cast<float4*>(out + (int64_t)grow * ld_out + gcol) = v;
-        }
+        if (grow < g.m && col_in)
+          f16x2_finish4<HAS_RES>(g, out, ld_out, S != nullptr, act_from, t, wi4, g.a2_inv[grow], bv4, grow, gcol);
       }
     }
   } else {
@@ -388,41 +289,9 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_8p_kernel(GemmArgs g) {
         for (int b = 0; b < 2; ++b) {
           const int col = n0 + wc * 64 + b * 32 + li;
           if (col >= g.n) continue;
-          const float wi = g.w_inv[col];
-          const float bv = HAS_BIAS ? g.bias[col] : 0.f;
-          const bool act = g.act_silu_from >= 0 && col >= g.act_silu_from;
-          const bool rows_in = row0 + 27 < g.m;
-          const f32x16& t = acc[a][i][b];
-          if (S != nullptr) {
-            float* sp = S + (int64_t)row0 * g.n + col;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int ro = (r & 3) + 8 * (r >> 2);
-              if (rows_in || row0 + ro < g.m) sp[(int64_t)ro * g.n] = t[r] * (wi * ainv[r]);
-            }
-            continue;
-          }
-          float* cp = C + (int64_t)row0 * g.ldc + col;
-          const float* rp = HAS_RES ? g.residual + (int64_t)row0 * g.ldc + col : nullptr;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int ro = (r & 3) + 8 * (r >> 2);
-            if (rows_in || row0 + ro < g.m) {
-              float v = t[r] * (wi * ainv[r]) + bv;
-              if (HAS_RES) v += rp[(int64_t)ro * g.ldc];
-              if (act) v = silu_hw(v);
-              cp[(int64_t)ro * g.ldc] = v;
-            }
-          }
+          LRAM_F16X2_STORE_ACC_TILE(acc[a][i][b], ainv, g.w_inv[col], row0, col);
         }
       }
-  }
-  if (ABL == 4) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    unsigned long long real_exit;
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(real_exit)::"memory");
-    if (wave == 0 && lane == 0) (reinterpret_cast<unsigned long long*>(g.splitk_ws) + 64 + 4 * (int64_t)blockIdx.x)[3] = real_exit;
-#endif
   }
 }
 #undef LRAM_WAIT_VM
@@ -455,15 +324,9 @@ void launch_gemm_f16x2_8p(const GemmArgs& g_in, hipStream_t stream) {
   const int tiles = ((g.m + BMT - 1) / BMT) * ((g.n + BNT - 1) / BNT);
   dim3 grid(tiles, 1, S), block(512);
   gemm_choose_xcd_split(g, BMT, BNT, 4);
-  const bool hb = g.bias != nullptr, hr = g.residual != nullptr;
-  if (hb && hr)
-    hipLaunchKernelGGL((gemm_f16x2_8p_kernel<true, true>), grid, block, 0, stream, g);
-  else if (hb)
-    hipLaunchKernelGGL((gemm_f16x2_8p_kernel<true, false>), grid, block, 0, stream, g);
-  else if (hr)
-    hipLaunchKernelGGL((gemm_f16x2_8p_kernel<false, true>), grid, block, 0, stream, g);
-  else
-    hipLaunchKernelGGL((gemm_f16x2_8p_kernel<false, false>), grid, block, 0, stream, g);
+  launch_bias_res(g, [&](auto b, auto r) {
+    hipLaunchKernelGGL((gemm_f16x2_8p_kernel<decltype(b)::value, decltype(r)::value>), grid, block, 0, stream, g);
+  });
   LRAM_HIP_CHECK(hipGetLastError());
   if (S > 1) launch_splitk_reduce(g, stream);
 }

@@ -24,13 +24,9 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
-#include "device_math.h"
+#include "gemm_f16x2_tile.h"
 
 namespace lram {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 constexpr int BK = 32;
@@ -112,7 +108,7 @@ __global__ __launch_bounds__(64 * WM * WN, NSTAGE == 1 ? 4 : 2) void gemm_f16x2p
     const int rbs = is_a ? BMT / 16 : BN / 16;        // row blocks per plane
     const int plane = q / rbs, rb = q % rbs;
     const int row = 16 * rb + (lane >> 2);
-    const int chunk = (lane & 3) ^ ((row >> 2) & 3);
+    const int chunk = (lane & 3) ^ f16x2_chunk_swizzle(row);
     const int lrow = is_a ? min(m0 + row, g.m - 1) - m0 : min(n0 + row, g.n - 1) - n0;   // row relative to the resource's base
     voff[i] = (unsigned)(((int64_t)plane * (is_a ? g.a2_plane : g.w2_plane) + (int64_t)lrow * 32 + 8 * chunk) * 2);
   }
@@ -140,7 +136,7 @@ __global__ __launch_bounds__(64 * WM * WN, NSTAGE == 1 ? 4 : 2) void gemm_f16x2p
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   const int li = lane & 31, lh = lane >> 5;
-  const int sw = (li >> 2) & 3;  // chunk swizzle of this lane's rows (tile row offsets are multiples of 32)
+  const int sw = f16x2_chunk_swizzle(li);  // chunk swizzle of this lane's rows (tile row offsets are multiples of 32)
   // Two-stage instances: the tile's BMT + BN inverse scales go into LDS by DMA too (4 bytes per lane, behind the tile stages
   // of the same array; the first barrier of the K loop publishes them), read by the epilogue.  Round 5: they used to sit in
   // 32 + 2 registers through the K loop (181 VGPRs) -- one register too many for a workgroup to start beside two read-pass
@@ -172,7 +168,7 @@ __global__ __launch_bounds__(64 * WM * WN, NSTAGE == 1 ? 4 : 2) void gemm_f16x2p
     if (g.mfma_prio) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < BK / 16; ++ks) {
-      const int ko = ((2 * ks + lh) ^ sw) << 3;
+      const int ko = f16x2_frag_offset(ks, lh, sw);
       f16x8 af[TI][2], bf[2][2];
 #pragma unroll
       for (int t = 0; t < 2; ++t)
@@ -181,15 +177,7 @@ __global__ __launch_bounds__(64 * WM * WN, NSTAGE == 1 ? 4 : 2) void gemm_f16x2p
           if (t < TI) af[t][p] = *reinterpret_cast<const f16x8*>(a_base + stage * STG + p * APL + 32 * t * BK + ko);
           bf[t][p] = *reinterpret_cast<const f16x8*>(b_base + stage * STG + p * PLANE + 32 * t * BK + ko);
         }
-#pragma unroll
-      for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          // smallest terms first
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i][1], bf[j][0], acc[i][j], 0, 0, 0);  // lo * hi
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i][0], bf[j][1], acc[i][j], 0, 0, 0);  // hi * lo
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i][0], bf[j][0], acc[i][j], 0, 0, 0);  // hi * hi
-        }
+      f16x2_products<TI>(acc, af, bf);
     }
     if (g.mfma_prio) __builtin_amdgcn_s_setprio(0);
   };
@@ -263,68 +251,26 @@ __global__ __launch_bounds__(64 * WM * WN, NSTAGE == 1 ? 4 : 2) void gemm_f16x2p
         for (int it = 0; it < PR / 4; ++it) {
           const int rl = rl0 + 4 * it, grow = m0 + rl;
           const float4 t = *reinterpret_cast<const lds_f32x4*>(stg + (4 * it + rq) * 64 + c4);
-          if (grow < g.m && col_in) {
-            const float ai = NSTAGE == 1 ? scl[rl] : sclf[rl];
-            float4 v;
-            v.x = t.x * (wi4.x * ai) + bv4.x, v.y = t.y * (wi4.y * ai) + bv4.y;
-            v.z = t.z * (wi4.z * ai) + bv4.z, v.w = t.w * (wi4.w * ai) + bv4.w;
-            if (HAS_RES && S == nullptr) {
-              const float4 rr = *reinterpret_cast<const float4*>(g.residual + (int64_t)grow * g.ldc + gcol);
-              v.x += rr.x, v.y += rr.y, v.z += rr.z, v.w += rr.w;
-            }
-            if (act_from >= 0) {
-              if (gcol + 0 >= act_from) v.x = silu_hw(v.x);
-              if (gcol + 1 >= act_from) v.y = silu_hw(v.y);
-              if (gcol + 2 >= act_from) v.z = silu_hw(v.z);
-              if (gcol + 3 >= act_from) v.w = silu_hw(v.w);
-            }
-            *reinterpret_cast<float4*>(outp + (int64_t)grow * ld_out + gcol) = v;
-          }
+          if (grow < g.m && col_in)
+            f16x2_finish4<HAS_RES>(g, outp, ld_out, S != nullptr, act_from, t, wi4, NSTAGE == 1 ? scl[rl] : sclf[rl], bv4, grow, gcol);
         }
       }
     return;
   }
 #pragma unroll
   for (int i = 0; i < TI; ++i) {
+    const int row0 = m0 + 32 * TI * wm + 32 * i + 4 * lh;
     float ainv[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = m0 + 32 * TI * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
+      const int row = row0 + (r & 3) + 8 * (r >> 2);
       ainv[r] = NSTAGE == 1 ? scl[row - m0] : sclf[row - m0];
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int col = n0 + 64 * wn + 32 * j + li;
       if (col >= g.n) continue;
-      const float wi = NSTAGE == 1 ? scl[BMT + col - n0] : sclf[BMT + col - n0];
-      const float bv = HAS_BIAS ? g.bias[col] : 0.f;
-      // (per (i, j) one base pointer; the 16 rows of the accumulator tile are compile-time multiples of the row pitch from it --
-      // the per-element 64-bit row * pitch products, bounds checks and libm SiLU of the first form were ~60 instructions per
-      // stored value, as many in the epilogue as in the whole K loop)
-      const int row0 = m0 + 32 * TI * wm + 32 * i + 4 * lh;
-      const bool act = g.act_silu_from >= 0 && col >= g.act_silu_from;
-      const bool rows_in = row0 + 27 < g.m;  // (uniform but for tiles on the lower edge)
-      if (S != nullptr) {  // raw partial sums into this split's slab [M][N]; bias / residual are applied by the reduce
-        float* sp = S + (int64_t)row0 * g.n + col;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int ro = (r & 3) + 8 * (r >> 2);
-          if (rows_in || row0 + ro < g.m) sp[(int64_t)ro * g.n] = acc[i][j][r] * (wi * ainv[r]);
-        }
-        continue;
-      }
-      float* cp = C + (int64_t)row0 * g.ldc + col;
-      const float* rp = HAS_RES ? g.residual + (int64_t)row0 * g.ldc + col : nullptr;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int ro = (r & 3) + 8 * (r >> 2);
-        if (rows_in || row0 + ro < g.m) {
-          float v = acc[i][j][r] * (wi * ainv[r]) + bv;
-          if (HAS_RES) v += rp[(int64_t)ro * g.ldc];
-          if (act) v = silu_hw(v);
-          cp[(int64_t)ro * g.ldc] = v;
-        }
-      }
+      LRAM_F16X2_STORE_ACC_TILE(acc[i][j], ainv, NSTAGE == 1 ? scl[BMT + col - n0] : sclf[BMT + col - n0], row0, col);
     }
   }
 }
@@ -383,16 +329,9 @@ void launch_row_split_f16x2(const float* a, int64_t lda, const float* gate, int6
 
 template <int NSTAGE, int TI, int WM, int WN>
 static void launch_stage(const GemmArgs& g, dim3 grid, hipStream_t stream) {
-  const bool hb = g.bias != nullptr, hr = g.residual != nullptr;
-  dim3 block(64 * WM * WN);
-  if (hb && hr)
-    hipLaunchKernelGGL((gemm_f16x2p_kernel<true, true, NSTAGE, TI, WM, WN>), grid, block, 0, stream, g);
-  else if (hb)
-    hipLaunchKernelGGL((gemm_f16x2p_kernel<true, false, NSTAGE, TI, WM, WN>), grid, block, 0, stream, g);
-  else if (hr)
-    hipLaunchKernelGGL((gemm_f16x2p_kernel<false, true, NSTAGE, TI, WM, WN>), grid, block, 0, stream, g);
-  else
-    hipLaunchKernelGGL((gemm_f16x2p_kernel<false, false, NSTAGE, TI, WM, WN>), grid, block, 0, stream, g);
+  launch_bias_res(g, [&](auto b, auto r) {
+    hipLaunchKernelGGL((gemm_f16x2p_kernel<decltype(b)::value, decltype(r)::value, NSTAGE, TI, WM, WN>), grid, dim3(64 * WM * WN), 0, stream, g);
+  });
 }
 
 // Workgroup tile of a launch.  64 x 128 where 128-row tiles would leave CUs without a workgroup AND K is short (16M at 1024

@@ -561,14 +561,9 @@ void launch_gemm_skinny_inst(const GemmArgs& g, hipStream_t stream) {
       return;
     }
   }
-  if (hb && hr)
-    hipLaunchKernelGGL((gemm_skinny_kernel<true, true, NW, Q, MULTI>), grid, block, 0, stream, g);
-  else if (hb)
-    hipLaunchKernelGGL((gemm_skinny_kernel<true, false, NW, Q, MULTI>), grid, block, 0, stream, g);
-  else if (hr)
-    hipLaunchKernelGGL((gemm_skinny_kernel<false, true, NW, Q, MULTI>), grid, block, 0, stream, g);
-  else
-    hipLaunchKernelGGL((gemm_skinny_kernel<false, false, NW, Q, MULTI>), grid, block, 0, stream, g);
+  launch_bias_res(g, [&](auto b, auto r) {
+    hipLaunchKernelGGL((gemm_skinny_kernel<decltype(b)::value, decltype(r)::value, NW, Q, MULTI>), grid, block, 0, stream, g);
+  });
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
@@ -612,15 +607,9 @@ void launch_gemm_f32(const GemmArgs& g_in, hipStream_t stream) {
   const int tiles = ((g.m + BM - 1) / BM) * ((g.n + BN - 1) / BN);
   dim3 grid(tiles, g.nb1 * g.nb2, S);
   dim3 block(256);
-  const bool hb = g.bias != nullptr, hr = g.residual != nullptr;
-  if (hb && hr)
-    hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, block, 0, stream, g);
-  else if (hb)
-    hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, block, 0, stream, g);
-  else if (hr)
-    hipLaunchKernelGGL((gemm_f32_kernel<false, true>), grid, block, 0, stream, g);
-  else
-    hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, block, 0, stream, g);
+  launch_bias_res(g, [&](auto b, auto r) {
+    hipLaunchKernelGGL((gemm_f32_kernel<decltype(b)::value, decltype(r)::value>), grid, block, 0, stream, g);
+  });
   LRAM_HIP_CHECK(hipGetLastError());
   if (S > 1) launch_splitk_reduce(g, stream);
 }

@@ -198,9 +198,9 @@ __global__ __launch_bounds__(64 * kNarrowWaves) void gemm_narrow16_kernel(GemmAr
       const int row_ = 4 * i + (lane >> 4), p_ = lane & 15;                                      \
       nh4 hi_, lo_;                                                                              \
       _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) {                                         \
-        const float x_ = AR[i][e_] * asc[i];                                                     \
-        const _Float16 h_ = (_Float16)x_;                                                        \
-        hi_[e_] = h_, lo_[e_] = (_Float16)(x_ - (float)h_);                                      \
+        _Float16 h_, l_;                                                                         \
+        split2(AR[i][e_] * asc[i], h_, l_);                                                      \
+        hi_[e_] = h_, lo_[e_] = l_;                                                              \
       }                                                                                          \
       _Float16* d_ = abuf + row_ * 64 + (((p_ >> 1) ^ ((row_ >> 1) & 7)) << 3) + ((p_ & 1) << 2); \
       *reinterpret_cast<nh4*>(d_) = hi_;                                                         \

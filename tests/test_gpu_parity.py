@@ -218,7 +218,9 @@ def test_gemm_f16x2_presplit_every_tile_is_bit_identical(hip_lib, monkeypatch, t
     monkeypatch.setenv("LRAM_GEMM_TILE", str(tile))
     monkeypatch.setenv("LRAM_F16P_STAGES", str(stages))
     # (tile 256 = the 8-phase kernel of gemm_f16x2_8p.hip: 256 x 256 outputs per workgroup, 8 staggered waves, a two-tile LDS
-    # ring filled six phases ahead with counted waits -- one, two, three and an odd number of K tiles, K splits, ragged edges)
+    # ring filled six phases ahead with counted waits -- one, two, three and an odd number of K tiles, ragged edges.  K is never
+    # split here: the standalone lram_gemm_* entries pass no split-K workspace, so every kernel's chooser returns 1 and the slab
+    # branch of the epilogues is not run by this test)
     for m, n, k in [(257, 129, 96), (300, 80, 1536), (1000, 700, 32), (3072, 3072, 768), (6144, 2048, 512), (513, 300, 64),
                     (700, 520, 160), (768, 1280, 2560)]:
         g = torch.Generator().manual_seed(m * 13 + n + tile)

@@ -66,7 +66,7 @@ def test_projection_workgroups_fit_beside_two_read_passes():
 
 def test_on_the_fly_projection_workgroup_budget():
     res = _resources("gemm_f16x2.hip")
-    two_stage = _one(res, "gemm_f16x2_kernelILb0ELb1ELi64ELb0ELi2ELb1E")        # proj_down of chain-bound slices: 64-row tile, two stages
+    two_stage = _one(res, "gemm_f16x2_kernelILb0ELb1ELi64ELb0ELb1E")            # proj_down of chain-bound slices: 64-row tile, two stages
     assert two_stage["VGPRs"] <= 160 and two_stage["LDS Size [bytes/block]"] <= 48 * 1024, two_stage
-    gated = _one(res, "gemm_f16x2_kernelILb0ELb1ELi64ELb1ELi1ELb0E")            # proj_down of the headline: 64-row tile, gate in the staging
+    gated = _one(res, "gemm_f16x2_kernelILb0ELb1ELi64ELb1ELb0E")                # proj_down of the headline: 64-row tile, gate in the staging
     assert gated["VGPRs"] <= 128 and gated["LDS Size [bytes/block]"] <= 36 * 1024, gated
