@@ -244,11 +244,19 @@ void launch_scatter_token0_indexed(float* x, const float* emb, const int32_t* sl
 void launch_embed_chunk(float* x, const float* emb, int64_t emb_stride, const float* rtg, const float* rew, int64_t in_stride,
                         const float* w_rtg, const float* b_rtg, const float* w_rew, const float* b_rew, int B, int steps, int T,
                         int D, hipStream_t stream);
-// argmax over logits [B, act_dim*n_vocab] (+ de-tokenise)
-void launch_action_argmax(const float* logits, float* actions, int32_t* tokens, int B, int act_dim, int n_vocab,
-                          int n_discrete, int action_channels, float tok_min, float tok_max, int discrete,
-                          int col_begin, hipStream_t stream, int col_end = -1, const uint8_t* slot_flags = nullptr,
-                          const uint8_t* slot_act = nullptr);   // slot table [B] + [B]: head mode / dims in use per env slot
+// The action head's geometry and the slot table's two device arrays ([envs] + [envs]: head mode / action dims in use per env
+// slot; both null: no table), passed by value to every head kernel (action_head.h holds the row rules they share).
+struct HeadGeom {
+  int act_dim = 0, n_vocab = 0, n_discrete = 0, action_channels = 0;
+  float tok_min = -1.f, tok_max = 1.f;
+};
+struct HeadSlots {
+  const uint8_t* flags = nullptr;
+  const uint8_t* act = nullptr;
+};
+// argmax over logits [B, act_dim*n_vocab] (+ de-tokenise); columns col_begin .. col_end - 1 (sample_kernels.hip)
+void launch_action_argmax(const float* logits, float* actions, int32_t* tokens, int B, const HeadGeom& g, const HeadSlots& s,
+                          int discrete, int col_begin, int col_end, hipStream_t stream);
 // The sampling mode of the same head (sample_kernels.hip): the token is drawn from the row instead of being its argmax.
 constexpr int kSampleMaxRow = 512;  // logits per row the sampling kernels hold in registers (8 per lane)
 struct SampleArgs {
@@ -267,15 +275,12 @@ struct SampleSlot {
   int32_t mode = 1;  // 0: greedy (the argmax rule), 1: sample
 };
 // slots: nullable device table, entry 0 = the launch's first env slot; null: the launch is what it was before the table
-void launch_action_sample(const float* logits, float* actions, int32_t* tokens, int B, int act_dim, int n_vocab,
-                          int n_discrete, int action_channels, float tok_min, float tok_max, int discrete, int col_begin,
-                          int col_end, const SampleArgs& sp, hipStream_t stream, const uint8_t* slot_flags = nullptr,
-                          const uint8_t* slot_act = nullptr, const SampleSlot* slots = nullptr);
+void launch_action_sample(const float* logits, float* actions, int32_t* tokens, int B, const HeadGeom& g, const HeadSlots& s,
+                          int discrete, int col_begin, int col_end, const SampleArgs& sp, const SampleSlot* slots,
+                          hipStream_t stream);
 // logp[B, act_dim] of tokens[B, act_dim] under the distribution launch_action_sample draws from (filters applied; sp.draw unused)
-void launch_action_logp(const float* logits, const int32_t* tokens, float* logp, int B, int act_dim, int n_vocab,
-                        int n_discrete, int discrete, const SampleArgs& sp, hipStream_t stream,
-                        const uint8_t* slot_flags = nullptr, const uint8_t* slot_act = nullptr,
-                        const SampleSlot* slots = nullptr);
+void launch_action_logp(const float* logits, const int32_t* tokens, float* logp, int B, const HeadGeom& g, const HeadSlots& s,
+                        int discrete, const SampleArgs& sp, const SampleSlot* slots, hipStream_t stream);
 void launch_sample_advance(uint64_t* draw, hipStream_t stream);  // ++*draw, one thread
 // rows of n logits at logits + r * ld (ld = 0: every row is row 0), one caller uniform per row -> tokens[rows]
 void launch_sample_tokens(const float* logits, int64_t rows, int n, int64_t ld, double temperature, int top_k, double top_p,
@@ -296,16 +301,14 @@ struct ScoreArgs {
   int64_t ld = 0;
   int64_t row0 = 0, rows = 0;
   int64_t inner = 1, outer = 1, off = 0;
-  int act_dim = 0, n_vocab = 0, n_discrete = 0, action_channels = 0;
-  float tok_min = -1.f, tok_max = 1.f;
+  HeadGeom geom;
+  HeadSlots slots;           // slot table [envs] + [envs], nullable
   int discrete = 0;          // 0 / 1; with a slot table the slot's flag decides
   int over = 0;              // logp normalises over 0: all n_vocab logits, 1: the selectable range
   double temperature = 1.0;  // MULTIPLIES the logits
   const float* target_actions = nullptr;   // [., act_dim] float actions, tokenised on the device -- or
   const int32_t* target_tokens = nullptr;  // [., act_dim] tokens (at most one of the two)
   const uint8_t* valid = nullptr;          // [.] nullable: rows with 0 get the fill values
-  const uint8_t* slot_flags = nullptr;     // slot table [envs] + [envs], nullable
-  const uint8_t* slot_act = nullptr;
   float* actions = nullptr;                // outputs, each nullable: [., act_dim]
   int32_t* tokens = nullptr;
   float* logp = nullptr;

@@ -13,7 +13,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 // torch.argmax order of (value, index) candidates: NaN is the maximum, the first index wins among equal values (NaNs
 // included), +-Inf compare as ordinary values.  Starting from (-inf, INT_MAX) every element of a non-empty row is taken
-// or loses to one that was, so the winner is always a real index.  (Action head: misc_kernels.hip, sample_kernels.hip.)
+// or loses to one that was, so the winner is always a real index.  (Action head: action_head.h.)
 __device__ __forceinline__ bool argmax_beats(float v, int i, float best, int bi) {
   const bool v_nan = v != v, best_nan = best != best;
   if (v_nan) return !best_nan || i < bi;
@@ -28,6 +28,12 @@ __device__ __forceinline__ float inv_tokenize_bin(int t, float bin_width, float 
 #pragma clang fp contract(off)
   const float scaled = (float)t * bin_width;
   return scaled + tok_min;
+}
+// Its inverse, MinMaxTokenizer.tokenize (minmax_tokenizer.py:14-29), of a finite x: the bin trunc((x - min) / bin_width) clamped to
+// 0 .. channels - 1 -- fp32 subtract, IEEE fp32 division.
+__device__ __forceinline__ int tokenize_bin(float x, float bin_width, float tok_min, int channels) {
+  const float q = __fdiv_rn(__fsub_rn(x, tok_min), bin_width);
+  return q <= 0.f ? 0 : (q >= (float)(channels - 1) ? channels - 1 : (int)q);
 }
 
 // torch.nn.functional.logsigmoid: min(x, 0) - log1p(exp(-|x|))

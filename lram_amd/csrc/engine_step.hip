@@ -191,16 +191,21 @@ void embed_tokens(lram_engine* e, const Pass& pass, const Inputs& in, const floa
                   (L == 1 && e->B <= kTokenTapMaxBatch) ? e->TOK.p + r0 * D : nullptr, nullptr, stok_on ? &stok : nullptr);
 }
 
+// The engine's head geometry, and the slot table of a call as the slice from env slot b0 on sees it (none unless the call is
+// per-slot).
+HeadGeom head_geom(const lram_config& c) { return {c.act_dim, c.n_vocab, c.n_discrete, c.action_channels, c.tok_min, c.tok_max}; }
+HeadSlots head_slots(const lram_engine* e, int discrete, size_t b0 = 0) {
+  if (discrete != LRAM_HEAD_PER_SLOT) return {};
+  return {e->slot_dev + b0, e->slot_dev + e->B + b0};
+}
+
 // What every score launch of a call shares: the head's geometry, the sink's tensors, the slot table of a per-slot call.
 ScoreArgs score_args(const lram_engine* e, const ScoreSink& k, int discrete) {
-  const lram_config& c = e->cfg;
   ScoreArgs a;
-  a.act_dim = c.act_dim, a.n_vocab = c.n_vocab, a.n_discrete = c.n_discrete, a.action_channels = c.action_channels;
-  a.tok_min = c.tok_min, a.tok_max = c.tok_max;
+  a.geom = head_geom(e->cfg), a.slots = head_slots(e, discrete);
   a.discrete = discrete == LRAM_HEAD_PER_SLOT ? 0 : discrete;
   a.over = k.over, a.temperature = k.temperature;
   a.target_actions = k.target_actions, a.target_tokens = k.target_tokens, a.valid = k.valid;
-  if (discrete == LRAM_HEAD_PER_SLOT) a.slot_flags = e->slot_dev, a.slot_act = e->slot_dev + e->B;
   a.actions = k.actions, a.tokens = k.tokens, a.logp = k.logp, a.logits_out = k.logits;
   return a;
 }
@@ -247,12 +252,10 @@ void action_head(lram_engine* e, const Pass& pass, const std::vector<Slice>& sl,
   const int col_begin = pass.compat_pass;
   const int col_end = (pass.compat_shared && col_begin + 1 < pass.compat_passes) ? col_begin + 1 : c.act_dim;
   const int col0 = pass.compat_shared ? col_begin : 0;
-  const bool per_slot = discrete == LRAM_HEAD_PER_SLOT;
   e->last_head = discrete;
+  const HeadGeom geom = head_geom(c);
   for (const Slice& x : sl) {
     const size_t r0 = (size_t)x.b0 * Tc, b0 = x.b0;
-    const uint8_t* sf = per_slot ? e->slot_dev + b0 : nullptr;
-    const uint8_t* sa = per_slot ? e->slot_dev + e->B + b0 : nullptr;
     GemmArgs gh;
     gh.a = e->HID.p + (r0 + pred) * D, gh.lda = (int64_t)Tc * D, gh.w = e->w_head + (size_t)col0 * c.n_vocab * D, gh.ldw = D;
     gh.c = e->LOGITS.p + b0 * nlog + (size_t)col0 * c.n_vocab, gh.ldc = nlog, gh.bias = e->b_head + (size_t)col0 * c.n_vocab;
@@ -265,17 +268,18 @@ void action_head(lram_engine* e, const Pass& pass, const std::vector<Slice>& sl,
       launch_action_score(a, x.s);
       continue;
     }
+    const float* logits = e->LOGITS.p + b0 * nlog;
+    float* act = actions + b0 * c.act_dim;
+    int32_t* tok = tokens ? tokens + b0 * c.act_dim : nullptr;
+    const HeadSlots slots = head_slots(e, discrete, b0);
     if (e->sampling) {
       SampleArgs sp = e->sample;
       sp.slot0 += b0, sp.draw = e->sample_draw;
-      launch_action_sample(e->LOGITS.p + b0 * nlog, actions + b0 * c.act_dim, tokens ? tokens + b0 * c.act_dim : nullptr,
-                           x.nb, c.act_dim, c.n_vocab, c.n_discrete, c.action_channels, c.tok_min, c.tok_max, discrete,
-                           col_begin, col_end, sp, x.s, sf, sa, e->sample_slots_dev ? e->sample_slots_dev + b0 : nullptr);
+      launch_action_sample(logits, act, tok, x.nb, geom, slots, discrete, col_begin, col_end, sp,
+                           e->sample_slots_dev ? e->sample_slots_dev + b0 : nullptr, x.s);
       continue;
     }
-    launch_action_argmax(e->LOGITS.p + b0 * nlog, actions + b0 * c.act_dim,
-                         tokens ? tokens + b0 * c.act_dim : nullptr, x.nb, c.act_dim, c.n_vocab, c.n_discrete,
-                         c.action_channels, c.tok_min, c.tok_max, discrete, col_begin, x.s, col_end, sf, sa);
+    launch_action_argmax(logits, act, tok, x.nb, geom, slots, discrete, col_begin, col_end, x.s);
   }
 }
 
@@ -850,12 +854,9 @@ int32_t lram_score_last_sampled(lram_engine* e, const int32_t* dev_tokens, float
     LRAM_REQUIRE(!(head == LRAM_HEAD_PER_SLOT && e->sample_slots.empty() && e->slot_has_discrete &&
                    e->sample.top_k > e->cfg.n_discrete),
                  "lram_score_last_sampled: sampling top_k exceeds n_discrete and the slot table holds a discrete slot");
-    const bool per_slot = head == LRAM_HEAD_PER_SLOT;
-    const lram_config& c = e->cfg;
     // (deterministic: no uniform is read, the draw counter is neither read nor advanced)
-    launch_action_logp(e->LOGITS.p, dev_tokens, dev_logp, e->B, c.act_dim, c.n_vocab, c.n_discrete, head, e->sample,
-                       static_cast<hipStream_t>(stream), per_slot ? e->slot_dev : nullptr, per_slot ? e->slot_dev + e->B : nullptr,
-                       e->sample_slots_dev);
+    launch_action_logp(e->LOGITS.p, dev_tokens, dev_logp, e->B, head_geom(e->cfg), head_slots(e, head), head, e->sample,
+                       e->sample_slots_dev, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -884,8 +885,8 @@ int32_t lram_score_tokens(const float* dev_logits, int64_t rows, int32_t act_dim
     LRAM_REQUIRE(discrete == 0 || discrete == 1, "lram_score_tokens: discrete must be 0 or 1");
     ScoreArgs a;
     a.logits = dev_logits, a.ld = (int64_t)act_dim * n_vocab, a.rows = rows;
-    a.act_dim = act_dim, a.n_vocab = n_vocab, a.n_discrete = n_discrete, a.action_channels = action_channels;
-    a.tok_min = tok_min, a.tok_max = tok_max, a.discrete = discrete, a.over = over, a.temperature = temperature;
+    a.geom = {act_dim, n_vocab, n_discrete, action_channels, tok_min, tok_max};
+    a.discrete = discrete, a.over = over, a.temperature = temperature;
     a.target_actions = dev_target_actions, a.target_tokens = dev_target_tokens, a.valid = dev_valid;
     a.actions = dev_actions, a.tokens = dev_tokens, a.logp = dev_logp;
     launch_action_score(a, static_cast<hipStream_t>(stream));

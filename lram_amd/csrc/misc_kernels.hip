@@ -1,10 +1,8 @@
-// Row norms, token front end, action head argmax / de-tokenisation, utility copies.
+// Row norms, token front end, utility copies.
 //
 // Reference functions replaced: nn.LayerNorm `embed_ln`, xlstm LayerNorm / LlamaRMSNorm
 // (src/algos/models/rms_norm.py:17-22), embed_return / embed_rewards Linear(1, D)
-// (src/algos/models/online_decision_transformer_model.py:522-530), torch.argmax +
-// MinMaxTokenizer.inv_tokenize (src/algos/models/multi_domain_discrete_dt_model.py:83-94,
-// src/tokenizers_custom/minmax_tokenizer.py:31-47).
+// (src/algos/models/online_decision_transformer_model.py:522-530).
 #include <cstdlib>
 
 #include "common.h"
@@ -217,65 +215,6 @@ __global__ __launch_bounds__(256) void embed_chunk_kernel(float* x, const float*
   *reinterpret_cast<float4*>(row + 2 * D) = make_float4(r * wr.x + br.x, r * wr.y + br.y, r * wr.z + br.z, r * wr.w + br.w);
 }
 
-// One wave per (env, action dim): first index of the maximum (torch.argmax rule, device_math.h::argmax_beats), then
-// inv_tokenize: max(tok - shift, 0) * ((max - min) / channels) + min.
-__global__ __launch_bounds__(256) void action_argmax_kernel(const float* logits, float* actions, int32_t* tokens,
-                                                            int B, int act_dim, int n_vocab, int n_discrete,
-                                                            int action_channels, float tok_min, float tok_max,
-                                                            int discrete, int col_begin, int col_end,
-                                                            const uint8_t* slot_flags, const uint8_t* slot_act) {
-  const int lane = threadIdx.x & 63;
-  const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int ndim = (discrete && slot_flags == nullptr) ? 1 : act_dim;
-  if (item >= B * ndim) return;
-  const int b = item / ndim, j = item - b * ndim;
-  if (j < col_begin || j >= col_end) return;  // repeated-forward mode: pass p writes action dim p, the last pass
-                                              // every dim from its own on (engine.hip::step_launches)
-  if (slot_flags != nullptr) {  // slot table (LRAM_HEAD_PER_SLOT): the wave's row decides, so the branch is wave-uniform
-    discrete = slot_flags[b] & 1;
-    if (j >= (int)slot_act[b]) {  // a column the slot does not use: the fill values, on every call
-      if (lane == 0) {
-        if (tokens != nullptr) tokens[(int64_t)b * act_dim + j] = -1;
-        actions[(int64_t)b * act_dim + j] = 0.f;
-      }
-      return;
-    }
-  }
-  const float* lg = logits + (int64_t)b * act_dim * n_vocab + (int64_t)j * n_vocab;
-  const int n = discrete ? n_discrete : n_vocab;
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int i = lane; i < n; i += 64) {
-    const float v = lg[i];
-    if (argmax_beats(v, i, best, bi)) {
-      best = v;
-      bi = i;
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(best, off, 64);
-    const int oi = __shfl_xor(bi, off, 64);
-    if (argmax_beats(ov, oi, best, bi)) {
-      best = ov;
-      bi = oi;
-    }
-  }
-  if (lane == 0) {
-    if (tokens != nullptr) tokens[(int64_t)b * act_dim + j] = bi;
-    float out;
-    if (discrete) {
-      out = (float)bi;
-    } else {
-      int t = bi - n_discrete;
-      t = t < 0 ? 0 : t;
-      const float bin_width = (tok_max - tok_min) / (float)action_channels;
-      out = inv_tokenize_bin(t, bin_width, tok_min);  // two roundings, as the reference: no FMA
-    }
-    actions[(int64_t)b * act_dim + j] = out;
-  }
-}
-
 // Observation front end: native obs [B, n_native] -> model input [B, state_dim]: scatter by an index table
 // (identity = zero-pad, decision_xlstm.py:16-19; DMControl dict obs -> 204-dim full space,
 // src/envs/dmcontrol_utils.py:35-59), then optional (x - mean) / std (decision_transformer_sb3.py:650-651).
@@ -450,20 +389,6 @@ void launch_embed_chunk(float* x, const float* emb, int64_t emb_stride, const fl
   const int64_t n = (int64_t)B * steps * (D >> 2);
   hipLaunchKernelGGL(embed_chunk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, emb, emb_stride, rtg, rew,
                      in_stride, w_rtg, b_rtg, w_rew, b_rew, B, steps, T, D);
-  LRAM_HIP_CHECK(hipGetLastError());
-}
-
-void launch_action_argmax(const float* logits, float* actions, int32_t* tokens, int B, int act_dim, int n_vocab,
-                          int n_discrete, int action_channels, float tok_min, float tok_max, int discrete,
-                          int col_begin, hipStream_t stream, int col_end, const uint8_t* slot_flags,
-                          const uint8_t* slot_act) {
-  LRAM_REQUIRE((slot_flags == nullptr) == (slot_act == nullptr), "action head: the slot table's two arrays go together");
-  // with a slot table: one wave per (env, action dim) over all act_dim columns, the head mode is read per env slot
-  const int items = B * ((discrete && slot_flags == nullptr) ? 1 : act_dim);
-  if (col_end < 0) col_end = act_dim;
-  hipLaunchKernelGGL(action_argmax_kernel, dim3((items + 3) / 4), dim3(256), 0, stream, logits, actions, tokens, B,
-                     act_dim, n_vocab, n_discrete, action_channels, tok_min, tok_max, discrete, col_begin, col_end,
-                     slot_flags, slot_act);
   LRAM_HIP_CHECK(hipGetLastError());
 }
 

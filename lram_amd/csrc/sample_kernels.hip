@@ -18,8 +18,9 @@
 // wave's env slot from a device table instead of the launch's scalars; mode 0 = greedy, the argmax rule at once.
 // logp_row (action_logp_kernel, sample_rows_kernel): the log-probability of a GIVEN token under the same support and
 // weights -- t * (x_tok - max) - log(sum over the support of exp(t * (x - max))), fp64, one fp32 rounding at the store.
-#include "common.h"
-#include "device_math.h"
+// The greedy head (action_argmax_kernel) lives here too: the sampling head's twin on the same grid.  The rules every head kernel
+// applies to its row -- which columns are in use, the argmax, the de-tokenisation, the staging -- are action_head.h's.
+#include "action_head.h"
 
 namespace lram {
 namespace {
@@ -189,23 +190,6 @@ __device__ __forceinline__ double wave_scan_f64(double inc, int lane) {
   return inc;
 }
 
-// The default path's rule (argmax_beats), as action_argmax_kernel applies it to the same row.
-__device__ __forceinline__ int row_argmax(const float* row, int n, int lane) {
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int i = lane; i < n; i += 64) {
-    const float x = row[i];
-    if (argmax_beats(x, i, best, bi)) best = x, bi = i;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(best, off, 64);
-    const int oi = __shfl_xor(bi, off, 64);
-    if (argmax_beats(ov, oi, best, bi)) best = ov, bi = oi;
-  }
-  return bi;
-}
-
 // The draw.  Returns the token (wave-uniform); greedy (a per-slot setting, wave-uniform): the argmax rule at once.
 template <int PER>
 __device__ __forceinline__ int sample_row(const float* row, int n, double temperature, int top_k, double top_p, double u,
@@ -267,123 +251,116 @@ __device__ __forceinline__ double logp_row(const float* row, int n, double tempe
   return lp;
 }
 
-// A wave's row: global -> its LDS strip, coalesced.  Every wave of the workgroup reaches the barrier behind it.
-template <int PER>
-__device__ __forceinline__ void stage_row(float* strip, const float* src, int n, int lane, bool active) {
-  if (active) {
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const int i = lane + 64 * j;
-      if (i < n) strip[i] = src[i];
-    }
-  }
-  __syncthreads();
+// The grid of an env-step's head (argmax and sampling): one wave per (env, action dim), four per workgroup -- over all act_dim
+// columns, or over column 0 alone on a discrete call without a slot table (columns j >= 1 are then left alone).  `live`: the
+// wave has a column, and it lies in col_begin .. col_end - 1 (repeated-forward mode: pass p writes action dim p, the last pass
+// every dim from its own on, engine_step.hip::action_head).
+__host__ __device__ __forceinline__ int step_columns(const HeadGeom& g, const HeadSlots& s, int discrete) {
+  return (discrete && s.flags == nullptr) ? 1 : g.act_dim;
+}
+struct StepItem {
+  int b, j;
+  bool live;
+};
+__device__ __forceinline__ StepItem step_item(int B, const HeadGeom& g, const HeadSlots& s, int discrete, int col_begin,
+                                              int col_end) {
+  const int item = blockIdx.x * 4 + (threadIdx.x >> 6), ndim = step_columns(g, s, discrete);
+  StepItem it;
+  it.b = item / ndim, it.j = item - it.b * ndim;
+  it.live = item < B * ndim && it.j >= col_begin && it.j < col_end;
+  return it;
+}
+// lane 0: the column's token (where asked for) and its action
+__device__ __forceinline__ void store_action(int64_t o, int tok, int discrete, const HeadGeom& g, int32_t* tokens, float* actions) {
+  if (tokens != nullptr) tokens[o] = tok;
+  if (actions != nullptr) actions[o] = detokenise(tok, discrete, g);
 }
 
-// The sampling counterpart of action_argmax_kernel (misc_kernels.hip), same grid: one wave per (env, action dim), four
-// per workgroup.  sp.draw is read, never written, here: sample_advance_kernel bumps it once per env-step behind every head
-// launch of that step.
+// The greedy head: first index of the row's maximum (torch.argmax rule), then inv_tokenize.  Nothing is staged: the row is
+// walked once in global memory, and a wave without work returns at once.
+__global__ __launch_bounds__(256) void action_argmax_kernel(const float* logits, float* actions, int32_t* tokens, int B,
+                                                            HeadGeom g, HeadSlots s, int discrete, int col_begin, int col_end) {
+  const int lane = threadIdx.x & 63;
+  const StepItem it = step_item(B, g, s, discrete, col_begin, col_end);
+  if (!it.live) return;
+  const HeadCol col = head_column(g, s, discrete, it.b, it.j);
+  const int64_t o = (int64_t)it.b * g.act_dim + it.j;
+  if (col.fill) {
+    if (lane == 0) store_fill(o, tokens, actions, nullptr);
+    return;
+  }
+  const int tok = row_argmax(logits + o * g.n_vocab, col.n, lane);
+  if (lane == 0) store_action(o, tok, col.discrete, g, tokens, actions);
+}
+
+// Its sampling counterpart, same grid.  sp.draw is read, never written, here: sample_advance_kernel bumps it once per env-step
+// behind every head launch of that step.
 // SLOTS: the settings come from the per-slot table (lram_set_sampling_slots; `slots` starts at the launch's first env slot)
 // instead of sp's scalars -- a compile-time split, so that the launch without a table is the code it was before the table.
 template <int PER, bool SLOTS>
 __device__ __forceinline__ void action_sample_body(float (&stage)[4][64 * PER], const float* logits, float* actions,
-                                                   int32_t* tokens, int B, int act_dim, int n_vocab, int n_discrete,
-                                                   int action_channels, float tok_min, float tok_max, int discrete,
-                                                   int col_begin, int col_end, const SampleArgs& sp, const uint8_t* slot_flags,
-                                                   const uint8_t* slot_act, const SampleSlot* slots) {
+                                                   int32_t* tokens, int B, const HeadGeom& g, const HeadSlots& s, int discrete,
+                                                   int col_begin, int col_end, const SampleArgs& sp, const SampleSlot* slots) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int item = blockIdx.x * 4 + wv;
-  const int ndim = (discrete && slot_flags == nullptr) ? 1 : act_dim;
-  const int b = item / ndim, j = item - b * ndim;
-  bool active = item < B * ndim && j >= col_begin && j < col_end;
-  bool fill = false;
-  if (active && slot_flags != nullptr) {  // slot table: head mode and dims in use of the wave's env slot (wave-uniform)
-    discrete = slot_flags[b] & 1;
-    fill = j >= (int)slot_act[b];
-    active = !fill;
-  }
-  const int n = discrete ? n_discrete : n_vocab;
-  stage_row<PER>(stage[wv], logits + (int64_t)b * act_dim * n_vocab + (int64_t)j * n_vocab, n, lane, active);
-  if (fill && lane == 0) {  // a column the slot does not use: the fill values, on every call
-    if (tokens != nullptr) tokens[(int64_t)b * act_dim + j] = -1;
-    actions[(int64_t)b * act_dim + j] = 0.f;
-  }
+  const StepItem it = step_item(B, g, s, discrete, col_begin, col_end);
+  const int b = it.b, j = it.j;
+  HeadCol col{discrete};
+  if (it.live) col = head_column(g, s, discrete, b, j);
+  const bool active = it.live && !col.fill;
+  const int64_t o = (int64_t)b * g.act_dim + j;
+  stage_row<PER>(stage[wv], logits + o * g.n_vocab, col.n, lane, active);
+  if (col.fill && lane == 0) store_fill(o, tokens, actions, nullptr);
   if (!active) return;
   const double u = philox_uniform(sp.seed, sp.slot0 + (uint64_t)b, (uint32_t)j, *sp.draw);
   int tok;
-  if constexpr (SLOTS) {  // the env slot's own settings (wave-uniform, like slot_flags[b])
+  if constexpr (SLOTS) {  // the env slot's own settings (wave-uniform, like the slot table's entry)
     const SampleSlot st = slots[b];
-    tok = sample_row<PER>(stage[wv], n, st.temperature, st.top_k, st.top_p, u, lane, st.mode == 0);
+    tok = sample_row<PER>(stage[wv], col.n, st.temperature, st.top_k, st.top_p, u, lane, st.mode == 0);
   } else {
-    tok = sample_row<PER>(stage[wv], n, sp.temperature, sp.top_k, sp.top_p, u, lane);
+    tok = sample_row<PER>(stage[wv], col.n, sp.temperature, sp.top_k, sp.top_p, u, lane);
   }
-  if (lane == 0) {
-    if (tokens != nullptr) tokens[(int64_t)b * act_dim + j] = tok;
-    float out;
-    if (discrete) {
-      out = (float)tok;
-    } else {  // inv_tokenize, as action_argmax_kernel
-      int t = tok - n_discrete;
-      t = t < 0 ? 0 : t;
-      const float bin_width = (tok_max - tok_min) / (float)action_channels;
-      out = inv_tokenize_bin(t, bin_width, tok_min);  // two roundings, as the reference: no FMA
-    }
-    actions[(int64_t)b * act_dim + j] = out;
-  }
+  if (lane == 0) store_action(o, tok, col.discrete, g, tokens, actions);
 }
 
 template <int PER>
 __global__ __launch_bounds__(256) void action_sample_kernel(const float* logits, float* actions, int32_t* tokens, int B,
-                                                            int act_dim, int n_vocab, int n_discrete, int action_channels,
-                                                            float tok_min, float tok_max, int discrete, int col_begin,
-                                                            int col_end, SampleArgs sp, const uint8_t* slot_flags,
-                                                            const uint8_t* slot_act) {
+                                                            HeadGeom g, HeadSlots s, int discrete, int col_begin, int col_end,
+                                                            SampleArgs sp) {
   __shared__ float stage[4][64 * PER];
-  action_sample_body<PER, false>(stage, logits, actions, tokens, B, act_dim, n_vocab, n_discrete, action_channels, tok_min,
-                                 tok_max, discrete, col_begin, col_end, sp, slot_flags, slot_act, nullptr);
+  action_sample_body<PER, false>(stage, logits, actions, tokens, B, g, s, discrete, col_begin, col_end, sp, nullptr);
 }
 
 template <int PER>
 __global__ __launch_bounds__(256) void action_sample_slots_kernel(const float* logits, float* actions, int32_t* tokens, int B,
-                                                                  int act_dim, int n_vocab, int n_discrete,
-                                                                  int action_channels, float tok_min, float tok_max,
-                                                                  int discrete, int col_begin, int col_end, SampleArgs sp,
-                                                                  const uint8_t* slot_flags, const uint8_t* slot_act,
-                                                                  const SampleSlot* slots) {
+                                                                  HeadGeom g, HeadSlots s, int discrete, int col_begin,
+                                                                  int col_end, SampleArgs sp, const SampleSlot* slots) {
   __shared__ float stage[4][64 * PER];
-  action_sample_body<PER, true>(stage, logits, actions, tokens, B, act_dim, n_vocab, n_discrete, action_channels, tok_min,
-                                tok_max, discrete, col_begin, col_end, sp, slot_flags, slot_act, slots);
+  action_sample_body<PER, true>(stage, logits, actions, tokens, B, g, s, discrete, col_begin, col_end, sp, slots);
 }
 
-// log-probabilities of given tokens under the distribution the head above draws from: same grid (always act_dim columns per
-// env, as action_score_kernel), same rows, same settings -- sp's scalars, or the per-slot table where `slots` is given.
-// Columns the slot does not use (j >= act_dim[slot]; j >= 1 on a discrete head) and token -1 get the fill value 0.
+// log-probabilities of given tokens under the distribution the head above draws from: always act_dim columns per env (as
+// action_score_kernel), same rows, same settings -- sp's scalars, or the per-slot table where `slots` is given.
+// Columns the head does not use and token -1 get the fill value 0.
 template <int PER>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void action_logp_kernel(const float* logits, const int32_t* tokens, float* logp, int B,
-                                                          int act_dim, int n_vocab, int n_discrete, int discrete,
-                                                          SampleArgs sp, const uint8_t* slot_flags, const uint8_t* slot_act,
-                                                          const SampleSlot* slots) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void action_logp_kernel(
+    const float* logits, const int32_t* tokens, float* logp, int B, HeadGeom g, HeadSlots s, int discrete, SampleArgs sp,
+    const SampleSlot* slots) {
   __shared__ float stage[4][64 * PER];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int item = blockIdx.x * 4 + wv;
-  const int b = item / act_dim, j = item - b * act_dim;
-  const bool in_grid = item < B * act_dim;
-  bool fill = false;
+  const int b = item / g.act_dim, j = item - b * g.act_dim;
+  const bool in_grid = item < B * g.act_dim;
+  const int64_t o = (int64_t)b * g.act_dim + j;
+  HeadCol col{discrete};
   int tok = -1;
   if (in_grid) {  // (every condition below is the same for the whole wave)
-    if (slot_flags != nullptr) {
-      discrete = slot_flags[b] & 1;
-      fill = j >= (int)slot_act[b];
-    } else {
-      fill = discrete && j >= 1;
-    }
-    tok = tokens[(int64_t)b * act_dim + j];
-    fill = fill || tok == -1;
+    col = head_column(g, s, discrete, b, j);
+    tok = tokens[o];
+    col.fill = col.fill || tok == -1;
   }
-  const bool active = in_grid && !fill;
-  const int n = discrete ? n_discrete : n_vocab;
-  stage_row<PER>(stage[wv], logits + (int64_t)b * act_dim * n_vocab + (int64_t)j * n_vocab, n, lane, active);
-  if (fill && lane == 0) logp[(int64_t)b * act_dim + j] = 0.f;
+  const bool active = in_grid && !col.fill;
+  stage_row<PER>(stage[wv], logits + o * g.n_vocab, col.n, lane, active);
+  if (col.fill && lane == 0) store_fill(o, nullptr, nullptr, logp);
   if (!active) return;
   double temperature = sp.temperature, top_p = sp.top_p;
   int top_k = sp.top_k;
@@ -392,9 +369,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void a
     const SampleSlot st = slots[b];
     temperature = st.temperature, top_p = st.top_p, top_k = st.top_k, greedy = st.mode == 0;
   }
-  const double lp = logp_row<PER>(stage[wv], n, uniform_f64(temperature), uniform_i32(top_k), uniform_f64(top_p),
+  const double lp = logp_row<PER>(stage[wv], col.n, uniform_f64(temperature), uniform_i32(top_k), uniform_f64(top_p),
                                  uniform_i32(tok), lane, uniform_i32(greedy) != 0);
-  if (lane == 0) logp[(int64_t)b * act_dim + j] = (float)lp;
+  if (lane == 0) logp[o] = (float)lp;
 }
 
 __global__ void sample_advance_kernel(uint64_t* draw) {
@@ -453,63 +430,52 @@ __global__ __launch_bounds__(256) void sample_uniforms_kernel(uint64_t seed, uin
 
 }  // namespace
 
-void launch_action_sample(const float* logits, float* actions, int32_t* tokens, int B, int act_dim, int n_vocab,
-                          int n_discrete, int action_channels, float tok_min, float tok_max, int discrete, int col_begin,
-                          int col_end, const SampleArgs& sp, hipStream_t stream, const uint8_t* slot_flags,
-                          const uint8_t* slot_act, const SampleSlot* slots) {
-  LRAM_REQUIRE((slot_flags == nullptr) == (slot_act == nullptr), "action sampling: the slot table's two arrays go together");
-  const bool per_slot = slot_flags != nullptr;
+void launch_action_argmax(const float* logits, float* actions, int32_t* tokens, int B, const HeadGeom& g, const HeadSlots& s,
+                          int discrete, int col_begin, int col_end, hipStream_t stream) {
+  LRAM_REQUIRE((s.flags == nullptr) == (s.act == nullptr), "action head: the slot table's two arrays go together");
+  // with a slot table: one wave per (env, action dim) over all act_dim columns, the head mode is read per env slot
+  const int items = B * step_columns(g, s, discrete);
+  hipLaunchKernelGGL(action_argmax_kernel, dim3((items + 3) / 4), dim3(256), 0, stream, logits, actions, tokens, B, g, s,
+                     discrete, col_begin, col_end);
+  LRAM_HIP_CHECK(hipGetLastError());
+}
+
+void launch_action_sample(const float* logits, float* actions, int32_t* tokens, int B, const HeadGeom& g, const HeadSlots& s,
+                          int discrete, int col_begin, int col_end, const SampleArgs& sp, const SampleSlot* slots,
+                          hipStream_t stream) {
+  LRAM_REQUIRE((s.flags == nullptr) == (s.act == nullptr), "action sampling: the slot table's two arrays go together");
+  const bool per_slot = s.flags != nullptr;
   // with a slot table the rows of one launch differ in length: PER comes from the largest, n_vocab (the engine has checked
   // top_k against n_discrete where the table holds a discrete slot)
-  const int n = (discrete && !per_slot) ? n_discrete : n_vocab;
+  const int n = (discrete && !per_slot) ? g.n_discrete : g.n_vocab;
   LRAM_REQUIRE(n >= 1 && n <= kSampleMaxRow, "action sampling: a row holds 1 .. 512 logits");
   // (per-slot settings: the engine has checked every sampling slot's top_k against the head that slot gets)
   LRAM_REQUIRE(slots != nullptr || sp.top_k <= n, "action sampling: top_k exceeds the number of logits of the head in use");
   LRAM_REQUIRE(sp.draw != nullptr, "action sampling: no draw counter");
-  const int items = B * ((discrete && !per_slot) ? 1 : act_dim);
+  const int items = B * step_columns(g, s, discrete);
   const dim3 grid((items + 3) / 4), block(256);
-  if (col_end < 0) col_end = act_dim;
-#define LRAM_SAMPLE_LAUNCH(PER)                                                                                             \
-  do {                                                                                                                      \
-    if (slots == nullptr)                                                                                                   \
-      hipLaunchKernelGGL(action_sample_kernel<PER>, grid, block, 0, stream, logits, actions, tokens, B, act_dim, n_vocab,   \
-                         n_discrete, action_channels, tok_min, tok_max, discrete, col_begin, col_end, sp, slot_flags,       \
-                         slot_act);                                                                                         \
-    else                                                                                                                    \
-      hipLaunchKernelGGL(action_sample_slots_kernel<PER>, grid, block, 0, stream, logits, actions, tokens, B, act_dim,      \
-                         n_vocab, n_discrete, action_channels, tok_min, tok_max, discrete, col_begin, col_end, sp,          \
-                         slot_flags, slot_act, slots);                                                                      \
-  } while (0)
-  if (n <= 64)
-    LRAM_SAMPLE_LAUNCH(1);
-  else if (n <= 320)
-    LRAM_SAMPLE_LAUNCH(5);
-  else
-    LRAM_SAMPLE_LAUNCH(8);
-#undef LRAM_SAMPLE_LAUNCH
+  with_per(n, [&](auto per) {
+    if (slots == nullptr)
+      hipLaunchKernelGGL(action_sample_kernel<decltype(per)::value>, grid, block, 0, stream, logits, actions, tokens, B, g, s, discrete,
+                         col_begin, col_end, sp);
+    else
+      hipLaunchKernelGGL(action_sample_slots_kernel<decltype(per)::value>, grid, block, 0, stream, logits, actions, tokens, B, g, s, discrete,
+                         col_begin, col_end, sp, slots);
+  });
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
-void launch_action_logp(const float* logits, const int32_t* tokens, float* logp, int B, int act_dim, int n_vocab,
-                        int n_discrete, int discrete, const SampleArgs& sp, hipStream_t stream, const uint8_t* slot_flags,
-                        const uint8_t* slot_act, const SampleSlot* slots) {
-  LRAM_REQUIRE((slot_flags == nullptr) == (slot_act == nullptr), "action logp: the slot table's two arrays go together");
-  LRAM_REQUIRE(logits && tokens && logp && B >= 1 && act_dim >= 1, "action logp: bad arguments");
-  const bool per_slot = slot_flags != nullptr;
-  const int n = (discrete && !per_slot) ? n_discrete : n_vocab;
-  LRAM_REQUIRE(n >= 1 && n <= kSampleMaxRow && n_discrete <= n_vocab, "action logp: a row holds 1 .. 512 logits");
+void launch_action_logp(const float* logits, const int32_t* tokens, float* logp, int B, const HeadGeom& g, const HeadSlots& s,
+                        int discrete, const SampleArgs& sp, const SampleSlot* slots, hipStream_t stream) {
+  LRAM_REQUIRE((s.flags == nullptr) == (s.act == nullptr), "action logp: the slot table's two arrays go together");
+  LRAM_REQUIRE(logits && tokens && logp && B >= 1 && g.act_dim >= 1, "action logp: bad arguments");
+  const int n = (discrete && s.flags == nullptr) ? g.n_discrete : g.n_vocab;
+  LRAM_REQUIRE(n >= 1 && n <= kSampleMaxRow && g.n_discrete <= g.n_vocab, "action logp: a row holds 1 .. 512 logits");
   LRAM_REQUIRE(slots != nullptr || sp.top_k <= n, "action logp: top_k exceeds the number of logits of the head in use");
-  const dim3 grid((B * act_dim + 3) / 4), block(256);
-#define LRAM_LOGP_LAUNCH(PER)                                                                                           \
-  hipLaunchKernelGGL(action_logp_kernel<PER>, grid, block, 0, stream, logits, tokens, logp, B, act_dim, n_vocab, n_discrete, \
-                     discrete, sp, slot_flags, slot_act, slots)
-  if (n <= 64)
-    LRAM_LOGP_LAUNCH(1);
-  else if (n <= 320)
-    LRAM_LOGP_LAUNCH(5);
-  else
-    LRAM_LOGP_LAUNCH(8);
-#undef LRAM_LOGP_LAUNCH
+  const dim3 grid((B * g.act_dim + 3) / 4), block(256);
+  with_per(n, [&](auto per) {
+    hipLaunchKernelGGL(action_logp_kernel<decltype(per)::value>, grid, block, 0, stream, logits, tokens, logp, B, g, s, discrete, sp, slots);
+  });
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
@@ -523,16 +489,10 @@ void launch_sample_tokens(const float* logits, int64_t rows, int n, int64_t ld, 
   LRAM_REQUIRE(n >= 1 && n <= kSampleMaxRow, "sample tokens: a row holds 1 .. 512 logits");
   LRAM_REQUIRE(rows >= 1 && rows <= ((int64_t)1 << 32), "sample tokens: rows must be in 1 .. 2^32");
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-#define LRAM_SAMPLE_LAUNCH(PER)                                                                                \
-  hipLaunchKernelGGL(sample_tokens_kernel<PER>, grid, block, 0, stream, logits, rows, n, ld, temperature, top_k, \
-                     top_p, uniform, tokens)
-  if (n <= 64)
-    LRAM_SAMPLE_LAUNCH(1);
-  else if (n <= 320)
-    LRAM_SAMPLE_LAUNCH(5);
-  else
-    LRAM_SAMPLE_LAUNCH(8);
-#undef LRAM_SAMPLE_LAUNCH
+  with_per(n, [&](auto per) {
+    hipLaunchKernelGGL(sample_tokens_kernel<decltype(per)::value>, grid, block, 0, stream, logits, rows, n, ld, temperature, top_k, top_p,
+                       uniform, tokens);
+  });
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
@@ -542,16 +502,10 @@ void launch_sample_rows(const float* logits, int64_t rows, int n, int64_t ld, co
   LRAM_REQUIRE(n >= 1 && n <= kSampleMaxRow, "sample rows: a row holds 1 .. 512 logits");
   LRAM_REQUIRE(rows >= 1 && rows <= ((int64_t)1 << 32), "sample rows: rows must be in 1 .. 2^32");
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-#define LRAM_SAMPLE_LAUNCH(PER)                                                                                         \
-  hipLaunchKernelGGL(sample_rows_kernel<PER>, grid, block, 0, stream, logits, rows, n, ld, mode, temperature, top_k, top_p, \
-                     uniform, tokens_in, tokens_out, logp_out)
-  if (n <= 64)
-    LRAM_SAMPLE_LAUNCH(1);
-  else if (n <= 320)
-    LRAM_SAMPLE_LAUNCH(5);
-  else
-    LRAM_SAMPLE_LAUNCH(8);
-#undef LRAM_SAMPLE_LAUNCH
+  with_per(n, [&](auto per) {
+    hipLaunchKernelGGL(sample_rows_kernel<decltype(per)::value>, grid, block, 0, stream, logits, rows, n, ld, mode, temperature, top_k, top_p,
+                       uniform, tokens_in, tokens_out, logp_out);
+  });
   LRAM_HIP_CHECK(hipGetLastError());
 }
 

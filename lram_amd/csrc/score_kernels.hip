@@ -6,11 +6,11 @@
 // with the targets tokenised as MinMaxTokenizer.tokenize does (src/tokenizers_custom/minmax_tokenizer.py:14-29) and
 // `temperature` multiplying the logits as sample_from_logits does (src/algos/models/model_utils.py:7-32).
 //
-// One wave per (row, action dim), four per workgroup: the grid of action_argmax_kernel (misc_kernels.hip) and
-// action_sample_kernel (sample_kernels.hip).  The row is read from global memory ONCE, coalesced, into the wave's LDS strip
-// (and from there, if asked, copied to the caller's logits tensor); everything else walks the strip:
-//   greedy token   first index of the maximum over the selectable range (argmax_beats: the argmax kernel's rule), then its
-//                  inv_tokenize arithmetic: a row gives the same token and action on both kernels
+// One wave per (row, action dim), four per workgroup, as action_argmax_kernel and action_sample_kernel (sample_kernels.hip).
+// The row is read from global memory ONCE, coalesced, into the wave's LDS strip (and on the way, if asked, copied to the caller's
+// logits tensor); everything else walks the strip:
+//   greedy token   first index of the maximum over the selectable range, then its action: the rules of action_head.h, which the
+//                  argmax and sampling kernels apply too -- a row gives the same token and action on all of them
 //   target token   an int32 token, or a float action tokenised here: trunc((x - min) / bin_width) clamped to
 //                  0 .. action_channels - 1, plus n_discrete -- fp32 subtract, IEEE fp32 division; discrete rows: (int)x
 //   logp           t * x[target] - logsumexp(t * x) over the normalisation range; maximum, sum and log in fp64, one fp32
@@ -20,8 +20,7 @@
 // target: -inf.  Rows with valid[row] == 0, columns j >= act_dim[slot] of a slot table and columns j >= 1 of a discrete call
 // write logp 0, token -1, action 0 and nothing else (wave-uniform branch).  Rows wider than 512 logits are not staged: they
 // are walked in global memory (the second walk is served by the cache).
-#include "common.h"
-#include "device_math.h"
+#include "action_head.h"
 
 namespace lram {
 namespace {
@@ -51,9 +50,9 @@ struct ScoreItem {
 __device__ __forceinline__ ScoreItem score_item(const ScoreArgs& a) {
   ScoreItem it;
   const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  it.in_grid = item < a.rows * a.act_dim;
-  it.r = it.in_grid ? item / a.act_dim : 0;
-  it.j = it.in_grid ? (int)(item - it.r * a.act_dim) : 0;
+  it.in_grid = item < a.rows * a.geom.act_dim;
+  it.r = it.in_grid ? item / a.geom.act_dim : 0;
+  it.j = it.in_grid ? (int)(item - it.r * a.geom.act_dim) : 0;
   const int64_t g = a.row0 + it.r;
   it.env = g / a.inner;
   it.orow = it.env * a.outer + a.off + (g - it.env * a.inner);
@@ -77,53 +76,31 @@ __device__ __forceinline__ ScoreItem score_item_ragged(const ScoreArgs& a) {
 template <int PER>
 __device__ __forceinline__ void score_row(const ScoreArgs& a, const ScoreItem& it, float (*stage)[64 * (PER > 0 ? PER : 1)]) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const bool in_grid = it.in_grid;
-  const int64_t r = it.r, env = it.env, orow = it.orow;
-  const int j = it.j;
-  const int64_t o = orow * a.act_dim + j;
-  int discrete = a.discrete;
-  bool fill = false;
-  if (in_grid) {  // (every condition below is the same for the whole wave)
-    if (it.pad || (a.valid != nullptr && a.valid[orow] == 0)) {
-      fill = true;
-    } else if (a.slot_flags != nullptr) {
-      discrete = a.slot_flags[env] & 1;
-      fill = j >= (int)a.slot_act[env];
-    } else {
-      fill = discrete && j >= 1;
-    }
+  const HeadGeom& g = a.geom;
+  const int64_t o = it.orow * g.act_dim + it.j;
+  HeadCol col{a.discrete};
+  if (it.in_grid) {  // (every condition below is the same for the whole wave)
+    if (it.pad || (a.valid != nullptr && a.valid[it.orow] == 0))
+      col.fill = true;
+    else
+      col = head_column(g, a.slots, a.discrete, it.env, it.j);
   }
-  const bool active = in_grid && !fill;
-  const int nsel = discrete ? a.n_discrete : a.n_vocab;      // the greedy token's range
-  const int nnorm = a.over ? nsel : a.n_vocab;               // the softmax's range (>= nsel)
-  const int nread = (a.logits_out != nullptr || !a.over) ? a.n_vocab : nsel;
-  const float* src = a.logits + r * a.ld + (int64_t)j * a.n_vocab;
-  const float* row = src;
+  const bool active = it.in_grid && !col.fill;
+  const int nsel = col.n;                                    // the greedy token's range
+  const int nnorm = a.over ? nsel : g.n_vocab;               // the softmax's range (>= nsel)
+  const int nread = (a.logits_out != nullptr || !a.over) ? g.n_vocab : nsel;
+  const float* row = a.logits + it.r * a.ld + (int64_t)it.j * g.n_vocab;
   if constexpr (PER > 0) {
-    if (active) {
-#pragma unroll
-      for (int q = 0; q < PER; ++q) {
-        const int i = lane + 64 * q;
-        if (i < nread) {
-          const float x = src[i];
-          stage[wv][i] = x;
-          if (a.logits_out != nullptr) a.logits_out[o * a.n_vocab + i] = x;
-        }
-      }
-    }
-    __syncthreads();
+    stage_row<PER>(stage[wv], row, nread, lane, active, a.logits_out, o * g.n_vocab);
     row = stage[wv];
   } else {
     if (active && a.logits_out != nullptr)
-      for (int i = lane; i < nread; i += 64) a.logits_out[o * a.n_vocab + i] = src[i];
+      for (int i = lane; i < nread; i += 64) a.logits_out[o * g.n_vocab + i] = row[i];
   }
-  if (fill && lane == 0) {
-    if (a.logp != nullptr) a.logp[o] = 0.f;
-    if (a.tokens != nullptr) a.tokens[o] = -1;
-    if (a.actions != nullptr) a.actions[o] = 0.f;
-  }
+  if (col.fill && lane == 0) store_fill(o, a.tokens, a.actions, a.logp);
   if (!active) return;
 
+  // one walk: the greedy token over the selectable range, the maximum and the NaN flag over the normalisation range
   float best = -INFINITY, vmax = -INFINITY;
   int bi = 0x7fffffff;
   bool nan_here = false;
@@ -131,30 +108,13 @@ __device__ __forceinline__ void score_row(const ScoreArgs& a, const ScoreItem& i
     const float x = row[i];
     nan_here |= x != x;
     vmax = fmaxf(vmax, x);
-    if (i < nsel && argmax_beats(x, i, best, bi)) best = x, bi = i;
+    argmax_take(x, i, best, bi, i < nsel);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(best, off, 64);
-    const int oi = __shfl_xor(bi, off, 64);
-    if (argmax_beats(ov, oi, best, bi)) best = ov, bi = oi;
-    vmax = fmaxf(vmax, __shfl_xor(vmax, off, 64));
-  }
+  wave_argmax(best, bi, &vmax);
   const bool has_nan = __any(nan_here);
   if (lane == 0) {
     if (a.tokens != nullptr) a.tokens[o] = bi;
-    if (a.actions != nullptr) {
-      float out;
-      if (discrete) {
-        out = (float)bi;
-      } else {  // inv_tokenize, as action_argmax_kernel
-        int t = bi - a.n_discrete;
-        t = t < 0 ? 0 : t;
-        const float bin_width = (a.tok_max - a.tok_min) / (float)a.action_channels;
-        out = inv_tokenize_bin(t, bin_width, a.tok_min);  // two roundings, as the reference: no FMA
-      }
-      a.actions[o] = out;
-    }
+    if (a.actions != nullptr) a.actions[o] = detokenise(bi, col.discrete, g);
   }
   if (a.logp == nullptr) return;
 
@@ -164,17 +124,8 @@ __device__ __forceinline__ void score_row(const ScoreArgs& a, const ScoreItem& i
     tgt = a.target_tokens[o];
   } else {
     const float x = a.target_actions[o];
-    if (x - x == 0.f) {  // finite
-      if (discrete) {
-        tgt = (int)x;
-      } else {  // MinMaxTokenizer.tokenize
-        const float bin_width = (a.tok_max - a.tok_min) / (float)a.action_channels;
-        const float q = __fdiv_rn(__fsub_rn(x, a.tok_min), bin_width);
-        const float top = (float)(a.action_channels - 1);
-        const int t = q <= 0.f ? 0 : (q >= top ? a.action_channels - 1 : (int)q);
-        tgt = t + a.n_discrete;
-      }
-    }
+    if (x - x == 0.f)  // finite
+      tgt = col.discrete ? (int)x : tokenize_bin(x, head_bin_width(g), g.tok_min, g.action_channels) + g.n_discrete;
   }
   // (t > 0 and rounding is monotone: the maximum of t * x is t * max x)
   const double zmax = a.temperature * (double)vmax;
@@ -210,11 +161,12 @@ __global__ __launch_bounds__(256) void action_score_ragged_kernel(ScoreArgs a) {
 
 void launch_action_score(const ScoreArgs& a, hipStream_t stream) {
   LRAM_REQUIRE(a.logits != nullptr && a.rows >= 1 && a.inner >= 1, "action score: bad rows");
-  LRAM_REQUIRE(a.act_dim >= 1 && a.n_vocab >= 1 && a.n_discrete >= 0 && a.n_discrete <= a.n_vocab && a.action_channels >= 1,
+  const HeadGeom& g = a.geom;
+  LRAM_REQUIRE(g.act_dim >= 1 && g.n_vocab >= 1 && g.n_discrete >= 0 && g.n_discrete <= g.n_vocab && g.action_channels >= 1,
                "action score: bad head dimensions");
-  LRAM_REQUIRE(!(a.discrete == 1 && a.slot_flags == nullptr && a.n_discrete < 1), "action score: a discrete head needs n_discrete >= 1");
-  LRAM_REQUIRE(a.ld >= (int64_t)a.act_dim * a.n_vocab, "action score: ld must be >= act_dim * n_vocab");
-  LRAM_REQUIRE((a.slot_flags == nullptr) == (a.slot_act == nullptr), "action score: the slot table's two arrays go together");
+  LRAM_REQUIRE(!(a.discrete == 1 && a.slots.flags == nullptr && g.n_discrete < 1), "action score: a discrete head needs n_discrete >= 1");
+  LRAM_REQUIRE(a.ld >= (int64_t)g.act_dim * g.n_vocab, "action score: ld must be >= act_dim * n_vocab");
+  LRAM_REQUIRE((a.slots.flags == nullptr) == (a.slots.act == nullptr), "action score: the slot table's two arrays go together");
   LRAM_REQUIRE(a.over == 0 || a.over == 1, "action score: over must be 0 (the whole vocabulary) or 1 (the selectable range)");
   LRAM_REQUIRE(a.temperature > 0.0 && a.temperature < (double)INFINITY, "action score: temperature must be finite and > 0");
   LRAM_REQUIRE(a.target_actions == nullptr || a.target_tokens == nullptr,
@@ -223,25 +175,19 @@ void launch_action_score(const ScoreArgs& a, hipStream_t stream) {
                "action score: logp needs a target (target_actions or target_tokens)");
   LRAM_REQUIRE(a.actions != nullptr || a.tokens != nullptr || a.logp != nullptr || a.logits_out != nullptr,
                "action score: no output is given");
-  const int64_t items = a.rows * a.act_dim;
+  const int64_t items = a.rows * a.geom.act_dim;
   LRAM_REQUIRE(items <= ((int64_t)1 << 32), "action score: rows * act_dim must be <= 2^32");
   const dim3 grid((unsigned)((items + 3) / 4)), block(256);
-#define LRAM_SCORE_LAUNCH(PER)                                                              \
-  do {                                                                                      \
-    if (a.start != nullptr)                                                                 \
-      hipLaunchKernelGGL(action_score_ragged_kernel<PER>, grid, block, 0, stream, a);       \
-    else                                                                                    \
-      hipLaunchKernelGGL(action_score_kernel<PER>, grid, block, 0, stream, a);              \
-  } while (0)
-  if (a.n_vocab <= 64)
-    LRAM_SCORE_LAUNCH(1);
-  else if (a.n_vocab <= 320)
-    LRAM_SCORE_LAUNCH(5);
-  else if (a.n_vocab <= kSampleMaxRow)
-    LRAM_SCORE_LAUNCH(8);
+  auto launch = [&](auto per) {
+    if (a.start != nullptr)
+      hipLaunchKernelGGL(action_score_ragged_kernel<decltype(per)::value>, grid, block, 0, stream, a);
+    else
+      hipLaunchKernelGGL(action_score_kernel<decltype(per)::value>, grid, block, 0, stream, a);
+  };
+  if (a.geom.n_vocab > kSampleMaxRow)
+    launch(std::integral_constant<int, 0>{});  // not staged: walked in global memory
   else
-    LRAM_SCORE_LAUNCH(0);
-#undef LRAM_SCORE_LAUNCH
+    with_per(a.geom.n_vocab, launch);
   LRAM_HIP_CHECK(hipGetLastError());
 }
 

@@ -1,9 +1,14 @@
 """The compiler's view of every GEMM kernel instance at two commits, for refactors that must not move the generated code.
-  gemm_isa_compare.py dump TREE OUTDIR              csrc/gemm_*.hip of a checkout -> OUTDIR/*.s + *.remarks (device only,
-                                                    the build's flags + -S -Rpass-analysis=kernel-resource-usage; no GPU needed)
+  gemm_isa_compare.py dump TREE OUTDIR [SOURCE ...] csrc/gemm_*.hip of a checkout -> OUTDIR/*.s + *.remarks (device only,
+                                                    the build's flags + -S -Rpass-analysis=kernel-resource-usage; no GPU needed);
+                                                    SOURCE: other file names or globs under csrc (sample_kernels.hip '*_kernels.hip')
   gemm_isa_compare.py compare OUT_A OUT_B REPORT    per instance: resources, K loop (first to last v_mfma), rest of the kernel
+  gemm_isa_compare.py resources OUT_A OUT_B REPORT  per instance: resources and a verdict only, for refactors that may move the code
+                                                    (changed argument lists) but not what a kernel occupies: no scratch, no spill,
+                                                    B's LDS = A's, B's occupancy >= A's; instances are matched by kernel name and
+                                                    template arguments, whatever their parameters and whichever file holds them
 Comments, debug directives, alignment directives, the __hip_cuid_* symbol and the function number in local labels are stripped
-before texts are compared.  (profiles/gemm_refactor_isa.txt is a report of this script.)"""
+before texts are compared.  (profiles/gemm_refactor_isa.txt and profiles/head_refactor_isa.txt are reports of this script.)"""
 import difflib
 import glob
 import os
@@ -19,8 +24,10 @@ from lram_amd.build import FLAGS  # noqa: E402
 KEYS = ["VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]"]
 
 
-def dump(tree, out):
+def dump(tree, out, patterns=()):
     os.makedirs(out, exist_ok=True)
+    csrc = os.path.join(tree, "lram_amd", "csrc")
+    sources = sorted({f for pat in (patterns or ["gemm_*.hip"]) for f in glob.glob(os.path.join(csrc, pat))})
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
     def one(src):
@@ -30,7 +37,7 @@ def dump(tree, out):
         open(os.path.join(out, base + ".remarks"), "w").write(p.stderr)
         return base, p.returncode
     with ThreadPoolExecutor(max_workers=6) as pool:
-        print(list(pool.map(one, sorted(glob.glob(os.path.join(tree, "lram_amd", "csrc", "gemm_*.hip"))))))
+        print(list(pool.map(one, sources)))
 
 
 def canon(name):
@@ -40,7 +47,13 @@ def canon(name):
     return re.sub(r"(gemm_f16x2_8p_kernelILb[01]ELb[01]E)Li0E(E)", r"\1\2", name)
 
 
-def resources(path):
+def kernel_id(name):
+    """Kernel name + template arguments of a mangled instance name: what is left once the parameter list is out of it."""
+    m = re.search(r"\d+([a-z0-9_]+_kernel)(I(?:L[a-z]n?\d+E)+E)?", name)
+    return m.group(1) + (m.group(2) or "") if m else name
+
+
+def resources(path, canon=canon):
     res, name = {}, None
     for line in open(path):
         m = re.search(r"Function Name: (\S+)", line)
@@ -112,8 +125,34 @@ def compare(pa, nw, report, shown=40):
     print(out[-1])
 
 
+def compare_resources(pa, nw, report):
+    keys = KEYS + ["VGPRs Spill", "SGPRs Spill"]
+    ra, rb = ({k: v for f in sorted(glob.glob(os.path.join(d, "*.remarks"))) for k, v in resources(f, kernel_id).items()}
+              for d in (pa, nw))
+    out, bad = ["The compiler's view of every kernel instance of the dumped files at two commits.", "resources only; A = " + os.path.basename(pa.rstrip("/")) + ", B = " + os.path.basename(nw.rstrip("/")), ""], 0
+    if set(ra) != set(rb):
+        bad += 1
+        out.append(f"INSTANCE SETS DIFFER: only A {sorted(set(ra) - set(rb))}, only B {sorted(set(rb) - set(ra))}")
+    for name in sorted(set(ra) & set(rb)):
+        a, b = ra[name], rb[name]
+        why = [f"{k} {b.get(k)}" for k in ("ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill") if b.get(k) != 0]
+        if b.get(KEYS[4]) != a.get(KEYS[4]):
+            why.append("LDS differs")
+        if b.get(KEYS[5], 0) < a.get(KEYS[5], 0):
+            why.append("occupancy below A's")
+        bad += bool(why)
+        out += [name, "  A: " + ", ".join(f"{k} {a.get(k)}" for k in keys), "  B: " + ", ".join(f"{k} {b.get(k)}" for k in keys),
+                "  " + ("ok" if not why else "NOT OK: " + "; ".join(why)) +
+                ("" if all(a.get(k) == b.get(k) for k in keys) else "   (registers differ)")]
+    out += ["", f"{len(set(ra) & set(rb))} instances; not ok: {bad}"]
+    open(report, "w").write("\n".join(out) + "\n")
+    print(out[-1])
+
+
 if __name__ == "__main__":
     if sys.argv[1] == "dump":
-        dump(sys.argv[2], sys.argv[3])
+        dump(sys.argv[2], sys.argv[3], sys.argv[4:])
+    elif sys.argv[1] == "resources":
+        compare_resources(sys.argv[2], sys.argv[3], sys.argv[4])
     else:
         compare(sys.argv[2], sys.argv[3], sys.argv[4])

@@ -29,6 +29,12 @@ CASES = {
     "over512": (12, 2, 500, 18),
     "disc300": (20, 1, 1, 300),
 }
+# The two row widths just past a PER class of the staged head kernels (V = 65: PER 5 at its lower edge, V = 321: PER 8 at its),
+# which no case above has: for tests/test_gpu_head_one_rule.py only, so the sweeps over CASES stay what they are.
+EDGE_CASES = {
+    "v65": (20, 3, 47, 18),
+    "v321": (20, 2, 303, 18),
+}
 BACKBONES = {
     "xlstm": dict(backbone="xlstm", kind="MDDXLSTM", d_model=128, n_blocks=2, slstm_at=[1]),
     "mamba": dict(backbone="mamba", kind="MDDMamba", d_model=64, n_blocks=2),
@@ -43,7 +49,7 @@ CONTEXT_L = 9         # stored contexts: two token-sequential chunks on Mamba
 
 
 def case_spec(cid, backbone, pred_token=1):
-    s, a, c, d = CASES[cid]
+    s, a, c, d = CASES[cid] if cid in CASES else EDGE_CASES[cid]
     return ModelSpec(**BACKBONES[backbone], state_dim=s, act_dim=a, action_channels=c, n_discrete=d, pred_token=pred_token)
 
 
