@@ -236,8 +236,9 @@ int32_t lram_score(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embe
  * d_model] embeddings exceed 2 GiB; the Mamba modes of lram_set_compat_mode (mamba_repeat > 1; stale_state, where a reset
  * re-initialises layer 0 only and the padding would leak into layers >= 1); scratch for the n_b == 0 slots that would leave less
  * than 2 GiB of device memory free.
- * Out of scope: a SHORTER context that CONTINUES a slot's state (needs length-aware state kernels); running a call on a subset of
- * slots without computing the other rows (kept slots are saved and restored, not skipped); image frames as stored contexts; the
+ * Out of scope: a SHORTER context that CONTINUES a slot's state (needs length-aware state kernels); stored contexts on a subset
+ * of slots without computing the other rows (kept slots are saved and restored, not skipped; env-STEPS on a live prefix of the
+ * slots are lram_set_live's, below, and these entries are refused while slots are parked); image frames as stored contexts; the
  * Mamba reference-trajectory modes.  The dense entries, the lazy step path and the GEMM dispatcher are unchanged. */
 int32_t lram_prefill_ragged(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
                             const float* dev_reward_seq, int32_t timesteps, const int32_t* host_lengths,
@@ -366,6 +367,47 @@ int64_t lram_slot_state_numel(const lram_engine* e);
 int32_t lram_state_copy_slots(lram_engine* e, const int32_t* host_src, const int32_t* host_dst, int32_t n, void* stream);
 int32_t lram_state_save_slots(lram_engine* e, const int32_t* host_slots, int32_t n, float* dev_records, void* stream);
 int32_t lram_state_load_slots(lram_engine* e, const int32_t* host_slots, int32_t n, const float* dev_records, void* stream);
+
+/* Live prefix: step only the env slots that have something to do.
+ * The state is allocated for `batch` slots; at any time the first n_live of them are LIVE and slots [n_live, batch) are PARKED.
+ * A parked slot keeps its recurrent state and no activation row of it is computed, read or written; what a step still does for
+ * it is the lazy matrix memory's bookkeeping (below: a few KB per slot carried to the step's ping-pong side, one fold when its
+ * class comes due).  Which env sits
+ * in which slot is the caller's business; slots are exchanged with lram_state_swap_slots.  The reference has no counterpart: its
+ * batched evaluation keeps forwarding an env that has stopped contributing and throws the result away (evaluation.py:184,
+ * 205-212: the `unfinished` mask only gates what is accumulated).
+ *
+ * lram_set_live: n_live in 1 .. batch.  Cheap: host bookkeeping only, no device synchronisation, no allocation.  Completes a
+ *   pending tail fold of the lazy matrix memory on `stream`; drops a captured graph only if n_live changes (n_live is one more
+ *   field of the captured step's key).  lram_state_alloc sets n_live = batch, and with n_live == batch every launch, argument and
+ *   bit is what it is on an engine that never called the setter.
+ * lram_get_live: the current n_live (0: no engine / no state).
+ * With n_live < batch:
+ *   - lram_step, lram_step_images, lram_step_slots, lram_score_last, lram_score_last_sampled and lram_get_taps read and write rows
+ *     < n_live only: every per-slot input, the reset mask included, and every output needs n_live rows; nothing beyond is touched.
+ *     The slice, kernel and fusion rules are judged on the live rows, as on an engine allocated with n_live slots; the state
+ *     mode (lazy or materialised) was chosen at allocation and does not move.
+ *   - lram_step_slots takes the frames of the image slots below n_live, in ascending slot order.
+ *   - A step's mask never resets a parked slot; lram_reset takes a `batch`-wide mask and may.
+ *   - Sampling: a call is one draw, the counter is engine-wide; a parked slot simply does not draw.
+ *   - Lazy matrix memory: folds keep covering every allocated slot of the class that is due until every class has come due once
+ *     since the live count changed or a swap / copy moved a window (a parked slot is folded at most once, the host-side bounds
+ *     stay true; afterwards every parked window is empty and no fold is launched over them); one small launch per mLSTM block
+ *     and step carries the parked slots' bookkeeping over to the step's ping-pong side.  A parked slot's record (lram_state_save_slots) stays within the fold's rounding in C
+ *     and bit-identical in every other tensor.
+ *   - Refused (message in lram_last_error, nothing launched): lram_prefill, lram_score, their ragged forms, lram_encoder_step.
+ *   - Unchanged, on all `batch` slots: lram_state_export / import, lram_state_copy_slots / save / load / swap, lram_lazy_peek,
+ *     lram_reset, lram_set_slot_table, lram_set_sampling_slots.
+ *
+ * lram_state_swap_slots: exchanges the recurrent state of slots host_a[i] and host_b[i], live or parked, in ONE launch; folds
+ *   nothing and touches no other slot.  Lists as lram_state_copy_slots' (HOST int32); all 2n indices distinct and in range, else
+ *   refused with nothing launched.  Lazy mode: the representation moves as it is (C_base, window rows, the live side of
+ *   coefficients / scale / count word) and the host-side pending bound of both fold classes is raised to the larger of the two.
+ *   After it record[a] is the old record[b] bit for bit, and vice versa.  Slot-table entries, per-slot sampling settings and the
+ *   Philox stream stay with the slot INDEX, as for a copy. */
+int32_t lram_set_live(lram_engine* e, int32_t n_live, void* stream);
+int32_t lram_get_live(const lram_engine* e);
+int32_t lram_state_swap_slots(lram_engine* e, const int32_t* host_a, const int32_t* host_b, int32_t n, void* stream);
 
 /* Micro-batch pipeline (xLSTM): the env slots are processed as `n` slices on engine-owned HIP streams; the
  * HBM-bound matrix-memory kernels of all slices run back to back on one stream while the other slices'

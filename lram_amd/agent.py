@@ -28,6 +28,7 @@ import torch
 
 from .config import ModelSpec
 from .engine import Engine, check_context_lengths
+from .rollout import SlotScheduler
 
 
 SAMPLE_DEFAULTS = {"temperature": 1.0, "top_k": 0, "top_p": 0.5}   # sample_from_logits' own (model_utils.py:7)
@@ -140,6 +141,7 @@ class RecurrentAgent:
         if graph:
             self.engine.set_graph_mode(True)
         self._zero_reward = torch.zeros(n_envs, dtype=torch.float32, device=self.device)
+        self.scheduler = SlotScheduler(n_envs)   # env id <-> engine slot while envs are parked (set_active)
         # Reference-trajectory modes of the Mamba agent (lram_set_compat_mode).  Off: one state
         # advance per env-step and a reset empties every layer.  On: the trajectory the reference's
         # DiscreteDecisionMamba.get_action_pred / InferenceParams.reset() actually produce.
@@ -308,6 +310,75 @@ class RecurrentAgent:
         self._need_batch("load_slots")
         self.engine.load_slots(slots, records)
 
+    # ---- parked envs: step only the envs that have something to do -------------------------------------
+    @property
+    def active(self):
+        """Env ids the agent steps, in engine slot order (every env unless set_active parked some)."""
+        sch = getattr(self, "scheduler", None)
+        return list(range(self.n_envs)) if sch is None else sch.live_envs()
+
+    def _slots_alike(self, a: int, b: int) -> Optional[str]:
+        """None where slots a and b carry the same slot-table entry and per-slot sampling setting, else what differs."""
+        table = getattr(self, "slot_table", None)
+        if table is not None:
+            for name in ("discrete", "act_dim", "image"):
+                col = getattr(table, name)
+                if col[a] != col[b]:
+                    return f"slot-table entry `{name}`"
+        cols = self.slot_sample_settings()
+        if cols is not None:
+            for name, col in cols.items():
+                if col[a] != col[b]:
+                    return f"per-slot sampling setting `{name}`"
+        return None
+
+    def set_active(self, env_ids):
+        """The envs predict_batch steps from now on (at least one).  The others are parked: their recurrent state stays in the
+        engine and a step costs them nothing (Engine.set_live); their rows of predict_batch's result hold 0.  The engine steps a
+        prefix of its slots, so parking and resuming exchange the state of slot pairs (Engine.swap_slots; at most one swap per
+        parked or resumed env, SlotScheduler).  Slot-table entries, per-slot sampling settings and the sampling stream stay
+        with the slot index: a change that would exchange two slots whose entries differ is refused (ValueError) with nothing
+        done.  fork_slots / save_slots / load_slots keep addressing engine SLOTS (scheduler.slot_of maps an env id)."""
+        import copy
+        want = [int(e) for e in env_ids]
+        if len(set(want)) != len(want) or any(not 0 <= e < self.n_envs for e in want):
+            raise ValueError(f"set_active: expected distinct env ids in 0 .. {self.n_envs - 1}")
+        if not want:
+            raise ValueError("set_active: at least one env must stay active")
+        sch = copy.deepcopy(self.scheduler)
+        now = set(sch.live_envs())
+        calls = []
+        # resume first: a change to a disjoint set (active {0} -> {1}) must not pass through an empty live set
+        resume = sorted(set(want) - now)
+        if resume:
+            calls.append(sch.resume(resume))
+        park = sorted(now - set(want))
+        if park:
+            calls.append(sch.park(park))
+        for a, b, _ in calls:
+            for sa, sb in zip(a, b):
+                diff = self._slots_alike(sa, sb)
+                if diff is not None:
+                    raise ValueError(f"set_active: would exchange engine slots {sa} and {sb}, whose {diff} differs -- those stay "
+                                     f"with the slot index (park envs of one domain and setting among themselves)")
+        for a, b, n_live in calls:
+            if a:
+                self.engine.swap_slots(a, b)
+            self.engine.set_live(n_live)
+        self.scheduler = sch
+
+    def _live_index(self) -> Optional[torch.Tensor]:
+        """Env id of every live slot as a device index, or None on today's path: every env active, identity permutation."""
+        sch = getattr(self, "scheduler", None)
+        if sch is None or (sch.n_live == sch.n and sch.identity):
+            return None
+        return torch.as_tensor(sch.live_envs(), dtype=torch.long, device=self.device)
+
+    def _scatter_rows(self, rows: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+        out = torch.zeros(self.n_envs, *rows.shape[1:], dtype=rows.dtype, device=rows.device)
+        out[idx] = rows
+        return out
+
     # ---- multiprocess evaluation (src/callbacks/custom_eval_callback.py:22-33, decision_xlstm.py:243-267) ----
     def make_pickleable(self, replace_cell: bool = False):
         """The native engine handle cannot be serialised: release it (spec and host weights stay), as the reference
@@ -321,6 +392,7 @@ class RecurrentAgent:
         armed again with the same settings, the per-slot ones included, and its draw count restarts at 0)."""
         if self.engine is None:
             self.engine = Engine(self.spec, self._state_dict, self.n_envs, self.device)
+            self.scheduler = SlotScheduler(self.n_envs)   # (fresh state: every env live, in its own slot)
             if self._graph:
                 self.engine.set_graph_mode(True)
             if self.compat_stale_state or self._compat_repeat_now != 1:
@@ -383,9 +455,18 @@ class RecurrentAgent:
         With a slot table `observation` is the pair (vector_obs [B, obs_dim] or None, images uint8 [n_image, C, H, W] or None):
         rows of vector_obs that belong to image slots are never read, frame k belongs to the k-th image slot.  Returns float32
         [B, act_dim]: a continuous slot's action in the columns below its act_dim, a discrete slot's index in column 0 (exact in
-        fp32), 0.0 elsewhere; `env_act_dim` is ignored."""
+        fp32), 0.0 elsewhere; `env_act_dim` is ignored.
+        With parked envs (set_active) the tensors stay full-width in env-id order: the live rows are gathered in slot order,
+        stepped, and the actions scattered back; the rows of parked envs hold 0 (then a fresh tensor, not an engine buffer), and
+        their reset flags are not looked at."""
         if getattr(self, "slot_table", None) is not None:
             return self._predict_batch_slots(observation, returns_to_go, rewards, reset_mask)
+        idx = self._live_index()   # (None: every env active in its own slot -- no gather)
+        if idx is not None:
+            observation = observation.to(self.device)[idx]
+            returns_to_go = returns_to_go.to(self.device).reshape(-1)[idx]
+            rewards = None if rewards is None else rewards.to(self.device).reshape(-1)[idx]
+            reset_mask = None if reset_mask is None else reset_mask.to(self.device).reshape(-1)[idx]
         images = observation.dim() == 4
         if images:   # frames go to the engine as they are: lram_step_images runs the CNN inside the step (per env slice)
             if not self.has_image_encoder:
@@ -394,7 +475,7 @@ class RecurrentAgent:
         else:
             obs, is_emb = self._prepare_obs(observation)
         rtg = returns_to_go.to(self.device, torch.float32).reshape(-1).contiguous()
-        rew = self._zero_reward if rewards is None else rewards.to(self.device, torch.float32).reshape(-1).contiguous()
+        rew = self._zero_reward[:rtg.shape[0]] if rewards is None else rewards.to(self.device, torch.float32).reshape(-1).contiguous()
         if reset_mask is not None:
             reset_mask = reset_mask.to(self.device, torch.uint8).contiguous()
         if getattr(self, "compat_mamba_repeat", False):
@@ -407,6 +488,8 @@ class RecurrentAgent:
             actions, _ = self.engine.step_images(obs, rtg, rew, reset_mask, discrete=self.is_discrete)
         else:
             actions, _ = self.engine.step(obs, rtg, rew, reset_mask, discrete=self.is_discrete, obs_is_embedding=is_emb)
+        if idx is not None:   # back to env-id order; the rows of parked envs hold 0
+            actions = self._scatter_rows(actions, idx)
         if self.is_discrete:
             return actions[:, :1].to(torch.int64)
         return actions if env_act_dim is None else actions[:, :env_act_dim]
@@ -492,15 +575,22 @@ class RecurrentAgent:
         over="selectable" / "vocab": under the unfiltered softmax -- the agent-level temperature multiplies the logits, top_k,
         top_p and per-slot settings are NOT applied.
         Columns a slot does not use hold 0."""
+        idx = self._live_index()
+        toks = self.engine._tokens if idx is None else self.engine._tokens[:idx.shape[0]]   # (the live rows)
         if over == "sampled":
-            return self.engine.last_logp(self.engine._tokens, over="sampled")
-        t = 1.0 if self.a_sample_kwargs is None else float(self.a_sample_kwargs["temperature"])
-        return self.engine.last_logp(self.engine._tokens, over=over, temperature=t)
+            lp = self.engine.last_logp(toks, over="sampled")
+        else:
+            t = 1.0 if self.a_sample_kwargs is None else float(self.a_sample_kwargs["temperature"])
+            lp = self.engine.last_logp(toks, over=over, temperature=t)
+        return lp if idx is None else self._scatter_rows(lp, idx)   # (rows of parked envs hold 0)
 
     def _predict_batch_slots(self, observation, returns_to_go, rewards, reset_mask):
         if not isinstance(observation, (tuple, list)) or len(observation) != 2:
             raise ValueError("with a slot table predict_batch takes observation = (vector_obs, images)")
         vec, images = observation
+        idx = self._live_index()
+        if idx is not None:
+            return self._predict_batch_slots_live(vec, images, returns_to_go, rewards, reset_mask, idx)
         n_img = self.slot_table.n_image
         if n_img > 0:
             if not self.has_image_encoder:
@@ -523,6 +613,34 @@ class RecurrentAgent:
             reset_mask = reset_mask.to(self.device, torch.uint8).contiguous()
         actions, _ = self.engine.step_slots(vec, images, rtg, rew, reset_mask)
         return actions
+
+    def _predict_batch_slots_live(self, vec, images, returns_to_go, rewards, reset_mask, idx):
+        """The mixed batch with parked envs: an env sits in a slot with its own table entry (set_active refuses anything else),
+        so env e's frame is the one its own slot index would take, and the engine gets the frames of the live image slots."""
+        n, table = self.n_envs, self.slot_table
+        is_img = torch.as_tensor(table.image).bool().cpu()
+        rank = torch.cumsum(is_img.long(), 0) - 1   # env id -> its frame among the call's frames
+        live = idx.cpu()
+        frames = rank[live][is_img[live]]
+        if table.n_image > 0 and (images is None or images.dim() != 4 or images.shape[0] != table.n_image):
+            raise ValueError(f"images: expected uint8 [{table.n_image}, C, H, W] (one frame per image slot, in slot order)")
+        img_l = None
+        if frames.numel() > 0:
+            img_l = images.to(self.device).to(torch.uint8)[frames.to(self.device)].contiguous()
+        if vec is None:
+            if frames.numel() != live.numel():
+                raise ValueError("vector_obs: None is allowed only when every slot is an image slot")
+            vec_l = None
+        else:
+            if vec.dim() != 2 or vec.shape[0] != n:
+                raise ValueError(f"vector_obs: expected [{n}, obs_dim]")
+            vec_l, _ = self._prepare_obs(vec.to(self.device)[idx])
+        rtg = returns_to_go.to(self.device, torch.float32).reshape(-1)[idx].contiguous()
+        rew = self._zero_reward[:rtg.shape[0]] if rewards is None else rewards.to(self.device, torch.float32).reshape(-1)[idx].contiguous()
+        if reset_mask is not None:
+            reset_mask = reset_mask.to(self.device, torch.uint8).reshape(-1)[idx].contiguous()
+        actions, _ = self.engine.step_slots(vec_l, img_l, rtg, rew, reset_mask)
+        return self._scatter_rows(actions, idx)
 
     # ---- reference single-env surface -------------------------------------------------------------
     @torch.no_grad()

@@ -449,7 +449,8 @@ struct MlstmLazyArgs {
   int B, T, NH, DH;
   int phase, period;      // env b folds when (phase + b) % period == 0 (staggered), or when the window would overflow
   int force;              // fold kernel: fold every env that has pending tokens (materialise)
-  int compact = 0;        // fold kernel: launch only over the envs whose phase comes up (no window can overflow)
+  int compact = 0;        // fold kernel: launch only over the envs whose phase comes up (no window can overflow); 2: the same grid
+                          // over parked env slots, by mlstm_lazy_fold_parked_kernel (view first, then the tile of C_base)
   int first = 0;          // set by the launcher
   int min_lds_bytes = 0;
 };
@@ -466,6 +467,9 @@ void launch_mlstm_lazy_clear(int32_t* count, float* g, const uint8_t* mask, int 
 // fold completed outside it, lazy_finish_prefold): g != nullptr: one block's g[b, :] = 1; g == nullptr: count[b] = 0 (pending
 // tokens and the zero bit).  One launch per block first -- they read the counts -- then the launch that clears them.
 void launch_mlstm_lazy_folded(int32_t* count, float* g, int B, int NH, int first, int period, hipStream_t stream);
+// The step's bookkeeping for `a.B` env slots that take no token this step (parked slots; the pointers start at the first of them,
+// a.reset is null): the "out" side <- the "in" side; count 0 and g = 1 for the envs whose fold runs this step.
+void launch_mlstm_lazy_parked(const MlstmLazyArgs& a, hipStream_t stream);
 void launch_lazy_counts_as_float(const int32_t* count, float* out, int B, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
@@ -508,6 +512,7 @@ struct SlotStateArgs {
   int rec_vec = 1;                     // 0: the record buffer is not 16-byte aligned: scalar path for the record side
 };
 void launch_slot_copy(const SlotStateArgs& a, hipStream_t stream);
+void launch_slot_swap(const SlotStateArgs& a, hipStream_t stream);   // slot src[i] <-> slot dst[i]: all 2n indices distinct
 void launch_slot_save(const SlotStateArgs& a, hipStream_t stream);
 void launch_slot_load(const SlotStateArgs& a, hipStream_t stream);
 // flag |= any listed record's sLSTM hidden plane (kSlotSegSlstmY segments) holds a value outside (-limit, limit), NaN included

@@ -72,7 +72,7 @@ struct BlockState {
 
 struct GraphKey {
   const void *obs, *rtg, *rew, *mask, *act, *tok;
-  int emb, discrete, B;
+  int emb, discrete, B;   // B: the rows of the captured step (the live prefix)
   hipStream_t stream;
   bool operator==(const GraphKey& o) const {
     return obs == o.obs && rtg == o.rtg && rew == o.rew && mask == o.mask && act == o.act && tok == o.tok &&
@@ -228,6 +228,15 @@ struct lram_engine {
   }
   // state + workspace
   int B = 0;
+  // Live prefix (lram_set_live): the stepping calls run on slots [0, n_live) only; slots [n_live, B) are parked -- they keep their
+  // recurrent state and no activation row of them is computed (lazy mode: their bookkeeping is carried over, run_xlstm_stack).  B stays what every state tensor is allocated and strided for; n_live is what a
+  // stepping call's rows, slices and size rules are judged on.  state_alloc sets n_live = B.
+  int n_live = 0;
+  // Lazy matrix memory: the lazy_step at which a parked slot may last have come by pending window tokens -- the live count
+  // changed, or a swap / copy moved a window.  A parked slot takes no token, so once every fold class has come due since then
+  // (lazy_period steps) all parked windows are empty, and the steps launch no fold over the parked range until this moves again.
+  int64_t parked_dirty_step = 0;
+  bool parked_windows_empty(int64_t step) const { return step - parked_dirty_step >= (int64_t)lazy_period; }
   std::vector<BlockState> st;
   DevBuf X, XN, TOK, HID, U, Q, K, V, XA, H, G, SCAL, RY, LOGITS, RES, DTP;
   DevBuf XN2;   // the norm output as f16x2 operand planes [2][B*T, D] f16 (pre-split projections): its own buffer -- a slice inside an
@@ -399,6 +408,7 @@ struct lram_engine {
     ascale_rows = 0;
     last_head = -1;
     B = 0;
+    n_live = 0;
     tok_cap = 0;
   }
   int dh() const { return cfg.inner / cfg.n_heads; }
@@ -490,6 +500,13 @@ inline double mlstm_block_bytes(const lram_engine* e) {
   if (!has_mlstm_block(e)) return 0.0;
   const double dh = (double)e->cfg.inner / e->cfg.n_heads;
   return (double)e->B * e->cfg.n_heads * dh * dh * 4.0;
+}
+
+// ... over the live prefix: what a stepping call's schedule (two slices or one, side-stream folds) is judged on
+inline double mlstm_live_bytes(const lram_engine* e) {
+  if (!has_mlstm_block(e)) return 0.0;
+  const double dh = (double)e->cfg.inner / e->cfg.n_heads;
+  return (double)e->n_live * e->cfg.n_heads * dh * dh * 4.0;
 }
 
 inline bool lazy_active(const lram_engine* e, int T) {

@@ -497,6 +497,7 @@ void lazy_alloc(lram_engine* e) {
   }
   LRAM_HIP_CHECK(hipDeviceSynchronize());
   e->lazy_step = 0;
+  e->parked_dirty_step = 0;
   e->prefold = lram_engine::Prefold{};
   e->lazy_ready = true;
   slot_segments_build(e);
@@ -581,6 +582,7 @@ void state_alloc(lram_engine* e, int B) {
     s.conv.zero();
   }
   e->B = B;
+  e->n_live = B;
   alloc_workspace(e, kMaxTokens);
   e->lazy = lazy_choice(e);
   if (e->lazy) lazy_alloc(e);

@@ -282,6 +282,7 @@ int32_t lram_state_copy_slots(lram_engine* e, const int32_t* host_src, const int
     SlotStateArgs a = slot_args(e, host_src, host_dst, n, s);
     a.n_chunks = a.lazy ? e->slot_n_chunks : e->slot_n_rec_chunks;
     launch_slot_copy(a, s);
+    e->parked_dirty_step = e->lazy_step;   // (a parked destination may hold a window now)
     if (a.lazy && (int)e->lazy_bound.size() == e->lazy_period) {
       // The copy carries its source's pending window into another fold class ((phase + b) % period): that class's host-side
       // bound must cover it, or the compact fold grid would skip an env whose window is about to overflow (the kernel's own
@@ -293,6 +294,51 @@ int32_t lram_state_copy_slots(lram_engine* e, const int32_t* host_src, const int
     }
   });
 }
+
+int32_t lram_state_swap_slots(lram_engine* e, const int32_t* host_a, const int32_t* host_b, int32_t n, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(e && e->B > 0, "lram_state_swap_slots: state not allocated (call lram_state_alloc)");
+    LRAM_REQUIRE(n >= 0 && (n == 0 || (host_a && host_b)), "lram_state_swap_slots: bad argument");
+    // (a slot on both sides, or twice on one, is refused by the copy's own rules: all 2n indices distinct and in range)
+    slot_lists_check("lram_state_swap_slots", host_a, host_b, n, e->B, true);
+    if (n == 0) return;
+    LRAM_HIP_CHECK(hipSetDevice(e->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    lazy_finish_prefold(e, s);
+    SlotStateArgs a = slot_args(e, host_a, host_b, n, s);
+    a.n_chunks = a.lazy ? e->slot_n_chunks : e->slot_n_rec_chunks;
+    launch_slot_swap(a, s);
+    e->parked_dirty_step = e->lazy_step;   // (a parked slot may hold a window now)
+    if (a.lazy && (int)e->lazy_bound.size() == e->lazy_period) {
+      // either slot's pending window now sits in the other's fold class: both classes' host-side bounds must cover both
+      // (as a copy raises its destination's)
+      const int P = e->lazy_period;
+      const std::vector<int> before = e->lazy_bound;
+      for (int i = 0; i < n; ++i) {
+        const int ca = host_a[i] % P, cb = host_b[i] % P;
+        e->lazy_bound[ca] = std::max(e->lazy_bound[ca], before[cb]);
+        e->lazy_bound[cb] = std::max(e->lazy_bound[cb], before[ca]);
+      }
+    }
+  });
+}
+
+int32_t lram_set_live(lram_engine* e, int32_t n_live, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(e && e->B > 0, "lram_set_live: state not allocated (call lram_state_alloc)");
+    LRAM_REQUIRE(n_live >= 1 && n_live <= e->B, "lram_set_live: n_live must be in 1 .. batch = " + std::to_string(e->B));
+    if (e->prefold.pending) {   // the tail fold belongs to the schedule of the rows it was launched for
+      LRAM_HIP_CHECK(hipSetDevice(e->device));
+      lazy_finish_prefold(e, static_cast<hipStream_t>(stream));
+    }
+    if (n_live == e->n_live) return;
+    e->n_live = n_live;
+    e->parked_dirty_step = e->lazy_step;   // (slots parked from here on hold the windows their last steps left)
+    e->drop_graph();   // the captured step's launches cover the rows it was captured for
+  });
+}
+
+int32_t lram_get_live(const lram_engine* e) { return e ? e->n_live : 0; }
 
 int32_t lram_state_save_slots(lram_engine* e, const int32_t* host_slots, int32_t n, float* dev_records, void* stream) {
   return guarded([&] {

@@ -461,7 +461,7 @@ void step_launches(lram_engine* e, Pass pass, const Inputs& in, const uint8_t* r
   pass.compat_passes = discrete ? 1 : std::max(1, std::min(e->compat_repeat, e->cfg.act_dim));
   pass.compat_shared = compat_shares(e, discrete);
   if (pass.compat_shared) {  // (allocated by compat_prepare ahead of this call: never inside a stream capture)
-    const size_t bt = (size_t)e->B * e->cfg.tokens_per_step;
+    const size_t bt = (size_t)e->n_live * e->cfg.tokens_per_step;   // (the rows of this call; compat_prepare allocates for the batch)
     LRAM_REQUIRE(e->X0.n >= bt * e->cfg.d_model && e->U0.n >= bt * 2 * e->cfg.d_inner,
                  "shared repeated forwards: workspace not prepared");
   }
@@ -471,6 +471,13 @@ void step_launches(lram_engine* e, Pass pass, const Inputs& in, const uint8_t* r
   for (pass.compat_pass = 0; pass.compat_pass < pass.compat_passes; ++pass.compat_pass)
     timesteps_launches(e, pass, in, pass.compat_pass == 0 ? reset : nullptr, discrete, actions, tokens, s);
   sample_draw_advance(e, s);
+}
+
+// Stored contexts and encoder calls run on every allocated slot: refused, with nothing launched, while slots are parked.
+void require_all_live(const lram_engine* e, const char* who) {
+  LRAM_REQUIRE(e->n_live == e->B, std::string(who) + ": " + std::to_string(e->B - e->n_live) + " of " + std::to_string(e->B) +
+                                      " env slots are parked (lram_set_live): stored contexts and encoder calls need every slot "
+                                      "live -- call lram_set_live(batch) first");
 }
 
 // What the entries that run (state, rtg, reward) env-steps share: the state is allocated, the front end fits the geometry, the
@@ -649,7 +656,7 @@ int32_t lram_step(lram_engine* e, const float* dev_obs, int32_t obs_is_embedding
     if (e->graph_mode && !(e->prof_on && e->prof_live)) {  // (a sampled run's un-timed steps keep the graph path)
       GraphKey key{};
       key.obs = dev_obs, key.rtg = dev_rtg, key.rew = dev_reward, key.mask = dev_reset_mask, key.act = dev_actions;
-      key.tok = dev_tokens, key.emb = obs_is_embedding, key.discrete = discrete, key.B = e->B, key.stream = s;
+      key.tok = dev_tokens, key.emb = obs_is_embedding, key.discrete = discrete, key.B = e->n_live, key.stream = s;
       if (!(e->graph_valid && key == e->graph_key)) {
         e->drop_graph();
         if (!e->capture_stream) LRAM_HIP_CHECK(hipStreamCreateWithFlags(&e->capture_stream, hipStreamNonBlocking));
@@ -700,9 +707,9 @@ int32_t lram_step_slots(lram_engine* e, const float* dev_obs, const uint8_t* dev
   return guarded([&] {
     step_entry(e, "lram_step_slots");
     LRAM_REQUIRE(e->slot_table, "lram_step_slots: no slot table is set (lram_set_slot_table)");
-    const int n_img = e->slot_n_image;
+    const int n_img = e->slot_img_prefix[e->n_live];   // the image slots of the live prefix: the frames this call is handed
     LRAM_REQUIRE(dev_rtg && dev_reward && dev_actions, "lram_step_slots: null device pointer");
-    LRAM_REQUIRE(dev_obs != nullptr || n_img == e->B, "lram_step_slots: dev_obs is NULL and the table holds vector slots");
+    LRAM_REQUIRE(dev_obs != nullptr || n_img == e->n_live, "lram_step_slots: dev_obs is NULL and the table holds vector slots");
     check_head_mode(e, LRAM_HEAD_PER_SLOT, "lram_step_slots");
     if (n_img > 0) {
       LRAM_REQUIRE(e->img_lin_w != nullptr, "lram_step_slots: the table holds image slots and no embed_image.* weights were uploaded");
@@ -724,6 +731,7 @@ int32_t lram_prefill(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_em
                      float* dev_actions, int32_t* dev_tokens, void* stream) {
   return guarded([&] {
     step_entry(e, "lram_prefill");
+    require_all_live(e, "lram_prefill");
     LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_prefill: null device pointer");
     LRAM_REQUIRE(timesteps >= 1, "lram_prefill: timesteps must be >= 1");
     if (dev_actions != nullptr) check_head_mode(e, discrete, "lram_prefill");
@@ -740,6 +748,7 @@ int32_t lram_score(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embe
                    double temperature, float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits, void* stream) {
   return guarded([&] {
     step_entry(e, "lram_score");
+    require_all_live(e, "lram_score");
     LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_score: null device pointer");
     LRAM_REQUIRE(timesteps >= 1, "lram_score: timesteps must be >= 1");
     const ScoreSink sink = score_sink_checked(e, "lram_score", discrete, dev_target_actions, dev_target_tokens, dev_valid, over,
@@ -756,6 +765,7 @@ int32_t lram_prefill_ragged(lram_engine* e, const float* dev_obs_seq, int32_t ob
                             const uint8_t* dev_reset_mask, int32_t discrete, float* dev_actions, int32_t* dev_tokens, void* stream) {
   return guarded([&] {
     step_entry(e, "lram_prefill_ragged");
+    require_all_live(e, "lram_prefill_ragged");
     LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_prefill_ragged: null device pointer");
     LRAM_REQUIRE(timesteps >= 1, "lram_prefill_ragged: timesteps must be >= 1");
     RaggedCall rc{e, "lram_prefill_ragged", timesteps, host_lengths, {}};
@@ -784,6 +794,7 @@ int32_t lram_score_ragged(lram_engine* e, const float* dev_obs_seq, int32_t obs_
                           float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits, void* stream) {
   return guarded([&] {
     step_entry(e, "lram_score_ragged");
+    require_all_live(e, "lram_score_ragged");
     LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_score_ragged: null device pointer");
     LRAM_REQUIRE(timesteps >= 1, "lram_score_ragged: timesteps must be >= 1");
     RaggedCall rc{e, "lram_score_ragged", timesteps, host_lengths, {}};
@@ -831,7 +842,7 @@ int32_t lram_score_last(lram_engine* e, const int32_t* dev_tokens, int32_t over,
     ScoreSink sink;
     sink.logp = dev_logp, sink.target_tokens = dev_tokens, sink.over = over, sink.temperature = temperature;
     ScoreArgs a = score_args(e, sink, e->last_head);
-    a.logits = e->LOGITS.p, a.ld = (int64_t)e->cfg.act_dim * e->cfg.n_vocab, a.rows = e->B;
+    a.logits = e->LOGITS.p, a.ld = (int64_t)e->cfg.act_dim * e->cfg.n_vocab, a.rows = e->n_live;
     launch_action_score(a, static_cast<hipStream_t>(stream));
   });
 }
@@ -855,7 +866,7 @@ int32_t lram_score_last_sampled(lram_engine* e, const int32_t* dev_tokens, float
                    e->sample.top_k > e->cfg.n_discrete),
                  "lram_score_last_sampled: sampling top_k exceeds n_discrete and the slot table holds a discrete slot");
     // (deterministic: no uniform is read, the draw counter is neither read nor advanced)
-    launch_action_logp(e->LOGITS.p, dev_tokens, dev_logp, e->B, head_geom(e->cfg), head_slots(e, head), head, e->sample,
+    launch_action_logp(e->LOGITS.p, dev_tokens, dev_logp, e->n_live, head_geom(e->cfg), head_slots(e, head), head, e->sample,
                        e->sample_slots_dev, static_cast<hipStream_t>(stream));
   });
 }
@@ -898,6 +909,7 @@ int32_t lram_encoder_step(lram_engine* e, const float* dev_inputs_embeds, int32_
   return guarded([&] {
     LRAM_REQUIRE(e && e->B > 0, "lram_encoder_step: state not allocated");
     LRAM_REQUIRE(dev_inputs_embeds && dev_hidden_out, "lram_encoder_step: null device pointer");
+    require_all_live(e, "lram_encoder_step");
     const bool chunk_ok = e->cfg.backbone == LRAM_BACKBONE_XLSTM && e->chunk_prefill && !e->graph_mode &&
                           mlstm_chunk_supported(e->cfg.inner, e->cfg.n_heads, e->cfg.conv_k);
     LRAM_REQUIRE((tokens >= 1 && tokens <= 4) || tokens == 6 || tokens == 9 || tokens == 12 ||
@@ -930,7 +942,7 @@ int32_t lram_get_taps(lram_engine* e, float* dev_tokens_embed, float* dev_hidden
   return guarded([&] {
     LRAM_REQUIRE(e && e->B > 0, "lram_get_taps: state not allocated");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t btd = sizeof(float) * (size_t)e->B * e->cfg.tokens_per_step * e->cfg.d_model;
+    const size_t btd = sizeof(float) * (size_t)e->n_live * e->cfg.tokens_per_step * e->cfg.d_model;   // (the live rows)
     if (dev_tokens_embed) {
       LRAM_REQUIRE(e->B <= kTokenTapMaxBatch,
                    "lram_get_taps: the embed_ln token tap is kept for batches of up to 1024 env slots only (it costs a "
@@ -939,7 +951,7 @@ int32_t lram_get_taps(lram_engine* e, float* dev_tokens_embed, float* dev_hidden
     }
     if (dev_hidden) LRAM_HIP_CHECK(hipMemcpyAsync(dev_hidden, e->HID.p, btd, hipMemcpyDeviceToDevice, s));
     if (dev_logits)
-      LRAM_HIP_CHECK(hipMemcpyAsync(dev_logits, e->LOGITS.p, sizeof(float) * e->LOGITS.n, hipMemcpyDeviceToDevice, s));
+      LRAM_HIP_CHECK(hipMemcpyAsync(dev_logits, e->LOGITS.p, sizeof(float) * (e->LOGITS.n / e->B) * e->n_live, hipMemcpyDeviceToDevice, s));
   });
 }
 

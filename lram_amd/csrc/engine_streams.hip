@@ -59,7 +59,8 @@ void stream_after(lram_engine* e, hipStream_t dst, hipStream_t src, bool boundar
   LRAM_HIP_CHECK(hipStreamWaitEvent(dst, ev, 0));
 }
 
-// Slices for this call.  One slice on the caller's stream unless micro-batching is on: then n_micro slices on
+// Slices for this call: they cut the live prefix [0, n_live) (lram_set_live; the whole batch unless the caller parked slots), and the
+// rules below are judged on its rows.  One slice on the caller's stream unless micro-batching is on: then n_micro slices on
 // engine-owned streams plus one stream that serialises the HBM-bound cell kernels (see run_xlstm_stack).
 std::vector<Slice> make_slices(lram_engine* e, hipStream_t s, hipStream_t* hbm) {
   int n = e->n_micro;
@@ -70,15 +71,15 @@ std::vector<Slice> make_slices(lram_engine* e, hipStream_t s, hipStream_t* hbm) 
     // (rounds 2-5 split from 512 envs only); 16M at 256 / 512 / 640 envs 219.8k vs 194.1k / 296.2k vs 297.1k / 304.8k vs 314.1k;
     // Mamba-48M at 512 / 768 / 1024 / 1536 envs 288.6k vs 275.0k / 380.4k vs 367.7k / 410.5k vs 416.9k / 432.8k vs 479.4k.
     if (e->cfg.backbone == LRAM_BACKBONE_MAMBA) {
-      n = e->B >= 1024 ? 2 : 1;
+      n = e->n_live >= 1024 ? 2 : 1;
     } else {
-      n = mlstm_block_bytes(e) >= 512.0 * 1024 * 1024 ? 2 : 1;
+      n = mlstm_live_bytes(e) >= 512.0 * 1024 * 1024 ? 2 : 1;
     }
   }
   if (e->graph_mode) n = 1;  // graph replay targets small, launch-bound batches: one slice, one stream
-  n = std::max(1, std::min(n, std::min(e->B, 8)));
+  n = std::max(1, std::min(n, std::min(e->n_live, 8)));
   *hbm = s;
-  if (n == 1) return {Slice{0, e->B, s}};
+  if (n == 1) return {Slice{0, e->n_live, s}};
   while ((int)e->micro_streams.size() < n) {
     hipStream_t ns;
     LRAM_HIP_CHECK(hipStreamCreateWithFlags(&ns, hipStreamNonBlocking));
@@ -87,7 +88,7 @@ std::vector<Slice> make_slices(lram_engine* e, hipStream_t s, hipStream_t* hbm) 
   if (!e->hbm_stream) LRAM_HIP_CHECK(hipStreamCreateWithFlags(&e->hbm_stream, hipStreamNonBlocking));
   *hbm = e->hbm_stream;
   std::vector<Slice> out;
-  const int base = e->B / n, rem = e->B % n;
+  const int base = e->n_live / n, rem = e->n_live % n;
   int b0 = 0;
   for (int i = 0; i < n; ++i) {
     const int nb = base + (i < rem ? 1 : 0);

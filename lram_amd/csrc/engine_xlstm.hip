@@ -109,7 +109,7 @@ bool lean_front(const lram_engine* e, int T) {
   return lazy_active(e, T) && mlstm_lazy_fused_scores(e->cfg.inner / e->cfg.n_heads);
 }
 
-bool split_up_now(const lram_engine* e) { return e->B >= 2048 && !e->graph_mode; }
+bool split_up_now(const lram_engine* e) { return e->n_live >= 2048 && !e->graph_mode; }
 
 // Output group norm + learnable skip inside the lazy read pass's epilogue (its workgroup holds a head's whole output
 // row), silu(z) written by proj_up's epilogue and multiplied onto proj_down's operand while that GEMM stages it: no
@@ -120,8 +120,8 @@ bool split_up_now(const lram_engine* e) { return e->B >= 2048 && !e->graph_mode;
 // operand pre-split by a row kernel: -0.5 %.)
 bool gn_fused(const lram_engine* e, int T) {
   const int dh = e->cfg.inner / e->cfg.n_heads;
-  return (e->gn_fuse == 1 || (e->gn_fuse == 2 && e->B >= 2048)) && lean_front(e, T) && e->use_bf16x3 && (dh == 256 || dh == 128) && T <= 4 &&
-         e->cfg.inner % 8 == 0 && e->cfg.d_model % 8 == 0 && e->B >= 64;  // (fewer rows take the GEMV path)
+  return (e->gn_fuse == 1 || (e->gn_fuse == 2 && e->n_live >= 2048)) && lean_front(e, T) && e->use_bf16x3 && (dh == 256 || dh == 128) && T <= 4 &&
+         e->cfg.inner % 8 == 0 && e->cfg.d_model % 8 == 0 && e->n_live >= 64;  // (fewer rows take the GEMV path)
 }
 
 void mlstm_front(lram_engine* e, const Pass& pass, int i, int T, const uint8_t* reset, const Slice& sl) {
@@ -476,7 +476,7 @@ void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* res
   // 16M at 128 / 256 / 448 envs 155.6k vs 149.5k / 224.2k vs 226.7k / 287.4k vs 297.2k.
   // (Only where the ONE slice is the automatic choice: a forced single slice -- lram_set_micro_batches(1), bench.py's "chip to
   // itself" measurement of the state pass -- keeps every kernel of the pass alone on the chip.)
-  const bool side_folds = lazy && sl.size() == 1 && e->n_micro == 0 && mlstm_block_bytes(e) >= 256.0 * 1024 * 1024;
+  const bool side_folds = lazy && sl.size() == 1 && e->n_micro == 0 && mlstm_live_bytes(e) >= 256.0 * 1024 * 1024;
   hipStream_t fold_stream = hbm;
   std::vector<hipEvent_t> fold_done(side_folds ? c.n_blocks : 0, nullptr);
   if (side_folds) {
@@ -486,10 +486,17 @@ void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* res
   }
   std::vector<char> folded(c.n_blocks, 0);
   auto launch_folds = [&](int i) {  // one launch per block over all env slots: folds do not care about the slices
-    MlstmLazyArgs la = lazy_args(e, i, T, reset, 0, e->B);
+    // (the step's reset mask holds the live rows only: parked slots [n_live, B) fold in a launch of their own, without a mask --
+    // a step never resets them -- so every class's fold still covers all its slots and the host-side bounds stay true)
+    MlstmLazyArgs la = lazy_args(e, i, T, reset, 0, e->n_live);
     la.compact = lazy_compact ? 1 : 0;
     prof_record(e, fold_stream, true, true);
     launch_mlstm_lazy_fold(la, fold_stream);
+    if (e->n_live < e->B && !e->parked_windows_empty(e->lazy_step)) {
+      MlstmLazyArgs lp = lazy_args(e, i, T, nullptr, e->n_live, e->B - e->n_live);
+      lp.compact = la.compact ? 2 : 0;   // (2: the compact grid, view first -- most parked windows are empty)
+      launch_mlstm_lazy_fold(lp, fold_stream);
+    }
     prof_record(e, fold_stream, false, true);
     folded[i] = 1;
   };
@@ -539,6 +546,16 @@ void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* res
       continue;
     }
     if (lazy && !folded[i]) launch_folds(i);  // (one slice, or a stack without an sLSTM block: the fold ahead of its read passes)
+    if (lazy && e->n_live < e->B) {
+      // Parked slots take no token, but the bookkeeping is ping-ponged by step parity: what a read pass leaves on the "out" side
+      // for a slot that received nothing -- coefficients, scale and count carried over; count 0 and g = 1 where the slot's fold
+      // ran this step -- is written for slots [n_live, B) here.  It reads the "in" side only, as the folds do, and sits on the
+      // first slice's stream ahead of that slice's read pass: the state-pass stream, and with it the tail fold, comes behind it.
+      MlstmLazyArgs lp = lazy_args(e, i, T, nullptr, e->n_live, e->B - e->n_live);
+      // (no fold was launched over the parked range: nothing there is due, whatever a window holds -- a phase no slot index meets)
+      if (e->parked_windows_empty(e->lazy_step)) lp.phase = 1, lp.period = 1 << 30;
+      launch_mlstm_lazy_parked(lp, sl[0].s);
+    }
     for (const Slice& x : sl) {
       mlstm_front(e, pass, i, T, reset, x);
       if (lazy) {
@@ -584,10 +601,16 @@ void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* res
       e->prefold.step = e->lazy_step + 1, e->prefold.period = e->lazy_period, e->prefold.B = e->B, e->prefold.blocks = 0;
       e->prefold.pending = true;
       for (int k = next_mlstm(-1); k >= 0 && e->prefold.blocks < lram_engine::fold_tail_blocks; k = next_mlstm(k)) {
-        MlstmLazyArgs la = lazy_args(e, k, T, nullptr, 0, e->B, 1);
+        // (live and parked range apart, as launch_folds has them: the parked one looks first, or is not launched at all)
+        MlstmLazyArgs la = lazy_args(e, k, T, nullptr, 0, e->n_live, 1);
         la.compact = 1;
         prof_record(e, hbm, true, true);
         launch_mlstm_lazy_fold(la, hbm);
+        if (e->n_live < e->B && !e->parked_windows_empty(e->lazy_step + 1)) {
+          MlstmLazyArgs lp = lazy_args(e, k, T, nullptr, e->n_live, e->B - e->n_live, 1);
+          lp.compact = 2;
+          launch_mlstm_lazy_fold(lp, hbm);
+        }
         prof_record(e, hbm, false, true);
         ++e->prefold.blocks;
       }

@@ -89,7 +89,9 @@ constexpr int WF = W;      // window rows held in LDS
 // (Removed after measurement, profiles/EXPERIMENTS.md: a 40-row LDS window for four workgroups per CU -- the fold got 25 %
 // shorter, the step did not; a fold + readout form that handed the read pass q . C_new for the strips it had just rewritten --
 // 2.3 GB of 48 fewer per step and 4-5 % SLOWER, because a fold that needs this step's q sits on the slice's critical chain.)
-__global__ __launch_bounds__(256) void mlstm_lazy_fold_kernel(MlstmLazyArgs a) {
+// (one body, two kernels: kLookFirst = false is the fold as it always was; true is the launch over parked env slots, below)
+template <bool kLookFirst>
+__device__ __forceinline__ void mlstm_lazy_fold_body(const MlstmLazyArgs& a) {
   __shared__ __attribute__((aligned(16))) float Vs[WF * kFPV];
   __shared__ __attribute__((aligned(16))) float Ks[(kFR / 32) * WF * kFPK];
   const int DH = a.DH, NH = a.NH;
@@ -114,7 +116,7 @@ __global__ __launch_bounds__(256) void mlstm_lazy_fold_kernel(MlstmLazyArgs a) {
   float cold[kFR / 32][16];
   LazyRaw raw = lazy_raw(a, b);
   const float g_raw = a.g_in[(int64_t)b * NH + h];
-  const bool early = a.compact != 0;
+  const bool early = !kLookFirst && a.compact != 0;
   if (early) {
 #pragma unroll
     for (int t = 0; t < kFR / 32; ++t)
@@ -198,6 +200,13 @@ __global__ __launch_bounds__(256) void mlstm_lazy_fold_kernel(MlstmLazyArgs a) {
     for (int r = 0; r < 16; ++r) cp0[(int64_t)(32 * t + (r & 3) + 8 * (r >> 2)) * DH] = acc[r];
   }
 }
+
+__global__ __launch_bounds__(256) void mlstm_lazy_fold_kernel(MlstmLazyArgs a) { mlstm_lazy_fold_body<false>(a); }
+
+// The fold over PARKED env slots (launch_mlstm_lazy_fold with compact == 2: the compact grid).  A parked window is empty from its
+// class's first fold on, so these workgroups look at the env's view first, as the full grid's do, instead of requesting a tile of
+// C_base they will not use: ~300 envs x 7 blocks x 1 MB read for nothing per step at 4096 slots otherwise.
+__global__ __launch_bounds__(256) void mlstm_lazy_fold_parked_kernel(MlstmLazyArgs a) { mlstm_lazy_fold_body<true>(a); }
 
 constexpr int WT = kLazyWT;  // window + this step's tokens (row pitch of the score rows)
 
@@ -800,6 +809,25 @@ __global__ __launch_bounds__(256) void mlstm_lazy_folded_kernel(int32_t* count, 
     count[b] = 0;
 }
 
+// Parked env slots (the engine's live prefix ends ahead of them): no token arrives, no read pass runs, but the step still flips
+// the ping-pong parity.  One wave per (env, head) pair, four pairs per workgroup, writes the "out" side a read pass would leave for
+// an env that received nothing: coefficients, scale and count word carried over as they are; where the env's fold runs this step
+// (the same lazy_view every kernel of the step evaluates; a.reset is null) what mlstm_lazy_folded_kernel writes -- count 0 with the
+// zero bit clear, g = 1.  Wave-uniform per pair; a.B counts the parked envs the pointers start at.
+// Bounds: pair < a.B * a.NH, so b < a.B and h < a.NH; lane < W coefficients.
+__global__ __launch_bounds__(256) void mlstm_lazy_parked_kernel(MlstmLazyArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t pair = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (pair >= (int64_t)a.B * a.NH) return;
+  const int b = (int)(pair / a.NH), h = (int)(pair - (int64_t)b * a.NH);
+  const LazyView lv = lazy_view(a, b);
+  if (lane < W) a.coef_out[pair * W + lane] = a.coef_in[pair * W + lane];
+  if (lane == 0) {
+    a.g_out[pair] = lv.fold ? 1.f : a.g_in[pair];
+    if (h == 0) a.count_out[b] = lv.fold ? 0 : a.count_in[b];
+  }
+}
+
 template <int T, int LPR, int UNR, int KPL, int WP = W>
 void launch_cell_tluk(const MlstmLazyArgs& a, hipStream_t s) {
   constexpr int CW = 4 * LPR, RP = 256 / LPR;
@@ -855,7 +883,10 @@ void launch_mlstm_lazy_fold(const MlstmLazyArgs& a_in, hipStream_t stream) {
     envs = (a.B - a.first + a.period - 1) / a.period;
   }
   const long nwg = envs * a.NH * (a.DH / kFC) * (a.DH / kFR);
-  hipLaunchKernelGGL(mlstm_lazy_fold_kernel, dim3((unsigned)nwg), dim3(256), 0, stream, a);
+  if (a.compact == 2)
+    hipLaunchKernelGGL(mlstm_lazy_fold_parked_kernel, dim3((unsigned)nwg), dim3(256), 0, stream, a);
+  else
+    hipLaunchKernelGGL(mlstm_lazy_fold_kernel, dim3((unsigned)nwg), dim3(256), 0, stream, a);
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
@@ -898,6 +929,14 @@ void launch_mlstm_lazy_folded(int32_t* count, float* g, int B, int NH, int first
   const int envs = (B - first + period - 1) / period;
   hipLaunchKernelGGL(mlstm_lazy_folded_kernel, dim3((unsigned)((envs * NH + 255) / 256)), dim3(256), 0, stream, count, g, B, NH,
                      first, period);
+  LRAM_HIP_CHECK(hipGetLastError());
+}
+
+void launch_mlstm_lazy_parked(const MlstmLazyArgs& a, hipStream_t stream) {
+  LRAM_REQUIRE(a.reset == nullptr && a.force == 0 && a.NH >= 1 && a.B <= 65535, "lazy mLSTM: bad parked-slot launch");
+  if (a.B <= 0) return;
+  const int64_t pairs = (int64_t)a.B * a.NH;
+  hipLaunchKernelGGL(mlstm_lazy_parked_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, stream, a);
   LRAM_HIP_CHECK(hipGetLastError());
 }
 

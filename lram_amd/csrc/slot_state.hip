@@ -1,4 +1,5 @@
-// Recurrent state of individual env slots on gfx950: copy slot -> slot (fork), save slots -> records, load records -> slots.
+// Recurrent state of individual env slots on gfx950: copy slot -> slot (fork), swap slot <-> slot, save slots -> records, load
+// records -> slots.
 //
 // The engine keeps every state tensor batch-major, one allocation per block and tensor; an env's state is therefore ~5 pieces
 // per block scattered over as many allocations (16M: 9 MB in 8 blocks, 206M: 112 MB in 20).  The engine describes them once in
@@ -15,6 +16,7 @@
 // ping-pong side of coefficients, scale and count word -- so the source is not folded and not written.  A SAVE computes
 // C = g C_base + sum_j c_j khat_j v_j^T on the fly into the record (slot_lazy_save_kernel) and writes no engine state.  A LOAD
 // writes C_base = C and marks the slot's window empty on the live side (count 0, zero bit clear, g = 1).
+// A SWAP moves what a copy moves, both ways: two chunks loaded, then stored crosswise.
 // The per-step score buffer `pw` of the lazy path is scratch (written and read inside one step) and is not moved.
 #include "common.h"
 
@@ -51,6 +53,49 @@ __device__ __forceinline__ void move_chunk(const float* __restrict__ src, float*
   }
 }
 
+// a pointer every lane of the wave holds the same value of, moved to scalar registers
+__device__ __forceinline__ float* uniform_ptr(float* p) {
+  const uint64_t v = reinterpret_cast<uint64_t>(p);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return reinterpret_cast<float*>(((uint64_t)hi << 32) | lo);
+}
+
+// `len` floats at p <-> `len` floats at q by one workgroup of 256 lanes (p and q never overlap: the slots of a swap are distinct).
+// Both chunks are loaded before either is stored: 2 x kPieces 16-byte pieces in flight per lane.
+__device__ __forceinline__ void swap_chunk(float* __restrict__ p, float* __restrict__ q, int len, bool vec) {
+  const int tid = threadIdx.x;
+  if (vec) {
+    // (both chunk bases are the same for every lane: held in scalar registers, a lane's address is base + one 32-bit offset --
+    // eight 64-bit lane addresses would take the kernel past 64 VGPRs)
+    v4f* p4 = reinterpret_cast<v4f*>(uniform_ptr(p));
+    v4f* q4 = reinterpret_cast<v4f*>(uniform_ptr(q));
+    const int n4 = len >> 2;
+    if (n4 == kPieces * 256) {   // a whole chunk (all but a segment's last): no lane is idle, nothing is predicated
+      v4f vp[kPieces], vq[kPieces];
+#pragma unroll
+      for (int u = 0; u < kPieces; ++u) vp[u] = __builtin_nontemporal_load(p4 + tid + 256 * u);
+#pragma unroll
+      for (int u = 0; u < kPieces; ++u) vq[u] = __builtin_nontemporal_load(q4 + tid + 256 * u);
+#pragma unroll
+      for (int u = 0; u < kPieces; ++u) __builtin_nontemporal_store(vq[u], p4 + tid + 256 * u);
+#pragma unroll
+      for (int u = 0; u < kPieces; ++u) __builtin_nontemporal_store(vp[u], q4 + tid + 256 * u);
+    } else {                     // a segment's tail (i < n4 <= 1024: inside the chunk): piece by piece
+      for (int i = tid; i < n4; i += 256) {
+        const v4f x = __builtin_nontemporal_load(p4 + i), y = __builtin_nontemporal_load(q4 + i);
+        __builtin_nontemporal_store(y, p4 + i), __builtin_nontemporal_store(x, q4 + i);
+      }
+    }
+  } else {  // bit patterns, not values: the count word travels through here
+    uint32_t* p1 = reinterpret_cast<uint32_t*>(p);
+    uint32_t* q1 = reinterpret_cast<uint32_t*>(q);
+    for (int i = tid; i < len; i += 256) {
+      const uint32_t x = p1[i], y = q1[i];
+      p1[i] = y, q1[i] = x;
+    }
+  }
+}
+
 __device__ __forceinline__ bool seg_live(const SlotSeg& sg, const SlotStateArgs& a) {
   if (sg.kind >= kSlotSegWindow && !a.lazy) return false;
   return sg.parity < 0 || sg.parity == a.parity;
@@ -66,6 +111,17 @@ __global__ __launch_bounds__(256) void slot_copy_kernel(SlotStateArgs a) {
   const int64_t sb = a.src[blockIdx.y], db = a.dst[blockIdx.y];
   const int len = min(kSlotChunk, sg.numel - ch.off);
   move_chunk(sg.base + sb * sg.stride + ch.off, sg.base + db * sg.stride + ch.off, len, (sg.vec & 1) != 0);
+}
+
+// grid (chunk, pair): slot src[pair] <-> slot dst[pair], every live segment.  The host has checked that all 2n indices are
+// distinct and in range, so no two workgroups touch the same floats.
+__global__ __launch_bounds__(256) void slot_swap_kernel(SlotStateArgs a) {
+  const SlotChunk ch = a.chunks[blockIdx.x];
+  const SlotSeg sg = a.segs[ch.seg];
+  if (!seg_live(sg, a)) return;
+  const int64_t sb = a.src[blockIdx.y], db = a.dst[blockIdx.y];
+  const int len = min(kSlotChunk, sg.numel - ch.off);
+  swap_chunk(sg.base + sb * sg.stride + ch.off, sg.base + db * sg.stride + ch.off, len, (sg.vec & 1) != 0);
 }
 
 // grid (record chunk, listed slot): record[pair] <- slot src[pair]; in lazy mode C is left to slot_lazy_save_kernel
@@ -182,6 +238,13 @@ void launch_slot_copy(const SlotStateArgs& a, hipStream_t stream) {
   if (a.n <= 0 || a.n_chunks <= 0) return;
   LRAM_REQUIRE(a.n <= 65535, "slot copy: at most 65535 pairs per call");
   hipLaunchKernelGGL(slot_copy_kernel, slot_grid(a.n_chunks, a.n), dim3(256), 0, stream, a);
+  LRAM_HIP_CHECK(hipGetLastError());
+}
+
+void launch_slot_swap(const SlotStateArgs& a, hipStream_t stream) {
+  if (a.n <= 0 || a.n_chunks <= 0) return;
+  LRAM_REQUIRE(a.n <= 65535, "slot swap: at most 65535 pairs per call");
+  hipLaunchKernelGGL(slot_swap_kernel, slot_grid(a.n_chunks, a.n), dim3(256), 0, stream, a);
   LRAM_HIP_CHECK(hipGetLastError());
 }
 

@@ -120,6 +120,9 @@ _SYMBOLS = {
     "lram_state_copy_slots": (ctypes.c_int32, [_VP, _VP, _VP, ctypes.c_int32, _VP]),
     "lram_state_save_slots": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP]),
     "lram_state_load_slots": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP]),
+    "lram_state_swap_slots": (ctypes.c_int32, [_VP, _VP, _VP, ctypes.c_int32, _VP]),
+    "lram_set_live": (ctypes.c_int32, [_VP, ctypes.c_int32, _VP]),
+    "lram_get_live": (ctypes.c_int32, [_VP]),
     "lram_stream_rmw": (ctypes.c_int32, [_VP, ctypes.c_size_t, _VP]),
     "lram_stream_read": (ctypes.c_int32, [_VP, ctypes.c_size_t, _VP, _VP]),
     "lram_gemm_counts": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]),
@@ -285,6 +288,15 @@ def check_slot_lists(src, dst, batch: int):
     return src, dst
 
 
+def check_swap_lists(a, b, batch: int):
+    """The rules of lram_state_swap_slots, checked on the host (no GPU needed): check_slot_lists' rules, plus all 2n indices
+    distinct (a slot is exchanged at most once per call).  Returns the lists as ints; raises ValueError."""
+    a, b = check_slot_lists(a, b, batch)
+    if len(set(a)) != len(a):
+        raise ValueError("a: a slot is listed twice (all indices of a swap must be distinct)")
+    return a, b
+
+
 def _i32_array(values):
     return (ctypes.c_int32 * max(1, len(values)))(*values)
 
@@ -377,6 +389,9 @@ class Engine:
     def alloc(self, batch: int):
         _check(self.lib, self.lib.lram_state_alloc(self._h, int(batch)))
         self.batch = int(batch)
+        self._live = self.batch
+        self._slot_image = None      # host copy of the slot table's image column (a new allocation drops the table)
+        self._n_img_live = 0         # image slots below `live`: the frames step_slots is handed
         B, A = self.batch, self.spec.act_dim
         # zeroed: a discrete head writes column 0 only, and the columns it leaves alone must not depend on what the allocator
         # hands out (two runs on the same inputs return the same tensors)
@@ -397,18 +412,19 @@ class Engine:
     def step(self, obs: torch.Tensor, rtg: torch.Tensor, reward: torch.Tensor,
              reset_mask: Optional[torch.Tensor] = None, discrete=False, obs_is_embedding: bool = False,
              out_actions: Optional[torch.Tensor] = None, out_tokens: Optional[torch.Tensor] = None):
-        """One env-step for all slots.  Inputs are device tensors (already resident in HBM).
+        """One env-step for all live slots (B = `live`: the whole batch unless set_live parked some).  Inputs are device
+        tensors (already resident in HBM).
         Returns (actions float32 [B, act_dim], tokens int32 [B, act_dim]); valid once the current
         stream has executed.  discrete=True: column 0 holds the action index; discrete="per_slot": the head mode of
         every slot comes from the slot table (set_slot_table)."""
-        B, spec = self.batch, self.spec
+        B, spec = self._live, self.spec
         _chk_dev(obs, torch.float32, (B, spec.d_model if obs_is_embedding else spec.state_dim), self.device, "obs")
         _chk_dev(rtg, torch.float32, (B,), self.device, "rtg")
         _chk_dev(reward, torch.float32, (B,), self.device, "reward")
         if reset_mask is not None:
             _chk_dev(reset_mask, torch.uint8, (B,), self.device, "reset_mask")
-        actions = self._actions if out_actions is None else out_actions
-        tokens = self._tokens if out_tokens is None else out_tokens
+        actions = self._live_rows(self._actions) if out_actions is None else out_actions
+        tokens = self._live_rows(self._tokens) if out_tokens is None else out_tokens
         _chk_dev(actions, torch.float32, (B, spec.act_dim), self.device, "out_actions")
         _chk_dev(tokens, torch.int32, (B, spec.act_dim), self.device, "out_tokens")
         _check(self.lib, self.lib.lram_step(self._h, _ptr(obs), int(obs_is_embedding), _ptr(rtg), _ptr(reward),
@@ -423,6 +439,7 @@ class Engine:
         Synchronises and drops a captured graph: not a hot-path call."""
         if discrete is None and act_dim is None and image is None:
             _check(self.lib, self.lib.lram_set_slot_table(self._h, None, None))
+            self._slot_image, self._n_img_live = None, 0
             return
         B = self.batch
         d = torch.as_tensor(discrete).reshape(-1).to("cpu")
@@ -439,6 +456,8 @@ class Engine:
         acts = a.to(torch.uint8).contiguous()
         _check(self.lib, self.lib.lram_set_slot_table(self._h, ctypes.c_void_p(flags.data_ptr()),
                                                       ctypes.c_void_p(acts.data_ptr())))
+        self._slot_image = i.bool().clone()
+        self._n_img_live = int(self._slot_image[:self._live].sum())
 
     def slot_table(self) -> Optional[dict]:
         """The table in effect (lram_get_slot_table): {"discrete": bool [B], "act_dim": int64 [B], "image": bool [B],
@@ -467,8 +486,10 @@ class Engine:
         images uint8 [n_image, C, H, W] -- frame k belongs to the k-th image slot in ascending slot order; None when the table
         holds no image slot.  Head mode per slot: a continuous slot fills columns < its act_dim, a discrete slot column 0 (the
         action index); every other column holds 0.0 / token -1.  Returns (actions, tokens) as step()."""
-        B, spec = self.batch, self.spec
+        B, spec = self._live, self.spec
         n_img = self.n_image_slots   # raises when no table is set
+        if B < self.batch:           # parked slots hand in no frame: the image slots of the live prefix (counted by
+            n_img = self._n_img_live  # set_slot_table / set_live, not per step)
         if obs is None:
             if n_img != B:
                 raise ValueError("obs: None is allowed only when every slot is an image slot")
@@ -486,8 +507,8 @@ class Engine:
         _chk_dev(reward, torch.float32, (B,), self.device, "reward")
         if reset_mask is not None:
             _chk_dev(reset_mask, torch.uint8, (B,), self.device, "reset_mask")
-        actions = self._actions if out_actions is None else out_actions
-        tokens = self._tokens if out_tokens is None else out_tokens
+        actions = self._live_rows(self._actions) if out_actions is None else out_actions
+        tokens = self._live_rows(self._tokens) if out_tokens is None else out_tokens
         _chk_dev(actions, torch.float32, (B, spec.act_dim), self.device, "out_actions")
         _chk_dev(tokens, torch.int32, (B, spec.act_dim), self.device, "out_tokens")
         _check(self.lib, self.lib.lram_step_slots(self._h, _ptr(obs), _ptr(images) if n_img > 0 else None, c, h, w, _ptr(rtg),
@@ -504,6 +525,7 @@ class Engine:
         [b, :lengths[b]] (left-aligned; the rows behind it are ignored), its state afterwards is that of its own context and its
         action the one at its own last timestep.  A length below L replaces the slot's state (the slot is reset first whatever
         `reset_mask` says); length L behaves as without lengths; length 0 leaves the slot alone (action 0, token -1)."""
+        self._need_all_live("prefill")
         B, spec = self.batch, self.spec
         L = obs_seq.shape[1]
         _chk_dev(obs_seq, torch.float32, (B, L, spec.d_model if obs_is_embedding else spec.state_dim), self.device,
@@ -539,6 +561,7 @@ class Engine:
         logits=True adds the raw logits.  The state afterwards equals prefill()'s; nothing is drawn in sampling mode.
         `lengths` as in prefill() (lram_score_ragged): rows [b, l] with l >= lengths[b] are masked, and the state afterwards is
         that of every env's own context."""
+        self._need_all_live("score")
         B, spec = self.batch, self.spec
         if obs_seq.dim() != 3:
             raise ValueError("obs_seq must be [B, L, state_dim]")
@@ -590,7 +613,7 @@ class Engine:
         where set_sampling_slots set a table, those of set_sampling otherwise, top-k / top-p applied (a token outside the
         support scores -inf, a greedy slot's argmax token 0).  `temperature` must then be left at its default: the armed one
         is used."""
-        B, A = self.batch, self.spec.act_dim
+        B, A = self._live, self.spec.act_dim   # (the live rows: what the last step returned)
         _chk_dev(tokens, torch.int32, (B, A), self.device, "tokens")
         out = torch.zeros(B, A, dtype=torch.float32, device=self.device)
         if over == "sampled":
@@ -623,7 +646,7 @@ class Engine:
         """One env-step from uint8 frames [B, C, H, W]: embed_images + step(obs_is_embedding=True) as one call (the reference's
         forward embeds image states inside `compute_inputs`, online_decision_transformer_model.py:463-530).  Same results as the two
         calls; the CNN runs per env slice beside the step's observation-independent state-pass work."""
-        B, spec = self.batch, self.spec
+        B, spec = self._live, self.spec
         if images.dim() != 4:
             raise ValueError("images must be [B, C, H, W]")
         _chk_dev(images, torch.uint8, (B, *images.shape[1:]), self.device, "images")
@@ -631,8 +654,8 @@ class Engine:
         _chk_dev(reward, torch.float32, (B,), self.device, "reward")
         if reset_mask is not None:
             _chk_dev(reset_mask, torch.uint8, (B,), self.device, "reset_mask")
-        actions = self._actions if out_actions is None else out_actions
-        tokens = self._tokens if out_tokens is None else out_tokens
+        actions = self._live_rows(self._actions) if out_actions is None else out_actions
+        tokens = self._live_rows(self._tokens) if out_tokens is None else out_tokens
         _chk_dev(actions, torch.float32, (B, spec.act_dim), self.device, "out_actions")
         _chk_dev(tokens, torch.int32, (B, spec.act_dim), self.device, "out_tokens")
         _check(self.lib, self.lib.lram_step_images(self._h, _ptr(images), int(images.shape[1]), int(images.shape[2]),
@@ -642,6 +665,7 @@ class Engine:
 
     def encoder_step(self, inputs_embeds: torch.Tensor, reset_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """`self.encoder(inputs_embeds=[B,T,D], use_cache=True)` plug point (decision_xlstm.py:138-169)."""
+        self._need_all_live("encoder_step")
         B, D = self.batch, self.spec.d_model
         T = inputs_embeds.shape[1]
         _chk_dev(inputs_embeds, torch.float32, (B, T, D), self.device, "inputs_embeds")
@@ -653,10 +677,10 @@ class Engine:
         return out
 
     def taps(self):
-        """(embed_ln tokens [B,T,D], encoder hidden [B,T,D], logits [B, act_dim*n_vocab]) of the last step."""
-        B, s = self.batch, self.spec
+        """(embed_ln tokens [B,T,D], encoder hidden [B,T,D], logits [B, act_dim*n_vocab]) of the last step (B = `live`)."""
+        B, s = self._live, self.spec
         hid = torch.empty(B, s.tokens_per_step, s.d_model, dtype=torch.float32, device=self.device)
-        tok = torch.empty_like(hid) if B <= 1024 else None   # the token tap is kept for small batches only
+        tok = torch.empty_like(hid) if self.batch <= 1024 else None   # the token tap is kept for small batches only
         logits = torch.empty(B, s.act_dim * s.n_vocab, dtype=torch.float32, device=self.device)
         _check(self.lib, self.lib.lram_get_taps(self._h, _ptr(tok), _ptr(hid), _ptr(logits), _stream_ptr(self.device)))
         return tok, hid, logits
@@ -720,6 +744,37 @@ class Engine:
                 for w, t in enumerate(blk["mlstm_state"]):
                     self.import_state_tensor(i, w, t)
             self.import_state_tensor(i, 3, blk["conv_state"][0])
+
+    # -- live prefix: step only the slots that have something to do --------------------------------
+    @property
+    def live(self) -> int:
+        """Slots [0, live) are live, [live, batch) parked (lram_get_live)."""
+        return self._live
+
+    def set_live(self, n: int):
+        """The first `n` slots (1 .. batch) are live from now on; the others are parked: they keep their recurrent state and
+        no row of them is computed (lram_set_live; lazy mode still carries their bookkeeping over each step).  step / step_images / step_slots / last_logp / taps then take and return `n` rows;
+        prefill / score / encoder_step raise until every slot is live again.  Cheap: no synchronisation, no allocation."""
+        _check(self.lib, self.lib.lram_set_live(self._h, int(n), _stream_ptr(self.device)))
+        self._live = int(self.lib.lram_get_live(self._h))
+        if self._slot_image is not None:
+            self._n_img_live = int(self._slot_image[:self._live].sum())
+
+    def swap_slots(self, a, b):
+        """Exchange the recurrent state of slots a[i] and b[i], live or parked, in one launch (lram_state_swap_slots).  All
+        indices distinct and in range.  Slot-table entries, per-slot sampling settings and the sampling stream stay with the
+        slot index."""
+        a, b = check_swap_lists(a, b, self.batch)
+        _check(self.lib, self.lib.lram_state_swap_slots(self._h, _i32_array(a), _i32_array(b), len(a),
+                                                        _stream_ptr(self.device)))
+
+    def _live_rows(self, buf: torch.Tensor) -> torch.Tensor:
+        return buf if self._live == self.batch else buf[:self._live]
+
+    def _need_all_live(self, what: str):
+        if self._live != self.batch:
+            raise LramError(f"{what}: {self.batch - self._live} of {self.batch} env slots are parked (set_live): stored "
+                            f"contexts and encoder calls need every slot live -- call set_live(batch) first")
 
     # -- state of individual env slots: fork / snapshot / restore ---------------------------------
     @property

@@ -78,6 +78,80 @@ class SyntheticVecEnv:
         self.episodes[dst_t] = self.episodes[src_t]
 
 
+class SlotScheduler:
+    """Which env sits in which engine slot while some envs are parked (Engine.set_live / swap_slots): pure bookkeeping, no GPU.
+
+    The engine steps the slots [0, n_live) and leaves [n_live, n) alone, so the live envs must sit in a prefix of the slots.
+    The scheduler keeps the permutation env id <-> slot; park() and resume() return the slot pairs to exchange and the new live
+    count.  Every parked or resumed env takes at most one swap, and all indices of one swap list are distinct (what
+    lram_state_swap_slots asks for).  The reference has no counterpart: its loop keeps forwarding an env that has finished its
+    share of episodes (src/callbacks/evaluation.py:184,205-212)."""
+
+    def __init__(self, n: int):
+        if n < 1:
+            raise ValueError("SlotScheduler: n must be >= 1")
+        self.n = int(n)
+        self.n_live = self.n
+        self.slot_of = list(range(self.n))   # env id -> slot
+        self.env_at = list(range(self.n))    # slot -> env id
+
+    def live_envs(self) -> List[int]:
+        """Env id of every live slot, in slot order."""
+        return self.env_at[:self.n_live]
+
+    def is_live(self, env: int) -> bool:
+        return self.slot_of[env] < self.n_live
+
+    @property
+    def identity(self) -> bool:
+        return all(e == s for s, e in enumerate(self.env_at))
+
+    def _ids(self, env_ids, want_live: bool, what: str) -> List[int]:
+        ids = [int(e) for e in env_ids]
+        if len(set(ids)) != len(ids):
+            raise ValueError(f"{what}: an env is listed twice")
+        for e in ids:
+            if not 0 <= e < self.n:
+                raise ValueError(f"{what}: env {e} outside 0 .. {self.n - 1}")
+            if self.is_live(e) != want_live:
+                raise ValueError(f"{what}: env {e} is {'parked already' if want_live else 'not parked'}")
+        return ids
+
+    def _swap(self, pairs):
+        for sa, sb in pairs:
+            ea, eb = self.env_at[sa], self.env_at[sb]
+            self.env_at[sa], self.env_at[sb] = eb, ea
+            self.slot_of[ea], self.slot_of[eb] = sb, sa
+
+    def park(self, env_ids):
+        """Park the listed live envs.  Returns (a, b, n_live): exchange slots a[i] <-> b[i], then n_live slots are live."""
+        ids = self._ids(env_ids, True, "park")
+        new_live = self.n_live - len(ids)
+        if new_live < 1:
+            raise ValueError("park: at least one env must stay live")
+        leaving = set(ids)
+        # a parked env below the new boundary changes places with a staying env in the stretch that gets parked
+        out = sorted(self.slot_of[e] for e in ids if self.slot_of[e] < new_live)
+        inn = [s for s in range(new_live, self.n_live) if self.env_at[s] not in leaving]
+        pairs = list(zip(out, inn))
+        self._swap(pairs)
+        self.n_live = new_live
+        return [p[0] for p in pairs], [p[1] for p in pairs], new_live
+
+    def resume(self, env_ids):
+        """Make the listed parked envs live again.  Returns (a, b, n_live) as park()."""
+        ids = self._ids(env_ids, False, "resume")
+        new_live = self.n_live + len(ids)
+        coming = set(ids)
+        # a resumed env beyond the new boundary changes places with a still-parked env in the stretch that goes live
+        far = sorted(self.slot_of[e] for e in ids if self.slot_of[e] >= new_live)
+        near = [s for s in range(self.n_live, new_live) if self.env_at[s] not in coming]
+        pairs = list(zip(near, far))
+        self._swap(pairs)
+        self.n_live = new_live
+        return [p[0] for p in pairs], [p[1] for p in pairs], new_live
+
+
 class BatchedRollout:
     """agent: object with predict_batch(obs, rtg, rewards, reset_mask, env_act_dim) (lram_amd.agent.RecurrentAgent)."""
 
@@ -141,7 +215,13 @@ class BatchedRollout:
         src, dst = check_slot_lists(src, dst, self.env.n_envs)
         if not src:
             return
-        self.agent.fork_slots(src, dst)
+        # src / dst name ENVS, as all of this driver's bookkeeping does; the agent's call addresses engine slots, which differ from
+        # env ids once set_active has exchanged slots
+        sch = getattr(self.agent, "scheduler", None)
+        if sch is not None and not sch.identity:
+            self.agent.fork_slots([sch.slot_of[e] for e in src], [sch.slot_of[e] for e in dst])
+        else:
+            self.agent.fork_slots(src, dst)
         if hasattr(self.env, "copy_slots"):
             self.env.copy_slots(src, dst)
         dev = self.obs.device
@@ -179,7 +259,7 @@ def evaluate_policy_batched(agent, env, n_eval_episodes: int = 10, target_return
                             callback: Optional[Callable[[dict, dict], None]] = None,
                             reward_threshold: Optional[float] = None, return_episode_rewards: bool = False,
                             task_id: int = 0, max_steps: Optional[int] = None,
-                            is_success_buffer: Optional[List[float]] = None):
+                            is_success_buffer: Optional[List[float]] = None, park_finished: bool = False):
     """`custom_evaluate_policy` (src/callbacks/evaluation.py:14-271) over a vector env of any width.
 
     Episodes are divided over the sub-envs as evenly as possible (:94-96) and an env stops contributing once it
@@ -188,12 +268,19 @@ def evaluate_policy_batched(agent, env, n_eval_episodes: int = 10, target_return
     `target_return` / `reward_scale` default to the agent's `compute_target_return_val` /
     `get_reward_scale_for_env` (:111-122); `agent.persist_context` selects the cross-episode mode; an env's
     `is_success` info at episode end is appended to `is_success_buffer` (the reference collects it through its
-    `_log_success_callback`, custom_eval_callback.py:36-52)."""
+    `_log_success_callback`, custom_eval_callback.py:36-52).
+    park_finished=True: an env that has finished its share is parked (agent.set_active) and the agent no longer steps it --
+    the reference keeps forwarding it and throws the result away.  The env object still steps all its sub-envs, with action 0
+    for the parked ones; rewards, lengths and counts equal those of park_finished=False (envs are independent)."""
     n = env.n_envs
     if target_return is None:
         target_return = agent.compute_target_return_val(env=env, task_id=task_id) * agent.get_reward_scale_for_env(None)
     if reward_scale is None:
         reward_scale = agent.get_reward_scale_for_env(None)
+    # every env takes part from the first step on: an agent that comes out of an evaluation with parked envs (park_finished) starts
+    # the next one with all of them active again
+    if hasattr(agent, "set_active") and len(agent.active) != n:
+        agent.set_active(range(n))
     ro = BatchedRollout(agent, env, target_return, reward_scale, env_act_dim,
                         persist_context=bool(getattr(agent, "persist_context", False)))
     targets = np.array([(n_eval_episodes + i) // n for i in range(n)], dtype=int)
@@ -228,6 +315,10 @@ def evaluate_policy_batched(agent, env, n_eval_episodes: int = 10, target_return
                     counts[i] += 1
             if done[i]:
                 cur_r[i], cur_l[i], start[i] = 0.0, 0, time.time()
+        if park_finished:
+            active = [i for i in range(n) if counts[i] < targets[i]]
+            if active and len(active) != len(agent.active):
+                agent.set_active(active)
         if max_steps is not None and steps >= max_steps:
             break
     # evaluation.py:258-261: the cache is dropped when the evaluation ends
