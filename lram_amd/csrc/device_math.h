@@ -67,6 +67,21 @@ __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff
 
 __device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
+__device__ __forceinline__ float dot4(const float4& x, const float4& y) { return x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w; }
+
+// Zeroing by a bit mask (keep = all ones or 0), not a branch or a multiply: no control flow on the flag that decides it -- the
+// compiler otherwise waits for that flag before it issues anything else -- and no NaN * 0.
+__device__ __forceinline__ float masked(float v, unsigned keep) { return __uint_as_float(__float_as_uint(v) & keep); }
+__device__ __forceinline__ float4 masked4(const float4& v, unsigned keep) {
+  return make_float4(masked(v.x, keep), masked(v.y, keep), masked(v.z, keep), masked(v.w, keep));
+}
+
+// ---- matrix-core accumulators ----
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+// row of the 32x32 MFMA accumulator held in register r by a lane of half lh
+__device__ __forceinline__ int acc_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
+
 // Exact 3-way bf16 split of an fp32 value, x = hi + mid + lo (the operand format of gemm_bf16x3.hip): producers that
 // feed a projection write these three planes instead of (or next to) the fp32 value, so the GEMM stages its A operand
 // with plain 16-byte copies.  p points at the element in plane 0; the planes are `plane` elements apart.

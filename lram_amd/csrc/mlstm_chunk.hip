@@ -24,11 +24,9 @@
 
 #include "common.h"
 #include "device_math.h"
+#include "xlstm_rules.h"
 
 namespace lram {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -36,17 +34,10 @@ constexpr int kLp = kChunkMaxTokens;  // 64: padded chunk length (two 32-row MFM
 constexpr int kThreads = 256;
 constexpr int kPreMaxGroups = 3;      // channel groups of 4 per thread: inner <= 3072
 
-__device__ __forceinline__ float dot4(const float4& x, const float4& y) {
-  return x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
-}
-
-// row of the 32x32 MFMA accumulator held in register r by a lane of half lh
-__device__ __forceinline__ int acc_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
-
 // =============================================================================================
-// Front end, token-parallel: one workgroup per (env, group of kTB consecutive tokens).  Same arithmetic (and the
-// same summation order) as mlstm_pre_seq_kernel; the conv window of the first three tokens reaches back into
-// conv_state.  Per-channel weights are loaded once per workgroup and reused for its kTB tokens.
+// Front end, token-parallel: one workgroup per (env, group of kTB consecutive tokens).  The token rules of
+// xlstm_rules.h with the partial sums in mlstm_pre_seq_kernel's order; the conv window of the first three tokens reaches
+// back into conv_state.  Per-channel weights are loaded once per workgroup and reused for its kTB tokens.
 // Writes q, k, v, xa rows and the raw gate pre-activations gates[row][head] = (i~, f~).
 // =============================================================================================
 constexpr int kTB = 4;
@@ -80,12 +71,12 @@ __global__ __launch_bounds__(kThreads) void mlstm_pre_tok_kernel(MlstmPreArgs a)
 #pragma unroll
     for (int c = 0; c < 4; ++c) cw[c] = *reinterpret_cast<const float4*>(a.conv_w + (int64_t)(c0 + c) * 4);
     const float4 cb = *reinterpret_cast<const float4*>(a.conv_b + c0);
-    const float4* wq = reinterpret_cast<const float4*>(a.wq + (int64_t)cg * 16);
-    const float4* wk = reinterpret_cast<const float4*>(a.wk + (int64_t)cg * 16);
-    const float4* wv = reinterpret_cast<const float4*>(a.wv + (int64_t)cg * 16);
-    const float4 wq0 = wq[0], wq1 = wq[1], wq2 = wq[2], wq3 = wq[3];
-    const float4 wk0 = wk[0], wk1 = wk[1], wk2 = wk[2], wk3 = wk[3];
-    const float4 wv0 = wv[0], wv1 = wv[1], wv2 = wv[2], wv3 = wv[3];
+    const float4* wqp = reinterpret_cast<const float4*>(a.wq + (int64_t)cg * 16);
+    const float4* wkp = reinterpret_cast<const float4*>(a.wk + (int64_t)cg * 16);
+    const float4* wvp = reinterpret_cast<const float4*>(a.wv + (int64_t)cg * 16);
+    const float4 wq[4] = {wqp[0], wqp[1], wqp[2], wqp[3]};
+    const float4 wk[4] = {wkp[0], wkp[1], wkp[2], wkp[3]};
+    const float4 wv[4] = {wvp[0], wvp[1], wvp[2], wvp[3]};
     float4 qs[kTB], ks[kTB], vs[kTB];
 #pragma unroll
     for (int j = 0; j < kTB; ++j) {
@@ -100,15 +91,8 @@ __global__ __launch_bounds__(kThreads) void mlstm_pre_tok_kernel(MlstmPreArgs a)
       win[1] = win[2];
       win[2] = win[3];
       win[3] = xm;
-      float4 y;
-      y.x = win[0].x * cw[0].x + win[1].x * cw[0].y + win[2].x * cw[0].z + win[3].x * cw[0].w + cb.x;
-      y.y = win[0].y * cw[1].x + win[1].y * cw[1].y + win[2].y * cw[1].z + win[3].y * cw[1].w + cb.y;
-      y.z = win[0].z * cw[2].x + win[1].z * cw[2].y + win[2].z * cw[2].z + win[3].z * cw[2].w + cb.z;
-      y.w = win[0].w * cw[3].x + win[1].w * cw[3].y + win[2].w * cw[3].z + win[3].w * cw[3].w + cb.w;
-      const float4 xa = make_float4(silu_f(y.x), silu_f(y.y), silu_f(y.z), silu_f(y.w));
-      const float4 q = make_float4(dot4(wq0, xa), dot4(wq1, xa), dot4(wq2, xa), dot4(wq3, xa));
-      const float4 k = make_float4(dot4(wk0, xa), dot4(wk1, xa), dot4(wk2, xa), dot4(wk3, xa));
-      const float4 v = make_float4(dot4(wv0, xm), dot4(wv1, xm), dot4(wv2, xm), dot4(wv3, xm));
+      const float4 xa = conv4_silu(win[0], win[1], win[2], win[3], cw, cb);
+      const float4 q = block4x4(wq, xa), k = block4x4(wk, xa), v = block4x4(wv, xm);
       *reinterpret_cast<float4*>(a.q + row * inner + c0) = q;
       *reinterpret_cast<float4*>(a.k + row * inner + c0) = k;
       *reinterpret_cast<float4*>(a.v + row * inner + c0) = v;
@@ -127,8 +111,8 @@ __global__ __launch_bounds__(kThreads) void mlstm_pre_tok_kernel(MlstmPreArgs a)
                    fv = *reinterpret_cast<const float4*>(wf + 2 * inner);
 #pragma unroll
       for (int j = 0; j < kTB; ++j) {
-        pi[j][h] += dot4(iq, qs[j]) + dot4(ik, ks[j]) + dot4(iv, vs[j]);
-        pf[j][h] += dot4(fq, qs[j]) + dot4(fk, ks[j]) + dot4(fv, vs[j]);
+        pi[j][h] += gate_partial(iq, ik, iv, qs[j], ks[j], vs[j]);
+        pf[j][h] += gate_partial(fq, fk, fv, qs[j], ks[j], vs[j]);
       }
     }
   }
@@ -184,26 +168,27 @@ __global__ __launch_bounds__(kThreads) void mlstm_chunk_scan_kernel(MlstmPreArgs
     if (valid) {
       const float2 g = *reinterpret_cast<const float2*>(a.gates + (((int64_t)b * T + t) * NH + h) * 2);
       gi = g.x;
-      lf = log_sigmoid(g.y);
+      lf = mlstm_log_f(g.y);
     }
-    // m_t = max(lf_t + m_{t-1}, gi_t)   (all lanes run the same chain; lane t keeps its own step)
+    // the m chain of mlstm_gate_step (all lanes run the same chain; lane t keeps its own step's m_{t-1} and m_t) ...
     float m = rs ? 0.f : a.m_state[(int64_t)b * NH + h];
-    float fa = 0.f, mt = 0.f;
+    float mp = 0.f, mt = 0.f;
 #pragma unroll
     for (int u = 0; u < kLp; ++u) {
       if (u < T) {
-        const float lfu = __shfl(lf, u, 64), giu = __shfl(gi, u, 64);
-        const float mn = fmaxf(lfu + m, giu);
+        const float mn = mlstm_m_next(__shfl(lf, u, 64), m, __shfl(gi, u, 64));
         if (lane == u) {
-          fa = lfu + m - mn;
+          mp = m;
           mt = mn;
         }
         m = mn;
       }
     }
     if (lane == 0) a.m_state[(int64_t)b * NH + h] = m;
-    const float f = valid ? expf(fa) : 1.f;
-    const float ig = valid ? expf(gi - mt) : 0.f;
+    // ... and its other half, per lane
+    const MlstmGate gt = mlstm_gate_fi(lf, mp, mt, gi);
+    const float f = valid ? gt.f : 1.f;
+    const float ig = valid ? gt.i : 0.f;
     // fcum_t = f_0 .. f_t ;  w_s = i_s f_{s+1} .. f_{T-1} ;  decay column D[t][s = lane] = i_s f_{s+1} .. f_t
     float fc = 1.f, fcum = 0.f;
     float d = ig;
@@ -248,8 +233,7 @@ __global__ __launch_bounds__(kThreads) void mlstm_chunk_scan_kernel(MlstmPreArgs
     for (int i = 0; i < 2; ++i) {
       const int t = lr + 32 * i;
       *reinterpret_cast<float4*>(Qs + t * kSP + lc) = rq[i];
-      *reinterpret_cast<float4*>(Ks + t * kSP + lc) =
-          make_float4(rk[i].x / sqrt_dh, rk[i].y / sqrt_dh, rk[i].z / sqrt_dh, rk[i].w / sqrt_dh);
+      *reinterpret_cast<float4*>(Ks + t * kSP + lc) = khat(rk[i], sqrt_dh);
     }
     __syncthreads();
     if (kt + 1 < nk) load_tile((kt + 1) * 32);
@@ -321,7 +305,7 @@ __global__ __launch_bounds__(kThreads) void mlstm_chunk_scan_kernel(MlstmPreArgs
       float rowsum = 0.f;  // entries beyond the diagonal are zero
 #pragma unroll 16
       for (int s = 0; s < kLp; ++s) rowsum += Dm[t * kDP + s];
-      den = fmaxf(fabsf(s_fc[t] * s_qn[t] + rowsum), expf(-s_m[t])) + 1e-6f;
+      den = mlstm_denominator(s_fc[t] * s_qn[t] + rowsum, s_m[t]);
     }
     vec[t] = s_fc[t];
     vec[kLp + t] = s_w[t];
@@ -336,7 +320,7 @@ __global__ __launch_bounds__(kThreads) void mlstm_chunk_scan_kernel(MlstmPreArgs
 #pragma unroll
       for (int j = 0; j < 8; ++j) kv[j] = kb[(int64_t)min(s0 + j, T - 1) * inner + r];  // w == 0 beyond T
 #pragma unroll
-      for (int j = 0; j < 8; ++j) n += s_w[s0 + j] * (kv[j] / sqrt_dh);
+      for (int j = 0; j < 8; ++j) n += s_w[s0 + j] * khat(kv[j], sqrt_dh);
     }
     nst[r] = n;
   }
@@ -480,8 +464,8 @@ __global__ __launch_bounds__(kThreads) void mlstm_cell_chunk_kernel(MlstmCellArg
       const int t = qrow + 32 * i;
       const float fc = s_fc[t], wt = s_w[t];
       *reinterpret_cast<float4*>(Qs + t * kSP + qc4) = make_float4(fc * rq[i].x, fc * rq[i].y, fc * rq[i].z, fc * rq[i].w);
-      *reinterpret_cast<float4*>(Ks + t * kPK + qc4) =
-          make_float4(wt * (rk[i].x / sqrt_dh), wt * (rk[i].y / sqrt_dh), wt * (rk[i].z / sqrt_dh), wt * (rk[i].w / sqrt_dh));
+      const float4 kh = khat(rk[i], sqrt_dh);
+      *reinterpret_cast<float4*>(Ks + t * kPK + qc4) = make_float4(wt * kh.x, wt * kh.y, wt * kh.z, wt * kh.w);
     }
     __syncthreads();
     if (it > 0) store_tile(cprev, r0 - kRT);

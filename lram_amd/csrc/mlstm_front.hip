@@ -1,8 +1,8 @@
 // mLSTM step front end for the large-batch lazy path on gfx950: several env slots per workgroup.
 //
-// Same arithmetic as mlstm_pre_kernel (xlstm_kernels.hip) in its lean form -- conv1d_step (4 taps, depthwise) -> SiLU ->
-// gate pre-activations Wi.[q,k,v] + bi, Wf.[q,k,v] + bf -> stabilised gate scalars f_t, i_t, m_t -> normaliser state n_t
-// and denominators max(|q_t . n_t|, exp(-m_t)) + 1e-6 -- for T = 3 tokens of one env-step (conv1d_step,
+// The token rules of xlstm_rules.h, as mlstm_pre_kernel (xlstm_kernels.hip) applies them in its lean form -- conv1d_step
+// (4 taps, depthwise) -> SiLU -> gate pre-activations Wi.[q,k,v] + bi, Wf.[q,k,v] + bf -> stabilised gate scalars f_t, i_t,
+// m_t -> normaliser state n_t and the denominators -- for T = 3 tokens of one env-step (conv1d_step,
 // LinearHeadwiseExpand q / k / v, mLSTMCell igate / fgate, recurrent_step_stabilized_simple; reference call site
 // src/algos/models/decision_xlstm.py:159-163).  What differs is how the work is laid out:
 //
@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "device_math.h"
+#include "xlstm_rules.h"
 
 namespace lram {
 
@@ -46,12 +47,6 @@ __global__ __launch_bounds__(256) void gate_coef_kernel(const float* wq, const f
   }
   gc[((int64_t)cg * 4 * NH + j) * 4 + c] = (float)a;
   gc[((int64_t)cg * 4 * NH + 2 * NH + j) * 4 + c] = (float)b;
-}
-
-__device__ __forceinline__ float dot4(const float4& x, const float4& y) { return x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w; }
-__device__ __forceinline__ float4 and4(const float4& v, unsigned keep) {
-  return make_float4(__uint_as_float(__float_as_uint(v.x) & keep), __uint_as_float(__float_as_uint(v.y) & keep),
-                     __uint_as_float(__float_as_uint(v.z) & keep), __uint_as_float(__float_as_uint(v.w) & keep));
 }
 
 // One step of a recursive-halving wave reduction: v[0 .. 2 n) -> r[0 .. n), lanes with bit M set keep the upper half.
@@ -113,24 +108,19 @@ __global__ __launch_bounds__(256) void mlstm_front_kernel(MlstmFrontArgs a) {
     const int buf = (b - e_begin) & 1;
     // restart: state is requested whether or not the env restarts and zeroed by a bit mask (no control flow on the flag)
     const unsigned keep = (a.reset != nullptr && rsb != 0) ? 0u : 0xFFFFFFFFu;
-    float4 w0 = and4(win[0], keep), w1 = and4(win[1], keep), w2 = and4(win[2], keep), w3 = and4(win[3], keep);
-    float4 n = and4(nst, keep);
-    float m = __uint_as_float(__float_as_uint(m_in) & keep);
+    float4 w0 = masked4(win[0], keep), w1 = masked4(win[1], keep), w2 = masked4(win[2], keep), w3 = masked4(win[3], keep);
+    float4 n = masked4(nst, keep);
+    float m = masked(m_in, keep);
     const float4 x0 = xm[0], x1 = xm[1], x2 = xm[2];
 
     // ---- conv -> SiLU, q / k, gate partial sums ----
     float4 q[T], k[T];
     float pg[T * kNG];
     auto token = [&](int t, const float4& p0, const float4& p1, const float4& p2, const float4& p3) {
-      float4 y;
-      y.x = p0.x * cw[0].x + p1.x * cw[0].y + p2.x * cw[0].z + p3.x * cw[0].w + cb.x;
-      y.y = p0.y * cw[1].x + p1.y * cw[1].y + p2.y * cw[1].z + p3.y * cw[1].w + cb.y;
-      y.z = p0.z * cw[2].x + p1.z * cw[2].y + p2.z * cw[2].z + p3.z * cw[2].w + cb.z;
-      y.w = p0.w * cw[3].x + p1.w * cw[3].y + p2.w * cw[3].z + p3.w * cw[3].w + cb.w;
-      const float4 xa = make_float4(silu_f(y.x), silu_f(y.y), silu_f(y.z), silu_f(y.w));
+      const float4 xa = conv4_silu(p0, p1, p2, p3, cw, cb);
       *reinterpret_cast<float4*>(a.xa + ((int64_t)b * T + t) * inner + c0) = xa;
-      q[t] = make_float4(dot4(wq[0], xa), dot4(wq[1], xa), dot4(wq[2], xa), dot4(wq[3], xa));
-      k[t] = make_float4(dot4(wk[0], xa), dot4(wk[1], xa), dot4(wk[2], xa), dot4(wk[3], xa));
+      q[t] = block4x4(wq, xa);
+      k[t] = block4x4(wk, xa);
 #pragma unroll
       for (int j = 0; j < kNG; ++j) pg[t * kNG + j] = dot4(gc[j], xa) + dot4(gc[kNG + j], p3);
     };
@@ -174,21 +164,16 @@ __global__ __launch_bounds__(256) void mlstm_front_kernel(MlstmFrontArgs a) {
       const float gi = red[buf][0][t * kNG + h] + red[buf][1][t * kNG + h] + red[buf][2][t * kNG + h] + red[buf][3][t * kNG + h] + bias_i;
       const float gf = red[buf][0][t * kNG + kNH + h] + red[buf][1][t * kNG + kNH + h] + red[buf][2][t * kNG + kNH + h] +
                        red[buf][3][t * kNG + kNH + h] + bias_f;
-      const float lf = log_sigmoid(gf);
-      const float mn = fmaxf(lf + m, gi);
-      f[t] = expf(lf + m - mn);
-      ig[t] = expf(gi - mn);
-      mt[t] = mn;
-      m = mn;
+      const MlstmGate g = mlstm_gate_step(gi, gf, m);
+      f[t] = g.f;
+      ig[t] = g.i;
+      mt[t] = m = g.m;
     }
     // ---- normaliser state and q_t . n_t (wave-local: the wave's 256 channels are the head) ----
     float d[T];
 #pragma unroll
     for (int t = 0; t < T; ++t) {
-      n.x = f[t] * n.x + ig[t] * (k[t].x / sqrt_dh);
-      n.y = f[t] * n.y + ig[t] * (k[t].y / sqrt_dh);
-      n.z = f[t] * n.z + ig[t] * (k[t].z / sqrt_dh);
-      n.w = f[t] * n.w + ig[t] * (k[t].w / sqrt_dh);
+      n = mlstm_n_step(n, f[t], ig[t], k[t], sqrt_dh);
       d[t] = wave_sum(dot4(q[t], n));
     }
     *reinterpret_cast<float4*>(a.n_state + (int64_t)b * inner + c0) = n;
@@ -196,8 +181,8 @@ __global__ __launch_bounds__(256) void mlstm_front_kernel(MlstmFrontArgs a) {
       a.m_state[(int64_t)b * kNH + h] = m;
 #pragma unroll
       for (int t = 0; t < T; ++t) {
-        const float denom = fmaxf(fabsf(d[t]), expf(-mt[t])) + 1e-6f;
-        *reinterpret_cast<float4*>(a.scal + (((int64_t)b * T + t) * kNH + h) * 4) = make_float4(f[t], ig[t], denom, mt[t]);
+        *reinterpret_cast<float4*>(a.scal + (((int64_t)b * T + t) * kNH + h) * 4) =
+            make_float4(f[t], ig[t], mlstm_denominator(d[t], mt[t]), mt[t]);
       }
     }
   }

@@ -22,11 +22,9 @@
 
 #include "common.h"
 #include "device_math.h"
+#include "xlstm_rules.h"
 
 namespace lram {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -73,8 +71,6 @@ __device__ __forceinline__ LazyView lazy_view_of(const MlstmLazyArgs& a, int b, 
   v.zero = v.rs ? true : (v.fold ? false : v.zero_in);
   return v;
 }
-
-__device__ __forceinline__ int acc_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
 
 // =============================================================================================
 // fold: one workgroup per (env, head, 128 columns); exits at once unless the env folds or restarts this step.
@@ -257,7 +253,7 @@ __global__ __launch_bounds__(256) void mlstm_lazy_score_kernel(MlstmLazyArgs a) 
 #pragma unroll
       for (int t = 0; t < T; ++t) {
         *reinterpret_cast<float4*>(qs + t * DH + r4) = qv[t];
-        *reinterpret_cast<float4*>(ks + t * DH + r4) = make_float4(kv[t].x / sqrt_dh, kv[t].y / sqrt_dh, kv[t].z / sqrt_dh, kv[t].w / sqrt_dh);
+        *reinterpret_cast<float4*>(ks + t * DH + r4) = khat(kv[t], sqrt_dh);
       }
     }
     for (int r = 4 * (tid + 256); r < DH; r += 1024) {   // (head dims beyond 1024)
@@ -266,7 +262,7 @@ __global__ __launch_bounds__(256) void mlstm_lazy_score_kernel(MlstmLazyArgs a) 
         const int64_t off = ((int64_t)b * T + t) * inner + (int64_t)h * DH + r;
         const float4 q4 = *reinterpret_cast<const float4*>(a.q + off), k4 = *reinterpret_cast<const float4*>(a.k + off);
         *reinterpret_cast<float4*>(qs + t * DH + r) = q4;
-        *reinterpret_cast<float4*>(ks + t * DH + r) = make_float4(k4.x / sqrt_dh, k4.y / sqrt_dh, k4.z / sqrt_dh, k4.w / sqrt_dh);
+        *reinterpret_cast<float4*>(ks + t * DH + r) = khat(k4, sqrt_dh);
       }
     }
   }
@@ -462,8 +458,8 @@ __global__ __launch_bounds__(256) void mlstm_lazy_cell_kernel(MlstmLazyArgs a) {
         xa[t] = *reinterpret_cast<const float4*>(a.lean_xa + ((int64_t)b * T + t) * inner + (ch & ~3));
 #pragma unroll
       for (int t = 0; t < T; ++t) {
-        qs[t * DH + r] = wq4.x * xa[t].x + wq4.y * xa[t].y + wq4.z * xa[t].z + wq4.w * xa[t].w;
-        ks[t * DH + r] = (wk4.x * xa[t].x + wk4.y * xa[t].y + wk4.z * xa[t].z + wk4.w * xa[t].w) / sqrt_dh;
+        qs[t * DH + r] = dot4(wq4, xa[t]);
+        ks[t * DH + r] = khat(dot4(wk4, xa[t]), sqrt_dh);
       }
     } else {
       float qv[T], kv[T];
@@ -476,7 +472,7 @@ __global__ __launch_bounds__(256) void mlstm_lazy_cell_kernel(MlstmLazyArgs a) {
 #pragma unroll
       for (int t = 0; t < T; ++t) {
         qs[t * DH + r] = qv[t];
-        ks[t * DH + r] = kv[t] / sqrt_dh;
+        ks[t * DH + r] = khat(kv[t], sqrt_dh);
       }
     }
   };

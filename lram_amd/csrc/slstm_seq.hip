@@ -13,7 +13,7 @@
 //     its four 32 x 32 accumulator tiles are the four GATES of those channels -- the B operand is read from a copy of R
 //     re-packed [head][k][channel][gate] (one float4 per lane and k step, 512 contiguous bytes per half wave, L2-resident:
 //     256 KB per head), so accumulator column `lane & 31` of tile g is gate g of the lane's channel and the pointwise cell
-//     ([3P] slstm_pointwise: per-element n == 0 first-step rule) is lane-local: no exchange of gate sums at all;
+//     (slstm_cell, xlstm_rules.h: the one copy every sLSTM kernel applies) is lane-local: no exchange of gate sums at all;
 //   * the cell state (c, n, m) of a lane's 16 (env, channel) pairs lives in registers across the T tokens and is written
 //     back once; h_t goes to LDS (next token's A operand) and to the output rows.
 // The k index of an MFMA step is split over the lane halves as k = (SDH / 2) (lane >> 5) + j (j = 0 .. SDH / 2 - 1): each lane reads its A
@@ -29,10 +29,9 @@
 
 #include "common.h"
 #include "device_math.h"
+#include "xlstm_rules.h"
 
 namespace lram {
-
-typedef float sq_f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 constexpr int kEnv = 32;
@@ -66,9 +65,9 @@ __global__ __launch_bounds__(2 * kSDH, kSDH <= 256 ? 2 : 3) void slstm_seq_kerne
     const int b = min(b0 + e, a.B - 1);
     *reinterpret_cast<float4*>(&hs[0][e][c4]) = *reinterpret_cast<const float4*>(a.state + (int64_t)b * H + head * kSDH + c4);
   }
-  // ---- this lane's cells: envs e_r = (r & 3) + 8 (r >> 2) + 4 lh, r = 0 .. 15 (the accumulator rows it holds) ----
+  // ---- this lane's cells: envs e_r = acc_row(r, lh), r = 0 .. 15 (the accumulator rows it holds) ----
   float cs[16], ns[16], ms[16];
-  auto env_of = [&](int r) { return min(b0 + (r & 3) + 8 * (r >> 2) + 4 * lh, a.B - 1); };  // (clamped: rows beyond B are dropped at the stores)
+  auto env_of = [&](int r) { return min(b0 + acc_row(r, lh), a.B - 1); };  // (clamped: rows beyond B are dropped at the stores)
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const float* st = a.state + (int64_t)env_of(r) * H + ch;
@@ -84,7 +83,7 @@ __global__ __launch_bounds__(2 * kSDH, kSDH <= 256 ? 2 : 3) void slstm_seq_kerne
 #pragma unroll 1
   for (int t = 0; t < T; ++t) {
     const int cur = t & 1;
-    sq_f32x16 acc[4];
+    f32x16 acc[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -134,18 +133,10 @@ __global__ __launch_bounds__(2 * kSDH, kSDH <= 256 ? 2 : 3) void slstm_seq_kerne
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int r = 2 * r2 + q;
-        const int e = (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int e = acc_row(r, lh);
         const float iraw = gi[q] + acc[0][r] + bi, fraw = gf[q] + acc[1][r] + bf;
         const float zraw = gz[q] + acc[2][r] + bz, oraw = go[q] + acc[3][r] + bo;
-        const float logfplusm = ms[r] + log_sigmoid(fraw);
-        const float mnew = (ns[r] == 0.f) ? iraw : fmaxf(iraw, logfplusm);
-        const float ogate = sigmoid_f(oraw);
-        const float igate = fminf(expf(iraw - mnew), 1.f);
-        const float fgate = fminf(expf(logfplusm - mnew), 1.f);
-        const float cnew = fgate * cs[r] + igate * tanhf(zraw);
-        const float nnew = fgate * ns[r] + igate;
-        const float ynew = ogate * cnew / nnew;
-        cs[r] = cnew, ns[r] = nnew, ms[r] = mnew;
+        const float ynew = slstm_cell(iraw, fraw, zraw, oraw, cs[r], ns[r], ms[r]);
         hs[cur ^ 1][e][32 * w + li] = ynew;
         if (b0 + e < a.B) {
           a.yout[((unsigned)(b0 + e) * (unsigned)T + (unsigned)t) * (unsigned)H + ycol] = ynew;
@@ -157,7 +148,7 @@ __global__ __launch_bounds__(2 * kSDH, kSDH <= 256 ? 2 : 3) void slstm_seq_kerne
   }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int e = (r & 3) + 8 * (r >> 2) + 4 * lh;
+    const int e = acc_row(r, lh);
     if (b0 + e < a.B) {
       float* st = a.state + (int64_t)(b0 + e) * H + ch;
       st[BH] = cs[r], st[2 * BH] = ns[r], st[3 * BH] = ms[r];
@@ -179,7 +170,6 @@ __global__ __launch_bounds__(2 * kSDH, kSDH <= 256 ? 2 : 3) void slstm_seq_kerne
 //     streaming R from L2 (the same bytes as fp32), not by the matrix pipe.
 // Differences from the fp32 form are those of the f16x2 GEMMs (22-bit operands, lo * lo dropped); LRAM_GEMM=f32 keeps the fp32 form.
 // =============================================================================================
-typedef float sq_f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 sq_f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 sq_f16x4 __attribute__((ext_vector_type(4)));
 constexpr int kEnv16 = 16;
@@ -257,11 +247,11 @@ __global__ __launch_bounds__(2 * kSDH, kSDH <= 128 ? 2 : 1) void slstm_seq16_ker
 #pragma unroll 1
   for (int t = 0; t < T; ++t) {
     const int cur = t & 1;
-    sq_f32x4 acc[2][4];
+    v4f acc[2][4];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) acc[ct][g] = (sq_f32x4)(0.f);
+      for (int g = 0; g < 4; ++g) acc[ct][g] = (v4f)(0.f);
     // the token's input pre-activations (Wx): requested before the K loop where the register budget allows (GE), so that their
     // round trip hides behind it
     const unsigned grow = 4u * (unsigned)H;
@@ -318,15 +308,7 @@ __global__ __launch_bounds__(2 * kSDH, kSDH <= 128 ? 2 : 1) void slstm_seq16_ker
         const int e = 4 * lg + r;
         const float iraw = gl[r][0] + acc[ct][0][r] * ri[ct][0] + bias[ct][0], fraw = gl[r][1] + acc[ct][1][r] * ri[ct][1] + bias[ct][1];
         const float zraw = gl[r][2] + acc[ct][2][r] * ri[ct][2] + bias[ct][2], oraw = gl[r][3] + acc[ct][3][r] * ri[ct][3] + bias[ct][3];
-        const float logfplusm = ms[ct][r] + log_sigmoid(fraw);
-        const float mnew = (ns[ct][r] == 0.f) ? iraw : fmaxf(iraw, logfplusm);
-        const float ogate = sigmoid_f(oraw);
-        const float igate = fminf(expf(iraw - mnew), 1.f);
-        const float fgate = fminf(expf(logfplusm - mnew), 1.f);
-        const float cnew = fgate * cs[ct][r] + igate * tanhf(zraw);
-        const float nnew = fgate * ns[ct][r] + igate;
-        const float ynew = ogate * cnew / nnew;
-        cs[ct][r] = cnew, ns[ct][r] = nnew, ms[ct][r] = mnew;
+        const float ynew = slstm_cell(iraw, fraw, zraw, oraw, cs[ct][r], ns[ct][r], ms[ct][r]);
         const float ysc = ynew * kHScale;
         const _Float16 yh = (_Float16)ysc;
         hs[cur ^ 1][0][e][chl + 16 * ct] = yh;

@@ -11,6 +11,7 @@
 
 #include "common.h"
 #include "device_math.h"
+#include "xlstm_rules.h"
 
 namespace lram {
 
@@ -18,7 +19,7 @@ namespace lram {
 // mLSTM front end: one workgroup per env.
 //   conv1d_step (K taps, depthwise) -> SiLU -> block-diagonal q/k (from the conv branch) and v (from the
 //   pre-conv branch) -> gate pre-activations Wi.[q,k,v]+bi, Wf.[q,k,v]+bf (block reduction) -> stabilised
-//   gate scalars f_t, i_t, m_t -> normaliser state n_t and denominators max(|q.n_t|, exp(-m_t)) + 1e-6.
+//   gate scalars f_t, i_t, m_t -> normaliser state n_t and the denominators: the token rules of xlstm_rules.h.
 // Writes q,k,v,xa rows, the per-(token, head) scalars, and the updated conv / n / m state.
 // =============================================================================================
 namespace {
@@ -56,12 +57,7 @@ __device__ __forceinline__ void mlstm_pre_body(const MlstmPreArgs& a, const int 
   constexpr bool single = SINGLE;  // the launcher guarantees ngroups <= kPreThreads
   // (state is requested whether or not the env restarts and zeroed afterwards: a load that waits for the reset flag's own
   // round trip puts one more dependent memory round trip at the head of every workgroup)
-  // (zeroed by a bit mask, not a branch or a multiply: no control flow on the flag -- the compiler otherwise waits for it
-  // before issuing anything else -- and no NaN * 0)
-  auto masked = [](float v, unsigned keep) { return __uint_as_float(__float_as_uint(v) & keep); };
-  auto masked4 = [&](const float4& v, unsigned keep) {
-    return make_float4(masked(v.x, keep), masked(v.y, keep), masked(v.z, keep), masked(v.w, keep));
-  };
+  // (zeroed by a bit mask, masked / masked4: no control flow on the flag)
   float m_pre = single ? a.m_state[(int64_t)b * NH + min(tid, NH - 1)] : 0.f;  // (every lane: no branch; masked below)
   float4 q_keep[T], k_keep[T], n_pre = f4_zero();
 #pragma unroll
@@ -109,27 +105,10 @@ __device__ __forceinline__ void mlstm_pre_body(const MlstmPreArgs& a, const int 
       win[1] = win[2];
       win[2] = win[3];
       win[3] = xm;
-      float4 y;
-      y.x = win[0].x * cw[0].x + win[1].x * cw[0].y + win[2].x * cw[0].z + win[3].x * cw[0].w + cb.x;
-      y.y = win[0].y * cw[1].x + win[1].y * cw[1].y + win[2].y * cw[1].z + win[3].y * cw[1].w + cb.y;
-      y.z = win[0].z * cw[2].x + win[1].z * cw[2].y + win[2].z * cw[2].z + win[3].z * cw[2].w + cb.z;
-      y.w = win[0].w * cw[3].x + win[1].w * cw[3].y + win[2].w * cw[3].z + win[3].w * cw[3].w + cb.w;
-      float4 xa;
-      xa.x = silu_f(y.x);
-      xa.y = silu_f(y.y);
-      xa.z = silu_f(y.z);
-      xa.w = silu_f(y.w);
-      auto bd = [](const float4* w, const float4& x) {
-        float4 r;
-        r.x = w[0].x * x.x + w[0].y * x.y + w[0].z * x.z + w[0].w * x.w;
-        r.y = w[1].x * x.x + w[1].y * x.y + w[1].z * x.z + w[1].w * x.w;
-        r.z = w[2].x * x.x + w[2].y * x.y + w[2].z * x.z + w[2].w * x.w;
-        r.w = w[3].x * x.x + w[3].y * x.y + w[3].z * x.z + w[3].w * x.w;
-        return r;
-      };
-      qt[t] = bd(wq, xa);
-      kt[t] = bd(wk, xa);
-      vt[t] = bd(wv, xm);
+      const float4 xa = conv4_silu(win[0], win[1], win[2], win[3], cw, cb);
+      qt[t] = block4x4(wq, xa);
+      kt[t] = block4x4(wk, xa);
+      vt[t] = block4x4(wv, xm);
       q_keep[t] = qt[t], k_keep[t] = kt[t];
       if (!a.lean) {  // lean: the consumer (lazy read pass) rebuilds q, k, v from xa and the x half of u
         *reinterpret_cast<float4*>(a.q + row * inner + c0) = qt[t];
@@ -151,11 +130,10 @@ __device__ __forceinline__ void mlstm_pre_body(const MlstmPreArgs& a, const int 
                    iv = *reinterpret_cast<const float4*>(wi + 2 * inner);
       const float4 fq = *reinterpret_cast<const float4*>(wf), fk = *reinterpret_cast<const float4*>(wf + inner),
                    fv = *reinterpret_cast<const float4*>(wf + 2 * inner);
-      auto dot = [](const float4& x, const float4& y) { return x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w; };
 #pragma unroll
       for (int t = 0; t < T; ++t) {
-        pi[t][h] += dot(iq, qt[t]) + dot(ik, kt[t]) + dot(iv, vt[t]);
-        pf[t][h] += dot(fq, qt[t]) + dot(fk, kt[t]) + dot(fv, vt[t]);
+        pi[t][h] += gate_partial(iq, ik, iv, qt[t], kt[t], vt[t]);
+        pf[t][h] += gate_partial(fq, fk, fv, qt[t], kt[t], vt[t]);
       }
     }
   }
@@ -190,12 +168,10 @@ __device__ __forceinline__ void mlstm_pre_body(const MlstmPreArgs& a, const int 
     float m = single ? m_pre : (rs ? 0.f : a.m_state[(int64_t)b * NH + h]);
 #pragma unroll
     for (int t = 0; t < T; ++t) {
-      const float lf = log_sigmoid(gate_f[t][h]);
-      const float mn = fmaxf(lf + m, gate_i[t][h]);
-      s_f[t][h] = expf(lf + m - mn);
-      s_i[t][h] = expf(gate_i[t][h] - mn);
-      s_m[t][h] = mn;
-      m = mn;
+      const MlstmGate g = mlstm_gate_step(gate_i[t][h], gate_f[t][h], m);
+      s_f[t][h] = g.f;
+      s_i[t][h] = g.i;
+      s_m[t][h] = m = g.m;
     }
     a.m_state[(int64_t)b * NH + h] = m;
   }
@@ -217,18 +193,10 @@ __device__ __forceinline__ void mlstm_pre_body(const MlstmPreArgs& a, const int 
       float4 qv, kv;
       if (single) {
         qv = q_keep[t], kv = k_keep[t];
-      } else if (a.lean) {  // same 4 x 4 block products as phase 1 (this thread's own xa rows)
+      } else if (a.lean) {  // the block products of phase 1 again (this thread's own xa rows)
         const float4 xa = *reinterpret_cast<const float4*>(a.xa + row * inner + c0);
-        const float* wq = a.wq + (int64_t)cg * 16;
-        const float* wk = a.wk + (int64_t)cg * 16;
-        qv.x = wq[0] * xa.x + wq[1] * xa.y + wq[2] * xa.z + wq[3] * xa.w;
-        qv.y = wq[4] * xa.x + wq[5] * xa.y + wq[6] * xa.z + wq[7] * xa.w;
-        qv.z = wq[8] * xa.x + wq[9] * xa.y + wq[10] * xa.z + wq[11] * xa.w;
-        qv.w = wq[12] * xa.x + wq[13] * xa.y + wq[14] * xa.z + wq[15] * xa.w;
-        kv.x = wk[0] * xa.x + wk[1] * xa.y + wk[2] * xa.z + wk[3] * xa.w;
-        kv.y = wk[4] * xa.x + wk[5] * xa.y + wk[6] * xa.z + wk[7] * xa.w;
-        kv.z = wk[8] * xa.x + wk[9] * xa.y + wk[10] * xa.z + wk[11] * xa.w;
-        kv.w = wk[12] * xa.x + wk[13] * xa.y + wk[14] * xa.z + wk[15] * xa.w;
+        qv = block4x4(reinterpret_cast<const float4*>(a.wq + (int64_t)cg * 16), xa);
+        kv = block4x4(reinterpret_cast<const float4*>(a.wk + (int64_t)cg * 16), xa);
       } else {
         qv = *reinterpret_cast<const float4*>(a.q + row * inner + c0);
         kv = *reinterpret_cast<const float4*>(a.k + row * inner + c0);
@@ -240,11 +208,8 @@ __device__ __forceinline__ void mlstm_pre_body(const MlstmPreArgs& a, const int 
           f = s_f[t][h];
           i = s_i[t][h];
         }
-      n.x = f * n.x + i * (kv.x / sqrt_dh);
-      n.y = f * n.y + i * (kv.y / sqrt_dh);
-      n.z = f * n.z + i * (kv.z / sqrt_dh);
-      n.w = f * n.w + i * (kv.w / sqrt_dh);
-      const float d = qv.x * n.x + qv.y * n.y + qv.z * n.z + qv.w * n.w;
+      n = mlstm_n_step(n, f, i, kv, sqrt_dh);
+      const float d = dot4(qv, n);
 #pragma unroll
       for (int h = 0; h < NH; ++h) pq[t][h] += (h == hh) ? d : 0.f;
     }
@@ -261,9 +226,8 @@ __device__ __forceinline__ void mlstm_pre_body(const MlstmPreArgs& a, const int 
   if (tid < T * NH) {
     const int t = tid / NH, h = tid - t * NH;
     const float qn = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-    const float denom = fmaxf(fabsf(qn), expf(-s_m[t][h])) + 1e-6f;
-    float4 o = make_float4(s_f[t][h], s_i[t][h], denom, s_m[t][h]);
-    *reinterpret_cast<float4*>(a.scal + (((int64_t)b * T + t) * NH + h) * 4) = o;
+    *reinterpret_cast<float4*>(a.scal + (((int64_t)b * T + t) * NH + h) * 4) =
+        make_float4(s_f[t][h], s_i[t][h], mlstm_denominator(qn, s_m[t][h]), s_m[t][h]);
   }
 }
 
@@ -272,8 +236,8 @@ __global__ __launch_bounds__(kPreThreads) void mlstm_pre_kernel(MlstmPreArgs a) 
   mlstm_pre_body<T, NH, SINGLE>(a, blockIdx.x);
 }
 
-// Large-T variant of the front end (context prefill: T = 3 x timesteps-per-chunk, up to kMaxTokens): the same
-// arithmetic token by token with a block reduction per token, so the register footprint does not grow with T.
+// Large-T variant of the front end (context prefill: T = 3 x timesteps-per-chunk, up to kMaxTokens): the same token
+// rules (xlstm_rules.h) token by token with a block reduction per token, so the register footprint does not grow with T.
 template <int NH>
 __global__ __launch_bounds__(kPreThreads) void mlstm_pre_seq_kernel(MlstmPreArgs a) {
   __shared__ float red[4][2 * NH];
@@ -294,7 +258,6 @@ __global__ __launch_bounds__(kPreThreads) void mlstm_pre_seq_kernel(MlstmPreArgs
     nst[g] = (rs || cg >= ngroups) ? f4_zero() : *reinterpret_cast<const float4*>(a.n_state + (int64_t)b * inner + c0);
   }
   if (tid < NH) s_m[tid] = rs ? 0.f : a.m_state[(int64_t)b * NH + tid];
-  auto dot = [](const float4& x, const float4& y) { return x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w; };
   for (int t = 0; t < T; ++t) {
     const int64_t row = (int64_t)b * T + t;
     float pi[NH], pf[NH];
@@ -316,21 +279,10 @@ __global__ __launch_bounds__(kPreThreads) void mlstm_pre_seq_kernel(MlstmPreArgs
 #pragma unroll
         for (int c = 0; c < 4; ++c) cw[c] = *reinterpret_cast<const float4*>(a.conv_w + (int64_t)(c0 + c) * 4);
         const float4 cb = *reinterpret_cast<const float4*>(a.conv_b + c0);
-        float4 y;
-        y.x = win[g][0].x * cw[0].x + win[g][1].x * cw[0].y + win[g][2].x * cw[0].z + win[g][3].x * cw[0].w + cb.x;
-        y.y = win[g][0].y * cw[1].x + win[g][1].y * cw[1].y + win[g][2].y * cw[1].z + win[g][3].y * cw[1].w + cb.y;
-        y.z = win[g][0].z * cw[2].x + win[g][1].z * cw[2].y + win[g][2].z * cw[2].z + win[g][3].z * cw[2].w + cb.z;
-        y.w = win[g][0].w * cw[3].x + win[g][1].w * cw[3].y + win[g][2].w * cw[3].z + win[g][3].w * cw[3].w + cb.w;
-        const float4 xa = make_float4(silu_f(y.x), silu_f(y.y), silu_f(y.z), silu_f(y.w));
-        float4 q, k, v;
-        {
-          const float4* wq = reinterpret_cast<const float4*>(a.wq + (int64_t)cg * 16);
-          const float4* wk = reinterpret_cast<const float4*>(a.wk + (int64_t)cg * 16);
-          const float4* wv = reinterpret_cast<const float4*>(a.wv + (int64_t)cg * 16);
-          q = make_float4(dot(wq[0], xa), dot(wq[1], xa), dot(wq[2], xa), dot(wq[3], xa));
-          k = make_float4(dot(wk[0], xa), dot(wk[1], xa), dot(wk[2], xa), dot(wk[3], xa));
-          v = make_float4(dot(wv[0], xm), dot(wv[1], xm), dot(wv[2], xm), dot(wv[3], xm));
-        }
+        const float4 xa = conv4_silu(win[g][0], win[g][1], win[g][2], win[g][3], cw, cb);
+        const float4 q = block4x4(reinterpret_cast<const float4*>(a.wq + (int64_t)cg * 16), xa);
+        const float4 k = block4x4(reinterpret_cast<const float4*>(a.wk + (int64_t)cg * 16), xa);
+        const float4 v = block4x4(reinterpret_cast<const float4*>(a.wv + (int64_t)cg * 16), xm);
         *reinterpret_cast<float4*>(a.q + row * inner + c0) = q;
         *reinterpret_cast<float4*>(a.k + row * inner + c0) = k;
         *reinterpret_cast<float4*>(a.v + row * inner + c0) = v;
@@ -341,10 +293,10 @@ __global__ __launch_bounds__(kPreThreads) void mlstm_pre_seq_kernel(MlstmPreArgs
         for (int h = 0; h < NH; ++h) {
           const float* wi = a.wi + (int64_t)h * 3 * inner + c0;
           const float* wf = a.wf + (int64_t)h * 3 * inner + c0;
-          pi[h] += dot(*reinterpret_cast<const float4*>(wi), q) + dot(*reinterpret_cast<const float4*>(wi + inner), k) +
-                   dot(*reinterpret_cast<const float4*>(wi + 2 * inner), v);
-          pf[h] += dot(*reinterpret_cast<const float4*>(wf), q) + dot(*reinterpret_cast<const float4*>(wf + inner), k) +
-                   dot(*reinterpret_cast<const float4*>(wf + 2 * inner), v);
+          pi[h] += gate_partial(*reinterpret_cast<const float4*>(wi), *reinterpret_cast<const float4*>(wi + inner),
+                                *reinterpret_cast<const float4*>(wi + 2 * inner), q, k, v);
+          pf[h] += gate_partial(*reinterpret_cast<const float4*>(wf), *reinterpret_cast<const float4*>(wf + inner),
+                                *reinterpret_cast<const float4*>(wf + 2 * inner), q, k, v);
         }
       }
     }
@@ -361,12 +313,10 @@ __global__ __launch_bounds__(kPreThreads) void mlstm_pre_seq_kernel(MlstmPreArgs
       const int h = tid;
       const float gi = red[0][2 * h] + red[1][2 * h] + red[2][2 * h] + red[3][2 * h] + a.bi[h];
       const float gf = red[0][2 * h + 1] + red[1][2 * h + 1] + red[2][2 * h + 1] + red[3][2 * h + 1] + a.bf[h];
-      const float m = s_m[h];
-      const float lf = log_sigmoid(gf);
-      const float mn = fmaxf(lf + m, gi);
-      s_f[h] = expf(lf + m - mn);
-      s_i[h] = expf(gi - mn);
-      s_m[h] = mn;
+      const MlstmGate g = mlstm_gate_step(gi, gf, s_m[h]);
+      s_f[h] = g.f;
+      s_i[h] = g.i;
+      s_m[h] = g.m;
     }
     __syncthreads();
     float pq[NH];
@@ -384,12 +334,8 @@ __global__ __launch_bounds__(kPreThreads) void mlstm_pre_seq_kernel(MlstmPreArgs
             f = s_f[h];
             i = s_i[h];
           }
-        float4& n = nst[g];
-        n.x = f * n.x + i * (kg[g].x / sqrt_dh);
-        n.y = f * n.y + i * (kg[g].y / sqrt_dh);
-        n.z = f * n.z + i * (kg[g].z / sqrt_dh);
-        n.w = f * n.w + i * (kg[g].w / sqrt_dh);
-        const float d = dot(qg[g], n);
+        nst[g] = mlstm_n_step(nst[g], f, i, kg[g], sqrt_dh);
+        const float d = dot4(qg[g], nst[g]);
 #pragma unroll
         for (int h = 0; h < NH; ++h) pq[h] += (h == hh) ? d : 0.f;
       }
@@ -403,8 +349,7 @@ __global__ __launch_bounds__(kPreThreads) void mlstm_pre_seq_kernel(MlstmPreArgs
     if (tid < NH) {
       const int h = tid;
       const float qn = red[0][h] + red[1][h] + red[2][h] + red[3][h];
-      const float denom = fmaxf(fabsf(qn), expf(-s_m[h])) + 1e-6f;
-      *reinterpret_cast<float4*>(a.scal + (row * NH + h) * 4) = make_float4(s_f[h], s_i[h], denom, s_m[h]);
+      *reinterpret_cast<float4*>(a.scal + (row * NH + h) * 4) = make_float4(s_f[h], s_i[h], mlstm_denominator(qn, s_m[h]), s_m[h]);
     }
     __syncthreads();
   }
@@ -428,7 +373,6 @@ __global__ __launch_bounds__(kPreThreads) void mlstm_pre_seq_kernel(MlstmPreArgs
 // (16 B, coalesced: a wave reads 64/LPR rows x LPR*16 B contiguous), the 256/LPR row groups stride over
 // the DH rows; every C element is loaded once, updated T times in registers and stored once.
 // =============================================================================================
-typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr int kCellThreads = 256;
 
 template <int T, int LPR, int kCellUnroll>
@@ -460,7 +404,7 @@ __device__ __forceinline__ void mlstm_cell_body(const MlstmCellArgs& a, const in
     for (int t = 0; t < T; ++t) {
       const int64_t off = ((int64_t)b * T + t) * inner + (int64_t)h * DH + r;
       qs[t * DH + r] = a.q[off];
-      aks[t * DH + r] = ig[t] * (a.k[off] / sqrt_dh);
+      aks[t * DH + r] = ig[t] * khat(a.k[off], sqrt_dh);
     }
   }
   const int col0 = slice * CW + 4 * cl;
@@ -625,17 +569,7 @@ __global__ __launch_bounds__(256) void slstm_conv_kernel(SlstmConvArgs a) {
     win[1] = win[2];
     win[2] = win[3];
     win[3] = x;
-    float4 y;
-    y.x = win[0].x * cw[0].x + win[1].x * cw[0].y + win[2].x * cw[0].z + win[3].x * cw[0].w + cb.x;
-    y.y = win[0].y * cw[1].x + win[1].y * cw[1].y + win[2].y * cw[1].z + win[3].y * cw[1].w + cb.y;
-    y.z = win[0].z * cw[2].x + win[1].z * cw[2].y + win[2].z * cw[2].z + win[3].z * cw[2].w + cb.z;
-    y.w = win[0].w * cw[3].x + win[1].w * cw[3].y + win[2].w * cw[3].z + win[3].w * cw[3].w + cb.w;
-    float4 o;
-    o.x = silu_f(y.x);
-    o.y = silu_f(y.y);
-    o.z = silu_f(y.z);
-    o.w = silu_f(y.w);
-    *reinterpret_cast<float4*>(a.xc + row * D + c0) = o;
+    *reinterpret_cast<float4*>(a.xc + row * D + c0) = conv4_silu(win[0], win[1], win[2], win[3], cw, cb);
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k)
@@ -671,12 +605,7 @@ __global__ __launch_bounds__(256) void slstm_conv_rt_kernel(SlstmConvArgs a) {
     win[1] = win[2];
     win[2] = win[3];
     win[3] = x;
-    float4 y;
-    y.x = win[0].x * cw[0].x + win[1].x * cw[0].y + win[2].x * cw[0].z + win[3].x * cw[0].w + cb.x;
-    y.y = win[0].y * cw[1].x + win[1].y * cw[1].y + win[2].y * cw[1].z + win[3].y * cw[1].w + cb.y;
-    y.z = win[0].z * cw[2].x + win[1].z * cw[2].y + win[2].z * cw[2].z + win[3].z * cw[2].w + cb.z;
-    y.w = win[0].w * cw[3].x + win[1].w * cw[3].y + win[2].w * cw[3].z + win[3].w * cw[3].w + cb.w;
-    *reinterpret_cast<float4*>(a.xc + row * D + c0) = make_float4(silu_f(y.x), silu_f(y.y), silu_f(y.z), silu_f(y.w));
+    *reinterpret_cast<float4*>(a.xc + row * D + c0) = conv4_silu(win[0], win[1], win[2], win[3], cw, cb);
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(a.conv_state + ((int64_t)b * 4 + k) * D + c0) = win[k];
@@ -687,7 +616,7 @@ __global__ __launch_bounds__(256) void slstm_conv_rt_kernel(SlstmConvArgs a) {
   }
 }
 
-// sLSTM pointwise cell update for token t ([3P] slstm_pointwise: per-element n == 0 first-step rule).
+// sLSTM pointwise cell update for token t (slstm_cell, xlstm_rules.h).
 __global__ __launch_bounds__(256) void slstm_pointwise_kernel(SlstmPointwiseArgs a) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int H = a.H;
@@ -703,19 +632,12 @@ __global__ __launch_bounds__(256) void slstm_pointwise_kernel(SlstmPointwiseArgs
   const float oraw = g[3 * H] + r[3 * H] + a.bias[3 * H + c];
   const int64_t BH = (int64_t)a.state_B * H;
   float* st = a.state + (int64_t)b * H + c;
-  const float cs = st[BH], ns = st[2 * BH], ms = st[3 * BH];
-  const float logfplusm = ms + log_sigmoid(fraw);
-  const float mnew = (ns == 0.f) ? iraw : fmaxf(iraw, logfplusm);
-  const float ogate = sigmoid_f(oraw);
-  const float igate = fminf(expf(iraw - mnew), 1.f);
-  const float fgate = fminf(expf(logfplusm - mnew), 1.f);
-  const float cnew = fgate * cs + igate * tanhf(zraw);
-  const float nnew = fgate * ns + igate;
-  const float ynew = ogate * cnew / nnew;
+  float cs = st[BH], ns = st[2 * BH], ms = st[3 * BH];
+  const float ynew = slstm_cell(iraw, fraw, zraw, oraw, cs, ns, ms);
   st[0] = ynew;
-  st[BH] = cnew;
-  st[2 * BH] = nnew;
-  st[3 * BH] = mnew;
+  st[BH] = cs;
+  st[2 * BH] = ns;
+  st[3 * BH] = ms;
   a.yout[row * H + c] = ynew;
 }
 
@@ -725,12 +647,11 @@ __global__ __launch_bounds__(256) void slstm_pointwise_kernel(SlstmPointwiseArgs
 // fp32 matrix-core instruction (v_mfma_f32_32x32x2_f32), K = SDH split over the four waves.  Each lane requests its
 // operands straight from global memory -- its env's h_{t-1} row and its output's R row over the wave's K range, contiguous
 // 16-byte runs, all in flight together (one memory round trip, no LDS staging) -- the four partial tiles meet in LDS, then
-// thread (env, channel) applies slstm_pointwise_kernel's cell update ([3P] slstm_pointwise) to its four gate sums.
+// thread (env, channel) applies the cell rule (slstm_cell, xlstm_rules.h) to its four gate sums.
 // h_{t-1} is read from `hprev` (the state's h plane for the first token of a launch sequence, the previous token's rows of
 // yout afterwards) and h_t goes to yout -- and to the state's h plane only when a.write_h is set (never in a launch that
 // reads that plane: other workgroups still need it).
 constexpr int kSlTokCh = 8, kSlTokEnv = 32;
-typedef float sl_f32x16 __attribute__((ext_vector_type(16)));
 template <int SDH>
 __global__ __launch_bounds__(256) void slstm_token_kernel(SlstmTokenArgs a) {
   __shared__ float part[4][kSlTokEnv][33];
@@ -763,11 +684,11 @@ __global__ __launch_bounds__(256) void slstm_token_kernel(SlstmTokenArgs a) {
               go = gp[3 * H] + a.bias[3 * H + c];
   const int64_t BH = (int64_t)a.state_B * H;
   float* st = a.state + (int64_t)bb * H + c;
-  const float cs = st[BH], ns = st[2 * BH], ms = st[3 * BH];
+  float cs = st[BH], ns = st[2 * BH], ms = st[3 * BH];
   // every request above is issued before the first matrix product (left alone, the scheduler feeds the products with one
   // or two loads in flight: S / 4 dependent round trips instead of one)
   __builtin_amdgcn_sched_barrier(0);
-  sl_f32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
@@ -779,26 +700,18 @@ __global__ __launch_bounds__(256) void slstm_token_kernel(SlstmTokenArgs a) {
   }
   // lane (li, lh) holds column n = li of rows (r & 3) + 8 (r >> 2) + 4 lh
 #pragma unroll
-  for (int r = 0; r < 16; ++r) part[w][(r & 3) + 8 * (r >> 2) + 4 * lh][li] = acc[r];
+  for (int r = 0; r < 16; ++r) part[w][acc_row(r, lh)][li] = acc[r];
   __syncthreads();
   if (!live) return;
   float sum[4];
 #pragma unroll
   for (int g = 0; g < 4; ++g)
     sum[g] = (part[0][e][4 * ch + g] + part[1][e][4 * ch + g]) + (part[2][e][4 * ch + g] + part[3][e][4 * ch + g]);
-  const float iraw = gi + sum[0], fraw = gf + sum[1], zraw = gz + sum[2], oraw = go + sum[3];
-  const float logfplusm = ms + log_sigmoid(fraw);
-  const float mnew = (ns == 0.f) ? iraw : fmaxf(iraw, logfplusm);
-  const float ogate = sigmoid_f(oraw);
-  const float igate = fminf(expf(iraw - mnew), 1.f);
-  const float fgate = fminf(expf(logfplusm - mnew), 1.f);
-  const float cnew = fgate * cs + igate * tanhf(zraw);
-  const float nnew = fgate * ns + igate;
-  const float ynew = ogate * cnew / nnew;
+  const float ynew = slstm_cell(gi + sum[0], gf + sum[1], gz + sum[2], go + sum[3], cs, ns, ms);
   if (a.write_h) st[0] = ynew;
-  st[BH] = cnew;
-  st[2 * BH] = nnew;
-  st[3 * BH] = mnew;
+  st[BH] = cs;
+  st[2 * BH] = ns;
+  st[3 * BH] = ms;
   a.yout[row * H + c] = ynew;
 }
 

@@ -1,0 +1,181 @@
+#!/usr/bin/env python3
+"""Byte identity of two builds of the library on the recurrent paths: for refactors of the xLSTM kernels that must not move a bit.
+
+A fixed list of small cases (CASES: one per kernel path of xlstm_kernels.hip, mlstm_chunk.hip, mlstm_front.hip and slstm_seq.hip --
+every mlstm_pre_kernel head count, lean and not, the multi-env front end, the token-sequential and the chunkwise prefill in both cell
+forms, the four forms of the sLSTM recurrence) runs once on the PARENT commit's library (csrc/_variants/<--parent>.so,
+LRAM_LIB_VARIANT: build the parent commit and copy its liblram_hip.so there) and once on this tree's.  Every case is a fresh child
+process under its own time limit; the first child that does not exit cleanly ends the run.  A child prints one sha256 over the
+actions and tokens of every step (the hidden rows of an encoder call) and one per exported state tensor of block 0, of the last
+block and of the first sLSTM block: C, n, m, conv, the four sLSTM planes.  Env counts are ragged against every kernel's envs per
+workgroup (7, 19, 37); slot 2 restarts in the middle of every run.  Geometries: tests/geometry_cases.py, tests/layout_cases.py and
+the published presets (the only 4-head geometries with an inner dim beyond 1024 or an sLSTM head dim of 320).
+
+    python scripts/ab_state_digests.py [--parent parent] [--out report.txt]
+
+Prints one line per case and a JSON summary; exit status 1 when a digest differs (or a child failed)."""
+import argparse
+import hashlib
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FRONT = {"LRAM_FRONT_MULTI": "1", "LRAM_FRONT_MIN_ENVS": "1", "LRAM_FRONT_EPW": "3"}
+GEMM, STEP = {"LRAM_SLSTM_SEQ": "0", "LRAM_SLSTM_FUSED_ROWS": "0"}, {"LRAM_SLSTM_FUSED_ROWS": "0"}
+# name: (geometry, env slots, run, state mode, environment); run = ("steps", n) | ("encoder", tokens) | ("prefill", L, L, ...)
+CASES = {
+    # mlstm_pre_kernel<3, NH>: every head count, eager (q / k / v rows written) and lazy (lean: phase 3 rebuilds q and k from xa --
+    # the branch runs where the read pass fuses the scores, head dim 128 / 256, so never in the 4-head kernel beyond one channel
+    # group per thread); 4 heads beyond and inside one channel group per thread
+    "pre_nh1": ("geo:nh1_dh128", 7, ("steps", 6), "eager", {}),
+    "pre_nh2": ("geo:nh2_dh128", 7, ("steps", 6), "eager", {}),
+    "pre_nh8": ("geo:nh8_dh128", 19, ("steps", 6), "eager", {}),
+    "pre_nh1_lean": ("geo:nh1_dh128", 7, ("steps", 8), "lazy", {}),
+    "pre_nh2_lean": ("geo:nh2_dh128", 7, ("steps", 8), "lazy", {}),
+    "pre_nh8_lean": ("geo:nh8_dh128", 19, ("steps", 8), "lazy", {}),
+    "pre_nh4_wide": ("preset:xlstm_48m", 7, ("steps", 4), "eager", {}),
+    "pre_nh4_single": ("preset:xlstm_16m", 19, ("steps", 6), "eager", {}),
+    "pre_nh4_single_lean": ("preset:xlstm_16m", 19, ("steps", 8), "lazy", {"LRAM_FRONT_MULTI": "0"}),
+    "pre_t4": ("preset:xlstm_16m", 7, ("encoder", 4), "eager", {}),
+    # mlstm_front_kernel<3>: 19 envs, 3 per workgroup (the last workgroup holds one)
+    "front_epw3": ("preset:xlstm_16m", 19, ("steps", 8), "lazy", FRONT),
+    # mlstm_pre_seq_kernel: a 7-timestep context = launches of 12 and 9 tokens
+    "prefill_seq_nh4": ("lay:s_last", 7, ("prefill", 7, 7), "eager", {"LRAM_PREFILL_CHUNK": "0"}),
+    "prefill_seq_nh2": ("geo:nh2_dh128", 7, ("prefill", 7, 7), "eager", {"LRAM_PREFILL_CHUNK": "0"}),
+    # chunkwise prefill, both cell kernels: a full 63-token pass (two token tiles), then 24 tokens (one tile)
+    "chunk3_nh4": ("lay:s_last", 7, ("prefill", 21, 8), "eager", {"LRAM_PREFILL_CHUNK": "1"}),
+    "chunk3_nh2": ("geo:nh2_dh128", 7, ("prefill", 21, 8), "eager", {"LRAM_PREFILL_CHUNK": "1"}),
+    "chunk32_nh4": ("lay:s_last", 7, ("prefill", 21, 8), "eager", {"LRAM_PREFILL_CHUNK": "2"}),
+    "chunk32_nh2": ("geo:nh2_dh128", 7, ("prefill", 21, 8), "eager", {"LRAM_PREFILL_CHUNK": "2"}),
+    # sLSTM: recurrent GEMM + slstm_pointwise_kernel, slstm_token_kernel, slstm_seq16_kernel, slstm_seq_kernel
+    "slstm_gemm_b37": ("preset:xlstm_16m", 37, ("steps", 4), None, GEMM),
+    "slstm_gemm_b7": ("preset:xlstm_16m", 7, ("steps", 4), None, GEMM),
+    "slstm_token_b7": ("preset:xlstm_16m", 7, ("steps", 4), None, {}),
+    "slstm_token_b37": ("preset:xlstm_16m", 37, ("steps", 4), None, {}),
+    "slstm_seq16_b37": ("preset:xlstm_16m", 37, ("steps", 4), None, {**STEP, "LRAM_SLSTM_SEQ": "1"}),
+    "slstm_seq16_b7": ("preset:xlstm_16m", 7, ("steps", 4), None, {**STEP, "LRAM_SLSTM_SEQ": "1"}),
+    "slstm_seq32_b37": ("preset:xlstm_16m", 37, ("steps", 4), None, {**STEP, "LRAM_SLSTM_SEQ": "2"}),
+    "slstm_seq32_b7": ("preset:xlstm_16m", 7, ("steps", 4), None, {**STEP, "LRAM_SLSTM_SEQ": "2"}),
+    "slstm_seq32_dh320": ("preset:xlstm_206m", 37, ("steps", 3), None, {**STEP, "LRAM_SLSTM_SEQ": "2"}),   # (the instances that spill)
+}
+RESTART_SLOT = 2
+
+
+def case_spec(geometry):
+    kind, name = geometry.split(":")
+    if kind == "preset":
+        from lram_amd import preset
+        return preset(name)
+    if kind == "geo":
+        from tests.geometry_cases import case_spec as geo
+        return geo(name)
+    from tests.layout_cases import case_spec as lay
+    return lay(name)
+
+
+def child(name):
+    import torch
+    from lram_amd import engine, init_state_dict
+    from tests.helpers import make_inputs
+    geometry, B, run, mode, _ = CASES[name]
+    spec = case_spec(geometry)
+    dev = torch.device("cuda", 0)
+    eng = engine.Engine(spec, init_state_dict(spec, seed=5), B, device=dev)
+    if mode is not None:
+        eng.set_state_mode(mode)
+    h, digests = hashlib.sha256(), {}
+
+    def take(t):
+        h.update(t.detach().cpu().contiguous().numpy().tobytes())
+
+    if run[0] == "encoder":
+        g = torch.Generator().manual_seed(3)
+        for call in range(2):   # the second call reads the state the first one left; slot RESTART_SLOT restarts in it
+            mask = torch.zeros(B, dtype=torch.uint8)
+            mask[RESTART_SLOT] = call
+            take(eng.encoder_step(torch.randn(B, run[1], spec.d_model, generator=g).to(dev), mask.to(dev)))
+    else:
+        seq = make_inputs(spec, B, sum(run[1:]), seed=41, reset_prob=0.0)   # (every slot starts at timestep 0)
+        seq[len(seq) // 2 if run[0] == "steps" else sum(run[1:-1])][3][RESTART_SLOT] = 1   # prefill: at the last context's start
+        if run[0] == "steps":
+            for obs, rtg, rew, mask in seq:
+                a, tok = eng.step(obs.to(dev), rtg.to(dev), rew.to(dev), mask.to(dev))
+                take(a), take(tok)
+        else:
+            t0 = 0
+            for L in run[1:]:   # one prefill call per context, on the state the one before left
+                part = seq[t0:t0 + L]
+                obs, rtg, rew = (torch.stack([x[i] for x in part], 1).contiguous().to(dev) for i in range(3))
+                a, tok = eng.prefill(obs, rtg, rew, part[0][3].to(dev))
+                take(a), take(tok)
+                t0 += L
+    torch.cuda.synchronize()
+    digests["outputs"] = h.hexdigest()
+    blocks = sorted({0, spec.n_blocks - 1} | set(list(spec.slstm_at)[:1]))
+    for blk in blocks:
+        for which, what in ((0, "planes"), (3, "conv")) if blk in spec.slstm_at else ((0, "C"), (1, "n"), (2, "m"), (3, "conv")):
+            t = eng.export_state_tensor(blk, which)
+            digests[f"block{blk}.{what}"] = hashlib.sha256(t.cpu().contiguous().numpy().tobytes()).hexdigest()
+    counts = eng.slstm_counts() if spec.slstm_at else {}
+    ran = eng.state_mode   # (what lram_get_state_mode reports: a "lazy" run took the lean front end where the head dim is 128 / 256)
+    eng.close()
+    print(json.dumps({"case": name, "digests": digests, "slstm": counts, "mode": ran}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", default="parent", help="csrc/_variants/<name>.so: the parent commit's library")
+    ap.add_argument("--out", help="write the report here as well")
+    ap.add_argument("--timeout", type=int, default=150, help="time limit of one child, seconds")
+    ap.add_argument("--case", choices=list(CASES), help="(internal) run one case in this process")
+    args = ap.parse_args()
+    if args.case:
+        return child(args.case)
+    if not os.path.exists(os.path.join(ROOT, "lram_amd", "csrc", "_variants", args.parent + ".so")):
+        sys.exit(f"csrc/_variants/{args.parent}.so is missing: build the parent commit and copy its liblram_hip.so there")
+    lines, results = [], {}
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    for lib in (args.parent, None):
+        for name, (_, _, _, _, env) in CASES.items():
+            env = {**os.environ, **env}
+            env.pop("LRAM_LIB_VARIANT", None)
+            if lib:
+                env["LRAM_LIB_VARIANT"] = lib
+            try:
+                p = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", name], capture_output=True, text=True,
+                                   timeout=args.timeout, env=env, cwd=ROOT)
+                rc, out, err = p.returncode, p.stdout, p.stderr
+            except subprocess.TimeoutExpired as e:
+                rc, out, err = 124, "", f"time limit of {args.timeout} s: {e}"
+            if rc != 0:   # nothing more runs on the device after a child that did not exit cleanly
+                say(f"{name} on {lib or 'tree'}: exit status {rc}\n{err[-2000:]}")
+                sys.exit(1)
+            results[(lib or "tree", name)] = json.loads(out.strip().splitlines()[-1])
+            print(f"[{lib or 'tree'}] {name}: done", file=sys.stderr, flush=True)
+    differ = []
+    for name, (geometry, B, run, mode, env) in CASES.items():
+        a, b = results[(args.parent, name)], results[("tree", name)]
+        bad = sorted(k for k in a["digests"] if a["digests"][k] != b["digests"].get(k))
+        differ += [f"{name}:{k}" for k in bad]
+        forms = " ".join(f"{k}={v}" for k, v in b["slstm"].items() if v)
+        say(f"{name:22s} {geometry:18s} B={B:<3d} {' '.join(map(str, run)):14s} {(mode or 'auto') + '>' + b['mode'][:5]:11s} "
+            f"{' '.join(f'{k}={v}' for k, v in env.items()) or '-':58s} {len(a['digests'])} digests "
+            f"{'EQUAL' if not bad else 'DIFFER: ' + ', '.join(bad)}  outputs {b['digests']['outputs'][:12]}  sLSTM launches: {forms or '-'}")
+    n = sum(len(results[("tree", c)]["digests"]) for c in CASES)
+    say(json.dumps({"cases": len(CASES), "digests": n, "differ": differ}))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(1 if differ else 0)
+
+
+if __name__ == "__main__":
+    main()
