@@ -422,6 +422,8 @@ void launch_mlstm_chunk_cell(const MlstmCellArgs& a, hipStream_t stream);
 // ---------------------------------------------------------------------------------------------
 constexpr int kLazyWindow = 48;  // window capacity in tokens
 constexpr int kLazyWT = kLazyWindow + 4;  // row pitch of the per-step window scores (LDS): window + this step's tokens
+// The fold class that is due at `step` (or at a launch's phase): the smallest b with (step + b) % period == 0.
+constexpr int lazy_due_class(int64_t step, int period) { return (period - (int)(step % period)) % period; }
 struct MlstmLazyArgs {
   float* C;               // [B, NH, DH, DH] C_base (fold: in/out; cell: in)
   float* wk;              // [B, NH, W, DH] window khat_j = k_j / sqrt(DH)

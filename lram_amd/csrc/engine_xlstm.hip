@@ -34,10 +34,27 @@ MlstmLazyArgs lazy_args(lram_engine* e, int i, int T, const uint8_t* reset, int 
 bool lazy_bound_compact(const lram_engine* e, int64_t step, int T) {
   const int P = e->lazy_period;
   if ((int)e->lazy_bound.size() != P) return false;
-  const int c_due = (P - (int)(step % P)) % P;
+  const int c_due = lazy_due_class(step, P);
   for (int cls = 0; cls < P; ++cls)
     if (cls != c_due && e->lazy_bound[cls] + T > kLazyWindow) return false;
   return true;
+}
+
+// The fold of one block over all env slots, for the step at lazy_step + step_off: the live range, then the parked range.  (A step's
+// reset mask holds the live rows only: parked slots [n_live, B) fold in a launch of their own, without a mask -- a step never resets
+// them -- so every class's fold still covers all its slots and the host-side bounds stay true.  The parked launch of a compact fold
+// takes the compact grid view first, compact == 2 -- most parked windows are empty -- or is not launched at all.)
+void fold_block(lram_engine* e, int i, int T, const uint8_t* reset, bool compact, int step_off, hipStream_t s) {
+  MlstmLazyArgs la = lazy_args(e, i, T, reset, 0, e->n_live, step_off);
+  la.compact = compact ? 1 : 0;
+  prof_record(e, s, true, true);
+  launch_mlstm_lazy_fold(la, s);
+  if (e->n_live < e->B && !e->parked_windows_empty(e->lazy_step + step_off)) {
+    MlstmLazyArgs lp = lazy_args(e, i, T, nullptr, e->n_live, e->B - e->n_live, step_off);
+    lp.compact = compact ? 2 : 0;
+    launch_mlstm_lazy_fold(lp, s);
+  }
+  prof_record(e, s, false, true);
 }
 
 }  // namespace
@@ -82,7 +99,7 @@ void lazy_finish_prefold(lram_engine* e, hipStream_t s) {
   const lram_config& c = e->cfg;
   const int B = e->B, NH = c.n_heads, P = e->lazy_period;
   const int side = (int)(e->lazy_step & 1);             // what the next step reads = what the last one wrote
-  const int first = (P - (int)(e->lazy_step % P)) % P;   // the due class: smallest b with (lazy_step + b) % P == 0
+  const int first = lazy_due_class(e->lazy_step, P);
   int k = 0;
   for (int i = 0; i < c.n_blocks; ++i) {
     if (c.block_is_slstm[i] || k++ < pf.blocks) continue;
@@ -451,7 +468,7 @@ void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* res
       e->lazy_bound.assign(P, kLazyWindow);
       lazy_compact = false;
     }
-    const int c_due = (P - (int)(e->lazy_step % P)) % P;
+    const int c_due = lazy_due_class(e->lazy_step, P);
     for (int cls = 0; cls < P; ++cls) {
       if (cls == c_due)
         e->lazy_bound[cls] = 0;
@@ -485,19 +502,8 @@ void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* res
     stream_after(e, fold_stream, sl[0].s);
   }
   std::vector<char> folded(c.n_blocks, 0);
-  auto launch_folds = [&](int i) {  // one launch per block over all env slots: folds do not care about the slices
-    // (the step's reset mask holds the live rows only: parked slots [n_live, B) fold in a launch of their own, without a mask --
-    // a step never resets them -- so every class's fold still covers all its slots and the host-side bounds stay true)
-    MlstmLazyArgs la = lazy_args(e, i, T, reset, 0, e->n_live);
-    la.compact = lazy_compact ? 1 : 0;
-    prof_record(e, fold_stream, true, true);
-    launch_mlstm_lazy_fold(la, fold_stream);
-    if (e->n_live < e->B && !e->parked_windows_empty(e->lazy_step)) {
-      MlstmLazyArgs lp = lazy_args(e, i, T, nullptr, e->n_live, e->B - e->n_live);
-      lp.compact = la.compact ? 2 : 0;   // (2: the compact grid, view first -- most parked windows are empty)
-      launch_mlstm_lazy_fold(lp, fold_stream);
-    }
-    prof_record(e, fold_stream, false, true);
+  auto launch_folds = [&](int i) {  // one fold per block over all env slots: folds do not care about the slices
+    fold_block(e, i, T, reset, lazy_compact, 0, fold_stream);
     folded[i] = 1;
   };
   auto next_mlstm = [&](int i) {
@@ -601,17 +607,7 @@ void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* res
       e->prefold.step = e->lazy_step + 1, e->prefold.period = e->lazy_period, e->prefold.B = e->B, e->prefold.blocks = 0;
       e->prefold.pending = true;
       for (int k = next_mlstm(-1); k >= 0 && e->prefold.blocks < lram_engine::fold_tail_blocks; k = next_mlstm(k)) {
-        // (live and parked range apart, as launch_folds has them: the parked one looks first, or is not launched at all)
-        MlstmLazyArgs la = lazy_args(e, k, T, nullptr, 0, e->n_live, 1);
-        la.compact = 1;
-        prof_record(e, hbm, true, true);
-        launch_mlstm_lazy_fold(la, hbm);
-        if (e->n_live < e->B && !e->parked_windows_empty(e->lazy_step + 1)) {
-          MlstmLazyArgs lp = lazy_args(e, k, T, nullptr, e->n_live, e->B - e->n_live, 1);
-          lp.compact = 2;
-          launch_mlstm_lazy_fold(lp, hbm);
-        }
-        prof_record(e, hbm, false, true);
+        fold_block(e, k, T, nullptr, true, 1, hbm);
         ++e->prefold.blocks;
       }
     }

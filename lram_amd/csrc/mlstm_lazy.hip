@@ -19,6 +19,7 @@
 // every kernel evaluates identically -- no flags, no inter-workgroup hand-off.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "device_math.h"
@@ -29,6 +30,7 @@ namespace lram {
 namespace {
 
 constexpr int W = kLazyWindow;
+constexpr int WT = kLazyWT;  // window + this step's tokens (row pitch of the score rows)
 
 struct LazyView {
   int n_in;   // tokens pending at the start of the step (what a fold merges)
@@ -71,6 +73,89 @@ __device__ __forceinline__ LazyView lazy_view_of(const MlstmLazyArgs& a, int b, 
   v.zero = v.rs ? true : (v.fold ? false : v.zero_in);
   return v;
 }
+// "Request first, look later": the view of the two raw words, resolved behind everything the kernel has requested so far
+// (late == false, the fold's launches that look first: no fence, the plain view).
+__device__ __forceinline__ LazyView lazy_view_late(const MlstmLazyArgs& a, int b, LazyRaw& raw, bool late = true) {
+  if (late) {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" : "+v"(raw.rb), "+v"(raw.word));  // opaque: the view (and its wait) stays behind the requests above
+  }
+  return lazy_view_of(a, b, raw);
+}
+
+// ---- The window rules, once: what a pending token contributes to a later readout, and what a step leaves for the next one.
+// Values in, values out, as in xlstm_rules.h; the kernels keep their own request order, fences, layouts and dot-product loops.
+
+// the step's starting scale: a restart or a fold leaves C_base at scale 1
+__device__ __forceinline__ float lazy_g0(const LazyView& lv, float g_raw) { return (lv.rs || lv.fold) ? 1.f : g_raw; }
+
+// gates of a step's T tokens for one (env, head): f_t, i_t, den_t and the running product F[t] = f_1 .. f_t
+template <int T>
+struct LazyGates {
+  float f[T], ig[T], den[T], F[T];
+  __device__ __forceinline__ LazyGates(const float* scal, int b, int h, int NH) {
+    float Fc = 1.f;
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      const float4 s = *reinterpret_cast<const float4*>(scal + (((int64_t)b * T + t) * NH + h) * 4);
+      f[t] = s.x;
+      ig[t] = s.y;
+      den[t] = s.z;
+      Fc *= s.x;
+      F[t] = Fc;
+    }
+  }
+};
+
+// c_{t,j}: row j of the window (n pending rows, then this step's tokens) as token t's readout sees it
+template <int T>
+__device__ __forceinline__ float window_coefficient(int j, int t, int n, const float* s_coef, const LazyGates<T>& g) {
+  if (j < n) return s_coef[j] * g.F[t];
+  const int u = j - n;  // this step's token u reaches t >= u with i_u f_{u+1} .. f_t
+  if (u > t) return 0.f;
+  float c = 1.f;
+#pragma unroll
+  for (int x = 0; x < T; ++x) {
+    if (x == u) c *= g.ig[x];
+    if (x > u && x <= t) c *= g.f[x];
+  }
+  return c;
+}
+
+// Bookkeeping for the next step ("out" side of the ping-pong): the rows' coefficients are the coefficient rule at the step's last
+// token, the scale has taken every f of the step, the count word carries the zero bit on.
+template <int T>
+__device__ __forceinline__ void write_window_book(const MlstmLazyArgs& a, int b, int h, int tid, int n, const LazyView& lv, float g0,
+                                                  const float* s_coef, const LazyGates<T>& g) {
+  const int64_t bh = (int64_t)b * a.NH + h;
+  if (tid < n + T) a.coef_out[bh * W + tid] = window_coefficient<T>(tid, T - 1, n, s_coef, g);
+  if (tid == 0) {
+    a.g_out[bh] = g0 * g.F[T - 1];
+    if (h == 0) a.count_out[b] = (n + T) | (lv.zero ? kZeroBit : 0);
+  }
+}
+
+// Tail of a row of scores: the lanes' partial dots q_t . khat_j reduced over the wave, times c_{t,j}; lane 0 stores p[t][j].
+template <int T>
+__device__ __forceinline__ void store_window_scores(const float (&p)[T], int j, int n, int lane, const float* s_coef,
+                                                    const LazyGates<T>& g, float* pw) {
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    const float s = wave_sum(p[t]);
+    if (lane == 0 && j < n + T) pw[t * WT + j] = window_coefficient<T>(j, t, n, s_coef, g) * s;
+  }
+}
+
+// dispatch of a launch on the step's token count: f(std::integral_constant<int, T>)
+template <class F>
+void with_tokens(int T, F&& f) {
+  switch (T) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
 
 // =============================================================================================
 // fold: one workgroup per (env, head, 128 columns); exits at once unless the env folds or restarts this step.
@@ -82,6 +167,8 @@ constexpr int kFPK = 40;   // LDS pitch of the scaled khat tile (32 rows of DH)
 constexpr int kFR = 64;    // rows of C per workgroup (two 32-row MFMA tiles): many short workgroups hide the
                            // load -> MFMA -> store latency of a fold better than few long ones
 constexpr int WF = W;      // window rows held in LDS
+// row of C that register r of the t-th 32 x 32 MFMA accumulator of a workgroup holds (lanes 32 .. 63: four rows further down)
+__device__ __forceinline__ int mfma32_row(int t, int r) { return 32 * t + (r & 3) + 8 * (r >> 2); }
 // (Removed after measurement, profiles/EXPERIMENTS.md: a 40-row LDS window for four workgroups per CU -- the fold got 25 %
 // shorter, the step did not; a fold + readout form that handed the read pass q . C_new for the strips it had just rewritten --
 // 2.3 GB of 48 fewer per step and 4-5 % SLOWER, because a fold that needs this step's q sits on the slice's critical chain.)
@@ -117,11 +204,9 @@ __device__ __forceinline__ void mlstm_lazy_fold_body(const MlstmLazyArgs& a) {
 #pragma unroll
     for (int t = 0; t < kFR / 32; ++t)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) cold[t][r] = cp0[(int64_t)(32 * t + (r & 3) + 8 * (r >> 2)) * DH];
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" : "+v"(raw.rb), "+v"(raw.word));  // opaque: the view (and its wait) stays behind the requests above
+      for (int r = 0; r < 16; ++r) cold[t][r] = cp0[(int64_t)mfma32_row(t, r) * DH];
   }
-  const LazyView lv = lazy_view_of(a, b, raw);
+  const LazyView lv = lazy_view_late(a, b, raw, early);
   if (!lv.fold) return;
   const int n = lv.n_in;
   const int kt8 = (n + 7) >> 3;
@@ -135,7 +220,7 @@ __device__ __forceinline__ void mlstm_lazy_fold_body(const MlstmLazyArgs& a) {
     for (int t = 0; t < kFR / 32; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        cold[t][r] = lv.zero_in ? 0.f : cp0[(int64_t)(32 * t + (r & 3) + 8 * (r >> 2)) * DH];
+        cold[t][r] = lv.zero_in ? 0.f : cp0[(int64_t)mfma32_row(t, r) * DH];
   } else if (lv.zero_in) {
 #pragma unroll
     for (int t = 0; t < kFR / 32; ++t)
@@ -193,7 +278,7 @@ __device__ __forceinline__ void mlstm_lazy_fold_body(const MlstmLazyArgs& a) {
       }
     }
 #pragma unroll
-    for (int r = 0; r < 16; ++r) cp0[(int64_t)(32 * t + (r & 3) + 8 * (r >> 2)) * DH] = acc[r];
+    for (int r = 0; r < 16; ++r) cp0[(int64_t)mfma32_row(t, r) * DH] = acc[r];
   }
 }
 
@@ -203,8 +288,6 @@ __global__ __launch_bounds__(256) void mlstm_lazy_fold_kernel(MlstmLazyArgs a) {
 // class's first fold on, so these workgroups look at the env's view first, as the full grid's do, instead of requesting a tile of
 // C_base they will not use: ~300 envs x 7 blocks x 1 MB read for nothing per step at 4096 slots otherwise.
 __global__ __launch_bounds__(256) void mlstm_lazy_fold_parked_kernel(MlstmLazyArgs a) { mlstm_lazy_fold_body<true>(a); }
-
-constexpr int WT = kLazyWT;  // window + this step's tokens (row pitch of the score rows)
 
 // =============================================================================================
 // score (geometries with several column slices per head, where the cell kernel's own score computation would be
@@ -229,16 +312,7 @@ __global__ __launch_bounds__(256) void mlstm_lazy_score_kernel(MlstmLazyArgs a) 
   LazyRaw raw = lazy_raw(a, b);
   const int64_t base = ((int64_t)b * NH + h) * W;
   const float coef_raw = tid < W ? a.coef_in[base + tid] : 0.f;
-  float f[T], ig[T], F[T];
-  float Fc = 1.f;
-#pragma unroll
-  for (int t = 0; t < T; ++t) {
-    const float4 s = *reinterpret_cast<const float4*>(a.scal + (((int64_t)b * T + t) * NH + h) * 4);
-    f[t] = s.x;
-    ig[t] = s.y;
-    Fc *= s.x;
-    F[t] = Fc;
-  }
+  const LazyGates<T> gates(a.scal, b, h, NH);  // (den is not used here)
   const float sqrt_dh = sqrtf((float)DH);
   {  // q / k of the step's tokens -> LDS: one float4 of four channels per thread (head dims up to 1024 without a loop)
     const int r4 = min(4 * tid, DH - 4);
@@ -266,28 +340,11 @@ __global__ __launch_bounds__(256) void mlstm_lazy_score_kernel(MlstmLazyArgs a) 
       }
     }
   }
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" : "+v"(raw.rb), "+v"(raw.word));  // opaque: the view (and its wait) stays behind the requests above
-  const LazyView lv = lazy_view_of(a, b, raw);
+  const LazyView lv = lazy_view_late(a, b, raw);
   const int n = lv.n;
   if (tid < W) s_coef[tid] = tid < n ? coef_raw : 0.f;
   __syncthreads();
-  // ---- bookkeeping for the next step ----
-  if (tid < n) a.coef_out[base + tid] = s_coef[tid] * F[T - 1];
-  if (tid < T) {
-    float c = 1.f;
-#pragma unroll
-    for (int x = 0; x < T; ++x) {
-      if (x == tid) c *= ig[x];
-      if (x > tid) c *= f[x];
-    }
-    a.coef_out[base + n + tid] = c;
-  }
-  if (tid == 0) {
-    const float g = (lv.rs || lv.fold) ? 1.f : a.g_in[(int64_t)b * NH + h];
-    a.g_out[(int64_t)b * NH + h] = g * F[T - 1];
-    if (h == 0) a.count_out[b] = (n + T) | (lv.zero ? kZeroBit : 0);
-  }
+  write_window_book<T>(a, b, h, tid, n, lv, tid == 0 ? lazy_g0(lv, a.g_in[(int64_t)b * NH + h]) : 0.f, s_coef, gates);
   // ---- p[t][j]: each wave takes four window rows at a time (their loads are issued together) ----
   const float* wkb = a.wk + base * DH;
   float* pwo = a.pw + (((int64_t)b * NH + h) * T) * WT;
@@ -341,31 +398,7 @@ __global__ __launch_bounds__(256) void mlstm_lazy_score_kernel(MlstmLazyArgs a) 
       }
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int j = j0 + i;
-#pragma unroll
-      for (int t = 0; t < T; ++t) {
-        const float s = wave_sum(p[i][t]);
-        if (lane == 0 && j < n + T) {
-          float c;
-          if (j < n) {
-            c = s_coef[j] * F[t];
-          } else {
-            const int u = j - n;  // this step's token u reaches t >= u with i_u f_{u+1} .. f_t
-            c = 0.f;
-            if (u <= t) {
-              c = 1.f;
-#pragma unroll
-              for (int x = 0; x < T; ++x) {
-                if (x == u) c *= ig[x];
-                if (x > u && x <= t) c *= f[x];
-              }
-            }
-          }
-          pwo[t * WT + j] = c * s;
-        }
-      }
-    }
+    for (int i = 0; i < 4; ++i) store_window_scores<T>(p[i], j0 + i, n, lane, s_coef, gates, pwo);
   }
 }
 
@@ -395,6 +428,15 @@ __global__ __launch_bounds__(256) void mlstm_lazy_score_kernel(MlstmLazyArgs a) 
 // default period of 13 and 3 tokens per step at most 36 rows are pending when a read pass starts; rows beyond it take a
 // late-load path).  Variants that were measured and removed (narrow requests, scores after the pass, first rows of C_base
 // requested before the scores, other row counts in flight): profiles/EXPERIMENTS.md.
+// registers of one of the cell kernel's modes: N values in the instances of that mode, nothing in the others
+template <class V, int N>
+struct ModeRegs {
+  V v[N];
+  __device__ __forceinline__ V& operator[](int i) { return v[i]; }
+};
+template <class V>
+struct ModeRegs<V, 0> {};
+
 template <int T, int LPR, int UNR, int KPL, int WP = W>
 __global__ __launch_bounds__(256) void mlstm_lazy_cell_kernel(MlstmLazyArgs a) {
   static_assert(KPL == 4 || KPL == 0 || KPL == -1, "KPL: 4 (wide window rows, scores first), 0 (late loads), -1 (score kernel)");
@@ -426,19 +468,7 @@ __global__ __launch_bounds__(256) void mlstm_lazy_cell_kernel(MlstmLazyArgs a) {
   LazyRaw raw = lazy_raw(a, b);
   const float g_raw = a.g_in[(int64_t)b * NH + h];
 
-  float den[T], G[T], f[T], ig[T], F[T];
-  {
-    float Fc = 1.f;
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-      const float4 s = *reinterpret_cast<const float4*>(a.scal + (((int64_t)b * T + t) * NH + h) * 4);
-      f[t] = s.x;
-      ig[t] = s.y;
-      den[t] = s.z;
-      Fc *= s.x;
-      F[t] = Fc;          // f_1 .. f_t
-    }
-  }
+  const LazyGates<T> gates(a.scal, b, h, NH);
   const float sqrt_dh = sqrtf((float)DH);
   const bool lean = KPL >= 0 && a.lean_wq != nullptr;
   // (the window coefficient is requested with everything above and kept or dropped once the pending count is known)
@@ -479,16 +509,15 @@ __global__ __launch_bounds__(256) void mlstm_lazy_cell_kernel(MlstmLazyArgs a) {
   if (tid < DH) stage_qk(tid);
   for (int r = tid + 256; r < DH; r += 256) stage_qk(r);
   // the view is resolved only here, with the q / k operands requested and stored
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" : "+v"(raw.rb), "+v"(raw.word));  // opaque: its consumers (and their wait) stay behind the requests above
-  const LazyView lv = lazy_view_of(a, b, raw);
+  const LazyView lv = lazy_view_late(a, b, raw);
   const int n = lv.n;
-  const float g0 = (lv.rs || lv.fold) ? 1.f : g_raw;
+  const float g0 = lazy_g0(lv, g_raw);
+  float G[T];
 #pragma unroll
-  for (int t = 0; t < T; ++t) G[t] = g0 * F[t];  // g f_1 .. f_t
+  for (int t = 0; t < T; ++t) G[t] = g0 * gates.F[t];  // g f_1 .. f_t
   const int64_t base = ((int64_t)b * NH + h) * W;
   if (tid < W) s_coef[tid] = tid < n ? coef_raw : 0.f;
-  if (KPL < 0) {  // scores and bookkeeping come from mlstm_lazy_score_kernel
+  if constexpr (WV) {  // scores and bookkeeping come from mlstm_lazy_score_kernel
     // (the score kernel writes each row's first n + T entries only: the rest is an earlier step's, possibly another episode's
     // NaN, which the zero v rows beyond the window would turn into NaN * 0)
     const float* pwi = a.pw + (((int64_t)b * NH + h) * T) * WT;
@@ -498,32 +527,30 @@ __global__ __launch_bounds__(256) void mlstm_lazy_cell_kernel(MlstmLazyArgs a) {
   }
   // window V column of this thread (threads >= CW idle here): in flight during the pass over C_base
   const float* wvb = a.wv + (base * DH) + slice * CW + (tid < CW ? tid : 0);
-  float vw[W4 || WV ? 1 : WP];
-  if (!W4 && !WV) {
+  ModeRegs<float, W4 || WV ? 0 : WP> vw;
+  if constexpr (!W4 && !WV) {
 #pragma unroll
-    for (int j = 0; j < WP; ++j) vw[W4 || WV ? 0 : j] = (tid < CW && j < n) ? wvb[(int64_t)j * DH] : 0.f;
+    for (int j = 0; j < WP; ++j) vw[j] = (tid < CW && j < n) ? wvb[(int64_t)j * DH] : 0.f;
   }
-  v4f v4r[WV ? kVRows : 1];
-  (void)v4r;
-  if (WV) {
+  ModeRegs<v4f, WV ? kVRows : 0> v4r;
+  if constexpr (WV) {
     const float* wvs = a.wv + base * DH + slice * CW + 4 * cl;
 #pragma unroll
     for (int i = 0; i < kVRows; ++i) {
       const int j = rg + RP * i;
-      v4r[WV ? i : 0] = (j < n && j < WP) ? *reinterpret_cast<const v4f*>(wvs + (int64_t)j * DH) : (v4f)(0.f);
+      v4r[i] = (j < n && j < WP) ? *reinterpret_cast<const v4f*>(wvs + (int64_t)j * DH) : (v4f)(0.f);
     }
   }
   // window khat rows of this wave (rows wave, wave + 4, ...), KPL values per lane and row
   const float* wkb = a.wk + base * DH;
-  v4f k4[W4 ? kRowsPerWave : 1], v4w[W4 ? kRowsPerWave : 1];
-  (void)k4, (void)v4w;
-  if (W4) {
+  ModeRegs<v4f, W4 ? kRowsPerWave : 0> k4, v4w;
+  if constexpr (W4) {
     const float* wvr = a.wv + base * DH;
 #pragma unroll
     for (int i = 0; i < kRowsPerWave; ++i) {
       const int j = wave + 4 * i;
-      k4[W4 ? i : 0] = j < n ? *reinterpret_cast<const v4f*>(wkb + (int64_t)j * DH + 4 * lane) : (v4f)(0.f);
-      v4w[W4 ? i : 0] = (j < n && j < WP) ? *reinterpret_cast<const v4f*>(wvr + (int64_t)j * DH + 4 * lane) : (v4f)(0.f);
+      k4[i] = j < n ? *reinterpret_cast<const v4f*>(wkb + (int64_t)j * DH + 4 * lane) : (v4f)(0.f);
+      v4w[i] = (j < n && j < WP) ? *reinterpret_cast<const v4f*>(wvr + (int64_t)j * DH + 4 * lane) : (v4f)(0.f);
     }
   }
   // (this step's v operands last: their combination waits for everything requested above, the window rows included)
@@ -549,35 +576,25 @@ __global__ __launch_bounds__(256) void mlstm_lazy_cell_kernel(MlstmLazyArgs a) {
   __syncthreads();
 
   // ---- window scores p[t][j] = c_{t,j} (q_t . khat_j), j over the pending window and this step's own tokens ----
-  auto coefficient = [&](int j, int t) -> float {
-    if (j < n) return s_coef[j] * F[t];
-    const int u = j - n;  // this step's token u reaches t >= u with i_u f_{u+1} .. f_t
-    if (u > t) return 0.f;
-    float c = 1.f;
+  ModeRegs<v4f, W4 || WV ? T : 0> accw;  // W4 / WV: this wave's (row group's) rows of sum_j p[t][j] v_j at its four columns
+  if constexpr (W4 || WV) {
 #pragma unroll
-    for (int x = 0; x < T; ++x) {
-      if (x == u) c *= ig[x];
-      if (x > u && x <= t) c *= f[x];
-    }
-    return c;
-  };
-  v4f accw[W4 || WV ? T : 1];  // W4 / WV: this wave's (row group's) rows of sum_j p[t][j] v_j at its four columns
-#pragma unroll
-  for (int t = 0; t < (W4 || WV ? T : 1); ++t) accw[t] = (v4f)(0.f);
+    for (int t = 0; t < T; ++t) accw[t] = (v4f)(0.f);
+  }
   auto window_scores = [&]() {
-  if (KPL < 0) {
-  } else if (W4) {
+  if constexpr (W4) {
 #pragma unroll
     for (int i = 0; i < kRowsPerWave; ++i) {
       const int j = wave + 4 * i;
       if (j < n + T) {  // (uniform over the wave)
-        const v4f kv = j < n ? k4[W4 ? i : 0] : *reinterpret_cast<const v4f*>(ks + (j - n) * DH + 4 * lane);
+        const v4f kv = j < n ? k4[i] : *reinterpret_cast<const v4f*>(ks + (j - n) * DH + 4 * lane);
 #pragma unroll
         for (int t = 0; t < T; ++t) {
           const v4f q4 = *reinterpret_cast<const v4f*>(qs + t * DH + 4 * lane);
-          const float sc = coefficient(j, t) * wave_sum_bcast(q4.x * kv.x + q4.y * kv.y + q4.z * kv.z + q4.w * kv.w);
+          const float sc = window_coefficient<T>(j, t, n, s_coef, gates) *
+                           wave_sum_bcast(q4.x * kv.x + q4.y * kv.y + q4.z * kv.z + q4.w * kv.w);
           if (lane == 0) pw[t * WT + j] = sc;
-          if (j < n && j < WP) accw[W4 ? t : 0] += sc * v4w[W4 ? i : 0];
+          if (j < n && j < WP) accw[t] += sc * v4w[i];
         }
       }
     }
@@ -591,14 +608,10 @@ __global__ __launch_bounds__(256) void mlstm_lazy_cell_kernel(MlstmLazyArgs a) {
 #pragma unroll
           for (int t = 0; t < T; ++t) p[t] += qs[t * DH + r] * kv;
         }
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-          const float sm = wave_sum(p[t]);
-          if (lane == 0) pw[t * WT + j] = coefficient(j, t) * sm;
-        }
+        store_window_scores<T>(p, j, n, lane, s_coef, gates, pw);
       }
     }
-  } else {
+  } else if constexpr (!WV) {
     for (int j0 = 4 * wave; j0 < n + T; j0 += 16) {  // four rows per wave at a time (their loads are issued together)
       float p[4][T];
 #pragma unroll
@@ -618,14 +631,7 @@ __global__ __launch_bounds__(256) void mlstm_lazy_cell_kernel(MlstmLazyArgs a) {
           for (int t = 0; t < T; ++t) p[i][t] += qs[t * DH + r] * kv[i];
       }
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int j = j0 + i;
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-          const float sm = wave_sum(p[i][t]);
-          if (lane == 0 && j < n + T) pw[t * WT + j] = coefficient(j, t) * sm;
-        }
-      }
+      for (int i = 0; i < 4; ++i) store_window_scores<T>(p[i], j0 + i, n, lane, s_coef, gates, pw);
     }
   }
   };
@@ -643,10 +649,11 @@ __global__ __launch_bounds__(256) void mlstm_lazy_cell_kernel(MlstmLazyArgs a) {
   // 33,008 / 33,220 -> 33,553 / 33,377 env-steps/s (+1 %; profiles/r05_ab_206m_chain.txt).  An LDS cap cannot do this here --
   // it takes the LDS those workgroups need -- and more rows in flight instead of idle registers (20 / 24: 186 / 211 VGPRs) lose.
   constexpr int kRegPad = WV ? 12 : 0;
-  float rpad[kRegPad > 0 ? kRegPad : 1];
-  (void)rpad;
+  ModeRegs<float, kRegPad> rpad;
+  if constexpr (WV) {
 #pragma unroll
-  for (int i = 0; i < kRegPad; ++i) asm volatile("v_mov_b32 %0, 0" : "=v"(rpad[i]));
+    for (int i = 0; i < kRegPad; ++i) asm volatile("v_mov_b32 %0, 0" : "=v"(rpad[i]));
+  }
   if (stream) {
     for (int r0 = rg; r0 < DH; r0 += RP * UNR) {
       v4f c[UNR];
@@ -665,21 +672,27 @@ __global__ __launch_bounds__(256) void mlstm_lazy_cell_kernel(MlstmLazyArgs a) {
       }
     }
   }
+  if constexpr (WV) {
 #pragma unroll
-  for (int i = 0; i < kRegPad; ++i) asm volatile("" ::"v"(rpad[i]));   // (the pad registers' live range ends here)
-  if (WV) {  // (pw: the score kernel's rows, in LDS since the barrier above; zero v rows beyond the pending window)
+    for (int i = 0; i < kRegPad; ++i) asm volatile("" ::"v"(rpad[i]));   // (the pad registers' live range ends here)
+    // (pw: the score kernel's rows, in LDS since the barrier above; zero v rows beyond the pending window)
 #pragma unroll
     for (int i = 0; i < kVRows; ++i) {
       const int j = rg + RP * i;
       if (j < WP) {
 #pragma unroll
-        for (int t = 0; t < T; ++t) accw[W4 || WV ? t : 0] += pw[t * WT + j] * v4r[WV ? i : 0];
+        for (int t = 0; t < T; ++t) accw[t] += pw[t * WT + j] * v4r[i];
       }
     }
   }
 #pragma unroll
-  for (int t = 0; t < T; ++t)
-    *reinterpret_cast<v4f*>(red + ((rg * T + t) * CW) + 4 * cl) = (W4 || WV) ? G[t] * acc[t] + accw[W4 || WV ? t : 0] : acc[t];
+  for (int t = 0; t < T; ++t) {
+    v4f* out = reinterpret_cast<v4f*>(red + ((rg * T + t) * CW) + 4 * cl);
+    if constexpr (W4 || WV)
+      *out = G[t] * acc[t] + accw[t];
+    else
+      *out = acc[t];
+  }
 
   if (!SF) window_scores();
   __syncthreads();
@@ -697,11 +710,11 @@ __global__ __launch_bounds__(256) void mlstm_lazy_cell_kernel(MlstmLazyArgs a) {
       for (int g = 0; g < RP; ++g) y += red[(g * T + t) * CW + c];
       hn[t] = (W4 || WV) ? y : G[t] * y;  // (W4 / WV: the row groups' sums hold G y + the window rows' part already)
     }
-    if (!W4 && !WV) {
+    if constexpr (!W4 && !WV) {
 #pragma unroll
       for (int j = 0; j < WP; ++j) {
 #pragma unroll
-        for (int t = 0; t < T; ++t) hn[t] += pw[t * WT + j] * vw[W4 || WV ? 0 : j];  // vw == 0 beyond the window, pw zero-filled
+        for (int t = 0; t < T; ++t) hn[t] += pw[t * WT + j] * vw[j];  // vw == 0 beyond the window, pw zero-filled
       }
     }
     if (WP < W) {
@@ -716,7 +729,7 @@ __global__ __launch_bounds__(256) void mlstm_lazy_cell_kernel(MlstmLazyArgs a) {
 #pragma unroll
       for (int t = u; t < T; ++t) hn[t] += pw[t * WT + n + u] * vcur[u];
 #pragma unroll
-    for (int t = 0; t < T; ++t) hv[t] = hn[t] / den[t];
+    for (int t = 0; t < T; ++t) hv[t] = hn[t] / gates.den[t];
     if (!gn) {
 #pragma unroll
       for (int t = 0; t < T; ++t) a.h[((int64_t)b * T + t) * inner + (int64_t)h * DH + slice * CW + c] = hv[t];
@@ -762,22 +775,7 @@ __global__ __launch_bounds__(256) void mlstm_lazy_cell_kernel(MlstmLazyArgs a) {
   if (slice == 0) {
     float* wko = a.wk + (base + n) * DH;
     for (int idx = tid; idx < T * DH; idx += 256) wko[idx] = ks[idx];
-    if (KPL < 0) return;
-    // ---- bookkeeping for the next step ("out" side of the ping-pong) ----
-    if (tid < n) a.coef_out[base + tid] = s_coef[tid] * F[T - 1];
-    if (tid < T) {
-      float c = 1.f;
-#pragma unroll
-      for (int x = 0; x < T; ++x) {
-        if (x == tid) c *= ig[x];
-        if (x > tid) c *= f[x];
-      }
-      a.coef_out[base + n + tid] = c;
-    }
-    if (tid == 0) {
-      a.g_out[(int64_t)b * NH + h] = g0 * F[T - 1];
-      if (h == 0) a.count_out[b] = (n + T) | (lv.zero ? kZeroBit : 0);
-    }
+    if constexpr (!WV) write_window_book<T>(a, b, h, tid, n, lv, g0, s_coef, gates);  // (WV: the score kernel's)
   }
 }
 
@@ -819,7 +817,7 @@ __global__ __launch_bounds__(256) void mlstm_lazy_parked_kernel(MlstmLazyArgs a)
   const LazyView lv = lazy_view(a, b);
   if (lane < W) a.coef_out[pair * W + lane] = a.coef_in[pair * W + lane];
   if (lane == 0) {
-    a.g_out[pair] = lv.fold ? 1.f : a.g_in[pair];
+    a.g_out[pair] = lazy_g0(lv, a.g_in[pair]);   // (a.reset is null: no restart)
     if (h == 0) a.count_out[b] = lv.fold ? 0 : a.count_in[b];
   }
 }
@@ -874,7 +872,7 @@ void launch_mlstm_lazy_fold(const MlstmLazyArgs& a_in, hipStream_t stream) {
   LRAM_REQUIRE(a.DH % kFC == 0 && a.DH % kFR == 0, "lazy mLSTM: head dim must be a multiple of 128");
   long envs = a.B;
   if (a.compact) {
-    a.first = (a.period - a.phase % a.period) % a.period;  // smallest b with (phase + b) % period == 0
+    a.first = lazy_due_class(a.phase, a.period);
     if (a.first >= a.B) return;
     envs = (a.B - a.first + a.period - 1) / a.period;
   }
@@ -893,23 +891,13 @@ void launch_mlstm_lazy_book(const MlstmLazyArgs& a, hipStream_t stream) {
   LRAM_REQUIRE(a.pw != nullptr, "lazy mLSTM: missing score buffer");
   dim3 grid(a.NH, a.B), block(256);
   const size_t shmem = sizeof(float) * 2 * a.T * a.DH;
-  switch (a.T) {
-    case 1: hipLaunchKernelGGL(mlstm_lazy_score_kernel<1>, grid, block, shmem, stream, a); break;
-    case 2: hipLaunchKernelGGL(mlstm_lazy_score_kernel<2>, grid, block, shmem, stream, a); break;
-    case 3: hipLaunchKernelGGL(mlstm_lazy_score_kernel<3>, grid, block, shmem, stream, a); break;
-    default: hipLaunchKernelGGL(mlstm_lazy_score_kernel<4>, grid, block, shmem, stream, a); break;
-  }
+  with_tokens(a.T, [&](auto t) { hipLaunchKernelGGL(mlstm_lazy_score_kernel<decltype(t)::value>, grid, block, shmem, stream, a); });
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
 void launch_mlstm_lazy_cell(const MlstmLazyArgs& a, hipStream_t stream) {
   LRAM_REQUIRE(mlstm_lazy_supported(a.DH, a.T), "lazy mLSTM: unsupported geometry");
-  switch (a.T) {
-    case 1: launch_cell_t<1>(a, stream); break;
-    case 2: launch_cell_t<2>(a, stream); break;
-    case 3: launch_cell_t<3>(a, stream); break;
-    default: launch_cell_t<4>(a, stream); break;
-  }
+  with_tokens(a.T, [&](auto t) { launch_cell_t<decltype(t)::value>(a, stream); });
   LRAM_HIP_CHECK(hipGetLastError());
 }
 

@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """Byte identity of two builds of the library on the recurrent paths: for refactors of the xLSTM kernels that must not move a bit.
 
-A fixed list of small cases (CASES: one per kernel path of xlstm_kernels.hip, mlstm_chunk.hip, mlstm_front.hip and slstm_seq.hip --
-every mlstm_pre_kernel head count, lean and not, the multi-env front end, the token-sequential and the chunkwise prefill in both cell
-forms, the four forms of the sLSTM recurrence) runs once on the PARENT commit's library (csrc/_variants/<--parent>.so,
+A fixed list of small cases (CASES: one per kernel path of xlstm_kernels.hip, mlstm_chunk.hip, mlstm_front.hip, slstm_seq.hip and
+mlstm_lazy.hip -- every mlstm_pre_kernel head count, lean and not, the multi-env front end, the token-sequential and the chunkwise
+prefill in both cell forms, the four forms of the sLSTM recurrence; the lazy matrix memory's read pass in its three score forms (head
+dim 256, head dim 128, scores from the score kernel at head dims 384 / 512 / 640 / 1024), windows of more than 36 pending rows (fold
+period 14), period 1, encoder calls of 1 / 2 / 4 tokens up to a window overflow, the group norm in the read pass, parked slots with
+the tail fold, an export in the middle of a window) runs once on the PARENT commit's library (csrc/_variants/<--parent>.so,
 LRAM_LIB_VARIANT: build the parent commit and copy its liblram_hip.so there) and once on this tree's.  Every case is a fresh child
 process under its own time limit; the first child that does not exit cleanly ends the run.  A child prints one sha256 over the
 actions and tokens of every step (the hidden rows of an encoder call) and one per exported state tensor of block 0, of the last
@@ -26,7 +29,9 @@ sys.path.insert(0, ROOT)
 
 FRONT = {"LRAM_FRONT_MULTI": "1", "LRAM_FRONT_MIN_ENVS": "1", "LRAM_FRONT_EPW": "3"}
 GEMM, STEP = {"LRAM_SLSTM_SEQ": "0", "LRAM_SLSTM_FUSED_ROWS": "0"}, {"LRAM_SLSTM_FUSED_ROWS": "0"}
-# name: (geometry, env slots, run, state mode, environment); run = ("steps", n) | ("encoder", tokens) | ("prefill", L, L, ...)
+# name: (geometry, env slots, run, state mode, environment[, lazy options]); run = ("steps", n) | ("encoder", tokens per call, ...) |
+# ("prefill", L, L, ...); lazy options: period = fold period, micro = env slices, live = live slots during the middle third of the
+# steps (the others are parked), export_at = step before which block 0's C is exported (digest "mid.C")
 CASES = {
     # mlstm_pre_kernel<3, NH>: every head count, eager (q / k / v rows written) and lazy (lean: phase 3 rebuilds q and k from xa --
     # the branch runs where the read pass fuses the scores, head dim 128 / 256, so never in the 4-head kernel beyond one channel
@@ -61,6 +66,29 @@ CASES = {
     "slstm_seq32_b37": ("preset:xlstm_16m", 37, ("steps", 4), None, {**STEP, "LRAM_SLSTM_SEQ": "2"}),
     "slstm_seq32_b7": ("preset:xlstm_16m", 7, ("steps", 4), None, {**STEP, "LRAM_SLSTM_SEQ": "2"}),
     "slstm_seq32_dh320": ("preset:xlstm_206m", 37, ("steps", 3), None, {**STEP, "LRAM_SLSTM_SEQ": "2"}),   # (the instances that spill)
+    # mlstm_lazy.hip: fold, score and read-pass kernels.  Scores from the score kernel: LPR = 64 (head dim 512), staging and dot loops
+    # beyond 768 columns (1024), LPR = 32 (384); fused scores at 256-wide heads with 8 heads
+    "lazy_dh512": ("geo:nh2_dh512", 7, ("steps", 8), "lazy", {}),
+    "lazy_dh1024": ("geo:nh1_dh1024", 7, ("steps", 8), "lazy", {}),
+    "lazy_dh384": ("preset:xlstm_48m", 7, ("steps", 6), "lazy", {}),
+    "lazy_nh8_dh256": ("geo:nh8_dh256", 19, ("steps", 8), "lazy", {}),
+    # fold period 14 (the longest lram_set_state_mode accepts): 39 rows pending at the last read pass before an env's fold -- the
+    # late-row paths beyond the 36-row prefetch
+    "lazy_p14_dh256": ("preset:xlstm_16m", 7, ("steps", 22), "lazy", {}, {"period": 14}),
+    "lazy_p14_dh512": ("geo:nh2_dh512", 7, ("steps", 22), "lazy", {}, {"period": 14}),
+    "lazy_p14_dh128": ("geo:nh2_dh128", 7, ("steps", 22), "lazy", {}, {"period": 14}),
+    "lazy_p1_dh128": ("geo:nh2_dh128", 7, ("steps", 8), "lazy", {}, {"period": 1}),
+    # encoder calls in lazy mode: T = 1, 2, 4 instances; twelve 4-token calls fill the window to 44 / 48 rows and overflow it ahead of
+    # the fold phase (full grid)
+    "lazy_enc_t124": ("preset:xlstm_16m", 7, ("encoder", 1, 2, 4, 2, 1, 4), "lazy", {}),
+    "lazy_enc_t124_dh512": ("geo:nh2_dh512", 7, ("encoder", 1, 2, 4, 2, 1, 4), "lazy", {}),
+    "lazy_enc_overflow": ("preset:xlstm_16m", 7, ("encoder",) + (4,) * 14, "lazy", {}, {"period": 14}),
+    "lazy_enc_overflow_dh512": ("geo:nh2_dh512", 7, ("encoder",) + (4,) * 14, "lazy", {}, {"period": 14}),
+    "lazy_gn_fuse": ("preset:xlstm_16m", 19, ("steps", 8), "lazy", {"LRAM_GN_FUSE": "1"}),
+    # parked slots (mlstm_lazy_parked_kernel, the parked fold) under two env slices (the tail fold), period 3; an export mid-window
+    "lazy_parked": ("preset:xlstm_16m", 19, ("steps", 18), "lazy", {}, {"period": 3, "micro": 2, "live": 11}),
+    "lazy_parked_dh512": ("geo:nh2_dh512", 19, ("steps", 18), "lazy", {}, {"period": 3, "micro": 2, "live": 11}),
+    "lazy_export_mid": ("preset:xlstm_16m", 7, ("steps", 10), "lazy", {}, {"export_at": 5}),
 }
 RESTART_SLOT = 2
 
@@ -81,12 +109,15 @@ def child(name):
     import torch
     from lram_amd import engine, init_state_dict
     from tests.helpers import make_inputs
-    geometry, B, run, mode, _ = CASES[name]
+    geometry, B, run, mode, _, *opt = CASES[name]
+    opt = opt[0] if opt else {}
     spec = case_spec(geometry)
     dev = torch.device("cuda", 0)
     eng = engine.Engine(spec, init_state_dict(spec, seed=5), B, device=dev)
     if mode is not None:
-        eng.set_state_mode(mode)
+        eng.set_state_mode(mode, opt.get("period", 0))
+    if "micro" in opt:
+        eng.set_micro_batches(opt["micro"])
     h, digests = hashlib.sha256(), {}
 
     def take(t):
@@ -94,16 +125,22 @@ def child(name):
 
     if run[0] == "encoder":
         g = torch.Generator().manual_seed(3)
-        for call in range(2):   # the second call reads the state the first one left; slot RESTART_SLOT restarts in it
+        calls = run[1:] if len(run) > 2 else run[1:] * 2
+        for call, T in enumerate(calls):   # each call reads the state the one before left; slot RESTART_SLOT restarts in the middle one
             mask = torch.zeros(B, dtype=torch.uint8)
-            mask[RESTART_SLOT] = call
-            take(eng.encoder_step(torch.randn(B, run[1], spec.d_model, generator=g).to(dev), mask.to(dev)))
+            mask[RESTART_SLOT] = call == len(calls) // 2
+            take(eng.encoder_step(torch.randn(B, T, spec.d_model, generator=g).to(dev), mask.to(dev)))
     else:
         seq = make_inputs(spec, B, sum(run[1:]), seed=41, reset_prob=0.0)   # (every slot starts at timestep 0)
         seq[len(seq) // 2 if run[0] == "steps" else sum(run[1:-1])][3][RESTART_SLOT] = 1   # prefill: at the last context's start
         if run[0] == "steps":
-            for obs, rtg, rew, mask in seq:
-                a, tok = eng.step(obs.to(dev), rtg.to(dev), rew.to(dev), mask.to(dev))
+            for t, (obs, rtg, rew, mask) in enumerate(seq):
+                if "live" in opt and t in (len(seq) // 3, 2 * len(seq) // 3):   # parked during the middle third of the steps
+                    eng.set_live(opt["live"] if t == len(seq) // 3 else B)
+                if t == opt.get("export_at"):   # (in the middle of a window: the export folds)
+                    digests["mid.C"] = hashlib.sha256(eng.export_state_tensor(0, 0).cpu().contiguous().numpy().tobytes()).hexdigest()
+                n = eng.live
+                a, tok = eng.step(obs[:n].to(dev), rtg[:n].to(dev), rew[:n].to(dev), mask[:n].to(dev))
                 take(a), take(tok)
         else:
             t0 = 0
@@ -144,8 +181,8 @@ def main():
         lines.append(line)
 
     for lib in (args.parent, None):
-        for name, (_, _, _, _, env) in CASES.items():
-            env = {**os.environ, **env}
+        for name, case in CASES.items():
+            env = {**os.environ, **case[4]}
             env.pop("LRAM_LIB_VARIANT", None)
             if lib:
                 env["LRAM_LIB_VARIANT"] = lib
@@ -161,7 +198,8 @@ def main():
             results[(lib or "tree", name)] = json.loads(out.strip().splitlines()[-1])
             print(f"[{lib or 'tree'}] {name}: done", file=sys.stderr, flush=True)
     differ = []
-    for name, (geometry, B, run, mode, env) in CASES.items():
+    for name, (geometry, B, run, mode, env, *opt) in CASES.items():
+        env = {**env, **(opt[0] if opt else {})}
         a, b = results[(args.parent, name)], results[("tree", name)]
         bad = sorted(k for k in a["digests"] if a["digests"][k] != b["digests"].get(k))
         differ += [f"{name}:{k}" for k in bad]

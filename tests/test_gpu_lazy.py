@@ -8,6 +8,7 @@ import torch
 from lram_amd import init_state_dict, preset
 from lram_amd.config import ModelSpec
 from oracle import dt_ref
+from tests.geometry_cases import case_spec
 from tests.helpers import assert_actions_match, make_inputs, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -119,6 +120,47 @@ def test_lazy_env_slices_and_206m_geometry(hip_lib, monkeypatch):
     for t, (obs, rtg, rew, mask) in enumerate(seq):
         ref, dbg = ora.step(obs, rtg, rew, mask, return_debug=True)
         assert_actions_match(outs[0][0][t], ref, dbg["logits"], spec, what=f"206M geometry step {t}")
+
+
+# Seeds of test_lazy_long_window_on_sliced_heads (weights: seed; inputs: 1234 + seed), chosen on the CPU as geometry_cases.STEP_SEEDS
+# are: over the whole trajectory (5 envs, 40 steps, reset probability 0.1) the ORACLE's own smallest top-2 logit gap is at least
+# 1e-3, five times the tie rule of helpers.assert_actions_match.  Value: (spec, seed, measured smallest gap).
+LONG_WINDOW_CASES = {
+    "nh2_dh512": (lambda: case_spec("nh2_dh512"), 7, 1.1e-03),
+    # (the 206M head geometry, 4 heads x 640, with the sweep's state_dim 20 / act_dim 4: 800 logit rows, as nh2_dh512 has)
+    "dh640": (lambda: ModelSpec(backbone="xlstm", d_model=1280, n_blocks=2, slstm_at=[1], state_dim=20, act_dim=4), 27, 2.0e-03),
+}
+
+
+@pytest.mark.parametrize("cid", list(LONG_WINDOW_CASES))
+def test_lazy_long_window_on_sliced_heads(hip_lib, cid):
+    """More than 36 pending rows in front of a sliced-head read pass (scores from mlstm_lazy_score_kernel, v rows beyond the 36-row
+    register prefetch loaded late): fold period 14 -- the longest lram_set_state_mode accepts, period * 3 + 4 <= 48; 39 rows are
+    pending at an env's last read pass before its fold -- over 40 steps with random restarts, at head dims 512 (LPR 64) and 640
+    (LPR 32).  Actions follow the oracle without a tie, lazy equals eager at the bars of test_lazy_steps_match_oracle_and_eager."""
+    from lram_amd.engine import Engine
+    make_spec, seed, gap = LONG_WINDOW_CASES[cid]
+    assert gap >= 1e-3
+    spec = make_spec()
+    sd = init_state_dict(spec, seed=seed)
+    B, steps = 5, 40
+    seq = make_inputs(spec, B, steps, seed=1234 + seed, reset_prob=0.1)
+    eager = Engine(spec, sd, B, device="cuda:0")
+    eager.set_state_mode("eager")
+    lazy = Engine(spec, sd, B, device="cuda:0")
+    lazy.set_state_mode(True, 14)
+    assert eager.state_mode == "materialised" and lazy.state_mode == "lazy"
+    a_e, a_l = _run(eager, seq), _run(lazy, seq)
+    ora = dt_ref.OraclePolicy(spec, sd)
+    ties = 0
+    for t, (obs, rtg, rew, mask) in enumerate(seq):
+        ref, dbg = ora.step(obs, rtg, rew, mask, return_debug=True)
+        ties += assert_actions_match(a_l[t], ref, dbg["logits"], spec, what=f"{cid} period 14 step {t}")
+    assert ties == 0
+    assert float((a_e - a_l).abs().max()) <= 1e-4
+    for which in (0, 1, 2, 3):
+        assert rel_err(lazy.export_state_tensor(0, which), eager.export_state_tensor(0, which)) < 2e-4, which
+    eager.close(), lazy.close()
 
 
 def test_lazy_mode_is_refused_or_ignored_where_it_does_not_apply(hip_lib):
