@@ -131,32 +131,7 @@ int gemm_choose_split_k(GemmArgs& g);                             // fills split
 // workgroups b, b + 8, ... share an L2.  Every XCD streams its M band of A once and wants its N band of W resident in
 // its 4 MB L2: the split (gm, gn) minimises M * gn + N * gm over the splits whose W band fits and that divide the tile grid.
 void gemm_choose_xcd_split(GemmArgs& g, int bm, int bn, int bytes_per_elem);
-// the tile a workgroup id maps to under that split (device side)
-__device__ __forceinline__ void gemm_tile_of(const GemmArgs& g, int bid, int tiles_m, int tiles_n, int& tm, int& tn) {
-  const int nwg = tiles_m * tiles_n;
-  if (g.panel_w > 0) {
-    const int x = bid & 7, q = nwg >> 3, r = nwg & 7;
-    const int pos = x * q + min(x, r) + (bid >> 3);           // XCD x owns walk positions [x q + min(x, r), ...)
-    const int per_panel = tiles_m * g.panel_w;
-    const int p = pos / per_panel, rem = pos - p * per_panel;
-    const int w = min(g.panel_w, tiles_n - p * g.panel_w);
-    const int row = rem / w;
-    tm = (p & 1) ? tiles_m - 1 - row : row;
-    tn = p * g.panel_w + rem - row * w;
-    return;
-  }
-  if (g.xcd_gm > 0) {
-    const int x = bid & 7, idx = bid >> 3;                    // XCD, position in that XCD's stream of workgroups
-    const int bm_t = tiles_m / g.xcd_gm, bn_t = tiles_n / g.xcd_gn;   // tiles per band
-    const int xm = x / g.xcd_gn, xn = x - xm * g.xcd_gn;
-    tm = xm * bm_t + idx / bn_t;                              // M outer, N inner: the band's N tiles of one M tile run together
-    tn = xn * bn_t + idx % bn_t;
-    return;
-  }
-  if ((nwg & 7) == 0) bid = (bid & 7) * (nwg >> 3) + (bid >> 3);
-  tm = bid / tiles_n;
-  tn = bid - tm * tiles_n;
-}
+// (the tile a workgroup id maps to under that split, device side: gemm_tile_of in gemm_tile.h)
 // The GEMM kernels are templated on <HAS_BIAS, HAS_RES>: calls f(has_bias, has_res) with the launch's two as
 // std::integral_constant<bool, ...> (a generic lambda names its instance with decltype(has_bias)::value).
 template <typename F>

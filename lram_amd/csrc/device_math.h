@@ -82,32 +82,43 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // row of the 32x32 MFMA accumulator held in register r by a lane of half lh
 __device__ __forceinline__ int acc_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
 
-// Exact 3-way bf16 split of an fp32 value, x = hi + mid + lo (the operand format of gemm_bf16x3.hip): producers that
-// feed a projection write these three planes instead of (or next to) the fp32 value, so the GEMM stages its A operand
-// with plain 16-byte copies.  p points at the element in plane 0; the planes are `plane` elements apart.
-__device__ __forceinline__ void split3_store(float x, uint16_t* p, int64_t plane) {
-  const __bf16 hi = (__bf16)x;
-  const float r1 = x - (float)hi;
-  const __bf16 mid = (__bf16)r1;
-  const __bf16 lo = (__bf16)(r1 - (float)mid);
-  p[0] = __builtin_bit_cast(uint16_t, hi);
-  p[plane] = __builtin_bit_cast(uint16_t, mid);
-  p[2 * plane] = __builtin_bit_cast(uint16_t, lo);
+// Hardware hands consecutive workgroup ids to the 8 XCDs in turn (ids b, b + 8, ... share an L2): the position this id takes
+// when every XCD is to own a contiguous run of a launch's nwg work items instead (grids that 8 divides; else the id itself).
+__device__ __forceinline__ int xcd_contiguous_id(int bid, int nwg) {
+  return (nwg & 7) == 0 ? (bid & 7) * (nwg >> 3) + (bid >> 3) : bid;
 }
-__device__ __forceinline__ void split3_store4(const float4& v, uint16_t* p, int64_t plane) {
-  const float xs[4] = {v.x, v.y, v.z, v.w};
-  uint16_t h[4], m[4], l[4];
+
+// ---- bf16x3: fp32-accurate products on the bf16 matrix cores (gemm_bf16x3.hip, the chunkwise cell of mlstm_chunk.hip) ----
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+// Exact 3-way bf16 split of an fp32 value, x = hi + mid + lo (8 + 8 + 8 significand bits; the residuals x - hi and
+// x - hi - mid are exact in fp32).
+__device__ __forceinline__ void split3(float x, __bf16& hi, __bf16& mid, __bf16& lo) {
+  hi = (__bf16)x;
+  const float r1 = x - (float)hi;
+  mid = (__bf16)r1;
+  lo = (__bf16)(r1 - (float)mid);
+}
+// ... of N values into three vectors V = bf16xN (a vector element does not bind to a reference)
+template <typename V, int N>
+__device__ __forceinline__ void split3v(const float (&x)[N], V& hi, V& mid, V& lo) {
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const __bf16 hi = (__bf16)xs[e];
-    const float r1 = xs[e] - (float)hi;
-    const __bf16 mid = (__bf16)r1;
-    const __bf16 lo = (__bf16)(r1 - (float)mid);
-    h[e] = __builtin_bit_cast(uint16_t, hi), m[e] = __builtin_bit_cast(uint16_t, mid), l[e] = __builtin_bit_cast(uint16_t, lo);
+  for (int e = 0; e < N; ++e) {
+    __bf16 h, m, l;
+    split3(x[e], h, m, l);
+    hi[e] = h, mid[e] = m, lo[e] = l;
   }
-  *reinterpret_cast<uint2*>(p) = make_uint2(h[0] | ((uint32_t)h[1] << 16), h[2] | ((uint32_t)h[3] << 16));
-  *reinterpret_cast<uint2*>(p + plane) = make_uint2(m[0] | ((uint32_t)m[1] << 16), m[2] | ((uint32_t)m[3] << 16));
-  *reinterpret_cast<uint2*>(p + 2 * plane) = make_uint2(l[0] | ((uint32_t)l[1] << 16), l[2] | ((uint32_t)l[3] << 16));
+}
+// acc += a * b over one 16-deep step, a = a[0] + a[1] + a[2] (hi, mid, lo), b likewise: the six largest piece products --
+// lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi, smallest terms first; the dropped mid*lo, lo*mid, lo*lo are <= 2^-24
+// relative.  The order is part of the result: every caller sums in it.
+__device__ __forceinline__ void bf16x3_products(f32x16& acc, const bf16x8 (&a)[3], const bf16x8 (&b)[3]) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
 }
 
 // ---- row maxima for the f16x2 GEMM (gemm_f16x2.hip) ----

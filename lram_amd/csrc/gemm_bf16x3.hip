@@ -14,28 +14,16 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
-#include "device_math.h"
+#include "gemm_tile.h"
 
 namespace lram {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 constexpr int BN = 128, BK = 32;
 constexpr int PITCH = 40;                 // bf16 elements per LDS row (80 B: conflict-free ds_read_b128)
 constexpr int PLANE = BN * PITCH;         // elements per 128-row plane (W; A when BM = 128)
 
-__device__ __forceinline__ void split3(float x, __bf16& hi, __bf16& mid, __bf16& lo) {
-  hi = (__bf16)x;
-  const float r1 = x - (float)hi;
-  mid = (__bf16)r1;
-  const float r2 = r1 - (float)mid;
-  lo = (__bf16)r2;
-}
-
+// (the split and the six products in their order: device_math.h; batch operands, tile order, K range, epilogue: gemm_tile.h)
 // (A pre-split A operand -- three bf16 planes written by its producer -- was built in round 2, measured 1-2 % slower end to end
 // than the split on the fly and removed in round 5: profiles/EXPERIMENTS.md.)
 // BM = 128: 64 x 64 per wave (2 x 2 MFMA tiles).  BM = 64: 32 x 64 per wave -- twice the workgroups for outputs with few
@@ -56,24 +44,12 @@ __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(GemmArgs g) {
   const int wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
 
-  const int z = blockIdx.y;
-  const int z1 = z / g.nb2, z2 = z - z1 * g.nb2;
-  // (operand tables: the outer batch index picks unrelated base pointers -- the four sLSTM gate projections as ONE launch)
-  const bool tab = g.w3_tab[0] != nullptr;
-  const float* A = tab ? g.a_tab[z2] + z1 * g.sA1 : g.a + z1 * g.sA1 + z2 * g.sA2;
-  const __bf16* W3 = tab ? reinterpret_cast<const __bf16*>(g.w3_tab[z2]) + z1 * g.sW1
-                         : reinterpret_cast<const __bf16*>(g.w3) + z1 * g.sW1 + z2 * g.sW2;
-  float* C = tab ? g.c_tab[z2] + z1 * g.sC1 : g.c + z1 * g.sC1 + z2 * g.sC2;
-  const float* R = HAS_RES ? g.residual + z1 * g.sC1 + z2 * g.sC2 : nullptr;
-  const float* bias = HAS_BIAS ? g.bias + z1 * g.sBias1 + z2 * g.sBias2 : nullptr;
-
+  // (operand tables: the four sLSTM gate projections as ONE launch)
+  LRAM_GEMM_BATCH_OPERANDS_TAB(blockIdx.y, HAS_BIAS, HAS_RES, __bf16, W3, reinterpret_cast<const __bf16*>(g.w3),
+                               g.w3_tab[0] != nullptr, g.w3_tab)
   const int tiles_n = (g.n + BN - 1) / BN;
-  const int tiles_m = (g.m + BM - 1) / BM;
-  const int nwg = tiles_n * tiles_m;
-  int bid = blockIdx.x;
-  if ((nwg & 7) == 0) bid = (bid & 7) * (nwg >> 3) + (bid >> 3);  // XCD-aware tile order (see gemm_f32.hip)
-  const int tm_idx = bid / tiles_n;
-  const int tn_idx = bid - tm_idx * tiles_n;
+  int tm_idx, tn_idx;
+  gemm_tile_1d(blockIdx.x, tiles_n * ((g.m + BM - 1) / BM), tiles_n, tm_idx, tn_idx);
   const int m0 = tm_idx * BM, n0 = tn_idx * BN;
 
   // staging registers: A 4 x float4 (fp32), W 6 x 16 B (bf16 planes)
@@ -113,14 +89,7 @@ __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(GemmArgs g) {
       bf16x4 hi, mid, lo;
       float xs[4] = {ra[i].x, ra[i].y, ra[i].z, ra[i].w};
       if (GATE) xs[0] *= rz[i].x, xs[1] *= rz[i].y, xs[2] *= rz[i].z, xs[3] *= rz[i].w;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        __bf16 h, m, l;
-        split3(xs[e], h, m, l);
-        hi[e] = h;
-        mid[e] = m;
-        lo[e] = l;
-      }
+      split3v(xs, hi, mid, lo);
       __bf16* dst = As + (lr + 32 * i) * PITCH + lc;
       *reinterpret_cast<bf16x4*>(dst) = hi;
       *reinterpret_cast<bf16x4*>(dst + APLANE) = mid;
@@ -149,9 +118,8 @@ __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(GemmArgs g) {
   const __bf16* a_base = As + (WM * wm + li) * PITCH + 8 * lh;
   const __bf16* b_base = Bs + (64 * wn + li) * PITCH + 8 * lh;
 
-  const int nk_all = (g.k + BK - 1) / BK;
-  const int kt0 = g.split_k > 1 ? blockIdx.z * g.k_tiles_per_split : 0;
-  const int nk = g.split_k > 1 ? min(nk_all, kt0 + g.k_tiles_per_split) : nk_all;
+  int kt0, nk;
+  gemm_k_range(g, (g.k + BK - 1) / BK, kt0, nk);
   load_tile(kt0 * BK);
   for (int kt = kt0; kt < nk; ++kt) {
     store_tile();
@@ -171,55 +139,13 @@ __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(GemmArgs g) {
 #pragma unroll
       for (int i = 0; i < TI; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          // smallest terms first
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][2], bf[j][0], acc[i][j], 0, 0, 0);  // lo * hi
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][2], acc[i][j], 0, 0, 0);  // hi * lo
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][1], acc[i][j], 0, 0, 0);  // mid * mid
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][0], acc[i][j], 0, 0, 0);  // mid * hi
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][1], acc[i][j], 0, 0, 0);  // hi * mid
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][0], acc[i][j], 0, 0, 0);  // hi * hi
-        }
+        for (int j = 0; j < 2; ++j) bf16x3_products(acc[i][j], af[i], bf[j]);
     }
     if (g.mfma_prio) __builtin_amdgcn_s_setprio(0);
     __syncthreads();
   }
 
-  // epilogue (C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5))
-  if (g.split_k > 1) {  // raw partial sums into this split's slab [M][N]; bias / residual are applied by the reduce
-    float* S = g.splitk_ws + (int64_t)blockIdx.z * g.m * g.n;
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int col = n0 + 64 * wn + 32 * j + li;
-        if (col >= g.n) continue;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = m0 + WM * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (row < g.m) S[(int64_t)row * g.n + col] = acc[i][j][r];
-        }
-      }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = n0 + 64 * wn + 32 * j + li;
-      if (col >= g.n) continue;
-      const float bv = HAS_BIAS ? bias[col] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + WM * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (row < g.m) {
-          float v = acc[i][j][r] + bv;
-          if (HAS_RES) v += R[(int64_t)row * g.ldc + col];
-          if (g.act_silu_from >= 0 && col >= g.act_silu_from) v = silu_hw(v);
-          C[(int64_t)row * g.ldc + col] = v;
-        }
-      }
-    }
+  LRAM_GEMM_STORE_ACC_TILES(TI, WM, true)   // split-K: the slab, and out; else C with bias, residual, SiLU columns
 }
 
 // out[p][i] = piece p of w[i]  (three consecutive planes of n bf16 each)

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256, DB ? 2 : 3) void gemm_f16x2_kernel(GemmArgs g)
   const int tiles_n = (g.n + BN - 1) / BN;
   const int tiles_m = (g.m + BM - 1) / BM;
   int tm_idx, tn_idx;
-  gemm_tile_of(g, blockIdx.x, tiles_m, tiles_n, tm_idx, tn_idx);  // XCD-aware tile order (common.h)
+  gemm_tile_of(g, blockIdx.x, tiles_m, tiles_n, tm_idx, tn_idx);  // XCD-aware tile order (gemm_tile.h)
   const int m0 = tm_idx * BM, n0 = tn_idx * BN;
 
   // row scales from the producers' row maxima: a row's maximum may arrive in `amax_parts` partial maxima (one per wave
@@ -207,9 +207,8 @@ __global__ __launch_bounds__(256, DB ? 2 : 3) void gemm_f16x2_kernel(GemmArgs g)
   const _Float16* b_base = Bs + (64 * wn + li) * PITCH + (DB ? 0 : 8 * lh);
   const int sw = f16x2_chunk_swizzle(li);  // DB: chunk swizzle of this lane's rows (row offsets of the tiles are multiples of 32)
 
-  const int nk_all = (g.k + BK - 1) / BK;
-  const int kt0 = g.split_k > 1 ? blockIdx.z * g.k_tiles_per_split : 0;
-  const int nk = g.split_k > 1 ? min(nk_all, kt0 + g.k_tiles_per_split) : nk_all;
+  int kt0, nk;
+  gemm_k_range(g, (g.k + BK - 1) / BK, kt0, nk);
   // fragment reads + products of 16-deep step ks of the tile in LDS stage `buf`
   auto frag_mfma = [&](int buf, int ks) {
     const int ko = DB ? f16x2_frag_offset(ks, lh, sw) : 16 * ks;

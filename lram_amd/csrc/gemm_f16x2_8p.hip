@@ -127,9 +127,8 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_8p_kernel(GemmArgs g) {
   const int a_row = (wr * 64 + li) * BK;   // + i * 32 * BK
   const int b_row = (wc * 32 + li) * BK;
 
-  const int nk_all = g.k / BK;
-  const int kt0 = g.split_k > 1 ? blockIdx.z * g.k_tiles_per_split : 0;
-  const int nk = g.split_k > 1 ? min(nk_all, kt0 + g.k_tiles_per_split) : nk_all;
+  int kt0, nk;
+  gemm_k_range(g, g.k / BK, kt0, nk);
 
   f16x8 af[2][2][2];     // [row tile i][ks][plane]
   f16x8 bf0[2][2], bf1[2][2];   // [ks][plane]

@@ -2,12 +2,10 @@
 // gemm_f16x2_8p.hip: 256 x 256 tiles, 8 phases): the product triple, the LDS chunk swizzle and the two epilogue forms.  The
 // kernels are bit-identical by contract (tests/test_gpu_parity.py) -- the arithmetic lives here once, the schedules stay theirs.
 #pragma once
-#include "common.h"
-#include "device_math.h"
+#include "gemm_tile.h"   // what they share with the other GEMM kernels: gemm_tile_of, gemm_k_range
 
 namespace lram {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(64 * WM * WN, NSTAGE == 1 ? 4 : 2) void gemm_f16x2p
   const int tiles_n = (g.n + BN - 1) / BN;
   const int tiles_m = (g.m + BMT - 1) / BMT;
   int tm_idx, tn_idx;
-  gemm_tile_of(g, blockIdx.x, tiles_m, tiles_n, tm_idx, tn_idx);  // XCD-aware tile order (common.h)
+  gemm_tile_of(g, blockIdx.x, tiles_m, tiles_n, tm_idx, tn_idx);  // XCD-aware tile order (gemm_tile.h)
   const int m0 = tm_idx * BMT, n0 = tn_idx * BN;
   // the tile's inverse row / column scales, requested before the first K tile and in LDS from its barrier on: the epilogue
   // used to request them only after the last MFMA -- a memory round trip at the end of every workgroup, and on grids of at
@@ -160,9 +160,8 @@ __global__ __launch_bounds__(64 * WM * WN, NSTAGE == 1 ? 4 : 2) void gemm_f16x2p
   const _Float16* a_base = lds + (32 * TI * wm + li) * BK;
   const _Float16* b_base = lds + 2 * APL + (64 * wn + li) * BK;
 
-  const int nk_all = g.k / BK;
-  const int kt0 = g.split_k > 1 ? blockIdx.z * g.k_tiles_per_split : 0;
-  const int nk = g.split_k > 1 ? min(nk_all, kt0 + g.k_tiles_per_split) : nk_all;
+  int kt0, nk;
+  gemm_k_range(g, g.k / BK, kt0, nk);
 
   auto mfma_tile = [&](int stage) {
     if (g.mfma_prio) __builtin_amdgcn_s_setprio(1);

@@ -9,14 +9,14 @@
 // 32x32 accumulators (64 VGPR).  Both operands are K-contiguous, staged global -> registers -> LDS
 // (row pitch 36 floats: ds_read_b128 of 16 consecutive rows hits 16 distinct 4-bank slots), next
 // K-tile's global loads are issued before the MFMAs of the current one.
+// (This file also hosts the launch policy every projection launcher shares: gemm_knobs, gemm_choose_split_k,
+// gemm_choose_xcd_split and the split-K reduce.)
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
+#include "gemm_tile.h"
 
 namespace lram {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 constexpr int BM = 128, BN = 128, BK = 32, PITCH = 36;
@@ -32,24 +32,10 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
   const int wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
 
-  // batch pointers
-  const int z = blockIdx.y;
-  const int z1 = z / g.nb2, z2 = z - z1 * g.nb2;
-  const float* A = g.a + z1 * g.sA1 + z2 * g.sA2;
-  const float* W = g.w + z1 * g.sW1 + z2 * g.sW2;
-  float* C = g.c + z1 * g.sC1 + z2 * g.sC2;
-  const float* R = HAS_RES ? g.residual + z1 * g.sC1 + z2 * g.sC2 : nullptr;
-  const float* bias = HAS_BIAS ? g.bias + z1 * g.sBias1 + z2 * g.sBias2 : nullptr;
-
-  // XCD-aware tile order: blocks b, b+8, ... share an XCD (and its L2); give each XCD a contiguous run
-  // of tiles so that neighbouring N-tiles of one M-tile (same A rows) hit the same L2.
+  LRAM_GEMM_BATCH_OPERANDS(blockIdx.y, HAS_BIAS, HAS_RES)
   const int tiles_n = (g.n + BN - 1) / BN;
-  const int tiles_m = (g.m + BM - 1) / BM;
-  const int nwg = tiles_n * tiles_m;
-  int bid = blockIdx.x;
-  if ((nwg & 7) == 0) bid = (bid & 7) * (nwg >> 3) + (bid >> 3);
-  const int tm_idx = bid / tiles_n;
-  const int tn_idx = bid - tm_idx * tiles_n;
+  int tm_idx, tn_idx;
+  gemm_tile_1d(blockIdx.x, tiles_n * ((g.m + BM - 1) / BM), tiles_n, tm_idx, tn_idx);
   const int m0 = tm_idx * BM, n0 = tn_idx * BN;
 
   // global -> register staging: 4 float4 of A and 4 of W per thread per K-tile
@@ -90,9 +76,8 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
   const float* a_base = As + (64 * wm + li) * PITCH + 4 * lh;
   const float* b_base = Bs + (64 * wn + li) * PITCH + 4 * lh;
 
-  const int nk_all = (g.k + BK - 1) / BK;
-  const int kt0 = g.split_k > 1 ? blockIdx.z * g.k_tiles_per_split : 0;
-  const int nk = g.split_k > 1 ? min(nk_all, kt0 + g.k_tiles_per_split) : nk_all;
+  int kt0, nk;
+  gemm_k_range(g, (g.k + BK - 1) / BK, kt0, nk);
   load_tile(kt0 * BK);
   for (int kt = kt0; kt < nk; ++kt) {
     store_tile();
@@ -120,40 +105,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
     __syncthreads();
   }
 
-  // epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-  if (g.split_k > 1) {  // raw partial sums into this split's slab [M][N]; bias / residual are applied by the reduce
-    float* S = g.splitk_ws + (int64_t)blockIdx.z * g.m * g.n;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int col = n0 + 64 * wn + 32 * j + li;
-        if (col >= g.n) continue;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = m0 + 64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (row < g.m) S[(int64_t)row * g.n + col] = acc[i][j][r];
-        }
-      }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = n0 + 64 * wn + 32 * j + li;
-      if (col >= g.n) continue;
-      const float bv = HAS_BIAS ? bias[col] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + 64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (row < g.m) {
-          float v = acc[i][j][r] + bv;
-          if (HAS_RES) v += R[(int64_t)row * g.ldc + col];
-          C[(int64_t)row * g.ldc + col] = v;
-        }
-      }
-    }
+  LRAM_GEMM_STORE_ACC_TILES(2, 64, false)   // (no SiLU columns: the dispatcher refuses act_silu_from for this kernel)
 }
 }  // namespace
 
@@ -168,13 +120,7 @@ constexpr int kGemvCols = 2;  // columns per wave
 
 __global__ __launch_bounds__(256) void gemv_small_m_kernel(GemmArgs g) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int z = blockIdx.y;
-  const int z1 = z / g.nb2, z2 = z - z1 * g.nb2;
-  const float* A = g.a + z1 * g.sA1 + z2 * g.sA2;
-  const float* W = g.w + z1 * g.sW1 + z2 * g.sW2;
-  float* C = g.c + z1 * g.sC1 + z2 * g.sC2;
-  const float* R = g.residual ? g.residual + z1 * g.sC1 + z2 * g.sC2 : nullptr;
-  const float* bias = g.bias ? g.bias + z1 * g.sBias1 + z2 * g.sBias2 : nullptr;
+  LRAM_GEMM_BATCH_OPERANDS(blockIdx.y, g.bias, g.residual)
   const int n0 = (blockIdx.x * 4 + wave) * kGemvCols;
   if (n0 >= g.n) return;
   float acc[kGemvMaxM][kGemvCols];
@@ -243,14 +189,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_kernel(GemmArgs g) {
   __shared__ float part[NW][32][33];
   __shared__ float stat[NORM ? 2 * NW : 1][32];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lh = lane >> 5;
-  const int z = blockIdx.z;
-  const int z1 = z / g.nb2, z2 = z - z1 * g.nb2;
-  const bool tab = g.a_tab[0] != nullptr;
-  const float* A = tab ? g.a_tab[z2] + z1 * g.sA1 : g.a + z1 * g.sA1 + z2 * g.sA2;
-  const float* W = tab ? g.w_tab[z2] + z1 * g.sW1 : g.w + z1 * g.sW1 + z2 * g.sW2;
-  float* C = tab ? g.c_tab[z2] + z1 * g.sC1 : g.c + z1 * g.sC1 + z2 * g.sC2;
-  const float* R = HAS_RES ? g.residual + z1 * g.sC1 + z2 * g.sC2 : nullptr;
-  const float* bias = HAS_BIAS ? g.bias + z1 * g.sBias1 + z2 * g.sBias2 : nullptr;
+  LRAM_GEMM_BATCH_OPERANDS_TAB(blockIdx.z, HAS_BIAS, HAS_RES, float, W, g.w, g.a_tab[0] != nullptr, g.w_tab)
   const int n0 = blockIdx.x * 32, m0 = blockIdx.y * 32;
   // lane group (w, lh) owns the float4 indices [q0, q1) of the K axis
   const int nq = g.k >> 2;
@@ -382,7 +321,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_kernel(GemmArgs g) {
     }
   }
 #pragma unroll
-  for (int r = 0; r < 16; ++r) part[w][(r & 3) + 8 * (r >> 2) + 4 * lh][li] = acc[r];
+  for (int r = 0; r < 16; ++r) part[w][acc_row(r, lh)][li] = acc[r];
   __syncthreads();
   if (!ok) return;
   float o[4];
@@ -543,9 +482,12 @@ void launch_splitk_reduce(const GemmArgs& g, hipStream_t stream) {
 
 bool gemm_small_m(const GemmArgs& g) { return g.m <= kGemvMaxM; }
 
+// The fp32 kernels of this file load both operands as 16-byte pieces: K and the row pitches / the batch strides in float4s.
+static bool k_and_pitches_x4(const GemmArgs& g) { return (g.k & 3) == 0 && (g.lda & 3) == 0 && (g.ldw & 3) == 0; }
+static bool batch_strides_x4(const GemmArgs& g) { return ((g.sA1 | g.sA2 | g.sW1 | g.sW2) & 3) == 0; }
+
 bool gemm_skinny_supported(const GemmArgs& g) {
-  return g.m >= 1 && g.k >= 32 && (g.k & 3) == 0 && (g.lda & 3) == 0 && (g.ldw & 3) == 0 &&
-         ((g.sA1 | g.sA2 | g.sW1 | g.sW2) & 3) == 0 && g.gate == nullptr && g.act_silu_from < 0 &&
+  return g.m >= 1 && g.k >= 32 && k_and_pitches_x4(g) && batch_strides_x4(g) && g.gate == nullptr && g.act_silu_from < 0 &&
          (reinterpret_cast<uintptr_t>(g.a) & 15) == 0 && (reinterpret_cast<uintptr_t>(g.w) & 15) == 0;
 }
 
@@ -593,17 +535,15 @@ void launch_gemm_skinny(const GemmArgs& g, hipStream_t stream) {
 void launch_gemm_f32(const GemmArgs& g_in, hipStream_t stream) {
   GemmArgs g = g_in;
   LRAM_REQUIRE(g.m > 0 && g.n > 0 && g.k > 0, "gemm: empty problem");
+  LRAM_REQUIRE(k_and_pitches_x4(g), "gemm: K, lda, ldw must be multiples of 4");
+  LRAM_REQUIRE(batch_strides_x4(g), "gemm: batch strides of A/W must be multiples of 4");
   if (gemm_small_m(g)) {
-    LRAM_REQUIRE((g.k & 3) == 0 && (g.lda & 3) == 0 && (g.ldw & 3) == 0, "gemm: K, lda, ldw must be multiples of 4");
-    LRAM_REQUIRE(((g.sA1 | g.sA2 | g.sW1 | g.sW2) & 3) == 0, "gemm: batch strides of A/W must be multiples of 4");
     dim3 grid((g.n + 4 * kGemvCols - 1) / (4 * kGemvCols), g.nb1 * g.nb2);
     hipLaunchKernelGGL(gemv_small_m_kernel, grid, dim3(256), 0, stream, g);
     LRAM_HIP_CHECK(hipGetLastError());
     return;
   }
   const int S = gemm_choose_split_k(g);
-  LRAM_REQUIRE((g.k & 3) == 0 && (g.lda & 3) == 0 && (g.ldw & 3) == 0, "gemm: K, lda, ldw must be multiples of 4");
-  LRAM_REQUIRE(((g.sA1 | g.sA2 | g.sW1 | g.sW2) & 3) == 0, "gemm: batch strides of A/W must be multiples of 4");
   const int tiles = ((g.m + BM - 1) / BM) * ((g.n + BN - 1) / BN);
   dim3 grid(tiles, g.nb1 * g.nb2, S);
   dim3 block(256);

@@ -50,6 +50,58 @@ __global__ __launch_bounds__(256) void narrow_pack_kernel(const float* w, int N,
 // gets at two per SIMD -- 8 waves spilled; the matrix-pipe time per SIMD is the same either way: 192 workgroups x 480 MFMAs)
 constexpr int kNarrowWaves = 4;
 
+// ---- what the two kernels of this file share (the exact-fp32 form and the f16x2 form below) ----
+// A loads: instruction i covers rows 4 i + (lane >> 4) of the workgroup's 16 (clamped to M), 16-byte slot lane & 15 of a
+// chunk's 256-byte row piece.  PER_ROW: what else the kernel sets up per instruction i (the f16x2 form: its row's scale).
+#define LRAM_NARROW_A_ROWS(AROW, PER_ROW)                                                                        \
+  _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                \
+    (AROW)[i] = g.a + (int64_t)min(m0 + 4 * i + (lane >> 4), g.m - 1) * g.lda + 4 * (lane & 15);                 \
+    PER_ROW;                                                                                                     \
+  }
+// The chunk walk: wave w takes chunks w, w + NW, ... and requests a chunk's operands a whole chunk ahead, into the register set
+// (a0, w0) or (a1, w1) the running chunk does not use.  A MACRO over the kernel's LOAD(AR, WR, chunk) / COMPUTE(AR, WR) macros
+// with the loop body written out twice: two named register sets -- arrays handed to lambdas by reference ended up in scratch
+// memory.  Names the kernel's wave, nchunks, NW, a0, a1, w0, w1.
+#define LRAM_NARROW_CHUNK_WALK(LOAD, COMPUTE)                \
+  {                                                          \
+    int c = wave;                                            \
+    if (c < nchunks) LOAD(a0, w0, c);                        \
+    while (c < nchunks) {                                    \
+      if (c + NW < nchunks) LOAD(a1, w1, c + NW);            \
+      COMPUTE(a0, w0);                                       \
+      c += NW;                                               \
+      if (c >= nchunks) break;                               \
+      if (c + NW < nchunks) LOAD(a0, w0, c + NW);            \
+      COMPUTE(a1, w1);                                       \
+      c += NW;                                               \
+    }                                                        \
+  }
+// The four waves' partial tiles -> red [wave][j][lane] float4, summed in wave order (deterministic), finished and stored.  C/D
+// layout of the 16 x 16 MFMA: col = lane & 15, row = 4 (lane >> 4) + reg; tile j has 256 values: one per thread.
+// FINISH: a statement on the sum s of (row rl of the workgroup's 16, col) -- the f16x2 form un-scales there, the fp32 form has
+// nothing to do; the bias follows.  Names the kernel's g, acc, wave, lane, tid, m0, J, NW, HAS_BIAS.
+// (MACROS, all three: as functions that take the accumulator tiles / the row pointers by reference, every instance of both
+// kernels got other registers and other code around its K loop; the fp32 kernel's row index is now summed as m0 + rl like the
+// f16x2 kernel's -- five instructions of its epilogue changed places, nothing else in the file moved)
+#define LRAM_NARROW_SUM_STORE(RED, FINISH)                                                         \
+  {                                                                                               \
+    float* red = (RED);                                                                           \
+    _Pragma("unroll") for (int j = 0; j < J; ++j)                                                 \
+      *reinterpret_cast<nf4*>(red + ((wave * J + j) * 64 + lane) * 4) = acc[j];                   \
+    __syncthreads();                                                                              \
+    _Pragma("unroll") for (int j = 0; j < J; ++j) {                                               \
+      const int ln = tid >> 2, reg = tid & 3;                                                     \
+      float s = red[((0 * J + j) * 64 + ln) * 4 + reg];                                           \
+      _Pragma("unroll") for (int w = 1; w < NW; ++w) s += red[((w * J + j) * 64 + ln) * 4 + reg]; \
+      const int rl = 4 * (ln >> 4) + reg, row = m0 + rl, col = 16 * j + (ln & 15);                \
+      if (row < g.m && col < g.n) {                                                               \
+        FINISH;                                                                                   \
+        if (HAS_BIAS) s += g.bias[col];                                                           \
+        g.c[(int64_t)row * g.ldc + col] = s;                                                      \
+      }                                                                                           \
+    }                                                                                             \
+  }
+
 template <int J, bool HAS_BIAS>
 __global__ __launch_bounds__(64 * kNarrowWaves) void gemm_narrow_kernel(GemmArgs g, const float4* __restrict__ wp) {
   constexpr int NW = kNarrowWaves;
@@ -59,10 +111,8 @@ __global__ __launch_bounds__(64 * kNarrowWaves) void gemm_narrow_kernel(GemmArgs
   const int m0 = blockIdx.x * 16;
   float* abuf = lds + wave * 1024;
   const int nchunks = g.k >> 6;
-  // A loads: instruction i covers rows 4 i + (lane >> 4), 16-byte slot lane & 15 of the chunk's 256-byte row piece
   const float* arow[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) arow[i] = g.a + (int64_t)min(m0 + 4 * i + (lane >> 4), g.m - 1) * g.lda + 4 * (lane & 15);
+  LRAM_NARROW_A_ROWS(arow, (void)0)
   const int r = lane & 15, q = lane >> 4;
   nf4 acc[J];
 #pragma unroll
@@ -70,7 +120,6 @@ __global__ __launch_bounds__(64 * kNarrowWaves) void gemm_narrow_kernel(GemmArgs
 
   // One wave per SIMD at most (192 workgroups for 3072 rows): nothing but this wave's own requests hides memory latency, so a
   // chunk's operands -- 4 float4 of A, 4 J float4 of W -- are requested a whole chunk (16 J MFMAs = 2560 cycles at J = 5) ahead.
-  // (two named register sets, the loop body written out twice: arrays handed to lambdas by reference ended up in scratch memory)
   nf4 a0[4], a1[4], w0[4 * J], w1[4 * J];   // (native vector values: HIP's float4 class arrays of the A set went to scratch too)
 #define LRAM_NARROW_LOAD(AR, WR, CH)                                                             \
   {                                                                                              \
@@ -93,41 +142,11 @@ __global__ __launch_bounds__(64 * kNarrowWaves) void gemm_narrow_kernel(GemmArgs
           acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4_[i], WR[gq * J + j][i], acc[j], 0, 0, 0); \
     }                                                                                            \
   }
-  int c = wave;
-  if (c < nchunks) LRAM_NARROW_LOAD(a0, w0, c);
-  while (c < nchunks) {
-    if (c + NW < nchunks) LRAM_NARROW_LOAD(a1, w1, c + NW);
-    LRAM_NARROW_COMPUTE(a0, w0);
-    c += NW;
-    if (c >= nchunks) break;
-    if (c + NW < nchunks) LRAM_NARROW_LOAD(a0, w0, c + NW);
-    LRAM_NARROW_COMPUTE(a1, w1);
-    c += NW;
-  }
+  LRAM_NARROW_CHUNK_WALK(LRAM_NARROW_LOAD, LRAM_NARROW_COMPUTE)
 #undef LRAM_NARROW_LOAD
 #undef LRAM_NARROW_COMPUTE
-  // partial tiles -> LDS [wave][j][lane] float4, summed in wave order
-  float* red = lds + NW * 1024;
-#pragma unroll
-  for (int j = 0; j < J; ++j) *reinterpret_cast<nf4*>(red + ((wave * J + j) * 64 + lane) * 4) = acc[j];
-  __syncthreads();
-  // C/D layout of the 16 x 16 MFMA: col = lane & 15, row = 4 (lane >> 4) + reg; tile j has 256 values: one per thread
-  {
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      const int ln = tid >> 2, reg = tid & 3;
-      float s = red[((0 * J + j) * 64 + ln) * 4 + reg];
-#pragma unroll
-      for (int w = 1; w < NW; ++w) s += red[((w * J + j) * 64 + ln) * 4 + reg];
-      const int row = m0 + 4 * (ln >> 4) + reg, col = 16 * j + (ln & 15);
-      if (row < g.m && col < g.n) {
-        if (HAS_BIAS) s += g.bias[col];
-        g.c[(int64_t)row * g.ldc + col] = s;
-      }
-    }
-  }
+  LRAM_NARROW_SUM_STORE(lds + NW * 1024, (void)rl)
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // f16x2 form: the same decomposition with the products as hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16 (the arithmetic of
@@ -167,11 +186,7 @@ __global__ __launch_bounds__(64 * kNarrowWaves) void gemm_narrow16_kernel(GemmAr
   __syncthreads();
   const float* arow[4];
   float asc[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    arow[i] = g.a + (int64_t)min(m0 + 4 * i + (lane >> 4), g.m - 1) * g.lda + 4 * (lane & 15);
-    asc[i] = scl[4 * i + (lane >> 4)];
-  }
+  LRAM_NARROW_A_ROWS(arow, asc[i] = scl[4 * i + (lane >> 4)])
   const int r = lane & 15, q = lane >> 4;
   nf4 acc[J];
 #pragma unroll
@@ -218,54 +233,30 @@ __global__ __launch_bounds__(64 * kNarrowWaves) void gemm_narrow16_kernel(GemmAr
         acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah_, WR[(s_ * J + j) * 2 + 0], acc[j], 0, 0, 0); \
     }                                                                                            \
   }
-  int c = wave;
-  if (c < nchunks) LRAM_NARROW16_LOAD(a0, w0, c);
-  while (c < nchunks) {
-    if (c + NW < nchunks) LRAM_NARROW16_LOAD(a1, w1, c + NW);
-    LRAM_NARROW16_COMPUTE(a0, w0);
-    c += NW;
-    if (c >= nchunks) break;
-    if (c + NW < nchunks) LRAM_NARROW16_LOAD(a0, w0, c + NW);
-    LRAM_NARROW16_COMPUTE(a1, w1);
-    c += NW;
-  }
+  LRAM_NARROW_CHUNK_WALK(LRAM_NARROW16_LOAD, LRAM_NARROW16_COMPUTE)
 #undef LRAM_NARROW16_LOAD
 #undef LRAM_NARROW16_COMPUTE
-  float* red = lds + NW * 1024 + 32;
-#pragma unroll
-  for (int j = 0; j < J; ++j) *reinterpret_cast<nf4*>(red + ((wave * J + j) * 64 + lane) * 4) = acc[j];
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const int ln = tid >> 2, reg = tid & 3;
-    float s = red[((0 * J + j) * 64 + ln) * 4 + reg];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) s += red[((w * J + j) * 64 + ln) * 4 + reg];
-    const int rl = 4 * (ln >> 4) + reg, row = m0 + rl, col = 16 * j + (ln & 15);
-    if (row < g.m && col < g.n) {
-      s *= scl[16 + rl] * g.w_inv[col];   // exact: powers of two
-      if (HAS_BIAS) s += g.bias[col];
-      g.c[(int64_t)row * g.ldc + col] = s;
-    }
+  LRAM_NARROW_SUM_STORE(lds + NW * 1024 + 32, s *= scl[16 + rl] * g.w_inv[col])   // exact: powers of two
+}
+
+// Both kernels are templated on <J = ceil(N / 16), HAS_BIAS> and launched on 16 rows per workgroup: calls f(J, has_bias, grid,
+// block) with the launch's two as std::integral_constant (in the style of launch_bias_res, common.h).
+template <typename F>
+void launch_narrow_j(const GemmArgs& g, F&& f) {
+  const dim3 grid((unsigned)((g.m + 15) / 16)), block(64 * kNarrowWaves);
+  const auto with_bias = [&](auto j) {
+    if (g.bias != nullptr) f(j, std::true_type{}, grid, block);
+    else f(j, std::false_type{}, grid, block);
+  };
+  switch ((g.n + 15) / 16) {
+    case 1: with_bias(std::integral_constant<int, 1>{}); break;
+    case 2: with_bias(std::integral_constant<int, 2>{}); break;
+    case 3: with_bias(std::integral_constant<int, 3>{}); break;
+    case 4: with_bias(std::integral_constant<int, 4>{}); break;
+    case 5: with_bias(std::integral_constant<int, 5>{}); break;
+    default: with_bias(std::integral_constant<int, 6>{}); break;
   }
-}
-
-template <int J>
-void launch16_j(const GemmArgs& g, hipStream_t stream) {
-  dim3 grid((unsigned)((g.m + 15) / 16)), block(64 * kNarrowWaves);
-  if (g.bias != nullptr)
-    hipLaunchKernelGGL((gemm_narrow16_kernel<J, true>), grid, block, 0, stream, g);
-  else
-    hipLaunchKernelGGL((gemm_narrow16_kernel<J, false>), grid, block, 0, stream, g);
-}
-
-template <int J>
-void launch_j(const GemmArgs& g, const float4* wp, hipStream_t stream) {
-  dim3 grid((unsigned)((g.m + 15) / 16)), block(64 * kNarrowWaves);
-  if (g.bias != nullptr)
-    hipLaunchKernelGGL((gemm_narrow_kernel<J, true>), grid, block, 0, stream, g, wp);
-  else
-    hipLaunchKernelGGL((gemm_narrow_kernel<J, false>), grid, block, 0, stream, g, wp);
+  LRAM_HIP_CHECK(hipGetLastError());
 }
 }  // namespace
 
@@ -294,29 +285,17 @@ bool gemm_narrow16_supported(const GemmArgs& g) {
 
 void launch_gemm_narrow16(const GemmArgs& g, hipStream_t stream) {
   LRAM_REQUIRE(g.m > 0 && gemm_narrow16_supported(g), "narrow-output projection (f16x2): unsupported operands");
-  switch ((g.n + 15) / 16) {
-    case 1: launch16_j<1>(g, stream); break;
-    case 2: launch16_j<2>(g, stream); break;
-    case 3: launch16_j<3>(g, stream); break;
-    case 4: launch16_j<4>(g, stream); break;
-    case 5: launch16_j<5>(g, stream); break;
-    default: launch16_j<6>(g, stream); break;
-  }
-  LRAM_HIP_CHECK(hipGetLastError());
+  launch_narrow_j(g, [&](auto j, auto b, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL((gemm_narrow16_kernel<decltype(j)::value, decltype(b)::value>), grid, block, 0, stream, g);
+  });
 }
 
 void launch_gemm_narrow(const GemmArgs& g, const float* packed, hipStream_t stream) {
   LRAM_REQUIRE(g.m > 0 && gemm_narrow_supported(g) && packed != nullptr, "narrow-output projection: unsupported operands");
   const float4* wp = reinterpret_cast<const float4*>(packed);
-  switch ((g.n + 15) / 16) {
-    case 1: launch_j<1>(g, wp, stream); break;
-    case 2: launch_j<2>(g, wp, stream); break;
-    case 3: launch_j<3>(g, wp, stream); break;
-    case 4: launch_j<4>(g, wp, stream); break;
-    case 5: launch_j<5>(g, wp, stream); break;
-    default: launch_j<6>(g, wp, stream); break;
-  }
-  LRAM_HIP_CHECK(hipGetLastError());
+  launch_narrow_j(g, [&](auto j, auto b, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL((gemm_narrow_kernel<decltype(j)::value, decltype(b)::value>), grid, block, 0, stream, g, wp);
+  });
 }
 
 }  // namespace lram

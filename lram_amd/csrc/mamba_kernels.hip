@@ -45,10 +45,6 @@ __global__ __launch_bounds__(256) void mamba_conv_kernel(MambaConvArgs a) {
   *reinterpret_cast<float4*>(a.conv_state + gid * 4) = win;
 }
 
-// selective_state_update for T tokens.  One workgroup = one env x 64 channels; 4 lanes per channel, each
-// owning 4 of the N = 16 states (16 B per lane, consecutive lanes consecutive addresses).  The env's B_t, C_t
-// vectors (shared by all its channels) are staged once in LDS and read back as broadcasts.
-//   dt = softplus(dt_proj(dt_raw) + dt_bias);  s = s * exp(dt * A) + x * (dt * B);  y = s . C + D x;  y *= silu(z)
 // same, runtime T (prefill chunks)
 __global__ __launch_bounds__(256) void mamba_conv_rt_kernel(MambaConvArgs a) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -96,6 +92,10 @@ __global__ __launch_bounds__(256) void mamba_dt_proj_kernel(const float* __restr
   dtp[gid] = acc;
 }
 
+// selective_state_update for T tokens.  One workgroup = one env x 64 channels; 4 lanes per channel, each
+// owning 4 of the N = 16 states (16 B per lane, consecutive lanes consecutive addresses).  The env's B_t, C_t
+// vectors (shared by all its channels) are staged once in LDS and read back as broadcasts.
+//   dt = softplus(dt_proj(dt_raw) + dt_bias);  s = s * exp(dt * A) + x * (dt * B);  y = s . C + D x;  y *= silu(z)
 // kSsmEnvs envs per workgroup (4 for an env-step: amortises A = -exp(A_log) and keeps 4 state loads in flight
 // per lane; 1 for the long prefill chunks, whose LDS staging grows with T)
 

@@ -357,9 +357,7 @@ __global__ __launch_bounds__(kThreads) void mlstm_cell_chunk_kernel(MlstmCellArg
   const int nslices = DH / kCW;
   // XCD-aware order: consecutive work items (the column slices of one (env, head), which share Q, K and A) run on
   // the same XCD back to back, so the second slice finds them in that XCD's L2
-  int wid = blockIdx.x;
-  const int nwg = gridDim.x;
-  if ((nwg & 7) == 0) wid = (wid & 7) * (nwg >> 3) + (wid >> 3);
+  const int wid = xcd_contiguous_id(blockIdx.x, gridDim.x);
   const int slice = wid % nslices;
   const int bh = wid / nslices;
   const int h = bh % NH, b = bh / NH;
@@ -553,37 +551,11 @@ __global__ __launch_bounds__(kThreads) void mlstm_cell_chunk_kernel(MlstmCellArg
 //     (w Khat)^T planes are staged per 32-row tile; 16-byte granules XOR-swizzled so ds_read_b128 / ds_write_b128 /
 //     ds_write_b64 are conflict-free without padding: 72 KB of LDS, two workgroups per CU.
 // =============================================================================================
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+// (the split, its vector form and the six products in their order: device_math.h)
 constexpr int kVPlane = kCW * kLp;   // bf16 elements per V plane   [128 columns][64 tokens]
 constexpr int kQPlane = kLp * kRT;   // per (fcum Q) plane          [64 tokens][32 row slots]
 constexpr int kKPlane = kRT * kLp;   // per (w Khat)^T plane        [32 rows][64 tokens]
 constexpr int kCell3Lds = 3 * (kVPlane + kQPlane + kKPlane) * 2;  // 73,728 B
-
-__device__ __forceinline__ void split3(float x, __bf16& hi, __bf16& mid, __bf16& lo) {
-  hi = (__bf16)x;
-  const float r1 = x - (float)hi;
-  mid = (__bf16)r1;
-  lo = (__bf16)(r1 - (float)mid);
-}
-template <typename V, int N>
-__device__ __forceinline__ void split3v(const float (&x)[N], V& hi, V& mid, V& lo) {
-#pragma unroll
-  for (int e = 0; e < N; ++e) {
-    __bf16 h, m, l;
-    split3(x[e], h, m, l);
-    hi[e] = h, mid[e] = m, lo[e] = l;
-  }
-}
-// acc += a * b with a = a[0] + a[1] + a[2], b likewise; smallest terms first
-__device__ __forceinline__ void mfma6(f32x16& acc, const bf16x8 (&a)[3], const bf16x8 (&b)[3]) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
-}
 
 __global__ __launch_bounds__(kThreads) void mlstm_cell_chunk3_kernel(MlstmCellArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -594,9 +566,7 @@ __global__ __launch_bounds__(kThreads) void mlstm_cell_chunk3_kernel(MlstmCellAr
 
   const int T = a.T, NH = a.NH, DH = a.DH, inner = NH * DH;
   const int nslices = DH / kCW;
-  int wid = blockIdx.x;  // XCD-aware order, as the fp32 form
-  const int nwg = gridDim.x;
-  if ((nwg & 7) == 0) wid = (wid & 7) * (nwg >> 3) + (wid >> 3);
+  const int wid = xcd_contiguous_id(blockIdx.x, gridDim.x);  // XCD-aware order, as the fp32 form
   const int slice = wid % nslices;
   const int bh = wid / nslices;
   const int h = bh % NH, b = bh / NH;
@@ -733,13 +703,13 @@ __global__ __launch_bounds__(kThreads) void mlstm_cell_chunk3_kernel(MlstmCellAr
         const __bf16* src = Qp + li * kRT + (((2 * lh + ks) ^ ((li >> 2) & 3)) << 3);
 #pragma unroll
         for (int p = 0; p < 3; ++p) qf[p] = *reinterpret_cast<const bf16x8*>(src + p * kQPlane);
-        mfma6(hacc0, qf, cb);
+        bf16x3_products(hacc0, qf, cb);
       }
       if (two) {
         const __bf16* src = Qp + (32 + li) * kRT + (((2 * lh + ks) ^ ((li >> 2) & 3)) << 3);   // ((32 + li) >> 2) & 3 == (li >> 2) & 3
 #pragma unroll
         for (int p = 0; p < 3; ++p) qf[p] = *reinterpret_cast<const bf16x8*>(src + p * kQPlane);
-        mfma6(hacc1, qf, cb);
+        bf16x3_products(hacc1, qf, cb);
       }
     }
     // ---- C_T[tile, cols] = fcum_{T-1} C_0[tile, cols] + (w Khat)[:, tile]^T V[:, cols] ----
@@ -755,7 +725,7 @@ __global__ __launch_bounds__(kThreads) void mlstm_cell_chunk3_kernel(MlstmCellAr
           kf[p] = *reinterpret_cast<const bf16x8*>(ksrc + p * kKPlane);
           vf[p] = *reinterpret_cast<const bf16x8*>(vsrc + p * kVPlane);
         }
-        mfma6(cacc, kf, vf);
+        bf16x3_products(cacc, kf, vf);
       }
     }
     cprev = cacc;
@@ -787,14 +757,14 @@ __global__ __launch_bounds__(kThreads) void mlstm_cell_chunk3_kernel(MlstmCellAr
           const float4 a1 = *reinterpret_cast<const float4*>(Ag + li * kLp + 16 * ks + 8 * lh + 4);
           const float x[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
           split3v(x, af[0], af[1], af[2]);
-          mfma6(hacc0, af, vf);
+          bf16x3_products(hacc0, af, vf);
         }
         if (two) {
           const float4 a0 = *reinterpret_cast<const float4*>(Ag + (32 + li) * kLp + 16 * ks + 8 * lh);
           const float4 a1 = *reinterpret_cast<const float4*>(Ag + (32 + li) * kLp + 16 * ks + 8 * lh + 4);
           const float x[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
           split3v(x, af[0], af[1], af[2]);
-          mfma6(hacc1, af, vf);
+          bf16x3_products(hacc1, af, vf);
         }
       }
     }

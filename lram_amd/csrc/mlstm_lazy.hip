@@ -179,9 +179,7 @@ __device__ __forceinline__ void mlstm_lazy_fold_body(const MlstmLazyArgs& a) {
   __shared__ __attribute__((aligned(16))) float Ks[(kFR / 32) * WF * kFPK];
   const int DH = a.DH, NH = a.NH;
   const int nsl = DH / kFC;
-  int wid = blockIdx.x;
-  const int nwg = gridDim.x;
-  if ((nwg & 7) == 0) wid = (wid & 7) * (nwg >> 3) + (wid >> 3);
+  int wid = xcd_contiguous_id(blockIdx.x, gridDim.x);
   const int nrs = DH / kFR;
   const int rsplit = wid % nrs;
   wid /= nrs;

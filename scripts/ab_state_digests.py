@@ -16,8 +16,15 @@ the published presets (the only 4-head geometries with an inner dim beyond 1024 
 
     python scripts/ab_state_digests.py [--parent parent] [--out report.txt]
 
+The GEMM kernels outside the engine's default paths have cases of their own: GEMM_CASES runs a standalone entry (lram_gemm_*,
+engine.gemm_f32(kernel=...)) on seeded operands of every shape the parity tests use (tests/test_gpu_parity.py), with bias and as
+an accumulating call, one digest per shape and form; the "tiles_*" cases are the engine runs of
+test_tile_kernels_carry_few_row_projections_within_the_parity_bars (the few-row kernel off: split-K and its reduce, gated operand,
+SiLU columns, batched and table-addressed GEMMs on the tile kernels).  --cases takes shell patterns: --cases 'gemm_*' 'tiles_*' 'chunk3_*'.
+
 Prints one line per case and a JSON summary; exit status 1 when a digest differs (or a child failed)."""
 import argparse
+import fnmatch
 import hashlib
 import json
 import os
@@ -89,6 +96,23 @@ CASES = {
     "lazy_parked": ("preset:xlstm_16m", 19, ("steps", 18), "lazy", {}, {"period": 3, "micro": 2, "live": 11}),
     "lazy_parked_dh512": ("geo:nh2_dh512", 19, ("steps", 18), "lazy", {}, {"period": 3, "micro": 2, "live": 11}),
     "lazy_export_mid": ("preset:xlstm_16m", 7, ("steps", 10), "lazy", {}, {"export_at": 5}),
+    # the 36- / 18-row projections on the 128 x 128 tile kernels (few-row kernel off), sLSTM recurrence as batched GEMMs
+    **{f"tiles_{kind}_{model[:5]}": (f"preset:{model}", B, ("steps", 4), None,
+                                     {"LRAM_GEMM": kind, "LRAM_GEMM_SKINNY_ROWS": "0", **GEMM})
+       for kind in ("bf16x3", "f32") for model, B in (("xlstm_16m", 12), ("mamba_48m", 6))},
+}
+# standalone GEMM entries: name -> (kernel of engine.gemm_f32, shapes (m, n, k)): the parameter lists of tests/test_gpu_parity.py
+_TILE = [(128, 128, 32), (96, 2192, 512), (300, 80, 1536), (1000, 1408, 512), (4096, 512, 1024), (1100, 1024, 40), (1030, 650, 40)]
+_NARROW = [(3072, 80, 1536), (300, 80, 1536), (257, 33, 256), (1000, 96, 320), (17, 5, 256), (4100, 80, 2560), (64, 16, 576),
+           (40, 48, 320), (40, 20, 256), (40, 60, 320)]
+GEMM_CASES = {
+    "gemm_f32": ("f32", _TILE + [(37, 204, 204), (9, 80, 1536)]),
+    "gemm_gemv": ("f32", [(5, 8, 4), (3, 2048, 512), (6, 513, 1024), (8, 80, 1536)]),
+    "gemm_bf16x3": ("bf16x3", _TILE + [(5, 8, 8), (257, 129, 48)]),
+    "gemm_few_row": ("skinny", [(9, 80, 1536), (96, 2192, 512), (36, 2048, 512), (96, 512, 1024), (192, 2816, 512), (33, 130, 36),
+                                (100, 513, 1344), (24, 1280, 2560), (63, 5120, 1280), (17, 32, 32)]),
+    "gemm_narrow": ("narrow", _NARROW),
+    "gemm_narrow16": ("narrow16", _NARROW),
 }
 RESTART_SLOT = 2
 
@@ -105,7 +129,27 @@ def case_spec(geometry):
     return lay(name)
 
 
+def child_gemm(name):
+    import torch
+    from lram_amd.engine import gemm_f32
+    kernel, shapes = GEMM_CASES[name]
+    digests = {}
+    for m, n, k in shapes:
+        g = torch.Generator().manual_seed(m * 7 + n + k)
+        a = (torch.randn(m, k, generator=g) * torch.exp(torch.randn(m, 1, generator=g))).cuda()   # rows of varied scale
+        w, bias, base = torch.randn(n, k, generator=g).cuda(), torch.randn(n, generator=g).cuda(), torch.randn(m, n, generator=g).cuda()
+        outs = [gemm_f32(a, w, bias, kernel=kernel)]
+        if not kernel.startswith("narrow"):   # (the narrow-output kernels take no residual)
+            outs.append(gemm_f32(a, w, None, out=base.clone(), accumulate=True, kernel=kernel))
+        torch.cuda.synchronize()
+        for form, t in zip(("bias", "accumulate"), outs):
+            digests[f"{m}x{n}x{k}.{form}"] = hashlib.sha256(t.cpu().contiguous().numpy().tobytes()).hexdigest()
+    print(json.dumps({"case": name, "digests": digests, "slstm": {}, "mode": kernel}))
+
+
 def child(name):
+    if name in GEMM_CASES:
+        return child_gemm(name)
     import torch
     from lram_amd import engine, init_state_dict
     from tests.helpers import make_inputs
@@ -152,12 +196,19 @@ def child(name):
                 t0 += L
     torch.cuda.synchronize()
     digests["outputs"] = h.hexdigest()
-    blocks = sorted({0, spec.n_blocks - 1} | set(list(spec.slstm_at)[:1]))
+    if spec.backbone == "mamba":   # conv and SSM state of the first and the last block
+        pkv = eng.export_past_key_values()
+        for blk in (0, spec.n_blocks - 1):
+            for which, what in ((0, "conv"), (1, "ssm")):
+                digests[f"block{blk}.{what}"] = hashlib.sha256(pkv[blk][which].cpu().contiguous().numpy().tobytes()).hexdigest()
+    blocks = [] if spec.backbone == "mamba" else sorted({0, spec.n_blocks - 1} | set(list(spec.slstm_at)[:1]))
     for blk in blocks:
         for which, what in ((0, "planes"), (3, "conv")) if blk in spec.slstm_at else ((0, "C"), (1, "n"), (2, "m"), (3, "conv")):
             t = eng.export_state_tensor(blk, which)
             digests[f"block{blk}.{what}"] = hashlib.sha256(t.cpu().contiguous().numpy().tobytes()).hexdigest()
-    counts = eng.slstm_counts() if spec.slstm_at else {}
+    counts = eng.slstm_counts() if spec.backbone != "mamba" and spec.slstm_at else {}
+    if name.startswith("tiles_"):   # which projection families ran (launch counts per family)
+        counts = {**counts, **{k: v["launches"] for k, v in eng.gemm_counts().items()}}
     ran = eng.state_mode   # (what lram_get_state_mode reports: a "lazy" run took the lean front end where the head dim is 128 / 256)
     eng.close()
     print(json.dumps({"case": name, "digests": digests, "slstm": counts, "mode": ran}))
@@ -168,20 +219,23 @@ def main():
     ap.add_argument("--parent", default="parent", help="csrc/_variants/<name>.so: the parent commit's library")
     ap.add_argument("--out", help="write the report here as well")
     ap.add_argument("--timeout", type=int, default=150, help="time limit of one child, seconds")
-    ap.add_argument("--case", choices=list(CASES), help="(internal) run one case in this process")
+    ap.add_argument("--case", choices=list(CASES) + list(GEMM_CASES), help="(internal) run one case in this process")
+    ap.add_argument("--cases", nargs="+", default=["*"], help="shell patterns: the cases to run (default: all)")
     args = ap.parse_args()
     if args.case:
         return child(args.case)
     if not os.path.exists(os.path.join(ROOT, "lram_amd", "csrc", "_variants", args.parent + ".so")):
         sys.exit(f"csrc/_variants/{args.parent}.so is missing: build the parent commit and copy its liblram_hip.so there")
     lines, results = [], {}
+    cases = {n: c for n, c in {**CASES, **{n: (f"entry:{k}", len(s), ("shapes",), None, {}) for n, (k, s) in GEMM_CASES.items()}}.items()
+             if any(fnmatch.fnmatch(n, pat) for pat in args.cases)}
 
     def say(line):
         print(line, flush=True)
         lines.append(line)
 
     for lib in (args.parent, None):
-        for name, case in CASES.items():
+        for name, case in cases.items():
             env = {**os.environ, **case[4]}
             env.pop("LRAM_LIB_VARIANT", None)
             if lib:
@@ -198,7 +252,7 @@ def main():
             results[(lib or "tree", name)] = json.loads(out.strip().splitlines()[-1])
             print(f"[{lib or 'tree'}] {name}: done", file=sys.stderr, flush=True)
     differ = []
-    for name, (geometry, B, run, mode, env, *opt) in CASES.items():
+    for name, (geometry, B, run, mode, env, *opt) in cases.items():
         env = {**env, **(opt[0] if opt else {})}
         a, b = results[(args.parent, name)], results[("tree", name)]
         bad = sorted(k for k in a["digests"] if a["digests"][k] != b["digests"].get(k))
@@ -206,9 +260,9 @@ def main():
         forms = " ".join(f"{k}={v}" for k, v in b["slstm"].items() if v)
         say(f"{name:22s} {geometry:18s} B={B:<3d} {' '.join(map(str, run)):14s} {(mode or 'auto') + '>' + b['mode'][:5]:11s} "
             f"{' '.join(f'{k}={v}' for k, v in env.items()) or '-':58s} {len(a['digests'])} digests "
-            f"{'EQUAL' if not bad else 'DIFFER: ' + ', '.join(bad)}  outputs {b['digests']['outputs'][:12]}  sLSTM launches: {forms or '-'}")
-    n = sum(len(results[("tree", c)]["digests"]) for c in CASES)
-    say(json.dumps({"cases": len(CASES), "digests": n, "differ": differ}))
+            f"{'EQUAL' if not bad else 'DIFFER: ' + ', '.join(bad)}  outputs {b['digests'].get('outputs', '-')[:12]}  sLSTM launches: {forms or '-'}")
+    n = sum(len(results[("tree", c)]["digests"]) for c in cases)
+    say(json.dumps({"cases": len(cases), "digests": n, "differ": differ}))
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")

@@ -27,6 +27,11 @@ SHAPES = [  # (tag, M, N, K)
     # C5 prefill: 206M, 512 slots in two slices x 63-token chunks = 16128 rows per projection launch
     ("c5_up", 16128, 5120, 1280), ("c5_down", 16128, 1280, 2560),
 ]
+# the few-row kernel ("skinny") runs these instead: 12 / 32 / 64 envs x 3 tokens, K <= 1024 (what the dispatcher gives it)
+FEW_ROW_SHAPES = [
+    ("16m_up_b12", 36, 2048, 512), ("16m_down_b12", 36, 512, 1024), ("16m_up_b32", 96, 2048, 512), ("16m_down_b32", 96, 512, 1024),
+    ("16m_ffn_up_b64", 192, 1408, 512), ("mamba_in_b32", 96, 3072, 768),
+]
 REPS = 5
 
 if __name__ == "__main__":
@@ -34,13 +39,15 @@ if __name__ == "__main__":
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(0)
     order = []
-    for tag, M, N, K in SHAPES:
+    for tag, M, N, K in SHAPES + (FEW_ROW_SHAPES if "skinny" in kernels else []):
         a = torch.randn(M, K, device=dev, generator=g)
         w = torch.randn(N, K, device=dev, generator=g) * 0.05
         for kern in kernels:
             if kern in ("f16x2p", "f16x2p8") and K % 32 != 0:
                 continue
             if kern in ("narrow", "narrow16") and (N > 96 or K % 64 != 0 or K < 256):
+                continue
+            if (kern == "skinny") != (M <= 192):
                 continue
             for _ in range(REPS):
                 gemm_f32(a, w, kernel=kern)

@@ -20,7 +20,7 @@ def _engine(spec, sd, B):
 
 @pytest.mark.parametrize("m,n,k", [(128, 128, 32), (96, 2192, 512), (300, 80, 1536), (1000, 1408, 512),
                                    (37, 204, 204), (4096, 512, 1024), (5, 8, 4), (3, 2048, 512), (6, 513, 1024),
-                                   (8, 80, 1536), (9, 80, 1536)])
+                                   (8, 80, 1536), (9, 80, 1536), (1100, 1024, 40), (1030, 650, 40)])
 def test_gemm_f32_matches_fp64(hip_lib, m, n, k):
     from lram_amd.engine import gemm_f32
     g = torch.Generator().manual_seed(m * 7 + n)
@@ -73,14 +73,14 @@ def test_gemm_few_row_kernel_matches_fp64(hip_lib, m, n, k):
 
 
 @pytest.mark.parametrize("m,n,k", [(3072, 80, 1536), (300, 80, 1536), (257, 33, 256), (1000, 96, 320), (17, 5, 256), (4100, 80, 2560),
-                                   (64, 16, 64 * 9), (40, 48, 64 * 5)])
+                                   (64, 16, 64 * 9), (40, 48, 64 * 5), (40, 20, 256), (40, 60, 320)])
 @pytest.mark.parametrize("kern", ["narrow", "narrow16"])
 def test_gemm_narrow_output_kernel_matches_fp64(hip_lib, m, n, k, kern):
     """gemm_narrow_kernel / gemm_narrow16_kernel (Mamba's x_proj in the engine: N = 80, K = 1536, from 256 operand rows): exact fp32
     products ("narrow") or f16x2 split products ("narrow16": the engine's default beside f16x2 projections) on the matrix
     cores, 16 rows x all columns per workgroup, K chunks of 64 dealt to 4 waves (fewer chunks than waves, a chunk count that 4
     does not divide), ragged last row block, column counts that are not multiples of 16, bias, a row range of a wider operand
-    and of a wider output -- the bar of the k-ordered fp32 kernel."""
+    and of a wider output -- the bar of the k-ordered fp32 kernel.  The shapes cover every instance J = ceil(N / 16) = 1 .. 6."""
     from lram_amd.engine import gemm_f32
     g = torch.Generator().manual_seed(m * 7 + n + k)
     a = torch.randn(m, k, generator=g)
@@ -114,10 +114,12 @@ def test_gemm_narrow_output_kernel_matches_fp64(hip_lib, m, n, k, kern):
 
 
 @pytest.mark.parametrize("m,n,k", [(128, 128, 32), (96, 2192, 512), (300, 80, 1536), (1000, 1408, 512),
-                                   (4096, 512, 1024), (5, 8, 8), (257, 129, 48)])
+                                   (4096, 512, 1024), (5, 8, 8), (257, 129, 48), (1100, 1024, 40), (1030, 650, 40)])
 def test_gemm_bf16x3_matches_fp64(hip_lib, m, n, k):
     """The projection kernel (3 x bf16 split operands, 6 MFMA products) is fp32-accurate: its error against
-    fp64 stays within a small factor of the exact fp32-MFMA kernel's on the same data."""
+    fp64 stays within a small factor of the exact fp32-MFMA kernel's on the same data.  The last two shapes run the 128-row
+    tile over 9 row tiles with a second K tile of 8 live elements: 72 tiles (the XCD tile order remaps) and 54 tiles with a
+    ragged last column tile (no remap); every other shape but (5, 8, 8) takes the 64-row tile."""
     from lram_amd.engine import gemm_f32
     g = torch.Generator().manual_seed(m * 11 + n)
     a = torch.randn(m, k, generator=g) * torch.exp(torch.randn(m, 1, generator=g))   # rows of varied scale
@@ -241,7 +243,7 @@ def test_gemm_f16x2_presplit_every_tile_is_bit_identical(hip_lib, monkeypatch, t
 @pytest.mark.parametrize("panel", [1, 5, 6, 99])
 def test_gemm_tile_order_is_a_bijection_on_the_device(hip_lib, monkeypatch, panel):
     """The workgroup id -> output tile map (XCD-aware: a 2-D split of the tile grid over the 8 L2s where one fits, else column
-    panels; csrc/common.h gemm_tile_of) only renames workgroups: every order gives the same bits as every other, on tile grids
+    panels; csrc/gemm_tile.h gemm_tile_of) only renames workgroups: every order gives the same bits as every other, on tile grids
     8 divides and on ones it does not, with a ragged last panel, for both f16x2 kernels."""
     from lram_amd.engine import gemm_f32
     outs = {}
@@ -288,8 +290,9 @@ def test_gemm_8phase_kernel_race_screen(hip_lib):
 
 
 def _run_parity(name, B, steps, seed=0, discrete=False, graph=False, hidden_tol=2e-4, state_tol=2e-4, spec=None,
-                sd=None, cond_aware=False, scheme="exercise", reset_prob=0.15, obs_gain=None, pooled=False):
-    """scheme: weight distribution (lram_amd/weights.py::init_state_dict); reset_prob: per-env, per-step restart probability;
+                sd=None, cond_aware=False, scheme="exercise", reset_prob=0.15, obs_gain=None, pooled=False, gemm_counts=None):
+    """gemm_counts: a dict that takes Engine.gemm_counts() of the run.
+    scheme: weight distribution (lram_amd/weights.py::init_state_dict); reset_prob: per-env, per-step restart probability;
     obs_gain: (channel, factor) scales one observation channel (un-normalised outlier).
     cond_aware: where the engine is further than the tolerance from the fp32 oracle, accept it if it is as close to
     the float64 evaluation as the fp32 oracle itself is (tests/helpers.py::Fp64Oracle) -- deep stacks meet inputs that
@@ -357,6 +360,8 @@ def _run_parity(name, B, steps, seed=0, discrete=False, graph=False, hidden_tol=
             else:   # [4, B, D] -> env-major
                 close(blk["slstm_state"].transpose(0, 1), ref["slstm_state"].transpose(0, 1),
                       r64["slstm_state"].transpose(0, 1), f"slstm state {i}")
+    if gemm_counts is not None:
+        gemm_counts.update(eng.gemm_counts())
     eng.close()
     # the fp64-aware escape hatch must stay the exception: at most 5 % of the compared rows may need it
     assert relaxed_rows_fraction() <= 0.05, f"{name}: {relaxed_rows_fraction():.1%} of the rows needed the fp64 rule"
@@ -586,6 +591,27 @@ def test_every_projection_kernel_kind_meets_the_parity_bars(hip_lib, monkeypatch
     monkeypatch.setenv("LRAM_GEMM", kind)
     monkeypatch.setenv("LRAM_F16_MIN_ROWS", "9")
     assert _run_parity(name, B=B, steps=steps) == 0
+
+
+@pytest.mark.parametrize("kind", ["bf16x3", "f32"])
+@pytest.mark.parametrize("name,B,steps", [("xlstm_16m", 12, 4), ("mamba_48m", 6, 4)])
+def test_tile_kernels_carry_few_row_projections_within_the_parity_bars(hip_lib, monkeypatch, kind, name, B, steps):
+    """With the few-row kernel off (LRAM_GEMM_SKINNY_ROWS=0) the 36- and 18-row projections of an oracle-sized batch run on the
+    128 x 128 tile kernels of the chosen family, in the forms the standalone entries cannot reach: split-K with the float4
+    reduce (proj_down: 4 tiles, K = 1024), the gated operand and the SiLU columns of proj_up / proj_down (bf16x3), the per-head
+    batched sLSTM GEMMs (recurrence as a GEMM: LRAM_SLSTM_SEQ=0, LRAM_SLSTM_FUSED_ROWS=0).  Same bars as the test above; the
+    family under test launched, and the few-row family carried nothing LRAM_GEMM_SKINNY_ROWS governs: its only launches are the
+    four sLSTM gate projections as one table-addressed launch per sLSTM block and step, which engine.h's slstm_gates_rows (a
+    compile-time 768 rows for head dims up to 128) sends there whatever the knob says."""
+    monkeypatch.setenv("LRAM_GEMM", kind)
+    monkeypatch.setenv("LRAM_GEMM_SKINNY_ROWS", "0")
+    monkeypatch.setenv("LRAM_SLSTM_SEQ", "0")
+    monkeypatch.setenv("LRAM_SLSTM_FUSED_ROWS", "0")
+    counts = {}
+    assert _run_parity(name, B=B, steps=steps, gemm_counts=counts) == 0
+    spec = preset(name)
+    gate_launches = 0 if spec.backbone == "mamba" else len(spec.slstm_at) * steps
+    assert counts[kind]["launches"] > 0 and counts["few_row_f32"]["launches"] == gate_launches, counts
 
 
 def test_discrete_head_bit_exact(hip_lib):

@@ -34,7 +34,7 @@ def _resources(src):
             name = m.group(1)
             res[name] = {}
             continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|LDS Size \[bytes/block\]|VGPRs Spill):\s+(\d+)", line)
+        m = re.search(r"remark:\s+(VGPRs|AGPRs|LDS Size \[bytes/block\]|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]):\s+(\d+)", line)
         if m and name:
             res[name][m.group(1)] = int(m.group(2))
     assert res, out[-2000:]
@@ -70,3 +70,28 @@ def test_on_the_fly_projection_workgroup_budget():
     assert two_stage["VGPRs"] <= 160 and two_stage["LDS Size [bytes/block]"] <= 48 * 1024, two_stage
     gated = _one(res, "gemm_f16x2_kernelILb0ELb1ELi64ELb1ELb0E")                # proj_down of the headline: 64-row tile, gate in the staging
     assert gated["VGPRs"] <= 128 and gated["LDS Size [bytes/block]"] <= 36 * 1024, gated
+
+
+# The GEMM kernels outside the f16x2 family share their batch addressing, tile order, K range and epilogue through macros and
+# inlined functions (csrc/gemm_tile.h, the macros of gemm_narrow.hip): what an instance occupies must not move with them.
+# (LDS bytes per workgroup, waves per SIMD) of the build the sharing was introduced on; no scratch and no spill in any of them.
+_PINNED = {
+    "gemm_bf16x3.hip": {"gemm_bf16x3_kernelILb0ELb0ELi128ELb0E": (61440, 2),       # 128-row tile
+                        "gemm_bf16x3_kernelILb0ELb0ELi64ELb0E": (46080, 3),        # 64-row tile
+                        "gemm_bf16x3_kernelILb0ELb1ELi64ELb1E": (46080, 3)},       # ... gated (proj_down)
+    "gemm_f32.hip": {"gemm_f32_kernelILb0ELb0E": (36864, 3),
+                     "gemm_skinny_kernelILb0ELb0ELi4ELi8ELb0ELb0E": (16896, 4)},
+    "gemm_narrow.hip": {**{f"gemm_narrow_kernelILi{j}ELb0E": v for j, v in
+                           zip(range(1, 7), ((20480, 4), (24576, 3), (28672, 2), (32768, 2), (36864, 1), (40960, 1)))},
+                        **{f"gemm_narrow16_kernelILi{j}ELb0E": v for j, v in
+                           zip(range(1, 7), ((20608, 4), (24704, 2), (28800, 2), (32896, 1), (36992, 1), (41088, 1)))}},
+}
+
+
+@pytest.mark.parametrize("src", sorted(_PINNED))
+def test_shared_gemm_pieces_cost_no_scratch_lds_or_occupancy(src):
+    res = _resources(src)
+    for needle, (lds, occupancy) in _PINNED[src].items():
+        r = _one(res, needle)
+        assert r["ScratchSize [bytes/lane]"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, (needle, r)
+        assert r["LDS Size [bytes/block]"] == lds and r["Occupancy [waves/SIMD]"] == occupancy, (needle, r)
