@@ -236,14 +236,50 @@ int32_t lram_score(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embe
  * d_model] embeddings exceed 2 GiB; the Mamba modes of lram_set_compat_mode (mamba_repeat > 1; stale_state, where a reset
  * re-initialises layer 0 only and the padding would leak into layers >= 1); scratch for the n_b == 0 slots that would leave less
  * than 2 GiB of device memory free.
- * Out of scope: a SHORTER context that CONTINUES a slot's state (needs length-aware state kernels); stored contexts on a subset
+ * Out of scope: stored contexts on a subset
  * of slots without computing the other rows (kept slots are saved and restored, not skipped; env-STEPS on a live prefix of the
  * slots are lram_set_live's, below, and these entries are refused while slots are parked); image frames as stored contexts; the
- * Mamba reference-trajectory modes.  The dense entries, the lazy step path and the GEMM dispatcher are unchanged. */
+ * Mamba reference-trajectory modes.  The dense entries, the lazy step path and the GEMM dispatcher are unchanged.  (A shorter
+ * context that CONTINUES a slot's state is lram_prefill_append / lram_score_append, below.) */
 int32_t lram_prefill_ragged(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
                             const float* dev_reward_seq, int32_t timesteps, const int32_t* host_lengths,
                             const uint8_t* dev_reset_mask, int32_t discrete, float* dev_actions, int32_t* dev_tokens, void* stream);
 int32_t lram_score_ragged(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
+                          const float* dev_reward_seq, int32_t timesteps, const int32_t* host_lengths,
+                          const uint8_t* dev_reset_mask, int32_t discrete, const float* dev_target_actions,
+                          const int32_t* dev_target_tokens, const uint8_t* dev_valid, int32_t over, double temperature,
+                          float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits, void* stream);
+
+/* Stored contexts of per-env length that are APPENDED to the state a slot holds: the ragged entries above, except that a context
+ * continues the slot's state instead of replacing it -- an in-context evaluation continued by a demonstration of per-env
+ * length, envs at different points of their episodes fed the steps they missed, a trajectory longer than one call can hold
+ * scored window by window (window k: lengths clamp(n_b - k W, 0, W), the mask on window 0 only).
+ *   inputs, outputs, host_lengths   as in the ragged entries: [batch, timesteps, ...] LEFT-aligned, host int32 lengths in
+ *                     0 .. timesteps; rows [b, n_b .. timesteps) are never read (raw observations: the state Linear runs over all
+ *                     rows and the padded result rows are never read) and may hold anything, NaN included
+ *   n_b > 0           env b's n_b timesteps are appended to the state the slot holds; dev_reset_mask[b] != 0 restarts it before
+ *                     its first timestep, whatever n_b is; a NULL mask restarts nobody
+ *   n_b == 0          the slot's state afterwards equals its state before the call bit for bit (pending lazy windows are folded
+ *                     first, as by every stored-context call); rows [b, *] of the inputs are never read, its dev_actions /
+ *                     dev_tokens row holds 0.0f / -1, its score rows are masked.  No record is saved or loaded and no scratch is
+ *                     allocated for such slots: there is no "less than 2 GiB free" refusal on these entries
+ *   dev_actions / dev_tokens, the score rows, sampling, lazy mode   as the ragged entries
+ * How: the chunk plan is the ragged entries' (lram_context_plan).  In every chunk that starts before s_b = timesteps - n_b env b is
+ * HELD: the engine hands the state-writing kernels a per-env flag under which they write no byte of the env's recurrent state
+ * (matrix memory, normaliser, stabiliser and conv state of an mLSTM block; cell and conv state of an sLSTM block; SSM and conv
+ * state of a Mamba layer) and ignore its reset flag; its activation rows are computed on zero tokens and never read.  The flag
+ * is a compile-time switch of those kernels: a chunk without a held env -- and every other entry of this header -- launches the
+ * instances without it.  With every n_b == timesteps the call makes the launches of lram_prefill / lram_score: outputs and state
+ * are bit-identical.  Env b's state afterwards is what n_b lram_step calls from its state before leave, up to fp32 rounding.
+ * Refused (message in lram_last_error, nothing launched, state untouched): what the ragged entries refuse, except the scratch
+ * rule -- a length outside 0 .. timesteps; all lengths 0; tokens_per_step != 3; d_model % 4 != 0; raw observations whose
+ * [batch, timesteps, d_model] embeddings exceed 2 GiB; both Mamba modes of lram_set_compat_mode; parked slots (lram_set_live).
+ * Out of scope: skipping the held envs' rows in the projections (hold stops state writes and, where it is free, state reads);
+ * stored contexts while slots are parked; image frames; the Mamba reference-trajectory modes. */
+int32_t lram_prefill_append(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
+                            const float* dev_reward_seq, int32_t timesteps, const int32_t* host_lengths,
+                            const uint8_t* dev_reset_mask, int32_t discrete, float* dev_actions, int32_t* dev_tokens, void* stream);
+int32_t lram_score_append(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
                           const float* dev_reward_seq, int32_t timesteps, const int32_t* host_lengths,
                           const uint8_t* dev_reset_mask, int32_t discrete, const float* dev_target_actions,
                           const int32_t* dev_target_tokens, const uint8_t* dev_valid, int32_t over, double temperature,
@@ -395,7 +431,7 @@ int32_t lram_state_load_slots(lram_engine* e, const int32_t* host_slots, int32_t
  *     stay true; afterwards every parked window is empty and no fold is launched over them); one small launch per mLSTM block
  *     and step carries the parked slots' bookkeeping over to the step's ping-pong side.  A parked slot's record (lram_state_save_slots) stays within the fold's rounding in C
  *     and bit-identical in every other tensor.
- *   - Refused (message in lram_last_error, nothing launched): lram_prefill, lram_score, their ragged forms, lram_encoder_step.
+ *   - Refused (message in lram_last_error, nothing launched): lram_prefill, lram_score, their ragged and append forms, lram_encoder_step.
  *   - Unchanged, on all `batch` slots: lram_state_export / import, lram_state_copy_slots / save / load / swap, lram_lazy_peek,
  *     lram_reset, lram_set_slot_table, lram_set_sampling_slots.
  *

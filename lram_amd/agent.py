@@ -27,7 +27,7 @@ from typing import Dict, Optional
 import torch
 
 from .config import ModelSpec
-from .engine import Engine, check_context_lengths
+from .engine import Engine, ScoreResult, check_context_lengths
 from .rollout import SlotScheduler
 
 
@@ -499,7 +499,8 @@ class RecurrentAgent:
     def score_trajectories(self, observations: torch.Tensor, returns_to_go: torch.Tensor,
                            rewards: Optional[torch.Tensor] = None, actions: Optional[torch.Tensor] = None,
                            lengths: Optional[torch.Tensor] = None, reset: bool = True, over: str = "vocab",
-                           temperature: float = 1.0, want=("actions", "tokens", "logp"), logits: bool = False):
+                           temperature: float = 1.0, want=("actions", "tokens", "logp"), logits: bool = False,
+                           window: Optional[int] = None):
         """Grade stored trajectories (Engine.score): observations [B, L, obs_dim] -- padded and normalised with state_mean /
         state_std as predict_batch does -- returns_to_go [B, L] in model units, rewards [B, L] (None: the reference loop's
         zero reward token), recorded `actions` [B, L, n] (float; n <= act_dim, padded with zeros; a discrete agent's action
@@ -509,7 +510,13 @@ class RecurrentAgent:
         length 0 keeps the state it had).  reset=True starts every env from an empty context; a length in 1 .. L - 1 always does,
         so reset=False together with such a length raises ValueError.  Returns the ScoreResult (per-timestep greedy actions / tokens and the log-probability of the recorded
         actions); rollout.score_loss turns it into the reference's loss.  With a slot table every slot is scored with its
-        own head; image observations are not taken here (embed them and call Engine.score with obs_is_embedding)."""
+        own head; image observations are not taken here (embed them and call Engine.score with obs_is_embedding).
+        `window=W` with W < L scores the trajectories in ceil(max(lengths) / W) calls (Engine.score(append=True)): call k covers
+        rows [k W, (k + 1) W) with the lengths clamp(lengths[b] - k W, 0, W), every call continuing the state the one before left;
+        `reset` is honoured on call 0 only.  The result is one ScoreResult of the full [B, L, ...] shape and the state afterwards
+        that of each env's own timesteps, as for the single call (up to fp32 rounding: the chunks differ); the engine embeds
+        B x W raw observations per call instead of B x L, which lifts the single call's 2 GiB bound.  Appended contexts never
+        replace a state, so reset=False with shorter lengths is accepted here.  window=None (or W >= L): the single call."""
         B = self.n_envs
         if observations.dim() != 3 or observations.shape[0] != B:
             raise ValueError(f"observations: expected [{B}, L, obs_dim], got {tuple(observations.shape)}")
@@ -526,16 +533,73 @@ class RecurrentAgent:
                 raise ValueError(f"actions: {a.shape[-1]} action dims exceed max_act_dim {self.spec.act_dim}")
             target = torch.zeros(B, L, self.spec.act_dim, dtype=torch.float32, device=self.device)
             target[..., : a.shape[-1]] = a
+        if window is not None and int(window) < 1:
+            raise ValueError(f"score_trajectories: window must be >= 1, got {window}")
+        windowed = window is not None and int(window) < L
         if lengths is not None:
             lengths = check_context_lengths(torch.as_tensor(lengths).reshape(-1), B, L)
-            if not reset and any(0 < n < L for n in lengths):
+            if not windowed and not reset and any(0 < n < L for n in lengths):
                 raise ValueError("score_trajectories: a context shorter than L replaces the env's state; reset=False cannot "
                                  "be combined with a length in 1 .. L - 1")
         mask = torch.ones(B, dtype=torch.uint8, device=self.device) if reset else None
         want = tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "logp" or target is not None)
         discrete = "per_slot" if getattr(self, "slot_table", None) is not None else self.is_discrete
-        return self.engine.score(obs, rtg, rew, actions=target, reset_mask=mask, discrete=discrete, over=over,
-                                 temperature=temperature, want=want, logits=logits, lengths=lengths)
+        if not windowed:
+            return self.engine.score(obs, rtg, rew, actions=target, reset_mask=mask, discrete=discrete, over=over,
+                                     temperature=temperature, want=want, logits=logits, lengths=lengths)
+        W = int(window)
+        n_all = [L] * B if lengths is None else list(lengths)
+        A = self.spec.act_dim
+        # the fill values of masked rows: what no window covers keeps them
+        out = ScoreResult(
+            actions=torch.zeros(B, L, A, dtype=torch.float32, device=self.device) if "actions" in want else None,
+            tokens=torch.full((B, L, A), -1, dtype=torch.int32, device=self.device) if "tokens" in want else None,
+            logp=torch.zeros(B, L, A, dtype=torch.float32, device=self.device) if "logp" in want else None,
+            logits=torch.zeros(B, L, A, self.spec.n_vocab, dtype=torch.float32, device=self.device) if logits else None)
+        for k in range(-(-max(n_all) // W)):
+            lo, hi = k * W, min((k + 1) * W, L)
+            part = self.engine.score(obs[:, lo:hi].contiguous(), rtg[:, lo:hi].contiguous(), rew[:, lo:hi].contiguous(),
+                                     actions=None if target is None else target[:, lo:hi].contiguous(),
+                                     reset_mask=mask if k == 0 else None, discrete=discrete, over=over, temperature=temperature,
+                                     want=want, logits=logits, lengths=[min(max(n - lo, 0), hi - lo) for n in n_all], append=True)
+            for name in ScoreResult.__slots__:
+                if getattr(out, name) is not None:
+                    getattr(out, name)[:, lo:hi] = getattr(part, name)
+        return out
+
+    @torch.no_grad()
+    def extend_contexts(self, observations: torch.Tensor, returns_to_go: torch.Tensor,
+                        rewards: Optional[torch.Tensor] = None, lengths=None, restart=None, want_action: bool = False):
+        """Append to every env's state a stored context of its own length in one call (Engine.prefill(lengths=..., append=True)),
+        after which predict_batch continues: the steps envs at different points of their episodes missed, or a demonstration
+        that continues an in-context evaluation (persist_context).  observations [B, L, obs_dim] -- native, padded and normalised
+        as prime_contexts does -- returns_to_go [B, L], rewards [B, L] (None: zeros), `lengths` [B]: env b takes its first
+        lengths[b] timesteps (None = all L); an env of length 0 keeps its state bit for bit.  `restart` [B] bool (None: nobody):
+        the envs that start from an empty state before their first timestep.  want_action=True returns the action at each env's
+        own last timestep (as predict_batch returns it; 0 for an env of length 0), else None."""
+        B = self.n_envs
+        if observations.dim() != 3 or observations.shape[0] != B:
+            raise ValueError(f"observations: expected [{B}, L, obs_dim], got {tuple(observations.shape)}")
+        L = observations.shape[1]
+        if lengths is not None:
+            lengths = check_context_lengths(torch.as_tensor(lengths).reshape(-1), B, L)
+        obs, _ = self._prepare_obs(observations.reshape(B * L, -1))
+        obs = obs.view(B, L, -1).contiguous()
+        rtg = returns_to_go.to(self.device, torch.float32).reshape(B, L).contiguous()
+        rew = torch.zeros(B, L, dtype=torch.float32, device=self.device) if rewards is None else \
+            rewards.to(self.device, torch.float32).reshape(B, L).contiguous()
+        mask = None
+        if restart is not None:
+            mask = torch.as_tensor(restart).reshape(-1)
+            if mask.shape[0] != B:
+                raise ValueError(f"restart: expected {B} entries (one per env), got {mask.shape[0]}")
+            mask = (mask != 0).to(self.device, torch.uint8).contiguous()
+        discrete = "per_slot" if getattr(self, "slot_table", None) is not None else self.is_discrete
+        actions, _ = self.engine.prefill(obs, rtg, rew, reset_mask=mask, discrete=discrete, want_action=want_action,
+                                         lengths=lengths, append=True)
+        if not want_action:
+            return None
+        return actions[:, :1].to(torch.int64) if self.is_discrete else actions
 
     @torch.no_grad()
     def prime_contexts(self, observations: torch.Tensor, returns_to_go: torch.Tensor,

@@ -308,6 +308,11 @@ void launch_embed_chunk_ragged(float* x, const float* emb, int64_t emb_stride, c
 // (start[b] == chunk_start[c], 0 < start[b] < L); a full-length env (start[b] == 0) takes reset[b] (nullable) on chunk 0.
 void launch_context_masks(uint8_t* mask, const int32_t* start, const int32_t* chunk_start, const uint8_t* reset, int n_chunks,
                           int B, int L, hipStream_t stream);
+// The append entries' rows (lram_prefill_append / lram_score_append): hold[c][b] = 1 where env b has not started by chunk c
+// (start[b] > chunk_start[c]: the state kernels write nothing of it), mask[c][b] = 1 where it starts at chunk c and the caller's
+// reset[b] (nullable) is set -- an env continues its state unless the caller restarts it.
+void launch_context_append_masks(uint8_t* hold, uint8_t* mask, const int32_t* start, const int32_t* chunk_start, const uint8_t* reset,
+                                 int n_chunks, int B, int L, hipStream_t stream);
 // fill values (logp 0, token -1, action 0) into the padded rows [b, L - start[b] + t], t = 0 .. steps - 1, of [B, L, act_dim]
 // tensors (each nullable): the call-timesteps ahead of the first chunk, which no score launch covers
 void launch_score_fill_ragged(float* actions, int32_t* tokens, float* logp, const int32_t* start, int B, int L, int steps,
@@ -344,6 +349,7 @@ struct MlstmPreArgs {
   float* gates = nullptr;  // [B*T, NH, 2] out  raw (i~, f~) gate pre-activations
   float* amat = nullptr;   // [B, NH, 64, 64] out  intra-chunk weights A[t][s]
   float* vec = nullptr;    // [B, NH, 3, 64] out   fcum_t | w_s | denom_t
+  const uint8_t* hold = nullptr;  // [B] or null: envs that take no token in this launch (no state byte written, reset ignored)
 };
 void launch_mlstm_pre(const MlstmPreArgs& a, hipStream_t stream);
 
@@ -387,6 +393,7 @@ struct MlstmCellArgs {
   const float* amat = nullptr;  // chunkwise prefill only (written by launch_mlstm_chunk_pre)
   const float* vec = nullptr;
   int chunk_exact_fp32 = 0;     // chunkwise cell on the fp32-input matrix cores (LRAM_CHUNK_CELL=0) instead of the bf16x3 form
+  const uint8_t* hold = nullptr;  // [B] or null: envs that take no token in this launch (no state byte written, reset ignored)
 };
 void launch_mlstm_cell(const MlstmCellArgs& a, hipStream_t stream);
 void launch_mlstm_chunk_cell(const MlstmCellArgs& a, hipStream_t stream);
@@ -537,6 +544,7 @@ struct SlstmConvArgs {
   const uint8_t* reset;
   int B, T, D, K;
   int state_B;          // env count of the full state tensor (stride of its leading [4] axis)
+  const uint8_t* hold = nullptr;  // [B] or null: envs that take no token in this launch (no state byte written, reset ignored)
 };
 void launch_slstm_conv(const SlstmConvArgs& a, hipStream_t stream);
 
@@ -548,6 +556,7 @@ struct SlstmPointwiseArgs {
   float* yout;         // [B*T, H]  y written at row b*T + t
   int B, T, t, H;
   int state_B;         // env count of the full state tensor
+  const uint8_t* hold = nullptr;  // [B] or null: envs that take no token in this launch (no state byte written, reset ignored)
 };
 void launch_slstm_pointwise(const SlstmPointwiseArgs& a, hipStream_t stream);
 
@@ -561,6 +570,7 @@ struct SlstmTokenArgs {
   float* state;        // [4, state_B, H] in/out (h plane written only when write_h)
   float* yout;         // [B*T, H]
   int B, T, t, H, NH, state_B, write_h;
+  const uint8_t* hold = nullptr;  // [B] or null: envs that take no token in this launch (no state byte written, reset ignored)
 };
 bool slstm_token_supported(int H, int NH);
 void launch_slstm_token(const SlstmTokenArgs& a, hipStream_t stream);
@@ -575,6 +585,7 @@ struct SlstmSeqArgs {
   float* state = nullptr;        // [4, state_B, H] in/out (h, c, n, m planes)
   float* yout = nullptr;         // [B*T, H]
   int B = 0, T = 0, H = 0, NH = 0, state_B = 0;
+  const uint8_t* hold = nullptr;  // [B] or null: envs that take no token in this launch (no state byte written, reset ignored)
 };
 void launch_slstm_h_range(const float* h, int64_t n, float limit, int* flag, hipStream_t stream);  // flag |= any element outside (-limit, limit), NaN included
 bool slstm_seq_supported(int H, int NH, int T);
@@ -597,6 +608,7 @@ struct MambaConvArgs {
   const uint8_t* reset;
   int B, T, d_inner, K;
   float* amax = nullptr;  // optional [B*T][d_inner / 64]: per-wave partial row maxima of xc (f16x2 GEMM's a_amax)
+  const uint8_t* hold = nullptr;  // [B] or null: envs that take no token in this launch (no state byte written, reset ignored)
 };
 void launch_mamba_conv(const MambaConvArgs& a, hipStream_t stream);
 
@@ -614,6 +626,7 @@ struct MambaSsmArgs {
   int B, T, d_inner, N, R;
   float* amax = nullptr;    // optional [B*T][d_inner / 64]: per-64-channel partial row maxima of y (f16x2 GEMM's a_amax)
   const float* dt_wt = nullptr;  // optional dt_proj.weight TRANSPOSED [R, d_inner]: dt_proj evaluated inside the kernel, dtp unused
+  const uint8_t* hold = nullptr;  // [B] or null: envs that take no token in this launch (no state byte written, reset ignored)
 };
 inline bool mamba_ssm_dt_fusable(int N, int R) { return N == 16 && R >= 1 && R <= 128; }
 void launch_transpose_f32(const float* src, int rows, int cols, float* dst, hipStream_t stream);

@@ -1,4 +1,4 @@
-// Stored contexts of per-env length (lram_prefill_ragged / lram_score_ragged): the kernels that stand between the caller's
+// Stored contexts of per-env length (lram_prefill_ragged / lram_score_ragged, and their append forms): the kernels that stand between the caller's
 // left-aligned [B, L, ...] tensors and a call whose contexts are END-aligned -- env b's context of n_b timesteps occupies the
 // call-timesteps start[b] = L - n_b .. L - 1.  No recurrent kernel knows about lengths: these kernels feed them zero tokens ahead
 // of an env's context, build the per-chunk reset masks that empty the env's state at its first timestep, and put the head's
@@ -8,7 +8,7 @@
 // forward (src/algos/universal_decision_transformer_sb3.py:398-434) and the per-env context windows of the evaluation loop
 // (src/algos/decision_transformer_sb3.py:628-666), here for a recurrent state.
 //
-// All four kernels move a few bytes per (env, timestep): one thread per 4 channels (float4) or per output element; the only
+// All five kernels move a few bytes per (env, timestep): one thread per 4 channels (float4) or per output element; the only
 // branch, t < start[b], is taken per (env, timestep) row.
 #include "common.h"
 
@@ -56,6 +56,20 @@ __global__ __launch_bounds__(256) void context_masks_kernel(uint8_t* mask, const
   mask[gid] = m;
 }
 
+// The append entries' two rows per chunk (lram_prefill_append / lram_score_append): an env that has not started yet is HELD -- the
+// state kernels write nothing of it (device_math.h: env_held) -- and an env restarts at its own first timestep only where the
+// caller's mask says so.  start[b] == L (no context) is held in every chunk; a held env is never reset in the same chunk.
+__global__ __launch_bounds__(256) void context_append_masks_kernel(uint8_t* hold, uint8_t* mask, const int32_t* start,
+                                                                   const int32_t* chunk_start, const uint8_t* reset, int n_chunks,
+                                                                   int B, int L) {
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (int64_t)n_chunks * B) return;
+  const int c = (int)(gid / B), b = (int)(gid - (int64_t)c * B);
+  const int s = start[b], cs = chunk_start[c];
+  hold[gid] = s > cs ? 1 : 0;
+  mask[gid] = (s == cs && s < L && reset != nullptr && reset[b] != 0) ? 1 : 0;
+}
+
 __global__ __launch_bounds__(256) void score_fill_ragged_kernel(float* actions, int32_t* tokens, float* logp, const int32_t* start,
                                                                 int B, int L, int steps, int act_dim) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -101,6 +115,15 @@ void launch_context_masks(uint8_t* mask, const int32_t* start, const int32_t* ch
   const int64_t n = (int64_t)n_chunks * B;
   hipLaunchKernelGGL(context_masks_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, mask, start, chunk_start,
                      reset, n_chunks, B, L);
+  LRAM_HIP_CHECK(hipGetLastError());
+}
+
+void launch_context_append_masks(uint8_t* hold, uint8_t* mask, const int32_t* start, const int32_t* chunk_start, const uint8_t* reset,
+                                 int n_chunks, int B, int L, hipStream_t stream) {
+  LRAM_REQUIRE(hold && mask && start && chunk_start && n_chunks >= 1 && B >= 1 && L >= 1, "context append masks: bad argument");
+  const int64_t n = (int64_t)n_chunks * B;
+  hipLaunchKernelGGL(context_append_masks_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, hold, mask, start,
+                     chunk_start, reset, n_chunks, B, L);
   LRAM_HIP_CHECK(hipGetLastError());
 }
 

@@ -65,6 +65,18 @@ __device__ __forceinline__ float softplus_hw(float x) {
 // exact (erf) GELU, torch.nn.functional.gelu default
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
 
+// The hold rule of the stored-context path (lram_prefill_append / lram_score_append): env b takes no token in this launch, so the
+// launch writes no byte of its recurrent state and ignores its reset flag.  HOLD is a compile-time switch: the instances every
+// other call launches (HOLD = false) contain nothing of it.  The flag is read through a pointer select (`other` = any readable
+// address of the launch), never under a branch on `hold`: no state request of the workgroup waits for it.
+template <bool HOLD>
+__device__ __forceinline__ bool env_held(const uint8_t* hold, int64_t b, const void* other) {
+  if (!HOLD) return false;
+  const uint8_t* hp = hold != nullptr ? hold + b : reinterpret_cast<const uint8_t*>(other);
+  const uint8_t hb = *hp;
+  return hold != nullptr && hb != 0;
+}
+
 __device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
 __device__ __forceinline__ float dot4(const float4& x, const float4& y) { return x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w; }

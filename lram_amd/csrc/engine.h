@@ -246,7 +246,8 @@ struct lram_engine {
   // Stored contexts of per-env length (lram_prefill_ragged / lram_score_ragged): CTX holds, as bytes of one allocation, int32
   // start[B] (call-timestep at which each env's context begins), int32 chunk_start[L] and the per-chunk reset masks
   // uint8[n_chunks, B]; KEEP the state records of the slots the call leaves alone (length 0), saved ahead of the first chunk
-  // and loaded back behind the last.  Both grown outside the launches, as SEQ_EMB is.
+  // and loaded back behind the last.  Both grown outside the launches, as SEQ_EMB is.  The append entries (lram_prefill_append /
+  // lram_score_append) put the per-chunk hold flags uint8[n_chunks, B] behind the reset masks and never touch KEEP.
   DevBuf CTX, KEEP;
   // lram_score: the head's logits for a block of (env, timestep) rows of one chunk, one region per chunk lane / env slice in
   // flight.  A region holds at most score_rows rows of act_dim * n_vocab floats (default 4096 rows: 34 MiB at 8 x 274 logits;
@@ -439,6 +440,10 @@ struct Pass {
   const std::vector<hipEvent_t>* lane_wait = nullptr;
   const std::vector<hipEvent_t>* lane_rec = nullptr;
   int n_slices = 1;                  // env slices of the stack pass under way (set by run_stack)
+  // hold flags of a stored-context chunk (lram_prefill_append / lram_score_append), engine-owned: device [B] or null, offset by a
+  // slice's b0 as the reset mask is.  hold[b] != 0: env b takes no token in this pass -- no state-writing kernel writes a byte of
+  // its recurrent state, and its reset flag is ignored.  Null (every other call): the kernels' instances without the rule.
+  const uint8_t* hold = nullptr;
 };
 
 // Per-timestep sink of a stored context (lram_score): where the head's outputs of EVERY timestep go.  Tensors are [B, L, act_dim]

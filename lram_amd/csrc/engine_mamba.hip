@@ -54,12 +54,14 @@ void mamba_stage(lram_engine* e, const Pass& pass, int i, int stage, int T, cons
     const bool xp_narrow32 = e->gemm_narrow_on && rows >= e->gemm_narrow_min_rows && e->narrow.count(w.x_proj) != 0 &&
                              !(e->use_f16x2 && e->gemm_narrow_f16);
     ca.reset = rs, ca.B = sl.nb, ca.T = T, ca.d_inner = di, ca.K = c.d_conv, ca.amax = xp_narrow32 ? nullptr : amx_xa;
+    ca.hold = pass.hold ? pass.hold + b0 : nullptr;   // (a stored-context chunk with a held env)
     launch_mamba_conv(ca, sl.s);
   } else {
     MambaSsmArgs sa;
     sa.ssm_state = st.s0.p + b0 * di * N, sa.xc = XA, sa.dtp = DTP, sa.dt_bias = w.dt_bias, sa.xdb = Q;
     sa.A_log = w.A_log, sa.Dp = w.Dp, sa.xz = U, sa.y = H, sa.reset = rs;
     sa.B = sl.nb, sa.T = T, sa.d_inner = di, sa.N = N, sa.R = R, sa.amax = amx_h;
+    sa.hold = pass.hold ? pass.hold + b0 : nullptr;
     if (dt_fused) sa.dt_wt = e->dt_wt[i].p, sa.dtp = nullptr;
     prof_record(e, sl.s, true);
     launch_mamba_ssm(sa, sl.s);

@@ -121,6 +121,9 @@ struct ContextPlan {
   std::vector<char> has_reset;    // per chunk: some env is reset at its start (others pass no mask at all, as a dense call does)
   const int32_t* dev_start = nullptr;   // [B]
   const uint8_t* dev_masks = nullptr;   // [n_chunks, B]
+  // the append entries (lram_prefill_append / lram_score_append): per chunk, some env has not started yet and is held (Pass::hold)
+  std::vector<char> has_hold;
+  const uint8_t* dev_hold = nullptr;    // [n_chunks, B]
 };
 
 // Token front end of one env slice for the chunk of Lc timesteps that starts at timestep l: embeds the chunk's tokens into the
@@ -392,6 +395,8 @@ void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, cons
     if (lanes) pass.lane_wait = ci > 0 ? &e->lane_ev[(lane + 1) % NL] : nullptr, pass.lane_rec = &e->lane_ev[lane];
     const uint8_t* chunk_reset = l == 0 ? reset : nullptr;
     if (plan != nullptr) chunk_reset = plan->has_reset[ci] ? plan->dev_masks + (size_t)ci * e->B : nullptr;
+    // (a chunk without a held env passes no hold pointer: it launches what a dense call launches)
+    if (plan != nullptr && plan->dev_hold != nullptr && plan->has_hold[ci]) pass.hold = plan->dev_hold + (size_t)ci * e->B;
     run_stack(e, pass, Tc, chunk_reset, use, lanes ? lane_s[lane] : hbm);
     if (sink != nullptr && L > 1)
       for (size_t i = 0; i < use.size(); ++i)
@@ -548,12 +553,16 @@ std::vector<int> context_plan(int L, int cap, const int32_t* lengths, int B, con
 // What lram_prefill_ragged and lram_score_ragged share.  check(): everything that refuses the call, before anything is launched or
 // allocated.  run(): the save of the kept slots, the plan's device tables, the chunks (`launch` runs timesteps_launches with the
 // plan), the load of the kept slots.  A call whose lengths all equal `timesteps` never gets here: it is the dense entry's.
+// `append` (lram_prefill_append / lram_score_append): an env's context continues the state the slot holds.  An env that has not
+// started by a chunk is HELD in it (ContextPlan::dev_hold -> Pass::hold) instead of being fed padding and reset at its start, so
+// the slots of length 0 need no record saved and loaded back: KEEP is not touched and no memory is asked for.
 struct RaggedCall {
   lram_engine* e;
   std::string w;
   int L;
   const int32_t* lengths;
   std::vector<int32_t> kept;   // slots with length 0
+  bool append = false;
 
   void check(int obs_is_embedding) {
     const lram_config& c = e->cfg;
@@ -584,7 +593,7 @@ struct RaggedCall {
   void run(const uint8_t* reset, hipStream_t s, Launch&& launch) {
     const int B = e->B;
     // scratch for the kept slots' records: refused, with nothing launched, when it would leave less than 2 GiB free
-    const size_t rec = (size_t)(lram_state_bytes_per_env(e) / 4), need = kept.size() * rec;
+    const size_t rec = (size_t)(lram_state_bytes_per_env(e) / 4), need = append ? 0 : kept.size() * rec;
     if (e->KEEP.n < need) {
       LRAM_HIP_CHECK(hipDeviceSynchronize());
       size_t free_b = 0, total_b = 0;
@@ -597,8 +606,8 @@ struct RaggedCall {
     ContextPlan plan;
     plan.starts = context_plan(L, L > 1 ? prefill_chunk_steps(e, L) : 1, lengths, B, w.c_str());
     const int n_chunks = (int)plan.starts.size();
-    // CTX: int32 start[B] | int32 chunk_start[L] | uint8 masks[L, B], as floats of one allocation
-    const size_t want = (size_t)B + L + ((size_t)L * B + 3) / 4;
+    // CTX: int32 start[B] | int32 chunk_start[L] | uint8 masks[L, B] (| uint8 hold[L, B], append), as floats of one allocation
+    const size_t want = (size_t)B + L + ((size_t)(append ? 2 : 1) * L * B + 3) / 4;
     if (e->CTX.n < want) {
       LRAM_HIP_CHECK(hipDeviceSynchronize());
       e->CTX.alloc(want);
@@ -607,23 +616,35 @@ struct RaggedCall {
     int32_t* dev_chunk = dev_start + B;
     uint8_t* dev_masks = reinterpret_cast<uint8_t*>(dev_chunk + L);
     plan.dev_start = dev_start, plan.dev_masks = dev_masks;
+    uint8_t* dev_hold = append ? dev_masks + (size_t)L * B : nullptr;
+    plan.dev_hold = dev_hold;
     std::vector<int32_t> host(B + n_chunks);
     plan.has_reset.assign(n_chunks, 0);
+    plan.has_hold.assign(n_chunks, 0);
     for (int b = 0; b < B; ++b) {
       const int sb = L - lengths[b];
       host[b] = sb;
+      // (every env with a context starts on a chunk boundary: the chunk it starts at)
+      const size_t at = sb < L ? std::lower_bound(plan.starts.begin(), plan.starts.end(), sb) - plan.starts.begin() : (size_t)n_chunks;
+      if (append) {   // restarted at its start only where the caller says so; held in every chunk before that one
+        if (sb < L && reset != nullptr) plan.has_reset[at] = 1;
+        for (size_t ci = 0; ci < at; ++ci) plan.has_hold[ci] = 1;
+        continue;
+      }
       if (sb == 0 && reset != nullptr) plan.has_reset[0] = 1;
-      if (sb > 0 && sb < L)
-        plan.has_reset[std::lower_bound(plan.starts.begin(), plan.starts.end(), sb) - plan.starts.begin()] = 1;
+      if (sb > 0 && sb < L) plan.has_reset[at] = 1;
     }
     for (int ci = 0; ci < n_chunks; ++ci) host[B + ci] = plan.starts[ci];
     // ---- from here on the call launches ----
     lazy_materialize(e, s);   // stored contexts fold pending windows first (and complete a tail fold)
-    if (!kept.empty()) save_slot_records(e, kept.data(), (int)kept.size(), e->KEEP.p, s);
+    if (!kept.empty() && !append) save_slot_records(e, kept.data(), (int)kept.size(), e->KEEP.p, s);
     // (pageable host memory: the copies have read `host` when they return; the device side is ordered on `s`)
     LRAM_HIP_CHECK(hipMemcpyAsync(dev_start, host.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
     LRAM_HIP_CHECK(hipMemcpyAsync(dev_chunk, host.data() + B, (size_t)n_chunks * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    launch_context_masks(dev_masks, dev_start, dev_chunk, reset, n_chunks, B, L, s);
+    if (append)
+      launch_context_append_masks(dev_hold, dev_masks, dev_start, dev_chunk, reset, n_chunks, B, L, s);
+    else
+      launch_context_masks(dev_masks, dev_start, dev_chunk, reset, n_chunks, B, L, s);
     {
       // every chunk on the materialised kernels, also the chunks of one timestep that an env-step would take through the lazy
       // read pass: a window left pending by a chunk in the middle of the call would be invisible to the chunk behind it
@@ -635,7 +656,7 @@ struct RaggedCall {
       e->lazy = false;
       launch(plan);
     }
-    if (!kept.empty()) load_slot_records(e, kept.data(), (int)kept.size(), e->KEEP.p, s);
+    if (!kept.empty() && !append) load_slot_records(e, kept.data(), (int)kept.size(), e->KEEP.p, s);
   }
 };
 }  // namespace
@@ -800,6 +821,64 @@ int32_t lram_score_ragged(lram_engine* e, const float* dev_obs_seq, int32_t obs_
     RaggedCall rc{e, "lram_score_ragged", timesteps, host_lengths, {}};
     rc.check(obs_is_embedding);
     const ScoreSink sink = score_sink_checked(e, "lram_score_ragged", discrete, dev_target_actions, dev_target_tokens, dev_valid, over,
+                                              temperature, dev_actions, dev_tokens, dev_logp, dev_logits);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Inputs in{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps};
+    if (rc.dense()) {            // every context of full length: lram_score's own launches
+      lazy_finish_prefold(e, s);   // (only an env-step takes a tail fold over)
+      timesteps_launches(e, Pass{}, in, dev_reset_mask, discrete, nullptr, nullptr, s, &sink);
+      return;
+    }
+    rc.run(dev_reset_mask, s, [&](const ContextPlan& plan) {
+      // the call-timesteps ahead of the first chunk are padding for every env: their rows take the fill values here
+      launch_score_fill_ragged(dev_actions, dev_tokens, dev_logp, plan.dev_start, e->B, timesteps, plan.starts[0], e->cfg.act_dim, s);
+      timesteps_launches(e, Pass{}, in, nullptr, discrete, nullptr, nullptr, s, &sink, &plan);
+    });
+  });
+}
+
+int32_t lram_prefill_append(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
+                            const float* dev_reward_seq, int32_t timesteps, const int32_t* host_lengths,
+                            const uint8_t* dev_reset_mask, int32_t discrete, float* dev_actions, int32_t* dev_tokens, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(e != nullptr, "lram_prefill_append: null engine");
+    step_entry(e, "lram_prefill_append");
+    require_all_live(e, "lram_prefill_append");
+    LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_prefill_append: null device pointer");
+    LRAM_REQUIRE(timesteps >= 1, "lram_prefill_append: timesteps must be >= 1");
+    RaggedCall rc{e, "lram_prefill_append", timesteps, host_lengths, {}, true};
+    rc.check(obs_is_embedding);
+    if (dev_actions != nullptr) check_head_mode(e, discrete, "lram_prefill_append");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Inputs in{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps};
+    if (rc.dense()) {            // every context of full length: lram_prefill's own launches
+      lazy_finish_prefold(e, s);   // (only an env-step takes a tail fold over)
+      timesteps_launches(e, Pass{}, in, dev_reset_mask, discrete, dev_actions, dev_tokens, s);
+    } else {
+      rc.run(dev_reset_mask, s, [&](const ContextPlan& plan) {
+        timesteps_launches(e, Pass{}, in, nullptr, discrete, dev_actions, dev_tokens, s, nullptr, &plan);
+        if (dev_actions != nullptr)   // slots without a context: 0 / -1 in place of the head's answer to the padding
+          launch_action_fill_kept(dev_actions, dev_tokens, plan.dev_start, e->B, timesteps, e->cfg.act_dim, s);
+      });
+    }
+    if (dev_actions != nullptr) sample_draw_advance(e, s);
+  });
+}
+
+int32_t lram_score_append(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
+                          const float* dev_reward_seq, int32_t timesteps, const int32_t* host_lengths,
+                          const uint8_t* dev_reset_mask, int32_t discrete, const float* dev_target_actions,
+                          const int32_t* dev_target_tokens, const uint8_t* dev_valid, int32_t over, double temperature,
+                          float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(e != nullptr, "lram_score_append: null engine");
+    step_entry(e, "lram_score_append");
+    require_all_live(e, "lram_score_append");
+    LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_score_append: null device pointer");
+    LRAM_REQUIRE(timesteps >= 1, "lram_score_append: timesteps must be >= 1");
+    RaggedCall rc{e, "lram_score_append", timesteps, host_lengths, {}, true};
+    rc.check(obs_is_embedding);
+    const ScoreSink sink = score_sink_checked(e, "lram_score_append", discrete, dev_target_actions, dev_target_tokens, dev_valid, over,
                                               temperature, dev_actions, dev_tokens, dev_logp, dev_logits);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Inputs in{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps};

@@ -182,6 +182,8 @@ void mlstm_front(lram_engine* e, const Pass& pass, int i, int T, const uint8_t* 
     fa.conv_w = w.conv_w, fa.conv_b = w.conv_b, fa.wq = w.wq, fa.wk = w.wk, fa.gc = e->gate_coef[i].p, fa.bi = w.bi, fa.bf = w.bf;
     fa.xa = e->XA.p + r0 * e->icols, fa.scal = e->SCAL.p + r0 * NH * 4, fa.reset = reset ? reset + b0 : nullptr;
     fa.B = sl.nb, fa.T = T, fa.inner = inner, fa.NH = NH, fa.K = c.conv_k;
+    // (the lean path belongs to the lazy read pass; stored contexts run materialised, so a held env never gets here)
+    LRAM_REQUIRE(pass.hold == nullptr, "mLSTM front end: the multi-env kernel has no hold rule (stored contexts run materialised)");
     launch_mlstm_front(fa, sl.s);
     return;
   }
@@ -193,6 +195,7 @@ void mlstm_front(lram_engine* e, const Pass& pass, int i, int T, const uint8_t* 
   pa.q = e->Q.p + r0 * e->icols, pa.k = e->K.p + r0 * e->icols, pa.v = e->V.p + r0 * e->icols;
   pa.xa = e->XA.p + r0 * e->icols;
   pa.scal = e->SCAL.p + r0 * NH * 4, pa.reset = reset ? reset + b0 : nullptr;
+  pa.hold = pass.hold ? pass.hold + b0 : nullptr;
   pa.B = sl.nb, pa.T = T, pa.inner = inner, pa.NH = NH, pa.K = c.conv_k;
   pa.lean = lean_front(e, T) ? 1 : 0;
   if (T > kMaxTokens) {
@@ -223,7 +226,7 @@ void mlstm_up_z(lram_engine* e, int i, int T, const Slice& sl) {
   gemm(e, up, sl.s);
 }
 
-void mlstm_cell(lram_engine* e, int i, int T, const uint8_t* reset, const Slice& sl, hipStream_t s) {
+void mlstm_cell(lram_engine* e, const Pass& pass, int i, int T, const uint8_t* reset, const Slice& sl, hipStream_t s) {
   const lram_config& c = e->cfg;
   const int inner = c.inner, NH = c.n_heads, DH = e->dh();
   const size_t r0 = (size_t)sl.b0 * T, b0 = sl.b0;
@@ -231,6 +234,7 @@ void mlstm_cell(lram_engine* e, int i, int T, const uint8_t* reset, const Slice&
   ca.C = e->st[i].s0.p + b0 * NH * DH * DH, ca.q = e->Q.p + r0 * e->icols, ca.k = e->K.p + r0 * e->icols;
   ca.v = e->V.p + r0 * e->icols, ca.scal = e->SCAL.p + r0 * NH * 4, ca.h = e->H.p + r0 * e->icols;
   ca.reset = reset ? reset + b0 : nullptr, ca.B = sl.nb, ca.T = T, ca.NH = NH, ca.DH = DH;
+  ca.hold = pass.hold ? pass.hold + b0 : nullptr;
   // Large launches: one cell workgroup per CU (84 KB of LDS each; a second one does not fit, two 37 KB GEMM
   // workgroups of the other slice do).  Measured on MI355X at B=4096/16M: 1.61 ms -> 1.47 ms per launch
   // (5.5 -> 6.0 TB/s) standalone; see DESIGN.md section 6.
@@ -312,7 +316,7 @@ bool slstm_gates_one_bf16x3(const lram_engine* e, GemmArgs& g4, const BlockWeigh
   return gemm_bf16x3_supported(g4) && !gemm_small_m(g4);
 }
 
-void slstm_block(lram_engine* e, int i, int T, const uint8_t* reset, const Slice& sl) {
+void slstm_block(lram_engine* e, const Pass& pass, int i, int T, const uint8_t* reset, const Slice& sl) {
   const lram_config& c = e->cfg;
   const int D = c.d_model, NH = c.n_heads, SDH = e->sdh(), F = c.ffn_dim, Hs = D, rows = sl.nb * T;
   const size_t r0 = (size_t)sl.b0 * T, b0 = sl.b0;
@@ -328,11 +332,12 @@ void slstm_block(lram_engine* e, int i, int T, const uint8_t* reset, const Slice
   float* Ubuf = e->U.p + r0 * e->ucols;
   float* Gbuf = e->G.p + r0 * e->icols;
   float* state = st.s0.p + b0 * Hs;      // [4, B, H] viewed from env b0 (leading-axis stride e->B * H)
+  const uint8_t* hold = pass.hold ? pass.hold + b0 : nullptr;   // (a stored-context chunk with a held env)
   launch_row_norm(X, D, XN, D, w.norm_g, w.norm_b, rows, D, c.ln_eps, c.norm_is_rms, s);
   SlstmConvArgs sa;
   sa.xn = XN, sa.conv_state = st.conv.p + b0 * c.conv_k * D, sa.slstm_state = state, sa.conv_w = w.conv_w;
   sa.conv_b = w.conv_b, sa.xc = XC, sa.reset = reset ? reset + b0 : nullptr, sa.B = sl.nb, sa.T = T, sa.D = D;
-  sa.K = c.conv_k, sa.state_B = e->B;
+  sa.K = c.conv_k, sa.state_B = e->B, sa.hold = hold;
   launch_slstm_conv(sa, s);
   GemmArgs g4;  // few rows: the four gate projections (per-head blocks, i / f on the conv branch, z / o on the norm) as ONE launch
   g4.a = XC, g4.lda = D, g4.sA1 = SDH, g4.w = w.gate_w[0], g4.ldw = SDH, g4.sW1 = (int64_t)SDH * SDH;
@@ -375,9 +380,12 @@ void slstm_block(lram_engine* e, int i, int T, const uint8_t* reset, const Slice
     ta.gates = gates, ta.rt = w.rt, ta.bias = w.rbias, ta.state = state, ta.yout = Y;
     ta.hprev = t == 0 ? state : Y + (int64_t)(t - 1) * Hs, ta.hprev_ld = t == 0 ? Hs : (int64_t)T * Hs;
     ta.B = sl.nb, ta.T = T, ta.t = t, ta.H = Hs, ta.NH = NH, ta.state_B = e->B, ta.write_h = (t == T - 1 && t > 0) ? 1 : 0;
+    ta.hold = hold;
     launch_slstm_token(ta, s);
     ++e->slstm_counts[0];
   }
+  // (a one-token pass copies the h plane of every env: a stored-context chunk, the only pass with held envs, holds whole timesteps)
+  LRAM_REQUIRE(hold == nullptr || T >= 3, "sLSTM block: held envs need whole timesteps of three tokens");
   if (tok_fused && T == 1)  // the single launch read the state's h plane: it is refreshed from the output rows afterwards
     LRAM_HIP_CHECK(hipMemcpyAsync(state, Y, (size_t)sl.nb * Hs * sizeof(float), hipMemcpyDeviceToDevice, s));
   // slices beyond the token kernel's: the whole step's recurrence as ONE launch (head dim 128; slstm_seq.hip)
@@ -389,7 +397,7 @@ void slstm_block(lram_engine* e, int i, int T, const uint8_t* reset, const Slice
       qa.rt2h = reinterpret_cast<const uint16_t*>(e->slstm_rt2[i].p), qa.rinv = e->slstm_rinv[i].p;
     else
       qa.rt2 = e->slstm_rt2[i].p;
-    qa.B = sl.nb, qa.T = T, qa.H = Hs, qa.NH = NH, qa.state_B = e->B;
+    qa.B = sl.nb, qa.T = T, qa.H = Hs, qa.NH = NH, qa.state_B = e->B, qa.hold = hold;
     launch_slstm_seq(qa, s);
     ++e->slstm_counts[1];
   }
@@ -402,7 +410,7 @@ void slstm_block(lram_engine* e, int i, int T, const uint8_t* reset, const Slice
     gemm(e, ra, s);
     SlstmPointwiseArgs pw;
     pw.gates = gates, pw.ry = RY, pw.bias = w.rbias, pw.state = state, pw.yout = Y;
-    pw.B = sl.nb, pw.T = T, pw.t = t, pw.H = Hs, pw.state_B = e->B;
+    pw.B = sl.nb, pw.T = T, pw.t = t, pw.H = Hs, pw.state_B = e->B, pw.hold = hold;
     launch_slstm_pointwise(pw, s);
     ++e->slstm_counts[2];
   }
@@ -442,6 +450,7 @@ void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* res
   const lram_config& c = e->cfg;
   const int D = c.d_model;
   const bool lazy = lazy_active(e, T);
+  LRAM_REQUIRE(!(lazy && pass.hold != nullptr), "xLSTM stack: the lazy kernels have no hold rule (stored contexts run materialised)");
   // Tail fold of the step before (lram_engine::prefold): this step is the one it was launched for when nothing came in between (every
   // other entry completes it), the period and the batch are the same, there are still two slices and this step's folds take the
   // compact grid.  Then the pre-folded blocks count as folded: their read passes see the due envs as lazy_view_of reports them --
@@ -548,7 +557,7 @@ void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* res
         for (int k = next_mlstm(i); k >= 0 && take > 0; k = next_mlstm(k))
           if (!folded[k]) launch_folds(k), --take;
       }
-      for (const Slice& x : sl) slstm_block(e, i, T, reset, x);
+      for (const Slice& x : sl) slstm_block(e, pass, i, T, reset, x);
       continue;
     }
     if (lazy && !folded[i]) launch_folds(i);  // (one slice, or a stack without an sLSTM block: the fold ahead of its read passes)
@@ -594,7 +603,7 @@ void run_xlstm_stack(lram_engine* e, const Pass& pass, int T, const uint8_t* res
         continue;
       }
       stream_after(e, hbm, x.s);
-      mlstm_cell(e, i, T, reset, x, hbm);
+      mlstm_cell(e, pass, i, T, reset, x, hbm);
       mlstm_up_z(e, i, T, x);
       stream_after(e, x.s, hbm);
     }

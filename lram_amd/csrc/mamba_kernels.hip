@@ -15,14 +15,16 @@ namespace {
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 
 // conv_state.roll(-1); conv_state[..., -1] = x;  xc = silu(sum_k conv_state[.., k] * w[d, k] + b[d])
-template <int T>
+// (hold, device_math.h: the env takes no token in this launch -- its conv state is not written and its reset flag is ignored)
+template <int T, bool HOLD = false>
 __global__ __launch_bounds__(256) void mamba_conv_kernel(MambaConvArgs a) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int di = a.d_inner;
   if (gid >= (int64_t)a.B * di) return;
   const int b = (int)(gid / di);
   const int d = (int)(gid - (int64_t)b * di);
-  const bool rs = a.reset != nullptr && a.reset[b] != 0;
+  const bool held = env_held<HOLD>(a.hold, b, a.conv_w);
+  const bool rs = a.reset != nullptr && a.reset[b] != 0 && !held;
   float4 win = rs ? f4_zero() : *reinterpret_cast<const float4*>(a.conv_state + gid * 4);
   const float4 w = *reinterpret_cast<const float4*>(a.conv_w + (int64_t)d * 4);
   const float bias = a.conv_b != nullptr ? a.conv_b[d] : 0.f;
@@ -42,17 +44,19 @@ __global__ __launch_bounds__(256) void mamba_conv_kernel(MambaConvArgs a) {
       if ((threadIdx.x & 63) == 63) a.amax[row * (di >> 6) + (d >> 6)] = m;  // this wave's 64 channels of the row
     }
   }
-  *reinterpret_cast<float4*>(a.conv_state + gid * 4) = win;
+  if (!held) *reinterpret_cast<float4*>(a.conv_state + gid * 4) = win;
 }
 
 // same, runtime T (prefill chunks)
+template <bool HOLD = false>
 __global__ __launch_bounds__(256) void mamba_conv_rt_kernel(MambaConvArgs a) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int di = a.d_inner;
   if (gid >= (int64_t)a.B * di) return;
   const int b = (int)(gid / di);
   const int d = (int)(gid - (int64_t)b * di);
-  const bool rs = a.reset != nullptr && a.reset[b] != 0;
+  const bool held = env_held<HOLD>(a.hold, b, a.conv_w);
+  const bool rs = a.reset != nullptr && a.reset[b] != 0 && !held;
   float4 win = rs ? f4_zero() : *reinterpret_cast<const float4*>(a.conv_state + gid * 4);
   const float4 w = *reinterpret_cast<const float4*>(a.conv_w + (int64_t)d * 4);
   const float bias = a.conv_b != nullptr ? a.conv_b[d] : 0.f;
@@ -65,7 +69,7 @@ __global__ __launch_bounds__(256) void mamba_conv_rt_kernel(MambaConvArgs a) {
     win.w = x;
     a.xc[row * di + d] = silu_hw(win.x * w.x + win.y * w.y + win.z * w.z + win.w * w.w + bias);
   }
-  *reinterpret_cast<float4*>(a.conv_state + gid * 4) = win;
+  if (!held) *reinterpret_cast<float4*>(a.conv_state + gid * 4) = win;
 }
 
 // dst[c][r] = src[r][c] (finalize-time helper: small weight matrices only)
@@ -103,7 +107,7 @@ __global__ __launch_bounds__(256) void mamba_dt_proj_kernel(const float* __restr
 // softplus(.), silu(z) and the per-(env, token) vectors B, C are staged in LDS with coalesced loads (dt and the
 // gate are evaluated once per channel there, not once per lane); outputs go back through LDS so the global
 // stores are full 256-byte rows.
-template <int T, int kSsmEnvs>
+template <int T, int kSsmEnvs, bool HOLD = false>
 __global__ __launch_bounds__(256) void mamba_ssm_kernel(MambaSsmArgs a) {
   __shared__ __attribute__((aligned(16))) float bc[kSsmEnvs][T][2][64];   // [env][token][B|C][n], N <= 64
   __shared__ float sc[kSsmEnvs][T][3][64];                                // x | dt | silu(z) per channel
@@ -128,10 +132,15 @@ __global__ __launch_bounds__(256) void mamba_ssm_kernel(MambaSsmArgs a) {
   const float4 A = make_float4(-expf(al.x), -expf(al.y), -expf(al.z), -expf(al.w));
   const float Dd = a.Dp[d];
   float4 s[kSsmEnvs];
+  // hold: a workgroup serves kSsmEnvs envs, so the rule is applied per env -- a held env's state is neither read (it enters as
+  // zeros, like a restart) nor written; the flags are requested here, ahead of the state, behind no branch
+  bool held[kSsmEnvs];
+#pragma unroll
+  for (int e = 0; e < kSsmEnvs; ++e) held[e] = env_held<HOLD>(a.hold, min(b0 + e, a.B - 1), a.A_log);
 #pragma unroll
   for (int e = 0; e < kSsmEnvs; ++e) {
     const int b = b0 + e;
-    const bool rs = e >= ne || (a.reset != nullptr && a.reset[b] != 0);
+    const bool rs = e >= ne || (a.reset != nullptr && a.reset[b] != 0) || held[e];
     if (rs) {
       s[e] = f4_zero();
     } else {  // streamed once per env-step: non-temporal, the projections' operands keep the caches
@@ -209,7 +218,7 @@ __global__ __launch_bounds__(256) void mamba_ssm_kernel(MambaSsmArgs a) {
       for (int off = 1; off < Q; off <<= 1) y += __shfl_xor(y, off, 64);
       if (qd == 0 && cl < cpb) yo[e][t][cl] = (y + Dd * x) * sc[e][t][2][cl];
     }
-    if (active) {
+    if (active && !held[e]) {
       v4f_t v;
       v.x = s[e].x, v.y = s[e].y, v.z = s[e].z, v.w = s[e].w;
       __builtin_nontemporal_store(v, reinterpret_cast<v4f_t*>(a.ssm_state + (((int64_t)b * di + d) * Q + qd) * 4));
@@ -253,13 +262,14 @@ __global__ __launch_bounds__(256) void mamba_ssm_kernel(MambaSsmArgs a) {
 // form through the wave's own 4 KB of LDS (in-order LDS pipeline of one wave: no barrier).  Without it each lane reads and writes
 // its 64 contiguous bytes as four 16-byte pieces at a 64-byte lane stride: that shape alone (no arithmetic, same grid) runs at
 // 2.5 TB/s, the coalesced one at 4.9 (scripts/rmw_pattern.cpp, profiles/r04_mamba_state_access_shape.txt).
-template <int T, int R, bool ILP, int OCC, bool TR>
+template <int T, int R, bool ILP, int OCC, bool TR, bool HOLD = false>
 __global__ __launch_bounds__(256, OCC) void mamba_ssm_lane_kernel(float* __restrict__ ssm_state, const float* __restrict__ xc,
                                                              const float* __restrict__ xz, const float* __restrict__ xdb,
                                                              const float* __restrict__ dt_wt, const float* __restrict__ dt_bias,
                                                              const float* __restrict__ A_log, const float* __restrict__ Dp,
                                                              const uint8_t* __restrict__ reset, float* __restrict__ y,
-                                                             float* __restrict__ amax, int B, int di, int epw) {
+                                                             float* __restrict__ amax, int B, int di, int epw,
+                                                             const uint8_t* __restrict__ hold) {
   constexpr int N = 16, LDX = R + 2 * N;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
@@ -300,7 +310,10 @@ __global__ __launch_bounds__(256, OCC) void mamba_ssm_lane_kernel(float* __restr
   request(e_begin);
   for (int b = e_begin; b < e_end; ++b) {
     float s[N], x[T], z[T];
-    const bool rs = reset != nullptr && __builtin_amdgcn_readfirstlane((int)reset[b]) != 0;  // wave-uniform: a scalar branch
+    // hold (wave-uniform like the reset flag: the wave's envs come one after the other): the env's state is not written, its reset
+    // flag is ignored; its state was requested a turn ahead whatever the flag says
+    const bool held = HOLD && __builtin_amdgcn_readfirstlane((int)hold[b]) != 0;
+    const bool rs = !held && reset != nullptr && __builtin_amdgcn_readfirstlane((int)reset[b]) != 0;  // wave-uniform: a scalar branch
     if (TR) {  // piece q of lane l is float4 64 q + l of the block; channel c owns float4s 4 c .. 4 c + 3
 #pragma unroll
       for (int q = 0; q < 4; ++q) tb[64 * q + lane] = sn[q];
@@ -352,6 +365,7 @@ __global__ __launch_bounds__(256, OCC) void mamba_ssm_lane_kernel(float* __restr
         if (lane == 63) amax[row * ncb + cb] = m;
       }
     }
+    if (held) continue;
     if (TR) {
       v4f_t o[4];
 #pragma unroll
@@ -396,6 +410,15 @@ void launch_mamba_conv(const MambaConvArgs& a, hipStream_t stream) {
   LRAM_REQUIRE(a.K == 4, "Mamba d_conv must be 4");
   const int64_t n = (int64_t)a.B * a.d_inner;
   dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  if (a.hold != nullptr) {   // a stored-context chunk with a held env (whole timesteps: T is a multiple of 3)
+    LRAM_REQUIRE(a.T >= 1 && a.T <= kMaxTokens, "tokens per launch out of range");
+    if (a.T == 3)
+      hipLaunchKernelGGL((mamba_conv_kernel<3, true>), grid, block, 0, stream, a);
+    else
+      hipLaunchKernelGGL(mamba_conv_rt_kernel<true>, grid, block, 0, stream, a);
+    LRAM_HIP_CHECK(hipGetLastError());
+    return;
+  }
   switch (a.T) {
     case 1: hipLaunchKernelGGL(mamba_conv_kernel<1>, grid, block, 0, stream, a); break;
     case 2: hipLaunchKernelGGL(mamba_conv_kernel<2>, grid, block, 0, stream, a); break;
@@ -403,7 +426,7 @@ void launch_mamba_conv(const MambaConvArgs& a, hipStream_t stream) {
     case 4: hipLaunchKernelGGL(mamba_conv_kernel<4>, grid, block, 0, stream, a); break;
     default:
       LRAM_REQUIRE(a.T >= 1 && a.T <= kMaxTokens, "tokens per launch out of range");
-      hipLaunchKernelGGL(mamba_conv_rt_kernel, grid, block, 0, stream, a);
+      hipLaunchKernelGGL(mamba_conv_rt_kernel<false>, grid, block, 0, stream, a);
   }
   LRAM_HIP_CHECK(hipGetLastError());
 }
@@ -423,12 +446,27 @@ void launch_mamba_ssm(const MambaSsmArgs& a, hipStream_t stream) {
     const int epw = 8;  // env slots per wave
     const long waves = (long)(a.d_inner / 64) * ((a.B + epw - 1) / epw);
     const dim3 grid((unsigned)((waves + 3) / 4));
-    hipLaunchKernelGGL((mamba_ssm_lane_kernel<3, 48, true, 3, true>), grid, block, 0, stream, a.ssm_state, a.xc, a.xz, a.xdb, a.dt_wt,
-                       a.dt_bias, a.A_log, a.Dp, a.reset, a.y, a.amax, a.B, a.d_inner, epw);
+    if (a.hold != nullptr)
+      hipLaunchKernelGGL((mamba_ssm_lane_kernel<3, 48, true, 3, true, true>), grid, block, 0, stream, a.ssm_state, a.xc, a.xz, a.xdb,
+                         a.dt_wt, a.dt_bias, a.A_log, a.Dp, a.reset, a.y, a.amax, a.B, a.d_inner, epw, a.hold);
+    else
+      hipLaunchKernelGGL((mamba_ssm_lane_kernel<3, 48, true, 3, true, false>), grid, block, 0, stream, a.ssm_state, a.xc, a.xz, a.xdb,
+                         a.dt_wt, a.dt_bias, a.A_log, a.Dp, a.reset, a.y, a.amax, a.B, a.d_inner, epw, a.hold);
     LRAM_HIP_CHECK(hipGetLastError());
     return;
   }
   dim3 g4(gx, (unsigned)((a.B + 3) / 4)), g1(gx, (unsigned)a.B);
+  if (a.hold != nullptr) {   // a stored-context chunk with a held env: whole timesteps of three tokens
+    switch (a.T) {
+      case 3: hipLaunchKernelGGL((mamba_ssm_kernel<3, 4, true>), g4, block, 0, stream, a); break;
+      case 6: hipLaunchKernelGGL((mamba_ssm_kernel<6, 1, true>), g1, block, 0, stream, a); break;
+      case 9: hipLaunchKernelGGL((mamba_ssm_kernel<9, 1, true>), g1, block, 0, stream, a); break;
+      case 12: hipLaunchKernelGGL((mamba_ssm_kernel<12, 1, true>), g1, block, 0, stream, a); break;
+      default: throw Error("lram: held envs need whole timesteps of three tokens (3, 6, 9 or 12 tokens per launch)");
+    }
+    LRAM_HIP_CHECK(hipGetLastError());
+    return;
+  }
   switch (a.T) {
     case 1: hipLaunchKernelGGL((mamba_ssm_kernel<1, 4>), g4, block, 0, stream, a); break;
     case 2: hipLaunchKernelGGL((mamba_ssm_kernel<2, 4>), g4, block, 0, stream, a); break;

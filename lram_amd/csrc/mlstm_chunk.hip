@@ -38,7 +38,8 @@ constexpr int kPreMaxGroups = 3;      // channel groups of 4 per thread: inner <
 // Front end, token-parallel: one workgroup per (env, group of kTB consecutive tokens).  The token rules of
 // xlstm_rules.h with the partial sums in mlstm_pre_seq_kernel's order; the conv window of the first three tokens reaches
 // back into conv_state.  Per-channel weights are loaded once per workgroup and reused for its kTB tokens.
-// Writes q, k, v, xa rows and the raw gate pre-activations gates[row][head] = (i~, f~).
+// Writes q, k, v, xa rows and the raw gate pre-activations gates[row][head] = (i~, f~).  (It writes no state: the hold rule of
+// the append entries, device_math.h, has nothing to stop here.)
 // =============================================================================================
 constexpr int kTB = 4;
 
@@ -145,6 +146,7 @@ __global__ __launch_bounds__(kThreads) void mlstm_pre_tok_kernel(MlstmPreArgs a)
 constexpr int kSP = 36;  // LDS row pitch of the 32-wide K tiles (floats): conflict-free ds_read_b128
 constexpr int kDP = 65;  // LDS row pitch of the 64 x 64 decay / A matrix
 
+template <bool HOLD>
 __global__ __launch_bounds__(kThreads) void mlstm_chunk_scan_kernel(MlstmPreArgs a) {
   __shared__ __attribute__((aligned(16))) float Qs[kLp * kSP];
   __shared__ __attribute__((aligned(16))) float Ks[kLp * kSP];
@@ -154,7 +156,8 @@ __global__ __launch_bounds__(kThreads) void mlstm_chunk_scan_kernel(MlstmPreArgs
   const int h = blockIdx.x, b = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int inner = a.inner, T = a.T, NH = a.NH, DH = inner / NH;
-  const bool rs = a.reset != nullptr && a.reset[b] != 0;
+  const bool held = env_held<HOLD>(a.hold, b, a.gates);   // (hold: m, n and conv state are not written, reset is ignored)
+  const bool rs = a.reset != nullptr && a.reset[b] != 0 && !held;
   const float sqrt_dh = sqrtf((float)DH);
   const float* qb = a.q + (int64_t)b * T * inner + (int64_t)h * DH;  // row t at + t * inner
   const float* kb = a.k + (int64_t)b * T * inner + (int64_t)h * DH;
@@ -184,7 +187,7 @@ __global__ __launch_bounds__(kThreads) void mlstm_chunk_scan_kernel(MlstmPreArgs
         m = mn;
       }
     }
-    if (lane == 0) a.m_state[(int64_t)b * NH + h] = m;
+    if (lane == 0 && !held) a.m_state[(int64_t)b * NH + h] = m;
     // ... and its other half, per lane
     const MlstmGate gt = mlstm_gate_fi(lf, mp, mt, gi);
     const float f = valid ? gt.f : 1.f;
@@ -322,10 +325,10 @@ __global__ __launch_bounds__(kThreads) void mlstm_chunk_scan_kernel(MlstmPreArgs
 #pragma unroll
       for (int j = 0; j < 8; ++j) n += s_w[s0 + j] * khat(kv[j], sqrt_dh);
     }
-    nst[r] = n;
+    if (!held) nst[r] = n;
   }
   // ---- 7. conv state = the chunk's last 4 inputs (T >= 4 on this path) ----
-  if (h == 0) {
+  if (h == 0 && !held) {
     for (int idx = tid; idx < inner; idx += kThreads * 1) {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
@@ -345,6 +348,7 @@ constexpr int kPV = 136;  // LDS row pitch of the 128-wide tiles (V, C): the two
 constexpr int kPK = 40;   // LDS row pitch of the (w Khat) tile
 constexpr int kCellChunkLds = (kLp * kPV + kRT * kPV + kLp * kSP + kLp * kPK) * 4;  // 71,680 B
 
+template <bool HOLD>
 __global__ __launch_bounds__(kThreads) void mlstm_cell_chunk_kernel(MlstmCellArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Vs = smem;                 // [64][kPV]   v_t, columns of this slice
@@ -363,7 +367,9 @@ __global__ __launch_bounds__(kThreads) void mlstm_cell_chunk_kernel(MlstmCellArg
   const int h = bh % NH, b = bh / NH;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
-  const bool rs = a.reset != nullptr && a.reset[b] != 0;
+  // (hold: the env's matrix memory is neither read -- it enters as zeros, like a restart -- nor written)
+  const bool held = env_held<HOLD>(a.hold, b, a.vec);
+  const bool rs = (a.reset != nullptr && a.reset[b] != 0) || held;
   const bool two = T > 32;
   const int kt8 = (T + 7) >> 3;  // 8-token groups in the contractions over tokens
   const float sqrt_dh = sqrtf((float)DH);
@@ -445,6 +451,7 @@ __global__ __launch_bounds__(kThreads) void mlstm_cell_chunk_kernel(MlstmCellArg
   const int64_t lane_off = (int64_t)(4 * lh) * DH + 32 * w + li;
   auto store_tile = [&](const f32x16& c, int r0) {
     float* dst = Cg + (int64_t)r0 * DH + lane_off;
+    if (held) return;
 #pragma unroll
     for (int r = 0; r < 16; ++r) __builtin_nontemporal_store(c[r], dst + (int64_t)((r & 3) + 8 * (r >> 2)) * DH);
   };
@@ -557,6 +564,7 @@ constexpr int kQPlane = kLp * kRT;   // per (fcum Q) plane          [64 tokens][
 constexpr int kKPlane = kRT * kLp;   // per (w Khat)^T plane        [32 rows][64 tokens]
 constexpr int kCell3Lds = 3 * (kVPlane + kQPlane + kKPlane) * 2;  // 73,728 B
 
+template <bool HOLD>
 __global__ __launch_bounds__(kThreads) void mlstm_cell_chunk3_kernel(MlstmCellArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   __bf16* Vp = reinterpret_cast<__bf16*>(smem_raw);  // [3][128][64]: granule g of row c at g ^ ((c >> 1) & 7)
@@ -572,7 +580,10 @@ __global__ __launch_bounds__(kThreads) void mlstm_cell_chunk3_kernel(MlstmCellAr
   const int h = bh % NH, b = bh / NH;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
-  const bool rs = a.reset != nullptr && a.reset[b] != 0;
+  // (hold: the range check of the two resources below does the predication -- with zero bytes in range the loads of the env's matrix
+  // memory return zeros and its stores are dropped, without a branch)
+  const bool held = env_held<HOLD>(a.hold, b, a.vec);
+  const bool rs = (a.reset != nullptr && a.reset[b] != 0) || held;
   const bool two = T > 32;
   const int kt16 = (T + 15) >> 4;  // 16-token steps of the contractions over tokens
   const float sqrt_dh = sqrtf((float)DH);
@@ -594,7 +605,7 @@ __global__ __launch_bounds__(kThreads) void mlstm_cell_chunk3_kernel(MlstmCellAr
   float* Cm = a.C + (((int64_t)b * NH + h) * DH) * DH;
   const uint32_t c_bytes = (uint32_t)DH * (uint32_t)DH * 4u;
   const __amdgpu_buffer_rsrc_t rc_in = __builtin_amdgcn_make_buffer_rsrc(Cm, 0, rs ? 0u : c_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rc_out = __builtin_amdgcn_make_buffer_rsrc(Cm, 0, c_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rc_out = __builtin_amdgcn_make_buffer_rsrc(Cm, 0, held ? 0u : c_bytes, 0x00020000);
   constexpr int kNt = 2;  // cache policy: non-temporal (C is touched once per pass)
   const int row_b = DH * 4, tok_b = inner * 4;
   // ---- V planes: thread (column, token half) gathers 8 consecutive tokens of its column per granule ----
@@ -800,7 +811,10 @@ void launch_mlstm_chunk_pre(const MlstmPreArgs& a, hipStream_t stream) {
     default: hipLaunchKernelGGL(mlstm_pre_tok_kernel<8>, grid, block, 0, stream, a); break;
   }
   LRAM_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(mlstm_chunk_scan_kernel, dim3(a.NH, a.B), block, 0, stream, a);
+  if (a.hold != nullptr)   // (launched only for a chunk with a held env: every other call keeps its instance)
+    hipLaunchKernelGGL(mlstm_chunk_scan_kernel<true>, dim3(a.NH, a.B), block, 0, stream, a);
+  else
+    hipLaunchKernelGGL(mlstm_chunk_scan_kernel<false>, dim3(a.NH, a.B), block, 0, stream, a);
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
@@ -810,16 +824,26 @@ void launch_mlstm_chunk_cell(const MlstmCellArgs& a, hipStream_t stream) {
   LRAM_REQUIRE(a.amat != nullptr && a.vec != nullptr, "chunkwise mLSTM: missing work buffers");
   static uint64_t raised = 0;
   if (first_use_on_device(raised)) {
-    LRAM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlstm_cell_chunk_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kCellChunkLds));
-    LRAM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlstm_cell_chunk3_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kCell3Lds));
+    for (const void* k : {reinterpret_cast<const void*>(&mlstm_cell_chunk_kernel<false>),
+                          reinterpret_cast<const void*>(&mlstm_cell_chunk_kernel<true>)})
+      LRAM_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kCellChunkLds));
+    for (const void* k : {reinterpret_cast<const void*>(&mlstm_cell_chunk3_kernel<false>),
+                          reinterpret_cast<const void*>(&mlstm_cell_chunk3_kernel<true>)})
+      LRAM_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kCell3Lds));
   }
   const long nwg = (long)a.B * a.NH * (a.DH / kCW);
-  if (a.chunk_exact_fp32)
-    hipLaunchKernelGGL(mlstm_cell_chunk_kernel, dim3((unsigned)nwg), dim3(kThreads), kCellChunkLds, stream, a);
-  else
-    hipLaunchKernelGGL(mlstm_cell_chunk3_kernel, dim3((unsigned)nwg), dim3(kThreads), kCell3Lds, stream, a);
+  const dim3 grid((unsigned)nwg), block(kThreads);
+  if (a.chunk_exact_fp32) {
+    if (a.hold != nullptr)
+      hipLaunchKernelGGL(mlstm_cell_chunk_kernel<true>, grid, block, kCellChunkLds, stream, a);
+    else
+      hipLaunchKernelGGL(mlstm_cell_chunk_kernel<false>, grid, block, kCellChunkLds, stream, a);
+  } else {
+    if (a.hold != nullptr)
+      hipLaunchKernelGGL(mlstm_cell_chunk3_kernel<true>, grid, block, kCell3Lds, stream, a);
+    else
+      hipLaunchKernelGGL(mlstm_cell_chunk3_kernel<false>, grid, block, kCell3Lds, stream, a);
+  }
   LRAM_HIP_CHECK(hipGetLastError());
 }
 

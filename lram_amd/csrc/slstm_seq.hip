@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void slstm_pack_rt_kernel(const float* rt, flo
   rt2[i] = rt[(((int64_t)head * 4 + g) * SDH + ch) * SDH + k];
 }
 
-template <int T, int kSDH>
+template <int T, int kSDH, bool HOLD = false>
 __global__ __launch_bounds__(2 * kSDH, kSDH <= 256 ? 2 : 3) void slstm_seq_kernel(SlstmSeqArgs a) {
   constexpr int kPitch = kSDH + 4, kHalf = kSDH / 2;   // K per lane half
   static_assert(kSDH % 32 == 0 && kHalf % 8 == 0, "head dim: a multiple of 32 whose half is a multiple of the 8-deep product round");
@@ -73,6 +73,10 @@ __global__ __launch_bounds__(2 * kSDH, kSDH <= 256 ? 2 : 3) void slstm_seq_kerne
     const float* st = a.state + (int64_t)env_of(r) * H + ch;
     cs[r] = st[BH], ns[r] = st[2 * BH], ms[r] = st[3 * BH];
   }
+  // hold (device_math.h): a workgroup serves 32 envs, so the state stores are predicated per env.  The HOLD instance reads the
+  // flags BEHIND the token loop and stores everything there -- the cell state as always, the state's h plane from the LDS copy of
+  // the last token's h instead of inside the loop -- so that nothing of it is live across the loop: the 320- and 384-wide heads
+  // run at three waves per SIMD and have no register to spare.  No state request waits for a flag.
   const float bi = a.bias[ch], bf = a.bias[H + ch], bz = a.bias[2 * H + ch], bo = a.bias[3 * H + ch];
   const float* bp = a.rt2 + (((int64_t)head * kSDH + kHalf * lh) * kSDH + 32 * w + li) * 4;  // k = kHalf lh + j: + j * SDH * 4
   __syncthreads();
@@ -140,7 +144,7 @@ __global__ __launch_bounds__(2 * kSDH, kSDH <= 256 ? 2 : 3) void slstm_seq_kerne
         hs[cur ^ 1][e][32 * w + li] = ynew;
         if (b0 + e < a.B) {
           a.yout[((unsigned)(b0 + e) * (unsigned)T + (unsigned)t) * (unsigned)H + ycol] = ynew;
-          if (t == T - 1) a.state[(unsigned)(b0 + e) * (unsigned)H + ycol] = ynew;   // the state's h plane: the step's last h
+          if (!HOLD && t == T - 1) a.state[(unsigned)(b0 + e) * (unsigned)H + ycol] = ynew;   // the state's h plane: the step's last h
         }
       }
     }
@@ -149,8 +153,9 @@ __global__ __launch_bounds__(2 * kSDH, kSDH <= 256 ? 2 : 3) void slstm_seq_kerne
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int e = acc_row(r, lh);
-    if (b0 + e < a.B) {
+    if (b0 + e < a.B && !env_held<HOLD>(a.hold, b0 + e, a.bias)) {
       float* st = a.state + (int64_t)(b0 + e) * H + ch;
+      if (HOLD) st[0] = hs[T & 1][e][32 * w + li];   // (h of the last token, complete behind the loop's last barrier)
       st[BH] = cs[r], st[2 * BH] = ns[r], st[3 * BH] = ms[r];
     }
   }
@@ -197,7 +202,7 @@ __global__ __launch_bounds__(256) void slstm_pack_rt16_kernel(const float* rt, _
   if (lane == 0) rinv[row] = 1.f / (sc * kHScale);
 }
 
-template <int T, int kSDH, bool GE>
+template <int T, int kSDH, bool GE, bool HOLD = false>
 __global__ __launch_bounds__(2 * kSDH, kSDH <= 128 ? 2 : 1) void slstm_seq16_kernel(SlstmSeqArgs a) {
   constexpr int KS = kSDH / 32, NU = 2 * KS, kPitch = kSDH + 8;   // K steps of 32, B units (k step, column tile), LDS row pitch (f16)
   __shared__ __attribute__((aligned(16))) _Float16 hs[2][2][kEnv16][kPitch];   // [buffer][plane][env][k]
@@ -233,6 +238,12 @@ __global__ __launch_bounds__(2 * kSDH, kSDH <= 128 ? 2 : 1) void slstm_seq16_ker
       const float* st = a.state + (int64_t)env_of(r) * H + ch0 + 16 * ct;
       cs[ct][r] = st[BH], ns[ct][r] = st[2 * BH], ms[ct][r] = st[3 * BH];
     }
+  // hold: one bit per env row of this lane (16 envs per workgroup: the state stores are predicated per env), as in the fp32 form
+  unsigned held = 0;
+  if (HOLD) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) held |= env_held<HOLD>(a.hold, env_of(r), a.bias) ? 1u << r : 0u;
+  }
   float bias[2][4], ri[2][4];
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct)
@@ -316,7 +327,7 @@ __global__ __launch_bounds__(2 * kSDH, kSDH <= 128 ? 2 : 1) void slstm_seq16_ker
         if (b0 + e < a.B) {
           const unsigned ycol = (unsigned)(ch0 + 16 * ct);
           a.yout[((unsigned)(b0 + e) * (unsigned)T + (unsigned)t) * (unsigned)H + ycol] = ynew;
-          if (t == T - 1) a.state[(unsigned)(b0 + e) * (unsigned)H + ycol] = ynew;   // the state's h plane: the step's last h
+          if (t == T - 1 && !(HOLD && (held >> r & 1u))) a.state[(unsigned)(b0 + e) * (unsigned)H + ycol] = ynew;   // the state's h plane: the step's last h
         }
       }
     }
@@ -327,7 +338,7 @@ __global__ __launch_bounds__(2 * kSDH, kSDH <= 128 ? 2 : 1) void slstm_seq16_ker
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int e = 4 * lg + r;
-      if (b0 + e < a.B) {
+      if (b0 + e < a.B && !(HOLD && (held >> r & 1u))) {
         float* st = a.state + (int64_t)(b0 + e) * H + ch0 + 16 * ct;
         st[BH] = cs[ct][r], st[2 * BH] = ns[ct][r], st[3 * BH] = ms[ct][r];
       }
@@ -366,8 +377,23 @@ void launch_slstm_pack_rt16(const float* rt, uint16_t* rt2h, float* rinv, int NH
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
+// The HOLD instances (a.hold given: a stored-context chunk with a held env): such a chunk holds whole timesteps, and T <= 4 here.
+template <int SDH>
+static void launch_seq_hold(const SlstmSeqArgs& a, hipStream_t stream) {
+  LRAM_REQUIRE(a.T == 3, "sLSTM step kernel: held envs need whole timesteps of three tokens");
+  if (a.rt2h != nullptr) {
+    constexpr bool GE = SDH <= 256;
+    const dim3 grid((unsigned)(a.NH * ((a.B + kEnv16 - 1) / kEnv16))), block(2 * SDH);
+    hipLaunchKernelGGL((slstm_seq16_kernel<3, SDH, GE, true>), grid, block, 0, stream, a);
+    return;
+  }
+  const dim3 grid((unsigned)(a.NH * ((a.B + kEnv - 1) / kEnv))), block(2 * SDH);
+  hipLaunchKernelGGL((slstm_seq_kernel<3, SDH, true>), grid, block, 0, stream, a);
+}
+
 template <int SDH>
 static void launch_seq_sdh(const SlstmSeqArgs& a, hipStream_t stream) {
+  if (a.hold != nullptr) return launch_seq_hold<SDH>(a, stream);
   if (a.rt2h != nullptr) {   // f16x2 form: 16 envs per workgroup; the gate rows requested early where 8 waves or fewer share the registers
     constexpr bool GE = SDH <= 256;
     const dim3 grid((unsigned)(a.NH * ((a.B + kEnv16 - 1) / kEnv16))), block(2 * SDH);

@@ -28,7 +28,7 @@ constexpr int kPreThreads = 256;
 constexpr int kMaxGroups = 4;  // channel groups (of 4) per thread: inner <= 4096
 
 // (body as a device function of the env index: the kernel calls it with blockIdx.x)
-template <int T, int NH, bool SINGLE = false>
+template <int T, int NH, bool SINGLE = false, bool HOLD = false>
 __device__ __forceinline__ void mlstm_pre_body(const MlstmPreArgs& a, const int b) {
   constexpr int NRED = 2 * T * NH;
   __shared__ float red[4][NRED];
@@ -44,7 +44,9 @@ __device__ __forceinline__ void mlstm_pre_body(const MlstmPreArgs& a, const int 
   // spot, ahead of every other request of the workgroup)
   const uint8_t* rsp = a.reset != nullptr ? a.reset + b : reinterpret_cast<const uint8_t*>(a.conv_w);
   const uint8_t rsb = *rsp;
-  const bool rs = a.reset != nullptr && rsb != 0;
+  // (hold: the env takes no token -- its conv / n / m state is not written and its reset flag is ignored; device_math.h)
+  const bool held = env_held<HOLD>(a.hold, b, a.conv_w);
+  const bool rs = a.reset != nullptr && rsb != 0 && !held;
 
   float pi[T][NH], pf[T][NH];
 #pragma unroll
@@ -90,7 +92,7 @@ __device__ __forceinline__ void mlstm_pre_body(const MlstmPreArgs& a, const int 
       __builtin_amdgcn_sched_barrier(0);
       unsigned flag = rsb;
       asm volatile("" : "+v"(flag));  // opaque here: the comparison cannot be hoisted (with its wait) above the requests
-      const unsigned keep = (a.reset != nullptr && flag != 0) ? 0u : 0xFFFFFFFFu;
+      const unsigned keep = (a.reset != nullptr && flag != 0 && !held) ? 0u : 0xFFFFFFFFu;
 #pragma unroll
       for (int k = 0; k < 4; ++k) win[k] = masked4(win[k], keep);
       n_pre = masked4(n_pre, keep);
@@ -120,7 +122,7 @@ __device__ __forceinline__ void mlstm_pre_body(const MlstmPreArgs& a, const int 
     // conv state after the T tokens (reference layout [B, K, inner], newest tap last)
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      if (k < a.K) *reinterpret_cast<float4*>(a.conv_state + ((int64_t)b * a.K + k) * inner + c0) = win[k];
+      if (k < a.K && !held) *reinterpret_cast<float4*>(a.conv_state + ((int64_t)b * a.K + k) * inner + c0) = win[k];
     // gate partial sums over this thread's 4 channels of q, k and v
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
@@ -173,7 +175,7 @@ __device__ __forceinline__ void mlstm_pre_body(const MlstmPreArgs& a, const int 
       s_i[t][h] = g.i;
       s_m[t][h] = m = g.m;
     }
-    a.m_state[(int64_t)b * NH + h] = m;
+    if (!held) a.m_state[(int64_t)b * NH + h] = m;
   }
   __syncthreads();
   // ---- phase 3: normaliser state n_t = f_t n_{t-1} + i_t k_t/sqrt(DH) and q_t . n_t -----------
@@ -213,7 +215,7 @@ __device__ __forceinline__ void mlstm_pre_body(const MlstmPreArgs& a, const int 
 #pragma unroll
       for (int h = 0; h < NH; ++h) pq[t][h] += (h == hh) ? d : 0.f;
     }
-    *reinterpret_cast<float4*>(a.n_state + (int64_t)b * inner + c0) = n;
+    if (!held) *reinterpret_cast<float4*>(a.n_state + (int64_t)b * inner + c0) = n;
   }
 #pragma unroll
   for (int t = 0; t < T; ++t)
@@ -231,20 +233,21 @@ __device__ __forceinline__ void mlstm_pre_body(const MlstmPreArgs& a, const int 
   }
 }
 
-template <int T, int NH, bool SINGLE = false>
+template <int T, int NH, bool SINGLE = false, bool HOLD = false>
 __global__ __launch_bounds__(kPreThreads) void mlstm_pre_kernel(MlstmPreArgs a) {
-  mlstm_pre_body<T, NH, SINGLE>(a, blockIdx.x);
+  mlstm_pre_body<T, NH, SINGLE, HOLD>(a, blockIdx.x);
 }
 
 // Large-T variant of the front end (context prefill: T = 3 x timesteps-per-chunk, up to kMaxTokens): the same token
 // rules (xlstm_rules.h) token by token with a block reduction per token, so the register footprint does not grow with T.
-template <int NH>
+template <int NH, bool HOLD = false>
 __global__ __launch_bounds__(kPreThreads) void mlstm_pre_seq_kernel(MlstmPreArgs a) {
   __shared__ float red[4][2 * NH];
   __shared__ float s_gi[NH], s_gf[NH], s_f[NH], s_i[NH], s_m[NH];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int inner = a.inner, T = a.T, DH = inner / NH, ngroups = inner >> 2;
-  const bool rs = a.reset != nullptr && a.reset[b] != 0;
+  const bool held = env_held<HOLD>(a.hold, b, a.conv_w);   // (no state byte written, reset ignored)
+  const bool rs = a.reset != nullptr && a.reset[b] != 0 && !held;
   const float sqrt_dh = sqrtf((float)DH);
   float4 win[kMaxGroups][4], nst[kMaxGroups];
 #pragma unroll
@@ -356,7 +359,7 @@ __global__ __launch_bounds__(kPreThreads) void mlstm_pre_seq_kernel(MlstmPreArgs
 #pragma unroll
   for (int g = 0; g < kMaxGroups; ++g) {
     const int cg = tid + g * kPreThreads;
-    if (cg < ngroups) {
+    if (cg < ngroups && !held) {
       const int c0 = cg << 2;
 #pragma unroll
       for (int k = 0; k < 4; ++k)
@@ -364,7 +367,7 @@ __global__ __launch_bounds__(kPreThreads) void mlstm_pre_seq_kernel(MlstmPreArgs
       *reinterpret_cast<float4*>(a.n_state + (int64_t)b * inner + c0) = nst[g];
     }
   }
-  if (tid < NH) a.m_state[(int64_t)b * NH + tid] = s_m[tid];
+  if (tid < NH && !held) a.m_state[(int64_t)b * NH + tid] = s_m[tid];
 }
 
 // =============================================================================================
@@ -375,7 +378,7 @@ __global__ __launch_bounds__(kPreThreads) void mlstm_pre_seq_kernel(MlstmPreArgs
 // =============================================================================================
 constexpr int kCellThreads = 256;
 
-template <int T, int LPR, int kCellUnroll>
+template <int T, int LPR, int kCellUnroll, bool HOLD = false>
 __device__ __forceinline__ void mlstm_cell_body(const MlstmCellArgs& a, const int slice, const int h, const int b,
                                                 float* smem) {
   constexpr int CW = 4 * LPR;
@@ -388,7 +391,9 @@ __device__ __forceinline__ void mlstm_cell_body(const MlstmCellArgs& a, const in
   const int tid = threadIdx.x;
   const int cl = tid % LPR, rg = tid / LPR;
   const int inner = a.NH * DH;
-  const bool rs = a.reset != nullptr && a.reset[b] != 0;
+  // (hold: the env's matrix memory is neither read -- it enters as zeros, like a restart -- nor written)
+  const bool held = env_held<HOLD>(a.hold, b, a.scal);
+  const bool rs = (a.reset != nullptr && a.reset[b] != 0) || held;
 
   float f[T], ig[T], den[T];
 #pragma unroll
@@ -437,7 +442,7 @@ __device__ __forceinline__ void mlstm_cell_body(const MlstmCellArgs& a, const in
           c[u] = f[t] * c[u] + av * vv[t];
           acc[t] += qv * c[u];
         }
-        __builtin_nontemporal_store(c[u], reinterpret_cast<v4f*>(Cb + (int64_t)r * DH));
+        if (!held) __builtin_nontemporal_store(c[u], reinterpret_cast<v4f*>(Cb + (int64_t)r * DH));
       }
     }
   }
@@ -457,10 +462,10 @@ __device__ __forceinline__ void mlstm_cell_body(const MlstmCellArgs& a, const in
   }
 }
 
-template <int T, int LPR, int kCellUnroll>
+template <int T, int LPR, int kCellUnroll, bool HOLD = false>
 __global__ __launch_bounds__(kCellThreads) void mlstm_cell_kernel(MlstmCellArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  mlstm_cell_body<T, LPR, kCellUnroll>(a, blockIdx.x, blockIdx.y, blockIdx.z, smem);
+  mlstm_cell_body<T, LPR, kCellUnroll, HOLD>(a, blockIdx.x, blockIdx.y, blockIdx.z, smem);
 }
 
 // =============================================================================================
@@ -543,14 +548,15 @@ __global__ __launch_bounds__(64) void group_norm_kernel(GroupNormArgs a) {
 // =============================================================================================
 // sLSTM: conv1d_step + SiLU on the block input (per env, T tokens), reset of the scalar state.
 // =============================================================================================
-template <int T>
+template <int T, bool HOLD = false>
 __global__ __launch_bounds__(256) void slstm_conv_kernel(SlstmConvArgs a) {
   const int ngroups = a.D >> 2;
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (int64_t)a.B * ngroups) return;
   const int b = (int)(gid / ngroups);
   const int c0 = (int)(gid - (int64_t)b * ngroups) << 2;
-  const bool rs = a.reset != nullptr && a.reset[b] != 0;
+  const bool held = env_held<HOLD>(a.hold, b, a.conv_w);   // (per thread: a workgroup serves several envs)
+  const bool rs = a.reset != nullptr && a.reset[b] != 0 && !held;
   const int D = a.D;
   float4 win[4];
 #pragma unroll
@@ -573,7 +579,7 @@ __global__ __launch_bounds__(256) void slstm_conv_kernel(SlstmConvArgs a) {
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k)
-    if (k < a.K) *reinterpret_cast<float4*>(a.conv_state + ((int64_t)b * a.K + k) * D + c0) = win[k];
+    if (k < a.K && !held) *reinterpret_cast<float4*>(a.conv_state + ((int64_t)b * a.K + k) * D + c0) = win[k];
   if (rs) {
 #pragma unroll
     for (int s = 0; s < 4; ++s)
@@ -582,13 +588,15 @@ __global__ __launch_bounds__(256) void slstm_conv_kernel(SlstmConvArgs a) {
 }
 
 // same, runtime T (prefill chunks)
+template <bool HOLD = false>
 __global__ __launch_bounds__(256) void slstm_conv_rt_kernel(SlstmConvArgs a) {
   const int ngroups = a.D >> 2;
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (int64_t)a.B * ngroups) return;
   const int b = (int)(gid / ngroups);
   const int c0 = (int)(gid - (int64_t)b * ngroups) << 2;
-  const bool rs = a.reset != nullptr && a.reset[b] != 0;
+  const bool held = env_held<HOLD>(a.hold, b, a.conv_w);
+  const bool rs = a.reset != nullptr && a.reset[b] != 0 && !held;
   const int D = a.D;
   float4 win[4];
 #pragma unroll
@@ -608,7 +616,8 @@ __global__ __launch_bounds__(256) void slstm_conv_rt_kernel(SlstmConvArgs a) {
     *reinterpret_cast<float4*>(a.xc + row * D + c0) = conv4_silu(win[0], win[1], win[2], win[3], cw, cb);
   }
 #pragma unroll
-  for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(a.conv_state + ((int64_t)b * 4 + k) * D + c0) = win[k];
+  for (int k = 0; k < 4; ++k)
+    if (!held) *reinterpret_cast<float4*>(a.conv_state + ((int64_t)b * 4 + k) * D + c0) = win[k];
   if (rs) {
 #pragma unroll
     for (int s = 0; s < 4; ++s)
@@ -617,6 +626,7 @@ __global__ __launch_bounds__(256) void slstm_conv_rt_kernel(SlstmConvArgs a) {
 }
 
 // sLSTM pointwise cell update for token t (slstm_cell, xlstm_rules.h).
+template <bool HOLD = false>
 __global__ __launch_bounds__(256) void slstm_pointwise_kernel(SlstmPointwiseArgs a) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int H = a.H;
@@ -634,10 +644,12 @@ __global__ __launch_bounds__(256) void slstm_pointwise_kernel(SlstmPointwiseArgs
   float* st = a.state + (int64_t)b * H + c;
   float cs = st[BH], ns = st[2 * BH], ms = st[3 * BH];
   const float ynew = slstm_cell(iraw, fraw, zraw, oraw, cs, ns, ms);
-  st[0] = ynew;
-  st[BH] = cs;
-  st[2 * BH] = ns;
-  st[3 * BH] = ms;
+  if (!env_held<HOLD>(a.hold, b, a.bias)) {
+    st[0] = ynew;
+    st[BH] = cs;
+    st[2 * BH] = ns;
+    st[3 * BH] = ms;
+  }
   a.yout[row * H + c] = ynew;
 }
 
@@ -652,7 +664,7 @@ __global__ __launch_bounds__(256) void slstm_pointwise_kernel(SlstmPointwiseArgs
 // yout afterwards) and h_t goes to yout -- and to the state's h plane only when a.write_h is set (never in a launch that
 // reads that plane: other workgroups still need it).
 constexpr int kSlTokCh = 8, kSlTokEnv = 32;
-template <int SDH>
+template <int SDH, bool HOLD = false>
 __global__ __launch_bounds__(256) void slstm_token_kernel(SlstmTokenArgs a) {
   __shared__ float part[4][kSlTokEnv][33];
   const int H = a.H;
@@ -685,6 +697,7 @@ __global__ __launch_bounds__(256) void slstm_token_kernel(SlstmTokenArgs a) {
   const int64_t BH = (int64_t)a.state_B * H;
   float* st = a.state + (int64_t)bb * H + c;
   float cs = st[BH], ns = st[2 * BH], ms = st[3 * BH];
+  const bool held = env_held<HOLD>(a.hold, bb, a.bias);   // (per thread: this thread's env; requested with the state)
   // every request above is issued before the first matrix product (left alone, the scheduler feeds the products with one
   // or two loads in flight: S / 4 dependent round trips instead of one)
   __builtin_amdgcn_sched_barrier(0);
@@ -708,10 +721,12 @@ __global__ __launch_bounds__(256) void slstm_token_kernel(SlstmTokenArgs a) {
   for (int g = 0; g < 4; ++g)
     sum[g] = (part[0][e][4 * ch + g] + part[1][e][4 * ch + g]) + (part[2][e][4 * ch + g] + part[3][e][4 * ch + g]);
   const float ynew = slstm_cell(gi + sum[0], gf + sum[1], gz + sum[2], go + sum[3], cs, ns, ms);
-  if (a.write_h) st[0] = ynew;
-  st[BH] = cs;
-  st[2 * BH] = ns;
-  st[3 * BH] = ms;
+  if (!held) {
+    if (a.write_h) st[0] = ynew;
+    st[BH] = cs;
+    st[2 * BH] = ns;
+    st[3 * BH] = ms;
+  }
   a.yout[row * H + c] = ynew;
 }
 
@@ -813,21 +828,36 @@ __global__ __launch_bounds__(256) void gelu_gate_kernel(const float* p, float* o
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-template <int T>
+template <int T, bool HOLD = false>
 static void launch_pre_t(const MlstmPreArgs& a, hipStream_t s) {
   dim3 grid(a.B), block(kPreThreads);
   // one channel group per thread: the variant with one dependent memory round trip
   const bool single = (a.inner >> 2) <= kPreThreads;
   switch (a.NH) {
-    case 1: hipLaunchKernelGGL((mlstm_pre_kernel<T, 1>), grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((mlstm_pre_kernel<T, 2>), grid, block, 0, s, a); break;
+    case 1: hipLaunchKernelGGL((mlstm_pre_kernel<T, 1, false, HOLD>), grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((mlstm_pre_kernel<T, 2, false, HOLD>), grid, block, 0, s, a); break;
     case 4:
       if (single)
-        hipLaunchKernelGGL((mlstm_pre_kernel<T, 4, true>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((mlstm_pre_kernel<T, 4, true, HOLD>), grid, block, 0, s, a);
       else
-        hipLaunchKernelGGL((mlstm_pre_kernel<T, 4>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((mlstm_pre_kernel<T, 4, false, HOLD>), grid, block, 0, s, a);
       break;
-    case 8: hipLaunchKernelGGL((mlstm_pre_kernel<T, 8>), grid, block, 0, s, a); break;
+    case 8: hipLaunchKernelGGL((mlstm_pre_kernel<T, 8, false, HOLD>), grid, block, 0, s, a); break;
+    default: throw Error("lram: mLSTM num_heads must be 1, 2, 4 or 8");
+  }
+}
+
+// The HOLD instances (a.hold given: a stored-context chunk with a held env).  Such a chunk holds whole timesteps of three tokens:
+// 3 through the front end above, 6 / 9 / 12 through the sequential one -- no other token count has a HOLD instance.
+static void launch_pre_hold(const MlstmPreArgs& a, hipStream_t stream) {
+  LRAM_REQUIRE(a.T % 3 == 0 && a.T <= kMaxTokens && !a.lean, "mLSTM front end: held envs need whole timesteps of three tokens");
+  if (a.T == 3) return launch_pre_t<3, true>(a, stream);
+  dim3 grid(a.B), block(kPreThreads);
+  switch (a.NH) {
+    case 1: hipLaunchKernelGGL((mlstm_pre_seq_kernel<1, true>), grid, block, 0, stream, a); break;
+    case 2: hipLaunchKernelGGL((mlstm_pre_seq_kernel<2, true>), grid, block, 0, stream, a); break;
+    case 4: hipLaunchKernelGGL((mlstm_pre_seq_kernel<4, true>), grid, block, 0, stream, a); break;
+    case 8: hipLaunchKernelGGL((mlstm_pre_seq_kernel<8, true>), grid, block, 0, stream, a); break;
     default: throw Error("lram: mLSTM num_heads must be 1, 2, 4 or 8");
   }
 }
@@ -838,6 +868,11 @@ void launch_mlstm_pre(const MlstmPreArgs& a, hipStream_t stream) {
   LRAM_REQUIRE(a.inner % (4 * a.NH) == 0, "mLSTM inner dim must be a multiple of 4*num_heads");
   LRAM_REQUIRE(a.inner <= 4 * kPreThreads * kMaxGroups, "mLSTM inner dim too large");
   LRAM_REQUIRE(a.K == 4, "conv weights are packed with 4 taps per channel");
+  if (a.hold != nullptr) {
+    launch_pre_hold(a, stream);
+    LRAM_HIP_CHECK(hipGetLastError());
+    return;
+  }
   switch (a.T) {
     case 1: launch_pre_t<1>(a, stream); break;
     case 2: launch_pre_t<2>(a, stream); break;
@@ -858,7 +893,7 @@ void launch_mlstm_pre(const MlstmPreArgs& a, hipStream_t stream) {
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
-template <int T, int LPR, int UNR>
+template <int T, int LPR, int UNR, bool HOLD = false>
 static void launch_cell_tlu(const MlstmCellArgs& a, hipStream_t s) {
   constexpr int CW = 4 * LPR, RP = kCellThreads / LPR;
   dim3 grid(a.DH / CW, a.NH, a.B), block(kCellThreads);
@@ -870,42 +905,53 @@ static void launch_cell_tlu(const MlstmCellArgs& a, hipStream_t s) {
   if (shmem > 48 * 1024) {
     static uint64_t raised = 0;
     if (first_use_on_device(raised)) {
-      LRAM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlstm_cell_kernel<T, LPR, UNR>),
+      LRAM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlstm_cell_kernel<T, LPR, UNR, HOLD>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
   }
-  hipLaunchKernelGGL((mlstm_cell_kernel<T, LPR, UNR>), grid, block, shmem, s, a);
+  hipLaunchKernelGGL((mlstm_cell_kernel<T, LPR, UNR, HOLD>), grid, block, shmem, s, a);
 }
 
-template <int T, int LPR>
+template <int T, int LPR, bool HOLD = false>
 static void launch_cell_tl(const MlstmCellArgs& a, hipStream_t s) {
   if (a.unroll >= 32)
-    launch_cell_tlu<T, LPR, 32>(a, s);
+    launch_cell_tlu<T, LPR, 32, HOLD>(a, s);
   else if (a.unroll >= 16)
-    launch_cell_tlu<T, LPR, 16>(a, s);
+    launch_cell_tlu<T, LPR, 16, HOLD>(a, s);
   else
-    launch_cell_tlu<T, LPR, 8>(a, s);
+    launch_cell_tlu<T, LPR, 8, HOLD>(a, s);
 }
 
-template <int T>
+template <int T, bool HOLD = false>
 static void launch_cell_t(const MlstmCellArgs& a, hipStream_t s) {
   // Few (env, head) pairs: cut the head's columns into narrower slices so that at least ~256 workgroups exist
   // (a single env at DH = 256 gets 16 workgroups of 64 columns instead of 4 of 256).
   const long pairs = (long)a.B * a.NH;
   if (a.DH % 256 == 0 && pairs * (a.DH / 256) >= 256)
-    launch_cell_tl<T, 64>(a, s);
+    launch_cell_tl<T, 64, HOLD>(a, s);
   else if (a.DH % 128 == 0 && pairs * (a.DH / 128) >= 256)
-    launch_cell_tl<T, 32>(a, s);
+    launch_cell_tl<T, 32, HOLD>(a, s);
   else if (a.DH % 64 == 0)
-    launch_cell_tl<T, 16>(a, s);
+    launch_cell_tl<T, 16, HOLD>(a, s);
   else if (a.DH % 16 == 0)  // the reference's *_half presets (head dims 352, 544, 720): 16-column slices
-    launch_cell_tl<T, 4>(a, s);
+    launch_cell_tl<T, 4, HOLD>(a, s);
   else
     throw Error("lram: mLSTM head dim must be a multiple of 16");
 }
 
 void launch_mlstm_cell(const MlstmCellArgs& a, hipStream_t stream) {
   if (a.T > kMaxTokens) return launch_mlstm_chunk_cell(a, stream);
+  if (a.hold != nullptr) {   // a stored-context chunk with a held env: whole timesteps of three tokens
+    switch (a.T) {
+      case 3: launch_cell_t<3, true>(a, stream); break;
+      case 6: launch_cell_t<6, true>(a, stream); break;
+      case 9: launch_cell_t<9, true>(a, stream); break;
+      case 12: launch_cell_t<12, true>(a, stream); break;
+      default: throw Error("lram: held envs need whole timesteps of three tokens (3, 6, 9 or 12 tokens per launch)");
+    }
+    LRAM_HIP_CHECK(hipGetLastError());
+    return;
+  }
   switch (a.T) {
     case 1: launch_cell_t<1>(a, stream); break;
     case 2: launch_cell_t<2>(a, stream); break;
@@ -936,6 +982,15 @@ void launch_slstm_conv(const SlstmConvArgs& a, hipStream_t stream) {
   LRAM_REQUIRE(a.K == 4 && a.D % 4 == 0, "sLSTM conv: K must be 4 and D a multiple of 4");
   const int64_t n = (int64_t)a.B * (a.D >> 2);
   dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  if (a.hold != nullptr) {   // a stored-context chunk with a held env (whole timesteps: T is a multiple of 3)
+    LRAM_REQUIRE(a.T >= 1 && a.T <= kChunkMaxTokens, "tokens per launch out of range");
+    if (a.T == 3)
+      hipLaunchKernelGGL((slstm_conv_kernel<3, true>), grid, block, 0, stream, a);
+    else
+      hipLaunchKernelGGL(slstm_conv_rt_kernel<true>, grid, block, 0, stream, a);
+    LRAM_HIP_CHECK(hipGetLastError());
+    return;
+  }
   switch (a.T) {
     case 1: hipLaunchKernelGGL(slstm_conv_kernel<1>, grid, block, 0, stream, a); break;
     case 2: hipLaunchKernelGGL(slstm_conv_kernel<2>, grid, block, 0, stream, a); break;
@@ -943,7 +998,7 @@ void launch_slstm_conv(const SlstmConvArgs& a, hipStream_t stream) {
     case 4: hipLaunchKernelGGL(slstm_conv_kernel<4>, grid, block, 0, stream, a); break;
     default:
       LRAM_REQUIRE(a.T >= 1 && a.T <= kChunkMaxTokens, "tokens per launch out of range");
-      hipLaunchKernelGGL(slstm_conv_rt_kernel, grid, block, 0, stream, a);
+      hipLaunchKernelGGL(slstm_conv_rt_kernel<false>, grid, block, 0, stream, a);
   }
   LRAM_HIP_CHECK(hipGetLastError());
 }
@@ -956,7 +1011,10 @@ bool slstm_token_supported(int H, int NH) {
 template <int SDH>
 void launch_slstm_token_sdh(const SlstmTokenArgs& a, hipStream_t stream) {
   const dim3 grid((unsigned)(a.NH * (SDH / kSlTokCh)), (unsigned)((a.B + kSlTokEnv - 1) / kSlTokEnv));
-  hipLaunchKernelGGL(slstm_token_kernel<SDH>, grid, dim3(256), 0, stream, a);
+  if (a.hold != nullptr)
+    hipLaunchKernelGGL((slstm_token_kernel<SDH, true>), grid, dim3(256), 0, stream, a);
+  else
+    hipLaunchKernelGGL((slstm_token_kernel<SDH, false>), grid, dim3(256), 0, stream, a);
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
@@ -975,7 +1033,10 @@ void launch_slstm_token(const SlstmTokenArgs& a, hipStream_t stream) {
 
 void launch_slstm_pointwise(const SlstmPointwiseArgs& a, hipStream_t stream) {
   const int64_t n = (int64_t)a.B * a.H;
-  hipLaunchKernelGGL(slstm_pointwise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  if (a.hold != nullptr)
+    hipLaunchKernelGGL(slstm_pointwise_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  else
+    hipLaunchKernelGGL(slstm_pointwise_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
   LRAM_HIP_CHECK(hipGetLastError());
 }
 

@@ -61,6 +61,10 @@ _SYMBOLS = {
                                              _VP, _VP]),
     "lram_score_ragged": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP, ctypes.c_int32, _VP, _VP, ctypes.c_int32, _VP, _VP,
                                            _VP, ctypes.c_int32, ctypes.c_double, _VP, _VP, _VP, _VP, _VP]),
+    "lram_prefill_append": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP, ctypes.c_int32, _VP, _VP, ctypes.c_int32, _VP,
+                                             _VP, _VP]),
+    "lram_score_append": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP, ctypes.c_int32, _VP, _VP, ctypes.c_int32, _VP, _VP,
+                                           _VP, ctypes.c_int32, ctypes.c_double, _VP, _VP, _VP, _VP, _VP]),
     "lram_context_plan": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, _VP, ctypes.c_int32, _VP, ctypes.c_int32,
                                            ctypes.POINTER(ctypes.c_int32)]),
     "lram_score_last": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, ctypes.c_double, _VP, _VP]),
@@ -518,13 +522,16 @@ class Engine:
 
     def prefill(self, obs_seq: torch.Tensor, rtg_seq: torch.Tensor, reward_seq: torch.Tensor,
                 reset_mask: Optional[torch.Tensor] = None, discrete=False, obs_is_embedding: bool = False,
-                want_action: bool = True, lengths=None):
+                want_action: bool = True, lengths=None, append: bool = False):
         """L stored timesteps in one call ([B, L, state_dim], [B, L], [B, L]); == L sequential step() calls.
         Returns (actions, tokens) of the last timestep (None when want_action is False).
         `lengths` (list / array / integer tensor of B entries, moved to the host; lram_prefill_ragged): env b's context is rows
         [b, :lengths[b]] (left-aligned; the rows behind it are ignored), its state afterwards is that of its own context and its
         action the one at its own last timestep.  A length below L replaces the slot's state (the slot is reset first whatever
-        `reset_mask` says); length L behaves as without lengths; length 0 leaves the slot alone (action 0, token -1)."""
+        `reset_mask` says); length L behaves as without lengths; length 0 leaves the slot alone (action 0, token -1).
+        `append=True` with lengths (lram_prefill_append): env b's lengths[b] timesteps are APPENDED to the state the slot holds;
+        `reset_mask[b]` alone decides whether it restarts before its first timestep (no mask: nobody does), and a slot of
+        length 0 is held -- no kernel writes its state.  Without lengths, append changes nothing: the dense call."""
         self._need_all_live("prefill")
         B, spec = self.batch, self.spec
         L = obs_seq.shape[1]
@@ -538,9 +545,10 @@ class Engine:
         tok = self._tokens if want_action else None
         if lengths is not None:
             n = _i32_array(check_context_lengths(lengths, B, L))
-            _check(self.lib, self.lib.lram_prefill_ragged(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq),
-                                                          _ptr(reward_seq), int(L), n, _ptr(reset_mask), _head_mode(discrete),
-                                                          _ptr(act), _ptr(tok), _stream_ptr(self.device)))
+            fn = self.lib.lram_prefill_append if append else self.lib.lram_prefill_ragged
+            _check(self.lib, fn(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq),
+                                _ptr(reward_seq), int(L), n, _ptr(reset_mask), _head_mode(discrete),
+                                _ptr(act), _ptr(tok), _stream_ptr(self.device)))
             return (act, tok) if want_action else (None, None)
         _check(self.lib, self.lib.lram_prefill(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq),
                                                _ptr(reward_seq), int(L), _ptr(reset_mask), _head_mode(discrete), _ptr(act),
@@ -551,7 +559,7 @@ class Engine:
               actions: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None,
               valid: Optional[torch.Tensor] = None, reset_mask: Optional[torch.Tensor] = None, discrete=False,
               over: str = "vocab", temperature: float = 1.0, want=("actions", "tokens", "logp"), logits: bool = False,
-              obs_is_embedding: bool = False, lengths=None) -> ScoreResult:
+              obs_is_embedding: bool = False, lengths=None, append: bool = False) -> ScoreResult:
         """Score L stored timesteps in one call (lram_score): prefill() with the action head at EVERY timestep -- the
         reference's no-cache forward plus the loss it takes from the logits (universal_decision_transformer_sb3.py:398-434).
         `actions` float32 [B, L, act_dim] (recorded actions, tokenised on the device) or `tokens` int32 [B, L, act_dim] are the
@@ -560,7 +568,8 @@ class Engine:
         picks from; `temperature` multiplies the logits.  `want` names the outputs among "actions", "tokens", "logp";
         logits=True adds the raw logits.  The state afterwards equals prefill()'s; nothing is drawn in sampling mode.
         `lengths` as in prefill() (lram_score_ragged): rows [b, l] with l >= lengths[b] are masked, and the state afterwards is
-        that of every env's own context."""
+        that of every env's own context.  `append=True` with lengths (lram_score_append): as in prefill() -- the contexts
+        continue the slots' states, which is how a trajectory longer than one call is scored window by window."""
         self._need_all_live("score")
         B, spec = self.batch, self.spec
         if obs_seq.dim() != 3:
@@ -593,11 +602,12 @@ class Engine:
             logits=torch.zeros(B, L, A, spec.n_vocab, dtype=torch.float32, device=self.device) if logits else None)
         if lengths is not None:
             n = _i32_array(check_context_lengths(lengths, B, L))
-            _check(self.lib, self.lib.lram_score_ragged(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq),
-                                                        _ptr(reward_seq), int(L), n, _ptr(reset_mask), _head_mode(discrete),
-                                                        _ptr(actions), _ptr(tokens), _ptr(valid), _over_mode(over),
-                                                        float(temperature), _ptr(res.actions), _ptr(res.tokens), _ptr(res.logp),
-                                                        _ptr(res.logits), _stream_ptr(self.device)))
+            fn = self.lib.lram_score_append if append else self.lib.lram_score_ragged
+            _check(self.lib, fn(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq),
+                                _ptr(reward_seq), int(L), n, _ptr(reset_mask), _head_mode(discrete),
+                                _ptr(actions), _ptr(tokens), _ptr(valid), _over_mode(over),
+                                float(temperature), _ptr(res.actions), _ptr(res.tokens), _ptr(res.logp),
+                                _ptr(res.logits), _stream_ptr(self.device)))
             return res
         _check(self.lib, self.lib.lram_score(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq), _ptr(reward_seq),
                                              int(L), _ptr(reset_mask), _head_mode(discrete), _ptr(actions), _ptr(tokens),
