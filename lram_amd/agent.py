@@ -494,6 +494,24 @@ class RecurrentAgent:
             return actions[:, :1].to(torch.int64)
         return actions if env_act_dim is None else actions[:, :env_act_dim]
 
+    def _prepare_contexts(self, observations, returns_to_go, rewards, lengths):
+        """What the stored-context calls share: observations [B, L, obs_dim] padded and normalised (_prepare_obs), returns_to_go
+        and rewards (None: zeros) as float32 [B, L] on the device, `lengths` checked (check_context_lengths; None stays None)
+        and the head mode the engine is to use.  Returns (obs, rtg, rew, lengths, discrete)."""
+        B = self.n_envs
+        if observations.dim() != 3 or observations.shape[0] != B:
+            raise ValueError(f"observations: expected [{B}, L, obs_dim], got {tuple(observations.shape)}")
+        L = observations.shape[1]
+        if lengths is not None:
+            lengths = check_context_lengths(torch.as_tensor(lengths).reshape(-1), B, L)
+        obs, _ = self._prepare_obs(observations.reshape(B * L, -1))
+        obs = obs.view(B, L, -1).contiguous()
+        rtg = returns_to_go.to(self.device, torch.float32).reshape(B, L).contiguous()
+        rew = torch.zeros(B, L, dtype=torch.float32, device=self.device) if rewards is None else \
+            rewards.to(self.device, torch.float32).reshape(B, L).contiguous()
+        discrete = "per_slot" if getattr(self, "slot_table", None) is not None else self.is_discrete
+        return obs, rtg, rew, lengths, discrete
+
     # ---- grading: stored trajectories and the actions just taken --------------------------------------
     @torch.no_grad()
     def score_trajectories(self, observations: torch.Tensor, returns_to_go: torch.Tensor,
@@ -517,15 +535,8 @@ class RecurrentAgent:
         that of each env's own timesteps, as for the single call (up to fp32 rounding: the chunks differ); the engine embeds
         B x W raw observations per call instead of B x L, which lifts the single call's 2 GiB bound.  Appended contexts never
         replace a state, so reset=False with shorter lengths is accepted here.  window=None (or W >= L): the single call."""
-        B = self.n_envs
-        if observations.dim() != 3 or observations.shape[0] != B:
-            raise ValueError(f"observations: expected [{B}, L, obs_dim], got {tuple(observations.shape)}")
-        L = observations.shape[1]
-        obs, _ = self._prepare_obs(observations.reshape(B * L, -1))
-        obs = obs.view(B, L, -1).contiguous()
-        rtg = returns_to_go.to(self.device, torch.float32).reshape(B, L).contiguous()
-        rew = torch.zeros(B, L, dtype=torch.float32, device=self.device) if rewards is None else \
-            rewards.to(self.device, torch.float32).reshape(B, L).contiguous()
+        obs, rtg, rew, lengths, discrete = self._prepare_contexts(observations, returns_to_go, rewards, lengths)
+        B, L = rtg.shape
         target = None
         if actions is not None:
             a = actions.to(self.device, torch.float32).reshape(B, L, -1)
@@ -536,14 +547,11 @@ class RecurrentAgent:
         if window is not None and int(window) < 1:
             raise ValueError(f"score_trajectories: window must be >= 1, got {window}")
         windowed = window is not None and int(window) < L
-        if lengths is not None:
-            lengths = check_context_lengths(torch.as_tensor(lengths).reshape(-1), B, L)
-            if not windowed and not reset and any(0 < n < L for n in lengths):
-                raise ValueError("score_trajectories: a context shorter than L replaces the env's state; reset=False cannot "
-                                 "be combined with a length in 1 .. L - 1")
+        if lengths is not None and not windowed and not reset and any(0 < n < L for n in lengths):
+            raise ValueError("score_trajectories: a context shorter than L replaces the env's state; reset=False cannot "
+                             "be combined with a length in 1 .. L - 1")
         mask = torch.ones(B, dtype=torch.uint8, device=self.device) if reset else None
         want = tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "logp" or target is not None)
-        discrete = "per_slot" if getattr(self, "slot_table", None) is not None else self.is_discrete
         if not windowed:
             return self.engine.score(obs, rtg, rew, actions=target, reset_mask=mask, discrete=discrete, over=over,
                                      temperature=temperature, want=want, logits=logits, lengths=lengths)
@@ -578,23 +586,13 @@ class RecurrentAgent:
         the envs that start from an empty state before their first timestep.  want_action=True returns the action at each env's
         own last timestep (as predict_batch returns it; 0 for an env of length 0), else None."""
         B = self.n_envs
-        if observations.dim() != 3 or observations.shape[0] != B:
-            raise ValueError(f"observations: expected [{B}, L, obs_dim], got {tuple(observations.shape)}")
-        L = observations.shape[1]
-        if lengths is not None:
-            lengths = check_context_lengths(torch.as_tensor(lengths).reshape(-1), B, L)
-        obs, _ = self._prepare_obs(observations.reshape(B * L, -1))
-        obs = obs.view(B, L, -1).contiguous()
-        rtg = returns_to_go.to(self.device, torch.float32).reshape(B, L).contiguous()
-        rew = torch.zeros(B, L, dtype=torch.float32, device=self.device) if rewards is None else \
-            rewards.to(self.device, torch.float32).reshape(B, L).contiguous()
+        obs, rtg, rew, lengths, discrete = self._prepare_contexts(observations, returns_to_go, rewards, lengths)
         mask = None
         if restart is not None:
             mask = torch.as_tensor(restart).reshape(-1)
             if mask.shape[0] != B:
                 raise ValueError(f"restart: expected {B} entries (one per env), got {mask.shape[0]}")
             mask = (mask != 0).to(self.device, torch.uint8).contiguous()
-        discrete = "per_slot" if getattr(self, "slot_table", None) is not None else self.is_discrete
         actions, _ = self.engine.prefill(obs, rtg, rew, reset_mask=mask, discrete=discrete, want_action=want_action,
                                          lengths=lengths, append=True)
         if not want_action:
@@ -611,18 +609,8 @@ class RecurrentAgent:
         action at each env's own last timestep (as predict_batch returns it), else None.  Image observations are not taken
         here, as in score_trajectories."""
         B = self.n_envs
-        if observations.dim() != 3 or observations.shape[0] != B:
-            raise ValueError(f"observations: expected [{B}, L, obs_dim], got {tuple(observations.shape)}")
-        L = observations.shape[1]
-        if lengths is not None:
-            lengths = check_context_lengths(torch.as_tensor(lengths).reshape(-1), B, L)
-        obs, _ = self._prepare_obs(observations.reshape(B * L, -1))
-        obs = obs.view(B, L, -1).contiguous()
-        rtg = returns_to_go.to(self.device, torch.float32).reshape(B, L).contiguous()
-        rew = torch.zeros(B, L, dtype=torch.float32, device=self.device) if rewards is None else \
-            rewards.to(self.device, torch.float32).reshape(B, L).contiguous()
+        obs, rtg, rew, lengths, discrete = self._prepare_contexts(observations, returns_to_go, rewards, lengths)
         mask = torch.ones(B, dtype=torch.uint8, device=self.device)
-        discrete = "per_slot" if getattr(self, "slot_table", None) is not None else self.is_discrete
         actions, _ = self.engine.prefill(obs, rtg, rew, reset_mask=mask, discrete=discrete, want_action=want_action,
                                          lengths=lengths)
         if not want_action:

@@ -297,22 +297,19 @@ struct ScoreArgs {
 };
 void launch_action_score(const ScoreArgs& a, hipStream_t stream);
 
-// Stored contexts of per-env length (context_kernels.hip; lram_prefill_ragged / lram_score_ragged).  start[b] = L - n_b is the
-// call-timestep at which env b's context begins inside a call of L timesteps (n_b = 0: start[b] = L, the slot only sees padding).
+// Stored contexts of per-env length (context_kernels.hip; the ragged and append entries).  start[b] = L - n_b is the
+// call-timestep at which env b's context begins inside a call of L timesteps (n_b = 0: start[b] = L, the slot only sees padding or is held).
 // launch_embed_chunk with a start per env: the token rows of call-timesteps t0 .. t0 + steps - 1; env b's rows of timestep t come
 // from row t - start[b] of its (left-aligned) emb / rtg / rew, rows with t < start[b] are zeros.
 void launch_embed_chunk_ragged(float* x, const float* emb, int64_t emb_stride, const float* rtg, const float* rew, int64_t in_stride,
                                const int32_t* start, int t0, const float* w_rtg, const float* b_rtg, const float* w_rew,
                                const float* b_rew, int B, int steps, int T, int D, hipStream_t stream);
-// mask[c][b] = 1 where env b is reset at the start of chunk c: its context starts there and is shorter than the call
-// (start[b] == chunk_start[c], 0 < start[b] < L); a full-length env (start[b] == 0) takes reset[b] (nullable) on chunk 0.
-void launch_context_masks(uint8_t* mask, const int32_t* start, const int32_t* chunk_start, const uint8_t* reset, int n_chunks,
-                          int B, int L, hipStream_t stream);
-// The append entries' rows (lram_prefill_append / lram_score_append): hold[c][b] = 1 where env b has not started by chunk c
-// (start[b] > chunk_start[c]: the state kernels write nothing of it), mask[c][b] = 1 where it starts at chunk c and the caller's
-// reset[b] (nullable) is set -- an env continues its state unless the caller restarts it.
-void launch_context_append_masks(uint8_t* hold, uint8_t* mask, const int32_t* start, const int32_t* chunk_start, const uint8_t* reset,
-                                 int n_chunks, int B, int L, hipStream_t stream);
+// The two flag rows of every chunk: mask[c][b] = 1 where env b starts at chunk c and restarts from an empty state -- where the
+// caller's reset[b] (nullable) is set, and with `replace` (the ragged entries; not the append ones) whenever 0 < start[b];
+// hold[c][b] = 1 where it has not started by chunk c (start[b] > chunk_start[c]: handed to the state kernels by the append
+// entries, which then write nothing of it).
+void launch_context_flags(uint8_t* hold, uint8_t* mask, const int32_t* start, const int32_t* chunk_start, const uint8_t* reset,
+                          bool replace, int n_chunks, int B, int L, hipStream_t stream);
 // fill values (logp 0, token -1, action 0) into the padded rows [b, L - start[b] + t], t = 0 .. steps - 1, of [B, L, act_dim]
 // tensors (each nullable): the call-timesteps ahead of the first chunk, which no score launch covers
 void launch_score_fill_ragged(float* actions, int32_t* tokens, float* logp, const int32_t* start, int B, int L, int steps,

@@ -1,14 +1,15 @@
-// Stored contexts of per-env length (lram_prefill_ragged / lram_score_ragged, and their append forms): the kernels that stand between the caller's
-// left-aligned [B, L, ...] tensors and a call whose contexts are END-aligned -- env b's context of n_b timesteps occupies the
-// call-timesteps start[b] = L - n_b .. L - 1.  No recurrent kernel knows about lengths: these kernels feed them zero tokens ahead
-// of an env's context, build the per-chunk reset masks that empty the env's state at its first timestep, and put the head's
-// outputs back at the left-aligned rows (the score sink's row arithmetic lives beside its dense twin, score_kernels.hip).
+// Stored contexts of per-env length (lram_prefill_ragged / lram_score_ragged, and their append forms): the kernels that stand
+// between the caller's left-aligned [B, L, ...] tensors and a call whose contexts are END-aligned -- env b's context of n_b
+// timesteps occupies the call-timesteps start[b] = L - n_b .. L - 1.  No recurrent kernel knows about lengths: these kernels feed
+// them zero tokens ahead of an env's context, build the per-chunk flags that restart an env at its first timestep (and, for the
+// append entries, hold it until then), and put the head's outputs back at the left-aligned rows (the score sink's row arithmetic
+// lives beside its dense twin, score_kernels.hip).
 //
 // Reference computation replaced: the padding + attention_mask handling of batches of unequal trajectories in the no-cache
 // forward (src/algos/universal_decision_transformer_sb3.py:398-434) and the per-env context windows of the evaluation loop
 // (src/algos/decision_transformer_sb3.py:628-666), here for a recurrent state.
 //
-// All five kernels move a few bytes per (env, timestep): one thread per 4 channels (float4) or per output element; the only
+// All four kernels move a few bytes per (env, timestep): one thread per 4 channels (float4) or per output element; the only
 // branch, t < start[b], is taken per (env, timestep) row.
 #include "common.h"
 
@@ -45,29 +46,20 @@ __global__ __launch_bounds__(256) void embed_chunk_ragged_kernel(float* x, const
   *reinterpret_cast<float4*>(row + 2 * D) = make_float4(r * wr.x + br.x, r * wr.y + br.y, r * wr.z + br.z, r * wr.w + br.w);
 }
 
-__global__ __launch_bounds__(256) void context_masks_kernel(uint8_t* mask, const int32_t* start, const int32_t* chunk_start,
-                                                            const uint8_t* reset, int n_chunks, int B, int L) {
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= (int64_t)n_chunks * B) return;
-  const int c = (int)(gid / B), b = (int)(gid - (int64_t)c * B);
-  const int s = start[b];
-  uint8_t m = (s > 0 && s < L && s == chunk_start[c]) ? 1 : 0;
-  if (c == 0 && s == 0 && reset != nullptr && reset[b] != 0) m = 1;
-  mask[gid] = m;
-}
-
-// The append entries' two rows per chunk (lram_prefill_append / lram_score_append): an env that has not started yet is HELD -- the
-// state kernels write nothing of it (device_math.h: env_held) -- and an env restarts at its own first timestep only where the
-// caller's mask says so.  start[b] == L (no context) is held in every chunk; a held env is never reset in the same chunk.
-__global__ __launch_bounds__(256) void context_append_masks_kernel(uint8_t* hold, uint8_t* mask, const int32_t* start,
-                                                                   const int32_t* chunk_start, const uint8_t* reset, int n_chunks,
-                                                                   int B, int L) {
+// The two flag rows of every chunk c, for every env b (s = start[b]).  mask[c][b]: the env restarts from an empty state at the
+// chunk's start, which is its own first timestep -- where the caller's mask says so, and with `replace` (lram_prefill_ragged /
+// lram_score_ragged) also wherever its context is shorter than the call.  hold[c][b]: the env has not started by the chunk; the
+// append entries pass the row to the state kernels, which then write nothing of the env (device_math.h: env_held), s == L (no
+// context) in every chunk.  A held env is never reset in the same chunk.
+__global__ __launch_bounds__(256) void context_flags_kernel(uint8_t* hold, uint8_t* mask, const int32_t* start,
+                                                            const int32_t* chunk_start, const uint8_t* reset, int replace,
+                                                            int n_chunks, int B, int L) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (int64_t)n_chunks * B) return;
   const int c = (int)(gid / B), b = (int)(gid - (int64_t)c * B);
   const int s = start[b], cs = chunk_start[c];
   hold[gid] = s > cs ? 1 : 0;
-  mask[gid] = (s == cs && s < L && reset != nullptr && reset[b] != 0) ? 1 : 0;
+  mask[gid] = (s == cs && s < L && ((replace && s > 0) || (reset != nullptr && reset[b] != 0))) ? 1 : 0;
 }
 
 __global__ __launch_bounds__(256) void score_fill_ragged_kernel(float* actions, int32_t* tokens, float* logp, const int32_t* start,
@@ -109,21 +101,12 @@ void launch_embed_chunk_ragged(float* x, const float* emb, int64_t emb_stride, c
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
-void launch_context_masks(uint8_t* mask, const int32_t* start, const int32_t* chunk_start, const uint8_t* reset, int n_chunks,
-                          int B, int L, hipStream_t stream) {
-  LRAM_REQUIRE(mask && start && chunk_start && n_chunks >= 1 && B >= 1 && L >= 1, "context masks: bad argument");
+void launch_context_flags(uint8_t* hold, uint8_t* mask, const int32_t* start, const int32_t* chunk_start, const uint8_t* reset,
+                          bool replace, int n_chunks, int B, int L, hipStream_t stream) {
+  LRAM_REQUIRE(hold && mask && start && chunk_start && n_chunks >= 1 && B >= 1 && L >= 1, "context flags: bad argument");
   const int64_t n = (int64_t)n_chunks * B;
-  hipLaunchKernelGGL(context_masks_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, mask, start, chunk_start,
-                     reset, n_chunks, B, L);
-  LRAM_HIP_CHECK(hipGetLastError());
-}
-
-void launch_context_append_masks(uint8_t* hold, uint8_t* mask, const int32_t* start, const int32_t* chunk_start, const uint8_t* reset,
-                                 int n_chunks, int B, int L, hipStream_t stream) {
-  LRAM_REQUIRE(hold && mask && start && chunk_start && n_chunks >= 1 && B >= 1 && L >= 1, "context append masks: bad argument");
-  const int64_t n = (int64_t)n_chunks * B;
-  hipLaunchKernelGGL(context_append_masks_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, hold, mask, start,
-                     chunk_start, reset, n_chunks, B, L);
+  hipLaunchKernelGGL(context_flags_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, hold, mask, start, chunk_start,
+                     reset, replace ? 1 : 0, n_chunks, B, L);
   LRAM_HIP_CHECK(hipGetLastError());
 }
 

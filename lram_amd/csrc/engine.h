@@ -243,11 +243,11 @@ struct lram_engine {
                 // sLSTM block uses XN as fp32 while another slice's mLSTM block holds planes
   DevBuf GATES, AMAT, VEC;           // chunkwise mLSTM prefill work buffers (allocated with the first long chunk)
   DevBuf SEQ_EMB;                    // state embeddings of a stored context [B, L, D] (lram_prefill)
-  // Stored contexts of per-env length (lram_prefill_ragged / lram_score_ragged): CTX holds, as bytes of one allocation, int32
-  // start[B] (call-timestep at which each env's context begins), int32 chunk_start[L] and the per-chunk reset masks
-  // uint8[n_chunks, B]; KEEP the state records of the slots the call leaves alone (length 0), saved ahead of the first chunk
-  // and loaded back behind the last.  Both grown outside the launches, as SEQ_EMB is.  The append entries (lram_prefill_append /
-  // lram_score_append) put the per-chunk hold flags uint8[n_chunks, B] behind the reset masks and never touch KEEP.
+  // Stored contexts of per-env length (the ragged and append entries): CTX holds, as bytes of one allocation, int32 start[B]
+  // (call-timestep at which each env's context begins), int32 chunk_start[L], the per-chunk reset masks uint8[n_chunks, B] and
+  // behind them the per-chunk hold flags uint8[n_chunks, B] (passed to the chunks of the append entries only); KEEP the state
+  // records of the slots a replace call leaves alone (length 0), saved ahead of the first chunk and loaded back behind the last.
+  // Both grown outside the launches, as SEQ_EMB is.
   DevBuf CTX, KEEP;
   // lram_score: the head's logits for a block of (env, timestep) rows of one chunk, one region per chunk lane / env slice in
   // flight.  A region holds at most score_rows rows of act_dim * n_vocab floats (default 4096 rows: 34 MiB at 8 x 274 logits;

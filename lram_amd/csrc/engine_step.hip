@@ -113,17 +113,17 @@ struct Inputs {
   int L;
 };
 
-// Stored contexts of per-env length (lram_prefill_ragged / lram_score_ragged): the contexts are end-aligned inside the call, env b
+// Stored contexts of per-env length (the ragged and append entries): the contexts are end-aligned inside the call, env b
 // starting at call-timestep L - n_b, and the chunks are cut so that every env starts on a chunk boundary (context_plan below).
-// Device pointers into lram_engine::CTX, filled on the call's stream ahead of the first chunk.
+// An env restarts at its own first timestep where its row of that chunk's mask says so; in an append call an env that has not
+// started by a chunk is held in it (Pass::hold).  Device pointers into lram_engine::CTX, filled on the call's stream ahead of the
+// first chunk.
 struct ContextPlan {
   std::vector<int> starts;        // ascending call-timesteps at which the chunks start; the last chunk ends at L
-  std::vector<char> has_reset;    // per chunk: some env is reset at its start (others pass no mask at all, as a dense call does)
-  const int32_t* dev_start = nullptr;   // [B]
-  const uint8_t* dev_masks = nullptr;   // [n_chunks, B]
-  // the append entries (lram_prefill_append / lram_score_append): per chunk, some env has not started yet and is held (Pass::hold)
-  std::vector<char> has_hold;
-  const uint8_t* dev_hold = nullptr;    // [n_chunks, B]
+  // per chunk: some env is reset at its start / held in it (a chunk without one passes no pointer at all, as a dense call does)
+  std::vector<char> has_reset, has_hold;
+  const int32_t* dev_start = nullptr;                      // [B]
+  const uint8_t *dev_masks = nullptr, *dev_hold = nullptr;   // [n_chunks, B] each
 };
 
 // Token front end of one env slice for the chunk of Lc timesteps that starts at timestep l: embeds the chunk's tokens into the
@@ -396,7 +396,7 @@ void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, cons
     const uint8_t* chunk_reset = l == 0 ? reset : nullptr;
     if (plan != nullptr) chunk_reset = plan->has_reset[ci] ? plan->dev_masks + (size_t)ci * e->B : nullptr;
     // (a chunk without a held env passes no hold pointer: it launches what a dense call launches)
-    if (plan != nullptr && plan->dev_hold != nullptr && plan->has_hold[ci]) pass.hold = plan->dev_hold + (size_t)ci * e->B;
+    if (plan != nullptr && plan->has_hold[ci]) pass.hold = plan->dev_hold + (size_t)ci * e->B;
     run_stack(e, pass, Tc, chunk_reset, use, lanes ? lane_s[lane] : hbm);
     if (sink != nullptr && L > 1)
       for (size_t i = 0; i < use.size(); ++i)
@@ -496,28 +496,32 @@ void step_entry(lram_engine* e, const char* who) {
 }
 
 
-// lram_score's refusals (before anything is launched, the recurrent state untouched) and its sink; `who` names the entry.
-ScoreSink score_sink_checked(const lram_engine* e, const char* who, int discrete, const float* dev_target_actions,
-                             const int32_t* dev_target_tokens, const uint8_t* dev_valid, int over, double temperature,
-                             float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits) {
+// The refusals of the score entries for the sink they were handed (before anything is launched, the recurrent state untouched);
+// `who` names the entry.
+void check_score_sink(const lram_engine* e, const char* who, int discrete, const ScoreSink& k) {
   const std::string w(who);
   LRAM_REQUIRE(e->compat_repeat <= 1, w + ": the Mamba repeated-forward mode is on (lram_set_compat_mode, mamba_repeat > 1): "
                                       "its trajectories advance the state once per action dim and are not scored");
-  LRAM_REQUIRE(!(dev_target_actions && dev_target_tokens),
-               w + ": both dev_target_actions and dev_target_tokens are given (at most one)");
-  LRAM_REQUIRE(dev_actions || dev_tokens || dev_logp || dev_logits, w + ": no output is given");
-  LRAM_REQUIRE(!dev_logp || dev_target_actions || dev_target_tokens,
+  LRAM_REQUIRE(!(k.target_actions && k.target_tokens), w + ": both dev_target_actions and dev_target_tokens are given (at most one)");
+  LRAM_REQUIRE(k.actions || k.tokens || k.logp || k.logits, w + ": no output is given");
+  LRAM_REQUIRE(!k.logp || k.target_actions || k.target_tokens,
                w + ": dev_logp needs a target (dev_target_actions or dev_target_tokens)");
-  LRAM_REQUIRE(over == 0 || over == 1, w + ": over must be 0 (the whole vocabulary) or 1 (the selectable range)");
-  LRAM_REQUIRE(temperature > 0.0 && temperature < (double)INFINITY, w + ": temperature must be finite and > 0");
+  LRAM_REQUIRE(k.over == 0 || k.over == 1, w + ": over must be 0 (the whole vocabulary) or 1 (the selectable range)");
+  LRAM_REQUIRE(k.temperature > 0.0 && k.temperature < (double)INFINITY, w + ": temperature must be finite and > 0");
   LRAM_REQUIRE(discrete == 0 || discrete == 1 || discrete == LRAM_HEAD_PER_SLOT, w + ": discrete must be 0, 1 or LRAM_HEAD_PER_SLOT");
   LRAM_REQUIRE(discrete != LRAM_HEAD_PER_SLOT || e->slot_table, w + ": LRAM_HEAD_PER_SLOT needs a slot table (lram_set_slot_table)");
   LRAM_REQUIRE(discrete != 1 || e->cfg.n_discrete >= 1, w + ": a discrete head needs n_discrete >= 1");
-  ScoreSink sink;
-  sink.actions = dev_actions, sink.tokens = dev_tokens, sink.logp = dev_logp, sink.logits = dev_logits;
-  sink.target_actions = dev_target_actions, sink.target_tokens = dev_target_tokens, sink.valid = dev_valid;
-  sink.over = over, sink.temperature = temperature;
-  return sink;
+}
+
+// The length rules of a call of L timesteps over B contexts of per-env length: every length in 0 .. L, not all of them 0.
+void check_lengths(const int32_t* lengths, int B, int L, const std::string& w) {
+  bool any = false;
+  for (int b = 0; b < B; ++b) {
+    LRAM_REQUIRE(lengths[b] >= 0 && lengths[b] <= L, w + ": length " + std::to_string(lengths[b]) + " of env slot " +
+                                                          std::to_string(b) + " is outside 0 .. timesteps = " + std::to_string(L));
+    any = any || lengths[b] > 0;
+  }
+  LRAM_REQUIRE(any, w + ": every length is 0 (no env slot has a context)");
 }
 
 // The chunk plan of a call of L timesteps over contexts of per-env length (include/lram_hip.h: lram_context_plan): pure host code.
@@ -525,14 +529,10 @@ ScoreSink score_sink_checked(const lram_engine* e, const char* who, int discrete
 std::vector<int> context_plan(int L, int cap, const int32_t* lengths, int B, const char* who) {
   const std::string w(who);
   LRAM_REQUIRE(L >= 1 && cap >= 1 && B >= 1 && lengths != nullptr, w + ": bad argument (timesteps, cap, batch >= 1, lengths given)");
+  check_lengths(lengths, B, L, w);
   std::vector<char> begins(L, 0);   // begins[t]: some env with a context starts at call-timestep t
-  bool any = false;
-  for (int b = 0; b < B; ++b) {
-    LRAM_REQUIRE(lengths[b] >= 0 && lengths[b] <= L, w + ": length " + std::to_string(lengths[b]) + " of env slot " +
-                                                          std::to_string(b) + " is outside 0 .. timesteps = " + std::to_string(L));
-    if (lengths[b] > 0) begins[L - lengths[b]] = 1, any = true;
-  }
-  LRAM_REQUIRE(any, w + ": every length is 0 (no env slot has a context)");
+  for (int b = 0; b < B; ++b)
+    if (lengths[b] > 0) begins[L - lengths[b]] = 1;
   std::vector<int> bounds;
   for (int t = 0; t < L; ++t)
     if (begins[t]) bounds.push_back(t);
@@ -550,31 +550,26 @@ std::vector<int> context_plan(int L, int cap, const int32_t* lengths, int B, con
   return starts;
 }
 
-// What lram_prefill_ragged and lram_score_ragged share.  check(): everything that refuses the call, before anything is launched or
-// allocated.  run(): the save of the kept slots, the plan's device tables, the chunks (`launch` runs timesteps_launches with the
-// plan), the load of the kept slots.  A call whose lengths all equal `timesteps` never gets here: it is the dense entry's.
-// `append` (lram_prefill_append / lram_score_append): an env's context continues the state the slot holds.  An env that has not
-// started by a chunk is HELD in it (ContextPlan::dev_hold -> Pass::hold) instead of being fed padding and reset at its start, so
-// the slots of length 0 need no record saved and loaded back: KEEP is not touched and no memory is asked for.
+// The per-env lengths of a stored-context call (the ragged and append entries).  check(): everything that refuses the call for its
+// lengths, before anything is launched or allocated.  run(): the plan and its device tables, then the chunks (`launch` runs
+// timesteps_launches with the plan).  A call whose lengths all equal `timesteps` never gets to run(): it is the dense entry's.
+// What an env sees ahead of its context differs by kind.  Replace (the ragged entries): zero tokens through every kernel and a
+// reset at its own first timestep, whatever the caller's mask says; the slots of length 0 have their records saved into KEEP
+// ahead of the chunks and loaded back behind them.  `append`: the env is HELD in every chunk it has not started by
+// (ContextPlan::dev_hold -> Pass::hold: no kernel writes its state) and restarts only where the caller's mask says so; KEEP is
+// not touched and no memory is asked for.
 struct RaggedCall {
   lram_engine* e;
-  std::string w;
+  std::string w;   // the entry's name
   int L;
   const int32_t* lengths;
-  std::vector<int32_t> kept;   // slots with length 0
+  ContextPlan plan;   // (made by run())
   bool append = false;
 
-  void check(int obs_is_embedding) {
+  void check(int obs_is_embedding) const {
     const lram_config& c = e->cfg;
     LRAM_REQUIRE(lengths != nullptr, w + ": host_lengths is NULL");
-    bool any = false;
-    for (int b = 0; b < e->B; ++b) {
-      LRAM_REQUIRE(lengths[b] >= 0 && lengths[b] <= L, w + ": length " + std::to_string(lengths[b]) + " of env slot " +
-                                                            std::to_string(b) + " is outside 0 .. timesteps = " + std::to_string(L));
-      any = any || lengths[b] > 0;
-      if (lengths[b] == 0) kept.push_back(b);
-    }
-    LRAM_REQUIRE(any, w + ": every length is 0 (no env slot has a context)");
+    check_lengths(lengths, e->B, L, w);
     LRAM_REQUIRE(c.d_model % 4 == 0, w + ": per-env lengths need d_model to be a multiple of 4 (the chunk front end moves float4)");
     LRAM_REQUIRE(e->compat_repeat <= 1, w + ": the Mamba repeated-forward mode is on (lram_set_compat_mode, mamba_repeat > 1): its "
                                             "trajectories advance the state once per action dim and take no per-env lengths");
@@ -592,8 +587,11 @@ struct RaggedCall {
   template <typename Launch>
   void run(const uint8_t* reset, hipStream_t s, Launch&& launch) {
     const int B = e->B;
+    std::vector<int32_t> kept;   // replace: the slots of length 0
+    for (int b = 0; b < B && !append; ++b)
+      if (lengths[b] == 0) kept.push_back(b);
     // scratch for the kept slots' records: refused, with nothing launched, when it would leave less than 2 GiB free
-    const size_t rec = (size_t)(lram_state_bytes_per_env(e) / 4), need = append ? 0 : kept.size() * rec;
+    const size_t need = kept.size() * (size_t)(lram_state_bytes_per_env(e) / 4);
     if (e->KEEP.n < need) {
       LRAM_HIP_CHECK(hipDeviceSynchronize());
       size_t free_b = 0, total_b = 0;
@@ -603,11 +601,10 @@ struct RaggedCall {
                        std::to_string(need * sizeof(float)) + " bytes) would leave less than 2 GiB of device memory free");
       e->KEEP.alloc(need);
     }
-    ContextPlan plan;
     plan.starts = context_plan(L, L > 1 ? prefill_chunk_steps(e, L) : 1, lengths, B, w.c_str());
     const int n_chunks = (int)plan.starts.size();
-    // CTX: int32 start[B] | int32 chunk_start[L] | uint8 masks[L, B] (| uint8 hold[L, B], append), as floats of one allocation
-    const size_t want = (size_t)B + L + ((size_t)(append ? 2 : 1) * L * B + 3) / 4;
+    // CTX: int32 start[B] | int32 chunk_start[L] | uint8 masks[L, B] | uint8 hold[L, B], as floats of one allocation
+    const size_t want = (size_t)B + L + ((size_t)2 * L * B + 3) / 4;
     if (e->CTX.n < want) {
       LRAM_HIP_CHECK(hipDeviceSynchronize());
       e->CTX.alloc(want);
@@ -615,9 +612,8 @@ struct RaggedCall {
     int32_t* dev_start = reinterpret_cast<int32_t*>(e->CTX.p);
     int32_t* dev_chunk = dev_start + B;
     uint8_t* dev_masks = reinterpret_cast<uint8_t*>(dev_chunk + L);
-    plan.dev_start = dev_start, plan.dev_masks = dev_masks;
-    uint8_t* dev_hold = append ? dev_masks + (size_t)L * B : nullptr;
-    plan.dev_hold = dev_hold;
+    uint8_t* dev_hold = dev_masks + (size_t)L * B;
+    plan.dev_start = dev_start, plan.dev_masks = dev_masks, plan.dev_hold = dev_hold;
     std::vector<int32_t> host(B + n_chunks);
     plan.has_reset.assign(n_chunks, 0);
     plan.has_hold.assign(n_chunks, 0);
@@ -626,25 +622,18 @@ struct RaggedCall {
       host[b] = sb;
       // (every env with a context starts on a chunk boundary: the chunk it starts at)
       const size_t at = sb < L ? std::lower_bound(plan.starts.begin(), plan.starts.end(), sb) - plan.starts.begin() : (size_t)n_chunks;
-      if (append) {   // restarted at its start only where the caller says so; held in every chunk before that one
-        if (sb < L && reset != nullptr) plan.has_reset[at] = 1;
-        for (size_t ci = 0; ci < at; ++ci) plan.has_hold[ci] = 1;
-        continue;
-      }
-      if (sb == 0 && reset != nullptr) plan.has_reset[0] = 1;
-      if (sb > 0 && sb < L) plan.has_reset[at] = 1;
+      // restarted at its start (context_flags_kernel's rule): where the caller's mask may say so; replace: every shorter context
+      if (sb < L && (reset != nullptr || (!append && sb > 0))) plan.has_reset[at] = 1;
+      for (size_t ci = 0; ci < at && append; ++ci) plan.has_hold[ci] = 1;   // append: held in every chunk before that one
     }
     for (int ci = 0; ci < n_chunks; ++ci) host[B + ci] = plan.starts[ci];
     // ---- from here on the call launches ----
     lazy_materialize(e, s);   // stored contexts fold pending windows first (and complete a tail fold)
-    if (!kept.empty() && !append) save_slot_records(e, kept.data(), (int)kept.size(), e->KEEP.p, s);
+    if (!kept.empty()) save_slot_records(e, kept.data(), (int)kept.size(), e->KEEP.p, s);
     // (pageable host memory: the copies have read `host` when they return; the device side is ordered on `s`)
     LRAM_HIP_CHECK(hipMemcpyAsync(dev_start, host.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
     LRAM_HIP_CHECK(hipMemcpyAsync(dev_chunk, host.data() + B, (size_t)n_chunks * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (append)
-      launch_context_append_masks(dev_hold, dev_masks, dev_start, dev_chunk, reset, n_chunks, B, L, s);
-    else
-      launch_context_masks(dev_masks, dev_start, dev_chunk, reset, n_chunks, B, L, s);
+    launch_context_flags(dev_hold, dev_masks, dev_start, dev_chunk, reset, !append, n_chunks, B, L, s);
     {
       // every chunk on the materialised kernels, also the chunks of one timestep that an env-step would take through the lazy
       // read pass: a window left pending by a chunk in the middle of the call would be invisible to the chunk behind it
@@ -656,9 +645,42 @@ struct RaggedCall {
       e->lazy = false;
       launch(plan);
     }
-    if (!kept.empty() && !append) load_slot_records(e, kept.data(), (int)kept.size(), e->KEEP.p, s);
+    if (!kept.empty()) load_slot_records(e, kept.data(), (int)kept.size(), e->KEEP.p, s);
   }
 };
+
+// What the six stored-context entries share, in this order: the refusals (the recurrent state is untouched by a refused call), the
+// launches, the draw count.  `who` names the entry in every message.  rc: the per-env lengths of the ragged and append entries,
+// null for the dense pair.  With a sink (the score entries) the head runs at every timestep and nothing is drawn; without one
+// `actions` / `tokens` (nullable) take the action at every env's own last timestep.
+void stored_context_call(lram_engine* e, const char* who, RaggedCall* rc, const Inputs& in, const uint8_t* reset, int discrete,
+                         float* actions, int32_t* tokens, const ScoreSink* sink, hipStream_t s) {
+  const std::string w(who);
+  step_entry(e, who);
+  require_all_live(e, who);
+  LRAM_REQUIRE(in.obs && in.rtg && in.rew, w + ": null device pointer");
+  LRAM_REQUIRE(in.L >= 1, w + ": timesteps must be >= 1");
+  if (rc != nullptr) rc->check(in.emb);
+  if (sink != nullptr)
+    check_score_sink(e, who, discrete, *sink);
+  else if (actions != nullptr)
+    check_head_mode(e, discrete, who);
+  if (rc == nullptr || rc->dense()) {   // every context of full length: the dense entry's own launches
+    lazy_finish_prefold(e, s);          // (only an env-step takes a tail fold over)
+    timesteps_launches(e, Pass{}, in, reset, discrete, actions, tokens, s, sink);
+  } else {
+    rc->run(reset, s, [&](const ContextPlan& plan) {
+      // the call-timesteps ahead of the first chunk are padding for every env: their rows of the sink take the fill values here
+      if (sink != nullptr)
+        launch_score_fill_ragged(sink->actions, sink->tokens, sink->logp, plan.dev_start, e->B, in.L, plan.starts[0], e->cfg.act_dim, s);
+      timesteps_launches(e, Pass{}, in, nullptr, discrete, actions, tokens, s, sink, &plan);
+      if (sink == nullptr && actions != nullptr)   // slots without a context: 0 / -1 in place of the head's answer to the padding
+        launch_action_fill_kept(actions, tokens, plan.dev_start, e->B, in.L, e->cfg.act_dim, s);
+    });
+  }
+  // (a score is never a draw: the sampling mode and its counter are left alone)
+  if (sink == nullptr && actions != nullptr) sample_draw_advance(e, s);
+}
 }  // namespace
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------
@@ -747,19 +769,13 @@ int32_t lram_step_slots(lram_engine* e, const float* dev_obs, const uint8_t* dev
   });
 }
 
+// The six stored-context entries: dense / ragged (replace) / append, each as prefill and as score -- one body (stored_context_call).
 int32_t lram_prefill(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
                      const float* dev_reward_seq, int32_t timesteps, const uint8_t* dev_reset_mask, int32_t discrete,
                      float* dev_actions, int32_t* dev_tokens, void* stream) {
   return guarded([&] {
-    step_entry(e, "lram_prefill");
-    require_all_live(e, "lram_prefill");
-    LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_prefill: null device pointer");
-    LRAM_REQUIRE(timesteps >= 1, "lram_prefill: timesteps must be >= 1");
-    if (dev_actions != nullptr) check_head_mode(e, discrete, "lram_prefill");
-    lazy_finish_prefold(e, static_cast<hipStream_t>(stream));   // (only an env-step takes a tail fold over)
-    timesteps_launches(e, Pass{}, Inputs{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps}, dev_reset_mask,
-                       discrete, dev_actions, dev_tokens, static_cast<hipStream_t>(stream));
-    if (dev_actions != nullptr) sample_draw_advance(e, static_cast<hipStream_t>(stream));
+    stored_context_call(e, "lram_prefill", nullptr, Inputs{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps},
+                        dev_reset_mask, discrete, dev_actions, dev_tokens, nullptr, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -768,16 +784,9 @@ int32_t lram_score(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embe
                    const float* dev_target_actions, const int32_t* dev_target_tokens, const uint8_t* dev_valid, int32_t over,
                    double temperature, float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits, void* stream) {
   return guarded([&] {
-    step_entry(e, "lram_score");
-    require_all_live(e, "lram_score");
-    LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_score: null device pointer");
-    LRAM_REQUIRE(timesteps >= 1, "lram_score: timesteps must be >= 1");
-    const ScoreSink sink = score_sink_checked(e, "lram_score", discrete, dev_target_actions, dev_target_tokens, dev_valid, over,
-                                              temperature, dev_actions, dev_tokens, dev_logp, dev_logits);
-    lazy_finish_prefold(e, static_cast<hipStream_t>(stream));   // (only an env-step takes a tail fold over)
-    // (never captured, never a draw: the sampling mode and its counter are left alone)
-    timesteps_launches(e, Pass{}, Inputs{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps}, dev_reset_mask,
-                       discrete, nullptr, nullptr, static_cast<hipStream_t>(stream), &sink);
+    const ScoreSink sink{dev_actions, dev_tokens, dev_logp, dev_logits, dev_target_actions, dev_target_tokens, dev_valid, over, temperature};
+    stored_context_call(e, "lram_score", nullptr, Inputs{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps},
+                        dev_reset_mask, discrete, nullptr, nullptr, &sink, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -785,26 +794,9 @@ int32_t lram_prefill_ragged(lram_engine* e, const float* dev_obs_seq, int32_t ob
                             const float* dev_reward_seq, int32_t timesteps, const int32_t* host_lengths,
                             const uint8_t* dev_reset_mask, int32_t discrete, float* dev_actions, int32_t* dev_tokens, void* stream) {
   return guarded([&] {
-    step_entry(e, "lram_prefill_ragged");
-    require_all_live(e, "lram_prefill_ragged");
-    LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_prefill_ragged: null device pointer");
-    LRAM_REQUIRE(timesteps >= 1, "lram_prefill_ragged: timesteps must be >= 1");
-    RaggedCall rc{e, "lram_prefill_ragged", timesteps, host_lengths, {}};
-    rc.check(obs_is_embedding);
-    if (dev_actions != nullptr) check_head_mode(e, discrete, "lram_prefill_ragged");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Inputs in{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps};
-    if (rc.dense()) {            // every context of full length: lram_prefill's own launches
-      lazy_finish_prefold(e, s);   // (only an env-step takes a tail fold over)
-      timesteps_launches(e, Pass{}, in, dev_reset_mask, discrete, dev_actions, dev_tokens, s);
-    } else {
-      rc.run(dev_reset_mask, s, [&](const ContextPlan& plan) {
-        timesteps_launches(e, Pass{}, in, nullptr, discrete, dev_actions, dev_tokens, s, nullptr, &plan);
-        if (dev_actions != nullptr)   // slots without a context: 0 / -1 in place of the head's answer to the padding
-          launch_action_fill_kept(dev_actions, dev_tokens, plan.dev_start, e->B, timesteps, e->cfg.act_dim, s);
-      });
-    }
-    if (dev_actions != nullptr) sample_draw_advance(e, s);
+    RaggedCall rc{e, "lram_prefill_ragged", timesteps, host_lengths, {}, false};
+    stored_context_call(e, rc.w.c_str(), &rc, Inputs{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps},
+                        dev_reset_mask, discrete, dev_actions, dev_tokens, nullptr, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -814,26 +806,10 @@ int32_t lram_score_ragged(lram_engine* e, const float* dev_obs_seq, int32_t obs_
                           const int32_t* dev_target_tokens, const uint8_t* dev_valid, int32_t over, double temperature,
                           float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits, void* stream) {
   return guarded([&] {
-    step_entry(e, "lram_score_ragged");
-    require_all_live(e, "lram_score_ragged");
-    LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_score_ragged: null device pointer");
-    LRAM_REQUIRE(timesteps >= 1, "lram_score_ragged: timesteps must be >= 1");
-    RaggedCall rc{e, "lram_score_ragged", timesteps, host_lengths, {}};
-    rc.check(obs_is_embedding);
-    const ScoreSink sink = score_sink_checked(e, "lram_score_ragged", discrete, dev_target_actions, dev_target_tokens, dev_valid, over,
-                                              temperature, dev_actions, dev_tokens, dev_logp, dev_logits);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Inputs in{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps};
-    if (rc.dense()) {            // every context of full length: lram_score's own launches
-      lazy_finish_prefold(e, s);   // (only an env-step takes a tail fold over)
-      timesteps_launches(e, Pass{}, in, dev_reset_mask, discrete, nullptr, nullptr, s, &sink);
-      return;
-    }
-    rc.run(dev_reset_mask, s, [&](const ContextPlan& plan) {
-      // the call-timesteps ahead of the first chunk are padding for every env: their rows take the fill values here
-      launch_score_fill_ragged(dev_actions, dev_tokens, dev_logp, plan.dev_start, e->B, timesteps, plan.starts[0], e->cfg.act_dim, s);
-      timesteps_launches(e, Pass{}, in, nullptr, discrete, nullptr, nullptr, s, &sink, &plan);
-    });
+    RaggedCall rc{e, "lram_score_ragged", timesteps, host_lengths, {}, false};
+    const ScoreSink sink{dev_actions, dev_tokens, dev_logp, dev_logits, dev_target_actions, dev_target_tokens, dev_valid, over, temperature};
+    stored_context_call(e, rc.w.c_str(), &rc, Inputs{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps},
+                        dev_reset_mask, discrete, nullptr, nullptr, &sink, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -842,26 +818,9 @@ int32_t lram_prefill_append(lram_engine* e, const float* dev_obs_seq, int32_t ob
                             const uint8_t* dev_reset_mask, int32_t discrete, float* dev_actions, int32_t* dev_tokens, void* stream) {
   return guarded([&] {
     LRAM_REQUIRE(e != nullptr, "lram_prefill_append: null engine");
-    step_entry(e, "lram_prefill_append");
-    require_all_live(e, "lram_prefill_append");
-    LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_prefill_append: null device pointer");
-    LRAM_REQUIRE(timesteps >= 1, "lram_prefill_append: timesteps must be >= 1");
     RaggedCall rc{e, "lram_prefill_append", timesteps, host_lengths, {}, true};
-    rc.check(obs_is_embedding);
-    if (dev_actions != nullptr) check_head_mode(e, discrete, "lram_prefill_append");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Inputs in{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps};
-    if (rc.dense()) {            // every context of full length: lram_prefill's own launches
-      lazy_finish_prefold(e, s);   // (only an env-step takes a tail fold over)
-      timesteps_launches(e, Pass{}, in, dev_reset_mask, discrete, dev_actions, dev_tokens, s);
-    } else {
-      rc.run(dev_reset_mask, s, [&](const ContextPlan& plan) {
-        timesteps_launches(e, Pass{}, in, nullptr, discrete, dev_actions, dev_tokens, s, nullptr, &plan);
-        if (dev_actions != nullptr)   // slots without a context: 0 / -1 in place of the head's answer to the padding
-          launch_action_fill_kept(dev_actions, dev_tokens, plan.dev_start, e->B, timesteps, e->cfg.act_dim, s);
-      });
-    }
-    if (dev_actions != nullptr) sample_draw_advance(e, s);
+    stored_context_call(e, rc.w.c_str(), &rc, Inputs{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps},
+                        dev_reset_mask, discrete, dev_actions, dev_tokens, nullptr, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -872,26 +831,10 @@ int32_t lram_score_append(lram_engine* e, const float* dev_obs_seq, int32_t obs_
                           float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits, void* stream) {
   return guarded([&] {
     LRAM_REQUIRE(e != nullptr, "lram_score_append: null engine");
-    step_entry(e, "lram_score_append");
-    require_all_live(e, "lram_score_append");
-    LRAM_REQUIRE(dev_obs_seq && dev_rtg_seq && dev_reward_seq, "lram_score_append: null device pointer");
-    LRAM_REQUIRE(timesteps >= 1, "lram_score_append: timesteps must be >= 1");
     RaggedCall rc{e, "lram_score_append", timesteps, host_lengths, {}, true};
-    rc.check(obs_is_embedding);
-    const ScoreSink sink = score_sink_checked(e, "lram_score_append", discrete, dev_target_actions, dev_target_tokens, dev_valid, over,
-                                              temperature, dev_actions, dev_tokens, dev_logp, dev_logits);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Inputs in{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps};
-    if (rc.dense()) {            // every context of full length: lram_score's own launches
-      lazy_finish_prefold(e, s);   // (only an env-step takes a tail fold over)
-      timesteps_launches(e, Pass{}, in, dev_reset_mask, discrete, nullptr, nullptr, s, &sink);
-      return;
-    }
-    rc.run(dev_reset_mask, s, [&](const ContextPlan& plan) {
-      // the call-timesteps ahead of the first chunk are padding for every env: their rows take the fill values here
-      launch_score_fill_ragged(dev_actions, dev_tokens, dev_logp, plan.dev_start, e->B, timesteps, plan.starts[0], e->cfg.act_dim, s);
-      timesteps_launches(e, Pass{}, in, nullptr, discrete, nullptr, nullptr, s, &sink, &plan);
-    });
+    const ScoreSink sink{dev_actions, dev_tokens, dev_logp, dev_logits, dev_target_actions, dev_target_tokens, dev_valid, over, temperature};
+    stored_context_call(e, rc.w.c_str(), &rc, Inputs{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps},
+                        dev_reset_mask, discrete, nullptr, nullptr, &sink, static_cast<hipStream_t>(stream));
   });
 }
 

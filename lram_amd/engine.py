@@ -520,6 +520,31 @@ class Engine:
                                                   _stream_ptr(self.device)))
         return actions, tokens
 
+    def _stored_context_call(self, kind: str, obs_seq, rtg_seq, reward_seq, reset_mask, obs_is_embedding, lengths, append):
+        """What prefill() and score() share: checks the [B, L, .] inputs and the reset mask, and returns (L, call).  call(*tail)
+        checks and normalises `lengths`, picks the C entry -- dense without lengths, else the append or the ragged (replace)
+        one -- and runs it: the arguments up to the reset mask from here, `tail` (from the head mode on) behind them."""
+        B, spec = self.batch, self.spec
+        L = obs_seq.shape[1]
+        _chk_dev(obs_seq, torch.float32, (B, L, spec.d_model if obs_is_embedding else spec.state_dim), self.device,
+                 "obs_seq")
+        _chk_dev(rtg_seq, torch.float32, (B, L), self.device, "rtg_seq")
+        _chk_dev(reward_seq, torch.float32, (B, L), self.device, "reward_seq")
+        if reset_mask is not None:
+            _chk_dev(reset_mask, torch.uint8, (B,), self.device, "reset_mask")
+        lib = self.lib
+
+        def call(*tail):
+            head = (self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq), _ptr(reward_seq), int(L))
+            tail = (_ptr(reset_mask), *tail, _stream_ptr(self.device))
+            if lengths is None:
+                _check(lib, lib.lram_prefill(*head, *tail) if kind == "prefill" else lib.lram_score(*head, *tail))
+                return
+            fn = {("prefill", False): lib.lram_prefill_ragged, ("prefill", True): lib.lram_prefill_append,
+                  ("score", False): lib.lram_score_ragged, ("score", True): lib.lram_score_append}[kind, bool(append)]
+            _check(lib, fn(*head, _i32_array(check_context_lengths(lengths, B, L)), *tail))
+        return L, call
+
     def prefill(self, obs_seq: torch.Tensor, rtg_seq: torch.Tensor, reward_seq: torch.Tensor,
                 reset_mask: Optional[torch.Tensor] = None, discrete=False, obs_is_embedding: bool = False,
                 want_action: bool = True, lengths=None, append: bool = False):
@@ -533,26 +558,10 @@ class Engine:
         `reset_mask[b]` alone decides whether it restarts before its first timestep (no mask: nobody does), and a slot of
         length 0 is held -- no kernel writes its state.  Without lengths, append changes nothing: the dense call."""
         self._need_all_live("prefill")
-        B, spec = self.batch, self.spec
-        L = obs_seq.shape[1]
-        _chk_dev(obs_seq, torch.float32, (B, L, spec.d_model if obs_is_embedding else spec.state_dim), self.device,
-                 "obs_seq")
-        _chk_dev(rtg_seq, torch.float32, (B, L), self.device, "rtg_seq")
-        _chk_dev(reward_seq, torch.float32, (B, L), self.device, "reward_seq")
-        if reset_mask is not None:
-            _chk_dev(reset_mask, torch.uint8, (B,), self.device, "reset_mask")
+        L, call = self._stored_context_call("prefill", obs_seq, rtg_seq, reward_seq, reset_mask, obs_is_embedding, lengths, append)
         act = self._actions if want_action else None
         tok = self._tokens if want_action else None
-        if lengths is not None:
-            n = _i32_array(check_context_lengths(lengths, B, L))
-            fn = self.lib.lram_prefill_append if append else self.lib.lram_prefill_ragged
-            _check(self.lib, fn(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq),
-                                _ptr(reward_seq), int(L), n, _ptr(reset_mask), _head_mode(discrete),
-                                _ptr(act), _ptr(tok), _stream_ptr(self.device)))
-            return (act, tok) if want_action else (None, None)
-        _check(self.lib, self.lib.lram_prefill(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq),
-                                               _ptr(reward_seq), int(L), _ptr(reset_mask), _head_mode(discrete), _ptr(act),
-                                               _ptr(tok), _stream_ptr(self.device)))
+        call(_head_mode(discrete), _ptr(act), _ptr(tok))
         return (act, tok) if want_action else (None, None)
 
     def score(self, obs_seq: torch.Tensor, rtg_seq: torch.Tensor, reward_seq: torch.Tensor, *,
@@ -574,17 +583,11 @@ class Engine:
         B, spec = self.batch, self.spec
         if obs_seq.dim() != 3:
             raise ValueError("obs_seq must be [B, L, state_dim]")
-        L = obs_seq.shape[1]
         want = (want,) if isinstance(want, str) else tuple(want)
         for w in want:
             if w not in ("actions", "tokens", "logp"):
                 raise ValueError(f'want: unknown output {w!r} (choose among "actions", "tokens", "logp")')
-        _chk_dev(obs_seq, torch.float32, (B, L, spec.d_model if obs_is_embedding else spec.state_dim), self.device,
-                 "obs_seq")
-        _chk_dev(rtg_seq, torch.float32, (B, L), self.device, "rtg_seq")
-        _chk_dev(reward_seq, torch.float32, (B, L), self.device, "reward_seq")
-        if reset_mask is not None:
-            _chk_dev(reset_mask, torch.uint8, (B,), self.device, "reset_mask")
+        L, call = self._stored_context_call("score", obs_seq, rtg_seq, reward_seq, reset_mask, obs_is_embedding, lengths, append)
         if actions is not None:
             _chk_dev(actions, torch.float32, (B, L, spec.act_dim), self.device, "actions")
         if tokens is not None:
@@ -600,19 +603,8 @@ class Engine:
             tokens=torch.zeros(B, L, A, dtype=torch.int32, device=self.device) if "tokens" in want else None,
             logp=torch.zeros(B, L, A, dtype=torch.float32, device=self.device) if "logp" in want else None,
             logits=torch.zeros(B, L, A, spec.n_vocab, dtype=torch.float32, device=self.device) if logits else None)
-        if lengths is not None:
-            n = _i32_array(check_context_lengths(lengths, B, L))
-            fn = self.lib.lram_score_append if append else self.lib.lram_score_ragged
-            _check(self.lib, fn(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq),
-                                _ptr(reward_seq), int(L), n, _ptr(reset_mask), _head_mode(discrete),
-                                _ptr(actions), _ptr(tokens), _ptr(valid), _over_mode(over),
-                                float(temperature), _ptr(res.actions), _ptr(res.tokens), _ptr(res.logp),
-                                _ptr(res.logits), _stream_ptr(self.device)))
-            return res
-        _check(self.lib, self.lib.lram_score(self._h, _ptr(obs_seq), int(obs_is_embedding), _ptr(rtg_seq), _ptr(reward_seq),
-                                             int(L), _ptr(reset_mask), _head_mode(discrete), _ptr(actions), _ptr(tokens),
-                                             _ptr(valid), _over_mode(over), float(temperature), _ptr(res.actions),
-                                             _ptr(res.tokens), _ptr(res.logp), _ptr(res.logits), _stream_ptr(self.device)))
+        call(_head_mode(discrete), _ptr(actions), _ptr(tokens), _ptr(valid), _over_mode(over), float(temperature), _ptr(res.actions),
+             _ptr(res.tokens), _ptr(res.logp), _ptr(res.logits))
         return res
 
     def last_logp(self, tokens: torch.Tensor, over: str = "selectable", temperature: float = 1.0) -> torch.Tensor:

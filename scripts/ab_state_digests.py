@@ -22,6 +22,11 @@ an accumulating call, one digest per shape and form; the "tiles_*" cases are the
 test_tile_kernels_carry_few_row_projections_within_the_parity_bars (the few-row kernel off: split-K and its reduce, gated operand,
 SiLU columns, batched and table-addressed GEMMs on the tile kernels).  --cases takes shell patterns: --cases 'gemm_*' 'tiles_*' 'chunk3_*'.
 
+The stored-context entries have cases of their own as well: CTX_CASES ("ctx_*") runs Engine.prefill / Engine.score with per-env
+lengths after 5 env-steps (no state is empty), every variant on a fresh engine in the case's child: the replace entry with an
+all-ones mask and without a mask, the append entry with the mask 1, 0, 1, 0, 1, 0.  Digests per variant: the returned actions
+and tokens (every ScoreResult tensor of a score), the state tensors above, and the save_slots record of every slot of length 0.
+
 Prints one line per case and a JSON summary; exit status 1 when a digest differs (or a child failed)."""
 import argparse
 import fnmatch
@@ -114,6 +119,25 @@ GEMM_CASES = {
     "gemm_narrow": ("narrow", _NARROW),
     "gemm_narrow16": ("narrow16", _NARROW),
 }
+# stored contexts of per-env length: name -> (geometry, env slots, timesteps, lengths (None: the dense entry), "prefill" | "score",
+# environment[, options]); options: mode = state mode, micro = env slices.  The smallest shapes that reach each path: the 16M plan
+# [0, 9, 17, 28, 38, 46] on the chunkwise kernels over the three lanes, on the token-sequential kernels and one chunk at a time;
+# slots of length 0 in both state modes; two env slices; the geometries without a chunkwise form; the sLSTM instances that spill
+_LEN16 = [47, 47, 30, 30, 9, 1]
+CTX_CASES = {
+    "ctx_16m": ("preset:xlstm_16m", 6, 47, _LEN16, "prefill", {}),
+    "ctx_16m_seq": ("preset:xlstm_16m", 6, 47, _LEN16, "prefill", {"LRAM_PREFILL_CHUNK": "0"}),
+    "ctx_16m_one": ("preset:xlstm_16m", 6, 47, _LEN16, "prefill", {"LRAM_PREFILL_CHUNK": "3"}),
+    "ctx_zero": ("preset:xlstm_16m", 4, 12, [0, 12, 0, 5], "prefill", {}, {"mode": "eager"}),
+    "ctx_zero_lazy": ("preset:xlstm_16m", 4, 12, [0, 12, 0, 5], "prefill", {}, {"mode": "lazy"}),
+    "ctx_micro2": ("preset:xlstm_16m", 6, 13, [13, 13, 8, 8, 3, 1], "prefill", {}, {"micro": 2}),
+    "ctx_xlstm_tiny": ("preset:xlstm_tiny", 4, 9, [9, 6, 2, 0], "prefill", {}),
+    "ctx_mamba_tiny": ("preset:mamba_tiny", 4, 9, [9, 6, 2, 0], "prefill", {}),
+    "ctx_206m": ("preset:xlstm_206m", 3, 6, [6, 3, 0], "prefill", {}),
+    "ctx_score_16m": ("preset:xlstm_16m", 6, 47, _LEN16, "score", {}),
+    "ctx_score_dense": ("preset:xlstm_16m", 6, 21, None, "score", {}),
+}
+CTX_PRE, CTX_APPEND_MASK = 5, [1, 0, 1, 0, 1, 0]
 RESTART_SLOT = 2
 
 
@@ -147,9 +171,76 @@ def child_gemm(name):
     print(json.dumps({"case": name, "digests": digests, "slstm": {}, "mode": kernel}))
 
 
+def _sha(t):
+    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+def state_digests(eng, spec, prefix=""):
+    """One digest per exported state tensor of block 0, of the last block and of the first sLSTM block (Mamba: conv and SSM state of
+    the first and the last block)."""
+    digests = {}
+    if spec.backbone == "mamba":
+        pkv = eng.export_past_key_values()
+        for blk in (0, spec.n_blocks - 1):
+            for which, what in ((0, "conv"), (1, "ssm")):
+                digests[f"{prefix}block{blk}.{what}"] = _sha(pkv[blk][which])
+    blocks = [] if spec.backbone == "mamba" else sorted({0, spec.n_blocks - 1} | set(list(spec.slstm_at)[:1]))
+    for blk in blocks:
+        for which, what in ((0, "planes"), (3, "conv")) if blk in spec.slstm_at else ((0, "C"), (1, "n"), (2, "m"), (3, "conv")):
+            digests[f"{prefix}block{blk}.{what}"] = _sha(eng.export_state_tensor(blk, which))
+    return digests
+
+
+def child_ctx(name):
+    import torch
+    from lram_amd import engine, init_state_dict
+    from tests.helpers import make_inputs
+    geometry, B, L, lengths, kind, _, *opt = CTX_CASES[name]
+    opt = opt[0] if opt else {}
+    spec = case_spec(geometry)
+    dev = torch.device("cuda", 0)
+    sd = init_state_dict(spec, seed=5)
+    seq = make_inputs(spec, B, L + CTX_PRE, seed=41, reset_prob=0.0)
+    obs, rtg, rew = (torch.stack([x[i] for x in seq[:L]], 1).contiguous() for i in range(3))
+    for b, n in enumerate(lengths or []):   # NaN in every padded position
+        obs[b, n:], rtg[b, n:], rew[b, n:] = float("nan"), float("nan"), float("nan")
+    obs, rtg, rew = obs.to(dev), rtg.to(dev), rew.to(dev)
+    target = (torch.rand(B, L, spec.act_dim, generator=torch.Generator().manual_seed(3)) * 2 - 1).to(dev)
+    ones, alternate = torch.ones(B, dtype=torch.uint8, device=dev), torch.tensor(CTX_APPEND_MASK[:B], dtype=torch.uint8, device=dev)
+    variants = [("dense", False, None)] if lengths is None else \
+        [("replace.ones", False, ones), ("replace.nomask", False, None), ("append", True, alternate)]
+    digests, ran = {}, None
+    for variant, append, mask in variants:
+        eng = engine.Engine(spec, sd, B, device=dev)
+        if "mode" in opt:
+            eng.set_state_mode(opt["mode"])
+        if "micro" in opt:
+            eng.set_micro_batches(opt["micro"])
+        for t in range(L, L + CTX_PRE):   # no state is empty
+            eng.step(*(x.to(dev) for x in seq[t][:3]), None)
+        if kind == "score":
+            res = eng.score(obs, rtg, rew, actions=target, reset_mask=mask, want=("actions", "tokens", "logp"), logits=True,
+                            lengths=lengths, append=append)
+            out = {k: getattr(res, k) for k in ("actions", "tokens", "logp", "logits")}
+        else:
+            out = dict(zip(("actions", "tokens"), eng.prefill(obs, rtg, rew, reset_mask=mask, lengths=lengths, append=append)))
+        torch.cuda.synchronize()
+        for k, t in out.items():
+            digests[f"{variant}.{k}"] = _sha(t)
+        digests.update(state_digests(eng, spec, variant + "."))
+        for b, n in enumerate(lengths or []):
+            if n == 0:
+                digests[f"{variant}.record{b}"] = _sha(eng.save_slots([b]))
+        ran = eng.state_mode
+        eng.close()
+    print(json.dumps({"case": name, "digests": digests, "slstm": {}, "mode": ran}))
+
+
 def child(name):
     if name in GEMM_CASES:
         return child_gemm(name)
+    if name in CTX_CASES:
+        return child_ctx(name)
     import torch
     from lram_amd import engine, init_state_dict
     from tests.helpers import make_inputs
@@ -196,16 +287,7 @@ def child(name):
                 t0 += L
     torch.cuda.synchronize()
     digests["outputs"] = h.hexdigest()
-    if spec.backbone == "mamba":   # conv and SSM state of the first and the last block
-        pkv = eng.export_past_key_values()
-        for blk in (0, spec.n_blocks - 1):
-            for which, what in ((0, "conv"), (1, "ssm")):
-                digests[f"block{blk}.{what}"] = hashlib.sha256(pkv[blk][which].cpu().contiguous().numpy().tobytes()).hexdigest()
-    blocks = [] if spec.backbone == "mamba" else sorted({0, spec.n_blocks - 1} | set(list(spec.slstm_at)[:1]))
-    for blk in blocks:
-        for which, what in ((0, "planes"), (3, "conv")) if blk in spec.slstm_at else ((0, "C"), (1, "n"), (2, "m"), (3, "conv")):
-            t = eng.export_state_tensor(blk, which)
-            digests[f"block{blk}.{what}"] = hashlib.sha256(t.cpu().contiguous().numpy().tobytes()).hexdigest()
+    digests.update(state_digests(eng, spec))
     counts = eng.slstm_counts() if spec.backbone != "mamba" and spec.slstm_at else {}
     if name.startswith("tiles_"):   # which projection families ran (launch counts per family)
         counts = {**counts, **{k: v["launches"] for k, v in eng.gemm_counts().items()}}
@@ -219,7 +301,7 @@ def main():
     ap.add_argument("--parent", default="parent", help="csrc/_variants/<name>.so: the parent commit's library")
     ap.add_argument("--out", help="write the report here as well")
     ap.add_argument("--timeout", type=int, default=150, help="time limit of one child, seconds")
-    ap.add_argument("--case", choices=list(CASES) + list(GEMM_CASES), help="(internal) run one case in this process")
+    ap.add_argument("--case", choices=list(CASES) + list(GEMM_CASES) + list(CTX_CASES), help="(internal) run one case in this process")
     ap.add_argument("--cases", nargs="+", default=["*"], help="shell patterns: the cases to run (default: all)")
     args = ap.parse_args()
     if args.case:
@@ -227,8 +309,10 @@ def main():
     if not os.path.exists(os.path.join(ROOT, "lram_amd", "csrc", "_variants", args.parent + ".so")):
         sys.exit(f"csrc/_variants/{args.parent}.so is missing: build the parent commit and copy its liblram_hip.so there")
     lines, results = [], {}
-    cases = {n: c for n, c in {**CASES, **{n: (f"entry:{k}", len(s), ("shapes",), None, {}) for n, (k, s) in GEMM_CASES.items()}}.items()
-             if any(fnmatch.fnmatch(n, pat) for pat in args.cases)}
+    every = {**CASES, **{n: (f"entry:{k}", len(s), ("shapes",), None, {}) for n, (k, s) in GEMM_CASES.items()},
+             **{n: (g, B, (kind, L, "full" if ls is None else ",".join(map(str, ls))), None, env, *opt)
+                for n, (g, B, L, ls, kind, env, *opt) in CTX_CASES.items()}}
+    cases = {n: c for n, c in every.items() if any(fnmatch.fnmatch(n, pat) for pat in args.cases)}
 
     def say(line):
         print(line, flush=True)

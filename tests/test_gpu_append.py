@@ -14,7 +14,6 @@ Bars: the ones tests/test_gpu_ragged.py holds stored contexts to, none tuned to 
   * bit for bit wherever two engine runs share a chunk plan, and for every held slot.
 Seeds (weights / inputs), chosen on the CPU for the 1e-3 gap rule alone: 16M case 41 / 5 (smallest gap 5.1e-3; the agent test uses
 it too), held-slot case 43 / 13 (1.5e-2; inputs 12 leave slot 0 a gap of 9.9e-4), tiny cases 17 / 31 (1.9e-2 and 2.9e-3)."""
-import copy
 import ctypes
 
 import pytest
@@ -22,100 +21,16 @@ import torch
 
 from lram_amd import init_state_dict, preset
 from lram_amd.engine import context_plan
-from oracle import dt_ref
+from tests.context_cases import DEV, EnvRef, bits, env_slices, export_state, new_engine, same_state, stack, steps, u8_mask
 from tests.helpers import assert_actions_match, make_inputs, rel_err, sampled_state, state_vs_oracle
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-NAN = float("nan")
 LENGTHS_16M = [47, 47, 30, 30, 9, 1]
 RESTART_16M = [0, 1, 0, 1, 0, 0]
 PRE = 5        # env-steps ahead of the append call (16M and held-slot cases)
 EXTRA = 3      # env-steps behind the contexts
 MIN_GAP = 1e-3
-
-
-def _engine(spec, sd, B):
-    from lram_amd.engine import Engine
-    return Engine(spec, sd, B, device=DEV)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _kinds(spec, blk):
-    return (0, 3) if (spec.backbone == "mamba" or blk in spec.slstm_at) else (0, 1, 2, 3)
-
-
-def _state(eng, spec):
-    out = [eng.export_state_tensor(blk, w).clone() for blk in range(spec.n_blocks) for w in _kinds(spec, blk)]
-    torch.cuda.synchronize()
-    return out
-
-
-def _same_state(a, b, what):
-    assert len(a) == len(b)
-    for i, (x, y) in enumerate(zip(a, b)):
-        assert torch.equal(_bits(x), _bits(y)), f"{what}: state tensor {i} differs"
-
-
-def _env_slices(eng, spec, b):
-    """env b's slice of every exported state tensor (the sLSTM state is [4, B, D]), on the host."""
-    out = []
-    for blk in range(spec.n_blocks):
-        for w in _kinds(spec, blk):
-            t = eng.export_state_tensor(blk, w)
-            out.append((t[:, b] if (spec.backbone == "xlstm" and blk in spec.slstm_at and w == 0) else t[b]).clone())
-    torch.cuda.synchronize()
-    return [t.cpu() for t in out]
-
-
-def _stack(seq, L, lengths=None, t0=0):
-    """[B, L, ...] device tensors of the timesteps t0 .. t0 + L - 1; with lengths, NaN in every padded position."""
-    obs, rtg, rew = (torch.stack([x[i] for x in seq[t0:t0 + L]], 1).contiguous() for i in range(3))
-    if lengths is not None:
-        for b, n in enumerate(lengths):
-            obs[b, n:], rtg[b, n:], rew[b, n:] = NAN, NAN, NAN
-    return obs.to(DEV), rtg.to(DEV), rew.to(DEV)
-
-
-def _mask(bits):
-    return torch.tensor(bits, dtype=torch.uint8, device=DEV)
-
-
-def _steps(eng, seq, ts):
-    for t in ts:
-        eng.step(*(x.to(DEV) for x in seq[t][:3]), None)
-
-
-def _min_gap(logits):
-    top2 = logits.topk(2, dim=-1).values
-    return float((top2[..., 0] - top2[..., 1]).min())
-
-
-class EnvRef:
-    """The oracle's run of ONE env from an empty state: the env-steps `pre` (timestep indices into seq), its context -- the first n
-    timesteps of its row of seq -- and then the env-steps `cont`.  act / logits / state: behind the context; cont: (action, logits)
-    of every step behind it.  min_gap: the smallest top-2 logit gap over the rows an engine is compared on (the context's last
-    timestep, or the last env-step ahead of it for an env without a context, and every step behind)."""
-
-    def __init__(self, spec, sd, seq, b, n, pre=(), cont=(), **oracle_kw):
-        ora = dt_ref.OraclePolicy(spec, sd, **oracle_kw)
-        row = lambda t: tuple(x[b:b + 1] for x in seq[t][:3])
-        self.act = self.logits = None
-        for t in list(pre) + list(range(n)):
-            self.act, dbg = ora.step(*row(t), return_debug=True)
-            self.logits = dbg["logits"]
-        self.state = copy.deepcopy(ora.state)
-        self.cont = []
-        for t in cont:
-            a, dbg = ora.step(*row(t), return_debug=True)
-            self.cont.append((a, dbg["logits"]))
-        self.cont_state = ora.state
-        compared = ([self.logits] if n > 0 else []) + [lg for _, lg in self.cont]
-        self.min_gap = min(_min_gap(lg) for lg in compared) if compared else float("inf")
 
 
 def _clear_margins(refs, what):
@@ -143,7 +58,7 @@ def _check_continued(eng, spec, b, actions, ref, snap, what):
         assert assert_actions_match(actions[b:b + 1], ref.act, ref.logits, spec, what=f"{what} env {b}") == 0
     slices, record = snap
     worst = 0.0
-    for i, (got, want) in enumerate(zip(_env_slices(eng, spec, b), slices)):
+    for i, (got, want) in enumerate(zip(env_slices(eng, spec, b), slices)):
         err = rel_err(got, want)
         worst = max(worst, err)
         assert err < 1e-4, (what, b, i, err)
@@ -155,14 +70,14 @@ def _check_continued(eng, spec, b, actions, ref, snap, what):
 def _stepping_snapshots(spec, sd, B, seq, pre, lengths, restart, L):
     """A second engine takes the env-steps `pre`, then timesteps 0 .. L - 1 one lram_step at a time (the restart flags on timestep
     0); env b's state -- every exported tensor and its save_slots record -- is taken right after its own last step."""
-    eng = _engine(spec, sd, B)
-    _steps(eng, seq, pre)
+    eng = new_engine(spec, sd, B)
+    steps(eng, seq, pre)
     snaps = {}
     for t in range(max(lengths)):
-        eng.step(*(x.to(DEV) for x in seq[t][:3]), _mask(restart) if t == 0 else None)
+        eng.step(*(x.to(DEV) for x in seq[t][:3]), u8_mask(restart) if t == 0 else None)
         for b, n in enumerate(lengths):
             if n == t + 1:
-                snaps[b] = (_env_slices(eng, spec, b), eng.save_slots([b]).cpu())
+                snaps[b] = (env_slices(eng, spec, b), eng.save_slots([b]).cpu())
     eng.close()
     return snaps
 
@@ -197,11 +112,11 @@ def _snaps16():
 def _run16(entry="append", mask=RESTART_16M, **kw):
     """A fresh engine: PRE env-steps, then the 16M contexts by the append (or the ragged) entry: (engine, actions, tokens)."""
     spec, sd, B, L, seq, _, _ = _case16()
-    eng = _engine(spec, sd, B)
+    eng = new_engine(spec, sd, B)
     for k, v in kw.items():
         getattr(eng, k)(v)
-    _steps(eng, seq, range(L, L + PRE))
-    act, tok = eng.prefill(*_stack(seq, L, LENGTHS_16M), reset_mask=_mask(mask), lengths=LENGTHS_16M, append=entry == "append")
+    steps(eng, seq, range(L, L + PRE))
+    act, tok = eng.prefill(*stack(seq, L, LENGTHS_16M), reset_mask=u8_mask(mask), lengths=LENGTHS_16M, append=entry == "append")
     torch.cuda.synchronize()
     return eng, act.clone(), tok.clone()
 
@@ -211,7 +126,7 @@ def _default16():
     if "default16" not in _CACHE:
         spec = _case16()[0]
         eng, act, tok = _run16()
-        _CACHE["default16"] = (act.cpu(), tok.cpu(), [t.cpu() for t in _state(eng, spec)])
+        _CACHE["default16"] = (act.cpu(), tok.cpu(), [t.cpu() for t in export_state(eng, spec)])
         eng.close()
     return _CACHE["default16"]
 
@@ -233,7 +148,7 @@ def test_appended_contexts_continue_or_restart_each_env(hip_lib):
     assert context_plan(L, LENGTHS_16M, 16) == [0, 9, 17, 28, 38, 46]
     eng, act, tok = _run16()
     assert bool(act.isfinite().all()) and bool((tok >= 0).all())
-    for t in _state(eng, spec):
+    for t in export_state(eng, spec):
         assert bool(t.isfinite().all())
     _check16(eng, act, "16M append")
     eng.close()
@@ -242,26 +157,28 @@ def test_appended_contexts_continue_or_restart_each_env(hip_lib):
 # ---- 2. bit identities -----------------------------------------------------------------------------------------------------------
 def test_full_lengths_are_bit_identical_to_prefill(hip_lib):
     spec, sd, B, L, seq, _, _ = _case16()
-    inputs = _stack(seq, L)
-    e_dense, e_app = _engine(spec, sd, B), _engine(spec, sd, B)
+    inputs = stack(seq, L)
+    e_dense, e_app = new_engine(spec, sd, B), new_engine(spec, sd, B)
     for rep in range(2):     # the second call continues (no reset)
-        mask = _mask([1] * B) if rep == 0 else None
+        mask = u8_mask([1] * B) if rep == 0 else None
         a_d, t_d = e_dense.prefill(*inputs, reset_mask=mask)
         a_a, t_a = e_app.prefill(*inputs, reset_mask=mask, lengths=[L] * B, append=True)
         torch.cuda.synchronize()
-        assert torch.equal(_bits(a_d), _bits(a_a)) and torch.equal(t_d, t_a), rep
-        _same_state(_state(e_dense, spec), _state(e_app, spec), f"full lengths, call {rep}")
+        assert torch.equal(bits(a_d), bits(a_a)) and torch.equal(t_d, t_a), rep
+        same_state(export_state(e_dense, spec), export_state(e_app, spec), f"full lengths, call {rep}")
     e_dense.close(), e_app.close()
 
 
 def test_restarting_everybody_is_bit_identical_to_the_ragged_entry(hip_lib):
     """All-ones mask: every env with a context restarts at its own first timestep, which is what lram_prefill_ragged does to it --
-    the same chunk plan, the same arithmetic per env; the held envs of a chunk only lose their state writes."""
+    the same chunk plan, the same arithmetic per env; the held envs of a chunk only lose their state writes.
+    (On this plan.  Where a chunk of ONE timestep holds an env -- the token-sequential kernels with a stretch of 4 k + 1 timesteps
+    ahead of a start -- the held form is a few ulp off the zero-fed one: DESIGN.md section 9, profiles/context_call_digests.txt.)"""
     spec, sd, B, L, seq, _, _ = _case16()
     e_app, a_app, t_app = _run16("append", [1] * B)
     e_rag, a_rag, t_rag = _run16("ragged", [1] * B)
-    assert torch.equal(_bits(a_app), _bits(a_rag)) and torch.equal(t_app, t_rag)
-    _same_state(_state(e_app, spec), _state(e_rag, spec), "append with an all-ones mask against the ragged entry")
+    assert torch.equal(bits(a_app), bits(a_rag)) and torch.equal(t_app, t_rag)
+    same_state(export_state(e_app, spec), export_state(e_rag, spec), "append with an all-ones mask against the ragged entry")
     e_app.close(), e_rag.close()
 
 
@@ -271,8 +188,8 @@ def test_one_chunk_at_a_time_equals_the_chunk_lanes(hip_lib, monkeypatch):
     monkeypatch.setenv("LRAM_PREFILL_CHUNK", "3")
     eng, act, tok = _run16()
     monkeypatch.delenv("LRAM_PREFILL_CHUNK")
-    assert torch.equal(_bits(act.cpu()), _bits(a0)) and torch.equal(tok.cpu(), t0)
-    _same_state([t.cpu() for t in _state(eng, spec)], s0, "lanes against one chunk at a time")
+    assert torch.equal(bits(act.cpu()), bits(a0)) and torch.equal(tok.cpu(), t0)
+    same_state([t.cpu() for t in export_state(eng, spec)], s0, "lanes against one chunk at a time")
     eng.close()
 
 
@@ -285,15 +202,15 @@ def test_two_env_slices_equal_one(hip_lib):
     assert context_plan(Ls, lengths, 13) == [0, 5, 10, 12]
     out = []
     for micro in (1, 2):
-        eng = _engine(spec, sd, B)
+        eng = new_engine(spec, sd, B)
         eng.set_micro_batches(micro)
         for mask in ([1] * B, RESTART_16M):
-            act, tok = eng.prefill(*_stack(seq, Ls, lengths), reset_mask=_mask(mask), lengths=lengths, append=True)
+            act, tok = eng.prefill(*stack(seq, Ls, lengths), reset_mask=u8_mask(mask), lengths=lengths, append=True)
         torch.cuda.synchronize()
-        out.append((act.cpu(), tok.cpu(), [t.cpu() for t in _state(eng, spec)]))
+        out.append((act.cpu(), tok.cpu(), [t.cpu() for t in export_state(eng, spec)]))
         eng.close()
-    assert torch.equal(_bits(out[0][0]), _bits(out[1][0])) and torch.equal(out[0][1], out[1][1])
-    _same_state(out[0][2], out[1][2], "two env slices against one")
+    assert torch.equal(bits(out[0][0]), bits(out[1][0])) and torch.equal(out[0][1], out[1][1])
+    same_state(out[0][2], out[1][2], "two env slices against one")
 
 
 # ---- 3. held slots ---------------------------------------------------------------------------------------------------------------
@@ -313,19 +230,19 @@ def test_held_slots_keep_every_byte_of_their_state(hip_lib, mode):
     refs = _CACHE["held"]
     _clear_margins(refs, f"held slots ({mode})")
     snaps = _stepping_snapshots(spec, sd, B, seq, pre, lengths, [0, 1, 0, 0], L)
-    eng = _engine(spec, sd, B)
+    eng = new_engine(spec, sd, B)
     if mode == "lazy":
         eng.set_state_mode("lazy")
     assert eng.state_mode == ("lazy" if mode == "lazy" else "materialised")
-    _steps(eng, seq, pre)
-    before = {b: (_env_slices(eng, spec, b), eng.save_slots([b]).cpu()) for b in (0, 2)}
-    act, tok = eng.prefill(*_stack(seq, L, lengths), reset_mask=_mask(restart), lengths=lengths, append=True)
+    steps(eng, seq, pre)
+    before = {b: (env_slices(eng, spec, b), eng.save_slots([b]).cpu()) for b in (0, 2)}
+    act, tok = eng.prefill(*stack(seq, L, lengths), reset_mask=u8_mask(restart), lengths=lengths, append=True)
     torch.cuda.synchronize()
     act, tok = act.clone(), tok.clone()
     for b in (0, 2):
-        for i, (x, y) in enumerate(zip(before[b][0], _env_slices(eng, spec, b))):
-            assert torch.equal(_bits(x), _bits(y)), (mode, b, i)
-        assert torch.equal(_bits(before[b][1]), _bits(eng.save_slots([b]).cpu())), (mode, b)
+        for i, (x, y) in enumerate(zip(before[b][0], env_slices(eng, spec, b))):
+            assert torch.equal(bits(x), bits(y)), (mode, b, i)
+        assert torch.equal(bits(before[b][1]), bits(eng.save_slots([b]).cpu())), (mode, b)
         assert bool((act[b] == 0).all()) and bool((tok[b] == -1).all()), (mode, b)
     assert assert_actions_match(act[1:2].cpu(), refs[1].act, refs[1].logits, spec, what=f"held slots ({mode}) env 1") == 0
     _check_continued(eng, spec, 1, None, refs[1], snaps[1], f"held slots ({mode})")
@@ -364,18 +281,18 @@ def test_appended_contexts_on_the_token_sequential_geometries(hip_lib, name):
     refs = [EnvRef(spec, sd, seq, b, n, pre=() if restart[b] else pre) for b, n in enumerate(lengths)]
     _clear_margins(refs, f"{name} append")
     snaps = _stepping_snapshots(spec, sd, B, seq, pre, lengths, restart, L)
-    eng = _engine(spec, sd, B)
-    _steps(eng, seq, pre)
-    held = (_env_slices(eng, spec, 2), eng.save_slots([2]).cpu())
-    act, tok = eng.prefill(*_stack(seq, L, lengths), reset_mask=_mask(restart), lengths=lengths, append=True)
+    eng = new_engine(spec, sd, B)
+    steps(eng, seq, pre)
+    held = (env_slices(eng, spec, 2), eng.save_slots([2]).cpu())
+    act, tok = eng.prefill(*stack(seq, L, lengths), reset_mask=u8_mask(restart), lengths=lengths, append=True)
     torch.cuda.synchronize()
     act, tok = act.clone(), tok.clone()
     assert bool(act.isfinite().all())
     for b, n in enumerate(lengths):
         if n == 0:
-            for i, (x, y) in enumerate(zip(held[0], _env_slices(eng, spec, b))):
-                assert torch.equal(_bits(x), _bits(y)), (name, i)
-            assert torch.equal(_bits(held[1]), _bits(eng.save_slots([b]).cpu()))
+            for i, (x, y) in enumerate(zip(held[0], env_slices(eng, spec, b))):
+                assert torch.equal(bits(x), bits(y)), (name, i)
+            assert torch.equal(bits(held[1]), bits(eng.save_slots([b]).cpu()))
             assert bool((act[b] == 0).all()) and bool((tok[b] == -1).all())
         elif restart[b]:
             _check_restarted(eng, spec, b, act.cpu(), refs[b], f"{name} append")
@@ -389,16 +306,16 @@ def test_score_in_two_appended_windows_against_one_ragged_call(hip_lib):
     """The 16M lengths scored as 24 + 23 timesteps (the second call appends) against one lram_score_ragged call over 47."""
     spec, sd, B, L, seq, _, _ = _case16()
     A, W = spec.act_dim, 24
-    obs, rtg, rew = _stack(seq, L, LENGTHS_16M)
+    obs, rtg, rew = stack(seq, L, LENGTHS_16M)
     g = torch.Generator().manual_seed(3)
     target = (torch.rand(B, L, A, generator=g) * 2 - 1).to(DEV)
-    e_one, e_win = _engine(spec, sd, B), _engine(spec, sd, B)
-    one = e_one.score(obs, rtg, rew, actions=target, reset_mask=_mask([1] * B), logits=True, lengths=LENGTHS_16M)
+    e_one, e_win = new_engine(spec, sd, B), new_engine(spec, sd, B)
+    one = e_one.score(obs, rtg, rew, actions=target, reset_mask=u8_mask([1] * B), logits=True, lengths=LENGTHS_16M)
     parts = []
     for lo, hi in ((0, W), (W, L)):
         n = [min(max(x - lo, 0), hi - lo) for x in LENGTHS_16M]
         parts.append(e_win.score(obs[:, lo:hi].contiguous(), rtg[:, lo:hi].contiguous(), rew[:, lo:hi].contiguous(),
-                                 actions=target[:, lo:hi].contiguous(), reset_mask=_mask([1] * B) if lo == 0 else None, lengths=n,
+                                 actions=target[:, lo:hi].contiguous(), reset_mask=u8_mask([1] * B) if lo == 0 else None, lengths=n,
                                  append=True))
     torch.cuda.synchronize()
     tokens, logp, actions = (torch.cat([getattr(p, k) for p in parts], 1).cpu() for k in ("tokens", "logp", "actions"))
@@ -409,7 +326,7 @@ def test_score_in_two_appended_windows_against_one_ragged_call(hip_lib):
         err = float((logp[b, :n].double() - one.logp[b, :n].cpu().double()).abs().max())
         print(f"[append] score env {b} (n = {n}): logp of two windows off the single call's by {err:.2e} (bar {bar:.2e})")
         assert bool(logp[b, :n].isfinite().all()) and err <= bar, (b, err, bar)
-    for i, (got, want) in enumerate(zip(_state(e_win, spec), _state(e_one, spec))):
+    for i, (got, want) in enumerate(zip(export_state(e_win, spec), export_state(e_one, spec))):
         assert rel_err(got, want) < 1e-4, i
     e_one.close(), e_win.close()
 
@@ -420,7 +337,7 @@ def test_agent_scores_in_windows_or_extends_contexts_and_continues(hip_lib):
     from lram_amd.agent import RecurrentAgent
     spec, sd, B, L, seq, empty, _ = _case16()
     _clear_margins(empty, "agent, 16M")
-    obs, rtg, _ = (x.cpu() for x in _stack(seq, L, LENGTHS_16M))
+    obs, rtg, _ = (x.cpu() for x in stack(seq, L, LENGTHS_16M))
     a_win = RecurrentAgent(spec, sd, n_envs=B, device=DEV)
     a_ext = RecurrentAgent(spec, sd, n_envs=B, device=DEV)
     g = torch.Generator().manual_seed(3)
@@ -455,9 +372,9 @@ def test_refused_calls_name_the_entry_and_leave_the_state_alone(hip_lib):
     sd = init_state_dict(spec, seed=17)
     B, L = 5, 47
     seq = make_inputs(spec, B, L, seed=31, reset_prob=0.0)
-    eng = _engine(spec, sd, B)
-    inputs = _stack(seq, L)
-    ones = _mask([1] * B)
+    eng = new_engine(spec, sd, B)
+    inputs = stack(seq, L)
+    ones = u8_mask([1] * B)
     eng.prefill(*inputs, reset_mask=ones, want_action=False)     # a state that is not empty
     good = [47, 30, 0, 9, 1]
     logp = torch.zeros(B, L, spec.act_dim, device=DEV)
@@ -482,7 +399,7 @@ def test_refused_calls_name_the_entry_and_leave_the_state_alone(hip_lib):
             assert entry in msg and all(n in msg for n in needles), msg
             after = eng.save_slots(list(range(B)))
             torch.cuda.synchronize()
-            assert torch.equal(_bits(before), _bits(after)), msg
+            assert torch.equal(bits(before), bits(after)), msg
 
     refused([47, 48, 0, 9, 1], "outside 0 .. timesteps")       # a length of 48
     refused([47, -1, 0, 9, 1], "outside 0 .. timesteps")

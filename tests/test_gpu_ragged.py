@@ -14,88 +14,19 @@ Bars, the ones the project already holds stored contexts to (none tuned to the c
 The 16M case -- 47 timesteps, lengths 47, 47, 30, 30, 9, 1, chunks of at most 16 -- has the plan [0, 9, 17, 28, 38, 46]: chunkwise
 chunks of 8 - 11 timesteps, a last chunk of one timestep on the token-sequential kernels (the env that starts on the last
 timestep), an sLSTM block, and six chunks over the three lanes."""
-import copy
-
 import pytest
 import torch
 
 from lram_amd import init_state_dict, preset
 from lram_amd.engine import LramError, context_plan
 from oracle import dt_ref
+from tests.context_cases import DEV, NAN, EnvRef, bits, env_slices, export_state, new_engine, same_state, stack
 from tests.helpers import assert_actions_match, make_inputs, rel_err, sampled_state, state_vs_oracle
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-NAN = float("nan")
 LENGTHS_16M = [47, 47, 30, 30, 9, 1]
 EXTRA = 3     # env-steps behind the contexts
-
-
-def _engine(spec, sd, B):
-    from lram_amd.engine import Engine
-    return Engine(spec, sd, B, device=DEV)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _kinds(spec, blk):
-    return (0, 3) if (spec.backbone == "mamba" or blk in spec.slstm_at) else (0, 1, 2, 3)
-
-
-def _state(eng, spec):
-    out = [eng.export_state_tensor(blk, w).clone() for blk in range(spec.n_blocks) for w in _kinds(spec, blk)]
-    torch.cuda.synchronize()
-    return out
-
-
-def _same_state(a, b, what):
-    assert len(a) == len(b)
-    for i, (x, y) in enumerate(zip(a, b)):
-        assert torch.equal(_bits(x), _bits(y)), f"{what}: state tensor {i} differs"
-
-
-def _env_slices(eng, spec, b):
-    """env b's slice of every exported state tensor (the sLSTM state is [4, B, D])."""
-    out = []
-    for blk in range(spec.n_blocks):
-        for w in _kinds(spec, blk):
-            t = eng.export_state_tensor(blk, w)
-            out.append((t[:, b] if (spec.backbone == "xlstm" and blk in spec.slstm_at and w == 0) else t[b]).clone())
-    torch.cuda.synchronize()
-    return out
-
-
-def _stack(seq, L, lengths=None):
-    """[B, L, ...] device tensors of the first L timesteps; with lengths, NaN in every padded position."""
-    obs, rtg, rew = (torch.stack([x[i] for x in seq[:L]], 1).contiguous() for i in range(3))
-    if lengths is not None:
-        for b, n in enumerate(lengths):
-            obs[b, n:], rtg[b, n:], rew[b, n:] = NAN, NAN, NAN
-    return obs.to(DEV), rtg.to(DEV), rew.to(DEV)
-
-
-class EnvRef:
-    """The oracle's run of ONE env from an empty state: `pre` env-steps on seq[L : L + pre] (a slot without a context keeps
-    what they leave), its context -- the first n timesteps of its row of `seq` -- and then `extra` env-steps on the timesteps
-    from seq[cont_from] on (default: behind the ones already taken)."""
-
-    def __init__(self, spec, sd, seq, b, n, L, extra, pre=0, cont_from=None, **oracle_kw):
-        ora = dt_ref.OraclePolicy(spec, sd, **oracle_kw)
-        row = lambda t: tuple(x[b:b + 1] for x in seq[t][:3])
-        self.act = self.logits = None
-        for t in list(range(L, L + pre)) + list(range(n)):
-            self.act, dbg = ora.step(*row(t), return_debug=True)
-            self.logits = dbg["logits"]
-        self.state = copy.deepcopy(ora.state)
-        self.cont = []
-        cont_from = L + pre if cont_from is None else cont_from
-        for k in range(extra):
-            a, dbg = ora.step(*row(cont_from + k), return_debug=True)
-            self.cont.append((a, dbg["logits"]))
-        self.cont_state = ora.state
 
 
 def _check_env(eng, spec, b, actions, ref, what, continued=False):
@@ -122,7 +53,7 @@ def _case16():
         sd = init_state_dict(spec, seed=41)
         B, L = 6, 47
         seq = make_inputs(spec, B, L + EXTRA, seed=5, reset_prob=0.0)
-        refs = [EnvRef(spec, sd, seq, b, n, L, EXTRA) for b, n in enumerate(LENGTHS_16M)]
+        refs = [EnvRef(spec, sd, seq, b, n, cont=range(L, L + EXTRA)) for b, n in enumerate(LENGTHS_16M)]
         _CACHE["m16"] = (spec, sd, B, L, seq, refs)
     return _CACHE["m16"]
 
@@ -130,11 +61,11 @@ def _case16():
 def _run16(**kw):
     """A fresh engine's ragged prefill of the 16M case: (engine, actions, tokens), synchronised."""
     spec, sd, B, L, seq, _ = _case16()
-    eng = _engine(spec, sd, B)
+    eng = new_engine(spec, sd, B)
     for k, v in kw.items():
         getattr(eng, k)(v)
     ones = torch.ones(B, dtype=torch.uint8, device=DEV)
-    act, tok = eng.prefill(*_stack(seq, L, LENGTHS_16M), reset_mask=ones, lengths=LENGTHS_16M)
+    act, tok = eng.prefill(*stack(seq, L, LENGTHS_16M), reset_mask=ones, lengths=LENGTHS_16M)
     torch.cuda.synchronize()
     return eng, act.clone(), tok.clone()
 
@@ -144,7 +75,7 @@ def _default16():
     if "default16" not in _CACHE:
         spec = _case16()[0]
         eng, act, tok = _run16()
-        _CACHE["default16"] = (act.cpu(), tok.cpu(), [t.cpu() for t in _state(eng, spec)])
+        _CACHE["default16"] = (act.cpu(), tok.cpu(), [t.cpu() for t in export_state(eng, spec)])
         eng.close()
     return _CACHE["default16"]
 
@@ -155,7 +86,7 @@ def test_ragged_prefill_gives_every_env_the_state_of_its_own_context(hip_lib):
     assert context_plan(L, LENGTHS_16M, 16) == [0, 9, 17, 28, 38, 46]
     eng, act, tok = _run16()
     assert bool(act.isfinite().all()) and bool((tok >= 0).all())
-    for t in _state(eng, spec):
+    for t in export_state(eng, spec):
         assert bool(t.isfinite().all())
     for b in range(B):
         _check_env(eng, spec, b, act.cpu(), refs[b], "16M ragged prefill")
@@ -165,16 +96,16 @@ def test_ragged_prefill_gives_every_env_the_state_of_its_own_context(hip_lib):
 # ---- 2. full lengths: the dense entry's launches ---------------------------------------------------------------------------------
 def test_full_lengths_are_bit_identical_to_prefill(hip_lib):
     spec, sd, B, L, seq, _ = _case16()
-    inputs = _stack(seq, L)
+    inputs = stack(seq, L)
     ones = torch.ones(B, dtype=torch.uint8, device=DEV)
-    e_dense, e_ragged = _engine(spec, sd, B), _engine(spec, sd, B)
+    e_dense, e_ragged = new_engine(spec, sd, B), new_engine(spec, sd, B)
     for rep in range(2):     # the second call continues (no reset)
         mask = ones if rep == 0 else None
         a_d, t_d = e_dense.prefill(*inputs, reset_mask=mask)
         a_r, t_r = e_ragged.prefill(*inputs, reset_mask=mask, lengths=[L] * B)
         torch.cuda.synchronize()
-        assert torch.equal(_bits(a_d), _bits(a_r)) and torch.equal(t_d, t_r), rep
-        _same_state(_state(e_dense, spec), _state(e_ragged, spec), f"full lengths, call {rep}")
+        assert torch.equal(bits(a_d), bits(a_r)) and torch.equal(t_d, t_r), rep
+        same_state(export_state(e_dense, spec), export_state(e_ragged, spec), f"full lengths, call {rep}")
     e_dense.close(), e_ragged.close()
 
 
@@ -191,8 +122,8 @@ def test_ragged_prefill_token_sequential_and_one_chunk_at_a_time(hip_lib, monkey
         _check_env(eng, spec, b, act.cpu(), refs[b], f"16M ragged prefill, LRAM_PREFILL_CHUNK={chunk_mode}")
     if chunk_mode == "3":
         a0, t0, s0 = _default16()
-        assert torch.equal(_bits(act.cpu()), _bits(a0)) and torch.equal(tok.cpu(), t0)
-        _same_state([t.cpu() for t in _state(eng, spec)], s0, "lanes against one chunk at a time")
+        assert torch.equal(bits(act.cpu()), bits(a0)) and torch.equal(tok.cpu(), t0)
+        same_state([t.cpu() for t in export_state(eng, spec)], s0, "lanes against one chunk at a time")
     eng.close()
 
 
@@ -203,11 +134,11 @@ def test_steps_continue_from_the_primed_contexts(hip_lib):
     spec, sd, B, L, seq, refs = _case16()
     L0 = 6
     seq0 = make_inputs(spec, B, L0, seed=77, reset_prob=0.0)
-    eng, e_step = _engine(spec, sd, B), _engine(spec, sd, B)
+    eng, e_step = new_engine(spec, sd, B), new_engine(spec, sd, B)
     ones = torch.ones(B, dtype=torch.uint8, device=DEV)
-    eng.prefill(*_stack(seq0, L0), reset_mask=ones, want_action=False)
+    eng.prefill(*stack(seq0, L0), reset_mask=ones, want_action=False)
     mask = torch.tensor([0, 1, 1, 1, 1, 1], dtype=torch.uint8, device=DEV)
-    eng.prefill(*_stack(seq, L, LENGTHS_16M), reset_mask=mask, lengths=LENGTHS_16M)
+    eng.prefill(*stack(seq, L, LENGTHS_16M), reset_mask=mask, lengths=LENGTHS_16M)
     for obs, rtg, rew, _ in seq0 + seq[:L]:
         e_step.step(obs.to(DEV), rtg.to(DEV), rew.to(DEV), None)
     for k in range(EXTRA):
@@ -219,7 +150,7 @@ def test_steps_continue_from_the_primed_contexts(hip_lib):
         assert_actions_match(act[:1].cpu(), a_step[:1].cpu(), lg[:1], spec, what=f"env 0, step {k}")
         for b in range(1, B):
             assert_actions_match(act[b:b + 1].cpu(), *refs[b].cont[k], spec, what=f"env {b}, step {k}")
-    for got, want in zip(_env_slices(eng, spec, 0), _env_slices(e_step, spec, 0)):
+    for got, want in zip(env_slices(eng, spec, 0), env_slices(e_step, spec, 0)):
         assert rel_err(got, want) < 1e-4
     for b in range(1, B):
         _check_env(eng, spec, b, None, refs[b], "16M, 3 steps behind the contexts", continued=True)
@@ -229,40 +160,41 @@ def test_steps_continue_from_the_primed_contexts(hip_lib):
 # ---- 5. slots without a context are left alone -----------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", ["auto", "lazy"])
 def test_slots_of_length_zero_keep_their_state(hip_lib, mode):
-    """5 env-steps, export, a ragged call with lengths 0, 12, 0, 5, export: slots 0 and 2 are bit for bit what they were (in lazy
-    mode against the export taken after the same fold: the first export folds), their action rows hold 0 / -1, and one more
-    env-step of all four envs follows the oracle."""
+    """5 env-steps, export, a ragged call with lengths 0, 12, 0, 5, export: slots 0 and 2 are bit for bit what they were, in every
+    exported tensor and in their save_slots records (in lazy mode against the export taken after the same fold: the first export
+    folds), their action rows hold 0 / -1, and one more env-step of all four envs follows the oracle."""
     spec = preset("xlstm_16m")
     sd = init_state_dict(spec, seed=43)
     B, L, pre, lengths = 4, 12, 5, [0, 12, 0, 5]
     seq = make_inputs(spec, B, L + pre + 1, seed=12, reset_prob=0.0)
     if "keep" not in _CACHE:   # the oracle: slots 0, 2 take 5 + 1 env-steps (no context), slots 1, 3 their context + 1 env-step
-        _CACHE["keep"] = [EnvRef(spec, sd, seq, b, n, L, 1, pre=0 if n else pre, cont_from=L + pre) for b, n in enumerate(lengths)]
+        _CACHE["keep"] = [EnvRef(spec, sd, seq, b, n, pre=() if n else range(L, L + pre), cont=[L + pre]) for b, n in enumerate(lengths)]
     refs = _CACHE["keep"]
-    eng = _engine(spec, sd, B)
+    eng = new_engine(spec, sd, B)
     if mode == "lazy":
         eng.set_state_mode("lazy")
     assert eng.state_mode == ("lazy" if mode == "lazy" else "materialised")
     for t in range(L, L + pre):
         eng.step(*(x.to(DEV) for x in seq[t][:3]), None)
-    before = {b: _env_slices(eng, spec, b) for b in (0, 2)}
+    before = {b: (env_slices(eng, spec, b), eng.save_slots([b]).cpu()) for b in (0, 2)}
     ones = torch.ones(B, dtype=torch.uint8, device=DEV)
-    act, tok = eng.prefill(*_stack(seq, L, lengths), reset_mask=ones, lengths=lengths)
+    act, tok = eng.prefill(*stack(seq, L, lengths), reset_mask=ones, lengths=lengths)
     torch.cuda.synchronize()
     act, tok = act.clone(), tok.clone()
     for b in (0, 2):
-        for i, (x, y) in enumerate(zip(before[b], _env_slices(eng, spec, b))):
-            assert torch.equal(_bits(x), _bits(y)), (mode, b, i)
+        for i, (x, y) in enumerate(zip(before[b][0], env_slices(eng, spec, b))):
+            assert torch.equal(bits(x), bits(y)), (mode, b, i)
+        assert torch.equal(bits(before[b][1]), bits(eng.save_slots([b]).cpu())), (mode, b)
         assert bool((act[b] == 0).all()) and bool((tok[b] == -1).all()), (mode, b)
     # the slots with a context: the oracle's action, and the state a dense prefill of the env's own n timesteps leaves (1e-4, the
     # engine-against-engine bar).  Not state_vs_oracle here: slot 3's 5 timesteps are one chunk in both calls -- bit-identical
     # states -- and on these inputs the dense entry itself is 8.0e-3 per element off the oracle in block 7's C (bar 5e-3;
     # 3.6e-3 by 5 lram_step calls), 2.3e-5 by rel_err: after 5 timesteps most of C is cancellation noise.
-    e_dense = _engine(spec, sd, B)
+    e_dense = new_engine(spec, sd, B)
     for b in (1, 3):
         assert_actions_match(act[b:b + 1].cpu(), refs[b].act, refs[b].logits, spec, what=f"kept slots ({mode}) env {b}")
-        e_dense.prefill(*_stack(seq, lengths[b]), reset_mask=ones, want_action=False)
-        for i, (got, want) in enumerate(zip(_env_slices(eng, spec, b), _env_slices(e_dense, spec, b))):
+        e_dense.prefill(*stack(seq, lengths[b]), reset_mask=ones, want_action=False)
+        for i, (got, want) in enumerate(zip(env_slices(eng, spec, b), env_slices(e_dense, spec, b))):
             assert rel_err(got, want) < 1e-4, (mode, b, i)
     e_dense.close()
     assert eng.state_mode == ("lazy" if mode == "lazy" else "materialised")
@@ -274,6 +206,46 @@ def test_slots_of_length_zero_keep_their_state(hip_lib, mode):
     eng.close()
 
 
+# ---- 5b. who restarts: a shorter context whatever the mask says, a full one where the mask says so -------------------------------
+@pytest.mark.parametrize("name", ["xlstm_tiny", "mamba_tiny"])
+def test_shorter_contexts_restart_whatever_the_mask_says_and_full_ones_obey_it(hip_lib, name):
+    """3 env-steps, then one replace call of 6 timesteps with lengths 6, 6, 3, 0 (plan [0, 3]), without a mask on one engine and
+    with an all-ones mask on another.  Env 2 (shorter) restarts at its first timestep on both: bit-identical state and action.
+    Envs 0 and 1 (full length) continue the 3 env-steps without a mask and start from an empty state with one.  Env 3 (length 0)
+    is held on both: every exported tensor and its record bit for bit what they were."""
+    spec = preset(name)
+    sd = init_state_dict(spec, seed=17)
+    B, L, lengths, npre = 4, 6, [6, 6, 3, 0], 3
+    assert context_plan(L, lengths, 4) == [0, 3]
+    seq = make_inputs(spec, B, L + npre, seed=31, reset_prob=0.0)
+    pre = range(L, L + npre)
+    continued = [EnvRef(spec, sd, seq, b, lengths[b], pre=pre) for b in (0, 1)]
+    empty = [EnvRef(spec, sd, seq, b, lengths[b]) for b in (0, 1)]
+    inputs = stack(seq, L, lengths)
+    out = {}
+    for kind, mask in (("no mask", None), ("all-ones mask", torch.ones(B, dtype=torch.uint8, device=DEV))):
+        eng = new_engine(spec, sd, B)
+        for t in pre:
+            eng.step(*(x.to(DEV) for x in seq[t][:3]), None)
+        before = (env_slices(eng, spec, 3), eng.save_slots([3]).cpu())
+        act, tok = eng.prefill(*inputs, reset_mask=mask, lengths=lengths)
+        torch.cuda.synchronize()
+        act, tok = act.clone(), tok.clone()
+        assert bool(act.isfinite().all())
+        for i, (x, y) in enumerate(zip(before[0], env_slices(eng, spec, 3))):
+            assert torch.equal(bits(x), bits(y)), (name, kind, i)
+        assert torch.equal(bits(before[1]), bits(eng.save_slots([3]).cpu())), (name, kind)
+        assert bool((act[3] == 0).all()) and bool((tok[3] == -1).all()), (name, kind)
+        for b, ref in zip((0, 1), continued if mask is None else empty):
+            _check_env(eng, spec, b, act.cpu(), ref, f"{name} replace call, {kind}")
+        out[kind] = (act.cpu(), tok.cpu(), env_slices(eng, spec, 2))
+        eng.close()
+    (a0, t0, s0), (a1, t1, s1) = out["no mask"], out["all-ones mask"]
+    assert torch.equal(bits(a0[2]), bits(a1[2])) and torch.equal(t0[2], t1[2])
+    for i, (x, y) in enumerate(zip(s0, s1)):
+        assert torch.equal(bits(x), bits(y)), (name, i)
+
+
 # ---- 6. scores at the left-aligned rows ------------------------------------------------------------------------------------------
 def test_ragged_score_against_dense_scores_per_length(hip_lib):
     spec = preset("xlstm_16m")
@@ -281,14 +253,14 @@ def test_ragged_score_against_dense_scores_per_length(hip_lib):
     B, L, lengths = 4, 40, [40, 23, 7, 1]
     A = spec.act_dim
     seq = make_inputs(spec, B, L, seed=21, reset_prob=0.0)
-    obs, rtg, rew = _stack(seq, L, lengths)
+    obs, rtg, rew = stack(seq, L, lengths)
     g = torch.Generator().manual_seed(3)
     target = (torch.rand(B, L, A, generator=g) * 2 - 1).to(DEV)
     valid = torch.ones(B, L, dtype=torch.uint8)
     valid[0, 3] = valid[1, 22] = valid[1, 5] = 0       # read at the left-aligned row
     valid = valid.to(DEV)
     ones = torch.ones(B, dtype=torch.uint8, device=DEV)
-    e_score, e_pre, e_ref = (_engine(spec, sd, B) for _ in range(3))
+    e_score, e_pre, e_ref = (new_engine(spec, sd, B) for _ in range(3))
     res = e_score.score(obs, rtg, rew, actions=target, valid=valid, reset_mask=ones, logits=True, lengths=lengths)
     a_pre, t_pre = e_pre.prefill(obs, rtg, rew, reset_mask=ones, lengths=lengths)
     torch.cuda.synchronize()
@@ -313,8 +285,8 @@ def test_ragged_score_against_dense_scores_per_length(hip_lib):
         assert err <= bar, (b, err, bar)
         # the env's last timestep went through the head launches prefill(lengths=...) makes for its action
         if valid[b, n - 1]:
-            assert torch.equal(_bits(res.actions[b, n - 1]), _bits(a_pre[b])) and torch.equal(res.tokens[b, n - 1], t_pre[b]), b
-    _same_state(_state(e_score, spec), _state(e_pre, spec), "score(lengths) against prefill(lengths)")
+            assert torch.equal(bits(res.actions[b, n - 1]), bits(a_pre[b])) and torch.equal(res.tokens[b, n - 1], t_pre[b]), b
+    same_state(export_state(e_score, spec), export_state(e_pre, spec), "score(lengths) against prefill(lengths)")
     for e in (e_score, e_pre, e_ref):
         e.close()
 
@@ -329,10 +301,10 @@ def test_ragged_prefill_on_the_token_sequential_geometries(hip_lib, name):
     B, L, lengths = 4, 11, [11, 6, 2, 1]
     assert context_plan(L, lengths, 4) == [0, 3, 5, 9, 10]
     seq = make_inputs(spec, B, L, seed=31, reset_prob=0.0)
-    refs = [EnvRef(spec, sd, seq, b, n, L, 0) for b, n in enumerate(lengths)]
-    eng = _engine(spec, sd, B)
+    refs = [EnvRef(spec, sd, seq, b, n) for b, n in enumerate(lengths)]
+    eng = new_engine(spec, sd, B)
     ones = torch.ones(B, dtype=torch.uint8, device=DEV)
-    inputs = _stack(seq, L, lengths)
+    inputs = stack(seq, L, lengths)
     act, _ = eng.prefill(*inputs, reset_mask=ones, lengths=lengths)
     torch.cuda.synchronize()
     assert bool(act.isfinite().all())
@@ -340,11 +312,11 @@ def test_ragged_prefill_on_the_token_sequential_geometries(hip_lib, name):
         _check_env(eng, spec, b, act.cpu(), refs[b], f"{name} ragged prefill")
 
     def refused(call, *needles):
-        before = _state(eng, spec)
+        before = export_state(eng, spec)
         with pytest.raises(LramError) as err:
             call()
         assert all(n in str(err.value) for n in needles), str(err.value)
-        _same_state(before, _state(eng, spec), str(err.value))
+        same_state(before, export_state(eng, spec), str(err.value))
 
     if spec.backbone == "mamba":
         for kw, needle in ((dict(mamba_repeat=2), "mamba_repeat"), (dict(stale_state=True), "stale_state")):
@@ -359,13 +331,13 @@ def test_ragged_prefill_on_the_token_sequential_geometries(hip_lib, name):
         arr = (ctypes.c_int32 * B)(*bad)
         rc = lambda: eng.lib.lram_prefill_ragged(eng._h, _ptr(inputs[0]), 0, _ptr(inputs[1]), _ptr(inputs[2]), L, arr, _ptr(ones), 0,
                                                  _ptr(eng._actions), _ptr(eng._tokens), _stream_ptr(eng.device))
-        before = _state(eng, spec)
+        before = export_state(eng, spec)
         assert rc() != 0 and needle in eng.lib.lram_last_error().decode(), eng.lib.lram_last_error()
-        _same_state(before, _state(eng, spec), needle)
+        same_state(before, export_state(eng, spec), needle)
     # ... and the engine is usable afterwards
     act2, _ = eng.prefill(*inputs, reset_mask=ones, lengths=lengths)
     torch.cuda.synchronize()
-    assert torch.equal(_bits(act2), _bits(act))
+    assert torch.equal(bits(act2), bits(act))
     eng.close()
 
 
@@ -384,7 +356,7 @@ def test_two_env_slices_equal_one(hip_lib):
     eng, act, tok = _run16(set_micro_batches=2)
     for b in range(B):
         _check_env(eng, spec, b, act.cpu(), refs[b], "16M ragged prefill, two env slices")
-    for i, (got, want) in enumerate(zip(_state(eng, spec), s0)):
+    for i, (got, want) in enumerate(zip(export_state(eng, spec), s0)):
         assert rel_err(got, want) < 1e-4, i
     eng.close()
     Ls, lengths = 13, [13, 13, 8, 8, 3, 1]
@@ -392,15 +364,15 @@ def test_two_env_slices_equal_one(hip_lib):
     ones = torch.ones(B, dtype=torch.uint8, device=DEV)
     out = []
     for micro in (1, 2):
-        eng = _engine(spec, sd, B)
+        eng = new_engine(spec, sd, B)
         eng.set_micro_batches(micro)
         for rep in range(2):    # the second call over a state that is not empty
-            act, tok = eng.prefill(*_stack(seq, Ls, lengths), reset_mask=ones, lengths=lengths)
+            act, tok = eng.prefill(*stack(seq, Ls, lengths), reset_mask=ones, lengths=lengths)
         torch.cuda.synchronize()
-        out.append((act.cpu(), tok.cpu(), [t.cpu() for t in _state(eng, spec)]))
+        out.append((act.cpu(), tok.cpu(), [t.cpu() for t in export_state(eng, spec)]))
         eng.close()
-    assert torch.equal(_bits(out[0][0]), _bits(out[1][0])) and torch.equal(out[0][1], out[1][1])
-    _same_state(out[0][2], out[1][2], "two env slices against one")
+    assert torch.equal(bits(out[0][0]), bits(out[1][0])) and torch.equal(out[0][1], out[1][1])
+    same_state(out[0][2], out[1][2], "two env slices against one")
 
 
 # ---- 9. the agent ----------------------------------------------------------------------------------------------------------------
@@ -425,7 +397,7 @@ def test_agent_scores_or_primes_contexts_and_continues(hip_lib):
     last = a_prime.prime_contexts(ctx_obs, ctx_rtg, lengths=lengths, want_action=True)
     torch.cuda.synchronize()
     for b, n in enumerate(lengths):
-        assert torch.equal(_bits(res.actions[b, n - 1]), _bits(last[b])), b
+        assert torch.equal(bits(res.actions[b, n - 1]), bits(last[b])), b
         assert bool((res.tokens[b, n:] == -1).all()) and bool(res.logp[b, :n, :n_act].isfinite().all()), b
     # env b's next observation is the one behind ITS context
     nxt_obs = torch.stack([obs[b, n] for b, n in enumerate(lengths)])
@@ -433,7 +405,7 @@ def test_agent_scores_or_primes_contexts_and_continues(hip_lib):
     act_s = a_score.predict_batch(nxt_obs, nxt_rtg).clone()
     act_p = a_prime.predict_batch(nxt_obs, nxt_rtg).clone()
     torch.cuda.synchronize()
-    assert torch.equal(_bits(act_s), _bits(act_p))
+    assert torch.equal(bits(act_s), bits(act_p))
     pad = torch.zeros(B, L + 1, spec.state_dim)
     pad[..., :n_obs] = obs
     for b, n in enumerate(lengths):
