@@ -21,8 +21,10 @@ import torch
 
 from lram_amd import init_state_dict, preset
 from lram_amd.engine import context_plan
-from tests.context_cases import DEV, EnvRef, bits, env_slices, export_state, new_engine, same_state, stack, steps, u8_mask
-from tests.helpers import assert_actions_match, make_inputs, rel_err, sampled_state, state_vs_oracle
+from tests.context_cases import (DEV, EnvRef, bits, check_continued as _check_continued, check_restarted as _check_restarted,
+                                 clear_margins as _clear_margins, env_slices, export_state, new_engine, same_state, stack, steps,
+                                 stepping_snapshots as _stepping_snapshots, u8_mask)
+from tests.helpers import assert_actions_match, make_inputs, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -30,56 +32,6 @@ LENGTHS_16M = [47, 47, 30, 30, 9, 1]
 RESTART_16M = [0, 1, 0, 1, 0, 0]
 PRE = 5        # env-steps ahead of the append call (16M and held-slot cases)
 EXTRA = 3      # env-steps behind the contexts
-MIN_GAP = 1e-3
-
-
-def _clear_margins(refs, what):
-    """Before the engine is consulted: every compared row of the oracle runs has a clear winner."""
-    gap = min(r.min_gap for r in refs)
-    print(f"[append] {what}: smallest oracle top-2 logit gap over the compared rows {gap:.3e} (needs >= {MIN_GAP:.0e})")
-    assert gap >= MIN_GAP, (what, gap)
-
-
-def _check_restarted(eng, spec, b, actions, ref, what):
-    """env b against its oracle run from an empty state: the action (no tie tolerated), every state tensor, block 0's conv state."""
-    if actions is not None:
-        assert assert_actions_match(actions[b:b + 1], ref.act, ref.logits, spec, what=f"{what} env {b}") == 0
-    export = sampled_state(eng, spec, [b])
-    state_vs_oracle(export, ref.state, spec, f"{what} env {b}", rows=[b])
-    conv = ref.state[0][0] if spec.backbone == "mamba" else ref.state["block_0"]["conv_state"][0]
-    err = rel_err(export(0, 3), conv)
-    print(f"[append] {what} env {b}: block 0 conv state rel_err {err:.2e} (bar 1e-5)")
-    assert err < 1e-5, (what, b, err)
-
-
-def _check_continued(eng, spec, b, actions, ref, snap, what):
-    """env b, which continued its state: the action against the oracle, the state against the stepping engine's snapshot."""
-    if actions is not None:
-        assert assert_actions_match(actions[b:b + 1], ref.act, ref.logits, spec, what=f"{what} env {b}") == 0
-    slices, record = snap
-    worst = 0.0
-    for i, (got, want) in enumerate(zip(env_slices(eng, spec, b), slices)):
-        err = rel_err(got, want)
-        worst = max(worst, err)
-        assert err < 1e-4, (what, b, i, err)
-    rec = rel_err(eng.save_slots([b]).cpu(), record)
-    print(f"[append] {what} env {b}: state against the stepping engine, worst tensor rel_err {worst:.2e}, record {rec:.2e} (bar 1e-4)")
-    assert rec < 1e-4, (what, b, rec)
-
-
-def _stepping_snapshots(spec, sd, B, seq, pre, lengths, restart, L):
-    """A second engine takes the env-steps `pre`, then timesteps 0 .. L - 1 one lram_step at a time (the restart flags on timestep
-    0); env b's state -- every exported tensor and its save_slots record -- is taken right after its own last step."""
-    eng = new_engine(spec, sd, B)
-    steps(eng, seq, pre)
-    snaps = {}
-    for t in range(max(lengths)):
-        eng.step(*(x.to(DEV) for x in seq[t][:3]), u8_mask(restart) if t == 0 else None)
-        for b, n in enumerate(lengths):
-            if n == t + 1:
-                snaps[b] = (env_slices(eng, spec, b), eng.save_slots([b]).cpu())
-    eng.close()
-    return snaps
 
 
 _CACHE = {}
