@@ -238,8 +238,8 @@ int32_t lram_score(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embe
  * than 2 GiB of device memory free.
  * Out of scope: stored contexts on a subset
  * of slots without computing the other rows (kept slots are saved and restored, not skipped; env-STEPS on a live prefix of the
- * slots are lram_set_live's, below, and these entries are refused while slots are parked); image frames as stored contexts; the
- * Mamba reference-trajectory modes.  The dense entries, the lazy step path and the GEMM dispatcher are unchanged.  (A shorter
+ * slots are lram_set_live's, below, and these entries are refused while slots are parked); the Mamba reference-trajectory
+ * modes (contexts from image frames: lram_prefill_frames, below).  The dense entries, the lazy step path and the GEMM dispatcher are unchanged.  (A shorter
  * context that CONTINUES a slot's state is lram_prefill_append / lram_score_append, below.) */
 int32_t lram_prefill_ragged(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
                             const float* dev_reward_seq, int32_t timesteps, const int32_t* host_lengths,
@@ -275,7 +275,7 @@ int32_t lram_score_ragged(lram_engine* e, const float* dev_obs_seq, int32_t obs_
  * rule -- a length outside 0 .. timesteps; all lengths 0; tokens_per_step != 3; d_model % 4 != 0; raw observations whose
  * [batch, timesteps, d_model] embeddings exceed 2 GiB; both Mamba modes of lram_set_compat_mode; parked slots (lram_set_live).
  * Out of scope: skipping the held envs' rows in the projections (hold stops state writes and, where it is free, state reads);
- * stored contexts while slots are parked; image frames; the Mamba reference-trajectory modes. */
+ * stored contexts while slots are parked; the Mamba reference-trajectory modes.  (Frames: lram_prefill_frames, below.) */
 int32_t lram_prefill_append(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
                             const float* dev_reward_seq, int32_t timesteps, const int32_t* host_lengths,
                             const uint8_t* dev_reset_mask, int32_t discrete, float* dev_actions, int32_t* dev_tokens, void* stream);
@@ -555,6 +555,12 @@ int32_t lram_gemm_counts(lram_engine* e, double* out8, int32_t reset);
  * to compare really ran.  (Reference: one sLSTMLayer.step per token, src/algos/models/decision_xlstm.py:155-166.) */
 int32_t lram_slstm_counts(lram_engine* e, int64_t* out3, int32_t reset);
 
+/* Measurement aid: what the frame-list front end (lram_embed_frames, lram_prefill_frames, lram_score_frames) has done since
+ * lram_create or the last call with `reset` != 0 -- out[0] frames convolved, out[1] tiles launched (one pass of the conv stages
+ * each), out[2] launches of the CNN's Linear.  The env-step entries (lram_embed_images, lram_step_images, lram_step_slots) are
+ * not counted.  Tests read it to prove that padded frames were skipped. */
+int32_t lram_image_counts(lram_engine* e, int64_t* out3, int32_t reset);
+
 /* Standalone kernel entry points used by tests and micro-benchmarks. */
 /* C[M,N] = A[M,K] * W[N,K]^T (+ bias[N]) (+ residual C_in)   fp32, MFMA 32x32x2 f32 (exact k-ordered fma chain) */
 int32_t lram_gemm_f32(const float* dev_a, int64_t lda, const float* dev_w, int64_t ldw, float* dev_c,
@@ -645,6 +651,48 @@ int32_t lram_embed_images(lram_engine* e, const uint8_t* dev_images, int32_t cha
 int32_t lram_step_images(lram_engine* e, const uint8_t* dev_images, int32_t channels, int32_t height, int32_t width,
                          const float* dev_rtg, const float* dev_reward, const uint8_t* dev_reset_mask, int32_t discrete,
                          float* dev_actions_out, int32_t* dev_tokens_out, void* stream);
+/* ANY number of frames, uint8 [n_frames, channels, height, width] -> [n_frames, d_model], n_frames >= 1 whatever the batch:
+ * lram_embed_images' arithmetic through the frame-list path of the stored contexts below.  The frames go through the conv
+ * stages in tiles of LRAM_IMG_TILE frames (read at lram_create; capped so that one tile's maps stay within 2 GiB), every
+ * tile's last map into its rows of one [n_frames, features] operand, and ONE Linear runs over all of it: the result does not
+ * depend on the tile, bit for bit.  (It may differ in the last bits from lram_embed_images on the same frames: the Linear's
+ * kernel is chosen by row count.)  Refused when that operand would exceed 2 GiB. */
+int32_t lram_embed_frames(lram_engine* e, const uint8_t* dev_frames, int64_t n_frames, int32_t channels, int32_t height,
+                          int32_t width, float* dev_embeddings, void* stream);
+/* Stored contexts whose observations are uint8 frames: lram_prefill / lram_score (host_lengths NULL), their ragged forms
+ * (host_lengths given, append 0: the replace rule) and their append forms (append 1), with the IMPALA CNN as the source of the
+ * state embeddings -- what the reference's forward does with a batch of image trajectories (`compute_inputs`,
+ * online_decision_transformer_model.py:463-530, under the masked loss of universal_decision_transformer_sb3.py:398-434).
+ *   dev_frames        uint8 [n, timesteps, channels, height, width], LEFT-aligned like every other input.  Without a slot table
+ *                     n = batch.  With one, n = its image slots, in ascending slot order (as lram_step_slots takes frames).
+ *   dev_obs_seq       float [batch, timesteps, state_dim]: required when a slot table with vector slots is set -- the state Linear
+ *                     runs over all of its rows first and the image slots' rows are then overwritten, so whatever the rows of
+ *                     image slots hold, NaN included, reaches no output.  Never read otherwise (NULL is fine).
+ *   host_lengths      NULL: every context has all `timesteps`.  Else as in the ragged / append entries, and only frames [b, l] with
+ *                     l < n_b are read: the engine builds, on the device, a list of the frames that count ({frame index, row
+ *                     b * timesteps + l} per entry, from the per-env starts and the slot table's image list) and the CNN runs
+ *                     over that list alone -- a padded frame is never read or convolved and costs nothing.
+ *   append            0 or 1; ignored without host_lengths.
+ *   everything else   as in lram_prefill / lram_score and their ragged / append forms: one body, the same refusals in the same order.
+ * With every length equal to `timesteps` the call makes the dense call's launches.  State, actions, tokens and log-probabilities
+ * are bit-identical to lram_prefill / lram_score(obs_is_embedding = 1) over lram_embed_frames of the same frames where the
+ * list is the same (a dense call); per-env lengths shorten the list, and the Linear's kernel follows its row count.
+ * Refused in addition (nothing launched, state untouched): no embed_image.* weights; a frame size that does not fit the Linear;
+ * tokens_per_step != 3, d_model % 4 != 0 or a Mamba mode of lram_set_compat_mode (the pass that makes all state embeddings
+ * ahead of the chunks does not exist there); [batch, timesteps, d_model] embeddings or flattened maps beyond 2 GiB; a slot table
+ * without image slots; dev_obs_seq NULL with vector slots in the table.
+ * Everything runs on the call's stream ahead of the first chunk.  Out of scope: overlapping the CNN with the chunk lanes; a
+ * matrix-core convolution (the step and the contexts keep one arithmetic). */
+int32_t lram_prefill_frames(lram_engine* e, const uint8_t* dev_frames, int32_t channels, int32_t height, int32_t width,
+                            const float* dev_obs_seq, const float* dev_rtg_seq, const float* dev_reward_seq, int32_t timesteps,
+                            const int32_t* host_lengths, int32_t append, const uint8_t* dev_reset_mask, int32_t discrete,
+                            float* dev_actions, int32_t* dev_tokens, void* stream);
+int32_t lram_score_frames(lram_engine* e, const uint8_t* dev_frames, int32_t channels, int32_t height, int32_t width,
+                          const float* dev_obs_seq, const float* dev_rtg_seq, const float* dev_reward_seq, int32_t timesteps,
+                          const int32_t* host_lengths, int32_t append, const uint8_t* dev_reset_mask, int32_t discrete,
+                          const float* dev_target_actions, const int32_t* dev_target_tokens, const uint8_t* dev_valid, int32_t over,
+                          double temperature, float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits,
+                          void* stream);
 
 /* Slot table: per env slot the head mode, the number of action dims in use and the observation kind -- what the reference's
  * evaluation loop hands every call for ONE env (`env_act_dim`, `is_discrete`: src/callbacks/evaluation.py:90-138; the head

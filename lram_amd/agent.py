@@ -497,20 +497,63 @@ class RecurrentAgent:
     def _prepare_contexts(self, observations, returns_to_go, rewards, lengths):
         """What the stored-context calls share: observations [B, L, obs_dim] padded and normalised (_prepare_obs), returns_to_go
         and rewards (None: zeros) as float32 [B, L] on the device, `lengths` checked (check_context_lengths; None stays None)
-        and the head mode the engine is to use.  Returns (obs, rtg, rew, lengths, discrete)."""
+        and the head mode the engine is to use.  Image observations: uint8 frames [B, L, C, H, W], or with a slot table the pair
+        (vector_obs [B, L, obs_dim] or None, frames uint8 [n_image, L, C, H, W] in slot order), as predict_batch takes one
+        timestep; the frames go to the engine as they are (Engine.prefill_frames / score_frames run the CNN inside the call).
+        Returns (obs, frames, rtg, rew, lengths, discrete): frames None for vector observations; with frames, obs is the vector
+        slots' rows or None."""
         B = self.n_envs
-        if observations.dim() != 3 or observations.shape[0] != B:
+        table = getattr(self, "slot_table", None)
+        frames = None
+        if isinstance(observations, (tuple, list)):
+            if table is None or len(observations) != 2:
+                raise ValueError("observations: the pair (vector_obs, frames) goes with a slot table")
+            observations, frames = observations
+            if frames is None and table.n_image > 0:
+                raise ValueError(f"frames: expected uint8 [{table.n_image}, L, C, H, W] (one row per image slot, in slot order)")
+        elif observations.dim() == 5:
+            if table is not None:
+                raise ValueError("observations: with a slot table image contexts are the pair (vector_obs, frames)")
+            observations, frames = None, observations
+        if frames is not None:
+            if not self.has_image_encoder:
+                raise RuntimeError("image observation given but the state dict has no embed_image.* weights")
+            n = B if table is None else table.n_image
+            if frames.dim() != 5 or frames.shape[0] != n:
+                raise ValueError(f"frames: expected uint8 [{n}, L, C, H, W], got {tuple(frames.shape)}")
+            frames = frames.to(self.device).to(torch.uint8).contiguous()
+            if table is not None and n == B:
+                observations = None   # (every slot takes frames)
+            elif table is not None and observations is None:
+                raise ValueError("vector_obs: None is allowed only when every slot is an image slot")
+        if frames is None and (observations.dim() != 3 or observations.shape[0] != B):
             raise ValueError(f"observations: expected [{B}, L, obs_dim], got {tuple(observations.shape)}")
-        L = observations.shape[1]
+        L = (observations if frames is None else frames).shape[1]
+        obs = None
+        if observations is not None:
+            if observations.dim() != 3 or observations.shape[0] != B or observations.shape[1] != L:
+                raise ValueError(f"vector_obs: expected [{B}, {L}, obs_dim], got {tuple(observations.shape)}")
+            obs, _ = self._prepare_obs(observations.reshape(B * L, -1))
+            obs = obs.view(B, L, -1).contiguous()
         if lengths is not None:
             lengths = check_context_lengths(torch.as_tensor(lengths).reshape(-1), B, L)
-        obs, _ = self._prepare_obs(observations.reshape(B * L, -1))
-        obs = obs.view(B, L, -1).contiguous()
         rtg = returns_to_go.to(self.device, torch.float32).reshape(B, L).contiguous()
         rew = torch.zeros(B, L, dtype=torch.float32, device=self.device) if rewards is None else \
             rewards.to(self.device, torch.float32).reshape(B, L).contiguous()
         discrete = "per_slot" if getattr(self, "slot_table", None) is not None else self.is_discrete
-        return obs, rtg, rew, lengths, discrete
+        return obs, frames, rtg, rew, lengths, discrete
+
+    def _engine_prefill(self, obs, frames, rtg, rew, **kw):
+        if frames is None:
+            return self.engine.prefill(obs, rtg, rew, **kw)
+        return self.engine.prefill_frames(frames, rtg, rew, obs_seq=obs, **kw)
+
+    def _engine_score(self, obs, frames, rtg, rew, lo=None, hi=None, **kw):
+        """Engine.score / score_frames on the timesteps [lo, hi) of the prepared inputs (None: all)."""
+        cut = (lambda t: t) if lo is None else (lambda t: None if t is None else t[:, lo:hi].contiguous())
+        if frames is None:
+            return self.engine.score(cut(obs), cut(rtg), cut(rew), **kw)
+        return self.engine.score_frames(cut(frames), cut(rtg), cut(rew), obs_seq=cut(obs), **kw)
 
     # ---- grading: stored trajectories and the actions just taken --------------------------------------
     @torch.no_grad()
@@ -528,14 +571,15 @@ class RecurrentAgent:
         length 0 keeps the state it had).  reset=True starts every env from an empty context; a length in 1 .. L - 1 always does,
         so reset=False together with such a length raises ValueError.  Returns the ScoreResult (per-timestep greedy actions / tokens and the log-probability of the recorded
         actions); rollout.score_loss turns it into the reference's loss.  With a slot table every slot is scored with its
-        own head; image observations are not taken here (embed them and call Engine.score with obs_is_embedding).
+        own head.  Image observations: uint8 frames [B, L, C, H, W], or with a slot table the pair (vector_obs, frames
+        [n_image, L, C, H, W]) as predict_batch takes one timestep (Engine.score_frames: padded frames are never convolved).
         `window=W` with W < L scores the trajectories in ceil(max(lengths) / W) calls (Engine.score(append=True)): call k covers
         rows [k W, (k + 1) W) with the lengths clamp(lengths[b] - k W, 0, W), every call continuing the state the one before left;
         `reset` is honoured on call 0 only.  The result is one ScoreResult of the full [B, L, ...] shape and the state afterwards
         that of each env's own timesteps, as for the single call (up to fp32 rounding: the chunks differ); the engine embeds
         B x W raw observations per call instead of B x L, which lifts the single call's 2 GiB bound.  Appended contexts never
         replace a state, so reset=False with shorter lengths is accepted here.  window=None (or W >= L): the single call."""
-        obs, rtg, rew, lengths, discrete = self._prepare_contexts(observations, returns_to_go, rewards, lengths)
+        obs, frames, rtg, rew, lengths, discrete = self._prepare_contexts(observations, returns_to_go, rewards, lengths)
         B, L = rtg.shape
         target = None
         if actions is not None:
@@ -553,8 +597,8 @@ class RecurrentAgent:
         mask = torch.ones(B, dtype=torch.uint8, device=self.device) if reset else None
         want = tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "logp" or target is not None)
         if not windowed:
-            return self.engine.score(obs, rtg, rew, actions=target, reset_mask=mask, discrete=discrete, over=over,
-                                     temperature=temperature, want=want, logits=logits, lengths=lengths)
+            return self._engine_score(obs, frames, rtg, rew, actions=target, reset_mask=mask, discrete=discrete, over=over,
+                                      temperature=temperature, want=want, logits=logits, lengths=lengths)
         W = int(window)
         n_all = [L] * B if lengths is None else list(lengths)
         A = self.spec.act_dim
@@ -566,10 +610,10 @@ class RecurrentAgent:
             logits=torch.zeros(B, L, A, self.spec.n_vocab, dtype=torch.float32, device=self.device) if logits else None)
         for k in range(-(-max(n_all) // W)):
             lo, hi = k * W, min((k + 1) * W, L)
-            part = self.engine.score(obs[:, lo:hi].contiguous(), rtg[:, lo:hi].contiguous(), rew[:, lo:hi].contiguous(),
-                                     actions=None if target is None else target[:, lo:hi].contiguous(),
-                                     reset_mask=mask if k == 0 else None, discrete=discrete, over=over, temperature=temperature,
-                                     want=want, logits=logits, lengths=[min(max(n - lo, 0), hi - lo) for n in n_all], append=True)
+            part = self._engine_score(obs, frames, rtg, rew, lo, hi,
+                                      actions=None if target is None else target[:, lo:hi].contiguous(),
+                                      reset_mask=mask if k == 0 else None, discrete=discrete, over=over, temperature=temperature,
+                                      want=want, logits=logits, lengths=[min(max(n - lo, 0), hi - lo) for n in n_all], append=True)
             for name in ScoreResult.__slots__:
                 if getattr(out, name) is not None:
                     getattr(out, name)[:, lo:hi] = getattr(part, name)
@@ -581,20 +625,20 @@ class RecurrentAgent:
         """Append to every env's state a stored context of its own length in one call (Engine.prefill(lengths=..., append=True)),
         after which predict_batch continues: the steps envs at different points of their episodes missed, or a demonstration
         that continues an in-context evaluation (persist_context).  observations [B, L, obs_dim] -- native, padded and normalised
-        as prime_contexts does -- returns_to_go [B, L], rewards [B, L] (None: zeros), `lengths` [B]: env b takes its first
+        as prime_contexts does, image observations included -- returns_to_go [B, L], rewards [B, L] (None: zeros), `lengths` [B]: env b takes its first
         lengths[b] timesteps (None = all L); an env of length 0 keeps its state bit for bit.  `restart` [B] bool (None: nobody):
         the envs that start from an empty state before their first timestep.  want_action=True returns the action at each env's
         own last timestep (as predict_batch returns it; 0 for an env of length 0), else None."""
         B = self.n_envs
-        obs, rtg, rew, lengths, discrete = self._prepare_contexts(observations, returns_to_go, rewards, lengths)
+        obs, frames, rtg, rew, lengths, discrete = self._prepare_contexts(observations, returns_to_go, rewards, lengths)
         mask = None
         if restart is not None:
             mask = torch.as_tensor(restart).reshape(-1)
             if mask.shape[0] != B:
                 raise ValueError(f"restart: expected {B} entries (one per env), got {mask.shape[0]}")
             mask = (mask != 0).to(self.device, torch.uint8).contiguous()
-        actions, _ = self.engine.prefill(obs, rtg, rew, reset_mask=mask, discrete=discrete, want_action=want_action,
-                                         lengths=lengths, append=True)
+        actions, _ = self._engine_prefill(obs, frames, rtg, rew, reset_mask=mask, discrete=discrete, want_action=want_action,
+                                          lengths=lengths, append=True)
         if not want_action:
             return None
         return actions[:, :1].to(torch.int64) if self.is_discrete else actions
@@ -606,13 +650,13 @@ class RecurrentAgent:
         continues: observations [B, L, obs_dim] -- padded and normalised as predict_batch does -- returns_to_go [B, L], rewards
         [B, L] (None: zeros) and `lengths` [B]: env b's context is its first lengths[b] timesteps (None = all L).  Every env
         with a context starts from an empty state; an env of length 0 keeps the state it has.  want_action=True returns the
-        action at each env's own last timestep (as predict_batch returns it), else None.  Image observations are not taken
-        here, as in score_trajectories."""
+        action at each env's own last timestep (as predict_batch returns it), else None.  Image observations as in
+        score_trajectories."""
         B = self.n_envs
-        obs, rtg, rew, lengths, discrete = self._prepare_contexts(observations, returns_to_go, rewards, lengths)
+        obs, frames, rtg, rew, lengths, discrete = self._prepare_contexts(observations, returns_to_go, rewards, lengths)
         mask = torch.ones(B, dtype=torch.uint8, device=self.device)
-        actions, _ = self.engine.prefill(obs, rtg, rew, reset_mask=mask, discrete=discrete, want_action=want_action,
-                                         lengths=lengths)
+        actions, _ = self._engine_prefill(obs, frames, rtg, rew, reset_mask=mask, discrete=discrete, want_action=want_action,
+                                          lengths=lengths)
         if not want_action:
             return None
         return actions[:, :1].to(torch.int64) if self.is_discrete else actions

@@ -643,10 +643,17 @@ struct Conv3x3Args {
   float* out;             // [B, COUT, H, W]
   int B, CIN, COUT, H, W;
   int in_relu, out_relu, in_u8;
+  const int32_t* src = nullptr;  // optional frame list ({src, dst} pairs): input frame k is in[src[2 * k]] (uint8 first conv only)
 };
+constexpr int kConvMaxFrames = 16384;   // frames per conv3x3 launch (grid.y), far below the 65535 a grid's y extent holds
 void launch_conv3x3(const Conv3x3Args& a, hipStream_t stream);
 void launch_maxpool3s2(const float* in, float* out, int64_t planes, int H, int W, hipStream_t stream);
 void launch_relu(float* x, int64_t n, hipStream_t stream);
+// Stored contexts from frames: the device table of {src, dst} pairs (one per frame that counts; n_env envs hand in frames of L
+// timesteps each, env k being slot slots[k] -- null: k -- with its first L - start[b] timesteps -- null: all L), and the ReLU of
+// the Linear's compact rows placed at their dst rows of `out`.
+void launch_frame_list(int32_t* list, const int32_t* start, const int32_t* slots, int n_env, int L, hipStream_t stream);
+void launch_relu_place_rows(const float* rows, const int32_t* list, float* out, int64_t N, int D, hipStream_t stream);
 
 // misc
 void launch_pad_obs(const float* native, int n_native, const int32_t* inv_index, const float* mean, const float* stdv,

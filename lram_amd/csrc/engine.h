@@ -152,6 +152,18 @@ struct lram_engine {
   int img_channels = 0, img_flat = 0;  // input channels, flattened feature count of the linear layer
   DevBuf IMG_P, IMG_X0, IMG_X1, IMG_T;
   DevBuf IMG_EMB;                      // [B, D] state-token embeddings of lram_step_images
+  // Stored contexts from frames (lram_embed_frames, lram_prefill_frames, lram_score_frames): the frames that count go through the
+  // conv stages in tiles of img_tile frames -- the four work buffers above then hold max(B, tile) frames, an env-step's regions
+  // where they always were -- every tile's last map into its rows of IMG_FLAT [N, img_flat]; ONE Linear over all N rows into
+  // IMG_ROWS [N, D] (the dispatcher picks its kernel by row count: per-tile launches would make the embeddings depend on the
+  // tile), then ReLU + placement.  IMG_LIST: the {src, dst} pairs, int32 [N][2].  All grown outside the launches, as SEQ_EMB is.
+  DevBuf IMG_FLAT, IMG_ROWS, IMG_LIST;
+  // LRAM_IMG_TILE (capped per frame size: frame_tile() in engine_step.hip).  206M, 64 envs x 512 timesteps of 64 x 64 frames, one
+  // job: the CNN's share of lram_prefill_frames at tiles of 128 / 256 / 512 / 1024 / 2048 frames 126.6 / 74.3 / 57.1 / 48.6 / 46.1 ms
+  // (the whole call 350.7 ms at 2048, 0.74 % ahead of 1024; profiles/image_contexts.txt).  The buffers follow the list: a call of
+  // fewer frames than the tile allocates for its own number.
+  int img_tile = 2048;
+  int64_t img_counts[3] = {0, 0, 0};   // frames convolved, tiles launched, Linear launches of those calls (lram_image_counts)
   // lram_step_images (Pass::images, the frames of the env-step under way): every env slice runs the IMPALA-CNN on
   // its own frames on its own stream, and the state-pass stream takes fold_bubbles_images folds ahead of the first read pass --
   // the VALU-bound CNN and the HBM-bound folds share the start of the step
@@ -402,7 +414,7 @@ struct lram_engine {
     drop_slot_segments();
     st.clear();
     for (DevBuf* b : {&X, &XN, &TOK, &HID, &U, &Q, &K, &V, &XA, &H, &G, &SCAL, &RY, &LOGITS, &RES, &DTP, &SK, &GATES,
-                      &AMAT, &VEC, &SEQ_EMB, &IMG_EMB, &IMG_P, &IMG_X0, &IMG_X1, &IMG_T, &XN2, &ASCALE, &AMX_XN, &AMX_XA, &AMX_H, &X0, &U0, &SCORE_LG, &CTX, &KEEP})
+                      &AMAT, &VEC, &SEQ_EMB, &IMG_EMB, &IMG_FLAT, &IMG_ROWS, &IMG_LIST, &IMG_P, &IMG_X0, &IMG_X1, &IMG_T, &XN2, &ASCALE, &AMX_XN, &AMX_XA, &AMX_H, &X0, &U0, &SCORE_LG, &CTX, &KEEP})
       b->release();
     for (auto& t : twin)
       for (DevBuf& b : t) b.release();

@@ -547,6 +547,7 @@ const Knob kKnobs[] = {
        e.chunk_prefill = std::atoi(v) != 0, e.chunk_exact_fp32 = std::atoi(v) == 2, e.chunk_lanes = std::atoi(v) != 3;
      }},
     {"LRAM_SCORE_ROWS", [](lram_engine& e, const char* v) { e.score_rows = std::max(lram_engine::kScoreMinRows, std::atoi(v)); }},
+    {"LRAM_IMG_TILE", [](lram_engine& e, const char* v) { e.img_tile = std::max(1, std::min(kConvMaxFrames, std::atoi(v))); }},
     {"LRAM_EVENT_SCOPE", [](lram_engine& e, const char* v) { e.event_device_scope = std::string(v) != "system"; }},
 };
 

@@ -31,10 +31,8 @@ ImageFrameFloats image_frame_floats(int H, int W) {
   return {std::max((size_t)16 * H * W, x), x};
 }
 
-// Checks the frame size against the uploaded weights, then makes the image work buffers hold B frames of H x W: every buffer
-// by what it holds at this size, each grown on its own need (two sizes that feed the same linear layer can differ in which
-// of them has the larger pooled map).  Synchronises when it has to grow one: never called between a fork and a join.
-void image_buffers(lram_engine* e, int C, int H, int W, const char* who) {
+// Checks the frame size against the uploaded weights: everything that refuses a call for its frames, nothing allocated.
+void check_frame_size(const lram_engine* e, int C, int H, int W, const char* who) {
   const std::string wh(who);
   LRAM_REQUIRE(e->img_lin_w != nullptr, wh + ": no embed_image.* weights were uploaded");
   LRAM_REQUIRE(C == e->img_channels, wh + ": channel count " + std::to_string(C) +
@@ -45,8 +43,16 @@ void image_buffers(lram_engine* e, int C, int H, int W, const char* who) {
                                               " (pooled " + std::to_string(h) + " x " + std::to_string(w) + ", " +
                                               std::to_string((int64_t)32 * h * w) + " features) does not match embed_image.linear.0.weight (" +
                                               std::to_string(e->img_flat) + " features)");
+}
+
+// ... then makes the image work buffers hold `frames` frames of H x W (an env-step: the batch; a frame list: the larger of the
+// batch and its tile): every buffer by what it holds at this size, each grown on its own need (two sizes that feed the same
+// linear layer can differ in which of them has the larger pooled map).  A region starts at a multiple of the per-frame size, so
+// growing a buffer moves nobody's region.  Synchronises when it has to grow one: never called between a fork and a join.
+void image_buffers(lram_engine* e, int C, int H, int W, const char* who, size_t frames = 0) {
+  check_frame_size(e, C, H, W, who);
   const ImageFrameFloats f = image_frame_floats(H, W);
-  const size_t B = e->B, np = B * f.p, nx = B * f.x;
+  const size_t B = std::max((size_t)e->B, frames), np = B * f.p, nx = B * f.x;
   if (np <= e->IMG_P.n && nx <= e->IMG_X0.n && nx <= e->IMG_X1.n && nx <= e->IMG_T.n) return;
   LRAM_HIP_CHECK(hipDeviceSynchronize());
   if (np > e->IMG_P.n) e->IMG_P.alloc(np);
@@ -62,47 +68,99 @@ void step_image_buffers(lram_engine* e, int C, int H, int W, const char* who) {
   }
 }
 
-// envs b0 .. b0 + nb - 1 (`images` / `out` point at env b0's frame / row; every env slice keeps to its own fixed region of the
-// work buffers, so slices at different stages of the CNN never touch each other's maps)
-void embed_images(lram_engine* e, const uint8_t* images, int C, int H, int W, float* out, hipStream_t s, int b0 = 0, int nb = -1) {
-  const int B = nb < 0 ? e->B : nb, D = e->cfg.d_model;
-  // (image_buffers has checked C, H, W against the weights; the env slices of one call share its buffers)
+// The three conv stages over B frames, their maps in the work buffers from frame region r0 on (every env slice of a step keeps
+// to its own fixed region, so slices at different stages of the CNN never touch each other's maps).  The last map -- act_flatten's
+// ReLU applied, NCHW: a row of the Linear's operand -- goes to `flat` [B, img_flat].  With a frame list the first conv reads frame
+// list[2 * k] of `images` as its k-th; without one, frame k.
+void cnn_stages(lram_engine* e, const uint8_t* images, const int32_t* list, int H, int W, int B, size_t r0, float* flat, hipStream_t s) {
   const ImageFrameFloats f = image_frame_floats(H, W);
-  LRAM_REQUIRE((size_t)e->B * f.p <= e->IMG_P.n && (size_t)e->B * f.x <= e->IMG_X0.n &&
-                   (size_t)e->B * f.x <= e->IMG_X1.n && (size_t)e->B * f.x <= e->IMG_T.n,
+  const size_t end = r0 + (size_t)B;
+  LRAM_REQUIRE(end * f.p <= e->IMG_P.n && end * f.x <= e->IMG_X0.n && end * f.x <= e->IMG_X1.n && end * f.x <= e->IMG_T.n,
                "image work buffers not allocated");
-  float* const P = e->IMG_P.p + (size_t)b0 * f.p;
-  float* const X0 = e->IMG_X0.p + (size_t)b0 * f.x;
-  float* const X1 = e->IMG_X1.p + (size_t)b0 * f.x;
-  float* const Tb = e->IMG_T.p + (size_t)b0 * f.x;
+  float* const P = e->IMG_P.p + r0 * f.p;
+  float* const X0 = e->IMG_X0.p + r0 * f.x;
+  float* const X1 = e->IMG_X1.p + r0 * f.x;
+  float* const Tb = e->IMG_T.p + r0 * f.x;
   const void* in = images;
   int in_u8 = 1;
   int h = H, w = W;
   for (int sidx = 0; sidx < 3; ++sidx) {
     const lram_engine::ImgConv* cv = e->img_conv[sidx];
     auto conv = [&](const lram_engine::ImgConv& c, const void* src, int u8, int relu_in, const float* res, float* dst,
-                    int relu_out) {
+                    int relu_out, const int32_t* frame_list = nullptr) {
       Conv3x3Args a;
-      a.in = src, a.w = c.w, a.bias = c.b, a.residual = res, a.out = dst;
+      a.in = src, a.w = c.w, a.bias = c.b, a.residual = res, a.out = dst, a.src = frame_list;
       a.B = B, a.CIN = c.cin, a.COUT = c.cout, a.H = h, a.W = w, a.in_relu = relu_in, a.out_relu = relu_out, a.in_u8 = u8;
       launch_conv3x3(a, s);
     };
-    conv(cv[0], in, in_u8, 0, nullptr, P, 0);
+    conv(cv[0], in, in_u8, 0, nullptr, P, 0, sidx == 0 ? list : nullptr);
     launch_maxpool3s2(P, X0, (int64_t)B * cv[0].cout, h, w, s);
     h = (h - 1) / 2 + 1, w = (w - 1) / 2 + 1;
     conv(cv[1], X0, 0, 1, nullptr, Tb, 0);
     conv(cv[2], Tb, 0, 1, X0, X1, 0);
     conv(cv[3], X1, 0, 1, nullptr, Tb, 0);
-    conv(cv[4], Tb, 0, 1, X1, X0, sidx == 2 ? 1 : 0);  // act_flatten's ReLU on the last map
+    conv(cv[4], Tb, 0, 1, X1, sidx == 2 ? flat : X0, sidx == 2 ? 1 : 0);  // act_flatten's ReLU on the last map
     in = X0;
     in_u8 = 0;
   }
   // stage s > 0 reads X0 and writes P, then pools back into X0: no aliasing within a launch
+}
+
+// envs b0 .. b0 + nb - 1 of an env-step (`images` / `out` point at env b0's frame / row)
+void embed_images(lram_engine* e, const uint8_t* images, int C, int H, int W, float* out, hipStream_t s, int b0 = 0, int nb = -1) {
+  const int B = nb < 0 ? e->B : nb, D = e->cfg.d_model;
+  // (image_buffers has checked C, H, W against the weights; the env slices of one call share its buffers)
+  float* const X0 = e->IMG_X0.p + (size_t)b0 * image_frame_floats(H, W).x;
+  cnn_stages(e, images, nullptr, H, W, B, (size_t)b0, X0, s);
   GemmArgs g;
   g.a = X0, g.lda = e->img_flat, g.w = e->img_lin_w, g.ldw = e->img_flat, g.c = out, g.ldc = D;
   g.bias = e->img_lin_b, g.m = B, g.n = D, g.k = e->img_flat;
   gemm(e, g, s);
   launch_relu(out, (int64_t)B * D, s);
+}
+
+// ---- stored contexts from frames: the frame list -------------------------------------------------------------------------
+// Frames per tile at this size: the knob, capped so that one tile's maps in the four work buffers stay within 2 GiB and the
+// conv's grid within kConvMaxFrames.
+int64_t frame_tile(const lram_engine* e, int H, int W) {
+  const ImageFrameFloats f = image_frame_floats(H, W);
+  const int64_t cap = std::max<int64_t>(1, (int64_t)(((size_t)1 << 29) / (f.p + 3 * f.x)));
+  return std::min<int64_t>({(int64_t)e->img_tile, cap, (int64_t)kConvMaxFrames});
+}
+
+// What a call of N listed frames needs beyond the work buffers: the list, the Linear's operand and its compact output rows.
+// check: refused, with nothing allocated or launched, when the operand would exceed 2 GiB.
+void check_frame_list(const lram_engine* e, int64_t N, const char* who) {
+  LRAM_REQUIRE((size_t)N * (size_t)e->img_flat <= ((size_t)1 << 29) && (size_t)N * (size_t)e->cfg.d_model <= ((size_t)1 << 29),
+               std::string(who) + ": the flattened maps of " + std::to_string(N) + " frames (" + std::to_string(e->img_flat) +
+                   " features each) exceed 2 GiB: split the call");
+}
+void frame_list_buffers(lram_engine* e, int C, int H, int W, int64_t N, const char* who) {
+  image_buffers(e, C, H, W, who, (size_t)std::min<int64_t>(N, frame_tile(e, H, W)));
+  const size_t flat = (size_t)N * e->img_flat, rows = (size_t)N * e->cfg.d_model, list = (size_t)2 * N;
+  if (e->IMG_FLAT.n >= flat && e->IMG_ROWS.n >= rows && e->IMG_LIST.n >= list) return;
+  LRAM_HIP_CHECK(hipDeviceSynchronize());
+  if (e->IMG_FLAT.n < flat) e->IMG_FLAT.alloc(flat);
+  if (e->IMG_ROWS.n < rows) e->IMG_ROWS.alloc(rows);
+  if (e->IMG_LIST.n < list) e->IMG_LIST.alloc(list);
+}
+
+// The N frames IMG_LIST names -> relu(Linear(cnn(frame src))) in row dst of `out` [., d_model]: the conv stages tile by tile,
+// one Linear over all N rows (the result does not depend on the tile), ReLU + placement.  Buffers by frame_list_buffers.
+void embed_frame_list(lram_engine* e, const uint8_t* frames, int H, int W, int64_t N, float* out, hipStream_t s) {
+  const int D = e->cfg.d_model;
+  const int64_t F = frame_tile(e, H, W);
+  const int32_t* list = reinterpret_cast<const int32_t*>(e->IMG_LIST.p);
+  for (int64_t t0 = 0; t0 < N; t0 += F) {
+    cnn_stages(e, frames, list + 2 * t0, H, W, (int)std::min(F, N - t0), 0, e->IMG_FLAT.p + (size_t)t0 * e->img_flat, s);
+    e->img_counts[1] += 1;
+  }
+  GemmArgs g;
+  g.a = e->IMG_FLAT.p, g.lda = e->img_flat, g.w = e->img_lin_w, g.ldw = e->img_flat, g.c = e->IMG_ROWS.p, g.ldc = D;
+  g.bias = e->img_lin_b, g.m = (int)N, g.n = D, g.k = e->img_flat;
+  gemm(e, g, s);
+  launch_relu_place_rows(e->IMG_ROWS.p, list, out, N, D, s);
+  e->img_counts[0] += N, e->img_counts[2] += 1;
 }
 
 // The (state, rtg, reward) inputs of a call: [B, L, .] / [B, L] row-major (L = 1: one env-step).
@@ -111,6 +169,10 @@ struct Inputs {
   int emb;   // obs holds state-token embeddings [., d_model] instead of observations [., state_dim]
   const float *rtg, *rew;
   int L;
+  // stored contexts from frames (lram_prefill_frames / lram_score_frames): uint8 [n, L, C, H, W], n the image slots of the slot
+  // table in ascending order (no table: every env).  obs is then the [B, L, state_dim] rows of a mixed table's vector slots, or null.
+  const uint8_t* frames = nullptr;
+  int img_c = 0, img_h = 0, img_w = 0;
 };
 
 // Stored contexts of per-env length (the ragged and append entries): the contexts are end-aligned inside the call, env b
@@ -122,9 +184,23 @@ struct ContextPlan {
   std::vector<int> starts;        // ascending call-timesteps at which the chunks start; the last chunk ends at L
   // per chunk: some env is reset at its start / held in it (a chunk without one passes no pointer at all, as a dense call does)
   std::vector<char> has_reset, has_hold;
+  const int32_t* lengths = nullptr;                        // the caller's host array [B]
   const int32_t* dev_start = nullptr;                      // [B]
   const uint8_t *dev_masks = nullptr, *dev_hold = nullptr;   // [n_chunks, B] each
 };
+
+// The frames of a stored-context call that count, and the envs that hand frames in: the image slots of a slot table (every env
+// without one), each with its own length (null: all L).
+struct FrameCount {
+  int n_env;
+  int64_t frames;
+};
+FrameCount count_frames(const lram_engine* e, int L, const int32_t* lengths) {
+  FrameCount n{0, 0};
+  for (int b = 0; b < e->B; ++b)
+    if (!e->slot_table || (e->slot_flags[b] & LRAM_SLOT_IMAGE)) n.n_env += 1, n.frames += lengths ? lengths[b] : L;
+  return n;
+}
 
 // Token front end of one env slice for the chunk of Lc timesteps that starts at timestep l: embeds the chunk's tokens into the
 // slice's rows of X and applies embed_ln.  seq_emb: the state embeddings of a stored context, made ahead of the chunks.
@@ -307,21 +383,34 @@ void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, cons
   // Stored contexts: the state embeddings of ALL timesteps as one GEMM ahead of the chunks (rows b * L + l, as the input lies),
   // instead of one few-row GEMM per timestep (206M, 64 envs x 512 timesteps: 1024 launches of 12-26 us -> 1 + one per chunk)
   const float* seq_emb = nullptr;
-  if ((L > 1 || plan != nullptr) && T == 3 && D % 4 == 0 && !call.compat_shared) {
+  // (a call from frames has no other front end: its entry has refused what would not get here)
+  if ((L > 1 || plan != nullptr || in.frames != nullptr) && T == 3 && D % 4 == 0 && !call.compat_shared) {
     if (in.emb) {
       seq_emb = in.obs;
     } else if ((size_t)e->B * L * D <= ((size_t)1 << 29)) {   // <= 2 GiB
+      const FrameCount fc = in.frames ? count_frames(e, L, plan ? plan->lengths : nullptr) : FrameCount{0, 0};
+      if (fc.frames > 0) frame_list_buffers(e, in.img_c, in.img_h, in.img_w, fc.frames, "stored context from frames");
       if (e->SEQ_EMB.n < (size_t)e->B * L * D) {
         LRAM_HIP_CHECK(hipDeviceSynchronize());
         e->SEQ_EMB.alloc((size_t)e->B * L * D);
       }
-      GemmArgs ge;
-      ge.a = in.obs, ge.lda = c.state_dim, ge.w = e->w_state, ge.ldw = c.state_dim, ge.c = e->SEQ_EMB.p, ge.ldc = D;
-      ge.bias = e->b_state, ge.m = e->B * L, ge.n = D, ge.k = c.state_dim;
-      gemm(e, ge, s);
+      if (in.obs != nullptr) {   // (from frames: the vector slots of a mixed table; the image slots' rows are overwritten below)
+        GemmArgs ge;
+        ge.a = in.obs, ge.lda = c.state_dim, ge.w = e->w_state, ge.ldw = c.state_dim, ge.c = e->SEQ_EMB.p, ge.ldc = D;
+        ge.bias = e->b_state, ge.m = e->B * L, ge.n = D, ge.k = c.state_dim;
+        gemm(e, ge, s);
+      }
+      // Frames: the third source.  The list of the frames that count is built on the device from the per-env starts and the
+      // slot table's image list; the CNN embeds exactly those into their rows b * L + l -- a padded frame is never read.
+      if (fc.frames > 0) {   // (0: a mixed table whose image slots all have length 0)
+        launch_frame_list(reinterpret_cast<int32_t*>(e->IMG_LIST.p), plan ? plan->dev_start : nullptr,
+                          e->slot_table ? e->slot_img_list : nullptr, fc.n_env, L, s);
+        embed_frame_list(e, in.frames, in.img_h, in.img_w, fc.frames, e->SEQ_EMB.p, s);
+      }
       seq_emb = e->SEQ_EMB.p;
     }
   }
+  LRAM_REQUIRE(in.frames == nullptr || seq_emb != nullptr, "stored context from frames: no state embeddings");
   // chunk lanes (see lram_engine::chunk_lanes): the last chunk -- the one the action head reads -- is on lane 0 = the primary
   // workspace and the caller's stream.  Where they apply they replace the automatic env slices of large batches as well: whole-batch
   // launches, three chunks in flight (16M, 1024 envs x 252 timesteps: 224.4 -> 215.5 ms; 206M, 512 envs x 63: 295.3 -> 274.0 ms).
@@ -613,7 +702,7 @@ struct RaggedCall {
     int32_t* dev_chunk = dev_start + B;
     uint8_t* dev_masks = reinterpret_cast<uint8_t*>(dev_chunk + L);
     uint8_t* dev_hold = dev_masks + (size_t)L * B;
-    plan.dev_start = dev_start, plan.dev_masks = dev_masks, plan.dev_hold = dev_hold;
+    plan.dev_start = dev_start, plan.dev_masks = dev_masks, plan.dev_hold = dev_hold, plan.lengths = lengths;
     std::vector<int32_t> host(B + n_chunks);
     plan.has_reset.assign(n_chunks, 0);
     plan.has_hold.assign(n_chunks, 0);
@@ -649,6 +738,23 @@ struct RaggedCall {
   }
 };
 
+// What the entries from frames refuse beyond the others (lram_prefill_frames / lram_score_frames), before anything is launched or
+// allocated: no image encoder, a frame size that does not fit it, a geometry or mode without the state-embedding front end, state
+// embeddings or flattened maps beyond 2 GiB.  (The entry itself has checked the slot table against dev_obs_seq.)
+void check_frames_call(const lram_engine* e, const char* who, const Inputs& in, const int32_t* lengths) {
+  const std::string w(who);
+  const lram_config& c = e->cfg;
+  LRAM_REQUIRE(in.img_c > 0 && in.img_h > 0 && in.img_w > 0, w + ": channels, height and width must be >= 1");
+  check_frame_size(e, in.img_c, in.img_h, in.img_w, who);
+  LRAM_REQUIRE(c.d_model % 4 == 0, w + ": stored contexts from frames need d_model to be a multiple of 4 (the chunk front end moves float4)");
+  LRAM_REQUIRE(e->compat_repeat <= 1 && !e->compat_stale && !compat_shares(e, 0),
+               w + ": a Mamba reference-trajectory mode is on (lram_set_compat_mode): its calls do not take their state "
+                   "embeddings from one pass ahead of the chunks, which is where the frames are embedded");
+  LRAM_REQUIRE((size_t)e->B * in.L * c.d_model <= ((size_t)1 << 29),
+               w + ": the [batch, timesteps, d_model] state embeddings of the frames exceed 2 GiB");
+  check_frame_list(e, count_frames(e, in.L, lengths).frames, who);
+}
+
 // What the six stored-context entries share, in this order: the refusals (the recurrent state is untouched by a refused call), the
 // launches, the draw count.  `who` names the entry in every message.  rc: the per-env lengths of the ragged and append entries,
 // null for the dense pair.  With a sink (the score entries) the head runs at every timestep and nothing is drawn; without one
@@ -658,9 +764,10 @@ void stored_context_call(lram_engine* e, const char* who, RaggedCall* rc, const 
   const std::string w(who);
   step_entry(e, who);
   require_all_live(e, who);
-  LRAM_REQUIRE(in.obs && in.rtg && in.rew, w + ": null device pointer");
+  LRAM_REQUIRE((in.obs || in.frames) && in.rtg && in.rew, w + ": null device pointer");
   LRAM_REQUIRE(in.L >= 1, w + ": timesteps must be >= 1");
   if (rc != nullptr) rc->check(in.emb);
+  if (in.frames != nullptr) check_frames_call(e, who, in, rc ? rc->lengths : nullptr);
   if (sink != nullptr)
     check_score_sink(e, who, discrete, *sink);
   else if (actions != nullptr)
@@ -680,6 +787,29 @@ void stored_context_call(lram_engine* e, const char* who, RaggedCall* rc, const 
   }
   // (a score is never a draw: the sampling mode and its counter are left alone)
   if (sink == nullptr && actions != nullptr) sample_draw_advance(e, s);
+}
+// The inputs of the entries from frames (lram_prefill_frames / lram_score_frames): the frames are a third source of the state
+// embeddings (timesteps_launches); per-env lengths, where given, make it a ragged or an append call.
+struct FramesCall {
+  Inputs in;
+  std::unique_ptr<RaggedCall> rc;
+};
+FramesCall frames_call(lram_engine* e, const char* who, const uint8_t* dev_frames, int32_t channels, int32_t height, int32_t width,
+                       const float* dev_obs_seq, const float* dev_rtg_seq, const float* dev_reward_seq, int32_t timesteps,
+                       const int32_t* host_lengths, int32_t append) {
+  const std::string w(who);
+  LRAM_REQUIRE(e != nullptr, w + ": null engine");
+  LRAM_REQUIRE(dev_frames != nullptr, w + ": dev_frames is NULL");
+  LRAM_REQUIRE(append == 0 || append == 1, w + ": append must be 0 (replace) or 1 (append)");
+  // the vector slots of a mixed table hand in observations; nobody else's dev_obs_seq is ever read
+  const bool mixed = e->slot_table && e->slot_n_image < e->B;
+  LRAM_REQUIRE(!e->slot_table || e->slot_n_image > 0, w + ": the slot table holds no image slot: there is no frame to take");
+  LRAM_REQUIRE(!mixed || dev_obs_seq != nullptr, w + ": dev_obs_seq is NULL and the slot table holds vector slots");
+  FramesCall fc;
+  fc.in = Inputs{mixed ? dev_obs_seq : nullptr, 0, dev_rtg_seq, dev_reward_seq, timesteps};
+  fc.in.frames = dev_frames, fc.in.img_c = channels, fc.in.img_h = height, fc.in.img_w = width;
+  if (host_lengths != nullptr) fc.rc.reset(new RaggedCall{e, w, timesteps, host_lengths, {}, append != 0});
+  return fc;
 }
 }  // namespace
 
@@ -835,6 +965,34 @@ int32_t lram_score_append(lram_engine* e, const float* dev_obs_seq, int32_t obs_
     const ScoreSink sink{dev_actions, dev_tokens, dev_logp, dev_logits, dev_target_actions, dev_target_tokens, dev_valid, over, temperature};
     stored_context_call(e, rc.w.c_str(), &rc, Inputs{dev_obs_seq, obs_is_embedding, dev_rtg_seq, dev_reward_seq, timesteps},
                         dev_reset_mask, discrete, nullptr, nullptr, &sink, static_cast<hipStream_t>(stream));
+  });
+}
+
+// Stored contexts from uint8 frames: the same body (frames_call above builds its inputs).
+int32_t lram_prefill_frames(lram_engine* e, const uint8_t* dev_frames, int32_t channels, int32_t height, int32_t width,
+                            const float* dev_obs_seq, const float* dev_rtg_seq, const float* dev_reward_seq, int32_t timesteps,
+                            const int32_t* host_lengths, int32_t append, const uint8_t* dev_reset_mask, int32_t discrete,
+                            float* dev_actions, int32_t* dev_tokens, void* stream) {
+  return guarded([&] {
+    FramesCall fc = frames_call(e, "lram_prefill_frames", dev_frames, channels, height, width, dev_obs_seq, dev_rtg_seq,
+                                dev_reward_seq, timesteps, host_lengths, append);
+    stored_context_call(e, "lram_prefill_frames", fc.rc.get(), fc.in, dev_reset_mask, discrete, dev_actions, dev_tokens, nullptr,
+                        static_cast<hipStream_t>(stream));
+  });
+}
+
+int32_t lram_score_frames(lram_engine* e, const uint8_t* dev_frames, int32_t channels, int32_t height, int32_t width,
+                          const float* dev_obs_seq, const float* dev_rtg_seq, const float* dev_reward_seq, int32_t timesteps,
+                          const int32_t* host_lengths, int32_t append, const uint8_t* dev_reset_mask, int32_t discrete,
+                          const float* dev_target_actions, const int32_t* dev_target_tokens, const uint8_t* dev_valid, int32_t over,
+                          double temperature, float* dev_actions, int32_t* dev_tokens, float* dev_logp, float* dev_logits,
+                          void* stream) {
+  return guarded([&] {
+    FramesCall fc = frames_call(e, "lram_score_frames", dev_frames, channels, height, width, dev_obs_seq, dev_rtg_seq,
+                                dev_reward_seq, timesteps, host_lengths, append);
+    const ScoreSink sink{dev_actions, dev_tokens, dev_logp, dev_logits, dev_target_actions, dev_target_tokens, dev_valid, over, temperature};
+    stored_context_call(e, "lram_score_frames", fc.rc.get(), fc.in, dev_reset_mask, discrete, nullptr, nullptr, &sink,
+                        static_cast<hipStream_t>(stream));
   });
 }
 
@@ -1006,6 +1164,31 @@ int32_t lram_embed_images(lram_engine* e, const uint8_t* dev_images, int32_t cha
     LRAM_HIP_CHECK(hipSetDevice(e->device));
     image_buffers(e, channels, height, width, "lram_embed_images");
     embed_images(e, dev_images, channels, height, width, dev_embeddings, static_cast<hipStream_t>(stream));
+  });
+}
+
+int32_t lram_embed_frames(lram_engine* e, const uint8_t* dev_frames, int64_t n_frames, int32_t channels, int32_t height,
+                          int32_t width, float* dev_embeddings, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(e && e->B > 0, "lram_embed_frames: state not allocated (call lram_state_alloc)");
+    LRAM_REQUIRE(dev_frames && dev_embeddings && n_frames >= 1 && channels > 0 && height > 0 && width > 0,
+                 "lram_embed_frames: bad argument");
+    LRAM_HIP_CHECK(hipSetDevice(e->device));
+    check_frame_size(e, channels, height, width, "lram_embed_frames");
+    check_frame_list(e, n_frames, "lram_embed_frames");
+    frame_list_buffers(e, channels, height, width, n_frames, "lram_embed_frames");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // (the identity list: one "env" of n_frames timesteps)
+    launch_frame_list(reinterpret_cast<int32_t*>(e->IMG_LIST.p), nullptr, nullptr, 1, (int)n_frames, s);
+    embed_frame_list(e, dev_frames, height, width, n_frames, dev_embeddings, s);
+  });
+}
+
+int32_t lram_image_counts(lram_engine* e, int64_t* out, int32_t reset) {
+  return guarded([&] {
+    LRAM_REQUIRE(e != nullptr && out != nullptr, "lram_image_counts: null argument");
+    std::copy(e->img_counts, e->img_counts + 3, out);
+    if (reset) std::fill(e->img_counts, e->img_counts + 3, (int64_t)0);
   });
 }
 

@@ -17,8 +17,10 @@
 namespace lram {
 namespace {
 
-// TS x TS output pixels per workgroup, G = 256 / TS^2 channel groups, CPT output channels per thread
-template <int TS, int CPT>
+// TS x TS output pixels per workgroup, G = 256 / TS^2 channel groups, CPT output channels per thread.
+// INDEXED (the first conv of a stored context's frame list): input frame k is a.src[2 * k] of the caller's frame tensor; the
+// output stays compact.  Every other launch takes the instances without it.
+template <int TS, int CPT, bool INDEXED>
 __global__ __launch_bounds__(256) void conv3x3_kernel(Conv3x3Args a) {
   extern __shared__ float tile[];  // [CIN][TS + 2][TS + 3]
   constexpr int TP = TS + 3;       // padded row pitch
@@ -28,6 +30,8 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(Conv3x3Args a) {
   const int tiles_x = (W + TS - 1) / TS;
   const int ty0 = (blockIdx.x / tiles_x) * TS, tx0 = (blockIdx.x % tiles_x) * TS;
   const int b = blockIdx.y;
+  int b_in = b;
+  if constexpr (INDEXED) b_in = a.src[2 * b];
   // ---- stage the input tile with a one-pixel halo ----
   const int halo = (TS + 2) * (TS + 2);
   for (int idx = tid; idx < CIN * halo; idx += 256) {
@@ -36,7 +40,7 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(Conv3x3Args a) {
     const int y = ty0 + yy - 1, x = tx0 + xx - 1;
     float v = 0.f;
     if (y >= 0 && y < H && x >= 0 && x < W) {
-      const int64_t off = (((int64_t)b * CIN + ci) * H + y) * W + x;
+      const int64_t off = (((int64_t)b_in * CIN + ci) * H + y) * W + x;
       v = a.in_u8 ? (float)reinterpret_cast<const uint8_t*>(a.in)[off] / 255.0f
                   : reinterpret_cast<const float*>(a.in)[off];
       if (a.in_relu) v = fmaxf(v, 0.f);
@@ -102,6 +106,54 @@ __global__ __launch_bounds__(256) void relu_kernel(float* x, int64_t n) {
   if (i < n) x[i] = fmaxf(x[i], 0.f);
 }
 
+// The frame list of a stored context: one {src, dst} entry per frame that counts, env by env (blockIdx.y = k, the k-th env that
+// hands in frames: slot slots[k], or k without a slot table), timestep by timestep.  src = k * L + l indexes the caller's frame
+// tensor, dst = b * L + l the rows of the state embeddings.  Env b's context is its first L - start[b] timesteps (start: the
+// call-timestep at which its end-aligned context begins; null: every context has all L), so the entries of the envs ahead of
+// it number the sum of their lengths: every workgroup sums them for itself.
+__global__ __launch_bounds__(256) void frame_list_kernel(int32_t* list, const int32_t* start, const int32_t* slots, int L) {
+  __shared__ int part[256];
+  const int k = blockIdx.y, tid = threadIdx.x;
+  int before = k * L;
+  if (start != nullptr) {   // (uniform over the launch)
+    int sum = 0;
+    for (int j = tid; j < k; j += 256) sum += L - start[slots != nullptr ? slots[j] : j];
+    part[tid] = sum;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (tid < w) part[tid] += part[tid + w];
+      __syncthreads();
+    }
+    before = part[0];
+  }
+  const int b = slots != nullptr ? slots[k] : k;
+  const int n = start != nullptr ? L - start[b] : L;
+  const int l = blockIdx.x * 256 + tid;
+  if (l < n) {
+    list[2 * (before + l)] = k * L + l;
+    list[2 * (before + l) + 1] = b * L + l;
+  }
+}
+
+// act_linear's ReLU over the compact rows of the frame list's Linear, each placed at its row list[2 * i + 1] of `out`; V
+// channels per thread (4: float4 moves)
+template <int V>
+__global__ __launch_bounds__(256) void relu_place_rows_kernel(const float* rows, const int32_t* list, float* out, int64_t N, int D) {
+  const int dv = D / V;
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= N * dv) return;
+  const int64_t i = gid / dv;
+  const int d = (int)(gid - i * dv) * V;
+  const float* src = rows + i * D + d;
+  float* dst = out + (int64_t)list[2 * i + 1] * D + d;
+  if constexpr (V == 4) {
+    const float4 v = *reinterpret_cast<const float4*>(src);
+    *reinterpret_cast<float4*>(dst) = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+  } else {
+    *dst = fmaxf(*src, 0.f);
+  }
+}
+
 }  // namespace
 
 void launch_conv3x3(const Conv3x3Args& a, hipStream_t stream) {
@@ -114,12 +166,34 @@ void launch_conv3x3(const Conv3x3Args& a, hipStream_t stream) {
   dim3 grid(((a.H + TS - 1) / TS) * ((a.W + TS - 1) / TS), a.B), block(256);
   const size_t shmem = sizeof(float) * (size_t)a.CIN * (TS + 2) * (TS + 3);
   LRAM_REQUIRE(shmem <= 64 * 1024, "conv3x3: too many input channels for the LDS tile");
-  if (small)
-    hipLaunchKernelGGL((conv3x3_kernel<8, 8>), grid, block, shmem, stream, a);
+  LRAM_REQUIRE(a.B <= kConvMaxFrames, "conv3x3: too many frames for one launch (the grid's y extent)");
+  if (a.src != nullptr) {
+    LRAM_REQUIRE(a.COUT == 16 && a.in_u8, "conv3x3: a frame list goes with the first conv of stage 1 only");
+    hipLaunchKernelGGL((conv3x3_kernel<16, 16, true>), grid, block, shmem, stream, a);
+  } else if (small)
+    hipLaunchKernelGGL((conv3x3_kernel<8, 8, false>), grid, block, shmem, stream, a);
   else if (a.COUT == 16)
-    hipLaunchKernelGGL((conv3x3_kernel<16, 16>), grid, block, shmem, stream, a);
+    hipLaunchKernelGGL((conv3x3_kernel<16, 16, false>), grid, block, shmem, stream, a);
   else
-    hipLaunchKernelGGL((conv3x3_kernel<16, 32>), grid, block, shmem, stream, a);
+    hipLaunchKernelGGL((conv3x3_kernel<16, 32, false>), grid, block, shmem, stream, a);
+  LRAM_HIP_CHECK(hipGetLastError());
+}
+
+void launch_frame_list(int32_t* list, const int32_t* start, const int32_t* slots, int n_env, int L, hipStream_t stream) {
+  LRAM_REQUIRE(list != nullptr && n_env >= 1 && n_env <= 65535 && L >= 1, "frame list: bad argument");
+  hipLaunchKernelGGL(frame_list_kernel, dim3((unsigned)((L + 255) / 256), (unsigned)n_env), dim3(256), 0, stream, list, start, slots, L);
+  LRAM_HIP_CHECK(hipGetLastError());
+}
+
+void launch_relu_place_rows(const float* rows, const int32_t* list, float* out, int64_t N, int D, hipStream_t stream) {
+  LRAM_REQUIRE(rows && list && out && N >= 1 && D >= 1, "relu + place: bad argument");
+  const bool vec = D % 4 == 0 && ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  const int64_t n = N * (vec ? D / 4 : D);
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  if (vec)
+    hipLaunchKernelGGL((relu_place_rows_kernel<4>), grid, block, 0, stream, rows, list, out, N, D);
+  else
+    hipLaunchKernelGGL((relu_place_rows_kernel<1>), grid, block, 0, stream, rows, list, out, N, D);
   LRAM_HIP_CHECK(hipGetLastError());
 }
 

@@ -117,6 +117,13 @@ _SYMBOLS = {
     "lram_embed_images": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _VP, _VP]),
     "lram_step_images": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _VP, _VP, _VP, ctypes.c_int32,
                          _VP, _VP, _VP]),
+    "lram_embed_frames": (ctypes.c_int32, [_VP, _VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _VP, _VP]),
+    "lram_prefill_frames": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _VP, _VP, _VP, ctypes.c_int32,
+                                             _VP, ctypes.c_int32, _VP, ctypes.c_int32, _VP, _VP, _VP]),
+    "lram_score_frames": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _VP, _VP, _VP, ctypes.c_int32,
+                                           _VP, ctypes.c_int32, _VP, ctypes.c_int32, _VP, _VP, _VP, ctypes.c_int32, ctypes.c_double,
+                                           _VP, _VP, _VP, _VP, _VP]),
+    "lram_image_counts": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]),
     "lram_set_state_mode": (ctypes.c_int32, [_VP, ctypes.c_int32, ctypes.c_int32]),
     "lram_get_state_mode": (ctypes.c_int32, [_VP]),
     "lram_lazy_peek": (ctypes.c_int32, [_VP, ctypes.c_int32, ctypes.c_int32, _VP, _VP]),
@@ -326,6 +333,33 @@ def check_context_lengths(lengths, batch: int, L: int):
     if not any(out):
         raise ValueError("lengths: every length is 0 (no env slot has a context)")
     return out
+
+
+def check_frame_contexts(frames: torch.Tensor, obs_seq: Optional[torch.Tensor], batch: int, n_image: Optional[int],
+                         state_dim: int):
+    """The shape rules of lram_prefill_frames / lram_score_frames, checked on the host (no GPU needed).  `frames`: uint8
+    [n, L, C, H, W] with n = batch without a slot table (n_image None), else the table's n_image image slots (at least one).
+    `obs_seq`: float32 [batch, L, state_dim], required exactly when the table holds vector slots (n_image < batch); otherwise
+    nobody reads it and it is not looked at.  Returns (L, C, H, W); raises ValueError."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 5:
+        got = f"{frames.dtype} {tuple(frames.shape)}" if isinstance(frames, torch.Tensor) else type(frames).__name__
+        raise ValueError(f"frames: expected a uint8 tensor [n, L, C, H, W], got {got}")
+    if n_image is not None and n_image < 1:
+        raise ValueError("frames: the slot table holds no image slot, so there is no frame to take")
+    n = batch if n_image is None else n_image
+    if frames.shape[0] != n:
+        what = "one row per env slot" if n_image is None else "one row per image slot of the slot table, in slot order"
+        raise ValueError(f"frames: expected {n} rows ({what}), got {frames.shape[0]}")
+    L, C, H, W = (int(x) for x in frames.shape[1:])
+    if min(L, C, H, W) < 1:
+        raise ValueError(f"frames: every extent of [n, L, C, H, W] must be >= 1, got {tuple(frames.shape)}")
+    mixed = n_image is not None and n_image < batch
+    if mixed:
+        if obs_seq is None:
+            raise ValueError("obs_seq: the slot table holds vector slots, their observations [batch, L, state_dim] are needed")
+        if obs_seq.dtype != torch.float32 or tuple(obs_seq.shape) != (batch, L, state_dim):
+            raise ValueError(f"obs_seq: expected float32 {(batch, L, state_dim)}, got {obs_seq.dtype} {tuple(obs_seq.shape)}")
+    return L, C, H, W
 
 
 def context_plan(L: int, lengths, cap: int):
@@ -545,6 +579,78 @@ class Engine:
             _check(lib, fn(*head, _i32_array(check_context_lengths(lengths, B, L)), *tail))
         return L, call
 
+    def _frames_context_call(self, kind: str, frames, obs_seq, rtg_seq, reward_seq, reset_mask, lengths, append):
+        """_stored_context_call for frames: checks the inputs (check_frame_contexts) and returns (L, call); call(*tail) runs
+        lram_prefill_frames / lram_score_frames with `tail` (from the head mode on) behind the reset mask."""
+        B = self.batch
+        n_img = int(self._slot_image.sum()) if self._slot_image is not None else None   # (None: no slot table)
+        L, C, H, W = check_frame_contexts(frames, obs_seq, B, n_img, self.spec.state_dim)
+        _chk_dev(frames, torch.uint8, tuple(frames.shape), self.device, "frames")
+        if n_img is None or n_img == B:
+            obs_seq = None   # (every slot takes frames: nobody reads it)
+        if obs_seq is not None:
+            _chk_dev(obs_seq, torch.float32, (B, L, self.spec.state_dim), self.device, "obs_seq")
+        _chk_dev(rtg_seq, torch.float32, (B, L), self.device, "rtg_seq")
+        _chk_dev(reward_seq, torch.float32, (B, L), self.device, "reward_seq")
+        if reset_mask is not None:
+            _chk_dev(reset_mask, torch.uint8, (B,), self.device, "reset_mask")
+        host = None if lengths is None else _i32_array(check_context_lengths(lengths, B, L))
+        fn = self.lib.lram_prefill_frames if kind == "prefill" else self.lib.lram_score_frames
+
+        def call(*tail):
+            _check(self.lib, fn(self._h, _ptr(frames), C, H, W, _ptr(obs_seq), _ptr(rtg_seq), _ptr(reward_seq), L, host,
+                                int(bool(append)), _ptr(reset_mask), *tail, _stream_ptr(self.device)))
+        return L, call
+
+    def prefill_frames(self, frames: torch.Tensor, rtg_seq: torch.Tensor, reward_seq: torch.Tensor,
+                       obs_seq: Optional[torch.Tensor] = None, lengths=None, append=False,
+                       reset_mask: Optional[torch.Tensor] = None, discrete=False, want_action: bool = True):
+        """prefill() from uint8 frames [n, L, C, H, W] (lram_prefill_frames): the IMPALA CNN embeds the frames inside the call,
+        and with `lengths` only the frames [b, l] with l < lengths[b] -- padded frames are never read or convolved.  Without a
+        slot table n = batch; with one, n = its image slots in ascending slot order (as step_slots takes frames) and `obs_seq`
+        float32 [B, L, state_dim] carries the vector slots' observations (rows of image slots are computed and overwritten:
+        anything, NaN included, may stand there).  `lengths`, `append`, `reset_mask`, `discrete`, `want_action` and the
+        result as in prefill().  Bit-identical to prefill(embed_frames(frames), obs_is_embedding=True) for a dense call."""
+        self._need_all_live("prefill_frames")
+        _, call = self._frames_context_call("prefill", frames, obs_seq, rtg_seq, reward_seq, reset_mask, lengths, append)
+        act = self._actions if want_action else None
+        tok = self._tokens if want_action else None
+        call(_head_mode(discrete), _ptr(act), _ptr(tok))
+        return (act, tok) if want_action else (None, None)
+
+    def score_frames(self, frames: torch.Tensor, rtg_seq: torch.Tensor, reward_seq: torch.Tensor, *,
+                     obs_seq: Optional[torch.Tensor] = None, lengths=None, append=False,
+                     actions: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None,
+                     valid: Optional[torch.Tensor] = None, reset_mask: Optional[torch.Tensor] = None, discrete=False,
+                     over: str = "vocab", temperature: float = 1.0, want=("actions", "tokens", "logp"),
+                     logits: bool = False) -> ScoreResult:
+        """score() from uint8 frames (lram_score_frames): `frames` / `obs_seq` as in prefill_frames(), everything else as in
+        score()."""
+        self._need_all_live("score_frames")
+        B, spec = self.batch, self.spec
+        want = (want,) if isinstance(want, str) else tuple(want)
+        for w in want:
+            if w not in ("actions", "tokens", "logp"):
+                raise ValueError(f'want: unknown output {w!r} (choose among "actions", "tokens", "logp")')
+        L, call = self._frames_context_call("score", frames, obs_seq, rtg_seq, reward_seq, reset_mask, lengths, append)
+        if actions is not None:
+            _chk_dev(actions, torch.float32, (B, L, spec.act_dim), self.device, "actions")
+        if tokens is not None:
+            _chk_dev(tokens, torch.int32, (B, L, spec.act_dim), self.device, "tokens")
+        if valid is not None:
+            if valid.dtype == torch.bool:
+                valid = valid.to(torch.uint8)
+            _chk_dev(valid, torch.uint8, (B, L), self.device, "valid")
+        A = spec.act_dim
+        res = ScoreResult(
+            actions=torch.zeros(B, L, A, dtype=torch.float32, device=self.device) if "actions" in want else None,
+            tokens=torch.zeros(B, L, A, dtype=torch.int32, device=self.device) if "tokens" in want else None,
+            logp=torch.zeros(B, L, A, dtype=torch.float32, device=self.device) if "logp" in want else None,
+            logits=torch.zeros(B, L, A, spec.n_vocab, dtype=torch.float32, device=self.device) if logits else None)
+        call(_head_mode(discrete), _ptr(actions), _ptr(tokens), _ptr(valid), _over_mode(over), float(temperature), _ptr(res.actions),
+             _ptr(res.tokens), _ptr(res.logp), _ptr(res.logits))
+        return res
+
     def prefill(self, obs_seq: torch.Tensor, rtg_seq: torch.Tensor, reward_seq: torch.Tensor,
                 reset_mask: Optional[torch.Tensor] = None, discrete=False, obs_is_embedding: bool = False,
                 want_action: bool = True, lengths=None, append: bool = False):
@@ -641,6 +747,29 @@ class Engine:
         _check(self.lib, self.lib.lram_embed_images(self._h, _ptr(images), int(images.shape[1]), int(images.shape[2]),
                                                     int(images.shape[3]), _ptr(out), _stream_ptr(self.device)))
         return out
+
+    def embed_frames(self, frames: torch.Tensor) -> torch.Tensor:
+        """uint8 frames [..., C, H, W], any number of them -> [..., d_model] (lram_embed_frames): embed_images' arithmetic
+        through the tiled frame-list path of prefill_frames; the result does not depend on LRAM_IMG_TILE."""
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() < 4:
+            raise ValueError("frames: expected a uint8 tensor [..., C, H, W]")
+        lead, (C, H, W) = tuple(frames.shape[:-3]), (int(x) for x in frames.shape[-3:])
+        n = 1
+        for x in lead:
+            n *= int(x)
+        if n < 1 or min(C, H, W) < 1:
+            raise ValueError(f"frames: no frame in a tensor of shape {tuple(frames.shape)}")
+        _chk_dev(frames, torch.uint8, tuple(frames.shape), self.device, "frames")
+        out = torch.empty(*lead, self.spec.d_model, dtype=torch.float32, device=self.device)
+        _check(self.lib, self.lib.lram_embed_frames(self._h, _ptr(frames), n, C, H, W, _ptr(out), _stream_ptr(self.device)))
+        return out
+
+    def image_counts(self, reset: bool = False) -> dict:
+        """What the frame-list front end has done since the last reset (lram_image_counts): "frames" convolved, "tiles"
+        launched, "linear" launches.  Padded frames are not among the frames."""
+        buf = (ctypes.c_int64 * 3)()
+        _check(self.lib, self.lib.lram_image_counts(self._h, buf, 1 if reset else 0))
+        return {"frames": int(buf[0]), "tiles": int(buf[1]), "linear": int(buf[2])}
 
     def step_images(self, images: torch.Tensor, rtg: torch.Tensor, reward: torch.Tensor,
                     reset_mask: Optional[torch.Tensor] = None, discrete=False,
