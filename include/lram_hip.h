@@ -236,9 +236,9 @@ int32_t lram_score(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embe
  * d_model] embeddings exceed 2 GiB; the Mamba modes of lram_set_compat_mode (mamba_repeat > 1; stale_state, where a reset
  * re-initialises layer 0 only and the padding would leak into layers >= 1); scratch for the n_b == 0 slots that would leave less
  * than 2 GiB of device memory free.
- * Out of scope: stored contexts on a subset
- * of slots without computing the other rows (kept slots are saved and restored, not skipped; env-STEPS on a live prefix of the
- * slots are lram_set_live's, below, and these entries are refused while slots are parked); the Mamba reference-trajectory
+ * Stored contexts on a subset of slots without computing the other rows: the context-rows modes of the live prefix
+ * (lram_set_context_rows, below; in the default mode kept slots are saved and restored, not skipped, and these entries are
+ * refused while slots are parked).  Out of scope: slot lists that are no prefix; the Mamba reference-trajectory
  * modes (contexts from image frames: lram_prefill_frames, below).  The dense entries, the lazy step path and the GEMM dispatcher are unchanged.  (A shorter
  * context that CONTINUES a slot's state is lram_prefill_append / lram_score_append, below.) */
 int32_t lram_prefill_ragged(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
@@ -274,8 +274,9 @@ int32_t lram_score_ragged(lram_engine* e, const float* dev_obs_seq, int32_t obs_
  * Refused (message in lram_last_error, nothing launched, state untouched): what the ragged entries refuse, except the scratch
  * rule -- a length outside 0 .. timesteps; all lengths 0; tokens_per_step != 3; d_model % 4 != 0; raw observations whose
  * [batch, timesteps, d_model] embeddings exceed 2 GiB; both Mamba modes of lram_set_compat_mode; parked slots (lram_set_live).
- * Out of scope: skipping the held envs' rows in the projections (hold stops state writes and, where it is free, state reads);
- * stored contexts while slots are parked; the Mamba reference-trajectory modes.  (Frames: lram_prefill_frames, below.) */
+ * Skipping the held envs' rows in the projections (hold stops state writes and, where it is free, state reads) and stored
+ * contexts while slots are parked: LRAM_CONTEXT_ROWS_STARTED / _LIVE (lram_set_context_rows, below).  Out of scope: the Mamba
+ * reference-trajectory modes.  (Frames: lram_prefill_frames, below.) */
 int32_t lram_prefill_append(lram_engine* e, const float* dev_obs_seq, int32_t obs_is_embedding, const float* dev_rtg_seq,
                             const float* dev_reward_seq, int32_t timesteps, const int32_t* host_lengths,
                             const uint8_t* dev_reset_mask, int32_t discrete, float* dev_actions, int32_t* dev_tokens, void* stream);
@@ -432,8 +433,37 @@ int32_t lram_state_load_slots(lram_engine* e, const int32_t* host_slots, int32_t
  *     and step carries the parked slots' bookkeeping over to the step's ping-pong side.  A parked slot's record (lram_state_save_slots) stays within the fold's rounding in C
  *     and bit-identical in every other tensor.
  *   - Refused (message in lram_last_error, nothing launched): lram_prefill, lram_score, their ragged and append forms, lram_encoder_step.
+ *     (That is the context-rows mode LRAM_CONTEXT_ROWS_ALL, the default; the other two modes, below, run them on the live prefix.)
  *   - Unchanged, on all `batch` slots: lram_state_export / import, lram_state_copy_slots / save / load / swap, lram_lazy_peek,
  *     lram_reset, lram_set_slot_table, lram_set_sampling_slots.
+ *
+ * Context rows: which slots the stored-context entries (lram_prefill, lram_score, their ragged, append and frames forms) and
+ * lram_encoder_step run on.  lram_set_context_rows is host bookkeeping only: no synchronisation, no allocation; a mode outside
+ * 0 .. 2 is refused and the mode stays.  lram_state_alloc sets the mode back to 0.  lram_get_context_rows: the mode (0: no engine).
+ *   LRAM_CONTEXT_ROWS_ALL (0)  every allocated slot, refused while slots are parked: launch for launch and bit for bit what the
+ *     entries did before the modes existed.
+ *   LRAM_CONTEXT_ROWS_LIVE (1)  the live prefix [0, n_live).  The entries read and write rows < n_live only: inputs, host_lengths,
+ *     the reset mask and every output have n_live rows; the frames entries take the frames of the image slots below n_live, in
+ *     ascending slot order, as lram_step_slots does.  Kernel, slice, chunk-lane and score-scratch rules are judged on the live
+ *     rows; the state keeps its allocation and strides; every other refusal of the entries stands (the 2 GiB bound on the state
+ *     embeddings is on n_live x timesteps x d_model).  A parked slot's record (lram_state_save_slots) is bit-identical afterwards
+ *     in materialised mode; in lazy mode the call folds every slot's pending window first, parked slots included, so a parked
+ *     record is bit-identical in every tensor but C, and C stays within the fold's rounding if the slot had a pending window.  With
+ *     n_live == batch the launches are mode 0's: bit-identical.  Sampling: one draw per action-producing call, as ever.
+ *   LRAM_CONTEXT_ROWS_STARTED (2)  mode 1, and for the entries that take host_lengths (ragged, append, frames with lengths) a row
+ *     rule: the lengths must be non-increasing in slot order over the live prefix -- otherwise the call is refused with nothing
+ *     launched, the message naming the first slot that breaks the order -- and the chunk that starts at call-timestep t runs rows
+ *     [0, r) only, r the number of envs with s_b = timesteps - n_b <= t.  The plan is lram_context_plan's.  No env is ever held,
+ *     so every chunk launches the plain kernel instances; no row is computed on zero tokens; a slot of length 0 is never a row,
+ *     so nothing is saved to or loaded from scratch and the "less than 2 GiB free" refusal cannot arise.  Resets: a replace call
+ *     restarts an env with 0 < n_b < timesteps at its own start, otherwise the caller's mask decides; a mask is used only in the
+ *     chunk where the env starts.  Score rows beyond an env's length and the action rows of length-0 slots hold the fill values of
+ *     the ragged entries.  Per env, state and outputs equal mode 1's up to fp32 rounding (the projection kernels are chosen by
+ *     row count); length-0 and parked slots are bit-identical; with every n_b == timesteps the launches are the dense entry's.
+ *     The dense entries and lram_encoder_step behave as in mode 1.
+ * lram_context_counts: a measurement aid in the style of lram_image_counts.  out4 receives what happened since the engine was
+ *   created or since the last call with reset != 0: stored-context calls, chunks run, env-timesteps computed (the sum over chunks
+ *   of rows x timesteps), slot records saved to scratch by the replace entries.  lram_encoder_step is not counted.
  *
  * lram_state_swap_slots: exchanges the recurrent state of slots host_a[i] and host_b[i], live or parked, in ONE launch; folds
  *   nothing and touches no other slot.  Lists as lram_state_copy_slots' (HOST int32); all 2n indices distinct and in range, else
@@ -444,6 +474,12 @@ int32_t lram_state_load_slots(lram_engine* e, const int32_t* host_slots, int32_t
 int32_t lram_set_live(lram_engine* e, int32_t n_live, void* stream);
 int32_t lram_get_live(const lram_engine* e);
 int32_t lram_state_swap_slots(lram_engine* e, const int32_t* host_a, const int32_t* host_b, int32_t n, void* stream);
+#define LRAM_CONTEXT_ROWS_ALL     0   /* default: every allocated slot; refused while slots are parked */
+#define LRAM_CONTEXT_ROWS_LIVE    1   /* the live prefix [0, n_live) */
+#define LRAM_CONTEXT_ROWS_STARTED 2   /* the live prefix, and in every chunk only the envs that have started */
+int32_t lram_set_context_rows(lram_engine* e, int32_t mode);
+int32_t lram_get_context_rows(const lram_engine* e);
+int32_t lram_context_counts(lram_engine* e, int64_t* out4, int32_t reset);
 
 /* Micro-batch pipeline (xLSTM): the env slots are processed as `n` slices on engine-owned HIP streams; the
  * HBM-bound matrix-memory kernels of all slices run back to back on one stream while the other slices'

@@ -21,6 +21,8 @@ point); `predict_batch` is the native entry: one call advances all B envs by one
 """
 from __future__ import annotations
 
+import contextlib
+import copy
 from types import SimpleNamespace
 from typing import Dict, Optional
 
@@ -374,10 +376,82 @@ class RecurrentAgent:
             return None
         return torch.as_tensor(sch.live_envs(), dtype=torch.long, device=self.device)
 
-    def _scatter_rows(self, rows: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
-        out = torch.zeros(self.n_envs, *rows.shape[1:], dtype=rows.dtype, device=rows.device)
+    def _scatter_rows(self, rows: torch.Tensor, idx: torch.Tensor, fill=0) -> torch.Tensor:
+        out = torch.full((self.n_envs, *rows.shape[1:]), fill, dtype=rows.dtype, device=rows.device)
         out[idx] = rows
         return out
+
+    @contextlib.contextmanager
+    def _context_envs(self, envs, lengths):
+        """The stored-context calls on a subset of the envs (prime_contexts / extend_contexts / score_trajectories, `envs=`):
+        brings the listed envs -- None: the active ones -- into a prefix of the engine's slots, makes that prefix the live one and
+        the engine's context rows "started" or "live", and yields the env id of every row of the call in slot order (a device
+        index); afterwards the slots, the live count and mode "all" are as before, so an env that was parked is parked again.
+        With `lengths` the envs are sorted by descending length, which is what mode "started" asks for; where that would
+        exchange two slots whose slot-table entry or per-slot sampling setting differs (_slots_alike) they keep the given order
+        and the mode is "live".  Yields None, with nothing done, on today's path: envs=None, every env active in its own slot."""
+        sch = self.scheduler
+        if envs is None and sch.n_live == sch.n and sch.identity:
+            yield None
+            return
+        part = sch.live_envs() if envs is None else [int(e) for e in envs]
+        if not part or len(set(part)) != len(part) or any(not 0 <= e < self.n_envs for e in part):
+            raise ValueError(f"envs: expected distinct env ids in 0 .. {self.n_envs - 1}, at least one")
+
+        def plan(order):
+            trial = copy.deepcopy(sch)
+            lists = trial.arrange(order)
+            for a, b in lists:
+                for sa, sb in zip(a, b):
+                    diff = self._slots_alike(sa, sb)
+                    if diff is not None:
+                        return None, (sa, sb, diff)
+            return trial, lists
+
+        trial, mode = None, "live"
+        if lengths is not None:
+            trial, lists = plan(sorted(part, key=lambda e: -int(lengths[e])))   # (stable: equal lengths keep their order)
+            mode = "started" if trial is not None else "live"
+        if trial is None:
+            trial, lists = plan(part)
+            if trial is None:
+                sa, sb, diff = lists
+                raise ValueError(f"envs: would exchange engine slots {sa} and {sb}, whose {diff} differs -- those stay with the "
+                                 f"slot index (list envs of one domain and setting)")
+        for a, b in lists:
+            self.engine.swap_slots(a, b)
+        trial.n_live = len(part)
+        self.engine.set_live(len(part))
+        self.engine.set_context_rows(mode)
+        self.scheduler = trial
+        try:
+            yield torch.as_tensor(trial.live_envs(), dtype=torch.long, device=self.device)
+        finally:
+            self.engine.set_context_rows("all")
+            for a, b in reversed(lists):   # (every list is an involution: the same lists in reverse order undo the arrangement)
+                self.engine.swap_slots(a, b)
+            self.engine.set_live(sch.n_live)
+            self.scheduler = sch
+
+    def _gather_contexts(self, idx, obs, frames, rtg, rew, lengths):
+        """The rows of the prepared contexts (_prepare_contexts) that a call on the envs `idx` (slot order) hands the engine.
+        With a slot table the frames are one row per image ENV in env-id order; the call takes those of the listed image envs."""
+        take = (lambda t: None if t is None else t[idx].contiguous())
+        envs = idx.tolist()
+        table = getattr(self, "slot_table", None)
+        if frames is not None and table is not None:
+            rank, k = {}, 0
+            for e in range(self.n_envs):
+                if table.image[e]:
+                    rank[e] = k
+                    k += 1
+            rows = [rank[e] for e in envs if e in rank]
+            frames = frames[torch.as_tensor(rows, dtype=torch.long, device=frames.device)].contiguous() if rows else None
+            if len(rows) == len(envs):
+                obs = None   # (every listed env is an image env)
+        elif frames is not None:
+            frames = take(frames)
+        return take(obs), frames, take(rtg), take(rew), None if lengths is None else [lengths[e] for e in envs]
 
     # ---- multiprocess evaluation (src/callbacks/custom_eval_callback.py:22-33, decision_xlstm.py:243-267) ----
     def make_pickleable(self, replace_cell: bool = False):
@@ -561,7 +635,7 @@ class RecurrentAgent:
                            rewards: Optional[torch.Tensor] = None, actions: Optional[torch.Tensor] = None,
                            lengths: Optional[torch.Tensor] = None, reset: bool = True, over: str = "vocab",
                            temperature: float = 1.0, want=("actions", "tokens", "logp"), logits: bool = False,
-                           window: Optional[int] = None):
+                           window: Optional[int] = None, envs=None):
         """Grade stored trajectories (Engine.score): observations [B, L, obs_dim] -- padded and normalised with state_mean /
         state_std as predict_batch does -- returns_to_go [B, L] in model units, rewards [B, L] (None: the reference loop's
         zero reward token), recorded `actions` [B, L, n] (float; n <= act_dim, padded with zeros; a discrete agent's action
@@ -578,7 +652,9 @@ class RecurrentAgent:
         `reset` is honoured on call 0 only.  The result is one ScoreResult of the full [B, L, ...] shape and the state afterwards
         that of each env's own timesteps, as for the single call (up to fp32 rounding: the chunks differ); the engine embeds
         B x W raw observations per call instead of B x L, which lifts the single call's 2 GiB bound.  Appended contexts never
-        replace a state, so reset=False with shorter lengths is accepted here.  window=None (or W >= L): the single call."""
+        replace a state, so reset=False with shorter lengths is accepted here.  window=None (or W >= L): the single call.
+        `envs` as in extend_contexts: the envs that are scored (None: the active ones); the others' rows of the result hold
+        the fill values of masked rows (0 / token -1) and their state is left alone."""
         obs, frames, rtg, rew, lengths, discrete = self._prepare_contexts(observations, returns_to_go, rewards, lengths)
         B, L = rtg.shape
         target = None
@@ -594,9 +670,24 @@ class RecurrentAgent:
         if lengths is not None and not windowed and not reset and any(0 < n < L for n in lengths):
             raise ValueError("score_trajectories: a context shorter than L replaces the env's state; reset=False cannot "
                              "be combined with a length in 1 .. L - 1")
-        mask = torch.ones(B, dtype=torch.uint8, device=self.device) if reset else None
         want = tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "logp" or target is not None)
-        if not windowed:
+        with self._context_envs(envs, lengths) as idx:
+            if idx is not None:   # the rows of the listed envs, in slot order; the others' rows of the result hold the fill values
+                obs, frames, rtg, rew, lengths = self._gather_contexts(idx, obs, frames, rtg, rew, lengths)
+                target = None if target is None else target[idx].contiguous()
+            res = self._score_rows(obs, frames, rtg, rew, target, lengths, discrete, reset, over, temperature, want, logits,
+                                   window if windowed else None)
+            if idx is not None:
+                fills = {"actions": 0, "tokens": -1, "logp": 0, "logits": 0}
+                res = ScoreResult(**{name: None if getattr(res, name) is None else self._scatter_rows(getattr(res, name), idx, fills[name])
+                                     for name in ScoreResult.__slots__})
+        return res
+
+    def _score_rows(self, obs, frames, rtg, rew, target, lengths, discrete, reset, over, temperature, want, logits, window):
+        """score_trajectories on the rows it hands the engine: one call, or `window` timesteps per call."""
+        B, L = rtg.shape
+        mask = torch.ones(B, dtype=torch.uint8, device=self.device) if reset else None
+        if window is None:
             return self._engine_score(obs, frames, rtg, rew, actions=target, reset_mask=mask, discrete=discrete, over=over,
                                       temperature=temperature, want=want, logits=logits, lengths=lengths)
         W = int(window)
@@ -621,14 +712,18 @@ class RecurrentAgent:
 
     @torch.no_grad()
     def extend_contexts(self, observations: torch.Tensor, returns_to_go: torch.Tensor,
-                        rewards: Optional[torch.Tensor] = None, lengths=None, restart=None, want_action: bool = False):
+                        rewards: Optional[torch.Tensor] = None, lengths=None, restart=None, want_action: bool = False,
+                        envs=None):
         """Append to every env's state a stored context of its own length in one call (Engine.prefill(lengths=..., append=True)),
         after which predict_batch continues: the steps envs at different points of their episodes missed, or a demonstration
         that continues an in-context evaluation (persist_context).  observations [B, L, obs_dim] -- native, padded and normalised
         as prime_contexts does, image observations included -- returns_to_go [B, L], rewards [B, L] (None: zeros), `lengths` [B]: env b takes its first
         lengths[b] timesteps (None = all L); an env of length 0 keeps its state bit for bit.  `restart` [B] bool (None: nobody):
         the envs that start from an empty state before their first timestep.  want_action=True returns the action at each env's
-        own last timestep (as predict_batch returns it; 0 for an env of length 0), else None."""
+        own last timestep (as predict_batch returns it; 0 for an env of length 0), else None.
+        `envs`: the env ids that take part (None: the active envs); every tensor stays full-width in env-id order, as in
+        predict_batch.  The others -- parked or not -- are not rows of the call: their state is left alone and their rows of the
+        result hold 0.  A listed env that was parked is parked again afterwards, its context extended (_context_envs)."""
         B = self.n_envs
         obs, frames, rtg, rew, lengths, discrete = self._prepare_contexts(observations, returns_to_go, rewards, lengths)
         mask = None
@@ -637,26 +732,36 @@ class RecurrentAgent:
             if mask.shape[0] != B:
                 raise ValueError(f"restart: expected {B} entries (one per env), got {mask.shape[0]}")
             mask = (mask != 0).to(self.device, torch.uint8).contiguous()
-        actions, _ = self._engine_prefill(obs, frames, rtg, rew, reset_mask=mask, discrete=discrete, want_action=want_action,
-                                          lengths=lengths, append=True)
+        with self._context_envs(envs, lengths) as idx:
+            if idx is not None:
+                obs, frames, rtg, rew, lengths = self._gather_contexts(idx, obs, frames, rtg, rew, lengths)
+                mask = None if mask is None else mask[idx].contiguous()
+            actions, _ = self._engine_prefill(obs, frames, rtg, rew, reset_mask=mask, discrete=discrete, want_action=want_action,
+                                              lengths=lengths, append=True)
+            if want_action and idx is not None:
+                actions = self._scatter_rows(actions, idx)
         if not want_action:
             return None
         return actions[:, :1].to(torch.int64) if self.is_discrete else actions
 
     @torch.no_grad()
     def prime_contexts(self, observations: torch.Tensor, returns_to_go: torch.Tensor,
-                       rewards: Optional[torch.Tensor] = None, lengths=None, want_action: bool = False):
+                       rewards: Optional[torch.Tensor] = None, lengths=None, want_action: bool = False, envs=None):
         """Prime every env with its own stored context in one call (Engine.prefill(lengths=...)), after which predict_batch
         continues: observations [B, L, obs_dim] -- padded and normalised as predict_batch does -- returns_to_go [B, L], rewards
         [B, L] (None: zeros) and `lengths` [B]: env b's context is its first lengths[b] timesteps (None = all L).  Every env
         with a context starts from an empty state; an env of length 0 keeps the state it has.  want_action=True returns the
         action at each env's own last timestep (as predict_batch returns it), else None.  Image observations as in
-        score_trajectories."""
-        B = self.n_envs
+        score_trajectories.  `envs` as in extend_contexts: the envs that are primed (None: the active ones)."""
         obs, frames, rtg, rew, lengths, discrete = self._prepare_contexts(observations, returns_to_go, rewards, lengths)
-        mask = torch.ones(B, dtype=torch.uint8, device=self.device)
-        actions, _ = self._engine_prefill(obs, frames, rtg, rew, reset_mask=mask, discrete=discrete, want_action=want_action,
-                                          lengths=lengths)
+        with self._context_envs(envs, lengths) as idx:
+            if idx is not None:
+                obs, frames, rtg, rew, lengths = self._gather_contexts(idx, obs, frames, rtg, rew, lengths)
+            mask = torch.ones(rtg.shape[0], dtype=torch.uint8, device=self.device)
+            actions, _ = self._engine_prefill(obs, frames, rtg, rew, reset_mask=mask, discrete=discrete, want_action=want_action,
+                                              lengths=lengths)
+            if want_action and idx is not None:
+                actions = self._scatter_rows(actions, idx)
         if not want_action:
             return None
         return actions[:, :1].to(torch.int64) if self.is_discrete else actions

@@ -244,6 +244,12 @@ struct lram_engine {
   // recurrent state and no activation row of them is computed (lazy mode: their bookkeeping is carried over, run_xlstm_stack).  B stays what every state tensor is allocated and strided for; n_live is what a
   // stepping call's rows, slices and size rules are judged on.  state_alloc sets n_live = B.
   int n_live = 0;
+  // Which slots a stored-context or encoder call runs on (lram_set_context_rows): 0 every allocated slot (refused while slots are
+  // parked), 1 the live prefix, 2 the live prefix and in every chunk only the envs that have started.  state_alloc sets 0.
+  int ctx_rows = 0;
+  // The rows such a call's inputs, outputs and size rules are judged on.  (Mode 0 with parked slots never gets to use it: refused.)
+  int context_rows() const { return ctx_rows == 0 ? B : n_live; }
+  int64_t ctx_counts[4] = {0, 0, 0, 0};   // stored-context calls, chunks, env-timesteps, records saved to KEEP (lram_context_counts)
   // Lazy matrix memory: the lazy_step at which a parked slot may last have come by pending window tokens -- the live count
   // changed, or a swap / copy moved a window.  A parked slot takes no token, so once every fold class has come due since then
   // (lazy_period steps) all parked windows are empty, and the steps launch no fold over the parked range until this moves again.
@@ -444,6 +450,7 @@ struct Pass {
   const uint8_t* images = nullptr;   // lram_step_images / lram_step_slots: the call's frames
   int img_c = 0, img_h = 0, img_w = 0;
   bool slots = false;                // mixed front end (lram_step_slots)
+  bool context = false;              // a stored-context entry's call: its chunks and rows are counted (lram_context_counts)
   // repeated forwards of the Mamba reference-trajectory mode: the forward under way, how many there are, and whether they
   // share the token front end and layer 0's in_proj (compat_shares())
   int compat_pass = 0, compat_passes = 1;

@@ -584,6 +584,7 @@ void state_alloc(lram_engine* e, int B) {
   }
   e->B = B;
   e->n_live = B;
+  e->ctx_rows = LRAM_CONTEXT_ROWS_ALL;
   alloc_workspace(e, kMaxTokens);
   e->lazy = lazy_choice(e);
   if (e->lazy) lazy_alloc(e);

@@ -184,20 +184,22 @@ struct ContextPlan {
   std::vector<int> starts;        // ascending call-timesteps at which the chunks start; the last chunk ends at L
   // per chunk: some env is reset at its start / held in it (a chunk without one passes no pointer at all, as a dense call does)
   std::vector<char> has_reset, has_hold;
+  // per chunk, LRAM_CONTEXT_ROWS_STARTED only (empty otherwise: every chunk runs all the call's rows): the chunk runs rows [0, rows[c])
+  std::vector<int> rows;
   const int32_t* lengths = nullptr;                        // the caller's host array [B]
   const int32_t* dev_start = nullptr;                      // [B]
   const uint8_t *dev_masks = nullptr, *dev_hold = nullptr;   // [n_chunks, B] each
 };
 
 // The frames of a stored-context call that count, and the envs that hand frames in: the image slots of a slot table (every env
-// without one), each with its own length (null: all L).
+// without one) among the call's rows (lram_engine::context_rows), each with its own length (null: all L).
 struct FrameCount {
   int n_env;
   int64_t frames;
 };
 FrameCount count_frames(const lram_engine* e, int L, const int32_t* lengths) {
   FrameCount n{0, 0};
-  for (int b = 0; b < e->B; ++b)
+  for (int b = 0; b < e->context_rows(); ++b)
     if (!e->slot_table || (e->slot_flags[b] & LRAM_SLOT_IMAGE)) n.n_env += 1, n.frames += lengths ? lengths[b] : L;
   return n;
 }
@@ -370,10 +372,12 @@ void action_head(lram_engine* e, const Pass& pass, const std::vector<Slice>& sl,
 // a sink makes for it (action_head) -- row [b, L - 1] of the sink is what lram_prefill computes, and LOGITS is left as it leaves it.
 // With a plan (per-env lengths) the chunks are the plan's instead of the fixed stride, chunk c takes row c of the plan's reset
 // masks instead of `reset` on the first chunk, and the front end and the sink place every env's rows by its own start.
+// The rows of a stored context are R = lram_engine::context_rows() -- the batch, or the live prefix (lram_set_context_rows); an
+// env-step's are the slices' (make_slices: the live prefix).  A plan with per-chunk rows clips every chunk's slices to them.
 void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, const uint8_t* reset, int discrete, float* actions,
                         int32_t* tokens, hipStream_t s, const ScoreSink* sink = nullptr, const ContextPlan* plan = nullptr) {
   const lram_config& c = e->cfg;
-  const int D = c.d_model, T = c.tokens_per_step, L = in.L;
+  const int D = c.d_model, T = c.tokens_per_step, L = in.L, R = e->context_rows();
   e->sync_used = 0, e->edge_used = 0;
   // Stored context is consumed in chunks: every block then reads and writes its recurrent state once per chunk
   // instead of once per timestep.  Up to 4 timesteps (12 tokens) per chunk through the token-sequential kernels,
@@ -387,17 +391,17 @@ void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, cons
   if ((L > 1 || plan != nullptr || in.frames != nullptr) && T == 3 && D % 4 == 0 && !call.compat_shared) {
     if (in.emb) {
       seq_emb = in.obs;
-    } else if ((size_t)e->B * L * D <= ((size_t)1 << 29)) {   // <= 2 GiB
+    } else if ((size_t)R * L * D <= ((size_t)1 << 29)) {   // <= 2 GiB
       const FrameCount fc = in.frames ? count_frames(e, L, plan ? plan->lengths : nullptr) : FrameCount{0, 0};
       if (fc.frames > 0) frame_list_buffers(e, in.img_c, in.img_h, in.img_w, fc.frames, "stored context from frames");
-      if (e->SEQ_EMB.n < (size_t)e->B * L * D) {
+      if (e->SEQ_EMB.n < (size_t)R * L * D) {
         LRAM_HIP_CHECK(hipDeviceSynchronize());
-        e->SEQ_EMB.alloc((size_t)e->B * L * D);
+        e->SEQ_EMB.alloc((size_t)R * L * D);
       }
       if (in.obs != nullptr) {   // (from frames: the vector slots of a mixed table; the image slots' rows are overwritten below)
         GemmArgs ge;
         ge.a = in.obs, ge.lda = c.state_dim, ge.w = e->w_state, ge.ldw = c.state_dim, ge.c = e->SEQ_EMB.p, ge.ldc = D;
-        ge.bias = e->b_state, ge.m = e->B * L, ge.n = D, ge.k = c.state_dim;
+        ge.bias = e->b_state, ge.m = R * L, ge.n = D, ge.k = c.state_dim;
         gemm(e, ge, s);
       }
       // Frames: the third source.  The list of the frames that count is built on the device from the per-env starts and the
@@ -426,11 +430,11 @@ void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, cons
   // of 4 timesteps: the lanes apply to them as they are)
   const bool lanes = e->n_micro <= 1 && n_chunks >= 2 && e->chunk_lanes && !e->graph_mode && !call.compat_shared && twin_ready(e);
   hipStream_t hbm = s;
-  const std::vector<Slice> sl = lanes ? std::vector<Slice>{Slice{0, e->B, s}} : make_slices(e, s, &hbm);
+  const std::vector<Slice> sl = lanes ? std::vector<Slice>{Slice{0, R, s}} : make_slices(e, s, &hbm);
   const bool multi = sl.size() > 1;
   const int NL = lanes ? e->n_lanes : 1;
   // scratch of the per-timestep head: one region per lane / slice (a one-timestep call has its only timestep scored by action_head)
-  const int64_t score_cap = std::max<int64_t>(lram_engine::kScoreMinRows, std::min<int64_t>(e->score_rows, (int64_t)e->B * kChunk));
+  const int64_t score_cap = std::max<int64_t>(lram_engine::kScoreMinRows, std::min<int64_t>(e->score_rows, (int64_t)R * kChunk));
   const size_t score_region = (size_t)score_cap * c.act_dim * c.n_vocab;
   if (sink != nullptr && L > 1) {
     const size_t want = score_region * (lanes ? (size_t)NL : sl.size());
@@ -452,14 +456,29 @@ void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, cons
       while ((int)v.size() < c.n_blocks) v.push_back(new_event(e, false));
     for (int k = 1; k < NL; ++k) stream_after(e, lane_s[k], s, true);
   }
+  // The slices of a chunk that runs rows [0, rows) only: every slice keeps its stream and its first row -- an env never changes
+  // streams between chunks -- and loses the rows beyond; `idx` keeps its number among the call's slices (its score scratch).
+  std::vector<Slice> use;
+  std::vector<size_t> use_idx;
+  auto clip_slices = [&](int rows) {
+    use.clear(), use_idx.clear();
+    for (size_t i = 0; i < sl.size(); ++i)
+      if (sl[i].b0 < rows) use.push_back(Slice{sl[i].b0, std::min(sl[i].nb, rows - sl[i].b0), sl[i].s}), use_idx.push_back(i);
+  };
+  const bool started = plan != nullptr && !plan->rows.empty();
   int Tc = T, last_steps = 1;
   for (int ci = 0; ci < n_chunks; ++ci) {
     const int l = chunk_at[ci], Lc = chunk_at[ci + 1] - l;
     Tc = T * Lc;
     last_steps = Lc;
     const int lane = (n_chunks - 1 - ci) % NL;
-    const std::vector<Slice> lane_sl = {Slice{0, e->B, lane_s[lane]}};
-    const std::vector<Slice>& use = lanes ? lane_sl : sl;
+    if (lanes)
+      use.assign(1, Slice{0, started ? plan->rows[ci] : R, lane_s[lane]}), use_idx.assign(1, (size_t)lane);
+    else if (started)
+      clip_slices(plan->rows[ci]);
+    else if (ci == 0)
+      clip_slices(sl.back().b0 + sl.back().nb);
+    if (call.context) e->ctx_counts[1] += 1, e->ctx_counts[2] += (int64_t)(use.back().b0 + use.back().nb) * Lc;
     // (scope guard: an exception out of a launch below must not leave the engine on a lane's workspace)
     struct LaneScope {
       lram_engine* e;
@@ -483,20 +502,21 @@ void timesteps_launches(lram_engine* e, const Pass& call, const Inputs& in, cons
     Pass pass = call;
     if (lanes) pass.lane_wait = ci > 0 ? &e->lane_ev[(lane + 1) % NL] : nullptr, pass.lane_rec = &e->lane_ev[lane];
     const uint8_t* chunk_reset = l == 0 ? reset : nullptr;
-    if (plan != nullptr) chunk_reset = plan->has_reset[ci] ? plan->dev_masks + (size_t)ci * e->B : nullptr;
+    if (plan != nullptr) chunk_reset = plan->has_reset[ci] ? plan->dev_masks + (size_t)ci * R : nullptr;
     // (a chunk without a held env passes no hold pointer: it launches what a dense call launches)
-    if (plan != nullptr && plan->has_hold[ci]) pass.hold = plan->dev_hold + (size_t)ci * e->B;
+    if (plan != nullptr && plan->has_hold[ci]) pass.hold = plan->dev_hold + (size_t)ci * R;
     run_stack(e, pass, Tc, chunk_reset, use, lanes ? lane_s[lane] : hbm);
     if (sink != nullptr && L > 1)
       for (size_t i = 0; i < use.size(); ++i)
-        score_chunk(e, *sink, use[i], e->SCORE_LG.p + (lanes ? (size_t)lane : i) * score_region, score_cap, l, Lc, L, discrete,
-                    ctx_start);
+        score_chunk(e, *sink, use[i], e->SCORE_LG.p + use_idx[i] * score_region, score_cap, l, Lc, L, discrete, ctx_start);
   }
   for (int k = 1; k < NL; ++k) stream_after(e, s, lane_s[k], true);
+  // the head on the rows of the last chunk (with per-chunk rows: the envs with a context; the others' rows take the fill values)
+  if (started || lanes) clip_slices(started ? plan->rows.back() : R);
   if (sink != nullptr)
-    action_head(e, call, sl, Tc, last_steps, discrete, nullptr, nullptr, sink, L, ctx_start);
+    action_head(e, call, use, Tc, last_steps, discrete, nullptr, nullptr, sink, L, ctx_start);
   else if (actions != nullptr)
-    action_head(e, call, sl, Tc, last_steps, discrete, actions, tokens);
+    action_head(e, call, use, Tc, last_steps, discrete, actions, tokens);
   if (multi && call.compat_pass == call.compat_passes - 1) join_slices(e, sl, hbm, s);
 }
 
@@ -567,8 +587,10 @@ void step_launches(lram_engine* e, Pass pass, const Inputs& in, const uint8_t* r
   sample_draw_advance(e, s);
 }
 
-// Stored contexts and encoder calls run on every allocated slot: refused, with nothing launched, while slots are parked.
+// Stored contexts and encoder calls run on every allocated slot unless lram_set_context_rows says otherwise: refused, with nothing
+// launched, while slots are parked.
 void require_all_live(const lram_engine* e, const char* who) {
+  if (e->ctx_rows != LRAM_CONTEXT_ROWS_ALL) return;   // (the live prefix is what the call runs on)
   LRAM_REQUIRE(e->n_live == e->B, std::string(who) + ": " + std::to_string(e->B - e->n_live) + " of " + std::to_string(e->B) +
                                       " env slots are parked (lram_set_live): stored contexts and encoder calls need every slot "
                                       "live -- call lram_set_live(batch) first");
@@ -657,27 +679,38 @@ struct RaggedCall {
 
   void check(int obs_is_embedding) const {
     const lram_config& c = e->cfg;
+    const int B = e->context_rows();
     LRAM_REQUIRE(lengths != nullptr, w + ": host_lengths is NULL");
-    check_lengths(lengths, e->B, L, w);
+    check_lengths(lengths, B, L, w);
+    // (started rows are a prefix of the slots in every chunk: an env never starts after one that sits behind it)
+    for (int b = 1; b < B && started(); ++b)
+      LRAM_REQUIRE(lengths[b] <= lengths[b - 1],
+                   w + ": LRAM_CONTEXT_ROWS_STARTED needs lengths that do not increase in slot order over the live prefix; length " +
+                       std::to_string(lengths[b]) + " of env slot " + std::to_string(b) + " exceeds length " +
+                       std::to_string(lengths[b - 1]) + " of env slot " + std::to_string(b - 1));
     LRAM_REQUIRE(c.d_model % 4 == 0, w + ": per-env lengths need d_model to be a multiple of 4 (the chunk front end moves float4)");
     LRAM_REQUIRE(e->compat_repeat <= 1, w + ": the Mamba repeated-forward mode is on (lram_set_compat_mode, mamba_repeat > 1): its "
                                             "trajectories advance the state once per action dim and take no per-env lengths");
     LRAM_REQUIRE(!e->compat_stale, w + ": the Mamba stale_state mode is on (lram_set_compat_mode): a reset re-initialises layer 0 "
                                        "only, so the padding ahead of a shorter context would leak into the other layers");
-    LRAM_REQUIRE(obs_is_embedding || (size_t)e->B * L * c.d_model <= ((size_t)1 << 29),
+    LRAM_REQUIRE(obs_is_embedding || (size_t)B * L * c.d_model <= ((size_t)1 << 29),
                  w + ": the [batch, timesteps, d_model] state embeddings of the raw observations exceed 2 GiB");
   }
+  bool started() const { return e->ctx_rows == LRAM_CONTEXT_ROWS_STARTED; }
   bool dense() const {
-    for (int b = 0; b < e->B; ++b)
+    for (int b = 0; b < e->context_rows(); ++b)
       if (lengths[b] != L) return false;
     return true;
   }
 
+  // B below: the rows of the call (lram_engine::context_rows) -- every table is that wide.  LRAM_CONTEXT_ROWS_STARTED: a chunk runs
+  // the envs that have started by it and nobody else, so no env is held, none is fed zero tokens, and a slot of length 0 is never
+  // a row: nothing to keep.
   template <typename Launch>
   void run(const uint8_t* reset, hipStream_t s, Launch&& launch) {
-    const int B = e->B;
+    const int B = e->context_rows();
     std::vector<int32_t> kept;   // replace: the slots of length 0
-    for (int b = 0; b < B && !append; ++b)
+    for (int b = 0; b < B && !append && !started(); ++b)
       if (lengths[b] == 0) kept.push_back(b);
     // scratch for the kept slots' records: refused, with nothing launched, when it would leave less than 2 GiB free
     const size_t need = kept.size() * (size_t)(lram_state_bytes_per_env(e) / 4);
@@ -713,11 +746,19 @@ struct RaggedCall {
       const size_t at = sb < L ? std::lower_bound(plan.starts.begin(), plan.starts.end(), sb) - plan.starts.begin() : (size_t)n_chunks;
       // restarted at its start (context_flags_kernel's rule): where the caller's mask may say so; replace: every shorter context
       if (sb < L && (reset != nullptr || (!append && sb > 0))) plan.has_reset[at] = 1;
-      for (size_t ci = 0; ci < at && append; ++ci) plan.has_hold[ci] = 1;   // append: held in every chunk before that one
+      for (size_t ci = 0; ci < at && append && !started(); ++ci) plan.has_hold[ci] = 1;   // append: held in every chunk before that one
     }
     for (int ci = 0; ci < n_chunks; ++ci) host[B + ci] = plan.starts[ci];
+    if (started()) {   // rows of chunk ci: the envs with s_b <= its start -- a prefix, the lengths do not increase (check())
+      plan.rows.assign(n_chunks, 0);
+      for (int ci = 0, r = 0; ci < n_chunks; ++ci) {
+        while (r < B && L - lengths[r] <= plan.starts[ci]) ++r;
+        plan.rows[ci] = r;
+      }
+    }
     // ---- from here on the call launches ----
     lazy_materialize(e, s);   // stored contexts fold pending windows first (and complete a tail fold)
+    e->ctx_counts[3] += (int64_t)kept.size();
     if (!kept.empty()) save_slot_records(e, kept.data(), (int)kept.size(), e->KEEP.p, s);
     // (pageable host memory: the copies have read `host` when they return; the device side is ordered on `s`)
     LRAM_HIP_CHECK(hipMemcpyAsync(dev_start, host.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -750,7 +791,7 @@ void check_frames_call(const lram_engine* e, const char* who, const Inputs& in, 
   LRAM_REQUIRE(e->compat_repeat <= 1 && !e->compat_stale && !compat_shares(e, 0),
                w + ": a Mamba reference-trajectory mode is on (lram_set_compat_mode): its calls do not take their state "
                    "embeddings from one pass ahead of the chunks, which is where the frames are embedded");
-  LRAM_REQUIRE((size_t)e->B * in.L * c.d_model <= ((size_t)1 << 29),
+  LRAM_REQUIRE((size_t)e->context_rows() * in.L * c.d_model <= ((size_t)1 << 29),
                w + ": the [batch, timesteps, d_model] state embeddings of the frames exceed 2 GiB");
   check_frame_list(e, count_frames(e, in.L, lengths).frames, who);
 }
@@ -772,17 +813,24 @@ void stored_context_call(lram_engine* e, const char* who, RaggedCall* rc, const 
     check_score_sink(e, who, discrete, *sink);
   else if (actions != nullptr)
     check_head_mode(e, discrete, who);
+  e->ctx_counts[0] += 1;
+  Pass pass;
+  pass.context = true;
+  const int R = e->context_rows();
   if (rc == nullptr || rc->dense()) {   // every context of full length: the dense entry's own launches
     lazy_finish_prefold(e, s);          // (only an env-step takes a tail fold over)
-    timesteps_launches(e, Pass{}, in, reset, discrete, actions, tokens, s, sink);
+    timesteps_launches(e, pass, in, reset, discrete, actions, tokens, s, sink);
   } else {
     rc->run(reset, s, [&](const ContextPlan& plan) {
       // the call-timesteps ahead of the first chunk are padding for every env: their rows of the sink take the fill values here
+      // (per-chunk rows: an env is in no chunk ahead of its start, so the fill covers every call-timestep -- for env b the
+      // kernel keeps to its padded rows [n_b, timesteps))
       if (sink != nullptr)
-        launch_score_fill_ragged(sink->actions, sink->tokens, sink->logp, plan.dev_start, e->B, in.L, plan.starts[0], e->cfg.act_dim, s);
-      timesteps_launches(e, Pass{}, in, nullptr, discrete, actions, tokens, s, sink, &plan);
+        launch_score_fill_ragged(sink->actions, sink->tokens, sink->logp, plan.dev_start, R, in.L,
+                                 plan.rows.empty() ? plan.starts[0] : in.L, e->cfg.act_dim, s);
+      timesteps_launches(e, pass, in, nullptr, discrete, actions, tokens, s, sink, &plan);
       if (sink == nullptr && actions != nullptr)   // slots without a context: 0 / -1 in place of the head's answer to the padding
-        launch_action_fill_kept(actions, tokens, plan.dev_start, e->B, in.L, e->cfg.act_dim, s);
+        launch_action_fill_kept(actions, tokens, plan.dev_start, R, in.L, e->cfg.act_dim, s);
     });
   }
   // (a score is never a draw: the sampling mode and its counter are left alone)
@@ -802,8 +850,10 @@ FramesCall frames_call(lram_engine* e, const char* who, const uint8_t* dev_frame
   LRAM_REQUIRE(dev_frames != nullptr, w + ": dev_frames is NULL");
   LRAM_REQUIRE(append == 0 || append == 1, w + ": append must be 0 (replace) or 1 (append)");
   // the vector slots of a mixed table hand in observations; nobody else's dev_obs_seq is ever read
-  const bool mixed = e->slot_table && e->slot_n_image < e->B;
-  LRAM_REQUIRE(!e->slot_table || e->slot_n_image > 0, w + ": the slot table holds no image slot: there is no frame to take");
+  // (judged on the rows of the call: the image slots of the live prefix where lram_set_context_rows says so, as lram_step_slots)
+  const int R = e->context_rows(), n_image = e->slot_table && R > 0 ? e->slot_img_prefix[R] : 0;
+  const bool mixed = e->slot_table && n_image < R;
+  LRAM_REQUIRE(!e->slot_table || n_image > 0, w + ": the slot table holds no image slot: there is no frame to take");
   LRAM_REQUIRE(!mixed || dev_obs_seq != nullptr, w + ": dev_obs_seq is NULL and the slot table holds vector slots");
   FramesCall fc;
   fc.in = Inputs{mixed ? dev_obs_seq : nullptr, 0, dev_rtg_seq, dev_reward_seq, timesteps};
@@ -1104,7 +1154,8 @@ int32_t lram_encoder_step(lram_engine* e, const float* dev_inputs_embeds, int32_
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     prof_tick(e);
-    const size_t bytes = sizeof(float) * (size_t)e->B * tokens * e->cfg.d_model;
+    // (the rows of the call: the slices below cut the live prefix, which is the batch unless lram_set_context_rows lets it differ)
+    const size_t bytes = sizeof(float) * (size_t)e->context_rows() * tokens * e->cfg.d_model;
     lazy_finish_prefold(e, s);   // (only an env-step takes a tail fold over)
     if (!lazy_active(e, tokens)) lazy_materialize(e, s);
     LRAM_HIP_CHECK(hipMemcpyAsync(e->X.p, dev_inputs_embeds, bytes, hipMemcpyDeviceToDevice, s));
@@ -1189,6 +1240,26 @@ int32_t lram_image_counts(lram_engine* e, int64_t* out, int32_t reset) {
     LRAM_REQUIRE(e != nullptr && out != nullptr, "lram_image_counts: null argument");
     std::copy(e->img_counts, e->img_counts + 3, out);
     if (reset) std::fill(e->img_counts, e->img_counts + 3, (int64_t)0);
+  });
+}
+
+// Which slots the stored-context and encoder entries run on: host bookkeeping only.
+int32_t lram_set_context_rows(lram_engine* e, int32_t mode) {
+  return guarded([&] {
+    LRAM_REQUIRE(e != nullptr, "lram_set_context_rows: null engine");
+    LRAM_REQUIRE(mode >= LRAM_CONTEXT_ROWS_ALL && mode <= LRAM_CONTEXT_ROWS_STARTED,
+                 "lram_set_context_rows: mode " + std::to_string(mode) + " is outside 0 .. 2 (LRAM_CONTEXT_ROWS_ALL, _LIVE, _STARTED)");
+    e->ctx_rows = mode;
+  });
+}
+
+int32_t lram_get_context_rows(const lram_engine* e) { return e ? e->ctx_rows : 0; }
+
+int32_t lram_context_counts(lram_engine* e, int64_t* out, int32_t reset) {
+  return guarded([&] {
+    LRAM_REQUIRE(e != nullptr && out != nullptr, "lram_context_counts: null argument");
+    std::copy(e->ctx_counts, e->ctx_counts + 4, out);
+    if (reset) std::fill(e->ctx_counts, e->ctx_counts + 4, (int64_t)0);
   });
 }
 

@@ -134,6 +134,9 @@ _SYMBOLS = {
     "lram_state_swap_slots": (ctypes.c_int32, [_VP, _VP, _VP, ctypes.c_int32, _VP]),
     "lram_set_live": (ctypes.c_int32, [_VP, ctypes.c_int32, _VP]),
     "lram_get_live": (ctypes.c_int32, [_VP]),
+    "lram_set_context_rows": (ctypes.c_int32, [_VP, ctypes.c_int32]),
+    "lram_get_context_rows": (ctypes.c_int32, [_VP]),
+    "lram_context_counts": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]),
     "lram_stream_rmw": (ctypes.c_int32, [_VP, ctypes.c_size_t, _VP]),
     "lram_stream_read": (ctypes.c_int32, [_VP, ctypes.c_size_t, _VP, _VP]),
     "lram_gemm_counts": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]),
@@ -312,6 +315,19 @@ def _i32_array(values):
     return (ctypes.c_int32 * max(1, len(values)))(*values)
 
 
+CONTEXT_ROWS = ("all", "live", "started")   # LRAM_CONTEXT_ROWS_ALL / _LIVE / _STARTED, by value
+
+
+def _context_batch(eng) -> int:
+    """The rows a stored-context or encoder call of `eng` takes: the batch, or the live count (Engine.set_context_rows)."""
+    return eng.batch if getattr(eng, "_context_rows", "all") == "all" else eng._live
+
+
+def _context_rows_of(eng, buf):
+    n = _context_batch(eng)
+    return buf if n == eng.batch else buf[:n]
+
+
 def check_context_lengths(lengths, batch: int, L: int):
     """The length rules of lram_prefill_ragged / lram_score_ragged, checked on the host (no GPU needed): `batch` integer
     entries (a list, a numpy array or an integer tensor, moved to the host), each in 0 .. L, not all 0.  Returns them as ints;
@@ -428,6 +444,7 @@ class Engine:
         _check(self.lib, self.lib.lram_state_alloc(self._h, int(batch)))
         self.batch = int(batch)
         self._live = self.batch
+        self._context_rows = "all"   # (lram_state_alloc sets the mode back)
         self._slot_image = None      # host copy of the slot table's image column (a new allocation drops the table)
         self._n_img_live = 0         # image slots below `live`: the frames step_slots is handed
         B, A = self.batch, self.spec.act_dim
@@ -558,7 +575,7 @@ class Engine:
         """What prefill() and score() share: checks the [B, L, .] inputs and the reset mask, and returns (L, call).  call(*tail)
         checks and normalises `lengths`, picks the C entry -- dense without lengths, else the append or the ragged (replace)
         one -- and runs it: the arguments up to the reset mask from here, `tail` (from the head mode on) behind them."""
-        B, spec = self.batch, self.spec
+        B, spec = _context_batch(self), self.spec
         L = obs_seq.shape[1]
         _chk_dev(obs_seq, torch.float32, (B, L, spec.d_model if obs_is_embedding else spec.state_dim), self.device,
                  "obs_seq")
@@ -582,8 +599,8 @@ class Engine:
     def _frames_context_call(self, kind: str, frames, obs_seq, rtg_seq, reward_seq, reset_mask, lengths, append):
         """_stored_context_call for frames: checks the inputs (check_frame_contexts) and returns (L, call); call(*tail) runs
         lram_prefill_frames / lram_score_frames with `tail` (from the head mode on) behind the reset mask."""
-        B = self.batch
-        n_img = int(self._slot_image.sum()) if self._slot_image is not None else None   # (None: no slot table)
+        B = _context_batch(self)   # (the image slots among the rows of the call hand in frames)
+        n_img = int(self._slot_image[:B].sum()) if self._slot_image is not None else None   # (None: no slot table)
         L, C, H, W = check_frame_contexts(frames, obs_seq, B, n_img, self.spec.state_dim)
         _chk_dev(frames, torch.uint8, tuple(frames.shape), self.device, "frames")
         if n_img is None or n_img == B:
@@ -613,8 +630,8 @@ class Engine:
         result as in prefill().  Bit-identical to prefill(embed_frames(frames), obs_is_embedding=True) for a dense call."""
         self._need_all_live("prefill_frames")
         _, call = self._frames_context_call("prefill", frames, obs_seq, rtg_seq, reward_seq, reset_mask, lengths, append)
-        act = self._actions if want_action else None
-        tok = self._tokens if want_action else None
+        act = _context_rows_of(self, self._actions) if want_action else None
+        tok = _context_rows_of(self, self._tokens) if want_action else None
         call(_head_mode(discrete), _ptr(act), _ptr(tok))
         return (act, tok) if want_action else (None, None)
 
@@ -627,7 +644,7 @@ class Engine:
         """score() from uint8 frames (lram_score_frames): `frames` / `obs_seq` as in prefill_frames(), everything else as in
         score()."""
         self._need_all_live("score_frames")
-        B, spec = self.batch, self.spec
+        B, spec = _context_batch(self), self.spec
         want = (want,) if isinstance(want, str) else tuple(want)
         for w in want:
             if w not in ("actions", "tokens", "logp"):
@@ -665,8 +682,8 @@ class Engine:
         length 0 is held -- no kernel writes its state.  Without lengths, append changes nothing: the dense call."""
         self._need_all_live("prefill")
         L, call = self._stored_context_call("prefill", obs_seq, rtg_seq, reward_seq, reset_mask, obs_is_embedding, lengths, append)
-        act = self._actions if want_action else None
-        tok = self._tokens if want_action else None
+        act = _context_rows_of(self, self._actions) if want_action else None
+        tok = _context_rows_of(self, self._tokens) if want_action else None
         call(_head_mode(discrete), _ptr(act), _ptr(tok))
         return (act, tok) if want_action else (None, None)
 
@@ -686,7 +703,7 @@ class Engine:
         that of every env's own context.  `append=True` with lengths (lram_score_append): as in prefill() -- the contexts
         continue the slots' states, which is how a trajectory longer than one call is scored window by window."""
         self._need_all_live("score")
-        B, spec = self.batch, self.spec
+        B, spec = _context_batch(self), self.spec
         if obs_seq.dim() != 3:
             raise ValueError("obs_seq must be [B, L, state_dim]")
         want = (want,) if isinstance(want, str) else tuple(want)
@@ -797,7 +814,7 @@ class Engine:
     def encoder_step(self, inputs_embeds: torch.Tensor, reset_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """`self.encoder(inputs_embeds=[B,T,D], use_cache=True)` plug point (decision_xlstm.py:138-169)."""
         self._need_all_live("encoder_step")
-        B, D = self.batch, self.spec.d_model
+        B, D = _context_batch(self), self.spec.d_model
         T = inputs_embeds.shape[1]
         _chk_dev(inputs_embeds, torch.float32, (B, T, D), self.device, "inputs_embeds")
         if reset_mask is not None:
@@ -885,7 +902,7 @@ class Engine:
     def set_live(self, n: int):
         """The first `n` slots (1 .. batch) are live from now on; the others are parked: they keep their recurrent state and
         no row of them is computed (lram_set_live; lazy mode still carries their bookkeeping over each step).  step / step_images / step_slots / last_logp / taps then take and return `n` rows;
-        prefill / score / encoder_step raise until every slot is live again.  Cheap: no synchronisation, no allocation."""
+        prefill / score / encoder_step raise until every slot is live again, unless set_context_rows says otherwise.  Cheap: no synchronisation, no allocation."""
         _check(self.lib, self.lib.lram_set_live(self._h, int(n), _stream_ptr(self.device)))
         self._live = int(self.lib.lram_get_live(self._h))
         if self._slot_image is not None:
@@ -899,11 +916,36 @@ class Engine:
         _check(self.lib, self.lib.lram_state_swap_slots(self._h, _i32_array(a), _i32_array(b), len(a),
                                                         _stream_ptr(self.device)))
 
+    # -- context rows: stored contexts and encoder calls on the live prefix -------------------------
+    @property
+    def context_rows(self) -> str:
+        """Which slots prefill / score / their frames forms / encoder_step run on (lram_get_context_rows): "all", "live" or
+        "started"."""
+        return self._context_rows
+
+    def set_context_rows(self, mode: str):
+        """"all" (the default; alloc() sets it back): every allocated slot, and the calls raise while slots are parked.
+        "live": the live prefix -- inputs, lengths, reset mask and results have `live` rows, parked slots are left alone.
+        "started": "live", and a call with `lengths` -- which must then not increase in slot order -- runs in every chunk only
+        the envs that have started by it: no held rows, no rows on zero tokens, no record saved for a slot of length 0.
+        Cheap: host bookkeeping only (lram_set_context_rows)."""
+        if mode not in CONTEXT_ROWS:
+            raise ValueError(f'context rows: unknown mode {mode!r} (choose among "all", "live", "started")')
+        _check(self.lib, self.lib.lram_set_context_rows(self._h, CONTEXT_ROWS.index(mode)))
+        self._context_rows = mode
+
+    def context_counts(self, reset: bool = False) -> dict:
+        """What the stored-context entries have done since the last reset (lram_context_counts): "calls", "chunks" run,
+        "env_timesteps" computed (the sum over chunks of rows x timesteps), "kept" slot records saved and restored."""
+        buf = (ctypes.c_int64 * 4)()
+        _check(self.lib, self.lib.lram_context_counts(self._h, buf, 1 if reset else 0))
+        return {"calls": int(buf[0]), "chunks": int(buf[1]), "env_timesteps": int(buf[2]), "kept": int(buf[3])}
+
     def _live_rows(self, buf: torch.Tensor) -> torch.Tensor:
         return buf if self._live == self.batch else buf[:self._live]
 
     def _need_all_live(self, what: str):
-        if self._live != self.batch:
+        if self._context_rows == "all" and self._live != self.batch:
             raise LramError(f"{what}: {self.batch - self._live} of {self.batch} env slots are parked (set_live): stored "
                             f"contexts and encoder calls need every slot live -- call set_live(batch) first")
 

@@ -151,6 +151,44 @@ class SlotScheduler:
         self.n_live = new_live
         return [p[0] for p in pairs], [p[1] for p in pairs], new_live
 
+    def arrange(self, env_ids):
+        """Put the listed envs, live or parked, into slots 0 .. n - 1 in the given order.  Returns the swap lists [(a, b), ...] to
+        hand to Engine.swap_slots one after the other -- at most two, however many envs are listed, and all indices of one
+        list distinct.  The live count is the caller's business and does not move; an env that is not listed moves only if it
+        sits in a slot the listed ones take.  Applying the lists again in reverse order undoes the arrangement.
+        Why two: the slots' contents move by a permutation, every cycle (c_0 -> c_1 -> ... -> c_{k-1} -> c_0) of it is a
+        rotation j -> j + 1, and a rotation is the product of the reflections j -> -j and j -> 1 - j (mod k), each an
+        involution: a list of disjoint swaps.  The first list holds the first reflection of every cycle, the second the second."""
+        ids = [int(e) for e in env_ids]
+        if len(set(ids)) != len(ids) or any(not 0 <= e < self.n for e in ids):
+            raise ValueError(f"arrange: expected distinct env ids in 0 .. {self.n - 1}")
+        n = len(ids)
+        to = {self.slot_of[e]: i for i, e in enumerate(ids)}   # slot now -> slot afterwards, of the listed envs
+        # An unlisted env in the prefix goes to the slot that the chain of listed envs ending at its slot started from: the
+        # chains close into cycles and no other slot is touched.
+        for f in [s for s in to if s >= n]:
+            d = f
+            while d in to:
+                d = to[d]
+            to[d] = f
+        first, second, seen = [], [], set()
+        for s0 in sorted(to):
+            if s0 in seen or to[s0] == s0:
+                continue
+            cyc = [s0]
+            while to[cyc[-1]] != s0:
+                cyc.append(to[cyc[-1]])
+            seen.update(cyc)
+            k = len(cyc)
+            first += [(cyc[j], cyc[-j % k]) for j in range(k) if j < -j % k]
+            second += [(cyc[j], cyc[(1 - j) % k]) for j in range(k) if j < (1 - j) % k]
+        lists = []
+        for pairs in (first, second):
+            if pairs:
+                self._swap(pairs)
+                lists.append(([p[0] for p in pairs], [p[1] for p in pairs]))
+        return lists
+
 
 class BatchedRollout:
     """agent: object with predict_batch(obs, rtg, rewards, reset_mask, env_act_dim) (lram_amd.agent.RecurrentAgent)."""
