@@ -757,6 +757,53 @@ int32_t lram_score_frames(lram_engine* e, const uint8_t* dev_frames, int32_t cha
 int32_t lram_set_slot_table(lram_engine* e, const uint8_t* host_flags, const uint8_t* host_act_dim);
 int32_t lram_get_slot_table(lram_engine* e, uint8_t* host_flags, uint8_t* host_act_dim, int32_t* n_image_slots);
 
+/* Allowed-action sets: which vocabulary tokens an env slot may take.  The reference cuts every env's row at `discrete_actions`
+ * alike (get_action_from_logits, src/algos/models/multi_domain_discrete_dt_model.py:83-88); the envs differ from that (Procgen
+ * has 15 actions, an Atari game on its minimal set 4 .. 18 that are no prefix of the full set, Dark-Room 5), and under sampling
+ * a slot would be handed an action its env does not have.
+ *   host_bits  host uint32[batch, words], words = ceil(cfg.n_vocab / 32): bit t & 31 of word t >> 5 set = token t is allowed.
+ *              NULL clears the mask.  Bits at or above n_vocab are ignored and read back as 0.
+ * The rule, the same in every head kernel: a column in use (env slot b, action dim j) with the selectable range [0, n)
+ * (n = n_discrete on a discrete column, n_vocab otherwise) works on the SUB-ROW x[i], i in S_b within [0, n), in vocabulary order,
+ * exactly as if the reference's function had been handed that sub-row, and maps the answer back to vocabulary indices:
+ *   - greedy (the argmax head, greedy slots of the sampling head, the greedy token / action of the score entries): the
+ *     first index of the sub-row's maximum;
+ *   - a draw (lram_set_sampling): sample_from_logits on the sub-row -- the quantile ranks its m = |S_b within [0, n)| values, top-k
+ *     keeps among them (a top_k above m keeps all), weights and inverse CDF in vocabulary order.  The Philox counter is
+ *     unchanged, so the uniform of a (slot, dim, draw) does not depend on the mask.  The argmax rule takes over where the
+ *     sub-row holds a NaN, its maximum is +-inf, or nothing is left.  Disallowed logits are invisible, a NaN included;
+ *   - lram_score_last_sampled: under that distribution; a disallowed token scores -inf, on the argmax rule the sub-row's
+ *     argmax scores 0;
+ *   - over = 1 (the selectable range) of lram_score* / lram_score_last: maximum, NaN flag and sum over the sub-row; a target
+ *     outside it scores -inf;
+ *   - over = 0 (the vocabulary): unchanged -- all n_vocab logits, the reference's cross-entropy; the greedy token and action
+ *     returned beside it still obey the mask;
+ *   - raw logits (the `logits` output of the score entries, lram_get_taps) are never altered.
+ * A token returned for a masked slot is always allowed; a mask that allows everything equals no mask, bit for bit.
+ *   - Not a hot-path call: like lram_set_slot_table it keeps a host copy and a device copy, synchronises and drops a captured
+ *     graph.  lram_state_alloc drops the mask.  lram_config and LRAM_ABI_VERSION are unchanged.
+ *   - The mask stays with the slot INDEX, as the slot table and the sampling table do: lram_state_copy_slots / swap_slots /
+ *     load_slots do not move it.  It applies to whatever rows a call takes (the live prefix, context rows, env slices).
+ *   - Refused, with nothing changed: words != ceil(n_vocab / 32); a slot that allows nothing inside its selectable range (with
+ *     a slot table the slot's own flag decides the range, without one it is [0, n_vocab)).  While some slot allows nothing
+ *     below n_discrete, a call with discrete = 1 is refused before anything is launched; and lram_set_slot_table is refused
+ *     while a mask is in effect if the new table would leave some slot an empty sub-row.
+ * lram_get_action_mask copies the mask in effect back (host_bits may be NULL; zeros when none is set) and sets *on to 0 / 1. */
+int32_t lram_set_action_mask(lram_engine* e, const uint32_t* host_bits, int32_t words);
+int32_t lram_get_action_mask(lram_engine* e, uint32_t* host_bits, int32_t words, int32_t* on);
+/* lram_sample_rows / lram_score_tokens with one allowed set per row (test / evidence entries of the rule above):
+ * dev_mask device uint32[rows, words], words = ceil(n / 32) resp. ceil(n_vocab / 32); every row's sub-row must be non-empty
+ * (not checked: the sets are device data; an empty one yields token INT32_MAX). */
+int32_t lram_sample_rows_masked(const float* dev_logits, int64_t rows, int32_t n, int64_t ld, const uint8_t* dev_mode,
+                                const double* dev_temperature, const int32_t* dev_top_k, const double* dev_top_p,
+                                const double* dev_uniform, const int32_t* dev_tokens_in, int32_t* dev_tokens_out,
+                                float* dev_logp_out, const uint32_t* dev_mask, int32_t words, void* stream);
+int32_t lram_score_tokens_masked(const float* dev_logits, int64_t rows, int32_t act_dim, int32_t n_vocab, int32_t n_discrete,
+                                 int32_t action_channels, float tok_min, float tok_max, int32_t discrete,
+                                 const float* dev_target_actions, const int32_t* dev_target_tokens, const uint8_t* dev_valid,
+                                 int32_t over, double temperature, float* dev_actions, int32_t* dev_tokens, float* dev_logp,
+                                 const uint32_t* dev_mask, int32_t words, void* stream);
+
 /* One env-step of a mixed batch: per slot the observation is a vector or a frame and the head is continuous or discrete, as the
  * slot table says -- the batched form of the reference's forward, which embeds `states` through embed_state or embed_image
  * depending on the env (online_decision_transformer_model.py:463-530) and reads the head as the env's kind asks

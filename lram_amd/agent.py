@@ -111,6 +111,9 @@ class RecurrentAgent:
             slot_table.sample_settings(spec.n_discrete, spec.n_vocab, a_sample_kwargs)   # (raises what the head would refuse)
         self.sample_seed, self.sample_slot_base = int(sample_seed), int(sample_slot_base)
         self._slot_sampling = {}   # set_slot_sampling: slot -> resolved dict | "greedy" (plain data: crosses a pickle)
+        self._slot_actions = {}    # set_slot_actions: slot -> tuple of allowed indices (plain data too)
+        if slot_table is not None:
+            slot_table.action_mask(spec.n_vocab, spec.n_discrete)   # (raises where a domain's set leaves its head's range)
         # host copy of the weights: lets the agent cross a process boundary (make_pickleable / reinit_cuda_kernels)
         self._state_dict = {k: v.detach().to("cpu") for k, v in state_dict.items()}
         self._graph = bool(graph)
@@ -161,6 +164,58 @@ class RecurrentAgent:
     def _apply_slot_table(self):
         if getattr(self, "slot_table", None) is not None:
             self.engine.set_slot_table(*self.slot_table.engine_arrays())
+        mask = self.slot_action_mask()
+        if mask is not None:   # (the table's sets, then set_slot_actions'; an engine without one is never asked)
+            self.engine.set_action_mask(mask)
+
+    def slot_action_mask(self) -> Optional[torch.Tensor]:
+        """The allowed sets the engine is given (Engine.set_action_mask's argument), bool [n_envs, n_vocab], or None where
+        every slot may take everything: the domains' own sets (SlotTable.action_mask), then set_slot_actions'."""
+        table = getattr(self, "slot_table", None)
+        own = getattr(self, "_slot_actions", {})
+        mask = None if table is None else table.action_mask(self.spec.n_vocab, self.spec.n_discrete)
+        if mask is None:
+            if not own:
+                return None
+            mask = torch.ones(self.n_envs, self.spec.n_vocab, dtype=torch.bool)
+        for b, acts in own.items():
+            mask[b] = False
+            mask[b, list(acts)] = True
+        return mask
+
+    def set_slot_actions(self, slots, allowed):
+        """The allowed set of single env slots, with or without a slot table -- an Atari game on its minimal action set beside
+        games on the full one.  `allowed`: indices (actions below n_discrete on a discrete slot, vocabulary tokens otherwise;
+        unique, non-empty), for every slot in `slots`; None gives the slots back their domain's set, or everything.  The sets
+        stay with the slot index, like the slot's sampling setting."""
+        slots = [int(b) for b in (slots.tolist() if isinstance(slots, torch.Tensor) else slots)]
+        acts = None
+        if allowed is not None:
+            acts = [a for a in (allowed.tolist() if isinstance(allowed, torch.Tensor) else allowed)]
+            if not acts or any(isinstance(a, bool) or int(a) != a or a < 0 for a in acts) or len(set(acts)) != len(acts):
+                raise ValueError(f"set_slot_actions: expected distinct indices >= 0 (at least one), got {acts}")
+            acts = tuple(int(a) for a in acts)
+        new = dict(self._slot_actions)
+        for b in slots:
+            if not 0 <= b < self.n_envs:
+                raise IndexError(f"set_slot_actions: slot {b} outside 0 .. {self.n_envs - 1}")
+            if acts is None:
+                new.pop(b, None)
+                continue
+            if max(acts) >= self._head_width(b):
+                raise ValueError(f"set_slot_actions: slot {b} selects among {self._head_width(b)} logits, got index {max(acts)}")
+            new[b] = acts
+        had, old = self.slot_action_mask() is not None, self._slot_actions
+        self._slot_actions = new
+        if self.engine is None:
+            return
+        mask = self.slot_action_mask()
+        if mask is not None or had:
+            try:
+                self.engine.set_action_mask(mask)
+            except Exception:
+                self._slot_actions = old   # a refused mask leaves the engine's as it was: so does the agent's record
+                raise
 
     @property
     def slot_is_discrete(self) -> torch.Tensor:
@@ -275,6 +330,19 @@ class RecurrentAgent:
                 for key, runs in groups.items()]
             if "a_sample_kwargs" not in mode and self._sampling_armed():
                 mode["a_sample_kwargs"] = {"seed": self.sample_seed, "slot_base": self.sample_slot_base}
+        mask = self.slot_action_mask() if hasattr(self, "_slot_actions") else None
+        if mask is not None:   # per distinct allowed set, the slot ranges that hold it (a set that allows everything: "all")
+            groups = {}
+            for b in range(self.n_envs):
+                key = tuple(torch.nonzero(mask[b]).reshape(-1).tolist())
+                runs = groups.setdefault(key, [])
+                if runs and runs[-1][1] == b:
+                    runs[-1][1] = b + 1
+                else:
+                    runs.append([b, b + 1])
+            mode["a_allowed"] = [{"slots": [tuple(r) for r in runs],
+                                  "allowed": "all" if len(key) == self.spec.n_vocab else list(key)}
+                                 for key, runs in groups.items()]
         return mode
 
     # ---- cache handle: `model.past_key_values = None` resets, reading exports the reference layout ----
@@ -320,7 +388,7 @@ class RecurrentAgent:
         return list(range(self.n_envs)) if sch is None else sch.live_envs()
 
     def _slots_alike(self, a: int, b: int) -> Optional[str]:
-        """None where slots a and b carry the same slot-table entry and per-slot sampling setting, else what differs."""
+        """None where slots a and b carry the same slot-table entry, per-slot sampling setting and allowed set, else what differs."""
         table = getattr(self, "slot_table", None)
         if table is not None:
             for name in ("discrete", "act_dim", "image"):
@@ -332,7 +400,19 @@ class RecurrentAgent:
             for name, col in cols.items():
                 if col[a] != col[b]:
                     return f"per-slot sampling setting `{name}`"
+        if self._slot_allowed(a) != self._slot_allowed(b):
+            return "allowed-action set"
         return None
+
+    def _slot_allowed(self, b: int):
+        """Slot b's allowed set as slot_action_mask() states it, without building the mask: a frozenset of indices, or None
+        where the slot may take every token."""
+        acts = getattr(self, "_slot_actions", {}).get(b)
+        if acts is None and getattr(self, "slot_table", None) is not None:
+            acts = self.slot_table.domain_of(b).allowed_actions
+        if acts is None or len(set(acts)) == self.spec.n_vocab:
+            return None
+        return frozenset(acts)
 
     def set_active(self, env_ids):
         """The envs predict_batch steps from now on (at least one).  The others are parked: their recurrent state stays in the

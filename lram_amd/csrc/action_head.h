@@ -64,6 +64,50 @@ __device__ __forceinline__ int row_argmax(const float* row, int n, int lane) {
   return bi;
 }
 
+// The allowed-set rule (lram_set_action_mask).  A column works on the SUB-ROW x[i], i in S within [0, n), in vocabulary order,
+// where S is its env slot's allowed set: a disallowed entry is not there, whatever it holds.  `w` = the slot's words.
+// Every kernel takes the rule as a compile-time MASK: the instances without it are the code they were.
+// (every lane of a wave has the wave's env: the slot's pointer is moved to scalar registers, its words are scalar loads)
+__device__ __forceinline__ const uint32_t* mask_words(const HeadMask& m, int64_t env) {
+  const uint64_t p = reinterpret_cast<uint64_t>(m.bits + env * m.words);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)p);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(p >> 32));
+  return reinterpret_cast<const uint32_t*>(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ bool mask_allows(const uint32_t* w, int i) { return (w[i >> 5] >> (i & 31)) & 1u; }
+// The argmax rule over the sub-row (one word read per element: the walk is lane-strided).  With a non-empty sub-row it ends
+// on a real index of it: argmax_beats from (-inf, INT_MAX) takes the first entry it sees, NaN and -inf included.
+__device__ __forceinline__ int row_argmax_masked(const float* row, int n, int lane, const uint32_t* w) {
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int i = lane; i < n; i += 64) argmax_take(row[i], i, best, bi, mask_allows(w, i));
+  wave_argmax(best, bi);
+  return bi;
+}
+// Staged rows (n <= 512: at most 16 words): lane l holds the PER (<= 8) consecutive entries from l * PER on, so its bits
+// come from at most two adjacent words.  Bit j of the result = entry l * PER + j is allowed; entries from 32 * words on are
+// not (the word behind a slot's last word is never read: behind the last slot's it is past the allocation).
+template <int PER>
+__device__ __forceinline__ uint32_t mask_lane_bits(const uint32_t* w, int words, int lane) {
+  static_assert(PER >= 1 && PER <= 8, "a lane's entries span at most two words");
+  const int first = lane * PER, k = first >> 5;
+  if (k >= words) return 0u;
+  const uint64_t lo = w[k], hi = k + 1 < words ? w[k + 1] : 0u;
+  return (uint32_t)(((hi << 32) | lo) >> (first & 31)) & ((1u << PER) - 1u);
+}
+// m = |S within [0, n)|, wave-uniform: lanes 0 .. words - 1 count their word cut at n, then a wave sum (words <= 64).
+__device__ __forceinline__ int mask_count(const uint32_t* w, int words, int n, int lane) {
+  int cnt = 0;
+  if (lane < words && lane * 32 < n) {
+    const int left = n - lane * 32;  // >= 1
+    const uint32_t cut = left >= 32 ? 0xffffffffu : (1u << left) - 1u;
+    cnt = __popc(w[lane] & cut);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+  return cnt;
+}
+
 // The action of a token: the token itself on a discrete column, otherwise inv_tokenize of its bin.
 __device__ __forceinline__ float head_bin_width(const HeadGeom& g) { return (g.tok_max - g.tok_min) / (float)g.action_channels; }
 __device__ __forceinline__ float detokenise(int tok, int discrete, const HeadGeom& g) {

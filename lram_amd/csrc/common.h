@@ -229,9 +229,16 @@ struct HeadSlots {
   const uint8_t* flags = nullptr;
   const uint8_t* act = nullptr;
 };
+// The allowed-action sets (lram_set_action_mask), next to the slot table: `words` uint32 per env slot, bit t & 31 of word t >> 5
+// = token t may be taken; entry 0 = the launch's first env slot.  bits null: no mask, and the launch is the code it was
+// before masks (a compile-time split, as the sampling table's).
+struct HeadMask {
+  const uint32_t* bits = nullptr;
+  int words = 0;
+};
 // argmax over logits [B, act_dim*n_vocab] (+ de-tokenise); columns col_begin .. col_end - 1 (sample_kernels.hip)
 void launch_action_argmax(const float* logits, float* actions, int32_t* tokens, int B, const HeadGeom& g, const HeadSlots& s,
-                          int discrete, int col_begin, int col_end, hipStream_t stream);
+                          int discrete, int col_begin, int col_end, hipStream_t stream, const HeadMask& mask = {});
 // The sampling mode of the same head (sample_kernels.hip): the token is drawn from the row instead of being its argmax.
 constexpr int kSampleMaxRow = 512;  // logits per row the sampling kernels hold in registers (8 per lane)
 struct SampleArgs {
@@ -252,10 +259,11 @@ struct SampleSlot {
 // slots: nullable device table, entry 0 = the launch's first env slot; null: the launch is what it was before the table
 void launch_action_sample(const float* logits, float* actions, int32_t* tokens, int B, const HeadGeom& g, const HeadSlots& s,
                           int discrete, int col_begin, int col_end, const SampleArgs& sp, const SampleSlot* slots,
-                          hipStream_t stream);
+                          hipStream_t stream, const HeadMask& mask = {});
 // logp[B, act_dim] of tokens[B, act_dim] under the distribution launch_action_sample draws from (filters applied; sp.draw unused)
 void launch_action_logp(const float* logits, const int32_t* tokens, float* logp, int B, const HeadGeom& g, const HeadSlots& s,
-                        int discrete, const SampleArgs& sp, const SampleSlot* slots, hipStream_t stream);
+                        int discrete, const SampleArgs& sp, const SampleSlot* slots, hipStream_t stream,
+                        const HeadMask& mask = {});
 void launch_sample_advance(uint64_t* draw, hipStream_t stream);  // ++*draw, one thread
 // rows of n logits at logits + r * ld (ld = 0: every row is row 0), one caller uniform per row -> tokens[rows]
 void launch_sample_tokens(const float* logits, int64_t rows, int n, int64_t ld, double temperature, int top_k, double top_p,
@@ -263,7 +271,7 @@ void launch_sample_tokens(const float* logits, int64_t rows, int n, int64_t ld, 
 // the same with per-row settings (device arrays [rows]); uniform + tokens_out: draw, tokens_in + logp_out: score (each pair nullable)
 void launch_sample_rows(const float* logits, int64_t rows, int n, int64_t ld, const uint8_t* mode, const double* temperature,
                         const int32_t* top_k, const double* top_p, const double* uniform, const int32_t* tokens_in,
-                        int32_t* tokens_out, float* logp_out, hipStream_t stream);
+                        int32_t* tokens_out, float* logp_out, hipStream_t stream, const HeadMask& mask = {});  // mask: [rows, words]
 // out[s * act_dim + j] = the uniform of env slot slot_base + s, action dim j, draw `draw`
 void launch_sample_uniforms(uint64_t seed, uint64_t slot_base, int64_t n_slots, int act_dim, uint64_t draw, double* out,
                             hipStream_t stream);
@@ -295,7 +303,9 @@ struct ScoreArgs {
   // call over t = 0 .. outer - 1 write every row of the tensors exactly once.
   const int32_t* start = nullptr;
 };
-void launch_action_score(const ScoreArgs& a, hipStream_t stream);
+// mask: allowed sets [envs, words], nullable: the greedy range and the over = 1 normalisation obey it.  It is an argument of the
+// masked kernels alone, so that the launch without one passes the argument block it always passed.
+void launch_action_score(const ScoreArgs& a, hipStream_t stream, const HeadMask& mask = {});
 
 // Stored contexts of per-env length (context_kernels.hip; the ragged and append entries).  start[b] = L - n_b is the
 // call-timestep at which env b's context begins inside a call of L timesteps (n_b = 0: start[b] = L, the slot only sees padding or is held).

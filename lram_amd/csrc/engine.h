@@ -180,6 +180,36 @@ struct lram_engine {
   int32_t* slot_img_list = nullptr;            // device [n_image_slots]
   int slot_n_image = 0;
   bool slot_has_discrete = false;
+  // Allowed-action sets (lram_set_action_mask): mask_words uint32 per env slot, bit t & 31 of word t >> 5 = token t may be
+  // taken.  Host copy + device copy [B, mask_words]; they stay with the slot INDEX, as the slot table does.  Every head launch
+  // passes head_mask(); without a mask that is {null, 0} and the launch is the unmasked kernel.  mask_no_discrete_at: the first
+  // slot that allows nothing below n_discrete (-1: none) -- what a discrete = 1 call is refused on before anything is launched.
+  int mask_words = 0;
+  std::vector<uint32_t> mask_bits;
+  uint32_t* mask_dev = nullptr;
+  int mask_no_discrete_at = -1;
+  // tokens of slot b's set below n (words of a [., words] table)
+  static int mask_count_below(const uint32_t* bits, int words, int b, int n) {
+    int cnt = 0;
+    for (int k = 0; k < words && k * 32 < n; ++k) {
+      const int left = n - k * 32;
+      cnt += __builtin_popcount(bits[(size_t)b * words + k] & (left >= 32 ? 0xffffffffu : (1u << left) - 1u));
+    }
+    return cnt;
+  }
+  // The first slot whose sub-row would be empty under the table `flags` (null: no table, every range is [0, n_vocab)); -1: none.
+  int mask_first_empty(const uint32_t* bits, int words, const uint8_t* flags) const {
+    for (int b = 0; b < B; ++b) {
+      const int n = (flags != nullptr && (flags[b] & 1)) ? cfg.n_discrete : cfg.n_vocab;
+      if (mask_count_below(bits, words, b, n) == 0) return b;
+    }
+    return -1;
+  }
+  void drop_action_mask() {
+    if (mask_dev) (void)hipFree(mask_dev);
+    mask_dev = nullptr, mask_words = 0, mask_no_discrete_at = -1;
+    mask_bits.clear();
+  }
   // lazy matrix memory: C_base read once per step, rewritten once per `lazy_period` steps (see mlstm_lazy.hip)
   int lazy_mode = 2;        // 0 materialised, 1 lazy, 2 auto (LRAM_STATE / lram_set_state_mode)
   bool lazy = false;        // effective choice for the current batch (decided in state_alloc / set_state_mode)
@@ -370,6 +400,7 @@ struct lram_engine {
     if (sample_draw) (void)hipFree(sample_draw);
     drop_sample_slots();
     drop_slot_table();
+    drop_action_mask();
   }
   void drop_slot_table() {
     if (slot_dev) (void)hipFree(slot_dev);

@@ -559,6 +559,7 @@ void state_alloc(lram_engine* e, int B) {
   e->release_state();
   e->drop_slot_table();   // the table describes the slots of one allocation
   e->drop_sample_slots(); // and so do the per-slot sampling settings
+  e->drop_action_mask();  // and the allowed-action sets
   const lram_config& c = e->cfg;
   const size_t D = c.d_model;
   e->st.resize(c.n_blocks);

@@ -150,6 +150,11 @@ int32_t lram_set_slot_table(lram_engine* e, const uint8_t* host_flags, const uin
         n_img += (f & LRAM_SLOT_IMAGE) ? 1 : 0;
       }
     }
+    if (!e->mask_bits.empty()) {  // a mask in effect: the new table (or none) must leave every slot a non-empty sub-row
+      const int at = e->mask_first_empty(e->mask_bits.data(), e->mask_words, host_flags);
+      LRAM_REQUIRE(at < 0, "lram_set_slot_table: the action mask in effect (lram_set_action_mask) allows slot " + std::to_string(at) +
+                               " nothing inside the selectable range this table gives it");
+    }
     LRAM_HIP_CHECK(hipSetDevice(e->device));
     LRAM_HIP_CHECK(hipDeviceSynchronize());  // steps in flight read the table they were launched with
     e->drop_graph();                         // the head launch and its table pointers are part of a captured step
@@ -175,6 +180,52 @@ int32_t lram_set_slot_table(lram_engine* e, const uint8_t* host_flags, const uin
     LRAM_HIP_CHECK(hipDeviceSynchronize());
     e->slot_n_image = n_img, e->slot_has_discrete = has_discrete, e->slot_table = true;
     e->sample_slot_maxima();   // which sampling slots are discrete has changed
+  });
+}
+
+int32_t lram_set_action_mask(lram_engine* e, const uint32_t* host_bits, int32_t words) {
+  return guarded([&] {
+    LRAM_REQUIRE(e && e->B > 0, "lram_set_action_mask: state not allocated (call lram_state_alloc)");
+    const int B = e->B, V = e->cfg.n_vocab, W = (V + 31) / 32;
+    std::vector<uint32_t> bits;
+    int no_discrete_at = -1;
+    if (host_bits != nullptr) {  // validate before anything changes: a refused mask leaves the one in effect as it is
+      LRAM_REQUIRE(words == W, "lram_set_action_mask: words must be ceil(n_vocab / 32) = " + std::to_string(W) + ", got " +
+                                   std::to_string(words));
+      bits.assign(host_bits, host_bits + (size_t)B * W);
+      if (V & 31)  // bits at or above n_vocab are ignored and read back as 0
+        for (int b = 0; b < B; ++b) bits[(size_t)b * W + W - 1] &= (1u << (V & 31)) - 1u;
+      const int at = e->mask_first_empty(bits.data(), W, e->slot_table ? e->slot_flags.data() : nullptr);
+      LRAM_REQUIRE(at < 0, "lram_set_action_mask: slot " + std::to_string(at) + " allows nothing inside its selectable range");
+      for (int b = 0; b < B && no_discrete_at < 0; ++b)
+        if (lram_engine::mask_count_below(bits.data(), W, b, e->cfg.n_discrete) == 0) no_discrete_at = b;
+    }
+    LRAM_HIP_CHECK(hipSetDevice(e->device));
+    LRAM_HIP_CHECK(hipDeviceSynchronize());  // steps in flight read the mask they were launched with
+    e->drop_graph();                         // the head launch (masked or not) and its pointers are part of a captured step
+    if (host_bits == nullptr) {
+      e->drop_action_mask();
+      return;
+    }
+    if (!e->mask_dev) LRAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->mask_dev), sizeof(uint32_t) * (size_t)B * W));
+    LRAM_HIP_CHECK(hipMemcpy(e->mask_dev, bits.data(), sizeof(uint32_t) * (size_t)B * W, hipMemcpyHostToDevice));
+    LRAM_HIP_CHECK(hipDeviceSynchronize());
+    e->mask_bits = std::move(bits), e->mask_words = W, e->mask_no_discrete_at = no_discrete_at;
+  });
+}
+
+int32_t lram_get_action_mask(lram_engine* e, uint32_t* host_bits, int32_t words, int32_t* on) {
+  return guarded([&] {
+    LRAM_REQUIRE(e && e->B > 0, "lram_get_action_mask: state not allocated (call lram_state_alloc)");
+    const int W = (e->cfg.n_vocab + 31) / 32;
+    if (host_bits != nullptr) {
+      LRAM_REQUIRE(words == W, "lram_get_action_mask: words must be ceil(n_vocab / 32) = " + std::to_string(W));
+      if (e->mask_bits.empty())
+        std::memset(host_bits, 0, sizeof(uint32_t) * (size_t)e->B * W);
+      else
+        std::memcpy(host_bits, e->mask_bits.data(), sizeof(uint32_t) * (size_t)e->B * W);
+    }
+    if (on) *on = e->mask_bits.empty() ? 0 : 1;
   });
 }
 

@@ -280,6 +280,18 @@ HeadSlots head_slots(const lram_engine* e, int discrete, size_t b0 = 0) {
   return {e->slot_dev + b0, e->slot_dev + e->B + b0};
 }
 
+// The allowed-action sets as the slice from env slot b0 on sees them ({null, 0} without a mask: the unmasked kernels).
+HeadMask head_mask(const lram_engine* e, size_t b0 = 0) {
+  if (e->mask_dev == nullptr) return {};
+  return {e->mask_dev + b0 * (size_t)e->mask_words, e->mask_words};
+}
+// A discrete = 1 call reads [0, n_discrete) on every slot: refused, before anything is launched, while some slot allows nothing there.
+void check_head_mask(const lram_engine* e, int discrete, const std::string& w) {
+  LRAM_REQUIRE(!(discrete == 1 && e->mask_no_discrete_at >= 0),
+               w + ": the action mask (lram_set_action_mask) allows slot " + std::to_string(e->mask_no_discrete_at) +
+                   " nothing below n_discrete: a discrete = 1 call would leave it an empty sub-row");
+}
+
 // What every score launch of a call shares: the head's geometry, the sink's tensors, the slot table of a per-slot call.
 ScoreArgs score_args(const lram_engine* e, const ScoreSink& k, int discrete) {
   ScoreArgs a;
@@ -315,7 +327,7 @@ void score_chunk(lram_engine* e, const ScoreSink& k, const Slice& x, float* scra
     ScoreArgs a = score_args(e, k, discrete);
     a.logits = scratch, a.ld = nlog, a.row0 = (int64_t)x.b0 * Lc + beg, a.rows = nr;
     a.inner = Lc, a.outer = L, a.off = l0, a.start = ctx_start;
-    launch_action_score(a, x.s);
+    launch_action_score(a, x.s, head_mask(e));
   }
 }
 
@@ -346,7 +358,7 @@ void action_head(lram_engine* e, const Pass& pass, const std::vector<Slice>& sl,
       ScoreArgs a = score_args(e, *sink, discrete);
       a.logits = e->LOGITS.p + b0 * nlog, a.ld = nlog, a.row0 = (int64_t)b0, a.rows = x.nb;
       a.inner = 1, a.outer = L, a.off = L - 1, a.start = ctx_start;
-      launch_action_score(a, x.s);
+      launch_action_score(a, x.s, head_mask(e));
       continue;
     }
     const float* logits = e->LOGITS.p + b0 * nlog;
@@ -357,10 +369,10 @@ void action_head(lram_engine* e, const Pass& pass, const std::vector<Slice>& sl,
       SampleArgs sp = e->sample;
       sp.slot0 += b0, sp.draw = e->sample_draw;
       launch_action_sample(logits, act, tok, x.nb, geom, slots, discrete, col_begin, col_end, sp,
-                           e->sample_slots_dev ? e->sample_slots_dev + b0 : nullptr, x.s);
+                           e->sample_slots_dev ? e->sample_slots_dev + b0 : nullptr, x.s, head_mask(e, b0));
       continue;
     }
-    launch_action_argmax(logits, act, tok, x.nb, geom, slots, discrete, col_begin, col_end, x.s);
+    launch_action_argmax(logits, act, tok, x.nb, geom, slots, discrete, col_begin, col_end, x.s, head_mask(e, b0));
   }
 }
 
@@ -544,6 +556,7 @@ void check_head_mode(const lram_engine* e, int discrete, const char* who) {
   // (n_discrete = 0 is a legal geometry -- the reference's dmcontrol head -- but an argmax over no logits is no action)
   LRAM_REQUIRE(discrete != 1 || e->cfg.n_discrete >= 1, std::string(who) + ": a discrete head needs n_discrete >= 1");
   check_sample_slots(e, discrete, who);
+  check_head_mask(e, discrete, who);
   if (discrete != LRAM_HEAD_PER_SLOT) return;
   const std::string w(who);
   LRAM_REQUIRE(e->slot_table, w + ": LRAM_HEAD_PER_SLOT needs a slot table (lram_set_slot_table)");
@@ -622,6 +635,7 @@ void check_score_sink(const lram_engine* e, const char* who, int discrete, const
   LRAM_REQUIRE(discrete == 0 || discrete == 1 || discrete == LRAM_HEAD_PER_SLOT, w + ": discrete must be 0, 1 or LRAM_HEAD_PER_SLOT");
   LRAM_REQUIRE(discrete != LRAM_HEAD_PER_SLOT || e->slot_table, w + ": LRAM_HEAD_PER_SLOT needs a slot table (lram_set_slot_table)");
   LRAM_REQUIRE(discrete != 1 || e->cfg.n_discrete >= 1, w + ": a discrete head needs n_discrete >= 1");
+  check_head_mask(e, discrete, w);
 }
 
 // The length rules of a call of L timesteps over B contexts of per-env length: every length in 0 .. L, not all of them 0.
@@ -861,6 +875,24 @@ FramesCall frames_call(lram_engine* e, const char* who, const uint8_t* dev_frame
   if (host_lengths != nullptr) fc.rc.reset(new RaggedCall{e, w, timesteps, host_lengths, {}, append != 0});
   return fc;
 }
+
+// lram_score_tokens and lram_score_tokens_masked: the scoring head's row code on caller logits; `who` names the entry called.
+void score_tokens_call(const char* who, const float* dev_logits, int64_t rows, const HeadGeom& geom, int discrete,
+                       const float* dev_target_actions, const int32_t* dev_target_tokens, const uint8_t* dev_valid, int over,
+                       double temperature, float* dev_actions, int32_t* dev_tokens, float* dev_logp, const HeadMask& mask,
+                       void* stream) {
+  const std::string w(who);
+  LRAM_REQUIRE(dev_logits != nullptr, w + ": null device pointer");
+  LRAM_REQUIRE(discrete == 0 || discrete == 1, w + ": discrete must be 0 or 1");
+  ScoreArgs a;
+  a.logits = dev_logits, a.ld = (int64_t)geom.act_dim * geom.n_vocab, a.rows = rows;
+  a.geom = geom;
+  a.discrete = discrete, a.over = over, a.temperature = temperature;
+  a.target_actions = dev_target_actions, a.target_tokens = dev_target_tokens, a.valid = dev_valid;
+  a.actions = dev_actions, a.tokens = dev_tokens, a.logp = dev_logp;
+  launch_action_score(a, static_cast<hipStream_t>(stream), mask);
+}
+
 }  // namespace
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------
@@ -1071,9 +1103,10 @@ int32_t lram_score_last(lram_engine* e, const int32_t* dev_tokens, int32_t over,
                  "lram_score_last: the last call was per-slot and the slot table has been cleared since");
     ScoreSink sink;
     sink.logp = dev_logp, sink.target_tokens = dev_tokens, sink.over = over, sink.temperature = temperature;
+    check_head_mask(e, e->last_head, "lram_score_last");
     ScoreArgs a = score_args(e, sink, e->last_head);
     a.logits = e->LOGITS.p, a.ld = (int64_t)e->cfg.act_dim * e->cfg.n_vocab, a.rows = e->n_live;
-    launch_action_score(a, static_cast<hipStream_t>(stream));
+    launch_action_score(a, static_cast<hipStream_t>(stream), head_mask(e));
   });
 }
 
@@ -1095,9 +1128,10 @@ int32_t lram_score_last_sampled(lram_engine* e, const int32_t* dev_tokens, float
     LRAM_REQUIRE(!(head == LRAM_HEAD_PER_SLOT && e->sample_slots.empty() && e->slot_has_discrete &&
                    e->sample.top_k > e->cfg.n_discrete),
                  "lram_score_last_sampled: sampling top_k exceeds n_discrete and the slot table holds a discrete slot");
+    check_head_mask(e, head, "lram_score_last_sampled");
     // (deterministic: no uniform is read, the draw counter is neither read nor advanced)
     launch_action_logp(e->LOGITS.p, dev_tokens, dev_logp, e->n_live, head_geom(e->cfg), head_slots(e, head), head, e->sample,
-                       e->sample_slots_dev, static_cast<hipStream_t>(stream));
+                       e->sample_slots_dev, static_cast<hipStream_t>(stream), head_mask(e));
   });
 }
 
@@ -1117,20 +1151,47 @@ int32_t lram_sample_rows(const float* dev_logits, int64_t rows, int32_t n, int64
   });
 }
 
+int32_t lram_sample_rows_masked(const float* dev_logits, int64_t rows, int32_t n, int64_t ld, const uint8_t* dev_mode,
+                                const double* dev_temperature, const int32_t* dev_top_k, const double* dev_top_p,
+                                const double* dev_uniform, const int32_t* dev_tokens_in, int32_t* dev_tokens_out,
+                                float* dev_logp_out, const uint32_t* dev_mask, int32_t words, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(dev_logits && dev_mode && dev_temperature && dev_top_k && dev_top_p && dev_mask,
+                 "lram_sample_rows_masked: null device pointer");
+    LRAM_REQUIRE((dev_uniform == nullptr) == (dev_tokens_out == nullptr),
+                 "lram_sample_rows_masked: dev_uniform and dev_tokens_out go together");
+    LRAM_REQUIRE((dev_tokens_in == nullptr) == (dev_logp_out == nullptr),
+                 "lram_sample_rows_masked: dev_tokens_in and dev_logp_out go together");
+    LRAM_REQUIRE(dev_tokens_out || dev_logp_out, "lram_sample_rows_masked: neither a draw nor a score is asked for");
+    LRAM_REQUIRE(ld == 0 || ld >= n, "lram_sample_rows_masked: ld must be 0 (one shared row) or >= n");
+    LRAM_REQUIRE(n >= 1 && words == (n + 31) / 32, "lram_sample_rows_masked: words must be ceil(n / 32)");
+    launch_sample_rows(dev_logits, rows, n, ld, dev_mode, dev_temperature, dev_top_k, dev_top_p, dev_uniform, dev_tokens_in,
+                       dev_tokens_out, dev_logp_out, static_cast<hipStream_t>(stream), HeadMask{dev_mask, words});
+  });
+}
+
 int32_t lram_score_tokens(const float* dev_logits, int64_t rows, int32_t act_dim, int32_t n_vocab, int32_t n_discrete,
                           int32_t action_channels, float tok_min, float tok_max, int32_t discrete, const float* dev_target_actions,
                           const int32_t* dev_target_tokens, const uint8_t* dev_valid, int32_t over, double temperature,
                           float* dev_actions, int32_t* dev_tokens, float* dev_logp, void* stream) {
   return guarded([&] {
-    LRAM_REQUIRE(dev_logits != nullptr, "lram_score_tokens: null device pointer");
-    LRAM_REQUIRE(discrete == 0 || discrete == 1, "lram_score_tokens: discrete must be 0 or 1");
-    ScoreArgs a;
-    a.logits = dev_logits, a.ld = (int64_t)act_dim * n_vocab, a.rows = rows;
-    a.geom = {act_dim, n_vocab, n_discrete, action_channels, tok_min, tok_max};
-    a.discrete = discrete, a.over = over, a.temperature = temperature;
-    a.target_actions = dev_target_actions, a.target_tokens = dev_target_tokens, a.valid = dev_valid;
-    a.actions = dev_actions, a.tokens = dev_tokens, a.logp = dev_logp;
-    launch_action_score(a, static_cast<hipStream_t>(stream));
+    score_tokens_call("lram_score_tokens", dev_logits, rows, {act_dim, n_vocab, n_discrete, action_channels, tok_min, tok_max},
+                      discrete, dev_target_actions, dev_target_tokens, dev_valid, over, temperature, dev_actions, dev_tokens,
+                      dev_logp, HeadMask{}, stream);
+  });
+}
+
+int32_t lram_score_tokens_masked(const float* dev_logits, int64_t rows, int32_t act_dim, int32_t n_vocab, int32_t n_discrete,
+                                 int32_t action_channels, float tok_min, float tok_max, int32_t discrete,
+                                 const float* dev_target_actions, const int32_t* dev_target_tokens, const uint8_t* dev_valid,
+                                 int32_t over, double temperature, float* dev_actions, int32_t* dev_tokens, float* dev_logp,
+                                 const uint32_t* dev_mask, int32_t words, void* stream) {
+  return guarded([&] {
+    LRAM_REQUIRE(dev_mask != nullptr, "lram_score_tokens_masked: null device pointer (dev_mask)");
+    LRAM_REQUIRE(words == (n_vocab + 31) / 32, "lram_score_tokens_masked: words must be ceil(n_vocab / 32)");
+    score_tokens_call("lram_score_tokens_masked", dev_logits, rows, {act_dim, n_vocab, n_discrete, action_channels, tok_min, tok_max},
+                      discrete, dev_target_actions, dev_target_tokens, dev_valid, over, temperature, dev_actions, dev_tokens,
+                      dev_logp, HeadMask{dev_mask, words}, stream);
   });
 }
 

@@ -84,17 +84,24 @@ __device__ __forceinline__ uint32_t wave_select(const uint32_t (&key)[PER], int 
 // takes the argmax rule instead: greedy (a per-slot setting), a NaN in the row, a maximum of +-inf, or nothing left.
 // (The body runs INSIDE the branch that computed the support: ballots and shuffles pin the control flow, so a second branch
 // on the same condition would not be merged with the first.)
-template <int PER, class Body>
+// MASK (w = the env slot's allowed set, `words` words): the row is its sub-row -- a disallowed entry is padding like one from
+// n on (v = -inf, the last key, never kept: invisible, a NaN included), and the quantile ranks the m allowed values.
+template <int PER, bool MASK = false, class Body>
 __device__ __forceinline__ bool with_row_support(const float* row, int n, int top_k, double top_p, int lane, bool greedy,
-                                                 Body&& body) {
+                                                 Body&& body, const uint32_t* w = nullptr, int words = 0) {
   float v[PER];
   float vmax = -INFINITY;
   uint32_t key[PER];
   bool nan_here = false;
+  uint32_t allow = (1u << PER) - 1u;
+  if constexpr (MASK) allow = mask_lane_bits<PER>(w, words, lane);
 #pragma unroll
   for (int j = 0; j < PER; ++j) {
     const int i = lane * PER + j;
-    v[j] = i < n ? row[i] + 0.f : -INFINITY;  // (-0 -> +0: one key per value)
+    if constexpr (MASK)
+      v[j] = (i < n && ((allow >> j) & 1u)) ? row[i] + 0.f : -INFINITY;
+    else
+      v[j] = i < n ? row[i] + 0.f : -INFINITY;  // (-0 -> +0: one key per value)
     nan_here |= v[j] != v[j];
     vmax = fmaxf(vmax, v[j]);
   }
@@ -105,12 +112,14 @@ __device__ __forceinline__ bool with_row_support(const float* row, int n, int to
     uint32_t keep = 0;  // bit j: entry j of this lane is in the support
 #pragma unroll
   for (int j = 0; j < PER; ++j) {
-    const bool valid = lane * PER + j < n;
+    const bool valid = lane * PER + j < n && (!MASK || ((allow >> j) & 1u));
     key[j] = valid ? order_key(v[j]) : 0xffffffffu;  // padding sorts last
     keep |= (valid ? 1u : 0u) << j;
   }
   if (top_p > 0.0) {
-    const double rank = top_p * (double)(n - 1);
+    int m = n;  // the values the quantile ranks: the sub-row's (wave-uniform; >= 1 here: its maximum is finite)
+    if constexpr (MASK) m = mask_count(w, words, n, lane);
+    const double rank = top_p * (double)(m - 1);
     const int lo = (int)floor(rank), hi = (int)ceil(rank);
     const double wgt = rank - (double)lo;
     const uint32_t klo = wave_select<PER>(key, lo);
@@ -191,11 +200,11 @@ __device__ __forceinline__ double wave_scan_f64(double inc, int lane) {
 }
 
 // The draw.  Returns the token (wave-uniform); greedy (a per-slot setting, wave-uniform): the argmax rule at once.
-template <int PER>
+template <int PER, bool MASK = false>
 __device__ __forceinline__ int sample_row(const float* row, int n, double temperature, int top_k, double top_p, double u,
-                                          int lane, bool greedy = false) {
+                                          int lane, bool greedy = false, const uint32_t* w = nullptr, int words = 0) {
   int token = 0x7fffffff;
-  const bool plain = with_row_support<PER>(row, n, top_k, top_p, lane, greedy, [&](const float (&v)[PER], float vmax, uint32_t keep) {
+  const bool plain = with_row_support<PER, MASK>(row, n, top_k, top_p, lane, greedy, [&](const float (&v)[PER], float vmax, uint32_t keep) {
     double w[PER];
     const double inc = wave_scan_f64(row_weights<PER>(v, vmax, keep, temperature, w), lane);
     const double total = __shfl(inc, 63, 64);
@@ -221,19 +230,23 @@ __device__ __forceinline__ int sample_row(const float* row, int n, double temper
     }
     token = first;
     return false;
-  });
-  if (plain) token = row_argmax(row, n, lane);
+  }, w, words);
+  if constexpr (MASK) {
+    if (plain) token = row_argmax_masked(row, n, lane, w);
+  } else {
+    if (plain) token = row_argmax(row, n, lane);
+  }
   return token;
 }
 
 // log of the probability with which sample_row returns `tok` (wave-uniform) from this row under these settings:
 // t * (x_tok - max) - log(sum over the support of exp(t * (x - max))), fp64 throughout; the caller rounds once to fp32.
 // Outside 0 .. n - 1 or outside the support: -inf.  A row on the argmax rule: 0 at the argmax token, -inf elsewhere.
-template <int PER>
+template <int PER, bool MASK = false>
 __device__ __forceinline__ double logp_row(const float* row, int n, double temperature, int top_k, double top_p, int tok,
-                                           int lane, bool greedy) {
+                                           int lane, bool greedy, const uint32_t* w = nullptr, int words = 0) {
   double lp = -(double)INFINITY;
-  const bool plain = with_row_support<PER>(row, n, top_k, top_p, lane, greedy, [&](const float (&v)[PER], float vmax, uint32_t keep) {
+  const bool plain = with_row_support<PER, MASK>(row, n, top_k, top_p, lane, greedy, [&](const float (&v)[PER], float vmax, uint32_t keep) {
     double w[PER], z = -(double)INFINITY;
     const double loc = row_weights<PER>(v, vmax, keep, temperature, w);
 #pragma unroll
@@ -246,8 +259,12 @@ __device__ __forceinline__ double logp_row(const float* row, int n, double tempe
       lp = z - log(total);           // (the support holds the maximum: total >= 1; a support of one entry gives 0 - log(1))
     }
     return false;
-  });
-  if (plain) lp = tok == row_argmax(row, n, lane) ? 0.0 : -(double)INFINITY;
+  }, w, words);
+  if constexpr (MASK) {
+    if (plain) lp = tok == row_argmax_masked(row, n, lane, w) ? 0.0 : -(double)INFINITY;
+  } else {
+    if (plain) lp = tok == row_argmax(row, n, lane) ? 0.0 : -(double)INFINITY;
+  }
   return lp;
 }
 
@@ -278,8 +295,10 @@ __device__ __forceinline__ void store_action(int64_t o, int tok, int discrete, c
 
 // The greedy head: first index of the row's maximum (torch.argmax rule), then inv_tokenize.  Nothing is staged: the row is
 // walked once in global memory, and a wave without work returns at once.
-__global__ __launch_bounds__(256) void action_argmax_kernel(const float* logits, float* actions, int32_t* tokens, int B,
-                                                            HeadGeom g, HeadSlots s, int discrete, int col_begin, int col_end) {
+template <bool MASK>
+__device__ __forceinline__ void action_argmax_body(const float* logits, float* actions, int32_t* tokens, int B, const HeadGeom& g,
+                                                   const HeadSlots& s, int discrete, int col_begin, int col_end,
+                                                   const HeadMask& mask) {
   const int lane = threadIdx.x & 63;
   const StepItem it = step_item(B, g, s, discrete, col_begin, col_end);
   if (!it.live) return;
@@ -289,18 +308,35 @@ __global__ __launch_bounds__(256) void action_argmax_kernel(const float* logits,
     if (lane == 0) store_fill(o, tokens, actions, nullptr);
     return;
   }
-  const int tok = row_argmax(logits + o * g.n_vocab, col.n, lane);
+  int tok;
+  if constexpr (MASK)
+    tok = row_argmax_masked(logits + o * g.n_vocab, col.n, lane, mask_words(mask, it.b));
+  else
+    tok = row_argmax(logits + o * g.n_vocab, col.n, lane);
   if (lane == 0) store_action(o, tok, col.discrete, g, tokens, actions);
+}
+__global__ __launch_bounds__(256) void action_argmax_kernel(const float* logits, float* actions, int32_t* tokens, int B,
+                                                            HeadGeom g, HeadSlots s, int discrete, int col_begin, int col_end) {
+  action_argmax_body<false>(logits, actions, tokens, B, g, s, discrete, col_begin, col_end, HeadMask{});
+}
+// Its twin under allowed sets (mask.bits starts at the launch's first env slot): the walk over the sub-row.
+__global__ __launch_bounds__(256) void action_argmax_masked_kernel(const float* logits, float* actions, int32_t* tokens, int B,
+                                                                   HeadGeom g, HeadSlots s, int discrete, int col_begin,
+                                                                   int col_end, HeadMask mask) {
+  action_argmax_body<true>(logits, actions, tokens, B, g, s, discrete, col_begin, col_end, mask);
 }
 
 // Its sampling counterpart, same grid.  sp.draw is read, never written, here: sample_advance_kernel bumps it once per env-step
 // behind every head launch of that step.
 // SLOTS: the settings come from the per-slot table (lram_set_sampling_slots; `slots` starts at the launch's first env slot)
 // instead of sp's scalars -- a compile-time split, so that the launch without a table is the code it was before the table.
-template <int PER, bool SLOTS>
+// MASK: the env slot's allowed set (mask.bits starts at the launch's first env slot, like `slots`); the masked kernel reads the
+// settings from the table where one is given and from sp's scalars otherwise (one instance per PER: it is not the hot launch).
+template <int PER, bool SLOTS, bool MASK = false>
 __device__ __forceinline__ void action_sample_body(float (&stage)[4][64 * PER], const float* logits, float* actions,
                                                    int32_t* tokens, int B, const HeadGeom& g, const HeadSlots& s, int discrete,
-                                                   int col_begin, int col_end, const SampleArgs& sp, const SampleSlot* slots) {
+                                                   int col_begin, int col_end, const SampleArgs& sp, const SampleSlot* slots,
+                                                   const HeadMask& mask = {}) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const StepItem it = step_item(B, g, s, discrete, col_begin, col_end);
   const int b = it.b, j = it.j;
@@ -313,7 +349,17 @@ __device__ __forceinline__ void action_sample_body(float (&stage)[4][64 * PER], 
   if (!active) return;
   const double u = philox_uniform(sp.seed, sp.slot0 + (uint64_t)b, (uint32_t)j, *sp.draw);
   int tok;
-  if constexpr (SLOTS) {  // the env slot's own settings (wave-uniform, like the slot table's entry)
+  if constexpr (MASK) {
+    double t = sp.temperature, p = sp.top_p;
+    int k = sp.top_k;
+    bool greedy = false;
+    if (slots != nullptr) {
+      const SampleSlot st = slots[b];
+      t = st.temperature, p = st.top_p, k = st.top_k, greedy = st.mode == 0;
+    }
+    tok = sample_row<PER, true>(stage[wv], col.n, uniform_f64(t), uniform_i32(k), uniform_f64(p), u, lane,
+                                uniform_i32(greedy) != 0, mask_words(mask, b), mask.words);
+  } else if constexpr (SLOTS) {  // the env slot's own settings (wave-uniform, like the slot table's entry)
     const SampleSlot st = slots[b];
     tok = sample_row<PER>(stage[wv], col.n, st.temperature, st.top_k, st.top_p, u, lane, st.mode == 0);
   } else {
@@ -338,14 +384,22 @@ __global__ __launch_bounds__(256) void action_sample_slots_kernel(const float* l
   action_sample_body<PER, true>(stage, logits, actions, tokens, B, g, s, discrete, col_begin, col_end, sp, slots);
 }
 
+template <int PER>
+__global__ __launch_bounds__(256) void action_sample_masked_kernel(const float* logits, float* actions, int32_t* tokens, int B,
+                                                                   HeadGeom g, HeadSlots s, int discrete, int col_begin,
+                                                                   int col_end, SampleArgs sp, const SampleSlot* slots,
+                                                                   HeadMask mask) {
+  __shared__ float stage[4][64 * PER];
+  action_sample_body<PER, false, true>(stage, logits, actions, tokens, B, g, s, discrete, col_begin, col_end, sp, slots, mask);
+}
+
 // log-probabilities of given tokens under the distribution the head above draws from: always act_dim columns per env (as
 // action_score_kernel), same rows, same settings -- sp's scalars, or the per-slot table where `slots` is given.
 // Columns the head does not use and token -1 get the fill value 0.
-template <int PER>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void action_logp_kernel(
-    const float* logits, const int32_t* tokens, float* logp, int B, HeadGeom g, HeadSlots s, int discrete, SampleArgs sp,
-    const SampleSlot* slots) {
-  __shared__ float stage[4][64 * PER];
+template <int PER, bool MASK>
+__device__ __forceinline__ void action_logp_body(float (&stage)[4][64 * PER], const float* logits, const int32_t* tokens,
+                                                 float* logp, int B, const HeadGeom& g, const HeadSlots& s, int discrete,
+                                                 const SampleArgs& sp, const SampleSlot* slots, const HeadMask& mask) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int item = blockIdx.x * 4 + wv;
   const int b = item / g.act_dim, j = item - b * g.act_dim;
@@ -369,9 +423,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void a
     const SampleSlot st = slots[b];
     temperature = st.temperature, top_p = st.top_p, top_k = st.top_k, greedy = st.mode == 0;
   }
-  const double lp = logp_row<PER>(stage[wv], col.n, uniform_f64(temperature), uniform_i32(top_k), uniform_f64(top_p),
-                                 uniform_i32(tok), lane, uniform_i32(greedy) != 0);
+  double lp;
+  if constexpr (MASK)
+    lp = logp_row<PER, true>(stage[wv], col.n, uniform_f64(temperature), uniform_i32(top_k), uniform_f64(top_p),
+                             uniform_i32(tok), lane, uniform_i32(greedy) != 0, mask_words(mask, b), mask.words);
+  else
+    lp = logp_row<PER>(stage[wv], col.n, uniform_f64(temperature), uniform_i32(top_k), uniform_f64(top_p),
+                       uniform_i32(tok), lane, uniform_i32(greedy) != 0);
   if (lane == 0) logp[o] = (float)lp;
+}
+template <int PER>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void action_logp_kernel(
+    const float* logits, const int32_t* tokens, float* logp, int B, HeadGeom g, HeadSlots s, int discrete, SampleArgs sp,
+    const SampleSlot* slots) {
+  __shared__ float stage[4][64 * PER];
+  action_logp_body<PER, false>(stage, logits, tokens, logp, B, g, s, discrete, sp, slots, HeadMask{});
+}
+template <int PER>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void action_logp_masked_kernel(
+    const float* logits, const int32_t* tokens, float* logp, int B, HeadGeom g, HeadSlots s, int discrete, SampleArgs sp,
+    const SampleSlot* slots, HeadMask mask) {
+  __shared__ float stage[4][64 * PER];
+  action_logp_body<PER, true>(stage, logits, tokens, logp, B, g, s, discrete, sp, slots, mask);
 }
 
 __global__ void sample_advance_kernel(uint64_t* draw) {
@@ -395,29 +468,50 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* logits,
 
 // Test / evidence entry with per-row settings (device arrays of length rows): draws (uniform -> tokens_out) and / or
 // log-probabilities of given tokens (tokens_in -> logp_out; token -1: the fill value 0) through the row code of the head.
+template <int PER, bool MASK>
+__device__ __forceinline__ void sample_rows_body(float (&stage)[4][64 * PER], const float* logits, int64_t rows, int n, int64_t ld,
+                                                 const uint8_t* mode, const double* temperature, const int32_t* top_k,
+                                                 const double* top_p, const double* uniform, const int32_t* tokens_in,
+                                                 int32_t* tokens_out, float* logp_out, const HeadMask& mask) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t r = (int64_t)blockIdx.x * 4 + wv;
+  const bool active = r < rows;
+  stage_row<PER>(stage[wv], logits + (active ? r : 0) * ld, n, lane, active);
+  if (!active) return;
+  double t = temperature[r], p = top_p[r];
+  int k = top_k[r];
+  bool greedy = mode[r] == 0;
+  const uint32_t* w = nullptr;
+  if constexpr (MASK) {  // row r's own set; the row's settings are wave-uniform: scalar registers, as in action_logp_kernel
+    w = mask_words(mask, r);
+    t = uniform_f64(t), p = uniform_f64(p), k = uniform_i32(k), greedy = uniform_i32(greedy) != 0;
+  }
+  if (tokens_out != nullptr) {
+    const int tok = sample_row<PER, MASK>(stage[wv], n, t, k, p, uniform[r], lane, greedy, w, mask.words);
+    if (lane == 0) tokens_out[r] = tok;
+  }
+  if (logp_out != nullptr) {
+    const int tok = tokens_in[r];
+    const double lp = tok == -1 ? 0.0 : logp_row<PER, MASK>(stage[wv], n, t, k, p, tok, lane, greedy, w, mask.words);
+    if (lane == 0) logp_out[r] = (float)lp;
+  }
+}
 template <int PER>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void sample_rows_kernel(const float* logits, int64_t rows, int n, int64_t ld,
                                                           const uint8_t* mode, const double* temperature, const int32_t* top_k,
                                                           const double* top_p, const double* uniform, const int32_t* tokens_in,
                                                           int32_t* tokens_out, float* logp_out) {
   __shared__ float stage[4][64 * PER];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t r = (int64_t)blockIdx.x * 4 + wv;
-  const bool active = r < rows;
-  stage_row<PER>(stage[wv], logits + (active ? r : 0) * ld, n, lane, active);
-  if (!active) return;
-  const double t = temperature[r], p = top_p[r];
-  const int k = top_k[r];
-  const bool greedy = mode[r] == 0;
-  if (tokens_out != nullptr) {
-    const int tok = sample_row<PER>(stage[wv], n, t, k, p, uniform[r], lane, greedy);
-    if (lane == 0) tokens_out[r] = tok;
-  }
-  if (logp_out != nullptr) {
-    const int tok = tokens_in[r];
-    const double lp = tok == -1 ? 0.0 : logp_row<PER>(stage[wv], n, t, k, p, tok, lane, greedy);
-    if (lane == 0) logp_out[r] = (float)lp;
-  }
+  sample_rows_body<PER, false>(stage, logits, rows, n, ld, mode, temperature, top_k, top_p, uniform, tokens_in, tokens_out, logp_out,
+                               HeadMask{});
+}
+template <int PER>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void sample_rows_masked_kernel(
+    const float* logits, int64_t rows, int n, int64_t ld, const uint8_t* mode, const double* temperature, const int32_t* top_k,
+    const double* top_p, const double* uniform, const int32_t* tokens_in, int32_t* tokens_out, float* logp_out, HeadMask mask) {
+  __shared__ float stage[4][64 * PER];
+  sample_rows_body<PER, true>(stage, logits, rows, n, ld, mode, temperature, top_k, top_p, uniform, tokens_in, tokens_out, logp_out,
+                              mask);
 }
 
 __global__ __launch_bounds__(256) void sample_uniforms_kernel(uint64_t seed, uint64_t slot_base, int64_t n_slots,
@@ -431,18 +525,23 @@ __global__ __launch_bounds__(256) void sample_uniforms_kernel(uint64_t seed, uin
 }  // namespace
 
 void launch_action_argmax(const float* logits, float* actions, int32_t* tokens, int B, const HeadGeom& g, const HeadSlots& s,
-                          int discrete, int col_begin, int col_end, hipStream_t stream) {
+                          int discrete, int col_begin, int col_end, hipStream_t stream, const HeadMask& mask) {
   LRAM_REQUIRE((s.flags == nullptr) == (s.act == nullptr), "action head: the slot table's two arrays go together");
+  LRAM_REQUIRE(mask.bits == nullptr || mask.words == (g.n_vocab + 31) / 32, "action head: the mask holds ceil(n_vocab / 32) words per slot");
   // with a slot table: one wave per (env, action dim) over all act_dim columns, the head mode is read per env slot
   const int items = B * step_columns(g, s, discrete);
-  hipLaunchKernelGGL(action_argmax_kernel, dim3((items + 3) / 4), dim3(256), 0, stream, logits, actions, tokens, B, g, s,
-                     discrete, col_begin, col_end);
+  if (mask.bits != nullptr)
+    hipLaunchKernelGGL(action_argmax_masked_kernel, dim3((items + 3) / 4), dim3(256), 0, stream, logits, actions, tokens, B, g, s,
+                       discrete, col_begin, col_end, mask);
+  else
+    hipLaunchKernelGGL(action_argmax_kernel, dim3((items + 3) / 4), dim3(256), 0, stream, logits, actions, tokens, B, g, s,
+                       discrete, col_begin, col_end);
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
 void launch_action_sample(const float* logits, float* actions, int32_t* tokens, int B, const HeadGeom& g, const HeadSlots& s,
                           int discrete, int col_begin, int col_end, const SampleArgs& sp, const SampleSlot* slots,
-                          hipStream_t stream) {
+                          hipStream_t stream, const HeadMask& mask) {
   LRAM_REQUIRE((s.flags == nullptr) == (s.act == nullptr), "action sampling: the slot table's two arrays go together");
   const bool per_slot = s.flags != nullptr;
   // with a slot table the rows of one launch differ in length: PER comes from the largest, n_vocab (the engine has checked
@@ -454,8 +553,13 @@ void launch_action_sample(const float* logits, float* actions, int32_t* tokens, 
   LRAM_REQUIRE(sp.draw != nullptr, "action sampling: no draw counter");
   const int items = B * step_columns(g, s, discrete);
   const dim3 grid((items + 3) / 4), block(256);
+  LRAM_REQUIRE(mask.bits == nullptr || mask.words == (g.n_vocab + 31) / 32,
+               "action sampling: the mask holds ceil(n_vocab / 32) words per slot");
   with_per(n, [&](auto per) {
-    if (slots == nullptr)
+    if (mask.bits != nullptr)
+      hipLaunchKernelGGL(action_sample_masked_kernel<decltype(per)::value>, grid, block, 0, stream, logits, actions, tokens, B, g, s,
+                         discrete, col_begin, col_end, sp, slots, mask);
+    else if (slots == nullptr)
       hipLaunchKernelGGL(action_sample_kernel<decltype(per)::value>, grid, block, 0, stream, logits, actions, tokens, B, g, s, discrete,
                          col_begin, col_end, sp);
     else
@@ -466,15 +570,20 @@ void launch_action_sample(const float* logits, float* actions, int32_t* tokens, 
 }
 
 void launch_action_logp(const float* logits, const int32_t* tokens, float* logp, int B, const HeadGeom& g, const HeadSlots& s,
-                        int discrete, const SampleArgs& sp, const SampleSlot* slots, hipStream_t stream) {
+                        int discrete, const SampleArgs& sp, const SampleSlot* slots, hipStream_t stream, const HeadMask& mask) {
   LRAM_REQUIRE((s.flags == nullptr) == (s.act == nullptr), "action logp: the slot table's two arrays go together");
   LRAM_REQUIRE(logits && tokens && logp && B >= 1 && g.act_dim >= 1, "action logp: bad arguments");
   const int n = (discrete && s.flags == nullptr) ? g.n_discrete : g.n_vocab;
   LRAM_REQUIRE(n >= 1 && n <= kSampleMaxRow && g.n_discrete <= g.n_vocab, "action logp: a row holds 1 .. 512 logits");
   LRAM_REQUIRE(slots != nullptr || sp.top_k <= n, "action logp: top_k exceeds the number of logits of the head in use");
   const dim3 grid((B * g.act_dim + 3) / 4), block(256);
+  LRAM_REQUIRE(mask.bits == nullptr || mask.words == (g.n_vocab + 31) / 32, "action logp: the mask holds ceil(n_vocab / 32) words per slot");
   with_per(n, [&](auto per) {
-    hipLaunchKernelGGL(action_logp_kernel<decltype(per)::value>, grid, block, 0, stream, logits, tokens, logp, B, g, s, discrete, sp, slots);
+    if (mask.bits != nullptr)
+      hipLaunchKernelGGL(action_logp_masked_kernel<decltype(per)::value>, grid, block, 0, stream, logits, tokens, logp, B, g, s,
+                         discrete, sp, slots, mask);
+    else
+      hipLaunchKernelGGL(action_logp_kernel<decltype(per)::value>, grid, block, 0, stream, logits, tokens, logp, B, g, s, discrete, sp, slots);
   });
   LRAM_HIP_CHECK(hipGetLastError());
 }
@@ -498,13 +607,18 @@ void launch_sample_tokens(const float* logits, int64_t rows, int n, int64_t ld, 
 
 void launch_sample_rows(const float* logits, int64_t rows, int n, int64_t ld, const uint8_t* mode, const double* temperature,
                         const int32_t* top_k, const double* top_p, const double* uniform, const int32_t* tokens_in,
-                        int32_t* tokens_out, float* logp_out, hipStream_t stream) {
+                        int32_t* tokens_out, float* logp_out, hipStream_t stream, const HeadMask& mask) {
   LRAM_REQUIRE(n >= 1 && n <= kSampleMaxRow, "sample rows: a row holds 1 .. 512 logits");
   LRAM_REQUIRE(rows >= 1 && rows <= ((int64_t)1 << 32), "sample rows: rows must be in 1 .. 2^32");
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  LRAM_REQUIRE(mask.bits == nullptr || mask.words == (n + 31) / 32, "sample rows: the mask holds ceil(n / 32) words per row");
   with_per(n, [&](auto per) {
-    hipLaunchKernelGGL(sample_rows_kernel<decltype(per)::value>, grid, block, 0, stream, logits, rows, n, ld, mode, temperature, top_k, top_p,
-                       uniform, tokens_in, tokens_out, logp_out);
+    if (mask.bits != nullptr)
+      hipLaunchKernelGGL(sample_rows_masked_kernel<decltype(per)::value>, grid, block, 0, stream, logits, rows, n, ld, mode, temperature,
+                         top_k, top_p, uniform, tokens_in, tokens_out, logp_out, mask);
+    else
+      hipLaunchKernelGGL(sample_rows_kernel<decltype(per)::value>, grid, block, 0, stream, logits, rows, n, ld, mode, temperature, top_k, top_p,
+                         uniform, tokens_in, tokens_out, logp_out);
   });
   LRAM_HIP_CHECK(hipGetLastError());
 }

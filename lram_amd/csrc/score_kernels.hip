@@ -73,8 +73,11 @@ __device__ __forceinline__ ScoreItem score_item_ragged(const ScoreArgs& a) {
 }
 
 // PER floats per lane in the wave's LDS strip; PER = 0: no strip, the row stays in global memory.
-template <int PER>
-__device__ __forceinline__ void score_row(const ScoreArgs& a, const ScoreItem& it, float (*stage)[64 * (PER > 0 ? PER : 1)]) {
+// MASK (`mask`, the env's allowed set): the greedy token is the argmax of the sub-row; with over = 1 the maximum, the NaN flag and
+// the sum run over the sub-row too and a target outside it scores -inf; with over = 0 the normalisation is what it is without a mask.
+template <int PER, bool MASK>
+__device__ __forceinline__ void score_row(const ScoreArgs& a, const ScoreItem& it, float (*stage)[64 * (PER > 0 ? PER : 1)],
+                                          const HeadMask& mask = {}) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const HeadGeom& g = a.geom;
   const int64_t o = it.orow * g.act_dim + it.j;
@@ -104,11 +107,21 @@ __device__ __forceinline__ void score_row(const ScoreArgs& a, const ScoreItem& i
   float best = -INFINITY, vmax = -INFINITY;
   int bi = 0x7fffffff;
   bool nan_here = false;
+  const uint32_t* w = nullptr;
+  if constexpr (MASK) w = mask_words(mask, it.env);
+  const bool sub = MASK && a.over;  // the normalisation runs over the sub-row (wave-uniform)
   for (int i = lane; i < nnorm; i += 64) {
     const float x = row[i];
-    nan_here |= x != x;
-    vmax = fmaxf(vmax, x);
-    argmax_take(x, i, best, bi, i < nsel);
+    if constexpr (MASK) {
+      const bool in = i < nsel && mask_allows(w, i), cnt = in || !sub;
+      nan_here |= cnt && x != x;
+      vmax = cnt ? fmaxf(vmax, x) : vmax;
+      argmax_take(x, i, best, bi, in);
+    } else {
+      nan_here |= x != x;
+      vmax = fmaxf(vmax, x);
+      argmax_take(x, i, best, bi, i < nsel);
+    }
   }
   wave_argmax(best, bi, &vmax);
   const bool has_nan = __any(nan_here);
@@ -130,11 +143,18 @@ __device__ __forceinline__ void score_row(const ScoreArgs& a, const ScoreItem& i
   // (t > 0 and rounding is monotone: the maximum of t * x is t * max x)
   const double zmax = a.temperature * (double)vmax;
   double sum = 0.0;
-  for (int i = lane; i < nnorm; i += 64) sum += exp(scaled_minus(a.temperature, row[i], zmax));
+  if constexpr (MASK) {
+    for (int i = lane; i < nnorm; i += 64)
+      if (!sub || mask_allows(w, i)) sum += exp(scaled_minus(a.temperature, row[i], zmax));
+  } else {
+    for (int i = lane; i < nnorm; i += 64) sum += exp(scaled_minus(a.temperature, row[i], zmax));
+  }
   sum = wave_sum_f64(sum);
   if (lane == 0) {
     float lp;
-    if (tgt < 0 || tgt >= nnorm)
+    bool outside = tgt < 0 || tgt >= nnorm;
+    if constexpr (MASK) outside = outside || (sub && !mask_allows(w, tgt));   // (read behind the range test: tgt is in 0 .. nnorm - 1)
+    if (outside)
       lp = -INFINITY;
     else if (has_nan)
       lp = __builtin_nanf("");
@@ -147,19 +167,30 @@ __device__ __forceinline__ void score_row(const ScoreArgs& a, const ScoreItem& i
 template <int PER>
 __global__ __launch_bounds__(256) void action_score_kernel(ScoreArgs a) {
   __shared__ float stage[4][64 * (PER > 0 ? PER : 1)];
-  score_row<PER>(a, score_item(a), stage);
+  score_row<PER, false>(a, score_item(a), stage);
+}
+// Its twin under allowed sets: a compile-time split, the kernel above is the code it was and takes the arguments it took.
+template <int PER>
+__global__ __launch_bounds__(256) void action_score_masked_kernel(ScoreArgs a, HeadMask mask) {
+  __shared__ float stage[4][64 * (PER > 0 ? PER : 1)];
+  score_row<PER, true>(a, score_item(a), stage, mask);
 }
 
 // Ragged score sink (lram_score_ragged): the row code above, the rows placed by score_item_ragged.
 template <int PER>
 __global__ __launch_bounds__(256) void action_score_ragged_kernel(ScoreArgs a) {
   __shared__ float stage[4][64 * (PER > 0 ? PER : 1)];
-  score_row<PER>(a, score_item_ragged(a), stage);
+  score_row<PER, false>(a, score_item_ragged(a), stage);
+}
+template <int PER>
+__global__ __launch_bounds__(256) void action_score_ragged_masked_kernel(ScoreArgs a, HeadMask mask) {
+  __shared__ float stage[4][64 * (PER > 0 ? PER : 1)];
+  score_row<PER, true>(a, score_item_ragged(a), stage, mask);
 }
 
 }  // namespace
 
-void launch_action_score(const ScoreArgs& a, hipStream_t stream) {
+void launch_action_score(const ScoreArgs& a, hipStream_t stream, const HeadMask& mask) {
   LRAM_REQUIRE(a.logits != nullptr && a.rows >= 1 && a.inner >= 1, "action score: bad rows");
   const HeadGeom& g = a.geom;
   LRAM_REQUIRE(g.act_dim >= 1 && g.n_vocab >= 1 && g.n_discrete >= 0 && g.n_discrete <= g.n_vocab && g.action_channels >= 1,
@@ -178,11 +209,20 @@ void launch_action_score(const ScoreArgs& a, hipStream_t stream) {
   const int64_t items = a.rows * a.geom.act_dim;
   LRAM_REQUIRE(items <= ((int64_t)1 << 32), "action score: rows * act_dim must be <= 2^32");
   const dim3 grid((unsigned)((items + 3) / 4)), block(256);
+  LRAM_REQUIRE(mask.bits == nullptr || mask.words == (g.n_vocab + 31) / 32,
+               "action score: the mask holds ceil(n_vocab / 32) words per env");
   auto launch = [&](auto per) {
-    if (a.start != nullptr)
-      hipLaunchKernelGGL(action_score_ragged_kernel<decltype(per)::value>, grid, block, 0, stream, a);
-    else
-      hipLaunchKernelGGL(action_score_kernel<decltype(per)::value>, grid, block, 0, stream, a);
+    constexpr int P = decltype(per)::value;
+    if (mask.bits != nullptr) {
+      if (a.start != nullptr)
+        hipLaunchKernelGGL(action_score_ragged_masked_kernel<P>, grid, block, 0, stream, a, mask);
+      else
+        hipLaunchKernelGGL(action_score_masked_kernel<P>, grid, block, 0, stream, a, mask);
+    } else if (a.start != nullptr) {
+      hipLaunchKernelGGL(action_score_ragged_kernel<P>, grid, block, 0, stream, a);
+    } else {
+      hipLaunchKernelGGL(action_score_kernel<P>, grid, block, 0, stream, a);
+    }
   };
   if (a.geom.n_vocab > kSampleMaxRow)
     launch(std::integral_constant<int, 0>{});  // not staged: walked in global memory

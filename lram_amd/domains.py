@@ -28,8 +28,20 @@ class Domain:
     # sample_from_logits' keywords for this domain, completed with its defaults and checked against THIS domain's head width;
     # "greedy" = argmax for this domain whatever the agent samples elsewhere
     a_sample_kwargs: object = None
+    # the actions this domain's envs have: action indices below n_discrete for a discrete domain (Procgen: range(15); Pong on its
+    # minimal set: 0, 1, 3, 4, 11, 12), vocabulary token ids for a continuous one; None = every token of the head's range
+    allowed_actions: Optional[Sequence[int]] = None
 
     def __post_init__(self):
+        if self.allowed_actions is not None:
+            acts = list(self.allowed_actions)
+            if not acts:
+                raise ValueError(f"domain {self.name!r}: allowed_actions is empty (None allows everything)")
+            if any(isinstance(a, bool) or int(a) != a or a < 0 for a in acts):
+                raise ValueError(f"domain {self.name!r}: allowed_actions must be integers >= 0, got {acts}")
+            if len(set(int(a) for a in acts)) != len(acts):
+                raise ValueError(f"domain {self.name!r}: allowed_actions lists an action twice: {acts}")
+            object.__setattr__(self, "allowed_actions", tuple(int(a) for a in acts))
         s = self.a_sample_kwargs
         if not (s is None or isinstance(s, dict) or s == "greedy"):
             raise ValueError(f"domain {self.name!r}: a_sample_kwargs must be None, a dict or \"greedy\", got {s!r}")
@@ -116,6 +128,26 @@ class SlotTable:
         return {"temperature": per_slot("temperature", 1.0, torch.float64), "top_k": per_slot("top_k", 0, torch.int32),
                 "top_p": per_slot("top_p", 0.0, torch.float64),
                 "greedy": torch.repeat_interleave(torch.tensor([s is None for s in per_domain], dtype=torch.bool), rep)}
+
+    def action_mask(self, n_vocab: int, n_discrete: int) -> Optional[torch.Tensor]:
+        """The allowed sets of the layout, bool [B, n_vocab] (the argument of Engine.set_action_mask), or None when no domain
+        states one.  A domain without a set allows every token.  Every index is checked against the domain's range: below
+        n_discrete for a discrete domain, below n_vocab otherwise."""
+        if all(d.allowed_actions is None for d in self.domains):
+            return None
+        rows = []
+        for d in self.domains:
+            row = torch.ones(int(n_vocab), dtype=torch.bool)
+            if d.allowed_actions is not None:
+                n = int(n_discrete) if d.discrete else int(n_vocab)
+                bad = [a for a in d.allowed_actions if a >= n]
+                if bad:
+                    raise ValueError(f"domain {d.name!r}: allowed_actions {bad} outside the {n} "
+                                     f"{'actions of the discrete head' if d.discrete else 'tokens of the vocabulary'}")
+                row = torch.zeros(int(n_vocab), dtype=torch.bool)
+                row[list(d.allowed_actions)] = True
+            rows.append(row)
+        return torch.repeat_interleave(torch.stack(rows), torch.tensor(self.counts), dim=0)
 
     @property
     def n_image(self) -> int:

@@ -143,6 +143,13 @@ _SYMBOLS = {
     "lram_slstm_counts": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]),
     "lram_set_slot_table": (ctypes.c_int32, [_VP, _VP, _VP]),
     "lram_get_slot_table": (ctypes.c_int32, [_VP, _VP, _VP, ctypes.POINTER(ctypes.c_int32)]),
+    "lram_set_action_mask": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32]),
+    "lram_get_action_mask": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+    "lram_sample_rows_masked": (ctypes.c_int32, [_VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, _VP, _VP, _VP, _VP, _VP,
+                                                 _VP, _VP, _VP, _VP, ctypes.c_int32, _VP]),
+    "lram_score_tokens_masked": (ctypes.c_int32, [_VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                  ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_int32, _VP, _VP, _VP,
+                                                  ctypes.c_int32, ctypes.c_double, _VP, _VP, _VP, _VP, ctypes.c_int32, _VP]),
     "lram_step_slots": (ctypes.c_int32, [_VP, _VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP,
                                          _VP]),
     "lram_pad_obs_slots": (ctypes.c_int32, [_VP, ctypes.c_int32, _VP, _VP, _VP, _VP, ctypes.c_int32, _VP, ctypes.c_int32,
@@ -311,6 +318,58 @@ def check_swap_lists(a, b, batch: int):
     return a, b
 
 
+def pack_action_mask(allowed) -> torch.Tensor:
+    """bool [rows, n] (tensor or array) -> int32 [rows, ceil(n / 32)] on the CPU holding the uint32 words of
+    lram_set_action_mask: bit t & 31 of word t >> 5 = token t is allowed."""
+    a = torch.as_tensor(allowed).to("cpu")
+    if a.dim() != 2 or a.shape[1] < 1:
+        raise ValueError(f"action mask: expected a 2-d bool array [rows, n], got shape {tuple(a.shape)}")
+    if a.dtype != torch.bool:
+        if a.dtype.is_floating_point or a.dtype.is_complex or bool(((a != 0) & (a != 1)).any()):
+            raise ValueError(f"action mask: expected bools (or 0 / 1 integers), got {a.dtype}")
+        a = a != 0
+    rows, n = a.shape
+    words = (n + 31) // 32
+    padded = torch.zeros(rows, words * 32, dtype=torch.int64)
+    padded[:, :n] = a
+    w = (padded.view(rows, words, 32) << torch.arange(32, dtype=torch.int64)).sum(-1)   # 0 .. 2^32 - 1
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32).contiguous()
+
+
+def unpack_action_mask(words: torch.Tensor, n: int) -> torch.Tensor:
+    """The inverse: int32 / uint32 words [rows, ceil(n / 32)] -> bool [rows, n]."""
+    w = torch.as_tensor(words).to("cpu").to(torch.int64) & 0xFFFFFFFF
+    if w.dim() != 2 or w.shape[1] != (int(n) + 31) // 32:
+        raise ValueError(f"action mask words: expected [rows, {(int(n) + 31) // 32}], got shape {tuple(w.shape)}")
+    bits = (w.unsqueeze(-1) >> torch.arange(32, dtype=torch.int64)) & 1
+    return bits.reshape(w.shape[0], -1)[:, :int(n)].bool().contiguous()
+
+
+def check_action_mask(mask, batch: int, n_vocab: int, n_discrete: int, slot_discrete=None) -> torch.Tensor:
+    """The refusal rules of lram_set_action_mask on the host: `mask` bool [batch, n_vocab]; every slot must allow something
+    inside its selectable range -- [0, n_discrete) where slot_discrete[b] (the slot table's head mode), [0, n_vocab) otherwise
+    and without a table.  Returns the mask as a CPU bool tensor; raises ValueError."""
+    m = torch.as_tensor(mask).to("cpu")
+    if m.dim() != 2 or tuple(m.shape) != (int(batch), int(n_vocab)):
+        raise ValueError(f"action mask: expected bool [{batch}, {n_vocab}] (one row per env slot), got shape {tuple(m.shape)}")
+    if m.dtype != torch.bool:
+        if m.dtype.is_floating_point or m.dtype.is_complex or bool(((m != 0) & (m != 1)).any()):
+            raise ValueError(f"action mask: expected bools (or 0 / 1 integers), got {m.dtype}")
+        m = m != 0
+    disc = torch.zeros(int(batch), dtype=torch.bool)
+    if slot_discrete is not None:
+        disc = torch.as_tensor(slot_discrete).to("cpu").reshape(-1).bool()
+        if disc.numel() != int(batch):
+            raise ValueError(f"slot_discrete: expected {batch} entries (one per env slot), got {disc.numel()}")
+        if bool(disc.any()) and int(n_discrete) < 1:
+            raise ValueError("slot_discrete: a discrete slot needs n_discrete >= 1")
+    count = torch.where(disc, m[:, :int(n_discrete)].sum(1), m.sum(1))
+    empty = torch.nonzero(count == 0).reshape(-1)
+    if empty.numel():
+        raise ValueError(f"action mask: slot {int(empty[0])} allows nothing inside its selectable range")
+    return m.contiguous()
+
+
 def _i32_array(values):
     return (ctypes.c_int32 * max(1, len(values)))(*values)
 
@@ -446,6 +505,7 @@ class Engine:
         self._live = self.batch
         self._context_rows = "all"   # (lram_state_alloc sets the mode back)
         self._slot_image = None      # host copy of the slot table's image column (a new allocation drops the table)
+        self._mask_words = None      # keeps the packed words of set_action_mask alive during the call (the engine copies them)
         self._n_img_live = 0         # image slots below `live`: the frames step_slots is handed
         B, A = self.batch, self.spec.act_dim
         # zeroed: a discrete head writes column 0 only, and the columns it leaves alone must not depend on what the allocator
@@ -513,6 +573,30 @@ class Engine:
                                                       ctypes.c_void_p(acts.data_ptr())))
         self._slot_image = i.bool().clone()
         self._n_img_live = int(self._slot_image[:self._live].sum())
+
+    def set_action_mask(self, allowed):
+        """Allowed-action sets (lram_set_action_mask): bool [batch, n_vocab] (tensor or array), allowed[b, t] = env slot b may
+        take vocabulary token t; None clears the mask.  Every head kernel then works on the slot's sub-row: the argmax, a
+        draw, its log-probability and over="selectable" scores; over="vocab" and raw logits are unchanged.  The sets stay
+        with the slot index.  Synchronises and drops a captured graph: not a hot-path call."""
+        if allowed is None:
+            _check(self.lib, self.lib.lram_set_action_mask(self._h, None, 0))
+            return
+        spec = self.spec
+        table = self.slot_table()
+        m = check_action_mask(allowed, self.batch, spec.n_vocab, spec.n_discrete, None if table is None else table["discrete"])
+        self._mask_words = pack_action_mask(m)
+        _check(self.lib, self.lib.lram_set_action_mask(self._h, ctypes.c_void_p(self._mask_words.data_ptr()),
+                                                       int(self._mask_words.shape[1])))
+
+    @property
+    def action_mask(self) -> Optional[torch.Tensor]:
+        """The mask in effect (lram_get_action_mask): bool [batch, n_vocab] on the CPU, or None."""
+        on = ctypes.c_int32(0)
+        words = torch.zeros(self.batch, (self.spec.n_vocab + 31) // 32, dtype=torch.int32)
+        _check(self.lib, self.lib.lram_get_action_mask(self._h, ctypes.c_void_p(words.data_ptr()), int(words.shape[1]),
+                                                       ctypes.byref(on)))
+        return unpack_action_mask(words, self.spec.n_vocab) if on.value else None
 
     def slot_table(self) -> Optional[dict]:
         """The table in effect (lram_get_slot_table): {"discrete": bool [B], "act_dim": int64 [B], "image": bool [B],
@@ -1187,11 +1271,18 @@ def slot_setting_arrays(n: int, temperature=1.0, top_k=0, top_p=0.0, greedy=Fals
     return out
 
 
+def _mask_words_dev(mask, rows: int, n: int, device) -> torch.Tensor:
+    """bool [rows, n] with no empty row -> its packed words on `device` (the dev_mask of the *_masked row entries)."""
+    m = check_action_mask(mask, rows, n, 0)
+    return pack_action_mask(m).to(device)
+
+
 def sample_rows(logits: torch.Tensor, *, temperature=1.0, top_k=0, top_p=0.0, greedy=False,
-                uniform: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None):
+                uniform: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None, mask=None):
     """The sampling head's row code with per-row settings on caller data (lram_sample_rows): logits float32 [R, n]; the
     settings scalars or arrays of length R.  uniform float64 [R] -> the drawn tokens int32 [R]; tokens int32 [R] -> their
-    log-probabilities float32 [R] under the row's filtered distribution.  Returns (drawn, logp), None where not asked for."""
+    log-probabilities float32 [R] under the row's filtered distribution.  Returns (drawn, logp), None where not asked for.
+    mask bool [R, n]: row r works on its allowed sub-row (lram_sample_rows_masked; every row must allow something)."""
     lib = load_library()
     if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
         raise ValueError("logits must be float32 [rows, n] with contiguous rows")
@@ -1216,6 +1307,12 @@ def sample_rows(logits: torch.Tensor, *, temperature=1.0, top_k=0, top_p=0.0, gr
     if tokens is not None:
         _chk_dev(tokens, torch.int32, (R,), dev, "tokens")
         logp = torch.empty(R, dtype=torch.float32, device=dev)
+    if mask is not None:
+        words = _mask_words_dev(mask, R, n, dev)
+        _check(lib, lib.lram_sample_rows_masked(_ptr(logits), R, int(n), int(logits.stride(0)), _ptr(mode), _ptr(t), _ptr(k),
+                                                _ptr(p), _ptr(uniform), _ptr(tokens), _ptr(drawn), _ptr(logp), _ptr(words),
+                                                int(words.shape[1]), _stream_ptr(dev)))
+        return drawn, logp
     _check(lib, lib.lram_sample_rows(_ptr(logits), R, int(n), int(logits.stride(0)), _ptr(mode), _ptr(t), _ptr(k), _ptr(p),
                                      _ptr(uniform), _ptr(tokens), _ptr(drawn), _ptr(logp), _stream_ptr(dev)))
     return drawn, logp
@@ -1223,9 +1320,11 @@ def sample_rows(logits: torch.Tensor, *, temperature=1.0, top_k=0, top_p=0.0, gr
 
 def score_tokens(logits: torch.Tensor, spec_or_dims, *, actions: Optional[torch.Tensor] = None,
                  tokens: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None, discrete: bool = False,
-                 over: str = "vocab", temperature: float = 1.0, want=("actions", "tokens", "logp")) -> ScoreResult:
+                 over: str = "vocab", temperature: float = 1.0, want=("actions", "tokens", "logp"), mask=None) -> ScoreResult:
     """The scoring head's device code on caller logits (lram_score_tokens): logits float32 [R, act_dim, n_vocab];
-    `spec_or_dims` a ModelSpec or (n_discrete, action_channels); targets / valid / outputs per row as Engine.score."""
+    `spec_or_dims` a ModelSpec or (n_discrete, action_channels); targets / valid / outputs per row as Engine.score.
+    mask bool [R, n_vocab]: row r's allowed set (lram_score_tokens_masked); it must allow something inside the row's
+    selectable range."""
     lib = load_library()
     if logits.dim() != 3 or logits.dtype != torch.float32 or not logits.is_contiguous():
         raise ValueError("logits must be a contiguous float32 tensor [rows, act_dim, n_vocab]")
@@ -1247,6 +1346,14 @@ def score_tokens(logits: torch.Tensor, spec_or_dims, *, actions: Optional[torch.
     res = ScoreResult(actions=torch.zeros(R, A, dtype=torch.float32, device=dev) if "actions" in want else None,
                       tokens=torch.zeros(R, A, dtype=torch.int32, device=dev) if "tokens" in want else None,
                       logp=torch.zeros(R, A, dtype=torch.float32, device=dev) if "logp" in want else None)
+    if mask is not None:
+        m = check_action_mask(mask, R, V, n_discrete, torch.full((R,), bool(discrete)))
+        words = pack_action_mask(m).to(dev)
+        _check(lib, lib.lram_score_tokens_masked(_ptr(logits), R, A, V, n_discrete, channels, -1.0, 1.0, int(bool(discrete)),
+                                                 _ptr(actions), _ptr(tokens), _ptr(valid), _over_mode(over), float(temperature),
+                                                 _ptr(res.actions), _ptr(res.tokens), _ptr(res.logp), _ptr(words),
+                                                 int(words.shape[1]), _stream_ptr(dev)))
+        return res
     _check(lib, lib.lram_score_tokens(_ptr(logits), R, A, V, n_discrete, channels, -1.0, 1.0, int(bool(discrete)),
                                       _ptr(actions), _ptr(tokens), _ptr(valid), _over_mode(over), float(temperature),
                                       _ptr(res.actions), _ptr(res.tokens), _ptr(res.logp), _stream_ptr(dev)))
