@@ -6,7 +6,10 @@
 //   engine_streams.hip  events, env slices, fork / join, the profiler                          (calls nothing)
 //   engine_xlstm.hip    the xLSTM stack and the lazy matrix memory's host side                 (calls gemm, streams)
 //   engine_mamba.hip    the Mamba stack                                                        (calls gemm, streams)
-//   engine_step.hip     image / token front end, action head, the step, prefill and score entries (calls the stacks, gemm, streams)
+//   engine_image.hip    the IMPALA-CNN image front end, its buffers, the frame list                (calls gemm)
+//   engine_head.hip     the action head, its refusals, the entries that run the head alone        (calls gemm)
+//   engine_step.hip     token front end, the chunk loop, the env-step and encoder entries          (calls the stacks, image, head, gemm, streams)
+//   engine_context.hip  stored contexts: the chunk plan, the one body of the eight entries         (calls step, image, head, state)
 //   engine_state.hip    reset, export / import, the slot table and the per-slot state calls
 #pragma once
 #include <algorithm>
@@ -158,7 +161,7 @@ struct lram_engine {
   // IMG_ROWS [N, D] (the dispatcher picks its kernel by row count: per-tile launches would make the embeddings depend on the
   // tile), then ReLU + placement.  IMG_LIST: the {src, dst} pairs, int32 [N][2].  All grown outside the launches, as SEQ_EMB is.
   DevBuf IMG_FLAT, IMG_ROWS, IMG_LIST;
-  // LRAM_IMG_TILE (capped per frame size: frame_tile() in engine_step.hip).  206M, 64 envs x 512 timesteps of 64 x 64 frames, one
+  // LRAM_IMG_TILE (capped per frame size: frame_tile() in engine_image.hip).  206M, 64 envs x 512 timesteps of 64 x 64 frames, one
   // job: the CNN's share of lram_prefill_frames at tiles of 128 / 256 / 512 / 1024 / 2048 frames 126.6 / 74.3 / 57.1 / 48.6 / 46.1 ms
   // (the whole call 350.7 ms at 2048, 0.74 % ahead of 1024; profiles/image_contexts.txt).  The buffers follow the list: a call of
   // fewer frames than the tile allocates for its own number.
@@ -474,7 +477,7 @@ struct Slice {
   hipStream_t s;
 };
 
-// What one call hands down to the kernels' launch sequence: built on the stack by the entry (step_launches, timesteps_launches,
+// What one call hands down to the kernels' launch sequence: built on the stack by the entry (step_launches, stored_context_call,
 // lram_encoder_step) and passed by const& through run_stack -> run_*_stack -> the block functions.  Nothing of it outlives the call.
 struct Pass {
   // what the caller handed in
@@ -510,7 +513,79 @@ struct ScoreSink {
   double temperature = 1.0;
 };
 
+// The (state, rtg, reward) inputs of a call: [B, L, .] / [B, L] row-major (L = 1: one env-step).
+struct Inputs {
+  const float* obs;
+  int emb;   // obs holds state-token embeddings [., d_model] instead of observations [., state_dim]
+  const float *rtg, *rew;
+  int L;
+  // stored contexts from frames (lram_prefill_frames / lram_score_frames): uint8 [n, L, C, H, W], n the image slots of the slot
+  // table in ascending order (no table: every env).  obs is then the [B, L, state_dim] rows of a mixed table's vector slots, or null.
+  const uint8_t* frames = nullptr;
+  int img_c = 0, img_h = 0, img_w = 0;
+};
+
+// Stored contexts of per-env length (the ragged and append entries): the contexts are end-aligned inside the call, env b
+// starting at call-timestep L - n_b, and the chunks are cut so that every env starts on a chunk boundary (context_plan in
+// engine_context.hip).  An env restarts at its own first timestep where its row of that chunk's mask says so; in an append call an
+// env that has not started by a chunk is held in it (Pass::hold).  Device pointers into lram_engine::CTX, filled on the call's
+// stream ahead of the first chunk.
+struct ContextPlan {
+  std::vector<int> starts;        // ascending call-timesteps at which the chunks start; the last chunk ends at L
+  // per chunk: some env is reset at its start / held in it (a chunk without one passes no pointer at all, as a dense call does)
+  std::vector<char> has_reset, has_hold;
+  // per chunk, LRAM_CONTEXT_ROWS_STARTED only (empty otherwise: every chunk runs all the call's rows): the chunk runs rows [0, rows[c])
+  std::vector<int> rows;
+  const int32_t* lengths = nullptr;                        // the caller's host array [B]
+  const int32_t* dev_start = nullptr;                      // [B]
+  const uint8_t *dev_masks = nullptr, *dev_hold = nullptr;   // [n_chunks, B] each
+};
+
+// One call of the (state, rtg, reward) front end, as its entry describes it: built on the entry's stack (an env-step: lram_step*;
+// a stored context: the eight entries of engine_context.hip) and read by const& from the chunk loop down to the head.  Either
+// `actions` / `tokens` take the action at the last timestep, or -- `scored` -- the sink takes the head's outputs at every timestep.
+struct Call {
+  const char* who;                   // the entry's name, in every message
+  Inputs in;
+  const uint8_t* reset = nullptr;    // device [rows] or null: who restarts before the first timestep
+  int discrete = 0;                  // head mode: 0, 1 or LRAM_HEAD_PER_SLOT
+  float* actions = nullptr;          // [rows, act_dim]; null in a stored context: no head at all (tokens is nullable on its own)
+  int32_t* tokens = nullptr;
+  bool scored = false;               // lram_score*: the head at every timestep into `sink`, nothing drawn
+  ScoreSink sink;
+  // stored contexts only
+  bool from_frames = false;          // an entry from frames: in.frames must be given
+  bool ragged = false;               // per-env lengths: host_lengths [rows] must be given (else every context has in.L timesteps)
+  const int32_t* host_lengths = nullptr;
+  int append = 0;                    // with lengths: 1 the contexts continue the slots' states, 0 they replace them
+  const ContextPlan* plan = nullptr; // the chunk plan while a call of per-env lengths is under way (set by stored_context_call)
+  const int32_t* ctx_start() const { return plan ? plan->dev_start : nullptr; }   // device [rows]: where every env's context begins
+};
+
+struct FrameCount {
+  int n_env;
+  int64_t frames;
+};
+
 extern thread_local std::string g_last_error;   // lram_last_error (defined in engine.hip)
+
+// Makes every listed buffer hold at least its number of floats: synchronises the device -- once -- only when one has to grow, then
+// runs `ahead` (what may still refuse the call) and allocates.  Never reached between a fork and a join.
+template <typename Ahead>
+void grow(std::initializer_list<std::pair<DevBuf*, size_t>> want, Ahead&& ahead) {
+  bool synced = false;
+  for (const auto& w : want) {
+    if (w.first->n >= w.second) continue;
+    if (!synced) {
+      LRAM_HIP_CHECK(hipDeviceSynchronize());
+      ahead();
+      synced = true;
+    }
+    w.first->alloc(w.second);
+  }
+}
+inline void grow(std::initializer_list<std::pair<DevBuf*, size_t>> want) { grow(want, [] {}); }
+inline void grow(DevBuf& b, size_t n) { grow({{&b, n}}); }
 
 // engine.hip
 void alloc_workspace(lram_engine* e, int tokens);
@@ -537,6 +612,26 @@ void join_slices(lram_engine* e, const std::vector<Slice>& sl, hipStream_t hbm, 
 // engine_state.hip
 void save_slot_records(lram_engine* e, const int32_t* host_slots, int n, float* dev_records, hipStream_t s);
 void load_slot_records(lram_engine* e, const int32_t* host_slots, int n, const float* dev_records, hipStream_t s);
+// engine_image.hip
+void check_frame_size(const lram_engine* e, int C, int H, int W, const char* who);
+void step_image_buffers(lram_engine* e, int C, int H, int W, const char* who);
+void embed_images(lram_engine* e, const uint8_t* images, int C, int H, int W, float* out, hipStream_t s, int b0, int nb);
+void check_frame_list(const lram_engine* e, int64_t N, const char* who);
+void frame_list_buffers(lram_engine* e, int C, int H, int W, int64_t N, const char* who);
+void embed_frame_list(lram_engine* e, const uint8_t* frames, int H, int W, int64_t N, float* out, hipStream_t s);
+// engine_head.hip
+void score_chunk(lram_engine* e, const Call& call, const Slice& x, float* scratch, int64_t cap, int l0, int Lc);
+void action_head(lram_engine* e, const Pass& pass, const Call& call, const std::vector<Slice>& sl, int Tc, int last_steps);
+void sample_draw_advance(lram_engine* e, hipStream_t s);
+void check_head_mode(const lram_engine* e, int discrete, const char* who);
+void check_score_sink(const lram_engine* e, const char* who, int discrete, const ScoreSink& k);
+// engine_step.hip
+bool compat_shares(const lram_engine* e, int discrete);
+void step_entry(lram_engine* e, const char* who);
+void require_all_live(const lram_engine* e, const char* who);
+void timesteps_launches(lram_engine* e, const Pass& base, const Call& call, hipStream_t s);
+// engine_context.hip
+FrameCount count_frames(const lram_engine* e, int L, const int32_t* lengths);
 // engine_xlstm.hip, engine_mamba.hip
 void lazy_materialize(lram_engine* e, hipStream_t s);
 void lazy_finish_prefold(lram_engine* e, hipStream_t s);

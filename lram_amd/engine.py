@@ -269,18 +269,23 @@ def _chk_dev(t: torch.Tensor, dtype, shape, device, name):
                          f"{t.dtype} {tuple(t.shape)} on {t.device} (contiguous={t.is_contiguous()})")
 
 
-def _slot_list(x, name: str):
-    """A list of env slot indices as plain ints (accepts lists, numpy arrays and integer tensors)."""
+def _int_list(x, name: str, what: str):
+    """A list, a numpy array or an integer tensor (moved to the host) as plain ints; `what` names its entries in the message."""
     if isinstance(x, torch.Tensor):
         if x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == torch.bool:
-            raise ValueError(f"{name}: expected integer slot indices, got {x.dtype}")
+            raise ValueError(f"{name}: expected integer {what}, got {x.dtype}")
         x = x.reshape(-1).tolist()
     out = []
     for v in x:
         if isinstance(v, bool) or int(v) != v:
-            raise ValueError(f"{name}: expected integer slot indices, got {v!r}")
+            raise ValueError(f"{name}: expected integer {what}, got {v!r}")
         out.append(int(v))
     return out
+
+
+def _slot_list(x, name: str):
+    """A list of env slot indices as plain ints."""
+    return _int_list(x, name, "slot indices")
 
 
 def check_slot_lists(src, dst, batch: int):
@@ -318,16 +323,22 @@ def check_swap_lists(a, b, batch: int):
     return a, b
 
 
+def _as_bools(a: torch.Tensor) -> torch.Tensor:
+    """A CPU tensor of bools, or of 0 / 1 integers, as bools."""
+    if a.dtype == torch.bool:
+        return a
+    if a.dtype.is_floating_point or a.dtype.is_complex or bool(((a != 0) & (a != 1)).any()):
+        raise ValueError(f"action mask: expected bools (or 0 / 1 integers), got {a.dtype}")
+    return a != 0
+
+
 def pack_action_mask(allowed) -> torch.Tensor:
     """bool [rows, n] (tensor or array) -> int32 [rows, ceil(n / 32)] on the CPU holding the uint32 words of
     lram_set_action_mask: bit t & 31 of word t >> 5 = token t is allowed."""
     a = torch.as_tensor(allowed).to("cpu")
     if a.dim() != 2 or a.shape[1] < 1:
         raise ValueError(f"action mask: expected a 2-d bool array [rows, n], got shape {tuple(a.shape)}")
-    if a.dtype != torch.bool:
-        if a.dtype.is_floating_point or a.dtype.is_complex or bool(((a != 0) & (a != 1)).any()):
-            raise ValueError(f"action mask: expected bools (or 0 / 1 integers), got {a.dtype}")
-        a = a != 0
+    a = _as_bools(a)
     rows, n = a.shape
     words = (n + 31) // 32
     padded = torch.zeros(rows, words * 32, dtype=torch.int64)
@@ -352,10 +363,7 @@ def check_action_mask(mask, batch: int, n_vocab: int, n_discrete: int, slot_disc
     m = torch.as_tensor(mask).to("cpu")
     if m.dim() != 2 or tuple(m.shape) != (int(batch), int(n_vocab)):
         raise ValueError(f"action mask: expected bool [{batch}, {n_vocab}] (one row per env slot), got shape {tuple(m.shape)}")
-    if m.dtype != torch.bool:
-        if m.dtype.is_floating_point or m.dtype.is_complex or bool(((m != 0) & (m != 1)).any()):
-            raise ValueError(f"action mask: expected bools (or 0 / 1 integers), got {m.dtype}")
-        m = m != 0
+    m = _as_bools(m)
     disc = torch.zeros(int(batch), dtype=torch.bool)
     if slot_discrete is not None:
         disc = torch.as_tensor(slot_discrete).to("cpu").reshape(-1).bool()
@@ -391,15 +399,7 @@ def check_context_lengths(lengths, batch: int, L: int):
     """The length rules of lram_prefill_ragged / lram_score_ragged, checked on the host (no GPU needed): `batch` integer
     entries (a list, a numpy array or an integer tensor, moved to the host), each in 0 .. L, not all 0.  Returns them as ints;
     raises ValueError."""
-    if isinstance(lengths, torch.Tensor):
-        if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
-            raise ValueError(f"lengths: expected integer lengths, got {lengths.dtype}")
-        lengths = lengths.reshape(-1).tolist()
-    out = []
-    for v in lengths:
-        if isinstance(v, bool) or int(v) != v:
-            raise ValueError(f"lengths: expected integer lengths, got {v!r}")
-        out.append(int(v))
+    out = _int_list(lengths, "lengths", "lengths")
     if len(out) != batch:
         raise ValueError(f"lengths: expected {batch} entries (one per env slot), got {len(out)}")
     for b, v in enumerate(out):
@@ -455,6 +455,43 @@ def context_plan(L: int, lengths, cap: int):
         n = -(-(hi - lo) // cap)
         starts.extend(range(lo, hi, -(-(hi - lo) // n)))
     return starts
+
+
+def _prefill_tail(eng, call, discrete, want_action: bool):
+    """What Engine.prefill() and prefill_frames() share behind their inputs: the action buffers of the call's rows (none unless
+    want_action), the call, the result."""
+    act = _context_rows_of(eng, eng._actions) if want_action else None
+    tok = _context_rows_of(eng, eng._tokens) if want_action else None
+    call(_head_mode(discrete), _ptr(act), _ptr(tok))
+    return (act, tok) if want_action else (None, None)
+
+
+def _score_tail(eng, context_call, actions, tokens, valid, discrete, over, temperature, want, logits) -> ScoreResult:
+    """What Engine.score() and score_frames() share: `want`, then the inputs (context_call() checks them and returns (L, call)),
+    the targets and `valid`, the zeroed ScoreResult, the call."""
+    B, A = _context_batch(eng), eng.spec.act_dim
+    want = (want,) if isinstance(want, str) else tuple(want)
+    for w in want:
+        if w not in ("actions", "tokens", "logp"):
+            raise ValueError(f'want: unknown output {w!r} (choose among "actions", "tokens", "logp")')
+    L, call = context_call()
+    if actions is not None:
+        _chk_dev(actions, torch.float32, (B, L, A), eng.device, "actions")
+    if tokens is not None:
+        _chk_dev(tokens, torch.int32, (B, L, A), eng.device, "tokens")
+    if valid is not None:
+        if valid.dtype == torch.bool:
+            valid = valid.to(torch.uint8)
+        _chk_dev(valid, torch.uint8, (B, L), eng.device, "valid")
+    # zeroed: the entries the call leaves alone (the logits of masked timesteps) must not depend on the allocator
+
+    def zeros(asked, dtype, *tail):
+        return torch.zeros(B, L, A, *tail, dtype=dtype, device=eng.device) if asked else None
+    res = ScoreResult(actions=zeros("actions" in want, torch.float32), tokens=zeros("tokens" in want, torch.int32),
+                      logp=zeros("logp" in want, torch.float32), logits=zeros(logits, torch.float32, eng.spec.n_vocab))
+    call(_head_mode(discrete), _ptr(actions), _ptr(tokens), _ptr(valid), _over_mode(over), float(temperature), _ptr(res.actions),
+         _ptr(res.tokens), _ptr(res.logp), _ptr(res.logits))
+    return res
 
 
 class Engine:
@@ -524,6 +561,20 @@ class Engine:
         _check(self.lib, self.lib.lram_reset(self._h, _ptr(env_mask), _stream_ptr(self.device)))
 
     # -- the hot path ----------------------------------------------------------------------------
+    def _step_io(self, rtg, reward, reset_mask, out_actions, out_tokens):
+        """What step(), step_images() and step_slots() share: checks rtg, reward and the reset mask of the live rows and
+        returns the checked output buffers (actions, tokens) -- the engine's own unless the caller handed some in."""
+        B, A = self._live, self.spec.act_dim
+        _chk_dev(rtg, torch.float32, (B,), self.device, "rtg")
+        _chk_dev(reward, torch.float32, (B,), self.device, "reward")
+        if reset_mask is not None:
+            _chk_dev(reset_mask, torch.uint8, (B,), self.device, "reset_mask")
+        actions = self._live_rows(self._actions) if out_actions is None else out_actions
+        tokens = self._live_rows(self._tokens) if out_tokens is None else out_tokens
+        _chk_dev(actions, torch.float32, (B, A), self.device, "out_actions")
+        _chk_dev(tokens, torch.int32, (B, A), self.device, "out_tokens")
+        return actions, tokens
+
     def step(self, obs: torch.Tensor, rtg: torch.Tensor, reward: torch.Tensor,
              reset_mask: Optional[torch.Tensor] = None, discrete=False, obs_is_embedding: bool = False,
              out_actions: Optional[torch.Tensor] = None, out_tokens: Optional[torch.Tensor] = None):
@@ -534,14 +585,7 @@ class Engine:
         every slot comes from the slot table (set_slot_table)."""
         B, spec = self._live, self.spec
         _chk_dev(obs, torch.float32, (B, spec.d_model if obs_is_embedding else spec.state_dim), self.device, "obs")
-        _chk_dev(rtg, torch.float32, (B,), self.device, "rtg")
-        _chk_dev(reward, torch.float32, (B,), self.device, "reward")
-        if reset_mask is not None:
-            _chk_dev(reset_mask, torch.uint8, (B,), self.device, "reset_mask")
-        actions = self._live_rows(self._actions) if out_actions is None else out_actions
-        tokens = self._live_rows(self._tokens) if out_tokens is None else out_tokens
-        _chk_dev(actions, torch.float32, (B, spec.act_dim), self.device, "out_actions")
-        _chk_dev(tokens, torch.int32, (B, spec.act_dim), self.device, "out_tokens")
+        actions, tokens = self._step_io(rtg, reward, reset_mask, out_actions, out_tokens)
         _check(self.lib, self.lib.lram_step(self._h, _ptr(obs), int(obs_is_embedding), _ptr(rtg), _ptr(reward),
                                             _ptr(reset_mask), _head_mode(discrete), _ptr(actions), _ptr(tokens),
                                             _stream_ptr(self.device)))
@@ -642,14 +686,7 @@ class Engine:
             c, h, w = (int(x) for x in images.shape[1:])
         elif images is not None and images.shape[0] != 0:
             raise ValueError(f"images: the slot table holds no image slot, got {images.shape[0]} frames")
-        _chk_dev(rtg, torch.float32, (B,), self.device, "rtg")
-        _chk_dev(reward, torch.float32, (B,), self.device, "reward")
-        if reset_mask is not None:
-            _chk_dev(reset_mask, torch.uint8, (B,), self.device, "reset_mask")
-        actions = self._live_rows(self._actions) if out_actions is None else out_actions
-        tokens = self._live_rows(self._tokens) if out_tokens is None else out_tokens
-        _chk_dev(actions, torch.float32, (B, spec.act_dim), self.device, "out_actions")
-        _chk_dev(tokens, torch.int32, (B, spec.act_dim), self.device, "out_tokens")
+        actions, tokens = self._step_io(rtg, reward, reset_mask, out_actions, out_tokens)
         _check(self.lib, self.lib.lram_step_slots(self._h, _ptr(obs), _ptr(images) if n_img > 0 else None, c, h, w, _ptr(rtg),
                                                   _ptr(reward), _ptr(reset_mask), _ptr(actions), _ptr(tokens),
                                                   _stream_ptr(self.device)))
@@ -714,10 +751,7 @@ class Engine:
         result as in prefill().  Bit-identical to prefill(embed_frames(frames), obs_is_embedding=True) for a dense call."""
         self._need_all_live("prefill_frames")
         _, call = self._frames_context_call("prefill", frames, obs_seq, rtg_seq, reward_seq, reset_mask, lengths, append)
-        act = _context_rows_of(self, self._actions) if want_action else None
-        tok = _context_rows_of(self, self._tokens) if want_action else None
-        call(_head_mode(discrete), _ptr(act), _ptr(tok))
-        return (act, tok) if want_action else (None, None)
+        return _prefill_tail(self, call, discrete, want_action)
 
     def score_frames(self, frames: torch.Tensor, rtg_seq: torch.Tensor, reward_seq: torch.Tensor, *,
                      obs_seq: Optional[torch.Tensor] = None, lengths=None, append=False,
@@ -728,29 +762,9 @@ class Engine:
         """score() from uint8 frames (lram_score_frames): `frames` / `obs_seq` as in prefill_frames(), everything else as in
         score()."""
         self._need_all_live("score_frames")
-        B, spec = _context_batch(self), self.spec
-        want = (want,) if isinstance(want, str) else tuple(want)
-        for w in want:
-            if w not in ("actions", "tokens", "logp"):
-                raise ValueError(f'want: unknown output {w!r} (choose among "actions", "tokens", "logp")')
-        L, call = self._frames_context_call("score", frames, obs_seq, rtg_seq, reward_seq, reset_mask, lengths, append)
-        if actions is not None:
-            _chk_dev(actions, torch.float32, (B, L, spec.act_dim), self.device, "actions")
-        if tokens is not None:
-            _chk_dev(tokens, torch.int32, (B, L, spec.act_dim), self.device, "tokens")
-        if valid is not None:
-            if valid.dtype == torch.bool:
-                valid = valid.to(torch.uint8)
-            _chk_dev(valid, torch.uint8, (B, L), self.device, "valid")
-        A = spec.act_dim
-        res = ScoreResult(
-            actions=torch.zeros(B, L, A, dtype=torch.float32, device=self.device) if "actions" in want else None,
-            tokens=torch.zeros(B, L, A, dtype=torch.int32, device=self.device) if "tokens" in want else None,
-            logp=torch.zeros(B, L, A, dtype=torch.float32, device=self.device) if "logp" in want else None,
-            logits=torch.zeros(B, L, A, spec.n_vocab, dtype=torch.float32, device=self.device) if logits else None)
-        call(_head_mode(discrete), _ptr(actions), _ptr(tokens), _ptr(valid), _over_mode(over), float(temperature), _ptr(res.actions),
-             _ptr(res.tokens), _ptr(res.logp), _ptr(res.logits))
-        return res
+        return _score_tail(self, lambda: self._frames_context_call("score", frames, obs_seq, rtg_seq, reward_seq, reset_mask, lengths,
+                                                                  append),
+                                actions, tokens, valid, discrete, over, temperature, want, logits)
 
     def prefill(self, obs_seq: torch.Tensor, rtg_seq: torch.Tensor, reward_seq: torch.Tensor,
                 reset_mask: Optional[torch.Tensor] = None, discrete=False, obs_is_embedding: bool = False,
@@ -766,10 +780,7 @@ class Engine:
         length 0 is held -- no kernel writes its state.  Without lengths, append changes nothing: the dense call."""
         self._need_all_live("prefill")
         L, call = self._stored_context_call("prefill", obs_seq, rtg_seq, reward_seq, reset_mask, obs_is_embedding, lengths, append)
-        act = _context_rows_of(self, self._actions) if want_action else None
-        tok = _context_rows_of(self, self._tokens) if want_action else None
-        call(_head_mode(discrete), _ptr(act), _ptr(tok))
-        return (act, tok) if want_action else (None, None)
+        return _prefill_tail(self, call, discrete, want_action)
 
     def score(self, obs_seq: torch.Tensor, rtg_seq: torch.Tensor, reward_seq: torch.Tensor, *,
               actions: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None,
@@ -787,32 +798,11 @@ class Engine:
         that of every env's own context.  `append=True` with lengths (lram_score_append): as in prefill() -- the contexts
         continue the slots' states, which is how a trajectory longer than one call is scored window by window."""
         self._need_all_live("score")
-        B, spec = _context_batch(self), self.spec
         if obs_seq.dim() != 3:
             raise ValueError("obs_seq must be [B, L, state_dim]")
-        want = (want,) if isinstance(want, str) else tuple(want)
-        for w in want:
-            if w not in ("actions", "tokens", "logp"):
-                raise ValueError(f'want: unknown output {w!r} (choose among "actions", "tokens", "logp")')
-        L, call = self._stored_context_call("score", obs_seq, rtg_seq, reward_seq, reset_mask, obs_is_embedding, lengths, append)
-        if actions is not None:
-            _chk_dev(actions, torch.float32, (B, L, spec.act_dim), self.device, "actions")
-        if tokens is not None:
-            _chk_dev(tokens, torch.int32, (B, L, spec.act_dim), self.device, "tokens")
-        if valid is not None:
-            if valid.dtype == torch.bool:
-                valid = valid.to(torch.uint8)
-            _chk_dev(valid, torch.uint8, (B, L), self.device, "valid")
-        A = spec.act_dim
-        # zeroed: the entries the call leaves alone (the logits of masked timesteps) must not depend on the allocator
-        res = ScoreResult(
-            actions=torch.zeros(B, L, A, dtype=torch.float32, device=self.device) if "actions" in want else None,
-            tokens=torch.zeros(B, L, A, dtype=torch.int32, device=self.device) if "tokens" in want else None,
-            logp=torch.zeros(B, L, A, dtype=torch.float32, device=self.device) if "logp" in want else None,
-            logits=torch.zeros(B, L, A, spec.n_vocab, dtype=torch.float32, device=self.device) if logits else None)
-        call(_head_mode(discrete), _ptr(actions), _ptr(tokens), _ptr(valid), _over_mode(over), float(temperature), _ptr(res.actions),
-             _ptr(res.tokens), _ptr(res.logp), _ptr(res.logits))
-        return res
+        return _score_tail(self, lambda: self._stored_context_call("score", obs_seq, rtg_seq, reward_seq, reset_mask, obs_is_embedding,
+                                                                  lengths, append),
+                                actions, tokens, valid, discrete, over, temperature, want, logits)
 
     def last_logp(self, tokens: torch.Tensor, over: str = "selectable", temperature: float = 1.0) -> torch.Tensor:
         """Log-probabilities float32 [B, act_dim] of `tokens` (int32 [B, act_dim]: what step / prefill just returned) under the
@@ -878,18 +868,10 @@ class Engine:
         """One env-step from uint8 frames [B, C, H, W]: embed_images + step(obs_is_embedding=True) as one call (the reference's
         forward embeds image states inside `compute_inputs`, online_decision_transformer_model.py:463-530).  Same results as the two
         calls; the CNN runs per env slice beside the step's observation-independent state-pass work."""
-        B, spec = self._live, self.spec
         if images.dim() != 4:
             raise ValueError("images must be [B, C, H, W]")
-        _chk_dev(images, torch.uint8, (B, *images.shape[1:]), self.device, "images")
-        _chk_dev(rtg, torch.float32, (B,), self.device, "rtg")
-        _chk_dev(reward, torch.float32, (B,), self.device, "reward")
-        if reset_mask is not None:
-            _chk_dev(reset_mask, torch.uint8, (B,), self.device, "reset_mask")
-        actions = self._live_rows(self._actions) if out_actions is None else out_actions
-        tokens = self._live_rows(self._tokens) if out_tokens is None else out_tokens
-        _chk_dev(actions, torch.float32, (B, spec.act_dim), self.device, "out_actions")
-        _chk_dev(tokens, torch.int32, (B, spec.act_dim), self.device, "out_tokens")
+        _chk_dev(images, torch.uint8, (self._live, *images.shape[1:]), self.device, "images")
+        actions, tokens = self._step_io(rtg, reward, reset_mask, out_actions, out_tokens)
         _check(self.lib, self.lib.lram_step_images(self._h, _ptr(images), int(images.shape[1]), int(images.shape[2]),
                                                    int(images.shape[3]), _ptr(rtg), _ptr(reward), _ptr(reset_mask),
                                                    _head_mode(discrete), _ptr(actions), _ptr(tokens), _stream_ptr(self.device)))

@@ -59,6 +59,16 @@ def test_null_engine_and_null_lengths_are_refused_with_a_message(hip_lib):
     assert hip_lib.lram_score_append(null, null, 0, null, null, 4, null, null, 0, null, null, null, 0, 1.0, null, null, null, null,
                                      null) != 0
     assert b"lram_score_append" in hip_lib.lram_last_error()
+    # ... as every stored-context entry does (one check for the eight of them, in their shared body), and the three env-step
+    # entries (step_entry); every argument null / 0, a temperature of 1
+    for name in ("lram_prefill", "lram_score", "lram_prefill_ragged", "lram_score_ragged", "lram_prefill_append",
+                 "lram_score_append", "lram_prefill_frames", "lram_score_frames", "lram_step", "lram_step_images",
+                 "lram_step_slots"):
+        args = [1.0 if t is ctypes.c_double else 0 if t is ctypes.c_int32 else null for t in engine._SYMBOLS[name][1]]
+        assert getattr(hip_lib, name)(*args) != 0, name
+        assert name.encode() + b":" in hip_lib.lram_last_error(), name
+        if name not in ("lram_step", "lram_step_images", "lram_step_slots"):
+            assert hip_lib.lram_last_error() == b"lram: " + name.encode() + b": null engine", name
     # (the library is shared by the session: a call that succeeds clears the thread's last error again)
     starts, n = (ctypes.c_int32 * 4)(), ctypes.c_int32()
     assert hip_lib.lram_context_plan(4, 2, (ctypes.c_int32 * 1)(4), 1, starts, 4, ctypes.byref(n)) == 0 and n.value == 2
@@ -67,10 +77,14 @@ def test_null_engine_and_null_lengths_are_refused_with_a_message(hip_lib):
     with pytest.raises((ValueError, TypeError)):
         engine.check_context_lengths(None, 3, 4)
     # ... and the library's check is the ragged entries' (RaggedCall::check), first thing behind the pointer checks
-    src = open(os.path.join(ROOT, "lram_amd", "csrc", "engine_step.hip")).read()
+    src = open(os.path.join(ROOT, "lram_amd", "csrc", "engine_context.hip")).read()
     assert 'LRAM_REQUIRE(lengths != nullptr, w + ": host_lengths is NULL")' in src
+    assert "if (c.ragged) rc.check(c.in.emb);" in src
+    # the append entries describe their call as kAppend, which is what sets Call::append (and makes the lengths mandatory)
     for name in ENTRIES:
-        assert 'RaggedCall rc{e, "%s", timesteps, host_lengths, {}, true};' % name in src, name
+        assert 'const Call c = vector_call("%s", kAppend, ' % name in src, name
+    assert "c.ragged = kind != kDense, c.host_lengths = host_lengths, c.append = kind == kAppend;" in src
+    assert "RaggedCall rc{e, w, c.in.L, c.host_lengths, c.append != 0, {}};" in src
 
 
 # ---- the agent calls, against a stand-in engine ------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """GPU: stored contexts from uint8 frames -- Engine.embed_frames / prefill_frames / score_frames (lram_embed_frames,
-lram_prefill_frames, lram_score_frames, lram_image_counts; the frame list in csrc/impala_cnn.hip and csrc/engine_step.hip) and the
+lram_prefill_frames, lram_score_frames, lram_image_counts; the frame list in csrc/impala_cnn.hip and csrc/engine_image.hip) and the
 agent calls on top of them.
 
 Shapes, the smallest at which the path can still go wrong: the image tests' model (xLSTM d_model 128, 2 blocks, sLSTM at 1,

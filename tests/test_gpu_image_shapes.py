@@ -1,4 +1,4 @@
-"""GPU: the image front end (csrc/impala_cnn.hip, `image_buffers` / `embed_images` in csrc/engine_step.hip) at frame sizes other
+"""GPU: the image front end (csrc/impala_cnn.hip, `image_buffers` / `embed_images` in csrc/engine_image.hip) at frame sizes other
 than 64 x 64, through lram_embed_images, lram_step_images and the image slots of lram_step_slots.
 
 At 64 x 64 the maps are 64 / 32 / 16 / 8 wide: whole numbers of conv tiles (16 x 16; 8 x 8 for 32-channel maps of at most 256
