@@ -645,6 +645,11 @@ int32_t lram_gemm_f16x2(const float* dev_a, int64_t lda, const float* dev_w, int
 int32_t lram_gemm_f16x2_presplit(const float* dev_a, int64_t lda, const float* dev_w, int64_t ldw, float* dev_c,
                                  int64_t ldc, const float* dev_bias, int32_t accumulate, int32_t m, int32_t n,
                                  int32_t k, void* stream);
+/* The same operands through the 8-phase 256 x 256 kernel (gemm_f16x2_8p.hip), which the pre-split launcher picks by itself
+ * only for large launches: same argument rules, bit-identical result.  Test / micro-benchmark entry. */
+int32_t lram_gemm_f16x2_presplit_8p(const float* dev_a, int64_t lda, const float* dev_w, int64_t ldw, float* dev_c,
+                                    int64_t ldc, const float* dev_bias, int32_t accumulate, int32_t m, int32_t n,
+                                    int32_t k, void* stream);
 /* The device code of the sampling head on caller data (test / evidence entry): row r = dev_logits + r * ld holds n <= 512
  * logits (ld = 0: every row is row 0), dev_uniform[r] (device double) its uniform in [0, 1); dev_tokens[r] (device int32)
  * receives the token of steps 1-4 of lram_set_sampling. */

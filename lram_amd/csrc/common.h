@@ -41,6 +41,18 @@ constexpr int kMaxTokens = 12;  // tokens per launch of the fused recurrent kern
                                 // timesteps (12 tokens) per state pass when a stored context is prefilled
 constexpr int kChunkMaxTokens = 64;  // tokens per state pass of the chunkwise (matrix-core) mLSTM prefill kernels
 
+// Measurement knobs of the projection launchers (LRAM_GEMM_TILE / LRAM_F16P_STAGES / LRAM_GEMM_PANEL / LRAM_SPLITK_TILES).  They
+// travel with the launch (GemmArgs::knobs): an engine reads them once, at lram_create, into lram_engine::gemm_knobs and
+// host::gemm() copies them into every launch; a standalone test / micro-benchmark entry (lram_gemm_*) reads the environment
+// when it is called -- that is how the bit-identity tests walk through tiles, stages and tile orders.  No launcher reads the
+// environment, and a launch whose args were never given knobs runs with these defaults.
+struct GemmKnobs {
+  int tile = 0;          // 64 / 128: force the workgroup tile height of the f16x2 kernels; 256: the 8-phase 256 x 256 kernel; -1: never it
+  int stages = 0;        // 1 / 2: force the LDS stage count of the pre-split kernel
+  int panel = 0;         // > 0: force the column-panel tile order with that width
+  int splitk_tiles = 56; // outputs with fewer 128 x 128 tiles than this are split along K
+};
+
 // ---------------------------------------------------------------------------------------------
 // GEMM  C[M,N] = A[M,K] * W[N,K]^T  (fp32 in, fp32 MFMA accumulate), optional bias / residual.
 // Two-level batching: z = z1 * nb2 + z2 ; pointer = base + z1 * s?1 + z2 * s?2.
@@ -112,19 +124,8 @@ struct GemmArgs {
   int mfma_prio = 0;      // set by the launcher: raise the wave's issue priority around the MFMA block
   int split_k = 1;        // set by the launcher
   int k_tiles_per_split = 0;
+  GemmKnobs knobs;        // host only (no kernel reads it): the launch policy's knobs, behind every field a kernel reads
 };
-// Measurement knobs of the projection launchers (LRAM_GEMM_TILE / LRAM_F16P_STAGES / LRAM_GEMM_PANEL / LRAM_SPLITK_TILES), read
-// from the environment ONCE -- no getenv on the step path (an environ scan per launch, and a race with a concurrent setenv from
-// another host thread) -- and again only where an engine is created (lram_create, like every other knob) or a standalone test /
-// micro-benchmark entry (lram_gemm_*) starts: that is how the bit-identity tests walk through tiles, stages and tile orders.
-struct GemmKnobs {
-  int tile = 0;          // 64 / 128: force the workgroup tile height of the f16x2 kernels; 256: the 8-phase 256 x 256 kernel; -1: never it
-  int stages = 0;        // 1 / 2: force the LDS stage count of the pre-split kernel
-  int panel = 0;         // > 0: force the column-panel tile order with that width
-  int splitk_tiles = 56; // outputs with fewer 128 x 128 tiles than this are split along K
-};
-const GemmKnobs& gemm_knobs();
-void gemm_knobs_reload();
 int gemm_choose_split_k(GemmArgs& g);                             // fills split_k / k_tiles_per_split, returns S
 // Output-tile -> XCD map of the 128-column-tile projection kernels (bm = their tile height, bytes_per_elem = operand bytes
 // per element as staged: 4 for fp32 / two f16 planes).  Hardware hands consecutive workgroup ids to the 8 XCDs in turn, so
@@ -375,7 +376,7 @@ struct MlstmFrontArgs {
   float* scal = nullptr;        // [B*T, NH, 4] out  (f_t, i_t, denom_t, m_t)
   const uint8_t* reset = nullptr;
   int B = 0, T = 0, inner = 0, NH = 0, K = 0;
-  int epw = 0;                  // env slots per workgroup (0 = default)
+  int epw = 0;                  // env slots per workgroup (0 = by slice size; lram_engine::front_epw)
 };
 bool mlstm_front_supported(int inner, int NH, int K, int T);
 void launch_mlstm_front(const MlstmFrontArgs& a, hipStream_t stream);
@@ -671,8 +672,8 @@ void launch_pad_obs(const float* native, int n_native, const int32_t* inv_index,
 void launch_pad_obs_slots(const float* native, int n_native, const int32_t* slot_row, const int32_t* inv_index,
                           const float* mean, const float* stdv, int n_rows, float* out, int B, int state_dim,
                           hipStream_t stream);
-void launch_stream_copy(float* dst, const float* src, size_t numel, hipStream_t stream);
-void launch_stream_read(const float* buf, size_t numel, float* sink, hipStream_t stream);  // read only; sink: 1024 floats
+void launch_stream_copy(float* dst, const float* src, size_t numel, hipStream_t stream, int variant);  // variant: 4 = the default
+void launch_stream_read(const float* buf, size_t numel, float* sink, hipStream_t stream, int variant);  // read only; sink: 1024 floats; variant: 1804 = the default
 void launch_stream_rmw(float* buf, size_t numel, hipStream_t stream);  // in place, the cell kernel's access pattern
 void launch_zero_rows(float* buf, const uint8_t* mask, int B, int64_t row_elems, int64_t outer, int64_t outer_stride,
                       hipStream_t stream);

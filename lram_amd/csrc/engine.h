@@ -103,6 +103,7 @@ struct lram_engine {
     size_t n;
   };
   std::map<const float*, Split> split;
+  GemmKnobs gemm_knobs;    // the projection launchers' knobs as the environment had them at lram_create: gemm() hands them to every launch
   bool use_bf16x3 = true;  // LRAM_GEMM=f32 selects the exact fp32-MFMA kernel everywhere
   // f16x2 projection kernel (gemm_f16x2.hip): un-batched weights also get two row-scaled f16 planes + inverse scales;
   // LRAM_GEMM=bf16x3 keeps the three-plane bf16 kernel for them too
@@ -135,6 +136,7 @@ struct lram_engine {
   std::vector<DevBuf> gate_coef;  // mLSTM: folded i / f gate coefficients per block (mlstm_front.hip), geometries it covers
   bool front_multi = true;     // LRAM_FRONT_MULTI=0: keep the one-workgroup-per-env front end for large launches too
   int front_min_envs = 256;    // LRAM_FRONT_MIN_ENVS: slices of at least this many env slots take the multi-env front end
+  int front_epw = 0;           // LRAM_FRONT_EPW: envs per workgroup of the multi-env front end (1 .. 64); 0 = by slice size
   std::vector<DevBuf> dt_wt;   // Mamba: dt_proj.weight transposed to [dt_rank, d_inner] per block (state-update kernel's operand)
   DevBuf ASCALE;  // per-row maxima of a GEMM's A operand computed by launch_row_amax, one region per stream slot (like
   size_t ascale_rows = 0;  // the split-K slabs)
@@ -598,6 +600,9 @@ bool takes_skinny_with_norm(const lram_engine* e, const GemmArgs& g);
 bool f16x2_rows(const lram_engine* e, int rows, int n, int k);
 bool f16x2_weight(const lram_engine* e, const float* w, int ldw, GemmArgs* g);
 bool presplit_for(const lram_engine* e, const float* w, int rows, int n, int k);
+bool narrow32_for(const lram_engine* e, const float* w, int rows, int n, int k);
+int env_int(const char* name, int dflt);   // for lram_create and the standalone entries only: nothing on the step path reads the environment
+GemmKnobs gemm_knobs_from_env();
 void gemm(lram_engine* e, GemmArgs& g, hipStream_t s);
 void make_split(lram_engine* e, const float* w, size_t n);
 // engine_streams.hip

@@ -169,10 +169,6 @@ void finalize(lram_engine* e) {
   }
   // bf16 split planes of every GEMM weight (LRAM_GEMM=f32 keeps the exact fp32-MFMA kernels instead)
   e->drop_splits();
-  if (const char* v = std::getenv("LRAM_GEMM")) {
-    e->use_bf16x3 = std::string(v) != "f32";
-    e->use_f16x2 = std::string(v) != "f32" && std::string(v) != "bf16x3";
-  }
   if (e->use_bf16x3 && e->use_f16x2) {
     // the big un-batched projections: (weight, rows, K); the per-head / per-gate batched GEMMs of the sLSTM block keep
     // bf16x3 (their operand rows would need one scale per head)
@@ -514,8 +510,8 @@ bool lazy_choice(const lram_engine* e) {
   return mlstm_block_bytes(e) >= 128.0 * 1024 * 1024;
 }
 
-// Environment knobs of lram_create (measurement / test switches), in the order of the table in DESIGN.md section 5.  (LRAM_GEMM is
-// read by finalize; the projection launchers' own process-wide knobs by gemm_knobs_reload().)
+// Environment knobs of lram_create (measurement / test switches), in the order of the table in DESIGN.md section 5.  (The projection
+// launchers' four knobs are read beside this table, by gemm_knobs_from_env().)
 struct Knob {
   const char* name;
   void (*set)(lram_engine& e, const char* v);
@@ -529,6 +525,10 @@ const Knob kKnobs[] = {
     {"LRAM_LAZY_CAP2_ENVS", [](lram_engine& e, const char* v) { e.lazy_cap2_envs = std::max(0, std::atoi(v)); }},
     {"LRAM_FOLD_TAIL", [](lram_engine& e, const char* v) { e.fold_tail = std::atoi(v) != 0; }},
     {"LRAM_GN_FUSE", [](lram_engine& e, const char* v) { e.gn_fuse = std::max(0, std::min(2, std::atoi(v))); }},
+    {"LRAM_GEMM", [](lram_engine& e, const char* v) {
+       const std::string kind(v);
+       e.use_bf16x3 = kind != "f32", e.use_f16x2 = kind != "f32" && kind != "bf16x3";
+     }},
     {"LRAM_F16_MIN_ROWS", [](lram_engine& e, const char* v) { e.f16x2_min_rows = std::max(9, std::atoi(v)); }},
     {"LRAM_GEMM_PRESPLIT", [](lram_engine& e, const char* v) { e.gemm_presplit = std::atoi(v) != 0; }},
     {"LRAM_GEMM_NARROW", [](lram_engine& e, const char* v) { e.gemm_narrow_on = std::atoi(v) != 0, e.gemm_narrow_f16 = std::atoi(v) != 2; }},
@@ -541,6 +541,7 @@ const Knob kKnobs[] = {
     {"LRAM_SLSTM_SEQ", [](lram_engine& e, const char* v) { e.slstm_seq = std::atoi(v) != 0, e.slstm_seq_f32 = std::atoi(v) == 2; }},
     {"LRAM_FRONT_MULTI", [](lram_engine& e, const char* v) { e.front_multi = std::atoi(v) != 0; }},
     {"LRAM_FRONT_MIN_ENVS", [](lram_engine& e, const char* v) { e.front_min_envs = std::max(1, std::atoi(v)); }},
+    {"LRAM_FRONT_EPW", [](lram_engine& e, const char* v) { e.front_epw = std::max(0, std::min(64, std::atoi(v))); }},
     {"LRAM_MAMBA_DT_FUSE", [](lram_engine& e, const char* v) { e.mamba_dt_fuse = std::atoi(v) != 0; }},
     {"LRAM_COMPAT_SHARE", [](lram_engine& e, const char* v) { e.compat_share = std::atoi(v) != 0; }},
     {"LRAM_PREFILL_CHUNK", [](lram_engine& e, const char* v) {
@@ -616,7 +617,7 @@ int32_t lram_create(const lram_config* cfg, int32_t device, lram_engine** out) {
     e->cfg = *cfg;
     e->device = device;
     // Environment knobs (measurement / test switches; the table is in DESIGN.md section 5)
-    gemm_knobs_reload();   // the projection launchers' process-wide knobs: read here, never on the step path
+    e->gemm_knobs = gemm_knobs_from_env();   // the projection launchers' knobs: this engine's from here on
     for (const Knob& k : kKnobs)
       if (const char* v = std::getenv(k.name)) k.set(*e, v);
     *out = e.release();

@@ -70,9 +70,33 @@ bool presplit_for(const lram_engine* e, const float* w, int rows, int n, int k) 
   return 4 * probe.w2_plane < (1ll << 31);
 }
 
+// Does gemm() send the projection `rows x k` against weight w to the exact-fp32 narrow kernel (which reads no row maxima)?  The
+// producer of A (Mamba's conv kernel) asks before it skips writing them; gemm() decides with the same narrow_takes().  A as the
+// engine's producers write it: rows of pitch k on a 16-byte boundary (the packed weight's own address stands in for it).
+bool narrow32_for(const lram_engine* e, const float* w, int rows, int n, int k) {
+  GemmArgs probe;
+  probe.a = w, probe.lda = k, probe.w = w, probe.ldw = k, probe.m = rows, probe.n = n, probe.k = k;
+  return narrow_takes(e, probe) && !(e->use_f16x2 && e->gemm_narrow_f16);
+}
+
+int env_int(const char* name, int dflt) {
+  const char* v = std::getenv(name);
+  return v ? std::atoi(v) : dflt;
+}
+
+GemmKnobs gemm_knobs_from_env() {
+  GemmKnobs k;
+  k.tile = env_int("LRAM_GEMM_TILE", k.tile);
+  k.stages = env_int("LRAM_F16P_STAGES", k.stages);
+  k.panel = env_int("LRAM_GEMM_PANEL", k.panel);
+  k.splitk_tiles = env_int("LRAM_SPLITK_TILES", k.splitk_tiles);
+  return k;
+}
+
 // GEMM dispatch: f16x2 (both operands pre-split, or A split while it is staged) for the big un-batched projections, the
 // few-row kernel for tens of rows, bf16x3 for the batched per-head GEMMs and whatever is left, exact fp32 MFMA as the fallback.
 void gemm(lram_engine* e, GemmArgs& g, hipStream_t s) {
+  g.knobs = e->gemm_knobs;
   if (e->SK.p != nullptr) {
     g.splitk_ws = e->SK.p + (size_t)stream_slot(e, s) * lram_engine::kSplitKSlotElems;
     g.splitk_ws_elems = (int64_t)lram_engine::kSplitKSlotElems;
@@ -151,13 +175,15 @@ void make_split(lram_engine* e, const float* w, size_t n) {
 // ---- standalone entries: one kernel family on caller-supplied operands ------------------------------------------------
 namespace {
 
-// The operands every entry shares (the split planes / packed weights of a family are added by its entry).
+// The operands every entry shares (the split planes / packed weights of a family are added by its entry), and the launch knobs
+// as the environment has them NOW: these are standalone test / micro-benchmark entries.
 GemmArgs entry_args(const float* dev_a, int64_t lda, const float* dev_w, int64_t ldw, float* dev_c, int64_t ldc,
                     const float* dev_bias, int32_t accumulate, int32_t m, int32_t n, int32_t k) {
   GemmArgs g;
   g.a = dev_a, g.lda = lda, g.w = dev_w, g.ldw = ldw, g.c = dev_c, g.ldc = ldc, g.bias = dev_bias;
   g.residual = accumulate ? dev_c : nullptr;
   g.m = m, g.n = n, g.k = k;
+  g.knobs = lram::host::gemm_knobs_from_env();
   return g;
 }
 
@@ -176,6 +202,25 @@ struct Scratch {
 void entry_split_weight(GemmArgs& g, uint16_t* planes, float* inv, hipStream_t s) {
   launch_split_f16x2(g.w, g.n, g.k, planes, inv, s);
   g.w2 = planes, g.w2_plane = (int64_t)split_f16x2_plane_elems((size_t)g.n, (size_t)g.k), g.w2_kt = 32 * (int64_t)g.n, g.w_inv = inv;
+}
+
+// The pre-split entries: both operands split into K-tile-major f16 planes, then `launch` (the pre-split launcher, or the 8-phase
+// kernel it dispatches to for large launches) on them.
+void entry_presplit(const float* dev_a, int64_t lda, const float* dev_w, int64_t ldw, float* dev_c, int64_t ldc, const float* dev_bias,
+                    int32_t accumulate, int32_t m, int32_t n, int32_t k, void* stream, void (*launch)(const GemmArgs&, hipStream_t)) {
+  LRAM_REQUIRE(ldw == k, "lram_gemm_f16x2_presplit: W must be contiguous [n, k]");
+  LRAM_REQUIRE(k % 32 == 0 && k <= 3072, "lram_gemm_f16x2_presplit: k must be a multiple of 32, <= 3072");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t wn = (size_t)n * k, an = (size_t)m * k;   // (k a multiple of 32: the planes have no padding)
+  Scratch<uint16_t> wp(2 * wn), ap(2 * an);
+  Scratch<float> scales((size_t)n + m);  // [n] inverse weight scales, then [m] inverse activation scales
+  GemmArgs g = entry_args(dev_a, lda, dev_w, ldw, dev_c, ldc, dev_bias, accumulate, m, n, k);
+  entry_split_weight(g, wp.p, scales.p, s);
+  launch_row_split_f16x2(dev_a, lda, nullptr, 0, m, k, ap.p, 32 * (int64_t)m, (int64_t)an, scales.p + n, s);
+  g.a = nullptr, g.lda = k;   // A goes in as its two planes
+  g.a2 = ap.p, g.a2_plane = (int64_t)an, g.a2_kt = 32 * (int64_t)m, g.a2_inv = scales.p + n;
+  launch(g, s);
+  LRAM_HIP_CHECK(hipStreamSynchronize(s));
 }
 
 }  // namespace
@@ -202,7 +247,6 @@ int32_t lram_slstm_counts(lram_engine* e, int64_t* out3, int32_t reset) {
 int32_t lram_gemm_f32(const float* dev_a, int64_t lda, const float* dev_w, int64_t ldw, float* dev_c, int64_t ldc,
                       const float* dev_bias, int32_t accumulate, int32_t m, int32_t n, int32_t k, void* stream) {
   return guarded([&] {
-    gemm_knobs_reload();   // standalone test / micro-benchmark entry: the launch knobs as the environment has them NOW
     GemmArgs g = entry_args(dev_a, lda, dev_w, ldw, dev_c, ldc, dev_bias, accumulate, m, n, k);
     launch_gemm_f32(g, static_cast<hipStream_t>(stream));
   });
@@ -211,7 +255,6 @@ int32_t lram_gemm_f32(const float* dev_a, int64_t lda, const float* dev_w, int64
 int32_t lram_gemm_skinny(const float* dev_a, int64_t lda, const float* dev_w, int64_t ldw, float* dev_c, int64_t ldc,
                          const float* dev_bias, int32_t accumulate, int32_t m, int32_t n, int32_t k, void* stream) {
   return guarded([&] {
-    gemm_knobs_reload();   // standalone test / micro-benchmark entry: the launch knobs as the environment has them NOW
     GemmArgs g = entry_args(dev_a, lda, dev_w, ldw, dev_c, ldc, dev_bias, accumulate, m, n, k);
     launch_gemm_skinny(g, static_cast<hipStream_t>(stream));
   });
@@ -234,7 +277,6 @@ int32_t lram_gemm_narrow(const float* dev_a, int64_t lda, const float* dev_w, in
 int32_t lram_gemm_narrow_f16x2(const float* dev_a, int64_t lda, const float* dev_w, int64_t ldw, float* dev_c, int64_t ldc,
                                const float* dev_bias, int32_t accumulate, int32_t m, int32_t n, int32_t k, void* stream) {
   return guarded([&] {
-    gemm_knobs_reload();
     LRAM_REQUIRE(ldw == k && accumulate == 0, "lram_gemm_narrow_f16x2: W must be contiguous [n, k]; no accumulation");
     LRAM_REQUIRE(gemm_narrow_shape(n, k), "lram_gemm_narrow_f16x2: n <= 96, k a multiple of 64, >= 256");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -253,7 +295,6 @@ int32_t lram_gemm_narrow_f16x2(const float* dev_a, int64_t lda, const float* dev
 int32_t lram_gemm_bf16x3(const float* dev_a, int64_t lda, const float* dev_w, int64_t ldw, float* dev_c, int64_t ldc,
                          const float* dev_bias, int32_t accumulate, int32_t m, int32_t n, int32_t k, void* stream) {
   return guarded([&] {
-    gemm_knobs_reload();   // standalone test / micro-benchmark entry: the launch knobs as the environment has them NOW
     LRAM_REQUIRE(ldw == k, "lram_gemm_bf16x3: W must be contiguous [n, k]");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t numel = (size_t)n * k;
@@ -269,7 +310,6 @@ int32_t lram_gemm_bf16x3(const float* dev_a, int64_t lda, const float* dev_w, in
 int32_t lram_gemm_f16x2(const float* dev_a, int64_t lda, const float* dev_w, int64_t ldw, float* dev_c, int64_t ldc,
                         const float* dev_bias, int32_t accumulate, int32_t m, int32_t n, int32_t k, void* stream) {
   return guarded([&] {
-    gemm_knobs_reload();   // standalone test / micro-benchmark entry: the launch knobs as the environment has them NOW
     LRAM_REQUIRE(ldw == k, "lram_gemm_f16x2: W must be contiguous [n, k]");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t numel = split_f16x2_plane_elems((size_t)n, (size_t)k);  // (K-tile-major planes)
@@ -287,20 +327,17 @@ int32_t lram_gemm_f16x2(const float* dev_a, int64_t lda, const float* dev_w, int
 int32_t lram_gemm_f16x2_presplit(const float* dev_a, int64_t lda, const float* dev_w, int64_t ldw, float* dev_c, int64_t ldc,
                                  const float* dev_bias, int32_t accumulate, int32_t m, int32_t n, int32_t k, void* stream) {
   return guarded([&] {
-    gemm_knobs_reload();   // standalone test / micro-benchmark entry: the launch knobs as the environment has them NOW
-    LRAM_REQUIRE(ldw == k, "lram_gemm_f16x2_presplit: W must be contiguous [n, k]");
-    LRAM_REQUIRE(k % 32 == 0 && k <= 3072, "lram_gemm_f16x2_presplit: k must be a multiple of 32, <= 3072");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t wn = (size_t)n * k, an = (size_t)m * k;   // (k a multiple of 32: the planes have no padding)
-    Scratch<uint16_t> wp(2 * wn), ap(2 * an);
-    Scratch<float> scales((size_t)n + m);  // [n] inverse weight scales, then [m] inverse activation scales
-    GemmArgs g = entry_args(dev_a, lda, dev_w, ldw, dev_c, ldc, dev_bias, accumulate, m, n, k);
-    entry_split_weight(g, wp.p, scales.p, s);
-    launch_row_split_f16x2(dev_a, lda, nullptr, 0, m, k, ap.p, 32 * (int64_t)m, (int64_t)an, scales.p + n, s);
-    g.a = nullptr, g.lda = k;   // A goes in as its two planes
-    g.a2 = ap.p, g.a2_plane = (int64_t)an, g.a2_kt = 32 * (int64_t)m, g.a2_inv = scales.p + n;
-    launch_gemm_f16x2p(g, s);
-    LRAM_HIP_CHECK(hipStreamSynchronize(s));
+    entry_presplit(dev_a, lda, dev_w, ldw, dev_c, ldc, dev_bias, accumulate, m, n, k, stream, launch_gemm_f16x2p);
+  });
+}
+
+int32_t lram_gemm_f16x2_presplit_8p(const float* dev_a, int64_t lda, const float* dev_w, int64_t ldw, float* dev_c, int64_t ldc,
+                                    const float* dev_bias, int32_t accumulate, int32_t m, int32_t n, int32_t k, void* stream) {
+  return guarded([&] {
+    entry_presplit(dev_a, lda, dev_w, ldw, dev_c, ldc, dev_bias, accumulate, m, n, k, stream, [](const GemmArgs& g, hipStream_t s) {
+      LRAM_REQUIRE(gemm_f16x2p_supported(g) && gemm_f16x2_8p_supported(g), "lram_gemm_f16x2_presplit_8p: unsupported operand layout");
+      launch_gemm_f16x2_8p(g, s);
+    });
   });
 }
 

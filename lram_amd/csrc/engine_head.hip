@@ -129,7 +129,7 @@ void score_chunk(lram_engine* e, const Call& call, const Slice& x, float* scratc
     GemmArgs gh;
     gh.a = e->HID.p + (((size_t)x.b0 * Lc + beg) * T + c.pred_token) * D, gh.lda = (int64_t)T * D;
     gh.w = e->w_head, gh.ldw = D, gh.c = scratch, gh.ldc = nlog, gh.bias = e->b_head;
-    gh.m = (int)nr, gh.n = (int)nlog, gh.k = D;
+    gh.m = (int)nr, gh.n = (int)nlog, gh.k = D, gh.knobs = e->gemm_knobs;   // (a tile launcher without gemm())
     launch_gemm_f32(gh, x.s);
     count_gemm(e, 2, gh);
     ScoreArgs a = score_args(e, call.sink, call.discrete);

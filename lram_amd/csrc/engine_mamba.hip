@@ -44,15 +44,14 @@ void mamba_stage(lram_engine* e, const Pass& pass, int i, int stage, int T, cons
   const bool ps_in = amx && presplit_for(e, w.in_proj, rows, 2 * di, D);
   uint16_t* xn2 = reinterpret_cast<uint16_t*>(e->XN2.p) + r0 * 32;  // K-tile-major planes: [D / 32][B * T][32]
   const int64_t xn2_kt = ps_in ? (int64_t)(e->XN2.n / D) * 32 : 0;
+  // x_proj's operand row maxima are not needed, and not written, where gemm() runs it in the exact-fp32 form of the narrow-output kernel
+  const bool xp_narrow32 = stage == 1 && narrow32_for(e, w.x_proj, rows, ldx, di);
   if (stage == 0) {
     launch_add_rms_norm(X, RES_in, RES_out, ps_in ? nullptr : XN, w.norm_g, rows, D, c.norm_eps, sl.s, ps_in ? nullptr : amx_xn,
                         ps_in ? xn2 : nullptr, (int64_t)e->XN2.n, ps_in ? amx_xn : nullptr, xn2_kt);
   } else if (stage == 1) {
     MambaConvArgs ca;
     ca.xz = U, ca.conv_state = st.conv.p + b0 * di * c.d_conv, ca.conv_w = w.conv_w, ca.conv_b = w.conv_b, ca.xc = XA;
-    // (x_proj's operand row maxima are not needed where it runs in the exact-fp32 form of the narrow-output kernel)
-    const bool xp_narrow32 = e->gemm_narrow_on && rows >= e->gemm_narrow_min_rows && e->narrow.count(w.x_proj) != 0 &&
-                             !(e->use_f16x2 && e->gemm_narrow_f16);
     ca.reset = rs, ca.B = sl.nb, ca.T = T, ca.d_inner = di, ca.K = c.d_conv, ca.amax = xp_narrow32 ? nullptr : amx_xa;
     ca.hold = pass.hold ? pass.hold + b0 : nullptr;   // (a stored-context chunk with a held env)
     launch_mamba_conv(ca, sl.s);
@@ -77,7 +76,7 @@ void mamba_stage(lram_engine* e, const Pass& pass, int i, int stage, int T, cons
   } else if (stage == 1) {
     GemmArgs xp;
     xp.a = XA, xp.lda = di, xp.w = w.x_proj, xp.ldw = di, xp.c = Q, xp.ldc = ldx;
-    xp.m = rows, xp.n = ldx, xp.k = di, xp.a_amax = amx_xa, xp.amax_parts = amx ? parts : 1;
+    xp.m = rows, xp.n = ldx, xp.k = di, xp.a_amax = xp_narrow32 ? nullptr : amx_xa, xp.amax_parts = amx ? parts : 1;
     gemm(e, xp, gs);
     if (!dt_fused && mamba_dt_proj_needs_plain_kernel(N, R)) {
       // (K = dt_rank or the row pitch dt_rank + 2 * d_state not a multiple of 4: the GEMM kernels' 16-byte operand loads do not apply)

@@ -464,11 +464,12 @@ int32_t lram_pad_obs_slots(const float* dev_native, int32_t n_native, const int3
 }
 
 int32_t lram_stream_copy(float* dev_dst, const float* dev_src, size_t numel, void* stream) {
-  return guarded([&] { launch_stream_copy(dev_dst, dev_src, numel, static_cast<hipStream_t>(stream)); });
+  // (standalone measurement entry: its knob as the environment has it now)
+  return guarded([&] { launch_stream_copy(dev_dst, dev_src, numel, static_cast<hipStream_t>(stream), env_int("LRAM_COPY_VARIANT", 4)); });
 }
 
 int32_t lram_stream_read(const float* dev_buf, size_t numel, float* dev_sink, void* stream) {
-  return guarded([&] { launch_stream_read(dev_buf, numel, dev_sink, static_cast<hipStream_t>(stream)); });
+  return guarded([&] { launch_stream_read(dev_buf, numel, dev_sink, static_cast<hipStream_t>(stream), env_int("LRAM_READ_VARIANT", 1804)); });
 }
 
 int32_t lram_stream_rmw(float* dev_buf, size_t numel, void* stream) {

@@ -181,7 +181,7 @@ void mlstm_front(lram_engine* e, const Pass& pass, int i, int T, const uint8_t* 
     fa.n_state = st.n.p + b0 * inner, fa.m_state = st.m.p + b0 * NH;
     fa.conv_w = w.conv_w, fa.conv_b = w.conv_b, fa.wq = w.wq, fa.wk = w.wk, fa.gc = e->gate_coef[i].p, fa.bi = w.bi, fa.bf = w.bf;
     fa.xa = e->XA.p + r0 * e->icols, fa.scal = e->SCAL.p + r0 * NH * 4, fa.reset = reset ? reset + b0 : nullptr;
-    fa.B = sl.nb, fa.T = T, fa.inner = inner, fa.NH = NH, fa.K = c.conv_k;
+    fa.B = sl.nb, fa.T = T, fa.inner = inner, fa.NH = NH, fa.K = c.conv_k, fa.epw = e->front_epw;
     // (the lean path belongs to the lazy read pass; stored contexts run materialised, so a held env never gets here)
     LRAM_REQUIRE(pass.hold == nullptr, "mLSTM front end: the multi-env kernel has no hold rule (stored contexts run materialised)");
     launch_mlstm_front(fa, sl.s);
@@ -357,6 +357,7 @@ void slstm_block(lram_engine* e, const Pass& pass, int i, int T, const uint8_t* 
   } else if (slstm_gates_one_bf16x3(e, g4, w, XC, XN, gates, Hs)) {
     // larger slices: the same ONE launch on the bf16x3 kernel (operand tables; every gate's tiles in one grid instead of four
     // short launches of 48-144 workgroups each on the slice's chain) -- bit-identical to the four launches
+    g4.knobs = e->gemm_knobs;   // (a tile launcher without gemm())
     launch_gemm_bf16x3(g4, s);
     count_gemm(e, 1, g4);
   } else {

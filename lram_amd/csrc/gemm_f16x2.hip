@@ -373,7 +373,7 @@ void launch_gemm_f16x2(const GemmArgs& g_in, hipStream_t stream) {
   // is short -- 1536 x 1024 x 512: 31.6 us with 96 tiles of 128 rows, 20.5 with 192 of 64 -- or LRAM_GEMM_TILE = 64 / 128 forces one),
   // and, this kernel's own clause, where 128-row tiles leave workgroup slots empty (three workgroups per CU: 768 slots) and the
   // launch is narrow
-  const int force_bm = gemm_knobs().tile;
+  const int force_bm = g.knobs.tile;
   const bool forced = force_bm == 64 || force_bm == 128;
   const bool small = gemm_f16x2p_tile(g, S) == 64 || (!forced && g.m > 64 && S == 1 && tiles128 < 768 && tiles_n <= 6);
   const int tiles = small ? ((g.m + 63) / 64) * tiles_n : tiles128;

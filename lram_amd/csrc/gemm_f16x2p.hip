@@ -338,7 +338,7 @@ static void launch_stage(const GemmArgs& g, dim3 grid, hipStream_t stream) {
 // launches keep 128 rows (inside the two-slice pipeline the small tile's 1.5 x operand traffic per flop costs Mamba-48M 2.3 %
 // and the 206M stack 1.5 %: profiles/r04_ab_tile_height.txt).  LRAM_GEMM_TILE (measurement knob): 64 / 128 force one.
 int gemm_f16x2p_tile(const GemmArgs& g, int S) {
-  const int force = gemm_knobs().tile;  // (cached: common.h GemmKnobs)
+  const int force = g.knobs.tile;
   if (force == 64 || force == 128) return force;
   const long tiles128 = (long)((g.m + 127) / 128) * ((g.n + 127) / 128);
   if (g.m > 64 && ((tiles128 * S < 256 && g.k <= 768) || tiles128 * S < 128)) return 64;
@@ -351,7 +351,7 @@ void launch_gemm_f16x2p(const GemmArgs& g_in, hipStream_t stream) {
   // 2 = two stages, the next tile's DMA under the current tile's MFMAs, one barrier per K tile, two workgroups per CU
   // default 0 = by grid size (same box, standalone: 16M proj_up 768 tiles 55 us with one stage / 65 with two; Mamba in_proj 576
   // tiles 67 / 80; 16M proj_down 192 tiles 50 / 40; Mamba out_proj 144 tiles 65 / 51 -- profiles/r04_gemm_f16x2p_durations.txt)
-  const int stages_env = gemm_knobs().stages;
+  const int stages_env = g.knobs.stages;
   g.mfma_prio = 1;
   LRAM_REQUIRE(g.m > 0 && g.n > 0 && g.k > 0, "gemm: empty problem");
   LRAM_REQUIRE(gemm_f16x2p_supported(g), "gemm f16x2 (pre-split operands): unsupported operand layout");
@@ -361,7 +361,7 @@ void launch_gemm_f16x2p(const GemmArgs& g_in, hipStream_t stream) {
   // 24576 x 2048 x 512 155 -> 147; everything a step launches is 0.6-1.0 x (profiles/r06_gemm_8phase_durations.txt).
   // LRAM_GEMM_TILE=256 forces it (tests, measurements), -1 keeps it off.
   {
-    const int force = gemm_knobs().tile;
+    const int force = g.knobs.tile;
     const long t256 = (long)((g.m + 255) / 256) * ((g.n + 255) / 256);
     const bool big = t256 >= 700 && g.k >= 512 && g.n >= 1024;
     // ... and where the caller says the launch shares the chip with another slice's memory-bound kernels and covers 0.25-0.63 of

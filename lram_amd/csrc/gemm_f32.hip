@@ -9,7 +9,7 @@
 // 32x32 accumulators (64 VGPR).  Both operands are K-contiguous, staged global -> registers -> LDS
 // (row pitch 36 floats: ds_read_b128 of 16 consecutive rows hits 16 distinct 4-bank slots), next
 // K-tile's global loads are issued before the MFMAs of the current one.
-// (This file also hosts the launch policy every projection launcher shares: gemm_knobs, gemm_choose_split_k,
+// (This file also hosts the launch policy every projection launcher shares: gemm_choose_split_k,
 // gemm_choose_xcd_split and the split-K reduce.)
 #include <algorithm>
 #include <cstdlib>
@@ -383,30 +383,6 @@ __global__ __launch_bounds__(256) void splitk_reduce4_kernel(GemmArgs g) {
 }
 }  // namespace
 
-namespace {
-GemmKnobs g_knobs;
-bool g_knobs_read = false;
-int env_int(const char* name, int dflt) {
-  const char* v = std::getenv(name);
-  return v ? std::atoi(v) : dflt;
-}
-}  // namespace
-
-void gemm_knobs_reload() {
-  GemmKnobs k;
-  k.tile = env_int("LRAM_GEMM_TILE", 0);
-  k.stages = env_int("LRAM_F16P_STAGES", 0);
-  k.panel = env_int("LRAM_GEMM_PANEL", 0);
-  k.splitk_tiles = env_int("LRAM_SPLITK_TILES", 56);
-  g_knobs = k;
-  g_knobs_read = true;
-}
-
-const GemmKnobs& gemm_knobs() {
-  if (!g_knobs_read) gemm_knobs_reload();
-  return g_knobs;
-}
-
 // Split-K when the output has too few 128x128 tiles to fill the 256 CUs and K is deep enough to split.
 int gemm_choose_split_k(GemmArgs& g) {
   g.split_k = 1;
@@ -422,7 +398,7 @@ int gemm_choose_split_k(GemmArgs& g) {
     // proj_down / ffn_down of 1024 slots split again, +2-3 % (361.1k / 364.8k -> 374.2k / 367.3k at a threshold of 64); the 206M
     // stack's 60-tile proj_down (K = 2560, five slabs of 3.9 MB) stays unsplit: split it loses 1.1 % (32.16k / 32.06k ->
     // 31.74k / 31.75k); 128: -6 % at 512 slots.  profiles/r05_ab_splitk_threshold.txt)
-  const int min_tiles = gemm_knobs().splitk_tiles;
+  const int min_tiles = g.knobs.splitk_tiles;
   if (tiles >= min_tiles || nk < 4) return 1;
   int S = std::min(std::min(nk / 2, 16), (256 + tiles - 1) / tiles);
   while (S > 1 && (int64_t)S * g.m * g.n > g.splitk_ws_elems) --S;
@@ -440,10 +416,10 @@ void gemm_choose_xcd_split(GemmArgs& g, int bm, int bn, int bytes_per_elem) {
   g.panel_w = 0;
   if (g.nb1 * g.nb2 != 1) return;
   const int tiles_m = (g.m + bm - 1) / bm, tiles_n = (g.n + bn - 1) / bn;
-  // LRAM_GEMM_PANEL (measurement knob; gemm_knobs(): the bit-identity test walks through the orders via the standalone entries):
+  // LRAM_GEMM_PANEL (measurement knob; the bit-identity test walks through the orders via the standalone entries):
   // > 0 forces the panel order with that width (a width >= the grid's = the one-dimensional map: each XCD a contiguous run of
   // the row-major order)
-  const int pw = gemm_knobs().panel;
+  const int pw = g.knobs.panel;
   if (pw > 0) {
     g.panel_w = std::min(pw, tiles_n);
     return;

@@ -433,15 +433,11 @@ void launch_pad_obs_slots(const float* native, int n_native, const int32_t* slot
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
-void launch_stream_copy(float* dst, const float* src, size_t numel, hipStream_t stream) {
+void launch_stream_copy(float* dst, const float* src, size_t numel, hipStream_t stream, int variant) {
   LRAM_REQUIRE(numel % 4 == 0, "stream copy: numel must be a multiple of 4");
-  // LRAM_COPY_VARIANT (measurement knob): 0 grid-stride loop, 1 blocked x8, 2 blocked x8 non-temporal,
+  // variant (LRAM_COPY_VARIANT of the lram_stream_copy entry, a measurement knob): 0 grid-stride loop, 1 blocked x8, 2 blocked x8 non-temporal,
   // 3 blocked x16 non-temporal, 4 blocked x4 non-temporal (default: measured 6.48 TB/s on MI355X against 4.4-5.5 for
   // the deeper variants and 5.0 for the grid-stride loop), 5 blocked x2 nt, 6 blocked x1 nt
-  static const int variant = [] {
-    const char* v = std::getenv("LRAM_COPY_VARIANT");
-    return v ? std::atoi(v) : 4;
-  }();
   const size_t n4 = numel / 4;
   v4c_t* d = reinterpret_cast<v4c_t*>(dst);
   const v4c_t* sp = reinterpret_cast<const v4c_t*>(src);
@@ -472,14 +468,10 @@ void launch_stream_rmw(float* buf, size_t numel, hipStream_t stream) {
   LRAM_HIP_CHECK(hipGetLastError());
 }
 
-void launch_stream_read(const float* buf, size_t numel, float* sink, hipStream_t stream) {
-  // LRAM_READ_VARIANT = 100 * rows-in-flight per thread (4 / 8 / 16) + log2(rows per workgroup / 64) (0..4), + 1000 to
+void launch_stream_read(const float* buf, size_t numel, float* sink, hipStream_t stream, int variant) {
+  // variant (LRAM_READ_VARIANT of the lram_stream_read entry) = 100 * rows-in-flight per thread (4 / 8 / 16) + log2(rows per workgroup / 64) (0..4), + 1000 to
   // request 48 KiB of LDS per workgroup (three workgroups per CU, the read pass's residency); default 1804: 8 rows in
   // flight, 1 MiB blocks, three workgroups per CU (6.0-6.6 TB/s over the variants on MI355X, profiles/r03_read_ceiling.txt)
-  static const int variant = [] {
-    const char* v = std::getenv("LRAM_READ_VARIANT");
-    return v ? std::atoi(v) : 1804;
-  }();
   const int unr = (variant % 1000) / 100, lg = variant % 100;
   const int rows = 64 << std::max(0, std::min(lg, 4));
   const size_t lds = variant >= 1000 ? 48 * 1024 : 0;

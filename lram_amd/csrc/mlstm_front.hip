@@ -203,16 +203,12 @@ void launch_mlstm_front(const MlstmFrontArgs& a_in, hipStream_t stream) {
   MlstmFrontArgs a = a_in;
   LRAM_REQUIRE(mlstm_front_supported(a.inner, a.NH, a.K, a.T), "mLSTM multi-env front end: unsupported geometry");
   LRAM_REQUIRE(a.gc != nullptr && (a.ldu & 3) == 0, "mLSTM multi-env front end: missing gate coefficients / misaligned u");
-  // LRAM_FRONT_EPW (measurement knob): env slots per workgroup
-  static const int epw_env = [] {
-    const char* v = std::getenv("LRAM_FRONT_EPW");
-    return v ? std::atoi(v) : 0;
-  }();
+  // a.epw: env slots per workgroup (the engine's LRAM_FRONT_EPW, a measurement knob); 0 = by slice size
   // (same box, 4096 env slots: 2 envs per workgroup 426.2k env-steps/s, 4: 429.4k, 8: 431.1k / 429.7k, 16: 430.8k / 431.9k;
   // the one-workgroup-per-env kernel 420.3k / 419.0k -- profiles/r04_ab_front_kernel.txt)
   // fewer envs per workgroup for smaller slices, so that the launch still covers the chip: one workgroup per CU from 256 envs
   // (512-env slices at 8 envs per workgroup are 64 workgroups: 58.7 us per launch in the 1024-slot timeline)
-  a.epw = epw_env > 0 ? epw_env : (a.epw > 0 ? a.epw : std::max(1, std::min(8, a.B / 256)));
+  if (a.epw <= 0) a.epw = std::max(1, std::min(8, a.B / 256));
   const int nwg = (a.B + a.epw - 1) / a.epw;
   hipLaunchKernelGGL(mlstm_front_kernel<3>, dim3((unsigned)nwg), dim3(256), 0, stream, a);
   LRAM_HIP_CHECK(hipGetLastError());

@@ -114,6 +114,8 @@ _SYMBOLS = {
                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _VP]),
     "lram_gemm_f16x2_presplit": (ctypes.c_int32, [_VP, ctypes.c_int64, _VP, ctypes.c_int64, _VP, ctypes.c_int64, _VP,
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _VP]),
+    "lram_gemm_f16x2_presplit_8p": (ctypes.c_int32, [_VP, ctypes.c_int64, _VP, ctypes.c_int64, _VP, ctypes.c_int64, _VP,
+                                                     ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _VP]),
     "lram_embed_images": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _VP, _VP]),
     "lram_step_images": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _VP, _VP, _VP, ctypes.c_int32,
                          _VP, _VP, _VP]),
@@ -166,7 +168,7 @@ def library_path() -> str:
     """The in-tree library; LRAM_LIB_VARIANT=<name> picks csrc/_variants/<name>.so instead -- A/B measurements of two
     builds inside one GPU call (scripts/gpu_ab.sh), never set in tests or by the driver."""
     here = os.path.dirname(os.path.abspath(__file__))
-    variant = os.environ.get("LRAM_LIB_VARIANT")
+    variant = os.getenv("LRAM_LIB_VARIANT")
     if variant:
         return os.path.join(here, "csrc", "_variants", variant + ".so")
     return os.path.join(here, "csrc", _LIB_NAME)
@@ -1191,19 +1193,9 @@ def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = No
     """out[M,N] = a[M,K] @ w[N,K]^T (+ bias) (+ out) through the library's fp32-MFMA kernel (kernel="f32") or the
     bf16x3 kernel (kernel="bf16x3") the engine uses for its projections."""
     lib = load_library()
-    if kernel == "f16x2p8":   # the pre-split entry with the 8-phase 256 x 256 kernel forced (the entry re-reads the launch knobs)
-        import os
-        old = os.environ.get("LRAM_GEMM_TILE")
-        os.environ["LRAM_GEMM_TILE"] = "256"
-        try:
-            return gemm_f32(a, w, bias, out, accumulate, "f16x2p")
-        finally:
-            if old is None:
-                del os.environ["LRAM_GEMM_TILE"]
-            else:
-                os.environ["LRAM_GEMM_TILE"] = old
-    fn = {"f32": lib.lram_gemm_f32, "bf16x3": lib.lram_gemm_bf16x3, 
-          "f16x2": lib.lram_gemm_f16x2, "f16x2p": lib.lram_gemm_f16x2_presplit, "skinny": lib.lram_gemm_skinny,
+    fn = {"f32": lib.lram_gemm_f32, "bf16x3": lib.lram_gemm_bf16x3,
+          "f16x2": lib.lram_gemm_f16x2, "f16x2p": lib.lram_gemm_f16x2_presplit, "f16x2p8": lib.lram_gemm_f16x2_presplit_8p,
+          "skinny": lib.lram_gemm_skinny,
           "narrow": lib.lram_gemm_narrow, "narrow16": lib.lram_gemm_narrow_f16x2}[kernel]
     M, K = a.shape
     N = w.shape[0]
