@@ -481,6 +481,63 @@ int32_t lram_set_context_rows(lram_engine* e, int32_t mode);
 int32_t lram_get_context_rows(const lram_engine* e);
 int32_t lram_context_counts(lram_engine* e, int64_t* out4, int32_t reset);
 
+/* Context-window inference: the reference's evaluation with use_inference_cache = False, which is its default and what its shipped
+ * configs run (src/algos/decision_transformer_sb3.py:86).  At every env-step the model is run FROM AN EMPTY STATE over the env's
+ * last K = eval_context_len timesteps, left-padded to K (predict / pad_inputs, decision_transformer_sb3.py:621-691) -- with the true
+ * rewards of past timesteps, and with the bookkeeping of the evaluation loop (src/callbacks/evaluation.py:130-251): the reward of
+ * the last step patched in, a finished episode's returns-to-go rewritten to the returns obtained, the context pruned to the last
+ * episodes.  The engine keeps the last K timesteps of every env slot in a device ring; one entry is the state-token embedding
+ * (d_model floats, before embed_ln), the return-to-go and the reward.  How many entries count is n_b in 0 .. K per slot, kept on
+ * the host.  A window step costs a K-timestep lram_prefill plus two passes over batch x K x d_model floats.
+ *
+ * lram_window_alloc   allocates the ring for K = timesteps >= 1 (all n_b = 0, no pad entry; about 2 x batch x K x d_model floats);
+ *                     0 frees it; lram_state_alloc frees it too.  Synchronises the device.  Refused: state not allocated,
+ *                     tokens_per_step != 3, d_model % 4 != 0, [batch, K, d_model] beyond 2 GiB.
+ * lram_window_set_pad the pad entry of LRAM_WINDOW_PAD_REFERENCE: dev_pad_obs float[state_dim] through the state Linear, or
+ *                     float[d_model] taken as it is (obs_is_embedding).  What the reference's zero padding becomes once it is
+ *                     normalised and embedded.  It belongs to the ring: lram_window_alloc drops it.
+ * lram_step_window    for every env slot b, in this order:
+ *     1 reset    host_reset[b] != 0: n_b = 0, dev_prev_reward[b] is ignored
+ *     2 patch    otherwise, if n_b > 0: the newest entry's reward = dev_prev_reward[b] (it was pushed with reward 0)
+ *     3 relabel  host_relabel[b] = m > 0: the rtg of the newest min(m, n_b) entries = the fp32 suffix sum of those entries'
+ *                rewards as they stand after the patch, accumulated from the newest backwards (s = r_newest, then s = r_j + s):
+ *                discount_cumsum with gamma 1
+ *     4 keep     host_keep[b] = k > 0: n_b = min(n_b, k), after the relabel
+ *     5 push     (embed_state(dev_obs[b]) or dev_obs[b] itself, dev_rtg[b], 0) is appended, n_b = min(n_b + 1, K): the oldest
+ *                entry falls out.  Raw observations go through the state Linear at `batch` rows
+ *     6 the windows, oldest to newest, go through the stored-context body from an empty state for every slot, and dev_actions /
+ *       dev_tokens (the latter nullable) take the action of the last timestep.  pad_mode LRAM_WINDOW_PAD_REFERENCE: the rows ahead of a
+ *       slot's n_b hold (pad entry, rtg 0, reward 0) and the call makes the launches of lram_prefill over K timesteps of
+ *       embeddings with every slot reset -- outputs, logits (lram_get_taps) and state are bit-identical to that call.
+ *       LRAM_WINDOW_PAD_NONE: only the n_b real timesteps count; the launches are those of lram_prefill_ragged with lengths n_b
+ *       (one chunk boundary per distinct length).
+ *   dev_obs          device float[batch, state_dim] (or [batch, d_model] embeddings)
+ *   dev_rtg, dev_prev_reward   device float[batch]
+ *   host_reset (uint8), host_relabel, host_keep (int32)   HOST arrays [batch], each nullable (nobody reset / relabelled / pruned)
+ *   The recurrent state afterwards is what that stored-context call leaves: a window step and lram_step on one engine overwrite
+ *   each other's state.  Sampling: one draw per call, as lram_prefill with dev_actions.  Never captured.
+ *   Refused (message in lram_last_error, nothing launched, ring, counts and state untouched): no ring; pad mode 0 without a pad
+ *   entry; a pad mode other than 0 or 1; parked slots (lram_set_live) or a context-rows mode other than LRAM_CONTEXT_ROWS_ALL; both
+ *   Mamba modes of lram_set_compat_mode; a relabel on a reset slot; a negative relabel or keep; a NULL dev_obs, dev_rtg,
+ *   dev_prev_reward or dev_actions; whatever lram_prefill refuses for `discrete`.
+ *   That promise covers the refusals, which are all made before the first launch.  A call that fails LATER -- device memory running
+ *   out while the stored-context body grows its workspace or the tables of a call of per-env lengths -- has already done steps
+ *   1 - 5: the ring, its counts and the push position are advanced by one timestep, consistently on host and device
+ *   (lram_window_peek shows them), and no action was produced.
+ * lram_window_peek    copies the windows, END-aligned and oldest to newest with zeros in the rows ahead of n_b, into dev_emb
+ *                     float[batch, K, d_model], dev_rtg and dev_reward float[batch, K], and the counts into host_counts
+ *                     int32[batch]; every pointer is nullable.
+ * Out of scope: slot tables that mix vector and image slots, parked slots, reading the ring in place from the chunk front end. */
+#define LRAM_WINDOW_PAD_REFERENCE 0   /* pad entry, rtg 0, reward 0 ahead of a shorter window: the reference's pad_inputs */
+#define LRAM_WINDOW_PAD_NONE      1   /* only the real timesteps count */
+int32_t lram_window_alloc(lram_engine* e, int32_t timesteps);
+int32_t lram_window_set_pad(lram_engine* e, const float* dev_pad_obs, int32_t obs_is_embedding, void* stream);
+int32_t lram_step_window(lram_engine* e, const float* dev_obs, int32_t obs_is_embedding, const float* dev_rtg,
+                         const float* dev_prev_reward, const uint8_t* host_reset, const int32_t* host_relabel,
+                         const int32_t* host_keep, int32_t pad_mode, int32_t discrete, float* dev_actions, int32_t* dev_tokens,
+                         void* stream);
+int32_t lram_window_peek(lram_engine* e, float* dev_emb, float* dev_rtg, float* dev_reward, int32_t* host_counts, void* stream);
+
 /* Micro-batch pipeline (xLSTM): the env slots are processed as `n` slices on engine-owned HIP streams; the
  * HBM-bound matrix-memory kernels of all slices run back to back on one stream while the other slices'
  * fp32-MFMA projections overlap them.  n = 1 disables it, 0 = automatic (2 slices where one mLSTM block's matrix memory over the batch reaches 512 MiB -- 16M from 512 env slots,

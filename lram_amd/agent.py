@@ -79,7 +79,7 @@ class RecurrentAgent:
                  compat_mamba_repeat: bool = False,
                  compat_stale_state: bool = False,
                  a_sample_kwargs: Optional[dict] = None, sample_seed: int = 0, sample_slot_base: int = 0,
-                 slot_table=None):
+                 slot_table=None, use_inference_cache: Optional[bool] = None, eval_context_len: Optional[int] = None):
         self.spec = spec
         # slot_table (lram_amd.domains.SlotTable): the batch holds envs of several domains -- head mode, action dims and
         # observation kind per env slot (the reference passes `env_act_dim` / `is_discrete` per call for its one env,
@@ -128,8 +128,12 @@ class RecurrentAgent:
         # (the PyTorch / MIOpen module that cross-checks them lives with the tests: tests/torch_image_encoder.py)
         self.has_image_encoder = any(k.startswith("embed_image.") for k in state_dict) and spec.image_shape is not None
         # attributes read by the evaluation loop
-        self.eval_context_len = spec.max_length
-        self.use_inference_cache = True
+        self.eval_context_len = spec.max_length if eval_context_len is None else int(eval_context_len)
+        # True: the recurrent state is stepped forever (the reference's cached path).  False -- the reference's default and what
+        # its shipped configs run: every env-step runs the model from an empty state over the env's last eval_context_len
+        # timesteps (Engine.step_window; decision_transformer_sb3.py:621-691).  See predict_batch.  Not given here: what the
+        # configuration set (agent_params.use_inference_cache -> ModelSpec.use_inference_cache; every preset says True).
+        self.use_inference_cache = bool(spec.use_inference_cache if use_inference_cache is None else use_inference_cache)
         self.reset_inf_cache_freq = spec.reset_inf_cache_freq
         # reference behaviour (False): the context is dropped when the cache is reset;
         # True: the last eval_context_len stored timesteps are fed back through Engine.prefill
@@ -160,6 +164,37 @@ class RecurrentAgent:
             self.engine.set_compat_mode(1, True)
         self._arm_sampling()
         self._apply_slot_table()
+        self._alloc_window()
+
+    def _window_kind(self) -> Optional[str]:
+        """None with the inference cache on; else what every slot's observation is in window mode: "vector" or "image".
+        A slot table is refused in this mode (ValueError): one that mixes vector and image slots cannot be served -- the ring
+        has one front end for the batch -- and per-slot heads over the ring are not wired yet."""
+        if getattr(self, "use_inference_cache", True):
+            return None
+        if getattr(self, "slot_table", None) is not None:
+            raise ValueError("use_inference_cache=False: slot tables are not served in context-window mode (one that mixes "
+                             "vector and image slots cannot be: the ring has one front end for the batch)")
+        return "image" if self.has_image_encoder else "vector"
+
+    def _alloc_window(self):
+        """Window mode: the ring of eval_context_len timesteps per env and the pad entry -- the reference pads the states with
+        zeros BEFORE it normalises them (pad_inputs, then (s - mean) / std), so the pad observation is (0 - state_mean) /
+        state_std through _prepare_obs; an image agent's is the embedding of an all-zero frame."""
+        kind = self._window_kind()
+        if kind is None:
+            return
+        if self.compat_mamba_repeat or self.compat_stale_state:
+            raise ValueError("use_inference_cache=False: compat_mamba_repeat / compat_stale_state describe the cached path")
+        if self.eval_context_len < 1:
+            raise ValueError(f"use_inference_cache=False: eval_context_len must be >= 1, got {self.eval_context_len}")
+        self.engine.alloc_window(self.eval_context_len)
+        if kind == "image":
+            frame = torch.zeros(self.n_envs, *self.spec.image_shape, dtype=torch.uint8, device=self.device)
+            self.engine.set_window_pad(self.engine.embed_images(frame)[0].clone(), is_embedding=True)
+        else:
+            pad, _ = self._prepare_obs(torch.zeros(1, self.spec.state_dim, device=self.device))
+            self.engine.set_window_pad(pad[0])
 
     def _apply_slot_table(self):
         if getattr(self, "slot_table", None) is not None:
@@ -359,6 +394,9 @@ class RecurrentAgent:
 
     # ---- per-slot cache handle: fork / snapshot / restore single env slots (n_envs > 1) ----
     def _need_batch(self, what: str):
+        if not getattr(self, "use_inference_cache", True):
+            raise RuntimeError(f"{what}() moves the recurrent state of env slots; with use_inference_cache=False an env's context "
+                               f"is its window on the device ring, which these calls do not move")
         if self.n_envs <= 1:
             raise RuntimeError(f"{what}() moves state between env slots of a batched agent; this agent has n_envs = 1 "
                                f"(use past_key_values for its one env)")
@@ -425,6 +463,9 @@ class RecurrentAgent:
         want = [int(e) for e in env_ids]
         if len(set(want)) != len(want) or any(not 0 <= e < self.n_envs for e in want):
             raise ValueError(f"set_active: expected distinct env ids in 0 .. {self.n_envs - 1}")
+        if not getattr(self, "use_inference_cache", True) and len(want) != self.n_envs:
+            raise ValueError("set_active: use_inference_cache=False steps every env slot (the window ring has one push "
+                             "position for the batch); parked envs are refused in this mode")
         if not want:
             raise ValueError("set_active: at least one env must stay active")
         sch = copy.deepcopy(self.scheduler)
@@ -553,6 +594,7 @@ class RecurrentAgent:
                 self.engine.set_compat_mode(self._compat_repeat_now, self.compat_stale_state)
             self._arm_sampling()
             self._apply_slot_table()
+            self._alloc_window()
 
     def __getstate__(self):
         d = dict(self.__dict__)
@@ -602,7 +644,8 @@ class RecurrentAgent:
     @torch.no_grad()
     def predict_batch(self, observation: torch.Tensor, returns_to_go: torch.Tensor,
                       rewards: Optional[torch.Tensor] = None, reset_mask: Optional[torch.Tensor] = None,
-                      env_act_dim: Optional[int] = None) -> torch.Tensor:
+                      env_act_dim: Optional[int] = None, prev_rewards: Optional[torch.Tensor] = None, relabel=None,
+                      keep=None) -> torch.Tensor:
         """observation [B, obs_dim] (or uint8 [B,3,64,64]), returns_to_go [B] -> actions [B, env_act_dim]
         (float32; for discrete agents int64 [B, 1]).  The returned tensor is a view of an engine-owned
         buffer that the next call overwrites.
@@ -612,7 +655,20 @@ class RecurrentAgent:
         fp32), 0.0 elsewhere; `env_act_dim` is ignored.
         With parked envs (set_active) the tensors stay full-width in env-id order: the live rows are gathered in slot order,
         stepped, and the actions scattered back; the rows of parked envs hold 0 (then a fresh tensor, not an engine buffer), and
-        their reset flags are not looked at."""
+        their reset flags are not looked at.
+        use_inference_cache=False (context-window inference, Engine.step_window): the model runs from an empty state over
+        every env's last eval_context_len timesteps, left-padded as the reference pads them.  `prev_rewards` [B] is the scaled
+        reward the PREVIOUS step earned (None: zeros) -- it becomes the reward of the newest stored timestep; `rewards` is not
+        looked at (the current timestep's reward token is 0, evaluation.py:132).  `reset_mask[b]` empties env b's window;
+        `relabel` / `keep` (host lists of B ints or None) are the episode-end bookkeeping of persist_context
+        (evaluation.py:213-237): relabel = m rewrites the returns-to-go of the newest m timesteps to the returns obtained,
+        keep = k prunes the window to its newest k timesteps.  Frames go through embed_images first.  A slot table -- one that
+        mixes vector and image slots, or any other -- is refused in this mode (at construction), and so are parked envs
+        (set_active)."""
+        if not getattr(self, "use_inference_cache", True):
+            return self._predict_batch_window(observation, returns_to_go, reset_mask, env_act_dim, prev_rewards, relabel, keep)
+        if prev_rewards is not None or relabel is not None or keep is not None:
+            raise ValueError("prev_rewards / relabel / keep belong to use_inference_cache=False (context-window inference)")
         if getattr(self, "slot_table", None) is not None:
             return self._predict_batch_slots(observation, returns_to_go, rewards, reset_mask)
         idx = self._live_index()   # (None: every env active in its own slot -- no gather)
@@ -644,6 +700,19 @@ class RecurrentAgent:
             actions, _ = self.engine.step(obs, rtg, rew, reset_mask, discrete=self.is_discrete, obs_is_embedding=is_emb)
         if idx is not None:   # back to env-id order; the rows of parked envs hold 0
             actions = self._scatter_rows(actions, idx)
+        if self.is_discrete:
+            return actions[:, :1].to(torch.int64)
+        return actions if env_act_dim is None else actions[:, :env_act_dim]
+
+    def _predict_batch_window(self, observation, returns_to_go, reset_mask, env_act_dim, prev_rewards, relabel, keep):
+        if not torch.is_tensor(observation) or observation.shape[0] != self.n_envs:
+            raise ValueError(f"observation: expected a tensor with one row per env slot ({self.n_envs})")
+        obs, is_emb = self._prepare_obs(observation)   # (frames: embed_images, then embeddings)
+        rtg = returns_to_go.to(self.device, torch.float32).reshape(-1).contiguous()
+        prev = self._zero_reward if prev_rewards is None else prev_rewards.to(self.device, torch.float32).reshape(-1).contiguous()
+        reset = None if reset_mask is None else [bool(v) for v in torch.as_tensor(reset_mask).reshape(-1).tolist()]
+        actions, _ = self.engine.step_window(obs, rtg, prev, reset=reset, relabel=relabel, keep=keep, pad="reference",
+                                             discrete=self.is_discrete, obs_is_embedding=is_emb)
         if self.is_discrete:
             return actions[:, :1].to(torch.int64)
         return actions if env_act_dim is None else actions[:, :env_act_dim]
@@ -957,7 +1026,11 @@ class RecurrentAgent:
     def get_action_pred(self, policy, states, actions, rewards, returns_to_go, timesteps, attention_mask,
                         deterministic, prompt, is_eval=False, task_id=None, env_act_dim=None):
         """With the inference cache on, only the last timestep's (state, rtg, reward) reach the encoder
-        (online_decision_transformer_model.py:466-470)."""
+        (online_decision_transformer_model.py:466-470).  use_inference_cache=False is served by predict_batch alone (it keeps
+        the history on the device); this single-env view raises in that mode."""
+        if not getattr(self, "use_inference_cache", True):
+            raise RuntimeError("use_inference_cache=False: the single-env predict / get_action_pred surface is not wired to "
+                               "the window ring; use predict_batch(..., prev_rewards=, relabel=, keep=)")
         obs = states[:, -1]
         rtg = returns_to_go[:, -1].reshape(1)
         rew = None if rewards is None else rewards[:, -1].reshape(1)

@@ -16,9 +16,9 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 SOURCES = ["engine.hip", "engine_gemm.hip", "engine_streams.hip", "engine_xlstm.hip", "engine_mamba.hip", "engine_image.hip",
-           "engine_head.hip", "engine_step.hip", "engine_context.hip", "engine_state.hip", "gemm_f32.hip", "gemm_bf16x3.hip", "gemm_f16x2.hip", "gemm_f16x2p.hip", "gemm_f16x2_8p.hip", "gemm_narrow.hip", "xlstm_kernels.hip",
+           "engine_head.hip", "engine_step.hip", "engine_context.hip", "engine_window.hip", "engine_state.hip", "gemm_f32.hip", "gemm_bf16x3.hip", "gemm_f16x2.hip", "gemm_f16x2p.hip", "gemm_f16x2_8p.hip", "gemm_narrow.hip", "xlstm_kernels.hip",
            "mlstm_chunk.hip", "mlstm_lazy.hip", "mlstm_front.hip", "slstm_seq.hip", "impala_cnn.hip", "misc_kernels.hip",
-           "mamba_kernels.hip", "sample_kernels.hip", "score_kernels.hip", "context_kernels.hip", "slot_state.hip", "selftest.hip"]
+           "mamba_kernels.hip", "sample_kernels.hip", "score_kernels.hip", "context_kernels.hip", "window_kernels.hip", "slot_state.hip", "selftest.hip"]
 BUILD_ID_SOURCE = "build_id.cpp"   # carries the hash of everything else; compiled on every build (a second)
 
 # every header / include fragment of csrc counts as a dependency of every object: *.h and *.inl are globbed, so a new

@@ -328,6 +328,20 @@ void launch_score_fill_ragged(float* actions, int32_t* tokens, float* logp, cons
 // rows of slots without a context (start[b] == L): actions 0, tokens -1 (each nullable)
 void launch_action_fill_kept(float* actions, int32_t* tokens, const int32_t* start, int B, int L, int act_dim, hipStream_t stream);
 
+// Context-window inference (window_kernels.hip; lram_step_window).  Every env slot has a ring of K entries -- ring_emb [B, K, D],
+// ring_rtg / ring_rew [B, K] -- and all envs push at the same position `head`; the entry of age a sits at (newest - a) mod K.
+// Per env, in this order: reward of the newest entry <- prev_reward[b] where patch[b]; rtg of the newest relabel[b] entries <- the
+// fp32 suffix sum of their rewards, accumulated from the newest backwards; then (rtg[b], 0) into position `head`.
+void launch_window_update(float* ring_rtg, float* ring_rew, const float* prev_reward, const float* rtg, const int32_t* patch,
+                          const int32_t* relabel, int head, int B, int K, hipStream_t stream);
+// emb [B, D] into position `head` of every env's ring (float4 rows)
+void launch_window_push_rows(float* ring_emb, const float* emb, int head, int B, int K, int D, hipStream_t stream);
+// The windows oldest to newest into [B, K, D] / [B, K] / [B, K] (each nullable): env b's count[b] entries end-aligned, or with `left`
+// in rows [0, count[b]); every other row takes (pad_emb, 0, 0), or zeros where pad_emb is null.  No entry beyond count[b] is read.
+void launch_window_gather(float* out_emb, float* out_rtg, float* out_rew, const float* ring_emb, const float* ring_rtg,
+                          const float* ring_rew, const int32_t* count, const float* pad_emb, bool left, int newest, int B, int K,
+                          int D, hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------------
 // xLSTM
 // ---------------------------------------------------------------------------------------------

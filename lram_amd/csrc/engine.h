@@ -10,6 +10,7 @@
 //   engine_head.hip     the action head, its refusals, the entries that run the head alone        (calls gemm)
 //   engine_step.hip     token front end, the chunk loop, the env-step and encoder entries          (calls the stacks, image, head, gemm, streams)
 //   engine_context.hip  stored contexts: the chunk plan, the one body of the eight entries         (calls step, image, head, state)
+//   engine_window.hip   context-window inference: the per-slot ring, lram_step_window                (calls context, gemm)
 //   engine_state.hip    reset, export / import, the slot table and the per-slot state calls
 #pragma once
 #include <algorithm>
@@ -302,6 +303,21 @@ struct lram_engine {
   // records of the slots a replace call leaves alone (length 0), saved ahead of the first chunk and loaded back behind the last.
   // Both grown outside the launches, as SEQ_EMB is.
   DevBuf CTX, KEEP;
+  // Context-window inference (engine_window.hip; lram_window_alloc / lram_step_window): every env slot's ring of its last win_K
+  // timesteps -- WIN_RING_EMB [B, K, D] state-token embeddings, WIN_RING_SC [2][B, K] rtg | reward -- with ONE push position for
+  // the batch (win_head: all envs push exactly one entry per call) and the per-env counts on the host.  WIN_EMB [B, K, D] and
+  // WIN_SC [2][B, K] are the laid-out windows a call hands to the stored-context body; WIN_PAD [D] the pad entry's embedding;
+  // WIN_CTL, as bytes of one allocation, int32 patch[B] | relabel[B] | count[B] (the counts persist: lram_window_peek reads
+  // them) and uint8 ones[B], the reset mask that restarts every env.  win_K == 0: no ring.
+  DevBuf WIN_RING_EMB, WIN_RING_SC, WIN_EMB, WIN_SC, WIN_PAD, WIN_CTL;
+  int win_K = 0, win_head = 0;
+  bool win_pad_set = false;
+  std::vector<int32_t> win_count;   // host [B], each in 0 .. win_K
+  void drop_window() {
+    for (DevBuf* b : {&WIN_RING_EMB, &WIN_RING_SC, &WIN_EMB, &WIN_SC, &WIN_PAD, &WIN_CTL}) b->release();
+    win_K = 0, win_head = 0, win_pad_set = false;
+    win_count.clear();
+  }
   // lram_score: the head's logits for a block of (env, timestep) rows of one chunk, one region per chunk lane / env slice in
   // flight.  A region holds at most score_rows rows of act_dim * n_vocab floats (default 4096 rows: 34 MiB at 8 x 274 logits;
   // LRAM_SCORE_ROWS at lram_create, at least 16); a chunk with more rows goes through it block by block.
@@ -460,6 +476,7 @@ struct lram_engine {
       b->release();
     for (auto& t : twin)
       for (DevBuf& b : t) b.release();
+    drop_window();
     ascale_rows = 0;
     last_head = -1;
     B = 0;
@@ -637,6 +654,8 @@ void require_all_live(const lram_engine* e, const char* who);
 void timesteps_launches(lram_engine* e, const Pass& base, const Call& call, hipStream_t s);
 // engine_context.hip
 FrameCount count_frames(const lram_engine* e, int L, const int32_t* lengths);
+void context_checks(lram_engine* e, Call& c);
+void context_launches(lram_engine* e, Call c, hipStream_t s);
 // engine_xlstm.hip, engine_mamba.hip
 void lazy_materialize(lram_engine* e, hipStream_t s);
 void lazy_finish_prefold(lram_engine* e, hipStream_t s);

@@ -193,7 +193,19 @@ void check_frames_call(const lram_engine* e, const Call& call) {
 // nothing is launched or allocated), the launches, the draw count.  c.who names the entry in every message.  A scored call runs
 // the head at every timestep and draws nothing; any other has c.actions / c.tokens (nullable) take the action at every env's own
 // last timestep.
+// (The two halves are lram::host functions: lram_step_window runs the refusals, then its own ring launches, then the launches.)
 void stored_context_call(lram_engine* e, Call c, hipStream_t s) {
+  context_checks(e, c);
+  context_launches(e, c, s);
+}
+
+}  // namespace
+
+namespace lram::host {
+
+// The refusals of a stored-context call, all of them: launches nothing, allocates nothing, changes nothing but c.in.obs (a call
+// from frames whose observations nobody reads) and the sampled profile's call count.
+void context_checks(lram_engine* e, Call& c) {
   const std::string w(c.who);
   LRAM_REQUIRE(e != nullptr, w + ": null engine");
   if (c.from_frames && !frames_entry(e, c)) c.in.obs = nullptr;
@@ -201,14 +213,20 @@ void stored_context_call(lram_engine* e, Call c, hipStream_t s) {
   require_all_live(e, c.who);
   LRAM_REQUIRE((c.in.obs || c.in.frames) && c.in.rtg && c.in.rew, w + ": null device pointer");
   LRAM_REQUIRE(c.in.L >= 1, w + ": timesteps must be >= 1");
-  RaggedCall rc{e, w, c.in.L, c.host_lengths, c.append != 0, {}};
+  const RaggedCall rc{e, w, c.in.L, c.host_lengths, c.append != 0, {}};
   if (c.ragged) rc.check(c.in.emb);
   if (c.in.frames != nullptr) check_frames_call(e, c);
-  const bool acts = !c.scored && c.actions != nullptr;
   if (c.scored)
     check_score_sink(e, c.who, c.discrete, c.sink);
-  else if (acts)
+  else if (c.actions != nullptr)
     check_head_mode(e, c.discrete, c.who);
+}
+
+// The launches and the draw count of a call that context_checks has passed.
+void context_launches(lram_engine* e, Call c, hipStream_t s) {
+  const std::string w(c.who);
+  RaggedCall rc{e, w, c.in.L, c.host_lengths, c.append != 0, {}};
+  const bool acts = !c.scored && c.actions != nullptr;
   e->ctx_counts[0] += 1;
   Pass pass;
   pass.context = true;
@@ -233,6 +251,10 @@ void stored_context_call(lram_engine* e, Call c, hipStream_t s) {
   // (a score is never a draw: the sampling mode and its counter are left alone)
   if (acts) sample_draw_advance(e, s);
 }
+
+}  // namespace lram::host
+
+namespace {
 
 // The entries fill a Call and hand it to the body.  Contexts of observations or embeddings: kReplace and kAppend take per-env
 // lengths (host_lengths must be given), kDense takes none.

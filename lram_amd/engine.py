@@ -139,6 +139,11 @@ _SYMBOLS = {
     "lram_set_context_rows": (ctypes.c_int32, [_VP, ctypes.c_int32]),
     "lram_get_context_rows": (ctypes.c_int32, [_VP]),
     "lram_context_counts": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]),
+    "lram_window_alloc": (ctypes.c_int32, [_VP, ctypes.c_int32]),
+    "lram_window_set_pad": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP]),
+    "lram_step_window": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP, ctypes.c_int32, ctypes.c_int32, _VP,
+                                          _VP, _VP]),
+    "lram_window_peek": (ctypes.c_int32, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "lram_stream_rmw": (ctypes.c_int32, [_VP, ctypes.c_size_t, _VP]),
     "lram_stream_read": (ctypes.c_int32, [_VP, ctypes.c_size_t, _VP, _VP]),
     "lram_gemm_counts": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]),
@@ -412,6 +417,64 @@ def check_context_lengths(lengths, batch: int, L: int):
     return out
 
 
+WINDOW_PAD = ("reference", "none")   # LRAM_WINDOW_PAD_REFERENCE / _NONE, by value
+
+
+def check_window_timesteps(K, batch: int, d_model: int) -> int:
+    """The rules of lram_window_alloc, checked on the host (no GPU needed): K an integer >= 0 (0 frees the ring), d_model a
+    multiple of 4 and [batch, K, d_model] floats within 2 GiB.  Returns K; raises ValueError."""
+    if isinstance(K, bool) or int(K) != K or K < 0:
+        raise ValueError(f"window: timesteps must be an integer >= 1 (0 frees the ring), got {K!r}")
+    K = int(K)
+    if K > 0 and d_model % 4 != 0:
+        raise ValueError(f"window: d_model {d_model} is no multiple of 4 (the ring's kernels move float4)")
+    if batch * K * d_model > (1 << 29):
+        raise ValueError(f"window: the [{batch}, {K}, {d_model}] windows exceed 2 GiB")
+    return K
+
+
+def check_window_controls(reset, relabel, keep, batch: int):
+    """The per-step control arrays of lram_step_window, checked on the host (no GPU needed).  Each is None or has `batch`
+    entries (a list, a numpy array or a tensor, moved to the host): `reset` bools or 0 / 1, `relabel` and `keep` integers
+    >= 0 (0: leave alone).  A relabel on a reset slot is refused: the reset drops the entries the relabel would rewrite.
+    Returns (reset, relabel, keep) as lists of ints or None; raises ValueError."""
+    def ints(x, name, what):
+        if x is None:
+            return None
+        if isinstance(x, torch.Tensor):
+            x = x.reshape(-1).tolist()
+        out = _int_list([int(v) if isinstance(v, bool) and name == "reset" else v for v in x], name, what)
+        if len(out) != batch:
+            raise ValueError(f"{name}: expected {batch} entries (one per env slot), got {len(out)}")
+        return out
+    reset = ints(reset, "reset", "flags")
+    relabel, keep = ints(relabel, "relabel", "counts"), ints(keep, "keep", "counts")
+    for b, v in enumerate(reset or ()):
+        if v not in (0, 1):
+            raise ValueError(f"reset: flag {v} of env slot {b} is neither 0 nor 1")
+    for name, arr in (("relabel", relabel), ("keep", keep)):
+        for b, v in enumerate(arr or ()):
+            if v < 0:
+                raise ValueError(f"{name}: {name} {v} of env slot {b} is negative")
+    if reset is not None and relabel is not None:
+        for b in range(batch):
+            if reset[b] and relabel[b] > 0:
+                raise ValueError(f"relabel: env slot {b} is reset and relabelled (relabel {relabel[b]})")
+    return reset, relabel, keep
+
+
+class WindowResult:
+    """What Engine.window() returns: the windows end-aligned and oldest to newest, rows ahead of an env's count zeroed --
+    `emb` float32 [B, K, d_model], `rtg` and `reward` float32 [B, K] on the device, `counts` a list of B ints."""
+    __slots__ = ("emb", "rtg", "reward", "counts")
+
+    def __init__(self, emb, rtg, reward, counts):
+        self.emb, self.rtg, self.reward, self.counts = emb, rtg, reward, counts
+
+    def __repr__(self):
+        return f"WindowResult(K={self.rtg.shape[1]}, counts={self.counts})"
+
+
 def check_frame_contexts(frames: torch.Tensor, obs_seq: Optional[torch.Tensor], batch: int, n_image: Optional[int],
                          state_dim: int):
     """The shape rules of lram_prefill_frames / lram_score_frames, checked on the host (no GPU needed).  `frames`: uint8
@@ -546,6 +609,7 @@ class Engine:
         self._slot_image = None      # host copy of the slot table's image column (a new allocation drops the table)
         self._mask_words = None      # keeps the packed words of set_action_mask alive during the call (the engine copies them)
         self._n_img_live = 0         # image slots below `live`: the frames step_slots is handed
+        self._window_K = 0           # (lram_state_alloc frees the window ring)
         B, A = self.batch, self.spec.act_dim
         # zeroed: a discrete head writes column 0 only, and the columns it leaves alone must not depend on what the allocator
         # hands out (two runs on the same inputs return the same tensors)
@@ -1008,6 +1072,64 @@ class Engine:
         buf = (ctypes.c_int64 * 4)()
         _check(self.lib, self.lib.lram_context_counts(self._h, buf, 1 if reset else 0))
         return {"calls": int(buf[0]), "chunks": int(buf[1]), "env_timesteps": int(buf[2]), "kept": int(buf[3])}
+
+    # -- context-window inference: the reference's cache-off evaluation ---------------------------------
+    @property
+    def window_timesteps(self) -> int:
+        """K of the ring alloc_window() made; 0: none (alloc() frees it)."""
+        return getattr(self, "_window_K", 0)
+
+    def alloc_window(self, K: int):
+        """The device ring of every env slot's last K timesteps (lram_window_alloc): all counts 0, no pad entry.  K = 0 frees
+        it.  Synchronises: not a hot-path call."""
+        K = check_window_timesteps(K, self.batch, self.spec.d_model)
+        _check(self.lib, self.lib.lram_window_alloc(self._h, K))
+        self._window_K = K
+
+    def set_window_pad(self, vec: torch.Tensor, is_embedding: bool = False):
+        """The pad entry of pad="reference" (lram_window_set_pad): a normalised observation float32 [state_dim], which goes
+        through the state Linear, or with is_embedding a state-token embedding float32 [d_model].  The reference pads with
+        zero observations before it normalises them: the vector is (0 - state_mean) / state_std."""
+        vec = vec.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        _chk_dev(vec, torch.float32, (self.spec.d_model if is_embedding else self.spec.state_dim,), self.device, "vec")
+        _check(self.lib, self.lib.lram_window_set_pad(self._h, _ptr(vec), int(bool(is_embedding)), _stream_ptr(self.device)))
+
+    def step_window(self, obs: torch.Tensor, rtg: torch.Tensor, prev_reward: torch.Tensor, reset=None, relabel=None, keep=None,
+                    pad: str = "reference", discrete=False, obs_is_embedding: bool = False):
+        """One env-step of the cache-off evaluation for all slots (lram_step_window): the ring takes the new timestep and the
+        model runs from an empty state over every env's last K timesteps.  `obs` float32 [B, state_dim] (or [B, d_model]),
+        `rtg` and `prev_reward` float32 [B] on the device; `reset` (bools), `relabel`, `keep` (ints >= 0) are HOST arrays of B
+        entries or None.  Per env, in this order: reset empties the window; otherwise prev_reward becomes the reward of the
+        newest entry; relabel = m rewrites the rtg of the newest m entries to the suffix sums of their rewards; keep = k
+        prunes the window to its newest k entries; then (obs, rtg, reward 0) is pushed.  pad="reference": shorter windows
+        are left-padded with the pad entry (set_window_pad), rtg 0 and reward 0, as the reference's pad_inputs does;
+        pad="none": only the real timesteps count.  Returns (actions, tokens) as step().  The recurrent state afterwards is
+        the stored-context call's: step_window and step on one engine overwrite each other's state."""
+        if pad not in WINDOW_PAD:
+            raise ValueError(f'pad: unknown mode {pad!r} (choose "reference" or "none")')
+        B, spec = self.batch, self.spec
+        _chk_dev(obs, torch.float32, (B, spec.d_model if obs_is_embedding else spec.state_dim), self.device, "obs")
+        _chk_dev(rtg, torch.float32, (B,), self.device, "rtg")
+        _chk_dev(prev_reward, torch.float32, (B,), self.device, "prev_reward")
+        reset, relabel, keep = check_window_controls(reset, relabel, keep, B)
+        host_reset = None if reset is None else (ctypes.c_uint8 * B)(*reset)
+        _check(self.lib, self.lib.lram_step_window(
+            self._h, _ptr(obs), int(obs_is_embedding), _ptr(rtg), _ptr(prev_reward), host_reset,
+            None if relabel is None else _i32_array(relabel), None if keep is None else _i32_array(keep),
+            WINDOW_PAD.index(pad), _head_mode(discrete), _ptr(self._actions), _ptr(self._tokens), _stream_ptr(self.device)))
+        return self._actions, self._tokens
+
+    def window(self) -> WindowResult:
+        """The windows as the ring holds them (lram_window_peek): see WindowResult."""
+        B, K, D = self.batch, self.window_timesteps, self.spec.d_model
+        if K < 1:
+            raise LramError("window: no window ring is allocated (alloc_window)")
+        emb = torch.empty(B, K, D, dtype=torch.float32, device=self.device)
+        rtg = torch.empty(B, K, dtype=torch.float32, device=self.device)
+        rew = torch.empty(B, K, dtype=torch.float32, device=self.device)
+        counts = (ctypes.c_int32 * B)()
+        _check(self.lib, self.lib.lram_window_peek(self._h, _ptr(emb), _ptr(rtg), _ptr(rew), counts, _stream_ptr(self.device)))
+        return WindowResult(emb, rtg, rew, list(counts))
 
     def _live_rows(self, buf: torch.Tensor) -> torch.Tensor:
         return buf if self._live == self.batch else buf[:self._live]

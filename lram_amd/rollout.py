@@ -191,7 +191,8 @@ class SlotScheduler:
 
 
 class BatchedRollout:
-    """agent: object with predict_batch(obs, rtg, rewards, reset_mask, env_act_dim) (lram_amd.agent.RecurrentAgent)."""
+    """agent: object with predict_batch(obs, rtg, rewards, reset_mask, env_act_dim) (lram_amd.agent.RecurrentAgent); one whose
+    `use_inference_cache` is False also takes prev_rewards=, relabel=, keep= (context-window mode, _step_window)."""
 
     def __init__(self, agent, env: SyntheticVecEnv, target_return, reward_scale,
                  env_act_dim: Optional[int] = None, persist_context: bool = False):
@@ -225,9 +226,53 @@ class BatchedRollout:
         self.ep_return = torch.zeros(env.n_envs, device=dev)
         self.finished_returns = []
         self.finished_lengths = []
+        # context-window mode (agent.use_inference_cache False; _step_window): the scaled reward of the step before, the relabel /
+        # keep lists the next call takes (None: no episode has just ended) and every env's finished episode lengths
+        self.prev_reward = torch.zeros(env.n_envs, device=dev)
+        self._window_relabel = self._window_keep = None
+        self._episode_lengths = [[] for _ in range(env.n_envs)]
+
+    @torch.no_grad()
+    def _step_window(self):
+        """One step with agent.use_inference_cache False (context-window inference; evaluation.py:130-251 with the cache off):
+        the agent is handed the scaled reward of the step before -- it becomes the reward of the newest stored timestep (:153) --
+        and at an episode end either the reset flag or, with persist_context, relabel = the episode's length (its returns-to-go
+        are rewritten to the returns obtained, :219-222) and keep = min(sum of the last seqs_per_sample - 1 episode lengths,
+        eval_context_len), eval_context_len when seqs_per_sample is 1 (:215-217, :223-224).  Episode ends reach the host."""
+        n = self.env.n_envs
+        actions = self.agent.predict_batch(self.obs, self.rtg, None, self.reset_mask, self.env_act_dim,
+                                           prev_rewards=self.prev_reward, relabel=self._window_relabel, keep=self._window_keep)
+        obs, reward, done = self.env.step(actions)
+        self.ep_return += reward
+        self.timestep += 1
+        self._window_relabel = self._window_keep = None
+        if bool(done.any()):
+            self.finished_returns.append(self.ep_return[done].clone())
+            self.finished_lengths.append(self.timestep[done].clone())
+            if self.persist_context:
+                K = int(self.agent.eval_context_len)
+                seqs = int(self.agent.replay_buffer.seqs_per_sample) - 1
+                self._window_relabel, self._window_keep = [0] * n, [0] * n
+                for b in torch.nonzero(done).reshape(-1).tolist():
+                    length = int(self.timestep[b])
+                    self._episode_lengths[b].append(length)
+                    self._window_relabel[b] = length
+                    self._window_keep[b] = min(sum(self._episode_lengths[b][-seqs:]), K) if seqs > 0 else K
+        rtg0 = self.rtg0 if torch.is_tensor(self.rtg0) else torch.full_like(self.rtg, self.rtg0)
+        # (fp32 reward / fp32 scale, as the rtg below; the reference divides the env's float64 reward and rounds once, :152-153)
+        self.prev_reward = (reward / self.reward_scale).to(torch.float32)
+        self.rtg = torch.where(done, rtg0, self.rtg - reward / self.reward_scale)
+        self.timestep = torch.where(done, torch.zeros_like(self.timestep), self.timestep)
+        self.ep_return = torch.where(done, torch.zeros_like(self.ep_return), self.ep_return)
+        self.reset_mask = torch.zeros_like(self.reset_mask) if self.persist_context else done.to(torch.uint8)
+        self.obs = obs
+        self.last_reward, self.last_done = reward, done
+        return actions
 
     @torch.no_grad()
     def step(self):
+        if not getattr(self.agent, "use_inference_cache", True):
+            return self._step_window()
         actions = self.agent.predict_batch(self.obs, self.rtg, None, self.reset_mask, self.env_act_dim)
         obs, reward, done = self.env.step(actions)
         self.ep_return += reward
@@ -307,6 +352,9 @@ def evaluate_policy_batched(agent, env, n_eval_episodes: int = 10, target_return
     `get_reward_scale_for_env` (:111-122); `agent.persist_context` selects the cross-episode mode; an env's
     `is_success` info at episode end is appended to `is_success_buffer` (the reference collects it through its
     `_log_success_callback`, custom_eval_callback.py:36-52).
+    An agent with `use_inference_cache` False is driven in context-window mode (BatchedRollout._step_window): the previous
+    step's scaled reward, the reset flag or -- with persist_context -- the relabel / keep of a finished episode go with every
+    call; park_finished is refused there, before the first step (ValueError).
     park_finished=True: an env that has finished its share is parked (agent.set_active) and the agent no longer steps it --
     the reference keeps forwarding it and throws the result away.  The env object still steps all its sub-envs, with action 0
     for the parked ones; rewards, lengths and counts equal those of park_finished=False (envs are independent)."""
@@ -317,6 +365,9 @@ def evaluate_policy_batched(agent, env, n_eval_episodes: int = 10, target_return
         reward_scale = agent.get_reward_scale_for_env(None)
     # every env takes part from the first step on: an agent that comes out of an evaluation with parked envs (park_finished) starts
     # the next one with all of them active again
+    if park_finished and not getattr(agent, "use_inference_cache", True):
+        raise ValueError("evaluate_policy_batched: park_finished needs the inference cache; with use_inference_cache=False every "
+                         "env slot is stepped (the window ring has one push position for the batch)")
     if hasattr(agent, "set_active") and len(agent.active) != n:
         agent.set_active(range(n))
     ro = BatchedRollout(agent, env, target_return, reward_scale, env_act_dim,
