@@ -487,8 +487,9 @@ int32_t lram_context_counts(lram_engine* e, int64_t* out4, int32_t reset);
  * rewards of past timesteps, and with the bookkeeping of the evaluation loop (src/callbacks/evaluation.py:130-251): the reward of
  * the last step patched in, a finished episode's returns-to-go rewritten to the returns obtained, the context pruned to the last
  * episodes.  The engine keeps the last K timesteps of every env slot in a device ring; one entry is the state-token embedding
- * (d_model floats, before embed_ln), the return-to-go and the reward.  How many entries count is n_b in 0 .. K per slot, kept on
- * the host.  A window step costs a K-timestep lram_prefill plus two passes over batch x K x d_model floats.
+ * (d_model floats, before embed_ln), the return-to-go and the reward.  How many entries count is n_b in 0 .. K per slot, and every
+ * slot has its own ring position; both are kept on the host and go to the device with the call, nothing is read back.  A window
+ * step costs a K-timestep lram_prefill over the rows it runs plus two passes over rows x K x d_model floats.
  *
  * lram_window_alloc   allocates the ring for K = timesteps >= 1 (all n_b = 0, no pad entry; about 2 x batch x K x d_model floats);
  *                     0 frees it; lram_state_alloc frees it too.  Synchronises the device.  Refused: state not allocated,
@@ -496,7 +497,11 @@ int32_t lram_context_counts(lram_engine* e, int64_t* out4, int32_t reset);
  * lram_window_set_pad the pad entry of LRAM_WINDOW_PAD_REFERENCE: dev_pad_obs float[state_dim] through the state Linear, or
  *                     float[d_model] taken as it is (obs_is_embedding).  What the reference's zero padding becomes once it is
  *                     normalised and embedded.  It belongs to the ring: lram_window_alloc drops it.
- * lram_step_window    for every env slot b, in this order:
+ * lram_window_set_slots / lram_window_get_slots   which slots a window step runs.  LRAM_WINDOW_SLOTS_SHARED (the default;
+ *                     lram_window_alloc and lram_state_alloc set it back): every slot, and parked slots are refused.
+ *                     LRAM_WINDOW_SLOTS_OWN: the live prefix [0, n_live) of lram_set_live -- see "live rows" below.  Host bookkeeping
+ *                     only: no synchronisation, no allocation, the ring is not touched.  Refused: no ring, a mode other than 0 or 1.
+ * lram_step_window    for every env slot b the call runs, in this order:
  *     1 reset    host_reset[b] != 0: n_b = 0, dev_prev_reward[b] is ignored
  *     2 patch    otherwise, if n_b > 0: the newest entry's reward = dev_prev_reward[b] (it was pushed with reward 0)
  *     3 relabel  host_relabel[b] = m > 0: the rtg of the newest min(m, n_b) entries = the fp32 suffix sum of those entries'
@@ -504,7 +509,7 @@ int32_t lram_context_counts(lram_engine* e, int64_t* out4, int32_t reset);
  *                discount_cumsum with gamma 1
  *     4 keep     host_keep[b] = k > 0: n_b = min(n_b, k), after the relabel
  *     5 push     (embed_state(dev_obs[b]) or dev_obs[b] itself, dev_rtg[b], 0) is appended, n_b = min(n_b + 1, K): the oldest
- *                entry falls out.  Raw observations go through the state Linear at `batch` rows
+ *                entry falls out.  Raw observations go through the state Linear at the call's rows
  *     6 the windows, oldest to newest, go through the stored-context body from an empty state for every slot, and dev_actions /
  *       dev_tokens (the latter nullable) take the action of the last timestep.  pad_mode LRAM_WINDOW_PAD_REFERENCE: the rows ahead of a
  *       slot's n_b hold (pad entry, rtg 0, reward 0) and the call makes the launches of lram_prefill over K timesteps of
@@ -516,20 +521,46 @@ int32_t lram_context_counts(lram_engine* e, int64_t* out4, int32_t reset);
  *   host_reset (uint8), host_relabel, host_keep (int32)   HOST arrays [batch], each nullable (nobody reset / relabelled / pruned)
  *   The recurrent state afterwards is what that stored-context call leaves: a window step and lram_step on one engine overwrite
  *   each other's state.  Sampling: one draw per call, as lram_prefill with dev_actions.  Never captured.
+ *   Live rows (LRAM_WINDOW_SLOTS_OWN with n_live < batch, the convention of lram_step): dev_obs, dev_rtg, dev_prev_reward and the
+ *   host arrays have n_live rows, dev_actions / dev_tokens take n_live rows, and steps 1 - 6 run on slots [0, n_live) alone: the
+ *   stored-context body as under LRAM_CONTEXT_ROWS_LIVE (outputs, logits and state bit-identical to lram_prefill[_ragged] in that
+ *   mode over the live slots' windows; lram_context_counts grows by n_live x K env-timesteps in pad mode 0).  A parked slot's ring
+ *   rows, position, count and recurrent state are untouched bit for bit, and no row of it is computed.  With every slot live the
+ *   two modes make the same launches.
  *   Refused (message in lram_last_error, nothing launched, ring, counts and state untouched): no ring; pad mode 0 without a pad
- *   entry; a pad mode other than 0 or 1; parked slots (lram_set_live) or a context-rows mode other than LRAM_CONTEXT_ROWS_ALL; both
+ *   entry; a pad mode other than 0 or 1; parked slots (lram_set_live) in LRAM_WINDOW_SLOTS_SHARED; a context-rows mode other than
+ *   LRAM_CONTEXT_ROWS_ALL set by the caller (in either slots mode); both
  *   Mamba modes of lram_set_compat_mode; a relabel on a reset slot; a negative relabel or keep; a NULL dev_obs, dev_rtg,
  *   dev_prev_reward or dev_actions; whatever lram_prefill refuses for `discrete`.
  *   That promise covers the refusals, which are all made before the first launch.  A call that fails LATER -- device memory running
  *   out while the stored-context body grows its workspace or the tables of a call of per-env lengths -- has already done steps
- *   1 - 5: the ring, its counts and the push position are advanced by one timestep, consistently on host and device
+ *   1 - 5: the ring, its counts and the positions of the call's slots are advanced by one timestep, consistently on host and device
  *   (lram_window_peek shows them), and no action was produced.
  * lram_window_peek    copies the windows, END-aligned and oldest to newest with zeros in the rows ahead of n_b, into dev_emb
  *                     float[batch, K, d_model], dev_rtg and dev_reward float[batch, K], and the counts into host_counts
- *                     int32[batch]; every pointer is nullable.
- * Out of scope: slot tables that mix vector and image slots, parked slots, reading the ring in place from the chunk front end. */
+ *                     int32[batch]; every pointer is nullable.  All `batch` slots, live or parked, in either slots mode.
+ *
+ * Windows move with their slots, beside the state movers and by their host-list rules (lram_state_copy_slots / _swap_slots /
+ * _save_slots / _load_slots); one launch each, in both slots modes, on live or parked slots.  They move whole windows -- entries,
+ * count and position -- touch no other slot and no recurrent state; the state movers keep leaving the ring alone.
+ * lram_window_copy_slots   slot host_dst[i]'s window becomes slot host_src[i]'s.  Sources may repeat (fan-out); destinations are
+ *                     unique and no slot is both source and destination.
+ * lram_window_swap_slots   exchanges the windows of slots host_a[i] and host_b[i]; all 2n indices distinct.
+ * lram_window_slot_numel   floats in one record: K x (d_model + 2) + 1 (0 and a message in lram_last_error without a ring).
+ * lram_window_save_slots   record i (dev_records float[n, numel]) = slot host_slots[i]'s window as lram_window_peek lays it out:
+ *                     K x d_model embeddings, K rtg, K rewards, END-aligned and oldest to newest with zeros ahead of n_b, then n_b
+ *                     as one trailing float.  Position-free: a record loads into any engine with the same K and d_model, whatever
+ *                     its ring positions.  Slots may repeat; at most `batch` per call.
+ * lram_window_load_slots   the inverse, slots unique.  The counts reach the host through one read-back of n floats, which
+ *                     synchronises `stream` (the only window call besides lram_window_alloc that waits for the device); a record
+ *                     whose trailing float is no integer in 0 .. K is refused before anything is written.
+ * Refused, with ring, counts, positions and state untouched: no ring, an index out of range, a destination listed twice, a slot
+ * that is both source and destination, (swap, load) a slot listed twice, a NULL list or records with n > 0.  n = 0 is a no-op.
+ * Out of scope: slot tables in window mode, reading the ring in place from the chunk front end. */
 #define LRAM_WINDOW_PAD_REFERENCE 0   /* pad entry, rtg 0, reward 0 ahead of a shorter window: the reference's pad_inputs */
 #define LRAM_WINDOW_PAD_NONE      1   /* only the real timesteps count */
+#define LRAM_WINDOW_SLOTS_SHARED  0   /* a window step runs every slot; parked slots are refused */
+#define LRAM_WINDOW_SLOTS_OWN     1   /* a window step runs the live prefix; parked slots keep their windows */
 int32_t lram_window_alloc(lram_engine* e, int32_t timesteps);
 int32_t lram_window_set_pad(lram_engine* e, const float* dev_pad_obs, int32_t obs_is_embedding, void* stream);
 int32_t lram_step_window(lram_engine* e, const float* dev_obs, int32_t obs_is_embedding, const float* dev_rtg,
@@ -537,6 +568,13 @@ int32_t lram_step_window(lram_engine* e, const float* dev_obs, int32_t obs_is_em
                          const int32_t* host_keep, int32_t pad_mode, int32_t discrete, float* dev_actions, int32_t* dev_tokens,
                          void* stream);
 int32_t lram_window_peek(lram_engine* e, float* dev_emb, float* dev_rtg, float* dev_reward, int32_t* host_counts, void* stream);
+int32_t lram_window_set_slots(lram_engine* e, int32_t mode);
+int32_t lram_window_get_slots(const lram_engine* e);
+int32_t lram_window_copy_slots(lram_engine* e, const int32_t* host_src, const int32_t* host_dst, int32_t n, void* stream);
+int32_t lram_window_swap_slots(lram_engine* e, const int32_t* host_a, const int32_t* host_b, int32_t n, void* stream);
+int64_t lram_window_slot_numel(const lram_engine* e);
+int32_t lram_window_save_slots(lram_engine* e, const int32_t* host_slots, int32_t n, float* dev_records, void* stream);
+int32_t lram_window_load_slots(lram_engine* e, const int32_t* host_slots, int32_t n, const float* dev_records, void* stream);
 
 /* Micro-batch pipeline (xLSTM): the env slots are processed as `n` slices on engine-owned HIP streams; the
  * HBM-bound matrix-memory kernels of all slices run back to back on one stream while the other slices'

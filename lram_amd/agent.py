@@ -71,6 +71,16 @@ class _InferenceParams:
         self._agent.engine.reset()
 
 
+def _take(x, envs, n_envs: int, name: str):
+    """The entries of a full-width host control array (one per env, or None) that belong to `envs`, in that order."""
+    if x is None:
+        return None
+    x = x.reshape(-1).tolist() if torch.is_tensor(x) else list(x)
+    if len(x) != n_envs:
+        raise ValueError(f"{name}: expected {n_envs} entries (one per env), got {len(x)}")
+    return [x[e] for e in envs]
+
+
 class RecurrentAgent:
     def __init__(self, spec: ModelSpec, state_dict: Dict[str, torch.Tensor], n_envs: int = 1, device=None,
                  discrete: bool = False, state_mean: Optional[torch.Tensor] = None,
@@ -79,7 +89,8 @@ class RecurrentAgent:
                  compat_mamba_repeat: bool = False,
                  compat_stale_state: bool = False,
                  a_sample_kwargs: Optional[dict] = None, sample_seed: int = 0, sample_slot_base: int = 0,
-                 slot_table=None, use_inference_cache: Optional[bool] = None, eval_context_len: Optional[int] = None):
+                 slot_table=None, use_inference_cache: Optional[bool] = None, eval_context_len: Optional[int] = None,
+                 window_slots: str = "shared"):
         self.spec = spec
         # slot_table (lram_amd.domains.SlotTable): the batch holds envs of several domains -- head mode, action dims and
         # observation kind per env slot (the reference passes `env_act_dim` / `is_discrete` per call for its one env,
@@ -134,6 +145,14 @@ class RecurrentAgent:
         # timesteps (Engine.step_window; decision_transformer_sb3.py:621-691).  See predict_batch.  Not given here: what the
         # configuration set (agent_params.use_inference_cache -> ModelSpec.use_inference_cache; every preset says True).
         self.use_inference_cache = bool(spec.use_inference_cache if use_inference_cache is None else use_inference_cache)
+        # Window mode only.  "shared" (default): every env is stepped in every call, and set_active / fork_slots / save_slots /
+        # load_slots refuse.  "own": every slot's window has its own ring position (Engine.set_window_slots), so envs can be
+        # parked and windows forked, saved and loaded with their slots.
+        if window_slots not in ("shared", "own"):
+            raise ValueError(f'window_slots: unknown mode {window_slots!r} (choose "shared" or "own")')
+        if window_slots == "own" and self.use_inference_cache:
+            raise ValueError('window_slots="own" belongs to use_inference_cache=False (context-window inference)')
+        self.window_slots = window_slots
         self.reset_inf_cache_freq = spec.reset_inf_cache_freq
         # reference behaviour (False): the context is dropped when the cache is reset;
         # True: the last eval_context_len stored timesteps are fed back through Engine.prefill
@@ -195,6 +214,8 @@ class RecurrentAgent:
         else:
             pad, _ = self._prepare_obs(torch.zeros(1, self.spec.state_dim, device=self.device))
             self.engine.set_window_pad(pad[0])
+        if getattr(self, "window_slots", "shared") == "own":
+            self.engine.set_window_slots("own")
 
     def _apply_slot_table(self):
         if getattr(self, "slot_table", None) is not None:
@@ -393,8 +414,12 @@ class RecurrentAgent:
             self.engine.import_past_key_values(value)
 
     # ---- per-slot cache handle: fork / snapshot / restore single env slots (n_envs > 1) ----
+    def _own_windows(self) -> bool:
+        """Window mode with window_slots="own": an env's context is its window, and it moves with the slot."""
+        return not getattr(self, "use_inference_cache", True) and getattr(self, "window_slots", "shared") == "own"
+
     def _need_batch(self, what: str):
-        if not getattr(self, "use_inference_cache", True):
+        if not getattr(self, "use_inference_cache", True) and not self._own_windows():
             raise RuntimeError(f"{what}() moves the recurrent state of env slots; with use_inference_cache=False an env's context "
                                f"is its window on the device ring, which these calls do not move")
         if self.n_envs <= 1:
@@ -404,18 +429,26 @@ class RecurrentAgent:
     def fork_slots(self, src, dst):
         """Slot dst[i] continues from slot src[i]'s context (Engine.copy_slots): the recurrent state is copied, nothing else of
         the batch is touched.  With a_sample_kwargs the forked slots draw independent continuations (the sampling stream belongs
-        to the slot index); slot-table entries are not moved, so fork within one domain."""
+        to the slot index); slot-table entries are not moved, so fork within one domain.
+        use_inference_cache=False with window_slots="own": fork_slots / save_slots / load_slots address the slots' WINDOWS
+        (Engine.copy_window_slots / save_window_slots / load_window_slots) -- there the window is the context."""
         self._need_batch("fork_slots")
+        if self._own_windows():   # (the context is the window: every step restarts the recurrent state from it)
+            return self.engine.copy_window_slots(src, dst)
         self.engine.copy_slots(src, dst)
 
     def save_slots(self, slots) -> torch.Tensor:
         """float32 [n, engine.slot_state_numel] records of the listed slots (Engine.save_slots): a per-env checkpoint."""
         self._need_batch("save_slots")
+        if self._own_windows():   # float32 [n, engine.window_slot_numel]: the windows, position-free
+            return self.engine.save_window_slots(slots)
         return self.engine.save_slots(slots)
 
     def load_slots(self, slots, records: torch.Tensor):
         """Restore records (save_slots of this or another agent of the same model) into the listed slots."""
         self._need_batch("load_slots")
+        if self._own_windows():
+            return self.engine.load_window_slots(slots, records)
         self.engine.load_slots(slots, records)
 
     # ---- parked envs: step only the envs that have something to do -------------------------------------
@@ -458,12 +491,14 @@ class RecurrentAgent:
         prefix of its slots, so parking and resuming exchange the state of slot pairs (Engine.swap_slots; at most one swap per
         parked or resumed env, SlotScheduler).  Slot-table entries, per-slot sampling settings and the sampling stream stay
         with the slot index: a change that would exchange two slots whose entries differ is refused (ValueError) with nothing
-        done.  fork_slots / save_slots / load_slots keep addressing engine SLOTS (scheduler.slot_of maps an env id)."""
+        done.  fork_slots / save_slots / load_slots keep addressing engine SLOTS (scheduler.slot_of maps an env id).
+        use_inference_cache=False: refused unless window_slots="own"; then every slot exchange also exchanges the windows
+        (Engine.swap_window_slots), and a parked env saves the K-timestep prefill a window step would have cost it."""
         import copy
         want = [int(e) for e in env_ids]
         if len(set(want)) != len(want) or any(not 0 <= e < self.n_envs for e in want):
             raise ValueError(f"set_active: expected distinct env ids in 0 .. {self.n_envs - 1}")
-        if not getattr(self, "use_inference_cache", True) and len(want) != self.n_envs:
+        if not getattr(self, "use_inference_cache", True) and not self._own_windows() and len(want) != self.n_envs:
             raise ValueError("set_active: use_inference_cache=False steps every env slot (the window ring has one push "
                              "position for the batch); parked envs are refused in this mode")
         if not want:
@@ -487,6 +522,8 @@ class RecurrentAgent:
         for a, b, n_live in calls:
             if a:
                 self.engine.swap_slots(a, b)
+                if self._own_windows():   # (an env's window goes where its state goes)
+                    self.engine.swap_window_slots(a, b)
             self.engine.set_live(n_live)
         self.scheduler = sch
 
@@ -664,7 +701,8 @@ class RecurrentAgent:
         (evaluation.py:213-237): relabel = m rewrites the returns-to-go of the newest m timesteps to the returns obtained,
         keep = k prunes the window to its newest k timesteps.  Frames go through embed_images first.  A slot table -- one that
         mixes vector and image slots, or any other -- is refused in this mode (at construction), and so are parked envs
-        (set_active)."""
+        (set_active) unless the agent was created with window_slots="own": then the tensors and the host lists stay
+        full-width in env-id order, the live envs' entries are gathered into slot order, and the rows of parked envs hold 0."""
         if not getattr(self, "use_inference_cache", True):
             return self._predict_batch_window(observation, returns_to_go, reset_mask, env_act_dim, prev_rewards, relabel, keep)
         if prev_rewards is not None or relabel is not None or keep is not None:
@@ -711,8 +749,16 @@ class RecurrentAgent:
         rtg = returns_to_go.to(self.device, torch.float32).reshape(-1).contiguous()
         prev = self._zero_reward if prev_rewards is None else prev_rewards.to(self.device, torch.float32).reshape(-1).contiguous()
         reset = None if reset_mask is None else [bool(v) for v in torch.as_tensor(reset_mask).reshape(-1).tolist()]
+        idx = self._live_index() if self._own_windows() else None   # (None: every env active in its own slot -- no gather)
+        if idx is not None:   # full-width arguments in env-id order -> the live slots' rows, in slot order
+            envs = idx.tolist()
+            obs, rtg, prev = obs[idx].contiguous(), rtg[idx].contiguous(), prev[idx].contiguous()
+            reset, relabel, keep = (_take(x, envs, self.n_envs, name) for x, name in
+                                    ((reset, "reset_mask"), (relabel, "relabel"), (keep, "keep")))
         actions, _ = self.engine.step_window(obs, rtg, prev, reset=reset, relabel=relabel, keep=keep, pad="reference",
                                              discrete=self.is_discrete, obs_is_embedding=is_emb)
+        if idx is not None:   # back to env-id order; the rows of parked envs hold 0
+            actions = self._scatter_rows(actions, idx)
         if self.is_discrete:
             return actions[:, :1].to(torch.int64)
         return actions if env_act_dim is None else actions[:, :env_act_dim]

@@ -329,18 +329,31 @@ void launch_score_fill_ragged(float* actions, int32_t* tokens, float* logp, cons
 void launch_action_fill_kept(float* actions, int32_t* tokens, const int32_t* start, int B, int L, int act_dim, hipStream_t stream);
 
 // Context-window inference (window_kernels.hip; lram_step_window).  Every env slot has a ring of K entries -- ring_emb [B, K, D],
-// ring_rtg / ring_rew [B, K] -- and all envs push at the same position `head`; the entry of age a sits at (newest - a) mod K.
-// Per env, in this order: reward of the newest entry <- prev_reward[b] where patch[b]; rtg of the newest relabel[b] entries <- the
-// fp32 suffix sum of their rewards, accumulated from the newest backwards; then (rtg[b], 0) into position `head`.
+// ring_rtg / ring_rew [B, K] -- and its own position: pos[b] (device [B]) is where slot b's newest entry sits, the entry of age a
+// at (pos[b] - a) mod K.  The kernels of a step run the first R slots (the live prefix) and leave every other slot alone.
+// Per env, in this order, with pos[b] the position this call pushes at: reward of the newest existing entry <- prev_reward[b]
+// where patch[b]; rtg of the newest relabel[b] entries <- the fp32 suffix sum of their rewards, accumulated from the newest
+// backwards; then (rtg[b], 0) into position pos[b].
 void launch_window_update(float* ring_rtg, float* ring_rew, const float* prev_reward, const float* rtg, const int32_t* patch,
-                          const int32_t* relabel, int head, int B, int K, hipStream_t stream);
-// emb [B, D] into position `head` of every env's ring (float4 rows)
-void launch_window_push_rows(float* ring_emb, const float* emb, int head, int B, int K, int D, hipStream_t stream);
-// The windows oldest to newest into [B, K, D] / [B, K] / [B, K] (each nullable): env b's count[b] entries end-aligned, or with `left`
+                          const int32_t* relabel, const int32_t* pos, int R, int K, hipStream_t stream);
+// emb [R, D] into position pos[b] of every env's ring (float4 rows)
+void launch_window_push_rows(float* ring_emb, const float* emb, const int32_t* pos, int R, int K, int D, hipStream_t stream);
+// The windows oldest to newest into [R, K, D] / [R, K] / [R, K] (each nullable): env b's count[b] entries end-aligned, or with `left`
 // in rows [0, count[b]); every other row takes (pad_emb, 0, 0), or zeros where pad_emb is null.  No entry beyond count[b] is read.
 void launch_window_gather(float* out_emb, float* out_rtg, float* out_rew, const float* ring_emb, const float* ring_rtg,
-                          const float* ring_rew, const int32_t* count, const float* pad_emb, bool left, int newest, int B, int K,
-                          int D, hipStream_t stream);
+                          const float* ring_rew, const int32_t* count, const int32_t* pos, const float* pad_emb, bool left, int R,
+                          int K, int D, hipStream_t stream);
+// Whole windows between slots, one launch: the raw ring rows of slot dst[i] <- those of slot src[i] (device lists [n]); `swap`: and
+// back.  Positions and counts travel on the host.  Every destination is distinct from every other slot of the call.
+void launch_window_move(float* ring_emb, float* ring_rtg, float* ring_rew, const int32_t* src, const int32_t* dst, int n, bool swap,
+                        int K, int D, hipStream_t stream);
+// Position-free records [n, K (D + 2) + 1]: the window of slot slots[i] end-aligned, oldest to newest, zeros ahead of count[b] --
+// [K, D] embeddings | [K] rtg | [K] rewards | the count as a float.  Load writes record row t to ring position t (newest at K - 1)
+// and leaves the count to the host.
+void launch_window_save(float* records, const float* ring_emb, const float* ring_rtg, const float* ring_rew, const int32_t* count,
+                        const int32_t* pos, const int32_t* slots, int n, int K, int D, hipStream_t stream);
+void launch_window_load(float* ring_emb, float* ring_rtg, float* ring_rew, const float* records, const int32_t* slots, int n, int K,
+                        int D, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // xLSTM

@@ -304,19 +304,22 @@ struct lram_engine {
   // Both grown outside the launches, as SEQ_EMB is.
   DevBuf CTX, KEEP;
   // Context-window inference (engine_window.hip; lram_window_alloc / lram_step_window): every env slot's ring of its last win_K
-  // timesteps -- WIN_RING_EMB [B, K, D] state-token embeddings, WIN_RING_SC [2][B, K] rtg | reward -- with ONE push position for
-  // the batch (win_head: all envs push exactly one entry per call) and the per-env counts on the host.  WIN_EMB [B, K, D] and
-  // WIN_SC [2][B, K] are the laid-out windows a call hands to the stored-context body; WIN_PAD [D] the pad entry's embedding;
-  // WIN_CTL, as bytes of one allocation, int32 patch[B] | relabel[B] | count[B] (the counts persist: lram_window_peek reads
-  // them) and uint8 ones[B], the reset mask that restarts every env.  win_K == 0: no ring.
+  // timesteps -- WIN_RING_EMB [B, K, D] state-token embeddings, WIN_RING_SC [2][B, K] rtg | reward -- with a position per slot
+  // (win_pos[b]: where slot b's newest entry sits; only the slots a call runs push) and the per-env counts, both on the host and
+  // uploaded with every call that changes them.  WIN_EMB [B, K, D] and WIN_SC [2][B, K] are the laid-out windows a call hands to
+  // the stored-context body (WIN_EMB's head also takes the state Linear's rows on their way into the ring); WIN_PAD [D] the pad
+  // entry's embedding; WIN_CTL, as bytes of one allocation, int32 patch[B] | relabel[B] | count[B] | pos[B] (counts and positions
+  // persist: lram_window_peek and the window movers read them) and uint8 ones[B], the reset mask that restarts every env.
+  // win_K == 0: no ring.  win_own: LRAM_WINDOW_SLOTS_OWN -- a window step runs the live prefix (lram_window_set_slots).
   DevBuf WIN_RING_EMB, WIN_RING_SC, WIN_EMB, WIN_SC, WIN_PAD, WIN_CTL;
-  int win_K = 0, win_head = 0;
-  bool win_pad_set = false;
+  int win_K = 0;
+  bool win_pad_set = false, win_own = false;
   std::vector<int32_t> win_count;   // host [B], each in 0 .. win_K
+  std::vector<int32_t> win_pos;     // host [B], each in 0 .. win_K - 1 (K - 1 in a fresh ring: the first push lands at 0)
   void drop_window() {
     for (DevBuf* b : {&WIN_RING_EMB, &WIN_RING_SC, &WIN_EMB, &WIN_SC, &WIN_PAD, &WIN_CTL}) b->release();
-    win_K = 0, win_head = 0, win_pad_set = false;
-    win_count.clear();
+    win_K = 0, win_pad_set = false, win_own = false;
+    win_count.clear(), win_pos.clear();
   }
   // lram_score: the head's logits for a block of (env, timestep) rows of one chunk, one region per chunk lane / env slice in
   // flight.  A region holds at most score_rows rows of act_dim * n_vocab floats (default 4096 rows: 34 MiB at 8 x 274 logits;
@@ -632,6 +635,7 @@ std::vector<Slice> make_slices(lram_engine* e, hipStream_t s, hipStream_t* hbm);
 void fork_slices(lram_engine* e, const std::vector<Slice>& sl, hipStream_t hbm, hipStream_t s);
 void join_slices(lram_engine* e, const std::vector<Slice>& sl, hipStream_t hbm, hipStream_t s);
 // engine_state.hip
+void slot_lists_check(const char* what, const int32_t* src, const int32_t* dst, int n, int B, bool unique_src);
 void save_slot_records(lram_engine* e, const int32_t* host_slots, int n, float* dev_records, hipStream_t s);
 void load_slot_records(lram_engine* e, const int32_t* host_slots, int n, const float* dev_records, hipStream_t s);
 // engine_image.hip

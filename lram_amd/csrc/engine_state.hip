@@ -21,8 +21,13 @@ StateView state_view(const lram_engine* e, int block, int which) {
   }
 }
 
+}  // namespace
+
+namespace lram::host {
+
 // ---- state of individual env slots: host-side helpers of lram_state_copy_slots / save / load --------------------------
-// Host-side rules of the index lists; `what` prefixes the message.  dst == nullptr: one list (save / load).
+// Host-side rules of the index lists (the window movers of engine_window.hip take the same); `what` prefixes the message.
+// dst == nullptr: one list (save / load).
 void slot_lists_check(const char* what, const int32_t* src, const int32_t* dst, int n, int B, bool unique_src) {
   const std::string w(what);
   std::vector<uint8_t> seen(B, 0);   // bit 0: a source, bit 1: a destination
@@ -39,6 +44,10 @@ void slot_lists_check(const char* what, const int32_t* src, const int32_t* dst, 
     seen[dst[i]] |= 2;
   }
 }
+
+}  // namespace lram::host
+
+namespace {
 
 SlotStateArgs slot_args(lram_engine* e, const int32_t* host_a, const int32_t* host_b, int n, hipStream_t s) {
   // (pageable host memory: the copy has read the caller's arrays when it returns; the device side is ordered on `s`)

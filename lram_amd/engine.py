@@ -144,6 +144,13 @@ _SYMBOLS = {
     "lram_step_window": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP, ctypes.c_int32, ctypes.c_int32, _VP,
                                           _VP, _VP]),
     "lram_window_peek": (ctypes.c_int32, [_VP, _VP, _VP, _VP, _VP, _VP]),
+    "lram_window_set_slots": (ctypes.c_int32, [_VP, ctypes.c_int32]),
+    "lram_window_get_slots": (ctypes.c_int32, [_VP]),
+    "lram_window_copy_slots": (ctypes.c_int32, [_VP, _VP, _VP, ctypes.c_int32, _VP]),
+    "lram_window_swap_slots": (ctypes.c_int32, [_VP, _VP, _VP, ctypes.c_int32, _VP]),
+    "lram_window_slot_numel": (ctypes.c_int64, [_VP]),
+    "lram_window_save_slots": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP]),
+    "lram_window_load_slots": (ctypes.c_int32, [_VP, _VP, ctypes.c_int32, _VP, _VP]),
     "lram_stream_rmw": (ctypes.c_int32, [_VP, ctypes.c_size_t, _VP]),
     "lram_stream_read": (ctypes.c_int32, [_VP, ctypes.c_size_t, _VP, _VP]),
     "lram_gemm_counts": (ctypes.c_int32, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]),
@@ -418,6 +425,7 @@ def check_context_lengths(lengths, batch: int, L: int):
 
 
 WINDOW_PAD = ("reference", "none")   # LRAM_WINDOW_PAD_REFERENCE / _NONE, by value
+WINDOW_SLOTS = ("shared", "own")     # LRAM_WINDOW_SLOTS_SHARED / _OWN, by value
 
 
 def check_window_timesteps(K, batch: int, d_model: int) -> int:
@@ -610,6 +618,7 @@ class Engine:
         self._mask_words = None      # keeps the packed words of set_action_mask alive during the call (the engine copies them)
         self._n_img_live = 0         # image slots below `live`: the frames step_slots is handed
         self._window_K = 0           # (lram_state_alloc frees the window ring)
+        self._window_slots = "shared"
         B, A = self.batch, self.spec.act_dim
         # zeroed: a discrete head writes column 0 only, and the columns it leaves alone must not depend on what the allocator
         # hands out (two runs on the same inputs return the same tensors)
@@ -1080,11 +1089,12 @@ class Engine:
         return getattr(self, "_window_K", 0)
 
     def alloc_window(self, K: int):
-        """The device ring of every env slot's last K timesteps (lram_window_alloc): all counts 0, no pad entry.  K = 0 frees
-        it.  Synchronises: not a hot-path call."""
+        """The device ring of every env slot's last K timesteps (lram_window_alloc): all counts 0, no pad entry, slots mode
+        "shared".  K = 0 frees it.  Synchronises: not a hot-path call."""
         K = check_window_timesteps(K, self.batch, self.spec.d_model)
         _check(self.lib, self.lib.lram_window_alloc(self._h, K))
         self._window_K = K
+        self._window_slots = "shared"
 
     def set_window_pad(self, vec: torch.Tensor, is_embedding: bool = False):
         """The pad entry of pad="reference" (lram_window_set_pad): a normalised observation float32 [state_dim], which goes
@@ -1093,6 +1103,21 @@ class Engine:
         vec = vec.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
         _chk_dev(vec, torch.float32, (self.spec.d_model if is_embedding else self.spec.state_dim,), self.device, "vec")
         _check(self.lib, self.lib.lram_window_set_pad(self._h, _ptr(vec), int(bool(is_embedding)), _stream_ptr(self.device)))
+
+    @property
+    def window_slots(self) -> str:
+        """Which slots step_window runs (lram_window_get_slots): "shared" or "own"."""
+        return getattr(self, "_window_slots", "shared")
+
+    def set_window_slots(self, mode: str):
+        """"shared" (the default; alloc() and alloc_window() set it back): step_window runs every slot and raises while slots
+        are parked.  "own": it runs the live prefix (set_live) -- inputs, control arrays and results have `live` rows, and a
+        parked slot keeps its window, count and recurrent state bit for bit.  Cheap: host bookkeeping only
+        (lram_window_set_slots)."""
+        if mode not in WINDOW_SLOTS:
+            raise ValueError(f'window slots: unknown mode {mode!r} (choose "shared" or "own")')
+        _check(self.lib, self.lib.lram_window_set_slots(self._h, WINDOW_SLOTS.index(mode)))
+        self._window_slots = mode
 
     def step_window(self, obs: torch.Tensor, rtg: torch.Tensor, prev_reward: torch.Tensor, reset=None, relabel=None, keep=None,
                     pad: str = "reference", discrete=False, obs_is_embedding: bool = False):
@@ -1104,10 +1129,11 @@ class Engine:
         prunes the window to its newest k entries; then (obs, rtg, reward 0) is pushed.  pad="reference": shorter windows
         are left-padded with the pad entry (set_window_pad), rtg 0 and reward 0, as the reference's pad_inputs does;
         pad="none": only the real timesteps count.  Returns (actions, tokens) as step().  The recurrent state afterwards is
-        the stored-context call's: step_window and step on one engine overwrite each other's state."""
+        the stored-context call's: step_window and step on one engine overwrite each other's state.
+        With set_window_slots("own") B is `live`: the call takes and returns `live` rows and runs slots [0, live) alone."""
         if pad not in WINDOW_PAD:
             raise ValueError(f'pad: unknown mode {pad!r} (choose "reference" or "none")')
-        B, spec = self.batch, self.spec
+        B, spec = (self._live if self.window_slots == "own" else self.batch), self.spec
         _chk_dev(obs, torch.float32, (B, spec.d_model if obs_is_embedding else spec.state_dim), self.device, "obs")
         _chk_dev(rtg, torch.float32, (B,), self.device, "rtg")
         _chk_dev(prev_reward, torch.float32, (B,), self.device, "prev_reward")
@@ -1117,10 +1143,12 @@ class Engine:
             self._h, _ptr(obs), int(obs_is_embedding), _ptr(rtg), _ptr(prev_reward), host_reset,
             None if relabel is None else _i32_array(relabel), None if keep is None else _i32_array(keep),
             WINDOW_PAD.index(pad), _head_mode(discrete), _ptr(self._actions), _ptr(self._tokens), _stream_ptr(self.device)))
+        if B != self.batch:
+            return self._actions[:B], self._tokens[:B]
         return self._actions, self._tokens
 
     def window(self) -> WindowResult:
-        """The windows as the ring holds them (lram_window_peek): see WindowResult."""
+        """The windows as the ring holds them (lram_window_peek), of every slot, live or parked: see WindowResult."""
         B, K, D = self.batch, self.window_timesteps, self.spec.d_model
         if K < 1:
             raise LramError("window: no window ring is allocated (alloc_window)")
@@ -1130,6 +1158,49 @@ class Engine:
         counts = (ctypes.c_int32 * B)()
         _check(self.lib, self.lib.lram_window_peek(self._h, _ptr(emb), _ptr(rtg), _ptr(rew), counts, _stream_ptr(self.device)))
         return WindowResult(emb, rtg, rew, list(counts))
+
+    # -- windows of individual env slots: they move as the recurrent state does (copy_slots / swap_slots / save_slots / load_slots)
+    @property
+    def window_slot_numel(self) -> int:
+        """Floats in one slot's window record (lram_window_slot_numel): K * (d_model + 2) + 1."""
+        if self.window_timesteps < 1:
+            raise LramError("window: no window ring is allocated (alloc_window)")
+        return int(self.lib.lram_window_slot_numel(self._h))
+
+    def copy_window_slots(self, src, dst):
+        """Slot dst[i]'s window -- entries and count -- becomes slot src[i]'s (lram_window_copy_slots), in one launch; `src` may
+        repeat.  No other slot's window and no recurrent state is touched."""
+        src, dst = check_slot_lists(src, dst, self.batch)
+        _check(self.lib, self.lib.lram_window_copy_slots(self._h, _i32_array(src), _i32_array(dst), len(src),
+                                                         _stream_ptr(self.device)))
+
+    def swap_window_slots(self, a, b):
+        """Exchange the windows of slots a[i] and b[i], live or parked, in one launch (lram_window_swap_slots).  All indices
+        distinct and in range."""
+        a, b = check_swap_lists(a, b, self.batch)
+        _check(self.lib, self.lib.lram_window_swap_slots(self._h, _i32_array(a), _i32_array(b), len(a),
+                                                         _stream_ptr(self.device)))
+
+    def save_window_slots(self, slots, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Records of the listed slots' windows, float32 [n, window_slot_numel] on the device (lram_window_save_slots): per
+        record the window as window() lays it out -- [K, d_model] embeddings, [K] rtg, [K] rewards, end-aligned with zeros
+        ahead of the count -- then the count as one float.  Position-free: it loads into any engine of the same K and d_model."""
+        slots = _slot_list(slots, "slots")
+        n, numel = len(slots), self.window_slot_numel
+        if out is None:
+            out = torch.empty(n, numel, dtype=torch.float32, device=self.device)
+        _chk_dev(out, torch.float32, (n, numel), self.device, "out")
+        _check(self.lib, self.lib.lram_window_save_slots(self._h, _i32_array(slots), n, _ptr(out), _stream_ptr(self.device)))
+        return out
+
+    def load_window_slots(self, slots, records: torch.Tensor):
+        """Write records [n, window_slot_numel] (as save_window_slots returns) into the listed slots' windows
+        (lram_window_load_slots).  Reads the n counts back: synchronises the stream."""
+        slots, _ = check_slot_lists(slots, None, self.batch)
+        records = records.to(device=self.device, dtype=torch.float32).contiguous()
+        _chk_dev(records, torch.float32, (len(slots), self.window_slot_numel), self.device, "records")
+        _check(self.lib, self.lib.lram_window_load_slots(self._h, _i32_array(slots), len(slots), _ptr(records),
+                                                         _stream_ptr(self.device)))
 
     def _live_rows(self, buf: torch.Tensor) -> torch.Tensor:
         return buf if self._live == self.batch else buf[:self._live]

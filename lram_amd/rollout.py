@@ -310,10 +310,16 @@ class BatchedRollout:
         dev = self.obs.device
         src_t = torch.as_tensor(src, dtype=torch.long, device=dev)
         dst_t = torch.as_tensor(dst, dtype=torch.long, device=dev)
-        for name in ("obs", "rtg", "timestep", "ep_return"):
+        for name in ("obs", "rtg", "timestep", "ep_return", "prev_reward"):
             t = getattr(self, name)
             t[dst_t] = t[src_t]
         self.reset_mask[dst_t] = 0
+        # context-window mode (an agent with window_slots="own" forks windows): what the next call hands over for the env
+        for s, d in zip(src, dst):
+            self._episode_lengths[d] = list(self._episode_lengths[s])
+            for arr in (self._window_relabel, self._window_keep):
+                if arr is not None:
+                    arr[d] = arr[s]
 
     def run(self, n_steps: int, sync=None) -> Dict[str, float]:
         if sync is not None:
@@ -354,7 +360,8 @@ def evaluate_policy_batched(agent, env, n_eval_episodes: int = 10, target_return
     `_log_success_callback`, custom_eval_callback.py:36-52).
     An agent with `use_inference_cache` False is driven in context-window mode (BatchedRollout._step_window): the previous
     step's scaled reward, the reset flag or -- with persist_context -- the relabel / keep of a finished episode go with every
-    call; park_finished is refused there, before the first step (ValueError).
+    call; park_finished is refused there, before the first step (ValueError), unless the agent was created with
+    window_slots="own" (every slot's window then has its own ring position, and a parked env's window waits with it).
     park_finished=True: an env that has finished its share is parked (agent.set_active) and the agent no longer steps it --
     the reference keeps forwarding it and throws the result away.  The env object still steps all its sub-envs, with action 0
     for the parked ones; rewards, lengths and counts equal those of park_finished=False (envs are independent)."""
@@ -365,9 +372,10 @@ def evaluate_policy_batched(agent, env, n_eval_episodes: int = 10, target_return
         reward_scale = agent.get_reward_scale_for_env(None)
     # every env takes part from the first step on: an agent that comes out of an evaluation with parked envs (park_finished) starts
     # the next one with all of them active again
-    if park_finished and not getattr(agent, "use_inference_cache", True):
+    if park_finished and not getattr(agent, "use_inference_cache", True) and getattr(agent, "window_slots", "shared") != "own":
         raise ValueError("evaluate_policy_batched: park_finished needs the inference cache; with use_inference_cache=False every "
-                         "env slot is stepped (the window ring has one push position for the batch)")
+                         "env slot is stepped (the window ring has one push position for the batch) unless the agent was "
+                         'created with window_slots="own"')
     if hasattr(agent, "set_active") and len(agent.active) != n:
         agent.set_active(range(n))
     ro = BatchedRollout(agent, env, target_return, reward_scale, env_act_dim,
